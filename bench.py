@@ -12,6 +12,11 @@ llava_next_video.py:622-647), while the vision encode of the next step's clips r
 prompt (ids and length), and consecutive steps use different clips (a resident pool of 2 x cps seeded clips is cycled).
 Random-init weights of the real architecture, synthetic pixels (no network for checkpoints / datasets).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`, `config`); `--dump-outputs DIR` also writes what the last timed step computed (see dump_outputs).  Everything else
+described below -- the sharded and serial latencies, the PCIe-inclusive and decode-only rates, the per-kernel-family profile (`roofline`,
+`stages`), the N > 1 diagnostics and the CPU baseline -- runs only under `--full`.
+
 N > 1 (one process per GPU, RCCL), two plans, both reported:
   * `value` (weak scaling): N x cps clips in flight per step; every clip's 12-segment frame batch is sharded over ALL N ranks
     (rotated per clip so the 12 % N remainder balances: each rank encodes exactly 12 segments per clip round), ONE all-gather of the
@@ -323,17 +328,21 @@ class Stepper:
             i = self.window(1)[0]
         vis = self.encode(i)
         seq, S = self.llm(vis, i)
-        return self.decode(seq), S
+        out = self.decode(seq)
+        self.last_outs, self.last_vis = [out], [vis]
+        return out, S
 
     def step_multi_serial(self, idx):
         """The launches of ONE timed step (CLIP over the step's key frames, InternVideo2 + projectors per clip, one ragged prefill, one
         batched decode of the clips `idx`) back to back on the CURRENT stream: what the profiled pass brackets with events."""
-        embs = [self.eng.splice(self.prompts[i % self.pool], vis) for vis, i in zip(self.encode_multi(idx), idx)]
+        vis = self.encode_multi(idx)
+        embs = [self.eng.splice(self.prompts[i % self.pool], v) for v, i in zip(vis, idx)]
         seqs = [self.eng.seq_alloc(e.shape[0] + self.new_tokens) for e in embs]
         self.eng.prefill_batch(seqs, embs)
         outs = self.eng.decode_greedy_batch(seqs, self.new_tokens, None)
         for seq in seqs:
             self.eng.seq_free(seq)
+        self.last_outs, self.last_vis = outs, vis
         return outs
 
     def step_sharded(self, i=0):
@@ -451,6 +460,7 @@ class Stepper:
             for seq in seqs:
                 self.eng.seq_free(seq)
         self.last_idx = idx[-1]
+        self.last_outs, self.last_vis = outs, self.vis_next                # ids of the clips completed, tokens of the clips encoded in this step
         return outs[-1], S
 
     def pipe_step(self):
@@ -472,6 +482,7 @@ class Stepper:
         with self.D.on(self.sL):
             out = self.decode(seq)
         self.last_idx = i
+        self.last_outs, self.last_vis = [out], [self.vis_next]
         return out, S
 
     time_decode = False
@@ -479,6 +490,7 @@ class Stepper:
     clip_batch = False
     iv2_batch = int(os.environ.get("GVL_BENCH_IV2_BATCH", "0")) or 64      # clips per InternVideo2 call (capped by the clips of a step)
     last_idx = 0
+    last_outs, last_vis = None, None           # what the last step returned (greedy ids per clip) and the visual tokens it encoded
     batch_prefill = os.environ.get("GVL_BENCH_BATCH_PREFILL", "1") != "0"
     overlap = os.environ.get("GVL_BENCH_OVERLAP", "full")
 
@@ -529,7 +541,7 @@ def cpu_c1_measured(dev, O, Wc, Wv, Wp, Wl, new_tokens):
             "oracle_ids": out, "reference_free_ids": meta["free_ids"], "oracle_ids_equal_reference_golden": out[:n] == meta["free_ids"][:n]}
 
 
-def cpu_baseline(dev, new_tokens=12, c1=False):
+def cpu_baseline(dev, new_tokens=12, c1=False, deadline=None):
     """The CPU oracle (fp32 torch restatement of the reference, eager attention, KV-cached greedy as HF generate does) timed END TO END
     on BASELINE configs[0] -- Phi-3.5, ONE 8-frame segment: CLIP 23 L + InternVideo2 39 blocks + projectors + splice + 32-layer
     prefill (S = 384) + 12 greedy tokens -- on this box's host cores (SURVEY §8d 'CPU baseline').  The weights are
@@ -562,8 +574,9 @@ def cpu_baseline(dev, new_tokens=12, c1=False):
     t2 = time.perf_counter()
     ref_ids = meta["greedy_ids"][:new_tokens]
     c1_skip = None
-    if c1 == "auto" and (t2 - t0) * 7.3 > 720.0:          # C1 / C0 measured 7.25x on the 128-core box (350.6 s / 48.4 s, profiles/r04_cpu_c1.json)
-        c1_skip = f"skipped: the C0 pass took {t2 - t0:.0f} s on {torch.get_num_threads()} threads, which predicts ~{(t2 - t0) * 7.3:.0f} s for the 96-frame pass (limit 720 s)"
+    c1_limit = 720.0 if deadline is None else min(720.0, deadline - time.monotonic())      # deadline: when the whole --full run should have ended
+    if c1 == "auto" and (t2 - t0) * 7.3 > c1_limit:       # C1 / C0 measured 7.25x on the 128-core box (350.6 s / 48.4 s, profiles/r04_cpu_c1.json)
+        c1_skip = f"skipped: the C0 pass took {t2 - t0:.0f} s on {torch.get_num_threads()} threads, which predicts ~{(t2 - t0) * 7.3:.0f} s for the 96-frame pass (limit {c1_limit:.0f} s)"
         c1 = False
     c1_measured = cpu_c1_measured(dev, O, Wc, Wv, Wp, Wl, new_tokens) if c1 else None
     t = _cpu_layer_samples(O)
@@ -573,7 +586,7 @@ def cpu_baseline(dev, new_tokens=12, c1=False):
                       "fp32 torch oracle (oracle/gvl_oracle.py), KV-cached greedy",
             "c0_seconds": {"vision": round(t1 - t0, 3), "llm_prefill_plus_decode": round(t2 - t1, 3), "total": round(t2 - t0, 3)},
             "oracle_ids_equal_reference_golden": out == ref_ids, "oracle_ids": out, "reference_ids": ref_ids,
-            "c1_measured": c1_measured if c1_measured is not None else (c1_skip or "not run (--no-cpu-c1; the default run times one real 96-frame oracle pass, ~6 min of host time)"),
+            "c1_measured": c1_measured if c1_measured is not None else (c1_skip or "not run (--no-cpu-c1; --full otherwise times one real 96-frame oracle pass, ~6 min of host time)"),
             "c1_scaled_estimate_clips_per_s": round(1.0 / c1_s, 5),
             "c1_scaled_estimate_from": "one full-width layer of each tower at the 96-frame shapes x layer counts (attention growth of the S=3520 prefill ignored): "
                                        + json.dumps({k: round(v, 3) for k, v in t.items()})}
@@ -596,14 +609,52 @@ def rccl_ranks_seen(eng, rank, world, dev, backend):
     return n, ok
 
 
+FULL_RUN_BUDGET_S = 540.0      # --full: the measured 96-frame CPU pass runs only if the prediction ends the whole run within this
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_VIS_ROWS = 256
+
+
+def dump_outputs(st, out_dir):
+    """--dump-outputs: what the LAST timed step computed, for comparing two builds output for output (the inputs are seeded, so the same
+    arguments give the same inputs in every run).  Call after the timed region's barrier (every stream synchronised).
+      greedy_ids.npy      float64 [clips, new_tokens]: the greedy ids of every clip the step completed (-1 pads an early stop)
+      visual_tokens.npy   float32 [clips, rows, hidden]: the visual tokens of every clip the step encoded (pipelined: the clips of the next
+                          step), the same seeded sample of DUMP_VIS_ROWS token rows of each clip in every run (bf16 values, exact in float32)
+    Together at most DUMP_BUDGET_BYTES.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    outs = [list(o) for o in st.last_outs]
+    ids = np.full((len(outs), max(len(o) for o in outs)), -1.0, dtype=np.float64)
+    for c, o in enumerate(outs):
+        ids[c, :len(o)] = o
+    vis = st.last_vis
+    n_rows, hidden = vis[0].shape
+    rows = min(n_rows, DUMP_VIS_ROWS, (DUMP_BUDGET_BYTES - ids.nbytes) // (4 * hidden * len(vis)))
+    g = torch.Generator(); g.manual_seed(20240607)
+    pick = torch.randperm(n_rows, generator=g)[:rows].sort().values
+    tok = np.stack([v[pick.to(v.device)].float().cpu().numpy() for v in vis])
+    assert ids.nbytes + tok.nbytes <= DUMP_BUDGET_BYTES
+    arrays = {"greedy_ids": ids, "visual_tokens": tok}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main(argv=None, engine_factory=None):
+    t_start = time.monotonic()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--new-tokens", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--plain", action="store_true", help="timed region only (warmup + steps clips in the process): the target of the rocprofv3 passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed steps, also run every extra measurement and check (latencies, PCIe-inclusive and decode-only rates, "
+                         "per-kernel-family profile / roofline, N > 1 diagnostics, CPU baseline) and print them in the same line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--plain", action="store_true", help="timed region only (warmup + steps clips in the process), bracketed with trace markers: "
+                                                         "the target of the rocprofv3 passes")
     ap.add_argument("--clips-per-step", type=int, default=int(os.environ.get("GVL_BENCH_CPS", "8")),
                     help="pipelined mode: clips per GPU per step; their prefill is one ragged pass and their greedy decode is batched (one weight stream per token for all of them)")
     ap.add_argument("--mode", choices=["pipelined", "serial", "serial_step"], default="pipelined",
@@ -614,13 +665,15 @@ def main(argv=None, engine_factory=None):
                     help="N > 1: the all-gather of the visual tokens -- torch.distributed.all_gather_into_tensor (default), or libgvl's OWN RCCL communicator "
                          "through the C ABI (gvl_comm_init + gvl_allgather_visual: the exchange a non-Python host of the library performs).  The other one is "
                          "timed as an extra either way (`clips_per_s_other_exchange`)")
-    ap.add_argument("--cpu-c1", action="store_true", help="(default since round 5; kept for old command lines) cpu_baseline: also time ONE real 96-frame (C1) oracle pass on the host cores (~6 min)")
-    ap.add_argument("--no-cpu-c1", action="store_true", help="cpu_baseline: only the 8-frame C0 pass + the scaled C1 estimate (skips the ~6 min measured 96-frame pass)")
+    ap.add_argument("--cpu-c1", action="store_true", help="(default of --full since round 5; kept for old command lines) cpu_baseline: also time ONE real 96-frame (C1) oracle pass on the host cores (~6 min)")
+    ap.add_argument("--no-cpu-c1", action="store_true", help="--full, cpu_baseline: only the 8-frame C0 pass + the scaled C1 estimate (skips the ~6 min measured 96-frame pass)")
     ap.add_argument("--debug-set", action="append", default=[], metavar="KEY=INT",
                     help="gvl_debug_set(KEY, INT) before the run (result-neutral launch parameters, include/gvl.h): A/B measurements in one place")
     ap.add_argument("--watchdog-s", type=float, default=float(os.environ.get("GVL_BENCH_WATCHDOG_S", "900")),
                     help="seconds one stage may last before the run is declared hung (0 = off)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -676,7 +729,7 @@ def main(argv=None, engine_factory=None):
 
     # ---- N > 1: diagnostics FIRST, so that a run that later hangs has already said what every rank can do ------------------------
     per_rank, ranks_seen, gvl_gather_ok = None, None, None
-    if world > 1:
+    if world > 1 and args.full:
         mine = dict(st.stage_times(prog), rank=rank)
         prog.enter("all_gather_object(per-rank stage times)")
         gathered = [None] * world
@@ -729,11 +782,39 @@ def main(argv=None, engine_factory=None):
     prog.partial.update(value=round(clips_per_s, 4), ms_per_step=round(1e3 * dt / args.steps, 2), scaling="weak", dtype="bf16", vs_baseline=None,
                         note="the run stopped after the timed region: extras missing")
     last_idx = st.last_idx if args.mode in ("pipelined", "serial_step") else (st.cursor - 1)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        prog.enter("dump outputs of the last timed step")
+        dumped = dump_outputs(st, args.dump_outputs)
 
     if args.plain:
         if rank == 0:
             print(json.dumps({"metric": "clips/sec (plain run for profiling)", "value": round(clips_per_s, 4), "unit": "clips/s", "n_gpus": world, "steps": args.steps,
                               "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 2), "mode": args.mode, "clips_per_step": cps, "clips_in_process": (args.steps + args.warmup) * cps + (cps if args.mode == "pipelined" else 0)}), flush=True)
+        prog.finish()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    head = {"metric": "clips/sec + grounding tokens/sec, 96-frame Phi3.5-3.8B @1/2/4/8 MI355X", "value": round(clips_per_s, 4), "unit": "clips/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 2), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
+            "data": "synthetic (random-init weights at full shape; every clip of a step has its own N(0,1) pixels and its own prompt ids and length; consecutive steps use different clips)",
+            "config": {"workload": "Phi-3.5-3.8B, 96 frames (12 segs x 8), 336^2 spatial + 224^2 temporal, "
+                                   f"prompts of {PROMPT_LEN_RANGE[0]}..{PROMPT_LEN_RANGE[1]} tokens (ragged), "
+                                   f"{args.new_tokens} greedy tokens, {cps} clip{'s' if cps > 1 else ''} per GPU per step" +
+                                   ((f" ({2 * cps} clips in flight per GPU: the vision encode of the next {cps} overlaps the ragged prefill + " +
+                                     ("batched greedy decode" if cps > 1 else "decode") + f" of the current {cps}" +
+                                     (f"; CLIP tower batched over the {SEGS * cps} key frames of a step" if clip_batch else "") + ")") if args.mode == "pipelined" else ""),
+                       "clips_per_step": cps, "ms_per_clip": round(1e3 * dt / (args.steps * cps), 2), "prefill_len_max": S, "visual_tokens": 12 * st.L,
+                       "distinct_clips_resident": st.pool,
+                       "parallelism": "1 GPU" if world == 1 else f"frame-batch sharded over {world} GPUs + all-gather of visual tokens, LLM replica per clip"},
+            "mode": args.mode}
+    if dumped is not None:
+        head["dumped_outputs"] = dumped
+    if not args.full:
+        # a plain run: the headline line only (every extra below runs under --full)
+        if rank == 0:
+            print(json.dumps(head), flush=True)
         prog.finish()
         if world > 1:
             torch.distributed.destroy_process_group()
@@ -979,26 +1060,14 @@ def main(argv=None, engine_factory=None):
             ranks_seen, gvl_gather_ok = res["v"]
 
     if rank == 0:
-        out = {"metric": "clips/sec + grounding tokens/sec, 96-frame Phi3.5-3.8B @1/2/4/8 MI355X", "value": round(clips_per_s, 4), "unit": "clips/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 2), "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
-               "data": "synthetic (random-init weights at full shape; every clip of a step has its own N(0,1) pixels and its own prompt ids and length; consecutive steps use different clips)",
-               "config": {"workload": "Phi-3.5-3.8B, 96 frames (12 segs x 8), 336^2 spatial + 224^2 temporal, "
-                                      f"prompts of {PROMPT_LEN_RANGE[0]}..{PROMPT_LEN_RANGE[1]} tokens (ragged), "
-                                      f"{args.new_tokens} greedy tokens, {cps} clip{'s' if cps > 1 else ''} per GPU per step" +
-                                      ((f" ({2 * cps} clips in flight per GPU: the vision encode of the next {cps} overlaps the ragged prefill + " +
-                                        ("batched greedy decode" if cps > 1 else "decode") + f" of the current {cps}" +
-                                        (f"; CLIP tower batched over the {SEGS * cps} key frames of a step" if clip_batch else "") + ")") if args.mode == "pipelined" else ""),
-                          "clips_per_step": cps, "ms_per_clip": round(1e3 * dt / (args.steps * cps), 2), "prefill_len_max": S, "visual_tokens": 12 * st.L,
-                          "distinct_clips_resident": st.pool,
-                          "parallelism": "1 GPU" if world == 1 else f"frame-batch sharded over {world} GPUs + all-gather of visual tokens, LLM replica per clip"},
+        out = {**head,
                "decode_tokens_per_s": None if decode_tok_s is None else round(world * decode_tok_s, 1),
                "decode_tokens_per_s_batched": None if decode_tok_s_batched is None else round(world * decode_tok_s_batched, 1),
                "decode_tokens_per_s_16seq": None if decode_tok_s_16 is None else round(world * decode_tok_s_16, 1),
                "clips_per_s_incl_pixel_h2d": None if clips_per_s_h2d is None else round(clips_per_s_h2d, 4), "single_clip_latency_ms": round(latency_ms, 2),
                "single_clip_latency_ms_sharded": round(sharded_ms, 2),
                "single_clip_sharded_plan": f"one clip's 12 segments over {world} rank{'s' if world > 1 else ''}, one all-gather, prefill + decode on rank 0 (strong scaling; `value` is the weak-scaling plan)",
-               "mode": args.mode, "ids_match_serial": same_ids,
+               "ids_match_serial": same_ids,
                "roofline": roofline, "stages": stages, "kv_pool": eng.kv_info()}
         if world > 1:
             out["exchange"] = st.exchange + (" (torch.distributed.all_gather_into_tensor)" if st.exchange == "torch" else " (gvl_allgather_visual through the C ABI, libgvl's own communicator)")
@@ -1011,9 +1080,9 @@ def main(argv=None, engine_factory=None):
             prog.enter("cpu_baseline (host cores)")
             prog.limit = max(prog.limit, 1800.0) if prog.limit > 0 else 0
             eng.close()                                  # give the HBM back: the C0 weights are generated on the GPU, then copied to the host
-            # the measured 96-frame pass runs by default (the driver's own line carries the whole CPU baseline); it is skipped when the
-            # C0 pass just timed predicts more than ~12 min for it (a host with few cores), so that the default run still ends within minutes
-            out["cpu_baseline"] = cpu_baseline(dev, args.new_tokens, c1="auto" if not args.no_cpu_c1 else False)
+            # the measured 96-frame pass runs by default under --full (the line carries the whole CPU baseline); it is skipped when the
+            # C0 pass just timed predicts that it would not end within FULL_RUN_BUDGET_S of the start (a host with few cores), so that --full ends within minutes
+            out["cpu_baseline"] = cpu_baseline(dev, args.new_tokens, c1="auto" if not args.no_cpu_c1 else False, deadline=t_start + FULL_RUN_BUDGET_S)
         print(json.dumps(out), flush=True)
     prog.finish()
     if diag_stuck:

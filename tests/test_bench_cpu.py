@@ -36,7 +36,7 @@ def _run(world, extra_args=(), extra_env=None, timeout=300):
 def test_bench_main_end_to_end_on_cpu(world, mode_args):
     if __import__("torch").cuda.is_available():
         pytest.skip("plumbing test is for the GPU-less container")
-    outs = _run(world, ("--steps", "3", "--warmup", "1", "--new-tokens", "6", *mode_args))
+    outs = _run(world, ("--full", "--steps", "3", "--warmup", "1", "--new-tokens", "6", *mode_args))
     for rc, o, e in outs:
         assert rc == 0, e[-2000:]
     lines = [l for l in outs[0][1].splitlines() if l.startswith("{")]
@@ -59,7 +59,7 @@ def test_bench_main_end_to_end_on_cpu(world, mode_args):
 def test_bench_watchdog_names_the_hung_stage():
     if __import__("torch").cuda.is_available():
         pytest.skip("plumbing test is for the GPU-less container")
-    outs = _run(2, ("--steps", "2", "--warmup", "1", "--new-tokens", "4", "--watchdog-s", "6"), {"GVL_STUB_HANG_RANK": "1", "GVL_STUB_HANG_AFTER": "3"}, timeout=120)
+    outs = _run(2, ("--full", "--steps", "2", "--warmup", "1", "--new-tokens", "4", "--watchdog-s", "6"), {"GVL_STUB_HANG_RANK": "1", "GVL_STUB_HANG_AFTER": "3"}, timeout=120)
     rc0, o0, e0 = outs[0]
     assert rc0 == 3, (rc0, e0[-1500:])
     lines = [l for l in o0.splitlines() if l.startswith("{")]
@@ -82,7 +82,7 @@ def test_bench_under_the_drivers_own_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GVL_BENCH_SAME_DEVICE")}
     env.update(GVL_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "tests", "bench_stub.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--master-port", str(port), os.path.join(ROOT, "tests", "bench_stub.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
                         "--new-tokens", "4"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -97,7 +97,7 @@ def test_a_hung_libgvl_communicator_check_does_not_cost_the_line():
     hangs, rank 0 still prints the complete line (value, roofline, per-rank stages; n_ranks_seen_by_rccl = "timed out") and every rank exits 0."""
     if __import__("torch").cuda.is_available():
         pytest.skip("plumbing test is for the GPU-less container")
-    outs = _run(2, ("--steps", "2", "--warmup", "1", "--new-tokens", "4"), {"GVL_STUB_COMM_HANG": "1", "GVL_BENCH_DIAG_S": "3"}, timeout=180)
+    outs = _run(2, ("--full", "--steps", "2", "--warmup", "1", "--new-tokens", "4"), {"GVL_STUB_COMM_HANG": "1", "GVL_BENCH_DIAG_S": "3"}, timeout=180)
     for rc, o, e in outs:
         assert rc == 0, e[-1500:]
     lines = [l for l in outs[0][1].splitlines() if l.startswith("{")]
@@ -114,7 +114,7 @@ def test_bench_exchange_through_the_engines_own_communicator_and_rank0_llm_mode(
     the clip's own rank produces in the weak-scaling plan."""
     if __import__("torch").cuda.is_available():
         pytest.skip("plumbing test is for the GPU-less container")
-    outs = _run(2, ("--steps", "3", "--warmup", "1", "--new-tokens", "6", "--exchange", exchange), {"GVL_STUB_COMM": "1"})
+    outs = _run(2, ("--full", "--steps", "3", "--warmup", "1", "--new-tokens", "6", "--exchange", exchange), {"GVL_STUB_COMM": "1"})
     for rc, o, e in outs:
         assert rc == 0, e[-2000:]
     lines = [l for l in outs[0][1].splitlines() if l.startswith("{")]
@@ -136,7 +136,7 @@ def test_bench_main_at_world_8_through_the_rotated_plan_and_the_rank0_llm_mode(s
     records a first hardware failure would be diagnosed from."""
     if __import__("torch").cuda.is_available():
         pytest.skip("plumbing test is for the GPU-less container")
-    outs = _run(8, ("--steps", "2", "--warmup", "1", "--new-tokens", "4", "--exchange", "gvl"), {"GVL_STUB_COMM": "1", "GVL_BENCH_SEGS": str(segs)}, timeout=600)
+    outs = _run(8, ("--full", "--steps", "2", "--warmup", "1", "--new-tokens", "4", "--exchange", "gvl"), {"GVL_STUB_COMM": "1", "GVL_BENCH_SEGS": str(segs)}, timeout=600)
     for rc, o, e in outs:
         assert rc == 0, e[-2000:]
     lines = [l for l in outs[0][1].splitlines() if l.startswith("{")]
@@ -148,3 +148,47 @@ def test_bench_main_at_world_8_through_the_rotated_plan_and_the_rank0_llm_mode(s
     assert r0["clips_per_s"] > 0 and r0["clips_per_round"] == 8 and r0["ids_match_the_per_rank_llm"] is True, r0
     assert d["n_ranks_seen_by_rccl"] == 8 and d["gvl_allgather_matches_rank_order"] is True
     assert d["single_clip_latency_ms_sharded"] > 0
+
+
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "mode"}
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_plain_bench_prints_the_headline_line_only(world):
+    """Without --full a run sets up, warms up, times --steps steps and prints the headline line: no latencies, profile, diagnostics or CPU baseline."""
+    if __import__("torch").cuda.is_available():
+        pytest.skip("plumbing test is for the GPU-less container")
+    outs = _run(world, ("--steps", "3", "--warmup", "1", "--new-tokens", "6"))
+    for rc, o, e in outs:
+        assert rc == 0, e[-2000:]
+    lines = [l for l in outs[0][1].splitlines() if l.startswith("{")]
+    assert len(lines) == 1, outs[0][1]
+    d = json.loads(lines[0])
+    assert set(d) == HEADLINE, sorted(set(d) ^ HEADLINE)
+    assert d["n_gpus"] == world and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "clips/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    cps = d["config"]["clips_per_step"]
+    assert abs(d["value"] - world * 3 * cps / (d["ms_per_step"] * 3e-3)) / d["value"] < max(1e-2, 0.011 / d["ms_per_step"])
+
+
+def test_dump_outputs_writes_the_last_timed_step_reproducibly(tmp_path):
+    """--dump-outputs DIR: the greedy ids of the clips the last timed step completed and a fixed sample of the visual tokens it encoded, as float
+    arrays within 64 MB; the same arguments give the same arrays, and another --steps ends on other clips (the pool of 2 x 8 clips alternates)."""
+    if __import__("torch").cuda.is_available():
+        pytest.skip("plumbing test is for the GPU-less container")
+    import numpy as np
+    got = {}
+    for tag, steps in (("a", "3"), ("b", "3"), ("c", "2")):
+        outs = _run(1, ("--steps", steps, "--warmup", "1", "--new-tokens", "6", "--dump-outputs", str(tmp_path / tag)))
+        assert outs[0][0] == 0, outs[0][2][-2000:]
+        d = json.loads([l for l in outs[0][1].splitlines() if l.startswith("{")][0])
+        assert d["steps"] == int(steps) and d["dumped_outputs"]["greedy_ids"] == [8, 6]
+        files = sorted(p.name for p in (tmp_path / tag).iterdir())
+        assert files == ["greedy_ids.npy", "visual_tokens.npy"]
+        got[tag] = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        assert sum(a.nbytes for a in got[tag].values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in got[tag].values())
+        assert got[tag]["visual_tokens"].shape == (8, 60, 16) and list(got[tag]["visual_tokens"].shape) == d["dumped_outputs"]["visual_tokens"]
+        assert len({tuple(r) for r in got[tag]["greedy_ids"]}) == 8                 # eight distinct clips
+    for k in got["a"]:
+        assert np.array_equal(got["a"][k], got["b"][k]), k
+    assert not np.array_equal(got["a"]["greedy_ids"], got["c"]["greedy_ids"])

@@ -6,7 +6,7 @@ cd /tmp; export TMPDIR=/tmp
 WHAT=${2:-all}
 db() { find "$1" -name "*.db" | head -1; }
 if [[ $WHAT == all || $WHAT == trace ]]; then
-  rocprofv3 --kernel-trace -d $OUT/default -- python $R/bench.py --no-cpu-baseline > $OUT/default.log 2>&1
+  rocprofv3 --kernel-trace -d $OUT/default -- python $R/bench.py --full --no-cpu-baseline > $OUT/default.log 2>&1
   python $R/tools/rocpd_stats.py "$(db $OUT/default)" $OUT/${TAG}_bench_kernel_stats.txt > /dev/null
   rocprofv3 --kernel-trace -d $OUT/serial -- python $R/bench.py --plain --mode serial --steps 6 --warmup 1 > $OUT/serial.log 2>&1
   python $R/tools/rocpd_stats.py "$(db $OUT/serial)" $OUT/${TAG}_bench_kernel_stats_serial.txt > /dev/null
