@@ -78,11 +78,15 @@ def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[
 
 
 def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logits: torch.Tensor, num_beams: int, max_new_tokens: int,
-                eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None) -> List[int]:
+                eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None,
+                process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None) -> List[int]:
     """first_logits [vocab]: logits after the prompt.  step(parents, tokens) -> logits [k, vocab] of the k new running beams, where new beam j
     continues old beam parents[j] with tokens[j] (the caller reorders its KV cache accordingly; at the first call every parent is 0 = the
     prompt).  Returns the NEW ids of the best hypothesis (eos included when it ended by eos), as HF does for inputs_embeds prompts.
-    sample: None = beam search; dict(temperature, top_k, top_p, generator) = beam-sample (module docstring)."""
+    sample: None = beam search; dict(temperature, top_k, top_p, generator) = beam-sample (module docstring).
+    process(histories, logprobs) -> logprobs: HF's logits processors (repetition penalty, no-repeat n-gram, min length; grounded_video_llm_amd/logits.py)
+    on the [k, vocab] log-softmax rows of the running beams, histories[j] = the ids beam j generated so far; applied before the warpers and before
+    the beam scores are added, as HF's _beam_search / _beam_sample do."""
     k = int(num_beams)
     if k < 2:
         raise ValueError("beam_search needs num_beams >= 2")
@@ -100,6 +104,8 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     done = False
     while True:
         lp = torch.log_softmax(logits.float(), dim=-1)
+        if process is not None:
+            lp = process([list(q) for q in seqs], lp)
         if sample is None:
             lp = lp + scores[:, None]
             top = torch.topk(lp.reshape(-1), 2 * k, largest=True, sorted=True)

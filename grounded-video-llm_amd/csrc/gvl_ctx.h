@@ -32,6 +32,12 @@ struct LlmLayerW { const bf16_t *ln1, *ln2, *qkvw, *ow, *guw, *downw;
                    const bf16_t *qkvd, *od, *gud, *downd;      // decode copies in MFMA tile order (gvl_decode.hip; bf16, or FP8 e4m3 when cfg.decode_fp8); null on the VALU fallback
                    const float *qkvs, *os, *gus, *downs; };    // FP8 variant: per-row power-of-two scales
 
+// HF logits processors of one sequence (gvl_logits.hip); the defaults switch every one of them off
+struct LogitsProc {
+  float penalty = 1.0f; int ngram = 0, min_new = 0, eos = -1;
+  bool on() const { return penalty != 1.0f || ngram > 0 || (min_new > 0 && eos >= 0); }
+};
+
 struct Seq {
   bool used = false; int max_tokens = 0, n_pages = 0; std::vector<int> pages;
   int* d_block_table = nullptr; int* d_pos = nullptr; int pos = 0; int n_gen = 0;
@@ -42,6 +48,7 @@ struct Seq {
   int* d_ngen = nullptr;  // device copy of n_gen: where the next generated id goes (a decode step carries no host counters)
   unsigned rng_stream = 0;  // sampling: which random stream this sequence draws from (assigned at its prefill)
   int* d_eos = nullptr; volatile int* h_eos = nullptr;   // host-mapped word: generation count at which this sequence produced eos (0 = not yet)
+  LogitsProc proc;          // HF logits processors of this sequence's token selection (gvl_seq_set_processors; default: gvl_ctx::proc_default)
 };
 
 struct ProfRec { int cat; hipEvent_t e0, e1; double work; };
@@ -102,6 +109,8 @@ struct gvl_ctx {
   hipEvent_t step_ev[3] = {nullptr, nullptr, nullptr};
   // token selection (gvl_set_sampling): greedy argmax unless `on`
   struct { bool on = false; float inv_temp = 1.f, top_p = 0.f; int top_k = 0; unsigned long long seed = 0; unsigned next_stream = 0; } sample;
+  // logits processors copied into every sequence allocated later (gvl_set_logits_processors); off by default
+  LogitsProc proc_default;
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
   // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of ~165 kernel launches
   struct { int decode_attn_cpb = 0, decode_attn_hpb = 0; bool decode_graph = true; int vision_in_place = 1, prefill_group = 4, attn_ring = 0, attn_pipe = 1, attn_pipe_rows = 128, patch_fused = 1, varlen_attn = 1, norm_fused = 1, last_layer_tail = 1; } dbg;

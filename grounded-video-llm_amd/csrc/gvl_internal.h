@@ -351,6 +351,13 @@ struct ArgmaxArgs { const float* logits; int n, batch; int* tok_ptrs[GVL_MAX_DEC
                     const int* step_override; };   // operator tests: generation step of row b when the row has no ngen counter
 int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st);
 int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
+// HF logits processors (repetition penalty -> no-repeat n-gram -> min length) on `batch` fp32 rows (stride ld), in place (gvl_logits.hip).  Row b's
+// history is hist[b][0 .. *len_ptrs[b]) (clamped to cap <= GVL_LOGITS_HIST_CAP; a null len_ptrs[b] = empty history); penalty 1 / ngram 0 /
+// min_new 0 switch a processor off; eos < 0 switches the min-length ban off.
+constexpr int GVL_LOGITS_HIST_CAP = 8192;   // = the sequences' output-list capacity (gvl_ctx::outlist_cap)
+struct LogitsProcArgs { float* logits; int n, ld, batch, cap; const int* hist[GVL_MAX_DECODE_BATCH]; const int* len_ptrs[GVL_MAX_DECODE_BATCH];
+                        float penalty[GVL_MAX_DECODE_BATCH]; int ngram[GVL_MAX_DECODE_BATCH], min_new[GVL_MAX_DECODE_BATCH], eos[GVL_MAX_DECODE_BATCH]; };
+int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st);
 // x[b][:] = table[*tok_ptrs[b]][:]  and  (*pos_ptrs[b])++ helpers of the batched decode loop
 struct TokPtrs { const int* p[GVL_MAX_DECODE_BATCH]; int n; };
 int gvl_launch_gather_tok_rows(const bf16_t* table, const TokPtrs& toks, bf16_t* dst, int cols, hipStream_t st);

@@ -36,8 +36,25 @@ int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st) {
   return 0;
 }
 
-// The next token of every row of `am`: argmax (greedy), or one draw per row when gvl_set_sampling switched sampling on
+// The next token of every row of `am`: argmax (greedy), or one draw per row when gvl_set_sampling switched sampling on.  When a sequence of the
+// group has logits processors (gvl_seq_set_processors), one launch applies them to the rows first; its history is the sequence's output list
+// (host-mapped) up to its device-side generation count, so a captured decode step replays with nothing baked in per step.  With every processor
+// off the launch sequence is the one without processors.
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
+  bool any_proc = false;
+  for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->proc.on();
+  if (any_proc) {
+    LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
+    lp.logits = const_cast<float*>(am.logits); lp.n = am.n; lp.ld = am.n; lp.batch = am.batch;
+    lp.cap = ctx->outlist_cap < GVL_LOGITS_HIST_CAP ? ctx->outlist_cap : GVL_LOGITS_HIST_CAP;
+    for (int b = 0; b < am.batch; ++b) {
+      const LogitsProc& q = sqs[b]->proc;
+      lp.hist[b] = sqs[b]->d_out; lp.len_ptrs[b] = sqs[b]->d_ngen;
+      lp.penalty[b] = q.penalty; lp.ngram[b] = q.ngram; lp.min_new[b] = q.eos >= 0 ? q.min_new : 0; lp.eos[b] = q.eos;
+    }
+    const int rc = gvl_launch_logits_process(lp, st);
+    if (rc) return rc;
+  }
   if (!ctx->sample.on) return gvl_launch_argmax(am, st);
   am.inv_temp = ctx->sample.inv_temp; am.top_p = ctx->sample.top_p; am.top_k = ctx->sample.top_k;
   am.seed_lo = (unsigned)ctx->sample.seed; am.seed_hi = (unsigned)(ctx->sample.seed >> 32);

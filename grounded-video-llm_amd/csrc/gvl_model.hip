@@ -480,6 +480,7 @@ int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
   }
   Seq& s = ctx->seqs[id];
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = 0; s.n_gen = 0; s.pages.clear();
+  s.proc = ctx->proc_default;                        // logits processors: the default of gvl_set_logits_processors
   for (int i = 0; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
   // preallocated slot: no hipMalloc / hipFree / device-wide sync per clip.  Work that uses the slot is stream ordered;
   // a freed slot or page may be handed out again only for work enqueued later on the same stream (one stream per ctx
@@ -515,7 +516,9 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
     ctx->seqs.emplace_back(); id = (int)ctx->seqs.size() - 1;
   }
   const std::vector<int> src_pages(ctx->seqs[src_seq].pages.begin(), ctx->seqs[src_seq].pages.begin() + shared);   // (emplace_back may have moved the source)
+  const LogitsProc src_proc = ctx->seqs[src_seq].proc;
   Seq& s = ctx->seqs[id];
+  s.proc = src_proc;
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = n_tokens; s.n_gen = 0; s.pages = src_pages;
   for (int p : s.pages) ++ctx->page_ref[p];          // whole pages of the prefix: immutable from now on for both holders (appends go to later pages)
   for (int i = shared; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
@@ -559,7 +562,9 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
   }
   const std::vector<int> src_pages = ctx->seqs[src_seq].pages;
   const int src_ngen = ctx->seqs[src_seq].n_gen;
+  const LogitsProc src_proc = ctx->seqs[src_seq].proc;
   Seq& s = ctx->seqs[id];
+  s.proc = src_proc;
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = pos; s.n_gen = src_ngen;
   s.pages.assign(src_pages.begin(), src_pages.begin() + shared);
   for (int p : s.pages) ++ctx->page_ref[p];
@@ -815,6 +820,42 @@ int gvl_op_sample(gvl_ctx* ctx, const float* logits, int n, int batch, float tem
   am.step_override = steps_dev;
   for (int b = 0; b < batch; ++b) { am.tok_ptrs[b] = tokens_dev + b; am.stream[b] = streams[b]; }
   RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
+  return 0;
+}
+
+// ---- HF logits processors (gvl_logits.hip): repetition penalty -> no-repeat n-gram -> min length, on the generated ids of each sequence
+static int check_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, const char* what) {
+  if (!(penalty > 0.f) || ngram < 0 || min_new < 0) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": penalty must be > 0, ngram >= 0, min_new >= 0");
+  return 0;
+}
+int gvl_set_logits_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, int eos_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = check_processors(ctx, penalty, ngram, min_new, "gvl_set_logits_processors")) return rc;
+  ctx->proc_default.penalty = penalty; ctx->proc_default.ngram = ngram; ctx->proc_default.min_new = min_new; ctx->proc_default.eos = eos_id < 0 ? -1 : eos_id;
+  return 0;
+}
+int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, int min_new, int eos_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_processors: bad seq");
+  if (const int rc = check_processors(ctx, penalty, ngram, min_new, "gvl_seq_set_processors")) return rc;
+  LogitsProc& q = ctx->seqs[seq_id].proc;
+  q.penalty = penalty; q.ngram = ngram; q.min_new = min_new; q.eos = eos_id < 0 ? -1 : eos_id;
+  return 0;
+}
+int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                          const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, void* stream) {
+  if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
+      hist_stride < 0 || (hist_stride > 0 && !hist_dev))
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
+  lp.logits = logits; lp.n = n; lp.ld = n; lp.batch = batch; lp.cap = hist_stride < GVL_LOGITS_HIST_CAP ? hist_stride : GVL_LOGITS_HIST_CAP;
+  for (int b = 0; b < batch; ++b) {
+    if (const int rc = check_processors(ctx, penalty[b], ngram[b], min_new[b], "gvl_op_logits_process")) return rc;
+    lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
+    lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
+  }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
   return 0;
 }
 

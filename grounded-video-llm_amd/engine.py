@@ -396,11 +396,14 @@ class Engine:
         self._chk(self.lib.gvl_decode_step_logits_batch(self.ctx, ids, n, tk, _ptr(logits), self.stream), "gvl_decode_step_logits_batch")
         return logits
 
-    def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int]) -> List[int]:
-        """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included)."""
+    def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None) -> List[int]:
+        """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  processors: a logits.Processors for this
+        sequence (None: the default of set_logits_processors)."""
         S = embeds.shape[0]
         seq = self.seq_alloc(min(S + max_new_tokens, self.geo.max_seq))
         try:
+            if processors is not None:
+                self.seq_set_processors(seq, *processors.args())
             self.prefill(seq, embeds)
             return self.decode_greedy(seq, max_new_tokens, eos_id)
         finally:
@@ -496,6 +499,40 @@ class Engine:
         self._chk(self.lib.gvl_op_sample(self.ctx, _ptr(logits.contiguous()), n, B, float(temperature), int(top_k or 0), float(top_p or 0.0),
                                          int(seed) & (2 ** 64 - 1), st, _ptr(steps_d), _ptr(out), self.stream), "gvl_op_sample")
         return out
+
+    def set_logits_processors(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, eos_id: Optional[int] = None):
+        """gvl_set_logits_processors: HF's repetition penalty / no-repeat n-gram / min-length processors for every sequence allocated AFTER this call
+        (the history is each sequence's generated ids only).  1.0 / 0 / 0 = off; min_new_tokens needs an eos id."""
+        self._chk(self.lib.gvl_set_logits_processors(self.ctx, float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
+                                                     -1 if eos_id is None else int(eos_id)), "gvl_set_logits_processors")
+
+    def seq_set_processors(self, seq: int, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                           eos_id: Optional[int] = None):
+        """gvl_seq_set_processors: the processors of one live sequence (overrides the default it was allocated with)."""
+        self._chk(self.lib.gvl_seq_set_processors(self.ctx, int(seq), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
+                                                  -1 if eos_id is None else int(eos_id)), "gvl_seq_set_processors")
+
+    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos):
+        """gvl_op_logits_process on fp32 rows [B, n] (any B; 16 rows per launch): row b gets the processors (penalty[b], ngram[b], min_new[b],
+        eos[b]) over the history histories[b].  `logits` must be a contiguous fp32 device tensor: it is changed IN PLACE and returned."""
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2 and logits.device == self.device
+        B, n = logits.shape
+        assert len(histories) == B
+        width = max([len(h) for h in histories] + [1])
+        hist = torch.zeros((B, width), dtype=torch.int32)
+        for b, h in enumerate(histories):
+            if len(h):
+                hist[b, :len(h)] = torch.as_tensor(list(h), dtype=torch.int32)
+        hist = hist.to(self.device)
+        lens = torch.tensor([len(h) for h in histories], dtype=torch.int32, device=self.device)
+        per_row = lambda v, t: [t(x) for x in (v if isinstance(v, (list, tuple)) else [v] * B)]
+        pe, ng, mn, eo = per_row(penalty, float), per_row(ngram, int), per_row(min_new, int), per_row(eos, lambda x: -1 if x is None else int(x))
+        for b0 in range(0, B, 16):
+            nb = min(16, B - b0)
+            self._chk(self.lib.gvl_op_logits_process(self.ctx, C.c_void_p(logits.data_ptr() + b0 * n * 4), n, nb, C.c_void_p(hist.data_ptr() + b0 * width * 4),
+                                                     width, C.c_void_p(lens.data_ptr() + b0 * 4), (C.c_float * nb)(*pe[b0:b0 + nb]), (C.c_int * nb)(*ng[b0:b0 + nb]),
+                                                     (C.c_int * nb)(*mn[b0:b0 + nb]), (C.c_int * nb)(*eo[b0:b0 + nb]), self.stream), "gvl_op_logits_process")
+        return logits
 
     def op_dgemm(self, W, x, bias=None):
         """x bf16 [B, K] (B <= 16) -> y f32 [B, N]: the skinny MFMA decode GEMM."""

@@ -19,6 +19,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import dist as gdist
+from . import logits as LP
 from . import prompts as P
 from . import weights as Wt
 from .engine import Engine, TowerGeometry
@@ -239,6 +240,16 @@ class LLAVA_NEXT_VIDEO:
         return vis.view(bs, S * L, self.geo.hidden)
 
     # generate -----------------------------------------------------------------------------------------------
+    def _select_processors(self, kw, embed_len: int) -> "LP.Processors":
+        """HF generate's logits processors for the kwargs the reference forwards (repetition_penalty, no_repeat_ngram_size, min_new_tokens /
+        min_length; logits.py), resolved for inputs_embeds of `embed_len` rows.  Sets the engine's default on EVERY generate call -- off when
+        absent, and off for beam search, which applies them to its log-softmax rows itself -- so nothing carries over from one call to the next
+        (the same rule as _select_tokens for sampling).  Returns the resolved processors."""
+        procs = LP.resolve(kw, getattr(self.tokenizer, "eos_token_id", None), embed_len)
+        beams = kw.get("num_beams", 1) not in (1, None)
+        self.engine.set_logits_processors(*(LP.OFF if beams else procs).args())
+        return procs
+
     def _select_tokens(self, kw):
         """HF generate's token selection for the kwargs the reference forwards (inference.py:170-176 -> llava_next_video.py:655-661):
         greedy, or temperature -> top-k (HF default 50) -> top-p sampling on the device; `seed` (extra) makes a run reproducible,
@@ -260,10 +271,14 @@ class LLAVA_NEXT_VIDEO:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.engine.set_sampling(True, t, 0 if top_k is None else int(top_k), top_p, seed)
 
+    def _n_visual(self, samples) -> int:
+        return int(samples["spatial_pixel_values"].shape[1]) * self.engine.tokens_per_seg
+
     @torch.inference_mode()
     def generate(self, samples, **generate_kwargs) -> List[str]:
-        self._select_tokens(generate_kwargs)
-        max_new = int(generate_kwargs.get("max_new_tokens", 2048))
+        """The reference's generate(samples, **generate_kwargs).  Besides greedy / sampling / beam search it honours HF's repetition_penalty,
+        no_repeat_ngram_size and min_new_tokens / min_length (logits.py; applied on the device to the generated ids only, as HF does for an
+        inputs_embeds prompt).  Other HF logits processors (bad_words_ids, sequence_bias, suppress_tokens, ...) are not supported and ignored."""
         if any(v == "text" for v in samples.get("video_ids", [])):
             # prepare_multimodal_inputs' `video_ids == 'text'` branch (llava_next_video.py:583-586) is a TRAINING device (dummy visual
             # rows appended with mask 0 so FSDP sees every parameter); the reference's inference never produces it.  forward() handles it.
@@ -271,6 +286,9 @@ class LLAVA_NEXT_VIDEO:
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
+        procs = self._select_processors(generate_kwargs, LP.padded_embed_len(ids_arr.shape[1], self._n_visual(samples)))
+        self._select_tokens(generate_kwargs)
+        max_new = int(generate_kwargs.get("max_new_tokens", 2048))
         feats = self.encode_images(samples)
         k = generate_kwargs.get("num_beams", 1) or 1
         if k > 1:                                         # HF beam search (do_sample=False), one sample at a time
@@ -288,20 +306,23 @@ class LLAVA_NEXT_VIDEO:
                 gen.manual_seed(int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
                 sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen)
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
-                                              float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample)
+                                              float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
+                                              processors=procs)
                        for b in range(ids_arr.shape[0])]
         else:
-            out_ids = self.generate_ids(ids_arr, mask, feats, max_new)
+            out_ids = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs)
         texts = self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)
         return [t.strip() for t in texts]
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
-                          sample: Optional[dict] = None) -> List[int]:
+                          sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None) -> List[int]:
         """generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
         teacher-forced batched decode step per token (gvl_decode_step_logits_batch: one stream of the weights for the k beams); log-softmax / top-2k of the step run on the device (torch), the bookkeeping on
-        the host."""
+        the host.  processors: HF's logits processors, applied by gvl_op_logits_process to every step's log-softmax rows before the beam scores
+        are added (HF _beam_search / _beam_sample); the beams' own sequences select their tokens without them (their raw logits are what the
+        steps return)."""
         from . import beam as B
         eng = self.engine
         gi = eng.decode_group_info()                     # which group sizes ONE batched step takes: asked from the library, not restated here
@@ -310,7 +331,14 @@ class LLAVA_NEXT_VIDEO:
         cap = min(emb.shape[0] + max_new + 1, self.geo.max_seq)
         beams: List[Optional[int]] = [eng.seq_alloc(cap)]
         fresh: List[int] = []                            # clones of the step in progress: owned here until they are installed in `beams`
+        process = None
+        if processors is not None and processors.active:
+            pa = processors.args()
+
+            def process(histories: List[List[int]], logprobs: torch.Tensor) -> torch.Tensor:
+                return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
         try:
+            eng.seq_set_processors(beams[0], *LP.OFF.args())     # the steps must hand back raw logits (clones copy this setting)
             first = eng.prefill(beams[0], emb, want_logits=True)
 
             def step(parents: List[int], toks: List[int]) -> torch.Tensor:
@@ -332,7 +360,7 @@ class LLAVA_NEXT_VIDEO:
                     return eng.decode_step_logits_batch(beams, toks)        # the k beams share ONE stream of the weights
                 return torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(beams, toks)])
 
-            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample)
+            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process)
         finally:
             for s_ in set(x for x in list(beams) + fresh if x is not None):
                 try:
@@ -344,22 +372,27 @@ class LLAVA_NEXT_VIDEO:
     def generate_shared(self, samples, prompts: Sequence[str], **generate_kwargs) -> List[str]:
         """Several prompts about ONE video.  The reference's inference.py calls generate() once per prompt (grounding / QA /
         referring, inference.py:178-182) and re-runs both vision towers every time; here the video is encoded once and the prompts
-        are prefilled and decoded together.  Texts are identical to one generate() call per prompt (batch-invariant kernels)."""
-        self._select_tokens(generate_kwargs)
+        are prefilled and decoded together.  Texts are identical to one generate() call per prompt (batch-invariant kernels) -- the logits
+        processors included: each prompt gets its own (its min_length is lowered by its own embedding length, as its own reference call would)."""
         if samples["spatial_pixel_values"].shape[0] != 1:
             raise ValueError("generate_shared takes the pixel tensors of one video")
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
         ids = [self.tokenizer_image_token(t) for t in prompts]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
-        feats = self.encode_images(samples)
         rows = [[int(t) for t, m in zip(ids_arr[i], mask[i]) if m] for i in range(len(prompts))]
-        out_ids = self._generate_shared_prefix(rows, feats[0], max_new)
+        n_vis = self._n_visual(samples)
+        self._select_processors(generate_kwargs, LP.padded_embed_len(len(rows[0]), n_vis) if rows else 0)
+        self._select_tokens(generate_kwargs)
+        procs = [LP.resolve(generate_kwargs, getattr(self.tokenizer, "eos_token_id", None), LP.padded_embed_len(len(r), n_vis)) for r in rows]
+        feats = self.encode_images(samples)
+        out_ids = self._generate_shared_prefix(rows, feats[0], max_new, procs)
         if out_ids is None:                              # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
-            out_ids = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new)
+            out_ids = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs)
         return [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
 
-    def _generate_shared_prefix(self, rows: List[List[int]], vis: torch.Tensor, max_new: int) -> Optional[List[List[int]]]:
+    def _generate_shared_prefix(self, rows: List[List[int]], vis: torch.Tensor, max_new: int,
+                                processors: Optional[List["LP.Processors"]] = None) -> Optional[List[List[int]]]:
         """Prompts about one video share the system prompt and the visual tokens: the common prefix (rounded down to 128 tokens = whole KV pages AND
         whole query blocks, so that every later row is computed exactly as in a full prefill) is prefilled ONCE; every prompt forks it
         (gvl_seq_fork: pages referenced, not copied) and prefills only its own tail (gvl_prefill_extend); the answers are decoded together.
@@ -393,8 +426,10 @@ class LLAVA_NEXT_VIDEO:
         try:
             base = eng.seq_alloc(prefix)
             eng.prefill(base, embs[0][:prefix])
-            for e in embs:
+            for i, e in enumerate(embs):
                 seqs.append(eng.seq_fork(base, prefix, min(e.shape[0] + max_new, self.geo.max_seq)))
+                if processors is not None:
+                    eng.seq_set_processors(seqs[-1], *processors[i].args())
                 eng.prefill_extend(seqs[-1], e[prefix:])
             return eng.decode_greedy_batch(seqs, max_new, eos)
         finally:
@@ -437,12 +472,16 @@ class LLAVA_NEXT_VIDEO:
 
     __call__ = forward
 
-    def generate_ids(self, ids_arr, mask, feats, max_new: int) -> List[List[int]]:
+    def generate_ids(self, ids_arr, mask, feats, max_new: int, processors=None) -> List[List[int]]:
+        """Greedy / sampled ids of every row.  processors: one logits.Processors for all rows, a list with one per row, or None (the engine's
+        default, set_logits_processors)."""
         eos = getattr(self.tokenizer, "eos_token_id", None)
         eng = self.engine
+        if processors is not None and not isinstance(processors, (list, tuple)):
+            processors = [processors] * ids_arr.shape[0]
         if ids_arr.shape[0] == 1:
             row = [int(t) for t, m in zip(ids_arr[0], mask[0]) if m]
-            return [eng.generate_ids(eng.splice(row, feats[0]), max_new, eos)]
+            return [eng.generate_ids(eng.splice(row, feats[0]), max_new, eos, processors=None if processors is None else processors[0])]
         # bs > 1 (the reference left-pads the batch, llava_next_video.py:622-647): every sample keeps its own paged KV and its
         # un-padded length -- identical maths to the masked left-padded batch.  Prefill runs over the packed rows of the batch
         # (gvl_prefill_varlen) and the greedy decode of the whole batch runs together (gvl_decode_greedy_batch: one weight stream
@@ -464,6 +503,8 @@ class LLAVA_NEXT_VIDEO:
                         if e.status == ERR_OOM and seqs:
                             break                      # pool full: run what fits, the rest in the next group
                         raise
+                    if processors is not None:
+                        eng.seq_set_processors(seqs[-1], *processors[i].args())
                     embs.append(emb)
                 eng.prefill_batch(seqs, embs)
                 out += eng.decode_greedy_batch(seqs, max_new, eos)

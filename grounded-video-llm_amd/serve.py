@@ -32,6 +32,7 @@ class _Request:
     seq: int = -1
     ids: List[int] = field(default_factory=list)
     n_gen: int = 0               # tokens generated on the device so far (>= len(ids) once eos was seen)
+    processors: object = None    # logits.Processors of this request (None: the engine's default)
 
 
 class ClipScheduler:
@@ -49,10 +50,18 @@ class ClipScheduler:
         self.stats = {"prefill_calls": 0, "decode_chunks": 0, "decode_seq_steps": 0, "wasted_seq_steps": 0, "max_concurrent": 0}
 
     # ---- public ------------------------------------------------------------------------------------------
-    def submit(self, embeds, max_new_tokens: int) -> int:
+    def submit(self, embeds, max_new_tokens: int, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+               min_new_tokens: Optional[int] = None) -> int:
+        """Queue one request.  repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors for THIS request (HF's validation;
+        applied on the device to its generated ids; min_new_tokens needs the scheduler's eos id).  Requests with different settings share one
+        decode group.  None for all three: the sequence keeps the engine's default (Engine.set_logits_processors)."""
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
-        r = _Request(self._next, embeds, int(max_new_tokens))
+        procs = None
+        if repetition_penalty is not None or no_repeat_ngram_size is not None or min_new_tokens is not None:
+            from . import logits as LP
+            procs = LP.resolve(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens), self.eos)
+        r = _Request(self._next, embeds, int(max_new_tokens), processors=procs)
         self._next += 1
         self.queue.append(r)
         return r.rid
@@ -102,6 +111,12 @@ class ClipScheduler:
                 if getattr(e, "status", 0) == L.ERR_OOM:     # KV pages exhausted: wait for a retirement (FIFO, no overtaking)
                     break
                 raise
+            if r.processors is not None:
+                try:
+                    self.eng.seq_set_processors(r.seq, *r.processors.args())
+                except Exception:
+                    self.eng.seq_free(r.seq)
+                    raise
             r.max_new = min(r.max_new, cap - S + 1)          # generate() stops at the context limit (Engine.generate_ids does too)
             self.queue.popleft()
             new.append(r)

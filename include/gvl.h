@@ -168,6 +168,18 @@ int gvl_decode_greedy(gvl_ctx* ctx, int seq_id, int max_new, int eos_id, int32_t
  * bookkeeping over gvl_seq_clone + gvl_decode_step_logits_batch (grounded_video_llm_amd/beam.py); beam-sample (num_beams > 1, do_sample = 1) is the
  * same bookkeeping with the 2 x num_beams candidates of a step drawn on the host from the warped beam distributions (beam.py). */
 int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, float top_p, uint64_t seed);
+/* HF generate()'s logits processors, applied on the device to a sequence's fp32 logits row at every token selection (prefill's first
+ * token, gvl_decode_greedy*, gvl_decode_steps; greedy and sampling alike), before the warpers / argmax, in HF's order:
+ *   penalty != 1   RepetitionPenaltyLogitsProcessor: every DISTINCT generated id t: s[t] = s[t] < 0 ? s[t] * penalty : s[t] / penalty
+ *   ngram > 0      NoRepeatNGramLogitsProcessor: an id that would complete an n-gram already generated gets -inf
+ *   min_new > 0    MinLength / MinNewTokensLength: s[eos_id] = -inf while fewer than min_new ids were generated (off when eos_id < 0)
+ * The history is the sequence's GENERATED ids only (up to 8192): the reference calls generate(inputs_embeds=...) without input_ids, so
+ * HF never sees the prompt's ids.  penalty 1, ngram 0, min_new 0 = off (the default): the token selection is then exactly the one without
+ * processors.  gvl_set_logits_processors sets the default every sequence allocated AFTER the call starts with (gvl_seq_alloc);
+ * gvl_seq_set_processors overrides one live sequence; gvl_seq_fork / gvl_seq_clone copy the source's settings (a clone's history starts
+ * empty: its generation count restarts at 0).  Errors: penalty not > 0 (NaN included), ngram < 0, min_new < 0. */
+int gvl_set_logits_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, int eos_id);
+int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, int min_new, int eos_id);
 /* Prefill of n_seqs sequences together, seq_lens[i] tokens each (ragged: prompts differ in length; the reference left-pads and
  * masks, llava_next_video.py:622-647 -- here the rows are packed back to back, no padding).  Groups of 4 / 2 / 1 sequences whose
  * rows fit cfg.max_prefill: the decoder GEMMs run over all rows of a group at once (better tile fill); RoPE / KV append / causal
@@ -333,6 +345,11 @@ int gvl_op_gemv(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float*
  * random stream streams[b] (host array) at generation step steps_dev[b] (device array).  batch <= 16. */
 int gvl_op_sample(gvl_ctx* ctx, const float* logits, int n, int batch, float temperature, int top_k, float top_p, uint64_t seed,
                   const uint32_t* streams, const int32_t* steps_dev, int32_t* tokens_dev, void* stream);
+/* The logits processors on their own (operator tests; beam search applies them to its log-softmax rows): logits f32 device [batch][n],
+ * changed IN PLACE; row b's history is hist_dev[b * hist_stride .. + lens_dev[b]) (int32 device; lengths are clamped to
+ * min(hist_stride, 8192)); per-row parameters are host arrays with gvl_set_logits_processors' meaning.  batch <= 16. */
+int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                          const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, void* stream);
 /* y[b][N] = W[N,K] x[b][K] (+bias) for b < batch <= 16 -- the decode projections as ONE skinny MFMA GEMM (the weight stream is
  * read once for all sequences; K % 256 == 0).  x bf16 [batch][K], y f32 [batch][N]. */
 int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch,

@@ -57,6 +57,9 @@ def parse_args(argv=None):
     p.add_argument("--max_new_tokens", type=int, default=2048)
     p.add_argument("--temperature", type=float, default=0.2)
     p.add_argument("--top_p", type=float, default=None)
+    p.add_argument("--repetition_penalty", type=float, default=None, help="HF RepetitionPenaltyLogitsProcessor on the generated ids (1.0 = off)")
+    p.add_argument("--no_repeat_ngram_size", type=int, default=None, help="HF NoRepeatNGramLogitsProcessor on the generated ids (0 = off)")
+    p.add_argument("--min_new_tokens", type=int, default=None, help="HF MinNewTokensLengthLogitsProcessor: no eos before this many new ids")
     p.add_argument("--share_visual", type=_bool, default=False, help="encode the video ONCE for the three prompts and batch them (the reference re-encodes per prompt)")
     p.add_argument("--synthetic", action="store_true", help="seeded random weights / frames / tokenizer (offline image)")
     p.add_argument("--synthetic_scale", type=str, default="small", choices=["small", "full"])
@@ -129,6 +132,9 @@ def main(argv=None):
         frames, fps, vlen, duration = read_frames(args.video_path, args.num_frames)
 
     kw = {"do_sample": args.do_sample, "num_beams": args.num_beams, "max_new_tokens": args.max_new_tokens, "temperature": args.temperature, "top_p": args.top_p, "seed": args.seed}
+    for name in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"):     # forwarded only when given, like any other HF generate kwarg
+        if getattr(args, name) is not None:
+            kw[name] = getattr(args, name)
     outs = {}
     modes = ("grounding", "qa", "referring")
     if args.share_visual:
