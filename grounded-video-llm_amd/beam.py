@@ -32,15 +32,15 @@ class _Hyps:
 
     def __init__(self, num_beams: int, length_penalty: float, early_stopping):
         self.k, self.lp, self.early = num_beams, length_penalty, early_stopping
-        self.beams: List[Tuple[float, List[int], bool]] = []
+        self.beams: List[Tuple[float, List[int], bool, List[float]]] = []   # (score, ids, ended by eos, per-token scores)
         self.worst = 1e9
 
-    def add(self, toks: Sequence[int], sum_logprobs: float, generated_len: int, by_eos: bool):
+    def add(self, toks: Sequence[int], sum_logprobs: float, generated_len: int, by_eos: bool, token_scores: Sequence[float] = ()):
         score = sum_logprobs / (generated_len ** self.lp)
         if len(self.beams) < self.k or score > self.worst:
-            self.beams.append((score, list(toks), by_eos))
+            self.beams.append((score, list(toks), by_eos, list(token_scores)))
             if len(self.beams) > self.k:
-                order = sorted((s, i) for i, (s, _, _) in enumerate(self.beams))
+                order = sorted((s, i) for i, (s, _, _, _) in enumerate(self.beams))
                 del self.beams[order[0][1]]
                 self.worst = order[1][0]
             else:
@@ -79,14 +79,18 @@ def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[
 
 def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logits: torch.Tensor, num_beams: int, max_new_tokens: int,
                 eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None,
-                process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None) -> List[int]:
+                process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None, with_scores: bool = False):
     """first_logits [vocab]: logits after the prompt.  step(parents, tokens) -> logits [k, vocab] of the k new running beams, where new beam j
     continues old beam parents[j] with tokens[j] (the caller reorders its KV cache accordingly; at the first call every parent is 0 = the
     prompt).  Returns the NEW ids of the best hypothesis (eos included when it ended by eos), as HF does for inputs_embeds prompts.
     sample: None = beam search; dict(temperature, top_k, top_p, generator) = beam-sample (module docstring).
     process(histories, logprobs) -> logprobs: HF's logits processors (repetition penalty, no-repeat n-gram, min length; grounded_video_llm_amd/logits.py)
     on the [k, vocab] log-softmax rows of the running beams, histories[j] = the ids beam j generated so far; applied before the warpers and before
-    the beam scores are added, as HF's _beam_search / _beam_sample do."""
+    the beam scores are added, as HF's _beam_search / _beam_sample do.
+    with_scores: return (ids, sequences_score, transition_scores) instead -- HF's definitions: sequences_score = the hypothesis score (sum of the
+    processed log-probabilities / generated_len ** length_penalty), transition_scores = compute_transition_scores(seq, scores, beam_indices,
+    normalize_logits=False), i.e. per new id the processed (beam-sample: warped) log-probability it had in the row of the beam it extended, before
+    the beam score was added -- tracked per running beam through the parent chain."""
     k = int(num_beams)
     if k < 2:
         raise ValueError("beam_search needs num_beams >= 2")
@@ -94,6 +98,7 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     if V < 2 * k:
         raise ValueError("vocabulary smaller than 2 x num_beams")
     seqs: List[List[int]] = [[] for _ in range(k)]
+    tsc: List[List[float]] = [[] for _ in range(k)]             # per running beam: the transition score of each of its ids
     # transformers 4.40.1: _beam_search starts beams 1..k-1 at -1e9 (the first step expands beam 0 only); _beam_sample starts EVERY beam at 0 -- its
     # first draw is over k identical rows, so the same token may be drawn from two rows and the running beams may start as duplicates
     scores = torch.zeros((k,), dtype=torch.float32, device=first_logits.device)
@@ -106,12 +111,14 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
         lp = torch.log_softmax(logits.float(), dim=-1)
         if process is not None:
             lp = process([list(q) for q in seqs], lp)
+        proc = lp                                        # (beam-sample: warped below) the rows HF reports as `scores`
         if sample is None:
             lp = lp + scores[:, None]
             top = torch.topk(lp.reshape(-1), 2 * k, largest=True, sorted=True)
             vals, idxs = top.values.tolist(), top.indices.tolist()
         else:
-            lp = warp_scores(lp, sample.get("temperature", 1.0), sample.get("top_k", 50), sample.get("top_p")) + scores[:, None]
+            proc = warp_scores(lp, sample.get("temperature", 1.0), sample.get("top_k", 50), sample.get("top_p"))
+            lp = proc + scores[:, None]
             flat = lp.reshape(-1)
             n_fin = int(torch.isfinite(flat).sum())
             if n_fin < 2 * k:                                # torch.multinomial(replacement=False) would silently hand back zero-probability indices
@@ -121,31 +128,33 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
             pv, order = torch.sort(flat[picks], descending=True)
             vals, idxs = pv.tolist(), picks[order].tolist()
         cur_len = len(seqs[0]) + 1
-        nxt: List[Tuple[float, int, int]] = []
-        for rank, (v, ix) in enumerate(zip(vals, idxs)):
+        pv_tok = proc.reshape(-1)[torch.as_tensor(idxs, device=proc.device)].tolist() if with_scores else [0.0] * len(idxs)
+        nxt: List[Tuple[float, int, int, float]] = []
+        for rank, (v, ix, t_sc) in enumerate(zip(vals, idxs, pv_tok)):
             b, tok = ix // V, ix % V
             if eos_id is not None and tok == eos_id:
                 if rank >= k:
                     continue
-                hyps.add(seqs[b], v, cur_len, True)
+                hyps.add(seqs[b], v, cur_len, True, tsc[b] + [t_sc])
             else:
-                nxt.append((v, tok, b))
+                nxt.append((v, tok, b, t_sc))
             if len(nxt) == k:
                 break
         if len(nxt) < k:
             raise ValueError("fewer than num_beams non-eos candidates among the top 2 x num_beams")
         done = done or hyps.is_done(max(vals), cur_len)
         # first step: every row is the prompt itself (beam-sample may have drawn from rows >= 1 of its k identical rows) -> parent 0
-        parents, toks = [0 if cur_len == 1 else b for _, _, b in nxt], [t for _, t, _ in nxt]
-        seqs = [seqs[b] + [t] for _, t, b in nxt]
-        scores = torch.tensor([v for v, _, _ in nxt], dtype=torch.float32, device=first_logits.device)
+        parents, toks = [0 if cur_len == 1 else b for _, _, b, _ in nxt], [t for _, t, _, _ in nxt]
+        seqs = [seqs[b] + [t] for _, t, b, _ in nxt]
+        tsc = [tsc[b] + [t_sc] for _, _, b, t_sc in nxt]
+        scores = torch.tensor([v for v, _, _, _ in nxt], dtype=torch.float32, device=first_logits.device)
         if done or len(seqs[0]) >= max_new_tokens:
             break
         logits = step(parents, toks)
     if not done:
         for j in range(k):                                   # finalize(): the open beams become hypotheses
-            hyps.add(seqs[j], float(scores[j]), len(seqs[j]), False)
-    best = max(hyps.beams, key=lambda x: x[0]) if hyps.beams else (0.0, seqs[0], False)
+            hyps.add(seqs[j], float(scores[j]), len(seqs[j]), False, tsc[j])
+    best = max(hyps.beams, key=lambda x: x[0]) if hyps.beams else (0.0, seqs[0], False, tsc[0])
     # python's sort is stable and HF takes sorted(...)[-1]: among equal scores the LAST added wins
     top_score = best[0]
     for h in hyps.beams:
@@ -154,4 +163,6 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     out = list(best[1])
     if best[2] and eos_id is not None and len(out) < max_new_tokens:
         out.append(eos_id)
+    if with_scores:
+        return out, float(best[0]), list(best[3])[:len(out)]
     return out

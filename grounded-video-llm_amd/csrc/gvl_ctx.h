@@ -49,6 +49,11 @@ struct Seq {
   unsigned rng_stream = 0;  // sampling: which random stream this sequence draws from (assigned at its prefill)
   int* d_eos = nullptr; volatile int* h_eos = nullptr;   // host-mapped word: generation count at which this sequence produced eos (0 = not yet)
   LogitsProc proc;          // HF logits processors of this sequence's token selection (gvl_seq_set_processors; default: gvl_ctx::proc_default)
+  // log-probabilities of the selected tokens (gvl_seq_set_logprobs; default: gvl_ctx::top_n_default): -1 off, 0 the selected token's, 1 .. 8 also the
+  // top N.  Device lists of the sequence's slot, index = generation step like d_out ([outlist_cap], top lists [outlist_cap][GVL_MAX_TOP_LOGPROBS]);
+  // null until the ctx allocated them (gvl_ctx::d_seq_lp / d_seq_top_*)
+  int top_n = -1;
+  float* d_lp = nullptr; int* d_top_ids = nullptr; float* d_top_lp = nullptr;
 };
 
 struct ProfRec { int cat; hipEvent_t e0, e1; double work; };
@@ -111,6 +116,10 @@ struct gvl_ctx {
   struct { bool on = false; float inv_temp = 1.f, top_p = 0.f; int top_k = 0; unsigned long long seed = 0; unsigned next_stream = 0; } sample;
   // logits processors copied into every sequence allocated later (gvl_set_logits_processors); off by default
   LogitsProc proc_default;
+  // log-probability lists of every sequence slot ([kMaxSeqs][outlist_cap], top lists x GVL_MAX_TOP_LOGPROBS: ~134 MB), allocated by the first
+  // gvl_set_logprobs / gvl_seq_set_logprobs that needs them; top_n_default is copied into every sequence allocated later
+  float* d_seq_lp = nullptr; int* d_seq_top_ids = nullptr; float* d_seq_top_lp = nullptr;
+  int top_n_default = -1;
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
   // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of ~165 kernel launches
   struct { int decode_attn_cpb = 0, decode_attn_hpb = 0; bool decode_graph = true; int vision_in_place = 1, prefill_group = 4, attn_ring = 0, attn_pipe = 1, attn_pipe_rows = 128, patch_fused = 1, varlen_attn = 1, norm_fused = 1, last_layer_tail = 1; } dbg;

@@ -824,7 +824,109 @@ int gvl_launch_gemv(const GemvArgs& a_in, hipStream_t st) {
   }
 }
 
+// ---- log-probabilities of the selected token and the best N alternatives (ArgmaxArgs.top_n / lp_lists / top_ids / top_lp).  The selection
+// kernels take a mode LPM: 0 = off (today's kernels, instruction for instruction), 1 = the selected token's log-probability, 2 = also the top N.
+// The distribution is the one the token was selected from: log_softmax of the (processed) row for greedy, the warped distribution for sampling
+// ((s - m) * invT over the final kept set, everything else -inf).  One extra pass over the row (in L2 by then): a fixed-order sum of
+// exp((s - m) * invT) over the kept set (strided per thread, then the smp_block_sum butterfly -- a pure function of the row), and a per-thread
+// register list of the best 8 finite kept entries, merged per wave (8 rounds of a butterfly max over the list heads) and across the 16 waves
+// through LDS.  The order is (value descending, lower id first), a strict total order: the merged list does not depend on who held what.
+// The token path is untouched: the pass runs after the selection's own passes and never feeds them.
+// (the sampler's helpers smp_* are shared with the sampling section below)
+__device__ __forceinline__ unsigned smp_fmix32(unsigned h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
+__device__ __forceinline__ unsigned smp_key(float v) { const unsigned b = __float_as_uint(v); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }   // order-preserving
+__device__ __forceinline__ float smp_block_sum(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);          // butterfly: bitwise the same total in every lane
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) t += sh[w];
+  return t;
+}
+__device__ __forceinline__ bool lp_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+// (v, i) into a thread's descending list: the carried entry swaps with every slot it beats (the list stays sorted, the last entry drops out)
+__device__ __forceinline__ void lp_insert(float (&tv)[GVL_MAX_TOP_LOGPROBS], int (&ti)[GVL_MAX_TOP_LOGPROBS], float v, int i) {
+  if (!lp_better(v, i, tv[GVL_MAX_TOP_LOGPROBS - 1], ti[GVL_MAX_TOP_LOGPROBS - 1])) return;
+#pragma unroll
+  for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j)
+    if (lp_better(v, i, tv[j], ti[j])) { const float t = tv[j]; const int u = ti[j]; tv[j] = v; ti[j] = i; v = t; i = u; }
+}
+// the best GVL_MAX_TOP_LOGPROBS entries of the 64 lists of a wave, in order, in every lane (wv / wi); the lists are consumed
+__device__ __forceinline__ void lp_wave_merge(float (&tv)[GVL_MAX_TOP_LOGPROBS], int (&ti)[GVL_MAX_TOP_LOGPROBS], float (&wv)[GVL_MAX_TOP_LOGPROBS],
+                                              int (&wi)[GVL_MAX_TOP_LOGPROBS]) {
+#pragma unroll
+  for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) {
+    float bv = tv[0]; int bi = ti[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+      if (lp_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    wv[r] = bv; wi[r] = bi;
+    if (bi >= 0 && ti[0] == bi) {          // ids are unique across lanes: exactly the owner pops its head
+#pragma unroll
+      for (int j = 0; j + 1 < GVL_MAX_TOP_LOGPROBS; ++j) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
+      tv[GVL_MAX_TOP_LOGPROBS - 1] = -INFINITY; ti[GVL_MAX_TOP_LOGPROBS - 1] = -1;
+    }
+  }
+}
+// Whole block, row b on (block-uniform).  Kept set: keys >= thr (0: every entry).  Returns log(sum over the kept set of exp((s - m) * invT));
+// with LPM == 2 and top_n[b] > 0 it also stores row b's top list at generation index g.
+template <int LPM>
+__device__ float lp_row_pass(const ArgmaxArgs& a, int b, const float* l, float m, float inv_temp, unsigned thr, int g) {
+  __shared__ float shz[16];
+  const int tid = threadIdx.x, n = a.n;
+  const bool top = LPM == 2 && a.top_n[b] > 0 && a.top_ids[b] && a.top_lp[b];
+  float tv[GVL_MAX_TOP_LOGPROBS]; int ti[GVL_MAX_TOP_LOGPROBS];
+#pragma unroll
+  for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j) { tv[j] = -INFINITY; ti[j] = -1; }
+  float z = 0.f;
+  for (int i = tid; i < n; i += 1024) {
+    const float v = l[i];
+    if (smp_key(v) < thr) continue;
+    z += expf((v - m) * inv_temp);
+    if (LPM == 2 && top && fabsf(v) < INFINITY) lp_insert(tv, ti, v, i);
+  }
+  const float lz = logf(smp_block_sum(z, shz));
+  if constexpr (LPM == 2) {
+    if (top) {
+      __shared__ float s_tv[16 * GVL_MAX_TOP_LOGPROBS];
+      __shared__ int s_ti[16 * GVL_MAX_TOP_LOGPROBS];
+      float wv[GVL_MAX_TOP_LOGPROBS]; int wi[GVL_MAX_TOP_LOGPROBS];
+      lp_wave_merge(tv, ti, wv, wi);
+      if ((tid & 63) == 0) {
+#pragma unroll
+        for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) { s_tv[(tid >> 6) * GVL_MAX_TOP_LOGPROBS + r] = wv[r]; s_ti[(tid >> 6) * GVL_MAX_TOP_LOGPROBS + r] = wi[r]; }
+      }
+      __syncthreads();
+      if (tid < 64) {
+        const int lane = tid;
+#pragma unroll
+        for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j) {
+          tv[j] = lane < 16 ? s_tv[lane * GVL_MAX_TOP_LOGPROBS + j] : -INFINITY; ti[j] = lane < 16 ? s_ti[lane * GVL_MAX_TOP_LOGPROBS + j] : -1;
+        }
+        lp_wave_merge(tv, ti, wv, wi);
+        float v = -INFINITY; int id = -1;
+#pragma unroll
+        for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) if (lane == r) { v = wv[r]; id = wi[r]; }
+        if (lane < GVL_MAX_TOP_LOGPROBS) {
+          const bool ok = lane < a.top_n[b] && id >= 0;
+          a.top_ids[b][(size_t)g * GVL_MAX_TOP_LOGPROBS + lane] = ok ? id : -1;
+          a.top_lp[b][(size_t)g * GVL_MAX_TOP_LOGPROBS + lane] = ok ? (v - m) * inv_temp - lz : -INFINITY;
+        }
+      }
+    }
+  }
+  return lz;
+}
+__device__ __forceinline__ bool lp_row_on(const ArgmaxArgs& a, int b) { return a.top_n[b] >= 0 && a.lp_lists[b] != nullptr; }
+__device__ __forceinline__ int lp_row_step(const ArgmaxArgs& a, int b) { return a.ngen_ptrs[b] ? *a.ngen_ptrs[b] : 0; }
+
 // greedy sampling: first index of the maximum (torch.argmax tie rule); one block per logit row
+template <int LPM>
 __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a) {
   __shared__ float bv[16];
   __shared__ int bi[16];
@@ -842,9 +944,18 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a) {
   }
   if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
   __syncthreads();
+  [[maybe_unused]] float lz = 0.f;
+  if constexpr (LPM > 0) {
+    if (lp_row_on(a, b)) {                   // every thread needs the row maximum: the same scan thread 0 makes below
+      float m = bv[0]; int mi = bi[0];
+      for (int w = 1; w < 16; ++w) if (bv[w] > m || (bv[w] == m && bi[w] < mi)) { m = bv[w]; mi = bi[w]; }
+      lz = lp_row_pass<LPM>(a, b, logits, m, 1.0f, 0u, lp_row_step(a, b));
+    }
+  }
   if (threadIdx.x == 0) {
     for (int w = 1; w < 16; ++w) if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
     *a.tok_ptrs[b] = idx;
+    if constexpr (LPM > 0) if (lp_row_on(a, b)) a.lp_lists[b][lp_row_step(a, b)] = 0.f - lz;   // s_tok - m = 0
     if (a.ngen_ptrs[b]) {
       const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
       if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -852,9 +963,25 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a) {
     if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
   }
 }
+// 0: no row wants log-probabilities (the launch is today's), 1: chosen tokens only, 2: some row wants its top N as well; -1: bad top_n
+static int lp_mode(const ArgmaxArgs& a) {
+  int mode = 0;
+  for (int b = 0; b < a.batch; ++b) {
+    if (a.top_n[b] > GVL_MAX_TOP_LOGPROBS) return -1;
+    if (a.top_n[b] < 0 || !a.lp_lists[b]) continue;
+    const int m = a.top_n[b] > 0 && a.top_ids[b] && a.top_lp[b] ? 2 : 1;
+    mode = m > mode ? m : mode;
+  }
+  return mode;
+}
 int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st) {
   if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH) return -1;
-  hipLaunchKernelGGL(argmax_kernel, dim3(a.batch), dim3(1024), 0, st, a);
+  switch (lp_mode(a)) {
+    case 0: hipLaunchKernelGGL(argmax_kernel<0>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    case 1: hipLaunchKernelGGL(argmax_kernel<1>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    case 2: hipLaunchKernelGGL(argmax_kernel<2>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    default: return -1;
+  }
   return CHECK_LAUNCH();
 }
 // ---- sampling (do_sample=True): the reference forwards do_sample / temperature / top_p to HF generate (models/llava_next_video.py:655-661;
@@ -866,19 +993,7 @@ int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st) {
 // reproduced, so parity is: same kept set and same token as the CPU restatement `sample_token` used by the tests (same hash), and the right distribution.
 // One block per row; every pass re-reads the row from L2 (32 k - 128 k floats).  All reductions run in a fixed order and every
 // thread sees the same totals, so the thresholds are wave-uniform and the result does not depend on the batch a row travels in.
-__device__ __forceinline__ unsigned smp_fmix32(unsigned h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
-__device__ __forceinline__ unsigned smp_key(float v) { const unsigned b = __float_as_uint(v); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }   // order-preserving
-__device__ __forceinline__ float smp_block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);          // butterfly: bitwise the same total in every lane
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) t += sh[w];
-  return t;
-}
+template <int LPM>
 __global__ __launch_bounds__(1024) void sample_kernel(const ArgmaxArgs a) {
   __shared__ float shf[16];
   __shared__ int shi[16];
@@ -967,10 +1082,25 @@ __global__ __launch_bounds__(1024) void sample_kernel(const ArgmaxArgs a) {
     }
     if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
   }
+  // log-probabilities, AFTER the selection (whose code is then the LPM = 0 kernel's, instruction for instruction): the normaliser and top N over
+  // the FINAL kept set, keys >= thr -- Z above is summed before top-p.  Thread 0's token / counter stores are visible to the block after the barrier.
+  if constexpr (LPM > 0) {
+    if (lp_row_on(a, b)) {
+      __syncthreads();
+      const int g = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] - 1 : 0;
+      const float lz = lp_row_pass<LPM>(a, b, l, m, a.inv_temp, thr, g);
+      if (tid == 0) { const int tok = *a.tok_ptrs[b]; a.lp_lists[b][g] = tok >= 0 && tok < n ? (l[tok] - m) * a.inv_temp - lz : -INFINITY; }
+    }
+  }
 }
 int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st) {
   if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH || !(a.inv_temp > 0.f) || a.top_k < 0 || a.top_p < 0.f) return -1;
-  hipLaunchKernelGGL(sample_kernel, dim3(a.batch), dim3(1024), 0, st, a);
+  switch (lp_mode(a)) {
+    case 0: hipLaunchKernelGGL(sample_kernel<0>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    case 1: hipLaunchKernelGGL(sample_kernel<1>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    case 2: hipLaunchKernelGGL(sample_kernel<2>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    default: return -1;
+  }
   return CHECK_LAUNCH();
 }
 __global__ void gather_tok_rows_kernel(const bf16_t* __restrict__ table, const TokPtrs toks, bf16_t* __restrict__ dst, int cols) {

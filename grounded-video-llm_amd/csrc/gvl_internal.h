@@ -348,7 +348,13 @@ struct ArgmaxArgs { const float* logits; int n, batch; int* tok_ptrs[GVL_MAX_DEC
                     // eos_flags[b] -- the host reads it two steps behind the GPU instead of draining the stream every 16 steps
                     int eos_id; int* eos_flags[GVL_MAX_DECODE_BATCH];
                     float inv_temp, top_p; int top_k; unsigned seed_lo, seed_hi; unsigned stream[GVL_MAX_DECODE_BATCH];
-                    const int* step_override; };   // operator tests: generation step of row b when the row has no ngen counter
+                    const int* step_override;      // operator tests: generation step of row b when the row has no ngen counter
+                    // log-probabilities (after every field above: the kernel-argument offsets of the off instantiations stay put).  Row b is on
+                    // when top_n[b] >= 0 and lp_lists[b] is set: lp_lists[b][g] = log-probability of its token under the distribution it was
+                    // selected from; top_n[b] = 1 .. GVL_MAX_TOP_LOGPROBS (with top_ids / top_lp set) also stores the best top_n entries at
+                    // [g * GVL_MAX_TOP_LOGPROBS ..) and pads the remaining slots with (-1, -inf).  g = *ngen_ptrs[b] (0 without a counter), as for out_lists.
+                    int top_n[GVL_MAX_DECODE_BATCH]; float* lp_lists[GVL_MAX_DECODE_BATCH]; int* top_ids[GVL_MAX_DECODE_BATCH]; float* top_lp[GVL_MAX_DECODE_BATCH]; };
+constexpr int GVL_MAX_TOP_LOGPROBS = 8;
 int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st);
 int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
 // HF logits processors (repetition penalty -> no-repeat n-gram -> min length) on `batch` fp32 rows (stride ld), in place (gvl_logits.hip).  Row b's

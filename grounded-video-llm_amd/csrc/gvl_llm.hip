@@ -39,7 +39,8 @@ int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st) {
 // The next token of every row of `am`: argmax (greedy), or one draw per row when gvl_set_sampling switched sampling on.  When a sequence of the
 // group has logits processors (gvl_seq_set_processors), one launch applies them to the rows first; its history is the sequence's output list
 // (host-mapped) up to its device-side generation count, so a captured decode step replays with nothing baked in per step.  With every processor
-// off the launch sequence is the one without processors.
+// off the launch sequence is the one without processors.  Sequences with log-probabilities on (gvl_seq_set_logprobs) get them from the same
+// launch (a second instantiation of the selection kernel); with every sequence of the group off it is the kernel without them.
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
   bool any_proc = false;
   for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->proc.on();
@@ -54,6 +55,12 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
     }
     const int rc = gvl_launch_logits_process(lp, st);
     if (rc) return rc;
+  }
+  for (int b = 0; b < am.batch; ++b) {             // log-probabilities (gvl_seq_set_logprobs): the sequence's slot lists, indexed by its device-side count
+    const Seq& q = *sqs[b];
+    if (q.top_n < 0 || !q.d_lp) continue;
+    am.top_n[b] = q.top_n; am.lp_lists[b] = q.d_lp;
+    if (q.top_n > 0) { am.top_ids[b] = q.d_top_ids; am.top_lp[b] = q.d_top_lp; }
   }
   if (!ctx->sample.on) return gvl_launch_argmax(am, st);
   am.inv_temp = ctx->sample.inv_temp; am.top_p = ctx->sample.top_p; am.top_k = ctx->sample.top_k;

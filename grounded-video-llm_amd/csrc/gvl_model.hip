@@ -180,7 +180,7 @@ int gvl_destroy(gvl_ctx* ctx) {
   for (void* p : ctx->nf_allocs) if (p) hipFree(p);
   ctx->nf_allocs.clear();
   if (ctx->comm) gvl_comm_destroy(ctx);
-  void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch};
+  void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch};
   for (void* p : ptrs) if (p) hipFree(p);
   for (auto& r : ctx->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   delete ctx;
@@ -466,6 +466,14 @@ int gvl_splice(gvl_ctx* ctx, const int64_t* ids, int n_ids, const uint16_t* visu
   return 0;
 }
 
+// the log-probability lists of slot `id` (null while the ctx has not allocated them)
+static void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
+  const size_t cap = (size_t)ctx->outlist_cap;
+  s.d_lp = ctx->d_seq_lp ? ctx->d_seq_lp + (size_t)id * cap : nullptr;
+  s.d_top_ids = ctx->d_seq_top_ids ? ctx->d_seq_top_ids + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
+  s.d_top_lp = ctx->d_seq_top_lp ? ctx->d_seq_top_lp + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
+}
+
 int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_alloc");
   if (max_tokens <= 0 || !seq_id) return fail(ctx, GVL_ERR_ARG, "gvl_seq_alloc: bad arguments");
@@ -481,6 +489,7 @@ int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
   Seq& s = ctx->seqs[id];
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = 0; s.n_gen = 0; s.pages.clear();
   s.proc = ctx->proc_default;                        // logits processors: the default of gvl_set_logits_processors
+  s.top_n = ctx->top_n_default;                      // log-probabilities: the default of gvl_set_logprobs
   for (int i = 0; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
   // preallocated slot: no hipMalloc / hipFree / device-wide sync per clip.  Work that uses the slot is stream ordered;
   // a freed slot or page may be handed out again only for work enqueued later on the same stream (one stream per ctx
@@ -490,6 +499,7 @@ int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
   s.d_tok = ctx->d_seq_tok + id;
   s.d_out = ctx->d_seq_out + (size_t)id * ctx->outlist_cap; s.h_out = ctx->h_seq_out + (size_t)id * ctx->outlist_cap;
   s.d_ngen = ctx->d_seq_ngen + id;
+  bind_logprobs(ctx, s, id);
   s.d_eos = ctx->d_eos_flags + id; s.h_eos = ctx->h_eos_flags + id;
   s.table_dirty = true;                               // written by the first prefill / decode on ITS stream (upload_table); d_pos likewise
   *seq_id = id;
@@ -517,8 +527,9 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
   }
   const std::vector<int> src_pages(ctx->seqs[src_seq].pages.begin(), ctx->seqs[src_seq].pages.begin() + shared);   // (emplace_back may have moved the source)
   const LogitsProc src_proc = ctx->seqs[src_seq].proc;
+  const int src_top_n = ctx->seqs[src_seq].top_n;
   Seq& s = ctx->seqs[id];
-  s.proc = src_proc;
+  s.proc = src_proc; s.top_n = src_top_n;
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = n_tokens; s.n_gen = 0; s.pages = src_pages;
   for (int p : s.pages) ++ctx->page_ref[p];          // whole pages of the prefix: immutable from now on for both holders (appends go to later pages)
   for (int i = shared; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
@@ -527,6 +538,7 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
   s.d_tok = ctx->d_seq_tok + id;
   s.d_out = ctx->d_seq_out + (size_t)id * ctx->outlist_cap; s.h_out = ctx->h_seq_out + (size_t)id * ctx->outlist_cap;
   s.d_ngen = ctx->d_seq_ngen + id;
+  bind_logprobs(ctx, s, id);
   s.d_eos = ctx->d_eos_flags + id; s.h_eos = ctx->h_eos_flags + id;
   s.table_dirty = true;
   *dst_seq = id;
@@ -563,8 +575,9 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
   const std::vector<int> src_pages = ctx->seqs[src_seq].pages;
   const int src_ngen = ctx->seqs[src_seq].n_gen;
   const LogitsProc src_proc = ctx->seqs[src_seq].proc;
+  const int src_top_n = ctx->seqs[src_seq].top_n;
   Seq& s = ctx->seqs[id];
-  s.proc = src_proc;
+  s.proc = src_proc; s.top_n = src_top_n;
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = pos; s.n_gen = src_ngen;
   s.pages.assign(src_pages.begin(), src_pages.begin() + shared);
   for (int p : s.pages) ++ctx->page_ref[p];
@@ -574,6 +587,7 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
   s.d_tok = ctx->d_seq_tok + id;
   s.d_out = ctx->d_seq_out + (size_t)id * ctx->outlist_cap; s.h_out = ctx->h_seq_out + (size_t)id * ctx->outlist_cap;
   s.d_ngen = ctx->d_seq_ngen + id;
+  bind_logprobs(ctx, s, id);
   s.d_eos = ctx->d_eos_flags + id; s.h_eos = ctx->h_eos_flags + id;
   hipStream_t st = (hipStream_t)stream;
   s.table_dirty = true;
@@ -856,6 +870,79 @@ int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const i
     lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
   }
   RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
+  return 0;
+}
+
+// ---- log-probabilities of the selected tokens (ArgmaxArgs.top_n / lp_lists / top_ids / top_lp; gvl_elem.hip)
+// the slot lists a setting needs, allocated on first use (never during a decode call: the setters run between calls); live sequences are rebound
+static int ensure_logprob_lists(gvl_ctx* ctx, int top_n, const char* what) {
+  if (top_n < -1 || top_n > GVL_MAX_TOP_LOGPROBS) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": top_n must be -1 (off), 0 (selected token) or 1 .. 8");
+  if (top_n < 0) return 0;
+  if (!ctx->has_llm) return fail(ctx, GVL_ERR_STATE, std::string(what) + ": no language model configured");
+  const size_t n = (size_t)gvl_ctx::kMaxSeqs * ctx->outlist_cap;
+  bool grew = false;
+  if (!ctx->d_seq_lp) { HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_lp, n * 4)); grew = true; }
+  if (top_n > 0 && !ctx->d_seq_top_ids) {
+    HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_top_ids, n * GVL_MAX_TOP_LOGPROBS * 4));
+    HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_top_lp, n * GVL_MAX_TOP_LOGPROBS * 4));
+    grew = true;
+  }
+  if (grew) for (size_t i = 0; i < ctx->seqs.size(); ++i) if (ctx->seqs[i].used) bind_logprobs(ctx, ctx->seqs[i], (int)i);
+  return 0;
+}
+int gvl_set_logprobs(gvl_ctx* ctx, int top_n) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = ensure_logprob_lists(ctx, top_n, "gvl_set_logprobs")) return rc;
+  ctx->top_n_default = top_n;
+  return 0;
+}
+int gvl_seq_set_logprobs(gvl_ctx* ctx, int seq_id, int top_n) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_logprobs: bad seq");
+  if (const int rc = ensure_logprob_lists(ctx, top_n, "gvl_seq_set_logprobs")) return rc;
+  ctx->seqs[seq_id].top_n = top_n;
+  return 0;
+}
+int gvl_seq_read_logprobs(gvl_ctx* ctx, int seq_id, int first, int cap, float* lp, int32_t* top_ids, float* top_lp, int* n_gen, void* stream) {
+  REQUIRE_READY(ctx->has_llm, "gvl_seq_read_logprobs");
+  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used || !n_gen || first < 0 || cap < 0)
+    return fail(ctx, GVL_ERR_ARG, "gvl_seq_read_logprobs: bad arguments");
+  const Seq& sq = ctx->seqs[seq_id];
+  if (lp && (sq.top_n < 0 || !sq.d_lp)) return fail(ctx, GVL_ERR_STATE, "gvl_seq_read_logprobs: the sequence has log-probabilities off");
+  if ((top_ids || top_lp) && (sq.top_n < 1 || !sq.d_top_ids)) return fail(ctx, GVL_ERR_STATE, "gvl_seq_read_logprobs: the sequence keeps no top-N lists");
+  *n_gen = sq.n_gen;
+  int n = sq.n_gen - first; if (n > cap) n = cap;
+  if (n > 0) {
+    hipStream_t st = (hipStream_t)stream;
+    const size_t K = GVL_MAX_TOP_LOGPROBS;
+    if (lp) HIPCHK(ctx, hipMemcpyAsync(lp, sq.d_lp + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (top_ids) HIPCHK(ctx, hipMemcpyAsync(top_ids, sq.d_top_ids + (size_t)first * K, (size_t)n * K * 4, hipMemcpyDeviceToHost, st));
+    if (top_lp) HIPCHK(ctx, hipMemcpyAsync(top_lp, sq.d_top_lp + (size_t)first * K, (size_t)n * K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+  }
+  return 0;
+}
+int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, int do_sample, float temperature, int top_k, float top_p, uint64_t seed,
+                           const uint32_t* streams, const int32_t* steps_dev, const int* top_n, int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev,
+                           float* top_lp_dev, void* stream) {
+  if (!ctx || !logits || !top_n || !tokens_dev || !lp_dev || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH)
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: bad arguments");
+  if (do_sample && (!streams || !steps_dev || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f))
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: bad sampling arguments");
+  hipStream_t st = (hipStream_t)stream;
+  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = logits; am.n = n; am.batch = batch;
+  for (int b = 0; b < batch; ++b) {
+    if (top_n[b] < -1 || top_n[b] > GVL_MAX_TOP_LOGPROBS || (top_n[b] > 0 && (!top_ids_dev || !top_lp_dev)))
+      return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: top_n must be -1 .. 8 (top lists needed for > 0)");
+    am.tok_ptrs[b] = tokens_dev + b;
+    am.top_n[b] = top_n[b]; am.lp_lists[b] = lp_dev + b;
+    if (top_n[b] > 0) { am.top_ids[b] = top_ids_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; am.top_lp[b] = top_lp_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; }
+  }
+  if (!do_sample) { RUN(GVL_PROF_OTHER, 0, gvl_launch_argmax(am, st)); return 0; }
+  am.inv_temp = 1.0f / temperature; am.top_k = top_k; am.top_p = top_p; am.seed_lo = (unsigned)seed; am.seed_hi = (unsigned)(seed >> 32);
+  am.step_override = steps_dev;
+  for (int b = 0; b < batch; ++b) am.stream[b] = streams[b];
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
   return 0;
 }
 

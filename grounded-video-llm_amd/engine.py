@@ -13,6 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import lib as L
+from . import logprobs as LPR
 
 bf = torch.bfloat16
 
@@ -396,16 +397,22 @@ class Engine:
         self._chk(self.lib.gvl_decode_step_logits_batch(self.ctx, ids, n, tk, _ptr(logits), self.stream), "gvl_decode_step_logits_batch")
         return logits
 
-    def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None) -> List[int]:
+    def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None):
         """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  processors: a logits.Processors for this
-        sequence (None: the default of set_logits_processors)."""
+        sequence (None: the default of set_logits_processors).  logprobs: None = ids only; -1 .. 8 = this sequence's seq_set_logprobs setting, and
+        the return value is (ids, (lp, top)) as seq_read_logprobs gives them for the ids (read before the sequence is freed)."""
         S = embeds.shape[0]
         seq = self.seq_alloc(min(S + max_new_tokens, self.geo.max_seq))
         try:
             if processors is not None:
                 self.seq_set_processors(seq, *processors.args())
+            if logprobs is not None:
+                self.seq_set_logprobs(seq, logprobs)
             self.prefill(seq, embeds)
-            return self.decode_greedy(seq, max_new_tokens, eos_id)
+            ids = self.decode_greedy(seq, max_new_tokens, eos_id)
+            if logprobs is None:
+                return ids
+            return ids, self.seq_read_logprobs(seq, 0, len(ids), top=logprobs > 0)
         finally:
             self.seq_free(seq)
 
@@ -533,6 +540,49 @@ class Engine:
                                                      width, C.c_void_p(lens.data_ptr() + b0 * 4), (C.c_float * nb)(*pe[b0:b0 + nb]), (C.c_int * nb)(*ng[b0:b0 + nb]),
                                                      (C.c_int * nb)(*mn[b0:b0 + nb]), (C.c_int * nb)(*eo[b0:b0 + nb]), self.stream), "gvl_op_logits_process")
         return logits
+
+    def set_logprobs(self, top_n: Optional[int] = -1):
+        """gvl_set_logprobs: log-probabilities of the selected tokens for every sequence allocated AFTER this call.  None / -1 = off, 0 = the selected
+        token's, 1 .. 8 = also the top N of the same distribution (include/gvl.h)."""
+        self._chk(self.lib.gvl_set_logprobs(self.ctx, -1 if top_n is None else int(top_n)), "gvl_set_logprobs")
+
+    def seq_set_logprobs(self, seq: int, top_n: Optional[int]):
+        """gvl_seq_set_logprobs: the setting of one live sequence (overrides the default it was allocated with)."""
+        self._chk(self.lib.gvl_seq_set_logprobs(self.ctx, int(seq), -1 if top_n is None else int(top_n)), "gvl_seq_set_logprobs")
+
+    def seq_read_logprobs(self, seq: int, first: int = 0, cap: int = 4096, top: bool = False):
+        """gvl_seq_read_logprobs (synchronises the stream): (lp, top_list) of the ids generated by `seq` from index `first` (at most cap); lp: one
+        float per id; top_list (top=True; the sequence's top_n >= 1): per id its top_n (id, log-probability) pairs without padding, else None."""
+        cap = max(int(cap), 0)
+        lp = (C.c_float * max(cap, 1))()
+        K = LPR.MAX_TOP
+        ti = (C.c_int32 * max(cap * K, 1))() if top else None
+        tv = (C.c_float * max(cap * K, 1))() if top else None
+        n = C.c_int(0)
+        self._chk(self.lib.gvl_seq_read_logprobs(self.ctx, int(seq), int(first), cap, lp, ti, tv, C.byref(n), self.stream), "gvl_seq_read_logprobs")
+        m = max(0, min(n.value - first, cap))
+        lps = [float(lp[i]) for i in range(m)]
+        if not top:
+            return lps, None
+        return lps, [LPR.top_pairs(ti[i * K:(i + 1) * K], tv[i * K:(i + 1) * K], K) for i in range(m)]
+
+    def op_select_logprobs(self, logits: torch.Tensor, top_n, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p=None,
+                           seed: int = 0, streams=None, steps=None):
+        """gvl_op_select_logprobs on fp32 rows [B, n] (B <= 16): (tokens int32 [B], lp f32 [B], top_ids int32 [B, 8], top_lp f32 [B, 8]) on the
+        device; row b's setting is top_n[b] (an int applies to every row).  Entries a row does not produce keep their fill (token -1, lp NaN,
+        top (-2, NaN))."""
+        B, n = logits.shape
+        tn = [int(x) for x in (top_n if isinstance(top_n, (list, tuple)) else [top_n] * B)]
+        toks = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        lp = torch.full((B,), float("nan"), dtype=torch.float32, device=self.device)
+        ti = torch.full((B, LPR.MAX_TOP), -2, dtype=torch.int32, device=self.device)
+        tv = torch.full((B, LPR.MAX_TOP), float("nan"), dtype=torch.float32, device=self.device)
+        st = (C.c_uint32 * B)(*[int(x) for x in (streams if streams is not None else [0] * B)])
+        steps_d = torch.tensor(list(steps) if steps is not None else [0] * B, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.gvl_op_select_logprobs(self.ctx, _ptr(logits.contiguous()), n, B, int(bool(do_sample)), float(temperature), int(top_k or 0),
+                                                  float(top_p or 0.0), int(seed) & (2 ** 64 - 1), st, _ptr(steps_d), (C.c_int * B)(*tn), _ptr(toks),
+                                                  _ptr(lp), _ptr(ti), _ptr(tv), self.stream), "gvl_op_select_logprobs")
+        return toks, lp, ti, tv
 
     def op_dgemm(self, W, x, bias=None):
         """x bf16 [B, K] (B <= 16) -> y f32 [B, N]: the skinny MFMA decode GEMM."""

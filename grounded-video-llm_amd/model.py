@@ -20,6 +20,7 @@ import torch
 
 from . import dist as gdist
 from . import logits as LP
+from . import logprobs as LPR
 from . import prompts as P
 from . import weights as Wt
 from .engine import Engine, TowerGeometry
@@ -250,6 +251,14 @@ class LLAVA_NEXT_VIDEO:
         self.engine.set_logits_processors(*(LP.OFF if beams else procs).args())
         return procs
 
+    def _select_logprobs(self, kw) -> "LPR.Options":
+        """return_dict_in_generate / output_scores / top_logprobs (logprobs.py; raises its ValueErrors).  Sets the engine's default on EVERY generate
+        call -- the call's setting, off for beam search (its scores come from beam.py) -- so nothing carries over from one call to the next."""
+        opts = LPR.resolve(kw)
+        beams = kw.get("num_beams", 1) not in (1, None)
+        self.engine.set_logprobs(-1 if beams else opts.top_n)
+        return opts
+
     def _select_tokens(self, kw):
         """HF generate's token selection for the kwargs the reference forwards (inference.py:170-176 -> llava_next_video.py:655-661):
         greedy, or temperature -> top-k (HF default 50) -> top-p sampling on the device; `seed` (extra) makes a run reproducible,
@@ -275,10 +284,12 @@ class LLAVA_NEXT_VIDEO:
         return int(samples["spatial_pixel_values"].shape[1]) * self.engine.tokens_per_seg
 
     @torch.inference_mode()
-    def generate(self, samples, **generate_kwargs) -> List[str]:
+    def generate(self, samples, **generate_kwargs):
         """The reference's generate(samples, **generate_kwargs).  Besides greedy / sampling / beam search it honours HF's repetition_penalty,
         no_repeat_ngram_size and min_new_tokens / min_length (logits.py; applied on the device to the generated ids only, as HF does for an
-        inputs_embeds prompt).  Other HF logits processors (bad_words_ids, sequence_bias, suppress_tokens, ...) are not supported and ignored."""
+        inputs_embeds prompt).  Other HF logits processors (bad_words_ids, sequence_bias, suppress_tokens, ...) are not supported and ignored.
+        return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
+        log-probabilities; logprobs.py) instead of the list of texts."""
         if any(v == "text" for v in samples.get("video_ids", [])):
             # prepare_multimodal_inputs' `video_ids == 'text'` branch (llava_next_video.py:583-586) is a TRAINING device (dummy visual
             # rows appended with mask 0 so FSDP sees every parameter); the reference's inference never produces it.  forward() handles it.
@@ -286,11 +297,13 @@ class LLAVA_NEXT_VIDEO:
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
+        opts = self._select_logprobs(generate_kwargs)
         procs = self._select_processors(generate_kwargs, LP.padded_embed_len(ids_arr.shape[1], self._n_visual(samples)))
         self._select_tokens(generate_kwargs)
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
         feats = self.encode_images(samples)
         k = generate_kwargs.get("num_beams", 1) or 1
+        lps, beam_scores = None, None
         if k > 1:                                         # HF beam search (do_sample=False), one sample at a time
             sample = None
             if generate_kwargs.get("do_sample", False):      # beam-sample (HF _beam_sample): the warpers' arguments as generate() takes them; one generator per call
@@ -305,24 +318,32 @@ class LLAVA_NEXT_VIDEO:
                 gen = torch.Generator(device=self.engine.device)
                 gen.manual_seed(int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
                 sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen)
+            scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs)
+                                              processors=procs, with_scores=scored)
                        for b in range(ids_arr.shape[0])]
+            if scored:
+                lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
+                out_ids = [r[0] for r in out_ids]
+        elif opts.top_n >= 0:
+            out_ids, lps = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs, logprobs=opts.top_n)
         else:
             out_ids = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs)
-        texts = self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)
-        return [t.strip() for t in texts]
+        texts = [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
+        if not opts.return_dict:
+            return texts
+        return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps, beam_scores)
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
-                          sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None) -> List[int]:
+                          sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False):
         """generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
         teacher-forced batched decode step per token (gvl_decode_step_logits_batch: one stream of the weights for the k beams); log-softmax / top-2k of the step run on the device (torch), the bookkeeping on
         the host.  processors: HF's logits processors, applied by gvl_op_logits_process to every step's log-softmax rows before the beam scores
         are added (HF _beam_search / _beam_sample); the beams' own sequences select their tokens without them (their raw logits are what the
-        steps return)."""
+        steps return).  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them."""
         from . import beam as B
         eng = self.engine
         gi = eng.decode_group_info()                     # which group sizes ONE batched step takes: asked from the library, not restated here
@@ -339,6 +360,7 @@ class LLAVA_NEXT_VIDEO:
                 return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
         try:
             eng.seq_set_processors(beams[0], *LP.OFF.args())     # the steps must hand back raw logits (clones copy this setting)
+            eng.seq_set_logprobs(beams[0], -1)                   # the scores come from the host rows (beam.py)
             first = eng.prefill(beams[0], emb, want_logits=True)
 
             def step(parents: List[int], toks: List[int]) -> torch.Tensor:
@@ -360,7 +382,7 @@ class LLAVA_NEXT_VIDEO:
                     return eng.decode_step_logits_batch(beams, toks)        # the k beams share ONE stream of the weights
                 return torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(beams, toks)])
 
-            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process)
+            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process, with_scores=with_scores)
         finally:
             for s_ in set(x for x in list(beams) + fresh if x is not None):
                 try:
@@ -369,11 +391,12 @@ class LLAVA_NEXT_VIDEO:
                     pass
 
     @torch.inference_mode()
-    def generate_shared(self, samples, prompts: Sequence[str], **generate_kwargs) -> List[str]:
+    def generate_shared(self, samples, prompts: Sequence[str], **generate_kwargs):
         """Several prompts about ONE video.  The reference's inference.py calls generate() once per prompt (grounding / QA /
         referring, inference.py:178-182) and re-runs both vision towers every time; here the video is encoded once and the prompts
         are prefilled and decoded together.  Texts are identical to one generate() call per prompt (batch-invariant kernels) -- the logits
-        processors included: each prompt gets its own (its min_length is lowered by its own embedding length, as its own reference call would)."""
+        processors included: each prompt gets its own (its min_length is lowered by its own embedding length, as its own reference call would).
+        return_dict_in_generate / output_scores / top_logprobs as in generate()."""
         if samples["spatial_pixel_values"].shape[0] != 1:
             raise ValueError("generate_shared takes the pixel tensors of one video")
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
@@ -382,21 +405,27 @@ class LLAVA_NEXT_VIDEO:
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
         rows = [[int(t) for t, m in zip(ids_arr[i], mask[i]) if m] for i in range(len(prompts))]
         n_vis = self._n_visual(samples)
+        opts = self._select_logprobs(generate_kwargs)
         self._select_processors(generate_kwargs, LP.padded_embed_len(len(rows[0]), n_vis) if rows else 0)
         self._select_tokens(generate_kwargs)
         procs = [LP.resolve(generate_kwargs, getattr(self.tokenizer, "eos_token_id", None), LP.padded_embed_len(len(r), n_vis)) for r in rows]
         feats = self.encode_images(samples)
-        out_ids = self._generate_shared_prefix(rows, feats[0], max_new, procs)
-        if out_ids is None:                              # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
-            out_ids = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs)
-        return [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
+        want = opts.top_n if opts.top_n >= 0 else None
+        res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want)
+        if res is None:                                  # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
+            res = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs, logprobs=want)
+        out_ids, lps = res if want is not None else (res, None)
+        texts = [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
+        if not opts.return_dict:
+            return texts
+        return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps)
 
     def _generate_shared_prefix(self, rows: List[List[int]], vis: torch.Tensor, max_new: int,
-                                processors: Optional[List["LP.Processors"]] = None) -> Optional[List[List[int]]]:
+                                processors: Optional[List["LP.Processors"]] = None, logprobs: Optional[int] = None):
         """Prompts about one video share the system prompt and the visual tokens: the common prefix (rounded down to 128 tokens = whole KV pages AND
         whole query blocks, so that every later row is computed exactly as in a full prefill) is prefilled ONCE; every prompt forks it
         (gvl_seq_fork: pages referenced, not copied) and prefills only its own tail (gvl_prefill_extend); the answers are decoded together.
-        Ids are bit-identical to one full prefill per prompt."""
+        Ids are bit-identical to one full prefill per prompt.  logprobs: as in generate_ids (then (ids, lps) is returned)."""
         eng = self.engine
         self.last_shared_prefix = 0                      # tokens prefilled once for all prompts in the last generate_shared call (0 = not shared)
         if len(rows) < 2:
@@ -430,8 +459,13 @@ class LLAVA_NEXT_VIDEO:
                 seqs.append(eng.seq_fork(base, prefix, min(e.shape[0] + max_new, self.geo.max_seq)))
                 if processors is not None:
                     eng.seq_set_processors(seqs[-1], *processors[i].args())
+                if logprobs is not None:
+                    eng.seq_set_logprobs(seqs[-1], logprobs)
                 eng.prefill_extend(seqs[-1], e[prefix:])
-            return eng.decode_greedy_batch(seqs, max_new, eos)
+            got = eng.decode_greedy_batch(seqs, max_new, eos)
+            if logprobs is None:
+                return got
+            return got, [eng.seq_read_logprobs(s_, 0, len(g), top=logprobs > 0) for s_, g in zip(seqs, got)]
         finally:
             for s_ in seqs:
                 eng.seq_free(s_)
@@ -472,16 +506,18 @@ class LLAVA_NEXT_VIDEO:
 
     __call__ = forward
 
-    def generate_ids(self, ids_arr, mask, feats, max_new: int, processors=None) -> List[List[int]]:
+    def generate_ids(self, ids_arr, mask, feats, max_new: int, processors=None, logprobs: Optional[int] = None):
         """Greedy / sampled ids of every row.  processors: one logits.Processors for all rows, a list with one per row, or None (the engine's
-        default, set_logits_processors)."""
+        default, set_logits_processors).  logprobs: None = the ids only; -1 .. 8 = every row's gvl_seq_set_logprobs setting, and the return value
+        is (ids, lps) with lps[i] = (lp, top) of row i as Engine.seq_read_logprobs reads them back before the sequence is freed."""
         eos = getattr(self.tokenizer, "eos_token_id", None)
         eng = self.engine
         if processors is not None and not isinstance(processors, (list, tuple)):
             processors = [processors] * ids_arr.shape[0]
         if ids_arr.shape[0] == 1:
             row = [int(t) for t, m in zip(ids_arr[0], mask[0]) if m]
-            return [eng.generate_ids(eng.splice(row, feats[0]), max_new, eos, processors=None if processors is None else processors[0])]
+            got = eng.generate_ids(eng.splice(row, feats[0]), max_new, eos, processors=None if processors is None else processors[0], logprobs=logprobs)
+            return [got] if logprobs is None else ([got[0]], [got[1]])
         # bs > 1 (the reference left-pads the batch, llava_next_video.py:622-647): every sample keeps its own paged KV and its
         # un-padded length -- identical maths to the masked left-padded batch.  Prefill runs over the packed rows of the batch
         # (gvl_prefill_varlen) and the greedy decode of the whole batch runs together (gvl_decode_greedy_batch: one weight stream
@@ -489,6 +525,7 @@ class LLAVA_NEXT_VIDEO:
         # The KV pool bounds how many samples are resident at once: the batch is processed in as many groups as it takes.
         from .lib import GvlError, ERR_OOM
         out: List[List[int]] = []
+        lps = []
         b, n = 0, ids_arr.shape[0]
         while b < n:
             seqs, embs = [], []
@@ -505,14 +542,19 @@ class LLAVA_NEXT_VIDEO:
                         raise
                     if processors is not None:
                         eng.seq_set_processors(seqs[-1], *processors[i].args())
+                    if logprobs is not None:
+                        eng.seq_set_logprobs(seqs[-1], logprobs)
                     embs.append(emb)
                 eng.prefill_batch(seqs, embs)
-                out += eng.decode_greedy_batch(seqs, max_new, eos)
+                got = eng.decode_greedy_batch(seqs, max_new, eos)
+                if logprobs is not None:
+                    lps += [eng.seq_read_logprobs(s_, 0, len(g), top=logprobs > 0) for s_, g in zip(seqs, got)]
+                out += got
             finally:
                 for seq in seqs:
                     eng.seq_free(seq)
             b += len(seqs)
-        return out
+        return out if logprobs is None else (out, lps)
 
 
 BASE_VOCAB = {"phi3.5": 32064, "llama3": 128256, "vicuna": 32000}     # tokenizer sizes before reset_embeddings [ext]

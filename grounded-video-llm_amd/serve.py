@@ -33,6 +33,7 @@ class _Request:
     ids: List[int] = field(default_factory=list)
     n_gen: int = 0               # tokens generated on the device so far (>= len(ids) once eos was seen)
     processors: object = None    # logits.Processors of this request (None: the engine's default)
+    logprobs: Optional[int] = None   # gvl_seq_set_logprobs setting of this request (None: the engine's default, not read back)
 
 
 class ClipScheduler:
@@ -46,25 +47,37 @@ class ClipScheduler:
         self.queue: Deque[_Request] = deque()
         self.active: List[_Request] = []
         self.done: Dict[int, List[int]] = {}
+        self.done_logprobs: Dict[int, tuple] = {}    # rid -> (lp, top) of a finished request that asked for them (logprobs())
         self._next = 0
         self.stats = {"prefill_calls": 0, "decode_chunks": 0, "decode_seq_steps": 0, "wasted_seq_steps": 0, "max_concurrent": 0}
 
     # ---- public ------------------------------------------------------------------------------------------
     def submit(self, embeds, max_new_tokens: int, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-               min_new_tokens: Optional[int] = None) -> int:
+               min_new_tokens: Optional[int] = None, logprobs: Optional[int] = None) -> int:
         """Queue one request.  repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors for THIS request (HF's validation;
         applied on the device to its generated ids; min_new_tokens needs the scheduler's eos id).  Requests with different settings share one
-        decode group.  None for all three: the sequence keeps the engine's default (Engine.set_logits_processors)."""
+        decode group.  None for all three: the sequence keeps the engine's default (Engine.set_logits_processors).
+        logprobs: 0 = the log-probability of every generated id, 1 .. 8 = also its top N alternatives (Engine.seq_set_logprobs); read back
+        with logprobs(rid) once the request finished."""
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
+            raise ValueError(f"logprobs must be None or an integer in 0 .. 8, not {logprobs!r}")
         procs = None
         if repetition_penalty is not None or no_repeat_ngram_size is not None or min_new_tokens is not None:
             from . import logits as LP
             procs = LP.resolve(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens), self.eos)
-        r = _Request(self._next, embeds, int(max_new_tokens), processors=procs)
+        r = _Request(self._next, embeds, int(max_new_tokens), processors=procs, logprobs=logprobs)
         self._next += 1
         self.queue.append(r)
         return r.rid
+
+    def logprobs(self, rid: int):
+        """(lp, top) of a finished request submitted with logprobs: lp[i] = the log-probability of its i-th id, top[i] = its top N (id,
+        log-probability) pairs (None for logprobs=0); truncated exactly like its ids."""
+        if rid not in self.done_logprobs:
+            raise KeyError(f"request {rid}: not finished, or submitted without logprobs")
+        return self.done_logprobs[rid]
 
     def pending(self) -> int:
         return len(self.queue) + len(self.active)
@@ -111,9 +124,12 @@ class ClipScheduler:
                 if getattr(e, "status", 0) == L.ERR_OOM:     # KV pages exhausted: wait for a retirement (FIFO, no overtaking)
                     break
                 raise
-            if r.processors is not None:
+            if r.processors is not None or r.logprobs is not None:
                 try:
-                    self.eng.seq_set_processors(r.seq, *r.processors.args())
+                    if r.processors is not None:
+                        self.eng.seq_set_processors(r.seq, *r.processors.args())
+                    if r.logprobs is not None:
+                        self.eng.seq_set_logprobs(r.seq, r.logprobs)
                 except Exception:
                     self.eng.seq_free(r.seq)
                     raise
@@ -142,6 +158,8 @@ class ClipScheduler:
                     stop = True
                     break
             if stop or len(r.ids) >= r.max_new:
+                if r.logprobs is not None:                   # before the slot is freed: its lists are reused by the next sequence
+                    self.done_logprobs[r.rid] = self.eng.seq_read_logprobs(r.seq, 0, len(r.ids), top=r.logprobs > 0)
                 self.eng.seq_free(r.seq)                     # seq_read synchronised the stream: no step of r is in flight
                 self.done[r.rid] = r.ids
                 finished.append(r.rid)

@@ -180,6 +180,23 @@ int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, 
  * empty: its generation count restarts at 0).  Errors: penalty not > 0 (NaN included), ngram < 0, min_new < 0. */
 int gvl_set_logits_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, int eos_id);
 int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, int min_new, int eos_id);
+/* Log-probabilities of the selected tokens, computed on the device by the token-selection kernel itself (prefill's first token,
+ * gvl_decode_greedy*, gvl_decode_steps; greedy and sampling alike; graph-replayed steps included).  The distribution is the one the token
+ * was selected from: greedy, log_softmax of the row after the logits processors, (s_tok - m) - log(sum_i exp(s_i - m)); sampling, the
+ * warped distribution HF samples from (temperature -> top-k -> top-p, everything outside the final kept set at -inf),
+ * (s_tok - m) / T - log(sum_kept exp((s_i - m) / T)).  fp32, fixed-order reductions: a row's values do not depend on its decode group
+ * or path.  top_n: -1 = off (the default; the selection launch is then exactly the one without log-probabilities), 0 = the selected
+ * token's only, 1 .. 8 = also the top_n best finite (kept) entries of the same distribution, by value descending,
+ * lower id first on ties, padded with (-1, -inf) when fewer exist.  The selected token is the same whatever top_n is.
+ * gvl_set_logprobs sets the default of sequences allocated AFTER the call; gvl_seq_set_logprobs one live sequence (fork / clone copy
+ * it).  The first setting that needs them allocates the per-slot device lists (top lists: ~134 MB).  Errors: top_n outside -1 .. 8.
+ * gvl_seq_read_logprobs follows gvl_seq_read: entries first .. min(n_gen, first + cap) - 1 to host arrays lp [cap] and top_ids /
+ * top_lp [cap][8] (slots >= the sequence's top_n hold (-1, -inf)); any of the three may be null; synchronises
+ * `stream`.  Asking for lp of a sequence with top_n -1, or for top lists with top_n < 1, is GVL_ERR_STATE. */
+int gvl_set_logprobs(gvl_ctx* ctx, int top_n);
+int gvl_seq_set_logprobs(gvl_ctx* ctx, int seq_id, int top_n);
+int gvl_seq_read_logprobs(gvl_ctx* ctx, int seq_id, int first, int cap, float* lp_host, int32_t* top_ids_host, float* top_lp_host, int* n_gen,
+                          void* stream);
 /* Prefill of n_seqs sequences together, seq_lens[i] tokens each (ragged: prompts differ in length; the reference left-pads and
  * masks, llava_next_video.py:622-647 -- here the rows are packed back to back, no padding).  Groups of 4 / 2 / 1 sequences whose
  * rows fit cfg.max_prefill: the decoder GEMMs run over all rows of a group at once (better tile fill); RoPE / KV append / causal
@@ -350,6 +367,12 @@ int gvl_op_sample(gvl_ctx* ctx, const float* logits, int n, int batch, float tem
  * min(hist_stride, 8192)); per-row parameters are host arrays with gvl_set_logits_processors' meaning.  batch <= 16. */
 int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
                           const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, void* stream);
+/* Token selection with log-probabilities on its own (operator tests): greedy (do_sample = 0; streams / steps_dev may be null) or
+ * gvl_op_sample's draw; row b with top_n[b] >= 0 (host array) stores its token's log-probability at lp_dev[b], and for top_n[b] >= 1
+ * its top list at top_ids_dev / top_lp_dev [b * 8 ..) (gvl_set_logprobs' meaning).  batch <= 16. */
+int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, int do_sample, float temperature, int top_k, float top_p,
+                           uint64_t seed, const uint32_t* streams, const int32_t* steps_dev, const int* top_n, int32_t* tokens_dev,
+                           float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, void* stream);
 /* y[b][N] = W[N,K] x[b][K] (+bias) for b < batch <= 16 -- the decode projections as ONE skinny MFMA GEMM (the weight stream is
  * read once for all sequences; K % 256 == 0).  x bf16 [batch][K], y f32 [batch][N]. */
 int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch,

@@ -60,6 +60,7 @@ def parse_args(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=None, help="HF RepetitionPenaltyLogitsProcessor on the generated ids (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=None, help="HF NoRepeatNGramLogitsProcessor on the generated ids (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=None, help="HF MinNewTokensLengthLogitsProcessor: no eos before this many new ids")
+    p.add_argument("--output_scores", action="store_true", help="print each answer's mean token log-prob and, for the grounding answer, every temporal token's probability")
     p.add_argument("--share_visual", type=_bool, default=False, help="encode the video ONCE for the three prompts and batch them (the reference re-encodes per prompt)")
     p.add_argument("--synthetic", action="store_true", help="seeded random weights / frames / tokenizer (offline image)")
     p.add_argument("--synthetic_scale", type=str, default="small", choices=["small", "full"])
@@ -135,20 +136,28 @@ def main(argv=None):
     for name in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"):     # forwarded only when given, like any other HF generate kwarg
         if getattr(args, name) is not None:
             kw[name] = getattr(args, name)
-    outs = {}
+    if args.output_scores:
+        kw.update(return_dict_in_generate=True, output_scores=True)
+    outs, scored = {}, {}
     modes = ("grounding", "qa", "referring")
     if args.share_visual:
         # one pre-processing + one vision encode for the three prompts (the reference re-encodes the video per prompt)
         per_mode = [create_inputs(args, mode, frames, duration, model.engine) for mode in modes[:1]]
         prompts = [per_mode[0]["prompts"][0]] + [create_prompt(args, mode, duration) for mode in modes[1:]]
-        texts = model.generate_shared(per_mode[0], prompts, **kw)
+        res = model.generate_shared(per_mode[0], prompts, **kw)
+        texts = res.texts if args.output_scores else res
         outs = {mode: (p, t) for mode, p, t in zip(modes, prompts, texts)}
+        if args.output_scores:
+            scored = {mode: (res.sequences[i], res.transition_scores[i]) for i, mode in enumerate(modes)}
     else:
         for i, mode in enumerate(modes):
             samples = create_inputs(args, mode, frames, duration, model.engine)
             # one sampler seed per call (HF's generator state advances between the reference's three generate() calls; the same seed
             # for all three would make their draws perfectly correlated)
-            outs[mode] = (samples["prompts"][0], model.generate(samples, **{**kw, "seed": args.seed + i})[0])
+            res = model.generate(samples, **{**kw, "seed": args.seed + i})
+            outs[mode] = (samples["prompts"][0], (res.texts if args.output_scores else res)[0])
+            if args.output_scores:
+                scored[mode] = (res.sequences[0], res.transition_scores[0])
     print("\n******grounding example******")
     print(outs["grounding"][0])
     print(P.parse_time_interval(outs["grounding"][1], duration, args.num_temporal_tokens, args.llm if args.llm != "vicuna" else "llama3"))
@@ -158,6 +167,23 @@ def main(argv=None):
     print("\n******videoqa example******")
     print(outs["qa"][0])
     print(outs["qa"][1])
+    if args.output_scores:
+        print_scores(model.tokenizer, scored)
+
+
+def print_scores(tokenizer, scored):
+    """--output_scores: the mean log-probability of every answer's tokens, and each temporal token <k> of the grounding answer with its probability."""
+    import math
+    import re
+    print("\n******scores******")
+    for mode, (ids, lps) in scored.items():
+        mean = sum(lps) / len(lps) if lps else float("nan")
+        print(f"{mode}: {len(ids)} tokens, mean log-prob {mean:.4f}")
+    ids, lps = scored["grounding"]
+    for t, lp in zip(ids, lps):
+        text = tokenizer.batch_decode([[t]], skip_special_tokens=False)[0].strip()
+        if re.fullmatch(r"<\d+>", text):
+            print(f"  {text}  p = {math.exp(lp):.4f}")
 
 
 if __name__ == "__main__":
