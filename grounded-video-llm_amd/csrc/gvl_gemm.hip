@@ -414,8 +414,8 @@ void gvl_gemm_set_a4(int v) { g_a4_mode.store(v, std::memory_order_relaxed); }
 // (profiles/r06_gemm4_lab_model.txt; tools/gemm4_lab.py 82,86,88 model):
 //   pipelined 4-wave (88): the epilogues with real VALU / LDS work behind the bf16 rounding -- erf-GELU (98: +5 % over the 8-wave kernel, +10 % over the plain 4-wave
 //                          one), SwiGLU (67: +4.5 %), residual + row statistics (136: +3 ... +7 %; 184: +1 ... +5 %) -- that work rides in the next tile's MFMA gaps;
-//   plain 4-wave (86):     the store-only epilogues (64, 0, ...: +2 ... +4 %; pipelining them buys nothing: what remains exposed either way is the accumulator drain);
 //                          bias alone (32: +2 %, its slice read once per tile into dead fragment registers);
+//   plain 4-wave (86):     the store-only epilogues (64, 0, 3, 8, 128: +2 ... +4 %; pipelining them buys nothing: what remains exposed either way is the accumulator drain);
 //   8-wave ping-pong (82): CLIP's quick-GELU (33: the 4-wave forms lose 1 ... 2 % there), the f32-output epilogues and everything the 4-wave kernels do not serve.
 static int big_form_preferred(int epi) {
   switch (epi) {
@@ -467,7 +467,8 @@ static int launch_pp(const GemmArgs& a_in, hipStream_t st) {
   // Rasterisation band: the 32 workgroups of an XCD walk a band of GM tile rows column by column, k-tile by k-tile in lock-step (an 8 x 4 patch of tiles).
   // MEASURED AND NOT ADOPTED (round 5, profiles/r05_ab_gemm_band.json + the PMC passes): GM = 32 / tile columns for narrow matrices (N = 1408: 5 rows x 6
   // columns, so that an A slice enters the XCD's L2 once) -- +0.4 % clips/s, inside the run-to-run spread, while the family's fabric-side traffic ROSE from
-  // 193 to 231 GB per clip (the W panel is re-read per band, and there are 154 bands instead of 96).  8 rows stay; gvl_debug_set("gemm_band") varies it.
+  // 193 to 231 GB per clip (the W panel is re-read per band, and there are 154 bands instead of 96).  The default is GVL_GEMM_BAND = 4 tile rows since round 6
+  // (gvl_internal.h: 8 -> 4 measured -2.1 % per step with the 4-wave kernels); gvl_debug_set("gemm_band") varies it.
   if (a.band <= 0) a.band = GVL_GEMM_BAND;
   if (const int bo = g_band_override.load(std::memory_order_relaxed); bo > 0) a.band = bo;
   static const bool no_persist = gvl_lab_env("GVL_GEMM_NO_PERSIST") != nullptr;                // A/B only
@@ -538,7 +539,8 @@ int gvl_launch_gemm(const GemmArgs& a_in, hipStream_t st) {
     // 477.7 us (InternVideo2, bias) -- profiles/r05_patch_gemm_floor.txt
     if (cfg == 21 && a.K >= 512 && t256 >= 512) cfg = 80;
   }
-  if ((cfg == 80 || cfg == 82 || (cfg >= 84 && cfg <= 87)) && ((size_t)a.N * a.ldw * 2 >= (1ull << 32) || (size_t)a.M * a.lda * 2 >= (1ull << 32))) cfg = 21;   // 32-bit DMA offsets
+  // 32-bit DMA offsets: every 256 x 256 form (80, 82, 84 ... 88 -- an explicit 85 / 88 included: both end in launch_pp) hands an operand of 4 GiB or more to cfg 21
+  if ((cfg == 80 || cfg == 82 || (cfg >= 84 && cfg <= 88)) && ((size_t)a.N * a.ldw * 2 >= (1ull << 32) || (size_t)a.M * a.lda * 2 >= (1ull << 32))) cfg = 21;
   const int epi = (a.act & 3) | ((a.out_f32 ? 1 : 0) << 2) | ((a.resid ? 1 : 0) << 3) | ((a.gamma ? 1 : 0) << 4) | ((a.bias ? 1 : 0) << 5) |
                   ((a.rowscale ? 1 : 0) << 6) | ((a.rowsq ? 1 : 0) << 7);
   if (a.rowsq && (a.N % 64 != 0 || a.out_f32 || a.act == GVL_ACT_SILU_MUL || a.rowsq_ld < a.N / 64 || a.grp_rows)) return -1;

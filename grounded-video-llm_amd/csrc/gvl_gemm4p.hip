@@ -6,10 +6,13 @@
 // VGPRs: the value every fused epilogue of the library is defined on), and everything behind it -- transposition through a private LDS staging area, residual add,
 // row sums of squares, whole-row stores -- runs as fillers in the MFMA gaps of the workgroup's NEXT tile (tools/gen_gemm4p.py -> gvl_gemm4p_loop.inc; a flush
 // statement finishes the last tile).  The statements take fixed-register operand blocks (v[0:15], s[36:51], s[52:67]) and the P registers v[32:159] as in / out
-// operands, so the compiler keeps them alive between tiles by construction.
+// operands, so the compiler keeps them alive between tiles by construction.  A statement declares every register it writes: P is in / out of the flush statement
+// too (the deferred program transposes it in place), and the parameter block is in / out for the row-statistics epilogues, whose program collects the statistics in
+// v12..v15 (GVL_A4P_VP_OUT_E* / GVL_A4P_VP_IN_E*, generated: gvl_gemm4p_operands.inc) -- tests/test_gemm4_loop_gen.py holds every instruction of the streams against these lists.
 // Reference shapes: models/internvideo2.py:587,603,631-634; models/modeling_phi3.py:459-464,659-663.
 #include "gvl_gemm_epi.h"
 #include "gvl_gemm4p_loop.inc"
+#include "gvl_gemm4p_operands.inc"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -32,10 +35,10 @@ struct SBlock {                      // 16 wave-uniform dwords, s[N : N + 15], a
 
 #define GVL_A4P_P_OUT(P) "={v[32:47]}"(P.p[0]), "={v[48:63]}"(P.p[1]), "={v[64:79]}"(P.p[2]), "={v[80:95]}"(P.p[3]), "={v[96:111]}"(P.p[4]), "={v[112:127]}"(P.p[5]), "={v[128:143]}"(P.p[6]), "={v[144:159]}"(P.p[7])
 #define GVL_A4P_P_INOUT(P) "+{v[32:47]}"(P.p[0]), "+{v[48:63]}"(P.p[1]), "+{v[64:79]}"(P.p[2]), "+{v[80:95]}"(P.p[3]), "+{v[96:111]}"(P.p[4]), "+{v[112:127]}"(P.p[5]), "+{v[128:143]}"(P.p[6]), "+{v[144:159]}"(P.p[7])
-#define GVL_A4P_P_IN(P) "{v[32:47]}"(P.p[0]), "{v[48:63]}"(P.p[1]), "{v[64:79]}"(P.p[2]), "{v[80:95]}"(P.p[3]), "{v[96:111]}"(P.p[4]), "{v[112:127]}"(P.p[5]), "{v[128:143]}"(P.p[6]), "{v[144:159]}"(P.p[7])
 // the scalar blocks travel as 4-dword tuples (the width of a buffer resource: the one SGPR tuple class hipcc copies around without detours through VGPRs)
-#define GVL_A4P_IN(vp, sa, sb) "{v[0:15]}"(vp), "{s[36:39]}"(sa.q[0]), "{s[40:43]}"(sa.q[1]), "{s[44:47]}"(sa.q[2]), "{s[48:51]}"(sa.q[3]), \
-                               "{s[52:55]}"(sb.q[0]), "{s[56:59]}"(sb.q[1]), "{s[60:63]}"(sb.q[2]), "{s[64:67]}"(sb.q[3]), "{s[68:71]}"(sb.bias)
+#define GVL_A4P_S_IN(sa, sb) "{s[36:39]}"(sa.q[0]), "{s[40:43]}"(sa.q[1]), "{s[44:47]}"(sa.q[2]), "{s[48:51]}"(sa.q[3]), \
+                             "{s[52:55]}"(sb.q[0]), "{s[56:59]}"(sb.q[1]), "{s[60:63]}"(sb.q[2]), "{s[64:67]}"(sb.q[3]), "{s[68:71]}"(sb.bias)
+#define GVL_A4P_IN(vp, sa, sb) "{v[0:15]}"(vp), GVL_A4P_S_IN(sa, sb)
 #define GVL_A4P_CLOB "memory", "scc", GVL_A4P_CLOBBER_SGPRS, "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167", "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175", \
   "v176", "v177", "v178", "v179", "v180", "v181", "v182", "v183", "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", \
   "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223", \
@@ -49,11 +52,12 @@ template <int EPI> struct A4pAsm;
     static __device__ __forceinline__ void tile0(PRegs& P, const u32x16_t& vp, const SBlock& sa, const SBlock& sb) {                                 \
       asm volatile(GVL_A4P_TILE0_E##E : GVL_A4P_P_OUT(P) : GVL_A4P_IN(vp, sa, sb) : GVL_A4P_CLOB, GVL_A4P_CLOBBER_AGPRS);                               \
     }                                                                                                                                                    \
-    static __device__ __forceinline__ void tile(PRegs& P, const u32x16_t& vp, const SBlock& sa, const SBlock& sb) {                                  \
-      asm volatile(GVL_A4P_TILE_E##E : GVL_A4P_P_INOUT(P) : GVL_A4P_IN(vp, sa, sb) : GVL_A4P_CLOB, GVL_A4P_CLOBBER_AGPRS);                              \
+    static __device__ __forceinline__ void tile(PRegs& P, u32x16_t& vp, const SBlock& sa, const SBlock& sb) {                                        \
+      asm volatile(GVL_A4P_TILE_E##E : GVL_A4P_P_INOUT(P) GVL_A4P_VP_OUT_E##E(vp) : GVL_A4P_VP_IN_E##E(vp) GVL_A4P_S_IN(sa, sb)                          \
+                   : GVL_A4P_CLOB, GVL_A4P_CLOBBER_AGPRS);                                                                                               \
     }                                                                                                                                                    \
-    static __device__ __forceinline__ void flush(const PRegs& P, const u32x16_t& vp, const SBlock& sa, const SBlock& sb) {                           \
-      asm volatile(GVL_A4P_FLUSH_E##E : : GVL_A4P_P_IN(P), GVL_A4P_IN(vp, sa, sb) : GVL_A4P_CLOB);                                                     \
+    static __device__ __forceinline__ void flush(PRegs& P, u32x16_t& vp, const SBlock& sa, const SBlock& sb) {                                       \
+      asm volatile(GVL_A4P_FLUSH_E##E : GVL_A4P_P_INOUT(P) GVL_A4P_VP_OUT_E##E(vp) : GVL_A4P_VP_IN_E##E(vp) GVL_A4P_S_IN(sa, sb) : GVL_A4P_CLOB);        \
     }                                                                                                                                                    \
   };
 GVL_A4P_EPI_LIST(GVL_A4P_DEF)

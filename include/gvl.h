@@ -301,11 +301,12 @@ int gvl_prof_read(gvl_ctx* ctx, int category, double* total_ms, int64_t* launche
  *                      (row statistics from the producing GEMM's epilogue, norm weight folded into the consuming GEMM's weight, row scale in its epilogue); 0: the
  *                      separate norm pass of rounds 1-4.  NOT bit-neutral -- the third stated exception below: two activation roundings of the reference
  *                      (x * rs and the gamma product, both to bf16) are gone and gamma * W is rounded once per weight instead
- *   "gemm_band"        0 (default): the ping-pong GEMM's rasterisation band is 8 tile rows; 1..64: that many rows for every later launch of the PROCESS (A/B only)
- *                      -- bit-identical
+ *   "gemm_band"        0 (default): the rasterisation band of the 256 x 256 GEMM kernels (8-wave ping-pong and both 4-wave forms) is 4 tile rows; 1..64: that many
+ *                      rows for every later launch of the PROCESS (A/B only) -- bit-identical
  *   "gemm_a4"          which form of the 256 x 256 GEMM kernel a launch takes: 1 (default) per fused epilogue, as measured -- the 4-wave kernel with the epilogue
- *                      pipelined into the next tile's main loop (gvl_gemm4p.hip) for erf-GELU / SwiGLU / residual + row statistics, the plain 4-wave kernel
- *                      (gvl_gemm4.hip: accumulators in AGPRs, hand-placed k loop) for store-only epilogues, the 8-wave ping-pong kernel for the rest;
+ *                      pipelined into the next tile's main loop (gvl_gemm4p.hip) for erf-GELU / SwiGLU / residual + row statistics / bias alone, the plain
+ *                      4-wave kernel (gvl_gemm4.hip: accumulators in AGPRs, hand-placed k loop) for the store-only epilogues (plain, row scale, SwiGLU without
+ *                      row scale, residual alone, row statistics alone), the 8-wave ping-pong kernel for the rest;
  *                      0: always the 8-wave kernel; 2: the plain 4-wave kernel wherever it serves; 3: the pipelined one wherever it serves.  For every later
  *                      launch of the PROCESS -- bit-identical
  *   "gemm_narrow"      1 (default): the pipelined 4-wave kernel runs a column tile with <= 128 real columns (N = 1408 = 5.5 tile columns: every sixth tile of

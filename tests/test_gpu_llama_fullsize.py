@@ -133,29 +133,31 @@ def _full_depth_vs_reference_golden(llama, name, norm_fused=1):
     # with the fusion switched off (the separate norm passes of rounds 1-4) the OLD caps must still hold -- nothing else moved
     cap, rms_cap = (E2E_FP32PREFIX_CAP, 1.20) if norm_fused else (1.25, 1.15)
     eng.debug_set("norm_fused", norm_fused)
-    name_ = name + ("" if norm_fused else " [norm_fused = 0]")
-    sp = synth.exact_tensor(sd["sp"], (1, n_segs, 3, 336, 336), device=DEV)[0]
-    tp = synth.exact_tensor(sd["tp"], (1, 8 * n_segs, 3, 224, 224), device=DEV)
-    tseg = tp.reshape(1, n_segs, 8, 3, 224, 224).permute(0, 1, 3, 2, 4, 5).flatten(0, 1).contiguous()
-    ms = geo.max_segs
-    vis = torch.cat([eng.encode_segments(sp[i:i + ms], tseg[i:i + ms]) for i in range(0, n_segs, ms)], 0)
-    assert vis.shape == (n_segs * L_SEG, 4096)
-    check(vis[None][:, ::st["feats"][0], ::st["feats"][1]], g["feats"], 1e-2, f"{name}: encode_images ({n_segs} segments, {n_segs * L_SEG} visual tokens) vs reference (fp32)")
-    emb = eng.splice(meta["ids"], vis)
-    S = meta["S"]
-    assert emb.shape[0] == S
-    scale = float(np.abs(g["logits_rows"]).max())
-    ref_bf = float(np.abs(g["logits_rows_bf16ref"] - g["logits_rows"]).max()) / scale
-    tol = max(1e-2, cap * ref_bf)
-    ls = st["logits"]
-    seq = eng.seq_alloc(S + len(meta["forced"]) + 8)
-    rows = [eng.prefill(seq, emb, want_logits=True).clone()]
-    for i, tok in enumerate(meta["forced"]):
-        lg = eng.decode_step_logits(seq, tok)
-        if (i + 1) % step == 0:
-            rows.append(lg.clone())
-    eng.seq_free(seq)
-    eng.debug_set("norm_fused", 1)
+    try:                                # the engine is module-scoped: a failure in between must not leave the unfused path on for every later test
+        name_ = name + ("" if norm_fused else " [norm_fused = 0]")
+        sp = synth.exact_tensor(sd["sp"], (1, n_segs, 3, 336, 336), device=DEV)[0]
+        tp = synth.exact_tensor(sd["tp"], (1, 8 * n_segs, 3, 224, 224), device=DEV)
+        tseg = tp.reshape(1, n_segs, 8, 3, 224, 224).permute(0, 1, 3, 2, 4, 5).flatten(0, 1).contiguous()
+        ms = geo.max_segs
+        vis = torch.cat([eng.encode_segments(sp[i:i + ms], tseg[i:i + ms]) for i in range(0, n_segs, ms)], 0)
+        assert vis.shape == (n_segs * L_SEG, 4096)
+        check(vis[None][:, ::st["feats"][0], ::st["feats"][1]], g["feats"], 1e-2, f"{name}: encode_images ({n_segs} segments, {n_segs * L_SEG} visual tokens) vs reference (fp32)")
+        emb = eng.splice(meta["ids"], vis)
+        S = meta["S"]
+        assert emb.shape[0] == S
+        scale = float(np.abs(g["logits_rows"]).max())
+        ref_bf = float(np.abs(g["logits_rows_bf16ref"] - g["logits_rows"]).max()) / scale
+        tol = max(1e-2, cap * ref_bf)
+        ls = st["logits"]
+        seq = eng.seq_alloc(S + len(meta["forced"]) + 8)
+        rows = [eng.prefill(seq, emb, want_logits=True).clone()]
+        for i, tok in enumerate(meta["forced"]):
+            lg = eng.decode_step_logits(seq, tok)
+            if (i + 1) % step == 0:
+                rows.append(lg.clone())
+        eng.seq_free(seq)
+    finally:
+        eng.debug_set("norm_fused", 1)
     assert len(rows) == g["logits_rows"].shape[0]
     errs = [float((r[::ls].cpu().double() - torch.as_tensor(g["logits_rows"][i]).double()).abs().max()) / scale for i, r in enumerate(rows)]
     print(f"[parity] {name_} Llama-3-8B 32 L, S={S}: the reference's own bf16 evaluation is {ref_bf:.3e} from its fp32 logits (scale {scale:.3f}); bound {tol:.2e}")

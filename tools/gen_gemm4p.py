@@ -20,7 +20,9 @@ Synchronisation of the deferred program (everything else is plain in-order issue
   * LDS reads (table, gamma, staging read-back) are consumed in a LATER PHASE than they were issued in: every phase of the main loop opens with s_waitcnt lgkmcnt(0)
     (marker PH in the program).  A wave's own ds_write -> ds_read of the staging area needs nothing: LDS operations of one wave execute in order.
   * global loads (residual) are consumed behind the NEXT end-of-phase-2 s_waitcnt vmcnt(0) of the main loop (marker KT).  Stores are never waited for.
-Registers: v0-15 per-lane parameters, v16-31 the compiler's, v32-159 P, v160-233 the main loop, v234-255 the deferred program / drain; s36-67 parameters.
+Registers: v0-15 per-lane parameters (v12-15 double as the row statistics of the deferred program: the block is an in / out operand of those epilogues' statements),
+v16-31 the compiler's, v32-159 P (in / out of every statement that runs the deferred program, the flush included: it transposes in place), v160-233 the main loop,
+v234-255 the deferred program / drain; s36-67 parameters.
 The C++ between two tile statements must not touch v32-v255 / a0-a255 (P and the accumulators live there across statements): tests/test_isa_budget.py audits the ISA.
 """
 import os
@@ -33,6 +35,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ALIGN_LOOP = [f".p2align {os.environ.get('GVL_A4_ALIGN', '6')}"] if os.environ.get("GVL_A4_ALIGN", "6") != "0" else []
 SHIFT = ["s_nop 0"] * int(os.environ.get("GVL_A4_SHIFT", "0"))
 OUT = os.path.join(HERE, "..", "grounded-video-llm_amd", "csrc", "gvl_gemm4p_loop.inc")
+OUT_OPS = os.path.join(HERE, "..", "grounded-video-llm_amd", "csrc", "gvl_gemm4p_operands.inc")     # what the statements WRITE outside their clobber lists, per epilogue
 
 MB, NB = 4, 4
 SLOT = 0x10000
@@ -723,9 +726,22 @@ def render():
     return "\n".join(o)
 
 
+def render_operands():
+    """The per-lane parameter block v[0:15] as an operand of the statements that run the deferred program (TILE, FLUSH): the row statistics are collected in
+    V_SQ = v12..v15 of that block, so for these epilogues it is an in / out operand ("+": the compiler must not count on its value afterwards); for the others it stays
+    an input.  Spliced into the output / input lists of the wrappers (gvl_gemm4p.hip); tests/test_gemm4_loop_gen.py audits every statement against its declaration."""
+    o = ["// GENERATED by tools/gen_gemm4p.py -- do not edit.  Operand declarations that follow from what the generated statements write.", "#pragma once", ""]
+    for e in EPIS:
+        sq = epi_flags(e)["sq"]
+        assert sq == any(f"v_cndmask_b32 v{V_SQ + k}," in ins for k in range(4) for ins in flush_asm(e))
+        o += [f"#define GVL_A4P_VP_OUT_E{e}(vp)" + (', "+{v[0:15]}"(vp)' if sq else ""), f"#define GVL_A4P_VP_IN_E{e}(vp)" + ("" if sq else ' "{v[0:15]}"(vp),')]
+    return "\n".join(o + [""])
+
+
 if __name__ == "__main__":
-    txt = render()
+    files = [(OUT, render()), (OUT_OPS, render_operands())]
     if "--check" in sys.argv:
-        sys.exit(0 if os.path.exists(OUT) and open(OUT).read() == txt else 1)
-    open(OUT, "w").write(txt)
-    print(f"wrote {os.path.normpath(OUT)}: {len(txt.splitlines())} lines")
+        sys.exit(0 if all(os.path.exists(p) and open(p).read() == txt for p, txt in files) else 1)
+    for p, txt in files:
+        open(p, "w").write(txt)
+        print(f"wrote {os.path.normpath(p)}: {len(txt.splitlines())} lines")
