@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "gvl_gemm_epi.h"
+#include "gvl_gemm_plan.h"
 
 // NS = LDS ring slots.  2: k-tile t+1 is requested while t is consumed (compiler-tracked DMA).  3: TWO k-tiles ahead, DMA issued from
 // inline asm with the waits counted by hand (`s_waitcnt vmcnt(NI)` leaves the newest tile in flight): for the planner's remainder /
@@ -402,28 +403,27 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs a, int tile
 #undef PP_BARRIER
 }
 
-// A/B only (gvl_debug_set("gemm_band" / "gemm_a4")): PROCESS-wide by design (documented in gvl.h), result-neutral; atomics because contexts of several host threads may
-// launch while one of them flips a knob
+
+// A/B only (gvl_debug_set("gemm_band" / "gemm_a4" / "gemm_narrow")): PROCESS-wide by design (documented in gvl.h), result-neutral; atomics because contexts of several
+// host threads may launch while one of them flips a knob
 static std::atomic<int> g_band_override{0};
 void gvl_gemm_set_band(int v) { g_band_override.store(v, std::memory_order_relaxed); }
-// Which launches of the 256 x 256 kernel take a 4-wave / AGPR form (gvl_gemm4.hip, gvl_gemm4p.hip) instead of the 8-wave ping-pong: see big_form_preferred and the
-// dispatch in gvl_launch_gemm.  Bit-identical whatever the value (gvl_debug_set("gemm_a4"); process-wide).
+// Which launches of the 256 x 256 kernel take a 4-wave / AGPR form (gvl_gemm4.hip, gvl_gemm4p.hip) instead of the 8-wave ping-pong: GemmKnobs.a4_mode and
+// big_form_preferred (gvl_gemm_plan.h).  Bit-identical whatever the value.
 static std::atomic<int> g_a4_mode{1};
 void gvl_gemm_set_a4(int v) { g_a4_mode.store(v, std::memory_order_relaxed); }
-// Which form of the 256 x 256 kernel an (epilogue) takes when the library chooses (cfg 80), from same-box interleaved runs on the model's shapes
-// (profiles/r06_gemm4_lab_model.txt; tools/gemm4_lab.py 82,86,88 model):
-//   pipelined 4-wave (88): the epilogues with real VALU / LDS work behind the bf16 rounding -- erf-GELU (98: +5 % over the 8-wave kernel, +10 % over the plain 4-wave
-//                          one), SwiGLU (67: +4.5 %), residual + row statistics (136: +3 ... +7 %; 184: +1 ... +5 %) -- that work rides in the next tile's MFMA gaps;
-//                          bias alone (32: +2 %, its slice read once per tile into dead fragment registers);
-//   plain 4-wave (86):     the store-only epilogues (64, 0, 3, 8, 128: +2 ... +4 %; pipelining them buys nothing: what remains exposed either way is the accumulator drain);
-//   8-wave ping-pong (82): CLIP's quick-GELU (33: the 4-wave forms lose 1 ... 2 % there), the f32-output epilogues and everything the 4-wave kernels do not serve.
-static int big_form_preferred(int epi) {
-  switch (epi) {
-    case 98: case 67: case 136: case 184: case 32: return 88;
-    case 64: case 0: case 3: case 8: case 128: return 86;
-    default: return 82;
-  }
+static std::atomic<int> g_narrow{1};
+void gvl_gemm_set_narrow(int v) { g_narrow.store(v, std::memory_order_relaxed); }
+
+// Compute units of the current device (the devices of a node are alike: asked once).  The planner costs a launch in whole CUs and takes this count as it is; the
+// persistent grids of the 256 x 256 kernels take `& ~7`: their tile walk deals the workgroups out to the 8 XCDs in equal shares.
+int gvl_device_cus() {
+  static const int n_cu = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) ? p.multiProcessorCount : 256; }();
+  return n_cu;
 }
+
+static_assert(GVL_EPI_QGELU == GVL_ACT_QUICK_GELU && GVL_EPI_GELU == GVL_ACT_GELU && GVL_EPI_SWIGLU == GVL_ACT_SILU_MUL, "the epilogue code's activation field holds GVL_ACT_*");
+
 // Phi(x) table of the current device (built once per device; blocking upload on first use, outside any timed region after warmup)
 static const float* gelu_table_device() {
   static const float* tabs[64] = {nullptr};
@@ -449,53 +449,33 @@ static const float* gelu_table_device() {
 }
 
 template <int EPI, int STG = 0>
-static int launch_pp(const GemmArgs& a_in, hipStream_t st) {
+static int launch_pp(const GemmArgs& a, hipStream_t st) {
   constexpr int BM = 256, BN = 256, RING = 2 * (BM + BN) * 128;
   constexpr int STGB = (STG && EPI >= 0 && (EPI & 4)) ? 8 * 32 * (128 * 4 + 16) : 0;    // f32 staging: 132 KiB
   constexpr bool TAB = STG && EPI >= 0 && (EPI & 3) == GVL_ACT_GELU;
   constexpr int LDS = (RING > STGB ? RING : STGB) + (STG ? 8 * 128 * 8 : 0) + (TAB ? GELU_TAB_BYTES : 0);   // + bias/gamma scratch + Phi table
   static GvlDevOnce once;
-  static const int n_cu = [] {                      // the devices of a node are alike: asked once
-    hipDeviceProp_t p; int d = 0;
-    return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) ? (p.multiProcessorCount & ~7) : 256;
-  }();
   auto kern = gemm_pp_kernel<BM, BN, EPI, STG>;
   if (gvl_set_max_lds(once, (const void*)kern, LDS)) return -3;
-  GemmArgs a = a_in;
   const int tiles_m = (a.M - a.m_begin + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-  const int tiles = tiles_m * tiles_n;
-  // Rasterisation band: the 32 workgroups of an XCD walk a band of GM tile rows column by column, k-tile by k-tile in lock-step (an 8 x 4 patch of tiles).
-  // MEASURED AND NOT ADOPTED (round 5, profiles/r05_ab_gemm_band.json + the PMC passes): GM = 32 / tile columns for narrow matrices (N = 1408: 5 rows x 6
-  // columns, so that an A slice enters the XCD's L2 once) -- +0.4 % clips/s, inside the run-to-run spread, while the family's fabric-side traffic ROSE from
-  // 193 to 231 GB per clip (the W panel is re-read per band, and there are 154 bands instead of 96).  The default is GVL_GEMM_BAND = 4 tile rows since round 6
-  // (gvl_internal.h: 8 -> 4 measured -2.1 % per step with the 4-wave kernels); gvl_debug_set("gemm_band") varies it.
-  if (a.band <= 0) a.band = GVL_GEMM_BAND;
-  if (const int bo = g_band_override.load(std::memory_order_relaxed); bo > 0) a.band = bo;
+  const int tiles = tiles_m * tiles_n, n_cu = gvl_device_cus() & ~7;
   static const bool no_persist = gvl_lab_env("GVL_GEMM_NO_PERSIST") != nullptr;                // A/B only
   const int grid = (tiles <= n_cu || no_persist) ? tiles : n_cu;
   static const bool timing = gvl_lab_env("GVL_GEMM_TIMING") != nullptr;                        // anatomy probe (tools/gemm_one.py)
-  if (timing) {
-    GemmArgs b = a;
-    const size_t n = (size_t)grid * 8 * 4;
-    if (hipMalloc((void**)&b.dbg, n * 8) != hipSuccess) return -3;
-    hipMemsetAsync(b.dbg, 0, n * 8, st);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, b, tiles_m, tiles_n);
-    std::vector<unsigned long long> hbuf(n);
-    hipStreamSynchronize(st);
-    hipMemcpy(hbuf.data(), b.dbg, n * 8, hipMemcpyDeviceToHost);
-    hipFree(b.dbg);
-    double s[3] = {0, 0, 0}; unsigned long long tmin = ~0ull, tmax = 0;
-    for (int g = 0; g < grid; ++g) for (int w = 0; w < 8; ++w) {
-      const unsigned long long* d = &hbuf[((size_t)g * 8 + w) * 4];
-      for (int k = 0; k < 3; ++k) s[k] += (double)(d[k + 1] - d[k]);
-      if (d[0] < tmin) tmin = d[0];
-      if (d[3] > tmax) tmax = d[3];
-    }
-    const double nw = (double)grid * 8;
-    fprintf(stderr, "[gemm timing] EPI %d M %d N %d K %d grid %d tiles %d: last tile per wave (cycles of s_memtime): prologue %.0f mainloop %.0f epilogue %.0f ; span of last tiles %llu\n",
-            EPI, a.M - a.m_begin, a.N, a.K, grid, tiles, s[0] / nw, s[1] / nw, s[2] / nw, tmax - tmin);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-  }
+  if (timing)
+    return gvl_gemm_probe_launch(a, (size_t)grid * 8 * 4, st, [&](const GemmArgs& b) { hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, b, tiles_m, tiles_n); },
+                                 [&](const std::vector<unsigned long long>& hbuf) {
+      double s[3] = {0, 0, 0}; unsigned long long tmin = ~0ull, tmax = 0;
+      for (int g = 0; g < grid; ++g) for (int w = 0; w < 8; ++w) {
+        const unsigned long long* d = &hbuf[((size_t)g * 8 + w) * 4];
+        for (int k = 0; k < 3; ++k) s[k] += (double)(d[k + 1] - d[k]);
+        if (d[0] < tmin) tmin = d[0];
+        if (d[3] > tmax) tmax = d[3];
+      }
+      const double nw = (double)grid * 8;
+      fprintf(stderr, "[gemm timing] EPI %d M %d N %d K %d grid %d tiles %d: last tile per wave (cycles of s_memtime): prologue %.0f mainloop %.0f epilogue %.0f ; span of last tiles %llu\n",
+              EPI, a.M - a.m_begin, a.N, a.K, grid, tiles, s[0] / nw, s[1] / nw, s[2] / nw, tmax - tmin);
+    });
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, a, tiles_m, tiles_n);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -518,172 +498,76 @@ static int launch_cfg(const GemmArgs& a, hipStream_t st) {
 
 double gvl_gemm_flops(const GemmArgs& a) { return 2.0 * a.M * (double)a.N * a.K; }
 
-int gvl_launch_gemm(const GemmArgs& a_in, hipStream_t st) {
-  GemmArgs a = a_in;
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return -1;
-  if (a.ldw == 0) a.ldw = a.K;
-  if (a.act == GVL_ACT_GELU && !a.act_table) { a.act_table = gelu_table_device(); if (!a.act_table) return -3; }   // every erf-GELU epilogue reads Phi from the table
-  if (a.K % BK != 0 || a.N % 4 != 0 || a.lda % 8 != 0 || a.ldw % 8 != 0 || a.ldw < a.K) return -1;   // K padded to 64 by the packer; 16-byte rows
-  if (a.act == GVL_ACT_SILU_MUL && (a.out_f32 || a.resid || a.gamma)) return -1;
-  int cfg = a.tile_cfg;
-  static const int env_cfg = [] { const char* e = gvl_lab_env("GVL_GEMM_CFG"); return e ? atoi(e) : 0; }();   // experiments only
-  if (cfg == 0 && env_cfg) cfg = env_cfg;
-  if (cfg == 0) {
-    // measured on MI355X (tools/gemm_bench.py, profiles/r01_gemm_microbench*.txt):
-    //  * cfg 82 = 256x256 ping-pong kernel: best whenever K is long enough to amortise its un-overlapped
-    //    prologue/epilogue (one block / CU) and there are enough tiles;
-    //  * cfg 21 = 128x128, 2 blocks / CU: short K or few tiles (CLIP out / fc2: 112 tiles).
-    const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    cfg = (a.K >= 1024 && t256 >= 128) ? 80 : 21;   // CLIP qkv / fc1 (K = 1024, 336 / 448 tiles): 82 measured +8...17 % over 21
-    // short K but thousands of tiles (the three-pass patch GEMM at the bench's M: K = 640, 864 / 4 608 tiles): 82 measured 76.6 vs 83.2 us (CLIP) and 454.6 vs
-    // 477.7 us (InternVideo2, bias) -- profiles/r05_patch_gemm_floor.txt
-    if (cfg == 21 && a.K >= 512 && t256 >= 512) cfg = 80;
+// One planned launch.  The staged (LDS, whole-row) epilogue is compile-time specialised per fused-epilogue code; GVL_EPI_GENERIC is the per-lane epilogue.
+static int dispatch(const GemmArgs& a, const GemmLaunch& l, hipStream_t st) {
+#define STAGED_SWITCH(LAUNCH)                                \
+  switch (l.epi) {                                           \
+    GVL_EPI_STAGED(LAUNCH)                                   \
+    default: return -1;                                      \
   }
-  // 32-bit DMA offsets: every 256 x 256 form (80, 82, 84 ... 88 -- an explicit 85 / 88 included: both end in launch_pp) hands an operand of 4 GiB or more to cfg 21
-  if ((cfg == 80 || cfg == 82 || (cfg >= 84 && cfg <= 88)) && ((size_t)a.N * a.ldw * 2 >= (1ull << 32) || (size_t)a.M * a.lda * 2 >= (1ull << 32))) cfg = 21;
-  const int epi = (a.act & 3) | ((a.out_f32 ? 1 : 0) << 2) | ((a.resid ? 1 : 0) << 3) | ((a.gamma ? 1 : 0) << 4) | ((a.bias ? 1 : 0) << 5) |
-                  ((a.rowscale ? 1 : 0) << 6) | ((a.rowsq ? 1 : 0) << 7);
-  if (a.rowsq && (a.N % 64 != 0 || a.out_f32 || a.act == GVL_ACT_SILU_MUL || a.rowsq_ld < a.N / 64 || a.grp_rows)) return -1;
-  if (cfg == 80 && a.tile_cfg == 0 && env_cfg == 0 && a.m_begin == 0) {
-    // Wave-quantisation planner.  The persistent 256x256 kernel runs one block per CU, so a launch costs ceil(tiles / CUs)
-    // tile times, and a partial last tile column (N = 1408 = 5.5 x 256) wastes half of its MFMA work.  Candidate plans, costed
-    // in units of one 256x256 tile time (the small kernel: see small_unit below):
-    //   W  whole GEMM on the big kernel;
-    //   M  whole rounds of tile ROWS on the big kernel, the remaining rows on the small kernel;
-    //   N  the full 256-wide tile columns through W or M, the N % 256 tail columns on the small kernel.
-    // e.g. InternVideo2 proj/fc2 (M = 24588, N = 1408): W = 3, M = 3.0, N = 2.5 (485 big tiles in 2 rounds + 193 small).
-    static const int n_cu = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) ? p.multiProcessorCount : 256; }();
-    // cost of up to one CU-count of small tiles, in big-tile times.  Half the FLOPs at ~0.76x the rate would be 0.33, but an
-    // under-filled small launch runs its lone blocks far below that rate: same-box A/B of the whole bench, 0.33 / 0.45-0.75 / 0.90
-    // -> GEMM time 73.4 / 73.0 / 75.7 ms per clip (GVL_GEMM_SMALLCOST = percent, experiments only)
-    static const double small_unit = [] { const char* e = gvl_lab_env("GVL_GEMM_SMALLCOST"); return e ? atoi(e) / 100.0 : 0.5; }();
-    auto small_cost = [&](long t) { const long halves = (t + n_cu - 1) / n_cu; return t > 0 ? small_unit * (double)halves : 0.0; };
-    struct Plan { double cost; int big_rows; };   // big_rows = tile rows given to the big kernel (all of them: no M split)
-    auto plan_mw = [&](int M, int N) {            // best of W and M for an [M, N] problem
-      const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
-      const long tiles = (long)tiles_m * tiles_n, rounds = tiles / n_cu;
-      Plan best{(double)((tiles + n_cu - 1) / n_cu), tiles_m};
-      if (rounds >= 1 && tiles % n_cu != 0) {
-        const int br = (int)((rounds * n_cu) / tiles_n);
-        if (br >= 1 && br < tiles_m) {
-          const double c = (double)rounds + small_cost((long)((M - br * 256 + 127) / 128) * ((N + 127) / 128));
-          if (c < best.cost - 0.1) best = Plan{c, br};
-        }
-      }
-      return best;
-    };
-    const Plan whole = plan_mw(a.M, a.N);
-    int n_big = a.N;
-    Plan chosen = whole;
-    if (a.N % 256 != 0 && a.N > 256 && a.act != GVL_ACT_SILU_MUL) {
-      const int nb = (a.N / 256) * 256;
-      const Plan p = plan_mw(a.M, nb);
-      const double c = p.cost + small_cost((long)((a.M + 127) / 128) * ((a.N - nb + 127) / 128));
-      if (c < whole.cost - 0.1) { chosen = Plan{c, p.big_rows}; n_big = nb; }
-    }
-    const int tiles_m = (a.M + 255) / 256;
-    if (n_big != a.N || chosen.big_rows < tiles_m) {
-      const int es_ = a.out_f32 ? 4 : 2;
-      auto cols = [&](const GemmArgs& g, int n0, int n1) {       // sub-problem on output columns [n0, n1): pointer offsets only
-        GemmArgs r = g;
-        r.W = g.W + (size_t)n0 * g.ldw; r.N = n1 - n0;
-        r.C = (char*)g.C + (size_t)n0 * es_;
-        if (g.resid) r.resid = (const char*)g.resid + (size_t)n0 * es_;
-        if (g.bias) r.bias = g.bias + n0;
-        if (g.gamma) r.gamma = g.gamma + n0;
-        if (g.rowsq) r.rowsq = g.rowsq + n0 / 64;    // n0 is a multiple of 256: whole 64-column blocks
-        return r;
-      };
-      GemmArgs left = cols(a, 0, n_big);
-      int rc = 0;
-      if (chosen.big_rows < tiles_m) {
-        GemmArgs big = left; big.M = chosen.big_rows * 256; big.tile_cfg = 80;
-        GemmArgs rest = left; rest.m_begin = chosen.big_rows * 256; rest.tile_cfg = 21;
-        rc = gvl_launch_gemm(big, st);
-        if (!rc) rc = gvl_launch_gemm(rest, st);
-      } else {
-        left.tile_cfg = 80;
-        rc = gvl_launch_gemm(left, st);
-      }
-      if (!rc && n_big != a.N) { GemmArgs tail = cols(a, n_big, a.N); tail.tile_cfg = 21; rc = gvl_launch_gemm(tail, st); }
-      return rc;
-    }
-  }
-  const int es = a.out_f32 ? 4 : 2;
-  const bool stg_ok = a.N % 16 == 0 && a.grp_rows == 0 && ((size_t)a.ldc * es) % 16 == 0 && ((uintptr_t)a.C & 15) == 0 &&
-                      (!a.resid || (((size_t)a.ldr * es) % 16 == 0 && ((uintptr_t)a.resid & 15) == 0));
-  if ((a.rowscale || a.rowsq) && (!stg_ok || cfg == 1 || cfg == 85)) return -1;   // the fused-RMSNorm epilogues exist in the staged (whole-row) form only
-  if (cfg == 21 && a.tile_cfg == 21 && env_cfg == 0) {   // planner remainder / tail launches only
-    static const int small64 = [] { const char* e = gvl_lab_env("GVL_GEMM_SMALL64"); return e ? atoi(e) : 3; }();   // 0 = off (A/B); measured -0.6 ms of GEMM time per clip
-    static const int n_cu2 = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) ? p.multiProcessorCount : 256; }();
-    const long t128 = (long)((a.M - a.m_begin + 127) / 128) * ((a.N + 127) / 128);
-    if (small64 && t128 * 2 <= (long)small64 * n_cu2) cfg = 22;
-  }
-  // cfg 80 = "the 256 x 256 kernel, the library's choice of form" (what the automatic selection and the planner ask for).  Forms, all bit-identical:
-  // 82 the 8-wave ping-pong kernel; 84 / 86 / 87 the 4-wave kernel (gvl_gemm4.hip, loop schedule 0 / 1 / 2); 88 the 4-wave kernel with the epilogue
-  // pipelined into the next tile's main loop (gvl_gemm4p.hip).  An explicit 84 ... 88 that does not serve the (epilogue, geometry) falls back towards 82.
-  if (cfg == 80 || (cfg >= 84 && cfg <= 88)) {
-    // gemm_a4 (gvl_debug_set): 0 = always the 8-wave kernel, 1 (default) = big_form_preferred, 2 = the plain 4-wave kernel wherever it serves, 3 = the pipelined one
-    // wherever it serves (then the plain one)
-    int form = cfg;
-    const int a4m = g_a4_mode.load(std::memory_order_relaxed);
-    if (cfg == 80) form = a4m == 0 ? 82 : (a4m == 1 ? big_form_preferred(epi) : (a4m == 2 ? 86 : 88));
-    GemmArgs b = a;
-    if (b.band <= 0) b.band = GVL_GEMM_BAND;
-    if (const int bo = g_band_override.load(std::memory_order_relaxed); bo > 0) b.band = bo;
-    if (stg_ok && form == 88) {
-      const int rc4 = gvl_launch_gemm_a4p(b, epi, st);
-      if (rc4 != -2) return rc4;
-      form = 86;
-    }
-    if (stg_ok && form >= 84 && form <= 87) {
-      const int rc4 = gvl_launch_gemm_a4(b, epi, form == 84 ? 0 : (form == 87 ? 2 : 1), st);
-      if (rc4 != -2) return rc4;
-    }
-    cfg = 82;
-  }
-  switch (cfg) {
-    case 1: return launch_cfg<128, 128, 2, 2, 0>(a, st);            // plain lock-step baseline (tests / A-B)
-    // cfg 21 / 82 run the LDS-staged whole-row epilogue (compile-time specialised per fused-epilogue code) whenever the
-    // output rows are 16-byte aligned; anything else takes the generic per-lane epilogue (EPI = -1).
-    case 21: {
-      if (stg_ok) switch (epi) {
-#define S_CASE(E) case E: return launch_cfg<128, 128, 2, 2, 1, E, 1>(a, st);
-        S_CASE(0) S_CASE(32) S_CASE(33) S_CASE(34) S_CASE(3) S_CASE(44) S_CASE(56) S_CASE(8) S_CASE(4) S_CASE(36)
-        S_CASE(64) S_CASE(67) S_CASE(98) S_CASE(128) S_CASE(136) S_CASE(184)     // fused RMSNorm: +64 row scale (consumer), +128 row sums of squares (producer)
+  switch (l.form) {
+    case GVL_FORM_LOCKSTEP_128: return launch_cfg<128, 128, 2, 2, 0>(a, st);
+    case GVL_FORM_128:
+      if (l.epi == GVL_EPI_GENERIC) return launch_cfg<128, 128, 2, 2, 1, -1>(a, st);
+#define S_CASE(E) case (E): return launch_cfg<128, 128, 2, 2, 1, (E), 1>(a, st);
+      STAGED_SWITCH(S_CASE)
 #undef S_CASE
-        default: break;
-      }
-      if (a.rowscale || a.rowsq) return -1;
-      return launch_cfg<128, 128, 2, 2, 1, -1>(a, st);
-    }
-    // cfg 22 = 64x128 tiles, same kernel (wave tile 32x64): twice the blocks of cfg 21 for launches that would leave most CUs with
-    // ONE 128x128 block (remainder rows / tail columns of the planner: 193-264 tiles on 512 slots).  Same k-order per output
-    // element as every other cfg, so the results are bit-identical.
-    case 22: {
+    case GVL_FORM_64x128:      // wave tile 32x64, same k-order per output element as every other form
+      if (l.epi == GVL_EPI_GENERIC) return launch_cfg<64, 128, 2, 2, 1, -1>(a, st);
       // 3-slot ring (two k-tiles of DMA in flight, 72 KB: still 2 blocks per CU); the 2-slot form measured 3-15 % slower on these launches (round 2)
-      if (stg_ok) switch (epi) {
-#define S_CASE(E) case E: return launch_cfg<64, 128, 2, 2, 1, E, 1, 3>(a, st);
-        S_CASE(0) S_CASE(32) S_CASE(33) S_CASE(34) S_CASE(3) S_CASE(44) S_CASE(56) S_CASE(8) S_CASE(4) S_CASE(36)
-        S_CASE(64) S_CASE(67) S_CASE(98) S_CASE(128) S_CASE(136) S_CASE(184)
+#define S_CASE(E) case (E): return launch_cfg<64, 128, 2, 2, 1, (E), 1, 3>(a, st);
+      STAGED_SWITCH(S_CASE)
 #undef S_CASE
-        default: break;
-      }
-      if (a.rowscale || a.rowsq) return -1;
-      return launch_cfg<64, 128, 2, 2, 1, -1>(a, st);
-    }
-    case 82: {
-      if (stg_ok) switch (epi) {
-#define PP_CASE(E) case E: return launch_pp<E, 1>(a, st);
-        PP_CASE(0) PP_CASE(32) PP_CASE(33) PP_CASE(34) PP_CASE(3) PP_CASE(44) PP_CASE(56) PP_CASE(8) PP_CASE(4) PP_CASE(36)
-        PP_CASE(64) PP_CASE(67) PP_CASE(98) PP_CASE(128) PP_CASE(136) PP_CASE(184)
+    case GVL_FORM_PP_STAGED:
+#define PP_CASE(E) case (E): return launch_pp<(E), 1>(a, st);
+      STAGED_SWITCH(PP_CASE)
 #undef PP_CASE
-        default: break;
-      }
-      if (a.rowscale || a.rowsq) return -1;
-      return launch_pp<-1>(a, st);
-    }
-    case 85: return launch_pp<-1>(a, st);                   // ping-pong with the per-lane epilogue (A/B only)
+    case GVL_FORM_PP_LANE: return launch_pp<-1>(a, st);
+    case GVL_FORM_A4_S0: case GVL_FORM_A4_S1: case GVL_FORM_A4_S2: return gvl_launch_gemm_a4(a, l.epi, l.form - GVL_FORM_A4_S0, st);
+    case GVL_FORM_A4P: return gvl_launch_gemm_a4p(a, l.epi, st);
     default: return -1;
   }
+#undef STAGED_SWITCH
+}
+
+// plan (gvl_gemm_plan.h: which forms, on which rows and columns) + dispatch
+int gvl_launch_gemm(const GemmArgs& a_in, hipStream_t st) {
+  static const int env_cfg = [] { const char* e = gvl_lab_env("GVL_GEMM_CFG"); return e ? atoi(e) : 0; }();   // experiments only
+  static const double small_unit = [] { const char* e = gvl_lab_env("GVL_GEMM_SMALLCOST"); return e ? atoi(e) / 100.0 : GVL_GEMM_KNOBS_DEFAULT.small_unit; }();   // percent
+  static const int small64 = [] { const char* e = gvl_lab_env("GVL_GEMM_SMALL64"); return e ? atoi(e) : GVL_GEMM_KNOBS_DEFAULT.small64; }();   // 0 = off (A/B)
+  const GemmKnobs knobs{gvl_device_cus(), env_cfg, g_a4_mode.load(std::memory_order_relaxed), small_unit, small64, g_narrow.load(std::memory_order_relaxed)};
+  GemmArgs a = a_in;
+  if (a.ldw == 0) a.ldw = a.K;
+  const int epi = epi_code(a.act, a.out_f32, a.resid, a.gamma, a.bias, a.rowscale, a.rowsq);
+  const GemmGeometry geo{a.M, a.N, a.K, a.lda, a.ldw, a.ldc, a.ldr, a.grp_rows, a.rowsq_ld, epi, a.tile_cfg,
+                         ((uintptr_t)a.C & 15) == 0 && (!a.resid || ((uintptr_t)a.resid & 15) == 0)};
+  GemmLaunch plan[GVL_GEMM_MAX_LAUNCHES];
+  const int n = gemm_plan(geo, knobs, plan);
+  if (n < 0) return -1;
+  if (a.act == GVL_ACT_GELU && !a.act_table) { a.act_table = gelu_table_device(); if (!a.act_table) return -3; }   // every erf-GELU epilogue reads Phi from the table
+  const size_t es = a.out_f32 ? 4 : 2;
+  for (int i = 0; i < n; ++i) {
+    const GemmLaunch& l = plan[i];
+    GemmArgs b = a;                                  // sub-problem on rows [m_begin, m_end) and columns [n_begin, n_end): pointer offsets only
+    b.m_begin = l.m_begin; b.M = l.m_end;
+    b.N = l.n_end - l.n_begin;
+    b.W = a.W + (size_t)l.n_begin * a.ldw;
+    b.C = (char*)a.C + (size_t)l.n_begin * es;
+    if (a.resid) b.resid = (const char*)a.resid + (size_t)l.n_begin * es;
+    if (a.bias) b.bias = a.bias + l.n_begin;
+    if (a.gamma) b.gamma = a.gamma + l.n_begin;
+    if (a.rowsq) b.rowsq = a.rowsq + l.n_begin / 64;    // n_begin is a multiple of 256: whole 64-column blocks
+    if (gemm_form_is_256(l.form)) {
+      // Rasterisation band: the 32 workgroups of an XCD walk a band of GM tile rows column by column, k-tile by k-tile in lock-step (an 8 x 4 patch of tiles).
+      // MEASURED AND NOT ADOPTED (round 5, profiles/r05_ab_gemm_band.json + the PMC passes): GM = 32 / tile columns for narrow matrices (N = 1408: 5 rows x 6
+      // columns, so that an A slice enters the XCD's L2 once) -- +0.4 % clips/s, inside the run-to-run spread, while the family's fabric-side traffic ROSE from
+      // 193 to 231 GB per clip (the W panel is re-read per band, and there are 154 bands instead of 96).  The default is GVL_GEMM_BAND = 4 tile rows since round 6
+      // (gvl_internal.h: 8 -> 4 measured -2.1 % per step with the 4-wave kernels); gvl_debug_set("gemm_band") varies it.
+      if (b.band <= 0) b.band = GVL_GEMM_BAND;
+      if (const int bo = g_band_override.load(std::memory_order_relaxed); bo > 0) b.band = bo;
+    }
+    if (l.form == GVL_FORM_A4P) b.narrow = knobs.narrow;
+    if (const int rc = dispatch(b, l, st)) return rc;
+  }
+  return 0;
 }

@@ -14,6 +14,7 @@
 // The epilogue is the shared LDS-staged whole-row epilogue (gvl_gemm_epi.h); it reads the accumulators block row by block row out of the AGPRs.
 // Reference shapes served: models/internvideo2.py:587,603,631-634; models/modeling_phi3.py:459-464,659-663; models/modeling_clip.py:264-266,340-342.
 #include "gvl_gemm_epi.h"
+#include "gvl_gemm_plan.h"
 #include "gvl_gemm4_loop.inc"
 #include <cstdio>
 #include <vector>
@@ -167,51 +168,36 @@ __global__ __launch_bounds__(256) void gemm_a4_kernel(const GemmArgs a, int tile
 }
 
 template <int EPI, int VAR>
-static int launch_a4(const GemmArgs& a_in, hipStream_t st) {
+static int launch_a4(const GemmArgs& a, hipStream_t st) {
   constexpr bool TAB = (EPI & 3) == GVL_ACT_GELU;
   constexpr int LDS = 2 * 65536 + 4 * 128 * 8 + (TAB ? GELU_TAB_BYTES : 0);
   static GvlDevOnce once;
-  static const int n_cu = [] {
-    hipDeviceProp_t p; int d = 0;
-    return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) ? (p.multiProcessorCount & ~7) : 256;
-  }();
   auto kern = gemm_a4_kernel<EPI, VAR>;
   if (gvl_set_max_lds(once, (const void*)kern, LDS)) return -3;
-  GemmArgs a = a_in;
   const int tiles_m = (a.M - a.m_begin + 255) / 256, tiles_n = (a.N + 255) / 256;
-  const int tiles = tiles_m * tiles_n;
-  if (a.band <= 0) a.band = GVL_GEMM_BAND;
+  const int tiles = tiles_m * tiles_n, n_cu = gvl_device_cus() & ~7;
   const int grid = tiles <= n_cu ? tiles : n_cu;
   static const bool timing = gvl_lab_env("GVL_GEMM_TIMING") != nullptr;                        // anatomy probe (LAB builds; tools/gemm4_lab.py)
-  if (timing) {
-    GemmArgs b = a;
-    const size_t n = (size_t)grid * 4 * 4;
-    if (hipMalloc((void**)&b.dbg, n * 8) != hipSuccess) return -3;
-    hipMemsetAsync(b.dbg, 0, n * 8, st);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, b, tiles_m, tiles_n);
-    std::vector<unsigned long long> hbuf(n);
-    hipStreamSynchronize(st);
-    hipMemcpy(hbuf.data(), b.dbg, n * 8, hipMemcpyDeviceToHost);
-    hipFree(b.dbg);
-    double s[4] = {0, 0, 0, 0};
-    for (size_t w = 0; w < n / 4; ++w) for (int k = 0; k < 4; ++k) s[k] += (double)hbuf[w * 4 + k];
-    const double nt = s[2] > 0 ? s[2] : 1, nw = (double)(n / 4);
-    fprintf(stderr, "[gemm4 timing] EPI %d VAR %d M %d N %d K %d grid %d tiles %d: per tile and wave (s_memtime cycles): loop %.0f (%.0f per k-tile) epilogue %.0f other %.0f ; tiles per wave %.2f\n",
-            EPI, VAR, a.M - a.m_begin, a.N, a.K, grid, tiles, s[0] / nt, s[0] / nt / (a.K / 64), s[1] / nt, (s[3] - s[0] - s[1]) / nt, nt / nw);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-  }
+  if (timing)
+    return gvl_gemm_probe_launch(a, (size_t)grid * 4 * 4, st, [&](const GemmArgs& b) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, b, tiles_m, tiles_n); },
+                                 [&](const std::vector<unsigned long long>& hbuf) {
+      const size_t n = hbuf.size();
+      double s[4] = {0, 0, 0, 0};
+      for (size_t w = 0; w < n / 4; ++w) for (int k = 0; k < 4; ++k) s[k] += (double)hbuf[w * 4 + k];
+      const double nt = s[2] > 0 ? s[2] : 1, nw = (double)(n / 4);
+      fprintf(stderr, "[gemm4 timing] EPI %d VAR %d M %d N %d K %d grid %d tiles %d: per tile and wave (s_memtime cycles): loop %.0f (%.0f per k-tile) epilogue %.0f other %.0f ; tiles per wave %.2f\n",
+              EPI, VAR, a.M - a.m_begin, a.N, a.K, grid, tiles, s[0] / nt, s[0] / nt / (a.K / 64), s[1] / nt, (s[3] - s[0] - s[1]) / nt, nt / nw);
+    });
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, a, tiles_m, tiles_n);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// -2: this (epilogue, geometry) is not served by the 4-wave kernel -- the caller takes the 8-wave one
+// template switch only: gemm_plan (gvl_gemm_plan.h) has decided that this (epilogue, geometry) is served here
 int gvl_launch_gemm_a4(const GemmArgs& a, int epi, int var, hipStream_t st) {
-  if (a.K % BK != 0 || a.K / BK < 3) return -2;
-  if (((size_t)a.N + 256) * (size_t)a.ldw * 2 >= (1ull << 32) || ((size_t)a.M + 256) * (size_t)a.lda * 2 >= (1ull << 32)) return -2;   // 32-bit buffer offsets
   switch (epi) {
-#define A4_CASE(E) case E: return var == 1 ? launch_a4<E, 1>(a, st) : (var == 2 ? launch_a4<E, 2>(a, st) : launch_a4<E, 0>(a, st));
-    A4_CASE(0) A4_CASE(32) A4_CASE(33) A4_CASE(34) A4_CASE(3) A4_CASE(56) A4_CASE(8) A4_CASE(64) A4_CASE(67) A4_CASE(98) A4_CASE(128) A4_CASE(136) A4_CASE(184)
+#define A4_CASE(E) case (E): return var == 1 ? launch_a4<(E), 1>(a, st) : (var == 2 ? launch_a4<(E), 2>(a, st) : launch_a4<(E), 0>(a, st));
+    GVL_EPI_A4(A4_CASE)
 #undef A4_CASE
-    default: return -2;
+    default: return -1;
   }
 }

@@ -311,41 +311,28 @@ static void balance_rounds(int tiles_m, int tiles_n, int band, int grid, bool la
   std::lock_guard<std::mutex> lk(g_rot_mu); g_rot_cache[key] = tab;
 }
 
-static std::atomic<int> g_narrow{1};          // A/B only, process-wide like gemm_a4 / gemm_band
-void gvl_gemm_set_narrow(int v) { g_narrow.store(v, std::memory_order_relaxed); }
-
 template <int EPI>
 static int launch_a4p(const GemmArgs& a_in, hipStream_t st) {
   static GvlDevOnce once;
-  static const int n_cu = [] {
-    hipDeviceProp_t p; int d = 0;
-    return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) ? (p.multiProcessorCount & ~7) : 256;
-  }();
   auto kern = gemm_a4p_kernel<EPI>;
   if (gvl_set_max_lds(once, (const void*)kern, a4p_lds<EPI>())) return -3;
   GemmArgs a = a_in;
-  if (a.K / BK < A4pAsm<EPI>::MIN_NK) return -2;
   const int tiles_m = (a.M - a.m_begin + 255) / 256, tiles_n = (a.N + 255) / 256;
-  const int tiles = tiles_m * tiles_n;
-  if (a.band <= 0) a.band = GVL_GEMM_BAND;
-  a.narrow = g_narrow.load(std::memory_order_relaxed);
+  const int tiles = tiles_m * tiles_n, n_cu = gvl_device_cus() & ~7;
   const int grid = tiles <= n_cu ? tiles : n_cu;
-  // gemm_narrow: 1 = narrow tiles + balanced walk, 2 = narrow tiles on the fixed walk (A/B), 0 = neither
+  // gemm_narrow (GemmArgs.narrow): 1 = narrow tiles + balanced walk, 2 = narrow tiles on the fixed walk (A/B), 0 = neither
   const bool has_narrow_col = A4pNarrow<EPI>::has && a.narrow && a.K / BK >= A4pNarrow<EPI>::MIN_NK && a.K / BK <= A4P_NARROW_MAX_NK && tiles_n * 256 - a.N >= 128;
   balance_rounds(tiles_m, tiles_n, a.band, grid, has_narrow_col && a.narrow == 1, a.rot);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), a4p_lds<EPI>(), st, a, tiles_m, tiles_n);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// -2: this (epilogue, geometry) is not served by the pipelined kernel
+// template switch only: gemm_plan (gvl_gemm_plan.h) has decided that this (epilogue, geometry) is served here
 int gvl_launch_gemm_a4p(const GemmArgs& a, int epi, hipStream_t st) {
-  if (a.K % BK != 0) return -2;
-  if (((size_t)a.N + 256) * (size_t)a.ldw * 2 >= (1ull << 32) || ((size_t)a.M + 256) * (size_t)a.lda * 2 >= (1ull << 32)) return -2;   // 32-bit buffer offsets
-  if ((size_t)a.ldc * 2 * 136 >= (1ull << 31) || (a.resid && (size_t)a.ldr * 2 * 136 >= (1ull << 31))) return -2;
   switch (epi) {
 #define A4P_CASE(E) case E: return launch_a4p<E>(a, st);
     GVL_A4P_EPI_LIST(A4P_CASE)
 #undef A4P_CASE
-    default: return -2;
+    default: return -1;
   }
 }

@@ -32,6 +32,7 @@ constexpr int GVL_MAX_PREFILL_BATCH = 8;  // most sequences whose rows share one
 // (include/gvl.h allows it), so "set once" means once per device ordinal -- a process-global flag would leave the second device at the
 // 64 KB default and its first big-LDS launch would fail.  One bit per ordinal (mod 64); racing first launches set it twice, harmlessly.
 #include <atomic>
+#include <vector>
 struct GvlDevOnce { std::atomic<unsigned long long> mask{0}; };
 inline int gvl_set_max_lds(GvlDevOnce& once, const void* kern, int bytes) {
   int d = 0;
@@ -143,10 +144,10 @@ struct GemmArgs {
   int round_pre_resid;           // 1: round (acc+bias) [and the gamma product] to bf16 before adding resid
   // output row remap: row m -> (m / grp_rows) * grp_stride + (m % grp_rows) + row_off   (grp_rows==0: identity)
   int grp_rows, grp_stride, row_off;
-  int tile_cfg;                  // 0 auto; see gvl_launch_gemm
+  int tile_cfg;                  // 0 auto; GVL_CFG_* (gvl_gemm_plan.h)
   int band;                      // ping-pong kernel: tile ROWS per rasterisation band (0 = the launcher's choice); any value gives the same result
   unsigned char rot[64];         // pipelined 4-wave kernel: workgroup c of an XCD takes offset (c + rot[round & 63]) mod (workgroups of the XCD) of its XCD's round (0: fixed)
-  int narrow;                    // set by the pipelined 4-wave launcher: tiles with <= 128 real columns run its narrow statements (gvl_debug_set "gemm_narrow"); result-neutral
+  int narrow;                    // set by gvl_launch_gemm for the pipelined 4-wave kernel: tiles with <= 128 real columns run its narrow statements (gvl_debug_set "gemm_narrow"); result-neutral
   int m_begin;                   // launch covers rows [m_begin, M) -- set internally by the wave-quantisation split
   // Fused RMSNorm (round 5).  CONSUMER side: rowscale[m] (f32, [M]) multiplies row m of the accumulator BEFORE bias / activation -- RMSNorm(x) . W^T =
   // rs[m] * (x . (W diag(gamma))^T): A is the RAW residual stream, W carries the norm weight (gvl_fold_gamma), rs = rsqrt(mean x^2 + eps).
@@ -162,16 +163,29 @@ struct GemmArgs {
 // kernels: 8 -> 4 rows = 701 -> 686 ms per step (-2.1 %), 2 / 3 / 6 / 16 rows: 694 / 688 / 692 / 732 (profiles/r06_ab_gemm_band.json; per shape: iv2.fc2 +3.7 %,
 // phi.down +4.9 %, the others within +-1.5 %: profiles/r06_gemm_band_shapes.txt).  (Round 5 had tried 5-row bands for N = 1408 only, on the 8-wave kernel.)
 constexpr int GVL_GEMM_BAND = 4;
-int gvl_launch_gemm(const GemmArgs& a, hipStream_t st);
-// gvl_gemm4.hip: the 4-wave / AGPR-accumulator form of the 256 x 256 kernel for the staged bf16 epilogue code `epi` (loop schedule variant `var`);
-// -2 = this epilogue or geometry is not served there (the caller launches the 8-wave kernel instead)
+int gvl_launch_gemm(const GemmArgs& a, hipStream_t st);   // gemm_plan (gvl_gemm_plan.h) + dispatch on the planned forms
+int gvl_device_cus();                                     // compute units of the current device, unmasked (see gvl_gemm.hip)
+// gvl_gemm4.hip / gvl_gemm4p.hip: the 4-wave / AGPR-accumulator form of the 256 x 256 kernel for the staged bf16 epilogue code `epi` (loop schedule variant `var`), and
+// the same kernel with the epilogue software-pipelined into the next tile's main loop.  Template switches only: gemm_plan decides whether they serve a launch.
 int gvl_launch_gemm_a4(const GemmArgs& a, int epi, int var, hipStream_t st);
-// gvl_gemm4p.hip: the same kernel with the epilogue software-pipelined into the next tile's main loop; -2 as above
 int gvl_launch_gemm_a4p(const GemmArgs& a, int epi, hipStream_t st);
 void gvl_gemm_set_a4(int v);     // A/B: 0 = the 256 x 256 launches stay on the 8-wave ping-pong kernel, 1 (default) = the 4-wave kernel where it is faster, 2 = wherever it serves
 void gvl_gemm_set_narrow(int v); // A/B: 0 = the pipelined 4-wave kernel runs a half-empty column tile (N = 1408: every sixth) as a full one (rounds <= 6a), 1 (default) = as a narrow tile
 void gvl_gemm_set_band(int v);   // A/B: tile rows per rasterisation band of the ping-pong kernel for every later launch of the process (0 = automatic)
 double gvl_gemm_flops(const GemmArgs& a);
+// GVL_GEMM_TIMING probes (LAB builds): `launch` runs with a zeroed buffer of n 64-bit cycle stamps in GemmArgs.dbg; once it has finished, `report` gets the stamps
+template <class Launch, class Report>
+inline int gvl_gemm_probe_launch(GemmArgs a, size_t n, hipStream_t st, Launch&& launch, Report&& report) {
+  if (hipMalloc((void**)&a.dbg, n * 8) != hipSuccess) return -3;
+  hipMemsetAsync(a.dbg, 0, n * 8, st);
+  launch(a);
+  std::vector<unsigned long long> hbuf(n);
+  hipStreamSynchronize(st);
+  hipMemcpy(hbuf.data(), a.dbg, n * 8, hipMemcpyDeviceToHost);
+  hipFree(a.dbg);
+  report(hbuf);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 // ---- attention (prefill / vision) -----------------------------------------------------------------
 struct AttnArgs {

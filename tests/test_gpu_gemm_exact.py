@@ -9,6 +9,9 @@ reference (tests/gemm_ref.py) -- where test_gpu_gemm4.py only compares the forms
 The output buffer carries GUARD rows behind row M - 1 (and the statistics buffer too): a kernel that writes a row beyond M changes them.
 What the library documents for a configuration that does not serve an epilogue is what the tests require: 84 ... 88 fall back towards 82 (gvl_gemm.hip, gvl_launch_gemm; gvl.h
 "gemm_a4") and must still give the right answer; tile_cfg 1 / 85 (per-lane epilogue, A/B only) REJECT the fused-RMSNorm operands (row scale / row statistics) with an error.
+Which kernel a (shape, epilogue, tile_cfg) runs is asked from the library's own plan (tests/gemm_plan.py): the forms are bit-identical, and many edge shapes here fall back on
+purpose, so test_the_cases_exercise_every_form asserts that for every epilogue each of 84 / 86 / 87 / 88 / 22 that serves it -- and 22 as a remainder of the automatic
+plan -- really runs on at least one shape of the list, and the 4 GiB cases assert that no 256 x 256 form runs.
 N moves in steps of 4 around 128 / 256: N % 4 == 0 is the library's contract (gvl_launch_gemm returns -1 otherwise), the row statistics need N % 64 == 0."""
 
 import pytest
@@ -19,6 +22,7 @@ pytestmark = pytest.mark.gpu
 from gpu_util import DEV, bf, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, lib as L  # noqa: E402
 import gemm_ref as R  # noqa: E402
+import gemm_plan as G  # noqa: E402
 from test_gpu_gemm4 import NARROW_SHAPES, P_SHAPES  # noqa: E402
 
 CFGS = [0, 1, 21, 22, 82, 84, 86, 87, 88, 85]
@@ -117,6 +121,24 @@ def test_exact_cases_bit_for_bit(eng, M, N, K):
 BOUNDED_SHAPES = [(300, 512, 1024), (1000, 1408, 1408), (513, 768, 1088), (2049, 256, 448), (3000, 1024, 192)]
 
 
+def epi_code(flags):
+    act = R.ACT_QUICK_GELU if "qgelu" in flags else R.ACT_GELU if "gelu" in flags else R.ACT_SILU_MUL if "silu" in flags else R.ACT_NONE
+    return act | sum(bit for name, bit in (("f32", G.F32), ("resid", G.RESID), ("gamma", G.GAMMA), ("bias", G.BIAS), ("rowscale", G.ROWSCALE), ("rowsq", G.ROWSQ)) if name in flags)
+
+
+@pytest.mark.parametrize("epis,shapes,planner", [(R.EXACT_EPIS, EXACT_SHAPES, True), (R.BOUNDED_EPIS, BOUNDED_SHAPES, False)], ids=["exact", "bounded"])
+def test_the_cases_exercise_every_form(epis, shapes, planner):
+    for name, flags in epis.items():
+        e = epi_code(flags)
+        ok = [s for s in shapes if not (e & G.ROWSQ and s[1] % 64) and not (e & (G.ROWSCALE | G.ROWSQ) and s[1] % 16)]
+        for cfg, form in G.FORM_OF_CFG.items():
+            serves = form == G.T64x128 or (e in G.A4P_MIN_NK if form == G.A4P else e in G.A4_EPIS)
+            hit = [s for s in ok if form in G.forms(*s, e, cfg)]
+            assert bool(hit) == serves, f"{name}: tile_cfg {cfg} (form {form}) {'runs on no shape of the list' if serves else f'unexpectedly runs on {hit}'}"
+        if planner:
+            assert any(len(f) > 1 and G.T64x128 in f for f in (G.forms(*s, e, 0) for s in ok)), f"{name}: no shape on which the automatic plan splits off a 64 x 128 remainder"
+
+
 @pytest.mark.parametrize("M,N,K", BOUNDED_SHAPES)
 def test_bounded_cases_inside_the_elementwise_bound(eng, M, N, K):
     for epi in R.BOUNDED_EPIS:
@@ -163,6 +185,7 @@ def test_A_of_more_than_4_GiB(eng):
         cols = torch.arange(N, device=DEV, dtype=torch.int64)
         c.W = R.exact_W_int(cols, torch.arange(K, device=DEV, dtype=torch.int64), seed).to(bf)
         for cfg in (0, 82, 88):
+            assert not set(G.forms(M, N, K, 0, cfg)) & set(G.BIG_FORMS)
             out, _ = run(eng, c, cfg)
             for lo, hi in bands(M):
                 want = R.exact_expected(torch.arange(lo, hi, device=DEV, dtype=torch.int64), cols, K, seed, c.flags).to(bf)
@@ -188,6 +211,7 @@ def test_W_of_more_than_4_GiB(eng):
         c.A = R.exact_A(rows, K, seed)
         c.bias = R.exact_vectors(rows, torch.arange(N, device=DEV, dtype=torch.int64), seed, c.flags)["bias"]
         for cfg in (0, 82, 88):
+            assert not set(G.forms(M, N, K, G.BIAS, cfg)) & set(G.BIG_FORMS)
             out, _ = run(eng, c, cfg)
             for lo, hi in bands(N):
                 want = R.exact_expected(rows, torch.arange(lo, hi, device=DEV, dtype=torch.int64), K, seed, c.flags).to(bf)
