@@ -38,6 +38,9 @@ struct LogitsProc {
   bool on() const { return penalty != 1.0f || ngram > 0 || (min_new > 0 && eos >= 0); }
 };
 
+// a token rule set (gvl_rules_create): one device blob (TokenRulesDev header + its arrays) and the sequences / default that reference it
+struct RuleSet { bool used = false; TokenRulesDev* d = nullptr; int refs = 0; };
+
 struct Seq {
   bool used = false; int max_tokens = 0, n_pages = 0; std::vector<int> pages;
   int* d_block_table = nullptr; int* d_pos = nullptr; int pos = 0; int n_gen = 0;
@@ -49,6 +52,7 @@ struct Seq {
   unsigned rng_stream = 0;  // sampling: which random stream this sequence draws from (assigned at its prefill)
   int* d_eos = nullptr; volatile int* h_eos = nullptr;   // host-mapped word: generation count at which this sequence produced eos (0 = not yet)
   LogitsProc proc;          // HF logits processors of this sequence's token selection (gvl_seq_set_processors; default: gvl_ctx::proc_default)
+  int rules = -1;           // token rule set of this sequence (gvl_seq_set_token_rules; default: gvl_ctx::rules_default), counted in RuleSet::refs; -1 none
   // log-probabilities of the selected tokens (gvl_seq_set_logprobs; default: gvl_ctx::top_n_default): -1 off, 0 the selected token's, 1 .. 8 also the
   // top N.  Device lists of the sequence's slot, index = generation step like d_out ([outlist_cap], top lists [outlist_cap][GVL_MAX_TOP_LOGPROBS]);
   // null until the ctx allocated them (gvl_ctx::d_seq_lp / d_seq_top_*)
@@ -116,6 +120,9 @@ struct gvl_ctx {
   struct { bool on = false; float inv_temp = 1.f, top_p = 0.f; int top_k = 0; unsigned long long seed = 0; unsigned next_stream = 0; } sample;
   // logits processors copied into every sequence allocated later (gvl_set_logits_processors); off by default
   LogitsProc proc_default;
+  // token rule sets (gvl_rules_create) and the one every sequence allocated later starts with (gvl_set_token_rules; -1 none, counted in refs)
+  std::vector<RuleSet> rule_sets; int rules_default = -1;
+  static constexpr int kMaxRuleSets = 1024;
   // log-probability lists of every sequence slot ([kMaxSeqs][outlist_cap], top lists x GVL_MAX_TOP_LOGPROBS: ~134 MB), allocated by the first
   // gvl_set_logprobs / gvl_seq_set_logprobs that needs them; top_n_default is copied into every sequence allocated later
   float* d_seq_lp = nullptr; int* d_seq_top_ids = nullptr; float* d_seq_top_lp = nullptr;

@@ -375,8 +375,20 @@ int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
 // history is hist[b][0 .. *len_ptrs[b]) (clamped to cap <= GVL_LOGITS_HIST_CAP; a null len_ptrs[b] = empty history); penalty 1 / ngram 0 /
 // min_new 0 switch a processor off; eos < 0 switches the min-length ban off.
 constexpr int GVL_LOGITS_HIST_CAP = 8192;   // = the sequences' output-list capacity (gvl_ctx::outlist_cap)
+// Token rules of a row (gvl_rules_create): sequence_bias -> [penalty -> n-gram] -> bad_words_ids -> [min length] -> forced eos -> suppress ->
+// begin suppress.  One immutable device blob of 32-bit words that starts with this header; every off_* is a word offset from the blob's start.
+// A bias table (stage 0 = sequence_bias, 1 = bad_words_ids) is grouped BY TARGET TOKEN: targets [n_tgt][3] = (target id, first entry, entries);
+// entries [..][3] = (fp32 bias bits, prefix offset into the stage's prefix ids, prefix length 0 .. GVL_RULES_MAX_SEQ_LEN - 1), a target's
+// length-1 entry first, then its multi-token entries in the caller's (dict) order.  Targets of one table are distinct.
+constexpr int GVL_RULES_MAX_IDS = 1 << 18;     // ids of one single-token list (suppress, begin suppress, forced eos) / length-1 entries of one table
+constexpr int GVL_RULES_MAX_SEQS = 1024;       // multi-token entries of one table
+constexpr int GVL_RULES_MAX_SEQ_LEN = 16;      // ids of one multi-token entry
+struct TokenRulesDev { int n_suppress, off_suppress, n_begin, off_begin, begin_at, n_force, off_force, force_at, n_multi;
+                       int n_tgt[2], off_tgt[2], off_ent[2], off_pre[2]; };
+// rules[b]: null = row b has no token rules; any row non-null selects the kernel's second instantiation (after every field the first one reads)
 struct LogitsProcArgs { float* logits; int n, ld, batch, cap; const int* hist[GVL_MAX_DECODE_BATCH]; const int* len_ptrs[GVL_MAX_DECODE_BATCH];
-                        float penalty[GVL_MAX_DECODE_BATCH]; int ngram[GVL_MAX_DECODE_BATCH], min_new[GVL_MAX_DECODE_BATCH], eos[GVL_MAX_DECODE_BATCH]; };
+                        float penalty[GVL_MAX_DECODE_BATCH]; int ngram[GVL_MAX_DECODE_BATCH], min_new[GVL_MAX_DECODE_BATCH], eos[GVL_MAX_DECODE_BATCH];
+                        const TokenRulesDev* rules[GVL_MAX_DECODE_BATCH]; };
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st);
 // x[b][:] = table[*tok_ptrs[b]][:]  and  (*pos_ptrs[b])++ helpers of the batched decode loop
 struct TokPtrs { const int* p[GVL_MAX_DECODE_BATCH]; int n; };

@@ -4,6 +4,12 @@
 //   RepetitionPenaltyLogitsProcessor   every DISTINCT token t of the history: s[t] = s[t] < 0 ? s[t] * p : s[t] / p (gather, then scatter)
 //   NoRepeatNGramLogitsProcessor       every window h[i .. i + n - 1) equal to the last n - 1 ids bans its next id: s[h[i + n - 1]] = -inf
 //   MinLength / MinNewTokensLength     s[eos] = -inf while the history is shorter than min_new
+// Token rules (gvl_rules_create; TokenRulesDev in gvl_internal.h) add HF's other token-level processors around them, in HF's order:
+//   SequenceBiasLogitsProcessor        BEFORE the penalty: s[t] += the fp32 sum (from 0.0f) of t's length-1 bias, then of every multi-token entry
+//                                      ending in t whose first len - 1 ids equal the last len - 1 history ids; entries longer than the history are skipped
+//   NoBadWordsLogitsProcessor          after the n-gram bans: the same mechanism with bias -inf
+//   ForcedEOSTokenLogitsProcessor      after the min-length ban, when the history holds force_at ids: every score -inf, the forced ids 0
+//   SuppressTokens / ...AtBegin        the listed scores -inf (at every step / when the history holds begin_at ids)
 // The history is the GENERATED ids only: the reference calls generate(inputs_embeds=...) without input_ids, so HF's input_ids start empty.
 // gfx950 only.
 #include "gvl_internal.h"
@@ -15,18 +21,47 @@
 // the barrier and writes after it, so a token that occurs several times is stored several times with the SAME value (penalised once, as HF's
 // gather -> scatter).  The bans come after a second barrier: no penalty store can overwrite a -inf.  Every operation is one IEEE fp32 multiply,
 // divide (correctly rounded: __fdiv_rn) or store -- the result is bit-identical to a torch restatement on the CPU.
+// RULES = true is the instantiation for launches in which a row has token rules (a null rules[b] = a row without).  One thread owns one target
+// token of a bias table: it sums that target's applicable entries in order and adds once, so no two threads store to one address and the sum
+// order is HF's.  Every stage that may store to an address another stage reads or stores differently is fenced by a block barrier (all
+// barrier conditions are uniform per block); RULES = false is the kernel without any of it.
+__device__ __forceinline__ void bias_stage(float* s, int n, const int* blob, const TokenRulesDev& R, int st, const int* h, int L, int tid) {
+  const int* tgt = blob + R.off_tgt[st]; const int* ent = blob + R.off_ent[st]; const int* pre = blob + R.off_pre[st];
+  for (int g = tid; g < R.n_tgt[st]; g += 1024) {
+    const int tk = tgt[3 * g], e0 = tgt[3 * g + 1], ne = tgt[3 * g + 2];
+    if (tk < 0 || tk >= n) continue;
+    float sum = 0.f; bool hit = false;
+    for (int e = e0; e < e0 + ne; ++e) {
+      const int po = ent[3 * e + 1], pl = ent[3 * e + 2];
+      if (pl > 0 && pl + 1 > L) continue;                    // HF: `len(sequence_ids) > input_ids.shape[1]` -> ignored
+      bool eq = true;
+      for (int j = 0; j < pl && eq; ++j) eq = h[L - pl + j] == pre[po + j];
+      if (eq) { sum = __fadd_rn(sum, __int_as_float(ent[3 * e])); hit = true; }
+    }
+    if (hit) s[tk] = __fadd_rn(s[tk], sum);
+  }
+}
+
+template <bool RULES>
 __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcArgs a) {
   __shared__ int h[GVL_LOGITS_HIST_CAP];
   const int b = blockIdx.x, tid = threadIdx.x;
   float* s = a.logits + (size_t)b * a.ld;
-  int L = a.len_ptrs[b] ? *a.len_ptrs[b] : 0;
-  L = L < 0 ? 0 : (L > a.cap ? a.cap : L);
+  const int Lraw = a.len_ptrs[b] ? *a.len_ptrs[b] : 0;
+  const int L = Lraw < 0 ? 0 : (Lraw > a.cap ? a.cap : Lraw);
+  TokenRulesDev R = {};                                      // all zero: every rule off
+  const int* blob = nullptr;
+  if constexpr (RULES) if (a.rules[b]) { R = *a.rules[b]; blob = reinterpret_cast<const int*>(a.rules[b]); }
   const float p = a.penalty[b];
   const int ng = a.ngram[b];
   const bool pen = p != 1.0f && L > 0, ban = ng > 0 && L >= ng;
-  if (pen || ban)
+  if (pen || ban || R.n_multi > 0)
     for (int i = tid; i < L; i += 1024) h[i] = a.hist[b][i];
   __syncthreads();
+  if constexpr (RULES) {                                     // sequence_bias lands before the penalty's gather
+    if (R.n_tgt[0] > 0) bias_stage(s, a.n, blob, R, 0, h, L, tid);
+    __syncthreads();
+  }
   if (pen) {
     constexpr int PER = GVL_LOGITS_HIST_CAP / 1024;
     float v[PER]; int t[PER];
@@ -53,15 +88,34 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcAr
       if (eq) { const int tk = h[i + m]; if (tk >= 0 && tk < a.n) s[tk] = -INFINITY; }
     }
   }
+  if constexpr (RULES) {                                     // bad_words_ids: after the penalty's scatter and the n-gram bans
+    __syncthreads();
+    if (R.n_tgt[1] > 0) bias_stage(s, a.n, blob, R, 1, h, L, tid);
+    __syncthreads();
+  }
   if (tid == 0 && L < a.min_new[b] && a.eos[b] >= 0 && a.eos[b] < a.n) s[a.eos[b]] = -INFINITY;
+  if constexpr (RULES) {
+    const bool force = R.n_force > 0 && Lraw == R.force_at;
+    __syncthreads();
+    if (force) for (int i = tid; i < a.n; i += 1024) s[i] = -INFINITY;
+    __syncthreads();
+    if (force) for (int j = tid; j < R.n_force; j += 1024) { const int tk = blob[R.off_force + j]; if (tk >= 0 && tk < a.n) s[tk] = 0.f; }
+    __syncthreads();
+    for (int j = tid; j < R.n_suppress; j += 1024) { const int tk = blob[R.off_suppress + j]; if (tk >= 0 && tk < a.n) s[tk] = -INFINITY; }
+    if (R.n_begin > 0 && Lraw == R.begin_at)
+      for (int j = tid; j < R.n_begin; j += 1024) { const int tk = blob[R.off_begin + j]; if (tk >= 0 && tk < a.n) s[tk] = -INFINITY; }
+  }
 }
 
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st) {
   if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH || !a.logits || a.n < 1 || a.ld < a.n || a.cap < 0 || a.cap > GVL_LOGITS_HIST_CAP) return -1;
+  bool rules = false;
   for (int b = 0; b < a.batch; ++b) {
     if (!(a.penalty[b] > 0.f) || a.ngram[b] < 0 || a.min_new[b] < 0) return -1;
-    if (a.cap > 0 && (a.penalty[b] != 1.0f || a.ngram[b] > 0) && a.len_ptrs[b] && !a.hist[b]) return -1;
+    if (a.cap > 0 && (a.penalty[b] != 1.0f || a.ngram[b] > 0 || a.rules[b]) && a.len_ptrs[b] && !a.hist[b]) return -1;
+    rules = rules || a.rules[b];
   }
-  hipLaunchKernelGGL(logits_process_kernel, dim3(a.batch), dim3(1024), 0, st, a);
+  if (rules) hipLaunchKernelGGL(logits_process_kernel<true>, dim3(a.batch), dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL(logits_process_kernel<false>, dim3(a.batch), dim3(1024), 0, st, a);
   return CHECK_LAUNCH();
 }

@@ -180,6 +180,7 @@ int gvl_destroy(gvl_ctx* ctx) {
   for (void* p : ctx->nf_allocs) if (p) hipFree(p);
   ctx->nf_allocs.clear();
   if (ctx->comm) gvl_comm_destroy(ctx);
+  for (RuleSet& r : ctx->rule_sets) if (r.used && r.d) hipFree(r.d);
   void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch};
   for (void* p : ptrs) if (p) hipFree(p);
   for (auto& r : ctx->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
@@ -466,6 +467,10 @@ int gvl_splice(gvl_ctx* ctx, const int64_t* ids, int n_ids, const uint16_t* visu
   return 0;
 }
 
+// a sequence takes / drops its reference to a token rule set (-1: none)
+static void rules_ref(gvl_ctx* ctx, int id) { if (id >= 0) ++ctx->rule_sets[id].refs; }
+static void rules_unref(gvl_ctx* ctx, int id) { if (id >= 0) --ctx->rule_sets[id].refs; }
+
 // the log-probability lists of slot `id` (null while the ctx has not allocated them)
 static void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
   const size_t cap = (size_t)ctx->outlist_cap;
@@ -490,6 +495,7 @@ int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = 0; s.n_gen = 0; s.pages.clear();
   s.proc = ctx->proc_default;                        // logits processors: the default of gvl_set_logits_processors
   s.top_n = ctx->top_n_default;                      // log-probabilities: the default of gvl_set_logprobs
+  s.rules = ctx->rules_default; rules_ref(ctx, s.rules);   // token rules: the default of gvl_set_token_rules
   for (int i = 0; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
   // preallocated slot: no hipMalloc / hipFree / device-wide sync per clip.  Work that uses the slot is stream ordered;
   // a freed slot or page may be handed out again only for work enqueued later on the same stream (one stream per ctx
@@ -509,6 +515,7 @@ int gvl_seq_free(gvl_ctx* ctx, int seq_id) {
   if (!ctx || seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_free: bad seq");
   Seq& s = ctx->seqs[seq_id];
   for (int p : s.pages) if (--ctx->page_ref[p] == 0) ctx->free_pages.push_back(p);     // a page shared with a fork lives on until its last holder is freed
+  rules_unref(ctx, s.rules);
   s = Seq();
   return 0;
 }
@@ -527,9 +534,10 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
   }
   const std::vector<int> src_pages(ctx->seqs[src_seq].pages.begin(), ctx->seqs[src_seq].pages.begin() + shared);   // (emplace_back may have moved the source)
   const LogitsProc src_proc = ctx->seqs[src_seq].proc;
-  const int src_top_n = ctx->seqs[src_seq].top_n;
+  const int src_top_n = ctx->seqs[src_seq].top_n, src_rules = ctx->seqs[src_seq].rules;
   Seq& s = ctx->seqs[id];
   s.proc = src_proc; s.top_n = src_top_n;
+  s.rules = src_rules; rules_ref(ctx, s.rules);
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = n_tokens; s.n_gen = 0; s.pages = src_pages;
   for (int p : s.pages) ++ctx->page_ref[p];          // whole pages of the prefix: immutable from now on for both holders (appends go to later pages)
   for (int i = shared; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
@@ -575,9 +583,10 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
   const std::vector<int> src_pages = ctx->seqs[src_seq].pages;
   const int src_ngen = ctx->seqs[src_seq].n_gen;
   const LogitsProc src_proc = ctx->seqs[src_seq].proc;
-  const int src_top_n = ctx->seqs[src_seq].top_n;
+  const int src_top_n = ctx->seqs[src_seq].top_n, src_rules = ctx->seqs[src_seq].rules;
   Seq& s = ctx->seqs[id];
   s.proc = src_proc; s.top_n = src_top_n;
+  s.rules = src_rules; rules_ref(ctx, s.rules);
   s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = pos; s.n_gen = src_ngen;
   s.pages.assign(src_pages.begin(), src_pages.begin() + shared);
   for (int p : s.pages) ++ctx->page_ref[p];
@@ -868,6 +877,133 @@ int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const i
     if (const int rc = check_processors(ctx, penalty[b], ngram[b], min_new[b], "gvl_op_logits_process")) return rc;
     lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
     lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
+  }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
+  return 0;
+}
+
+// ---- token rules (TokenRulesDev, gvl_logits.hip): sequence_bias / bad_words_ids / forced eos / suppress lists as immutable device objects
+static int check_ids(gvl_ctx* ctx, const int32_t* ids, int n, const char* what) {
+  if (n < 0 || (n > 0 && !ids)) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + ": bad list");
+  if (n > GVL_RULES_MAX_IDS) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + " holds " + std::to_string(n) + " ids, the limit is " + std::to_string(GVL_RULES_MAX_IDS));
+  for (int i = 0; i < n; ++i) if (ids[i] < 0) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + ": negative token id");
+  return 0;
+}
+static int check_table(gvl_ctx* ctx, const gvl_bias_table& t, const char* what, int* n_multi) {
+  const std::string w = std::string("gvl_rules_create: ") + what;
+  if (t.n_targets < 0 || t.n_entries < 0 || t.n_prefix < 0 || (t.n_targets > 0 && !t.targets) || (t.n_entries > 0 && (!t.entry_bias || !t.entry_prefix)) || (t.n_prefix > 0 && !t.prefix))
+    return fail(ctx, GVL_ERR_ARG, w + ": bad table");
+  int multi = 0;
+  for (int e = 0; e < t.n_entries; ++e) {
+    const int po = t.entry_prefix[2 * e], pl = t.entry_prefix[2 * e + 1];
+    if (pl < 0 || po < 0) return fail(ctx, GVL_ERR_ARG, w + ": bad prefix range");
+    if (pl + 1 > GVL_RULES_MAX_SEQ_LEN) return fail(ctx, GVL_ERR_ARG, w + ": an entry holds " + std::to_string(pl + 1) + " ids, the limit is " + std::to_string(GVL_RULES_MAX_SEQ_LEN));
+    if ((int64_t)po + pl > t.n_prefix) return fail(ctx, GVL_ERR_ARG, w + ": bad prefix range");
+    multi += pl > 0;
+  }
+  if (multi > GVL_RULES_MAX_SEQS) return fail(ctx, GVL_ERR_ARG, w + " holds " + std::to_string(multi) + " multi-token entries, the limit is " + std::to_string(GVL_RULES_MAX_SEQS));
+  if (t.n_entries - multi > GVL_RULES_MAX_IDS) return fail(ctx, GVL_ERR_ARG, w + " holds " + std::to_string(t.n_entries - multi) + " single-token entries, the limit is " + std::to_string(GVL_RULES_MAX_IDS));
+  if (t.n_targets > t.n_entries) return fail(ctx, GVL_ERR_ARG, w + ": more targets than entries");
+  std::vector<int> seen; seen.reserve(t.n_targets);
+  for (int g = 0; g < t.n_targets; ++g) {
+    const int tk = t.targets[3 * g], e0 = t.targets[3 * g + 1], ne = t.targets[3 * g + 2];
+    if (tk < 0 || e0 < 0 || ne < 1 || (int64_t)e0 + ne > t.n_entries) return fail(ctx, GVL_ERR_ARG, w + ": bad target group");
+    seen.push_back(tk);
+  }
+  for (int i = 0; i < t.n_prefix; ++i) if (t.prefix[i] < 0) return fail(ctx, GVL_ERR_ARG, w + ": negative token id");
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(ctx, GVL_ERR_ARG, w + ": a target token appears in two groups (one thread owns one target)");
+  *n_multi += multi;
+  return 0;
+}
+int gvl_rules_create(gvl_ctx* ctx, const gvl_rules_desc* d, int* rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!d || !rules_id) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: bad arguments");
+  if (const int rc = check_ids(ctx, d->suppress, d->n_suppress, "suppress")) return rc;
+  if (const int rc = check_ids(ctx, d->begin_suppress, d->n_begin_suppress, "begin_suppress")) return rc;
+  if (const int rc = check_ids(ctx, d->force_ids, d->n_force, "force_ids")) return rc;
+  if ((d->n_begin_suppress > 0 && d->begin_index < 0) || (d->n_force > 0 && d->force_at < 0)) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: begin_index / force_at must be >= 0");
+  int n_multi = 0;
+  if (const int rc = check_table(ctx, d->bias[0], "bias[0] (sequence_bias)", &n_multi)) return rc;
+  if (const int rc = check_table(ctx, d->bias[1], "bias[1] (bad_words_ids)", &n_multi)) return rc;
+  int id = -1;
+  for (size_t i = 0; i < ctx->rule_sets.size(); ++i) if (!ctx->rule_sets[i].used) { id = (int)i; break; }
+  if (id < 0) {
+    if ((int)ctx->rule_sets.size() >= gvl_ctx::kMaxRuleSets) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: too many live rule sets (limit 1024)");
+    ctx->rule_sets.emplace_back(); id = (int)ctx->rule_sets.size() - 1;
+  }
+  // the blob: header, then every array, as 32-bit words
+  static_assert(sizeof(TokenRulesDev) % 4 == 0, "header is whole words");
+  std::vector<int32_t> w(sizeof(TokenRulesDev) / 4, 0);
+  TokenRulesDev h; memset(&h, 0, sizeof(h));
+  auto put = [&w](const int32_t* p, size_t n) { const int off = (int)w.size(); if (n) w.insert(w.end(), p, p + n); return off; };
+  h.n_suppress = d->n_suppress; h.off_suppress = put(d->suppress, d->n_suppress);
+  h.n_begin = d->n_begin_suppress; h.off_begin = put(d->begin_suppress, d->n_begin_suppress); h.begin_at = d->begin_index;
+  h.n_force = d->n_force; h.off_force = put(d->force_ids, d->n_force); h.force_at = d->force_at;
+  h.n_multi = n_multi;
+  for (int st = 0; st < 2; ++st) {
+    const gvl_bias_table& t = d->bias[st];
+    h.n_tgt[st] = t.n_targets; h.off_tgt[st] = put(t.targets, (size_t)t.n_targets * 3);
+    h.off_ent[st] = (int)w.size();
+    for (int e = 0; e < t.n_entries; ++e) {
+      int32_t bits; memcpy(&bits, &t.entry_bias[e], 4);
+      w.push_back(bits); w.push_back(t.entry_prefix[2 * e]); w.push_back(t.entry_prefix[2 * e + 1]);
+    }
+    h.off_pre[st] = put(t.prefix, t.n_prefix);
+  }
+  memcpy(w.data(), &h, sizeof(h));
+  RuleSet& r = ctx->rule_sets[id];
+  HIPCHK(ctx, hipMalloc((void**)&r.d, w.size() * 4));
+  const hipError_t e = hipMemcpy(r.d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(r.d); r.d = nullptr; return gvl_hipfail(ctx, e, "gvl_rules_create: hipMemcpy"); }
+  r.used = true; r.refs = 0;
+  *rules_id = id;
+  return 0;
+}
+static int check_rules_id(gvl_ctx* ctx, int id, const char* what) {
+  if (id < -1 || id >= (int)ctx->rule_sets.size() || (id >= 0 && !ctx->rule_sets[id].used)) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": no such rule set");
+  return 0;
+}
+int gvl_rules_destroy(gvl_ctx* ctx, int rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (rules_id < 0) return fail(ctx, GVL_ERR_ARG, "gvl_rules_destroy: no such rule set");
+  if (const int rc = check_rules_id(ctx, rules_id, "gvl_rules_destroy")) return rc;
+  RuleSet& r = ctx->rule_sets[rules_id];
+  if (r.refs > 0) return fail(ctx, GVL_ERR_STATE, "gvl_rules_destroy: the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)");
+  HIPCHK(ctx, hipDeviceSynchronize());                 // every launch that read the set has finished before its memory goes
+  hipFree(r.d);
+  r = RuleSet();
+  return 0;
+}
+int gvl_set_token_rules(gvl_ctx* ctx, int rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = check_rules_id(ctx, rules_id, "gvl_set_token_rules")) return rc;
+  rules_ref(ctx, rules_id); rules_unref(ctx, ctx->rules_default);
+  ctx->rules_default = rules_id;
+  return 0;
+}
+int gvl_seq_set_token_rules(gvl_ctx* ctx, int seq_id, int rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_token_rules: bad seq");
+  if (const int rc = check_rules_id(ctx, rules_id, "gvl_seq_set_token_rules")) return rc;
+  rules_ref(ctx, rules_id); rules_unref(ctx, ctx->seqs[seq_id].rules);
+  ctx->seqs[seq_id].rules = rules_id;
+  return 0;
+}
+int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                                const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
+  if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || !rules_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
+      hist_stride < 0 || (hist_stride > 0 && !hist_dev))
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process_rules: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
+  lp.logits = logits; lp.n = n; lp.ld = n; lp.batch = batch; lp.cap = hist_stride < GVL_LOGITS_HIST_CAP ? hist_stride : GVL_LOGITS_HIST_CAP;
+  for (int b = 0; b < batch; ++b) {
+    if (const int rc = check_processors(ctx, penalty[b], ngram[b], min_new[b], "gvl_op_logits_process_rules")) return rc;
+    if (const int rc = check_rules_id(ctx, rules_ids[b], "gvl_op_logits_process_rules")) return rc;
+    lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
+    lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
+    lp.rules[b] = rules_ids[b] >= 0 ? ctx->rule_sets[rules_ids[b]].d : nullptr;
   }
   RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
   return 0;

@@ -10,6 +10,7 @@ import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -397,9 +398,10 @@ class Engine:
         self._chk(self.lib.gvl_decode_step_logits_batch(self.ctx, ids, n, tk, _ptr(logits), self.stream), "gvl_decode_step_logits_batch")
         return logits
 
-    def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None):
+    def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None,
+                     rules: Optional[int] = None):
         """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  processors: a logits.Processors for this
-        sequence (None: the default of set_logits_processors).  logprobs: None = ids only; -1 .. 8 = this sequence's seq_set_logprobs setting, and
+        sequence (None: the default of set_logits_processors).  rules: a rule-set id for this sequence (None: the default of set_token_rules).  logprobs: None = ids only; -1 .. 8 = this sequence's seq_set_logprobs setting, and
         the return value is (ids, (lp, top)) as seq_read_logprobs gives them for the ids (read before the sequence is freed)."""
         S = embeds.shape[0]
         seq = self.seq_alloc(min(S + max_new_tokens, self.geo.max_seq))
@@ -408,6 +410,8 @@ class Engine:
                 self.seq_set_processors(seq, *processors.args())
             if logprobs is not None:
                 self.seq_set_logprobs(seq, logprobs)
+            if rules is not None:
+                self.seq_set_token_rules(seq, rules)
             self.prefill(seq, embeds)
             ids = self.decode_greedy(seq, max_new_tokens, eos_id)
             if logprobs is None:
@@ -519,9 +523,11 @@ class Engine:
         self._chk(self.lib.gvl_seq_set_processors(self.ctx, int(seq), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
                                                   -1 if eos_id is None else int(eos_id)), "gvl_seq_set_processors")
 
-    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos):
+    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos, rules=None):
         """gvl_op_logits_process on fp32 rows [B, n] (any B; 16 rows per launch): row b gets the processors (penalty[b], ngram[b], min_new[b],
-        eos[b]) over the history histories[b].  `logits` must be a contiguous fp32 device tensor: it is changed IN PLACE and returned."""
+        eos[b]) over the history histories[b].  `logits` must be a contiguous fp32 device tensor: it is changed IN PLACE and returned.
+        rules: None, one rule-set id (rules_create) for every row, or a list with an id or None per row -- then gvl_op_logits_process_rules
+        runs the whole ordered pipeline (token rules around the processors)."""
         assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2 and logits.device == self.device
         B, n = logits.shape
         assert len(histories) == B
@@ -534,12 +540,58 @@ class Engine:
         lens = torch.tensor([len(h) for h in histories], dtype=torch.int32, device=self.device)
         per_row = lambda v, t: [t(x) for x in (v if isinstance(v, (list, tuple)) else [v] * B)]
         pe, ng, mn, eo = per_row(penalty, float), per_row(ngram, int), per_row(min_new, int), per_row(eos, lambda x: -1 if x is None else int(x))
+        ru = None if rules is None else per_row(rules, lambda x: -1 if x is None else int(x))
         for b0 in range(0, B, 16):
             nb = min(16, B - b0)
-            self._chk(self.lib.gvl_op_logits_process(self.ctx, C.c_void_p(logits.data_ptr() + b0 * n * 4), n, nb, C.c_void_p(hist.data_ptr() + b0 * width * 4),
-                                                     width, C.c_void_p(lens.data_ptr() + b0 * 4), (C.c_float * nb)(*pe[b0:b0 + nb]), (C.c_int * nb)(*ng[b0:b0 + nb]),
-                                                     (C.c_int * nb)(*mn[b0:b0 + nb]), (C.c_int * nb)(*eo[b0:b0 + nb]), self.stream), "gvl_op_logits_process")
+            args = (self.ctx, C.c_void_p(logits.data_ptr() + b0 * n * 4), n, nb, C.c_void_p(hist.data_ptr() + b0 * width * 4),
+                    width, C.c_void_p(lens.data_ptr() + b0 * 4), (C.c_float * nb)(*pe[b0:b0 + nb]), (C.c_int * nb)(*ng[b0:b0 + nb]),
+                    (C.c_int * nb)(*mn[b0:b0 + nb]), (C.c_int * nb)(*eo[b0:b0 + nb]))
+            if ru is None:
+                self._chk(self.lib.gvl_op_logits_process(*args, self.stream), "gvl_op_logits_process")
+            else:
+                self._chk(self.lib.gvl_op_logits_process_rules(*args, (C.c_int * nb)(*ru[b0:b0 + nb]), self.stream), "gvl_op_logits_process_rules")
         return logits
+
+    # ---- token rules (logits.TokenRules -> a device rule set) ---------------------------------------------------
+    def rules_create(self, rules) -> int:
+        """gvl_rules_create: a logits.TokenRules (or anything with its fields) as an immutable device rule set; returns its id.  Raises GvlError
+        (status ERR_ARG, with the library's message) for a set beyond the library's capacities."""
+        keep = []
+
+        def ints(v):
+            a = np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1))
+            keep.append(a)
+            return len(a), a.ctypes.data_as(C.POINTER(C.c_int32))
+        d = L.GvlRulesDesc()
+        d.n_suppress, d.suppress = ints(rules.suppress)
+        d.n_begin_suppress, d.begin_suppress = ints(rules.begin_suppress)
+        d.begin_index = int(rules.begin_index)
+        d.n_force, d.force_ids = ints(rules.force_ids)
+        d.force_at = int(rules.force_at)
+        for st, t in enumerate((rules.sequence_bias, rules.bad_words)):
+            bt = d.bias[st]
+            n3, bt.targets = ints(t.targets)
+            bt.n_targets = n3 // 3
+            eb = np.ascontiguousarray(np.asarray(t.entry_bias, dtype=np.float32).reshape(-1))
+            keep.append(eb)
+            bt.n_entries, bt.entry_bias = len(eb), eb.ctypes.data_as(C.POINTER(C.c_float))
+            _, bt.entry_prefix = ints(t.entry_prefix)
+            bt.n_prefix, bt.prefix = ints(t.prefix)
+        rid = C.c_int(-1)
+        self._chk(self.lib.gvl_rules_create(self.ctx, C.byref(d), C.byref(rid)), "gvl_rules_create")
+        return rid.value
+
+    def rules_destroy(self, rules_id: int):
+        """gvl_rules_destroy: GvlError (ERR_STATE) while a live sequence or the default still references the set."""
+        self._chk(self.lib.gvl_rules_destroy(self.ctx, int(rules_id)), "gvl_rules_destroy")
+
+    def set_token_rules(self, rules_id: Optional[int] = None):
+        """gvl_set_token_rules: the rule set of every sequence allocated AFTER this call (None / -1: none)."""
+        self._chk(self.lib.gvl_set_token_rules(self.ctx, -1 if rules_id is None else int(rules_id)), "gvl_set_token_rules")
+
+    def seq_set_token_rules(self, seq: int, rules_id: Optional[int]):
+        """gvl_seq_set_token_rules: the rule set of one live sequence (None / -1: none)."""
+        self._chk(self.lib.gvl_seq_set_token_rules(self.ctx, int(seq), -1 if rules_id is None else int(rules_id)), "gvl_seq_set_token_rules")
 
     def set_logprobs(self, top_n: Optional[int] = -1):
         """gvl_set_logprobs: log-probabilities of the selected tokens for every sequence allocated AFTER this call.  None / -1 = off, 0 = the selected

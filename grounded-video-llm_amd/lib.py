@@ -33,6 +33,18 @@ class GvlConfig(C.Structure):
     ]
 
 
+class GvlBiasTable(C.Structure):
+    """gvl_bias_table (include/gvl.h): one bias stage of a token rule set, grouped by target token."""
+    _fields_ = [("n_targets", C.c_int32), ("targets", C.POINTER(C.c_int32)), ("n_entries", C.c_int32), ("entry_bias", C.POINTER(C.c_float)),
+                ("entry_prefix", C.POINTER(C.c_int32)), ("n_prefix", C.c_int32), ("prefix", C.POINTER(C.c_int32))]
+
+
+class GvlRulesDesc(C.Structure):
+    """gvl_rules_desc (include/gvl.h)."""
+    _fields_ = [("n_suppress", C.c_int32), ("suppress", C.POINTER(C.c_int32)), ("n_begin_suppress", C.c_int32), ("begin_suppress", C.POINTER(C.c_int32)),
+                ("begin_index", C.c_int32), ("n_force", C.c_int32), ("force_ids", C.POINTER(C.c_int32)), ("force_at", C.c_int32), ("bias", GvlBiasTable * 2)]
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "gvl_create": (C.c_int, [C.POINTER(GvlConfig), C.POINTER(C.c_void_p)]),
@@ -91,6 +103,12 @@ _SIGS = {
     "gvl_seq_set_processors": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]),
     "gvl_op_logits_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "gvl_rules_create": (C.c_int, [C.c_void_p, C.POINTER(GvlRulesDesc), C.POINTER(C.c_int)]),
+    "gvl_rules_destroy": (C.c_int, [C.c_void_p, C.c_int]),
+    "gvl_set_token_rules": (C.c_int, [C.c_void_p, C.c_int]),
+    "gvl_seq_set_token_rules": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "gvl_op_logits_process_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "gvl_set_logprobs": (C.c_int, [C.c_void_p, C.c_int]),
     "gvl_seq_set_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gvl_seq_read_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -13,13 +13,29 @@ Semantics (transformers 4.40.1 as the reference pins; the installed 5.x agrees o
   * min_length with inputs_embeds is lowered by the embedding length: max(min_length - inputs_embeds.shape[1], 0); min_new_tokens, when given,
     takes precedence (min_length = min_new_tokens + 0).  For a batch the embedding length is the reference's PADDED batch length (its rows are
     stacked at one length, llava_next_video.py:568-594): left-padded id length - 1 + visual rows.
+
+Token rules (`sequence_bias`, `bad_words_ids`, `forced_eos_token_id`, `suppress_tokens`, `begin_suppress_tokens`) are the other token-level
+processors of `_get_logits_processor`; `resolve_rules` validates them as HF does and flattens them into the arrays of a device rule set
+(gvl_rules_create).  The whole order is
+  sequence_bias -> repetition penalty -> no-repeat n-gram -> bad_words_ids -> min_length / min_new_tokens -> forced_eos_token_id
+    -> suppress_tokens -> begin_suppress_tokens -> warpers.
+As the installed transformers computes them with inputs_embeds and no input_ids:
+  * sequence_bias / bad_words_ids: per target token (an entry's last id) an fp32 sum from 0.0: the length-1 entry, then, in dict order, the
+    multi-token entries whose first len - 1 ids equal the last len - 1 generated ids; the sum is added to the score once.  An entry is skipped
+    while it is LONGER THAN THE HISTORY (`len(sequence_ids) > input_ids.shape[1]`): a 2-token entry first applies at the third new token.
+    bad_words_ids is the same mechanism with bias -inf, entries equal to [eos] dropped.
+  * forced_eos_token_id: when max_new_tokens - 1 ids were generated every score becomes -inf and the forced ids' scores 0.
+  * suppress_tokens: -inf at every step; begin_suppress_tokens: -inf only while nothing was generated yet (begin_index 0).
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional
 
-KWARGS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "min_length")
+import numpy as np
+
+RULE_KWARGS = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "suppress_tokens", "begin_suppress_tokens")
+KWARGS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "min_length") + RULE_KWARGS
 
 
 @dataclass(frozen=True)
@@ -75,3 +91,160 @@ def resolve(kw: dict, eos_id: Optional[int], embed_len: int = 0) -> Processors:
 def padded_embed_len(ids_width: int, n_visual: int) -> int:
     """Rows of the reference's inputs_embeds for a batch whose left-padded id rows are `ids_width` wide (one image slot -> n_visual rows)."""
     return int(ids_width) - 1 + int(n_visual)
+
+
+# ---- token rules -----------------------------------------------------------------------------------------------------------------
+MAX_IDS = 1 << 18        # ids of one single-token list / single-token entries of one bias table (GVL_RULES_MAX_IDS)
+MAX_SEQS = 1024          # multi-token entries of one bias table (GVL_RULES_MAX_SEQS)
+MAX_SEQ_LEN = 16         # ids of one multi-token entry (GVL_RULES_MAX_SEQ_LEN)
+
+
+@dataclass(frozen=True)
+class BiasTable:
+    """{ids: bias} grouped by target token (an entry's last id) for the device: one thread owns one target and sums its entries in order.
+    targets: (target, first_entry, n_entries); entry e: bias entry_bias[e] (fp32 value) and the prefix ids prefix[off : off + len] with
+    (off, len) = entry_prefix[e].  Within a group the length-1 entry comes first, then the multi-token entries in dict order."""
+    targets: tuple = ()
+    entry_bias: tuple = ()
+    entry_prefix: tuple = ()
+    prefix: tuple = ()
+
+    def to_dict(self) -> dict:
+        out = {}
+        for t, e0, ne in self.targets:
+            for e in range(e0, e0 + ne):
+                off, ln = self.entry_prefix[e]
+                out[tuple(self.prefix[off:off + ln]) + (t,)] = self.entry_bias[e]
+        return out
+
+
+def group_by_target(bias: dict, what: str = "sequence_bias") -> BiasTable:
+    """dict {tuple of ids: float} -> BiasTable.  Raises ValueError beyond the capacities of the device rule set (nothing is truncated)."""
+    groups: dict = {}
+    n_multi = 0
+    for ids, b in bias.items():
+        ids = tuple(int(t) for t in ids)
+        if len(ids) > MAX_SEQ_LEN:
+            raise ValueError(f"`{what}`: an entry of {len(ids)} ids exceeds the limit of {MAX_SEQ_LEN} ids per entry")
+        n_multi += len(ids) > 1
+        g = groups.setdefault(ids[-1], [[], []])
+        g[0 if len(ids) == 1 else 1].append((ids[:-1], float(np.float32(b))))
+    if n_multi > MAX_SEQS:
+        raise ValueError(f"`{what}`: {n_multi} multi-token entries exceed the limit of {MAX_SEQS}")
+    if len(bias) - n_multi > MAX_IDS:
+        raise ValueError(f"`{what}`: {len(bias) - n_multi} single-token entries exceed the limit of {MAX_IDS}")
+    targets, eb, ep, pre = [], [], [], []
+    for t, (single, multi) in groups.items():
+        targets.append((t, len(eb), len(single) + len(multi)))
+        for ids, b in single + multi:
+            eb.append(b)
+            ep.append((len(pre), len(ids)))
+            pre.extend(ids)
+    return BiasTable(tuple(targets), tuple(eb), tuple(ep), tuple(pre))
+
+
+@dataclass(frozen=True)
+class TokenRules:
+    """One generate() call's token rules as the device takes them (gvl_rules_create); the defaults switch every rule off."""
+    suppress: tuple = ()
+    begin_suppress: tuple = ()
+    begin_index: int = 0
+    force_ids: tuple = ()          # forced_eos_token_id(s); applied when exactly force_at ids were generated
+    force_at: int = 0
+    sequence_bias: BiasTable = field(default_factory=BiasTable)
+    bad_words: BiasTable = field(default_factory=BiasTable)
+
+    @property
+    def active(self) -> bool:
+        return bool(self.suppress or self.begin_suppress or self.force_ids or self.sequence_bias.targets or self.bad_words.targets)
+
+
+NO_RULES = TokenRules()
+
+
+def _validate_sequence_bias(sequence_bias):
+    """SequenceBiasLogitsProcessor._validate_arguments + _convert_list_arguments_into_dict, with HF's messages."""
+    if not isinstance(sequence_bias, dict) and not isinstance(sequence_bias, list) or len(sequence_bias) == 0:
+        raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sequence_bias}.")
+    if isinstance(sequence_bias, dict) and any(not isinstance(ids, tuple) for ids in sequence_bias):
+        raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sequence_bias}.")
+    if isinstance(sequence_bias, dict) and any(
+            any((not isinstance(t, (int, np.integer)) or t < 0) for t in ids) or len(ids) == 0 for ids in sequence_bias):
+        raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sequence_bias}.")
+
+    def pair_ok(seq):
+        return isinstance(seq[0], list) and all(isinstance(t, (int, np.integer)) and t > 0 for t in seq[0]) and isinstance(seq[1], float)
+    if isinstance(sequence_bias, list) and any((not pair_ok(seq)) or len(seq) == 0 for seq in sequence_bias):
+        raise ValueError(f"Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, but is {sequence_bias}.")
+    if isinstance(sequence_bias, dict) and any(not isinstance(b, float) for b in sequence_bias.values()):
+        raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sequence_bias}.")
+    if isinstance(sequence_bias, list):
+        return {tuple(seq[0]): seq[1] for seq in sequence_bias}
+    return dict(sequence_bias)
+
+
+def _validate_bad_words(bad_words_ids, eos_id):
+    """NoBadWordsLogitsProcessor.__init__: HF's messages, [eos] entries dropped, every sequence -> bias -inf."""
+    if not isinstance(bad_words_ids, list) or len(bad_words_ids) == 0:
+        raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+    if any(not isinstance(w, list) for w in bad_words_ids):
+        raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad_words_ids}.")
+    if any(any((not isinstance(t, (int, np.integer)) or t < 0) for t in w) for w in bad_words_ids):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+    if any(len(w) == 0 for w in bad_words_ids):                                # HF: an IndexError at the first call
+        raise ValueError(f"Each list in `bad_words_ids` has to be non-empty, but is {bad_words_ids}.")
+    if eos_id is not None and eos_id >= 0:
+        bad_words_ids = [w for w in bad_words_ids if w != [eos_id]]
+    return {tuple(w): float("-inf") for w in bad_words_ids}                    # may be empty (only [eos] given): HF then bans nothing
+
+
+def _id_list(ids, what: str, vocab: Optional[int]) -> tuple:
+    """suppress lists: HF builds torch.tensor(list(ids)) and masks with isin, so ids outside the vocabulary never match; they are dropped here."""
+    out = []
+    for t in list(ids):
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+            raise ValueError(f"`{what}` has to be a list of integers, but is {ids}.")
+        if t >= 0 and (vocab is None or t < vocab):
+            out.append(int(t))
+    out = tuple(dict.fromkeys(out))
+    if len(out) > MAX_IDS:
+        raise ValueError(f"`{what}`: {len(out)} ids exceed the limit of {MAX_IDS}")
+    return out
+
+
+def resolve_rules(kw: dict, eos_id: Optional[int], max_new: int, vocab: Optional[int] = None) -> TokenRules:
+    """HF kwargs -> TokenRules for one reference generate(inputs_embeds=..., max_new_tokens=max_new) call.  Raises HF's ValueErrors with HF's
+    messages, and ValueError for a rule set beyond the device capacities.  vocab (when known) enables HF's vocabulary check of the biased ids."""
+    sb, bw = BiasTable(), BiasTable()
+    if kw.get("sequence_bias") is not None:
+        d = _validate_sequence_bias(kw["sequence_bias"])
+        if vocab is not None:                                                 # SequenceBiasLogitsProcessor._prepare_bias_variables
+            bad = [t for ids in d for t in ids if t >= vocab]
+            if bad:
+                raise ValueError(f"The model vocabulary size is {vocab}, but the following tokens were being biased: {bad}")
+        sb = group_by_target(d, "sequence_bias")
+    if kw.get("bad_words_ids") is not None:
+        d = _validate_bad_words(kw["bad_words_ids"], eos_id)
+        if vocab is not None:
+            bad = [t for ids in d for t in ids if t >= vocab]
+            if bad:
+                raise ValueError(f"The model vocabulary size is {vocab}, but the following tokens were being biased: {bad}")
+        bw = group_by_target(d, "bad_words_ids")
+    force, force_at = (), 0
+    fe = kw.get("forced_eos_token_id")
+    if fe is not None:
+        ids = [fe] if isinstance(fe, (int, np.integer)) and not isinstance(fe, bool) else list(fe)
+        if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0 for t in ids):    # ForcedEOSTokenLogitsProcessor.__init__
+            import torch
+            raise ValueError(f"`eos_token_id` has to be a list of positive integers, but is {torch.tensor(ids)}")
+        if vocab is not None and any(t >= vocab for t in ids):
+            raise ValueError(f"`forced_eos_token_id` {ids} outside the vocabulary of {vocab} tokens")   # HF: an IndexError at the forced step
+        force = tuple(dict.fromkeys(int(t) for t in ids))
+        if len(force) > MAX_IDS:
+            raise ValueError(f"`forced_eos_token_id`: {len(force)} ids exceed the limit of {MAX_IDS}")
+        force_at = int(max_new) - 1
+        if force_at < 0:
+            force = ()
+    sup = _id_list(kw["suppress_tokens"], "suppress_tokens", vocab) if kw.get("suppress_tokens") is not None else ()
+    beg = _id_list(kw["begin_suppress_tokens"], "begin_suppress_tokens", vocab) if kw.get("begin_suppress_tokens") is not None else ()
+    return TokenRules(sup, beg, 0, force, force_at, sb, bw)

@@ -251,6 +251,25 @@ class LLAVA_NEXT_VIDEO:
         self.engine.set_logits_processors(*(LP.OFF if beams else procs).args())
         return procs
 
+    def _select_rules(self, kw, max_new: int) -> Optional[int]:
+        """HF's token rules (sequence_bias, bad_words_ids, forced_eos_token_id, suppress_tokens, begin_suppress_tokens; logits.resolve_rules) as a
+        device rule set.  Sets the engine's default on EVERY generate call -- none when absent, and none for beam search, which passes the set
+        to its own processing of the log-softmax rows -- so nothing carries over.  Returns the rule set's id (None: no rules); the caller
+        clears the default and destroys the set in a `finally` (_drop_rules)."""
+        rules = LP.resolve_rules(kw, getattr(self.tokenizer, "eos_token_id", None), max_new, self.geo.vocab)
+        self.engine.set_token_rules(None)
+        if not rules.active:
+            return None
+        rid = self.engine.rules_create(rules)
+        if kw.get("num_beams", 1) in (1, None):
+            self.engine.set_token_rules(rid)
+        return rid
+
+    def _drop_rules(self, rid: Optional[int]):
+        self.engine.set_token_rules(None)
+        if rid is not None:
+            self.engine.rules_destroy(rid)
+
     def _select_logprobs(self, kw) -> "LPR.Options":
         """return_dict_in_generate / output_scores / top_logprobs (logprobs.py; raises its ValueErrors).  Sets the engine's default on EVERY generate
         call -- the call's setting, off for beam search (its scores come from beam.py) -- so nothing carries over from one call to the next."""
@@ -287,7 +306,11 @@ class LLAVA_NEXT_VIDEO:
     def generate(self, samples, **generate_kwargs):
         """The reference's generate(samples, **generate_kwargs).  Besides greedy / sampling / beam search it honours HF's repetition_penalty,
         no_repeat_ngram_size and min_new_tokens / min_length (logits.py; applied on the device to the generated ids only, as HF does for an
-        inputs_embeds prompt).  Other HF logits processors (bad_words_ids, sequence_bias, suppress_tokens, ...) are not supported and ignored.
+        inputs_embeds prompt), and the token rules sequence_bias, bad_words_ids, forced_eos_token_id, suppress_tokens and begin_suppress_tokens,
+        in HF's order (logits.py), with HF's validation errors; a rule set beyond the device capacities raises ValueError.  Still not supported
+        and ignored: bad_words_ids=None, prefix_allowed_tokens_fn, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
+        remove_invalid_values, exponential_decay_length_penalty, guidance_scale, diversity / constrained beams (num_beam_groups, constraints,
+        force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p.
         return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
         log-probabilities; logprobs.py) instead of the list of texts."""
         if any(v == "text" for v in samples.get("video_ids", [])):
@@ -301,6 +324,13 @@ class LLAVA_NEXT_VIDEO:
         procs = self._select_processors(generate_kwargs, LP.padded_embed_len(ids_arr.shape[1], self._n_visual(samples)))
         self._select_tokens(generate_kwargs)
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
+        rid = self._select_rules(generate_kwargs, max_new)
+        try:
+            return self._generate(samples, generate_kwargs, ids_arr, mask, opts, procs, max_new, rid)
+        finally:
+            self._drop_rules(rid)
+
+    def _generate(self, samples, generate_kwargs, ids_arr, mask, opts, procs, max_new: int, rid: Optional[int]):
         feats = self.encode_images(samples)
         k = generate_kwargs.get("num_beams", 1) or 1
         lps, beam_scores = None, None
@@ -321,7 +351,7 @@ class LLAVA_NEXT_VIDEO:
             scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs, with_scores=scored)
+                                              processors=procs, with_scores=scored, rules=rid)
                        for b in range(ids_arr.shape[0])]
             if scored:
                 lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
@@ -336,14 +366,15 @@ class LLAVA_NEXT_VIDEO:
         return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps, beam_scores)
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
-                          sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False):
+                          sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
+                          rules: Optional[int] = None):
         """generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
         teacher-forced batched decode step per token (gvl_decode_step_logits_batch: one stream of the weights for the k beams); log-softmax / top-2k of the step run on the device (torch), the bookkeeping on
         the host.  processors: HF's logits processors, applied by gvl_op_logits_process to every step's log-softmax rows before the beam scores
         are added (HF _beam_search / _beam_sample); the beams' own sequences select their tokens without them (their raw logits are what the
-        steps return).  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them."""
+        steps return).  rules: a rule-set id (Engine.rules_create) applied in the same pass, in HF's order.  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them."""
         from . import beam as B
         eng = self.engine
         gi = eng.decode_group_info()                     # which group sizes ONE batched step takes: asked from the library, not restated here
@@ -353,13 +384,16 @@ class LLAVA_NEXT_VIDEO:
         beams: List[Optional[int]] = [eng.seq_alloc(cap)]
         fresh: List[int] = []                            # clones of the step in progress: owned here until they are installed in `beams`
         process = None
-        if processors is not None and processors.active:
-            pa = processors.args()
+        if (processors is not None and processors.active) or rules is not None:
+            pa = (processors if processors is not None else LP.OFF).args()
 
             def process(histories: List[List[int]], logprobs: torch.Tensor) -> torch.Tensor:
-                return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
+                if rules is None:
+                    return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
+                return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules)
         try:
             eng.seq_set_processors(beams[0], *LP.OFF.args())     # the steps must hand back raw logits (clones copy this setting)
+            eng.seq_set_token_rules(beams[0], None)
             eng.seq_set_logprobs(beams[0], -1)                   # the scores come from the host rows (beam.py)
             first = eng.prefill(beams[0], emb, want_logits=True)
 
@@ -409,11 +443,15 @@ class LLAVA_NEXT_VIDEO:
         self._select_processors(generate_kwargs, LP.padded_embed_len(len(rows[0]), n_vis) if rows else 0)
         self._select_tokens(generate_kwargs)
         procs = [LP.resolve(generate_kwargs, getattr(self.tokenizer, "eos_token_id", None), LP.padded_embed_len(len(r), n_vis)) for r in rows]
-        feats = self.encode_images(samples)
-        want = opts.top_n if opts.top_n >= 0 else None
-        res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want)
-        if res is None:                                  # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
-            res = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs, logprobs=want)
+        rid = self._select_rules(dict(generate_kwargs, num_beams=1), max_new)    # token rules: every sequence allocated below starts with them
+        try:
+            feats = self.encode_images(samples)
+            want = opts.top_n if opts.top_n >= 0 else None
+            res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want)
+            if res is None:                              # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
+                res = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs, logprobs=want)
+        finally:
+            self._drop_rules(rid)
         out_ids, lps = res if want is not None else (res, None)
         texts = [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
         if not opts.return_dict:

@@ -34,6 +34,8 @@ class _Request:
     n_gen: int = 0               # tokens generated on the device so far (>= len(ids) once eos was seen)
     processors: object = None    # logits.Processors of this request (None: the engine's default)
     logprobs: Optional[int] = None   # gvl_seq_set_logprobs setting of this request (None: the engine's default, not read back)
+    rules: object = None         # logits.TokenRules of this request (None: the engine's default)
+    rules_id: Optional[int] = None   # its device rule set: created when the request is admitted, destroyed when it retires
 
 
 class ClipScheduler:
@@ -53,12 +55,16 @@ class ClipScheduler:
 
     # ---- public ------------------------------------------------------------------------------------------
     def submit(self, embeds, max_new_tokens: int, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-               min_new_tokens: Optional[int] = None, logprobs: Optional[int] = None) -> int:
+               min_new_tokens: Optional[int] = None, logprobs: Optional[int] = None, bad_words_ids=None, sequence_bias=None, suppress_tokens=None,
+               begin_suppress_tokens=None, forced_eos_token_id=None) -> int:
         """Queue one request.  repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors for THIS request (HF's validation;
         applied on the device to its generated ids; min_new_tokens needs the scheduler's eos id).  Requests with different settings share one
         decode group.  None for all three: the sequence keeps the engine's default (Engine.set_logits_processors).
         logprobs: 0 = the log-probability of every generated id, 1 .. 8 = also its top N alternatives (Engine.seq_set_logprobs); read back
-        with logprobs(rid) once the request finished."""
+        with logprobs(rid) once the request finished.
+        bad_words_ids / sequence_bias / suppress_tokens / begin_suppress_tokens / forced_eos_token_id: HF's token rules for THIS request
+        (logits.resolve_rules: HF's validation; forced eos at this request's max_new_tokens); its device rule set lives from admission to
+        retirement.  None for all five: the sequence keeps the engine's default (Engine.set_token_rules)."""
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
@@ -67,7 +73,13 @@ class ClipScheduler:
         if repetition_penalty is not None or no_repeat_ngram_size is not None or min_new_tokens is not None:
             from . import logits as LP
             procs = LP.resolve(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens), self.eos)
-        r = _Request(self._next, embeds, int(max_new_tokens), processors=procs, logprobs=logprobs)
+        rules = None
+        rkw = dict(bad_words_ids=bad_words_ids, sequence_bias=sequence_bias, suppress_tokens=suppress_tokens,
+                   begin_suppress_tokens=begin_suppress_tokens, forced_eos_token_id=forced_eos_token_id)
+        if any(v is not None for v in rkw.values()):
+            from . import logits as LP
+            rules = LP.resolve_rules(rkw, self.eos, int(max_new_tokens), getattr(getattr(self.eng, "geo", None), "vocab", None))
+        r = _Request(self._next, embeds, int(max_new_tokens), processors=procs, logprobs=logprobs, rules=rules)
         self._next += 1
         self.queue.append(r)
         return r.rid
@@ -124,14 +136,18 @@ class ClipScheduler:
                 if getattr(e, "status", 0) == L.ERR_OOM:     # KV pages exhausted: wait for a retirement (FIFO, no overtaking)
                     break
                 raise
-            if r.processors is not None or r.logprobs is not None:
+            if r.processors is not None or r.logprobs is not None or r.rules is not None:
                 try:
                     if r.processors is not None:
                         self.eng.seq_set_processors(r.seq, *r.processors.args())
                     if r.logprobs is not None:
                         self.eng.seq_set_logprobs(r.seq, r.logprobs)
+                    if r.rules is not None:                  # an inactive set still overrides the engine's default: this request runs without rules
+                        r.rules_id = self.eng.rules_create(r.rules) if r.rules.active else None
+                        self.eng.seq_set_token_rules(r.seq, r.rules_id)
                 except Exception:
                     self.eng.seq_free(r.seq)
+                    self._drop_rules(r)
                     raise
             r.max_new = min(r.max_new, cap - S + 1)          # generate() stops at the context limit (Engine.generate_ids does too)
             self.queue.popleft()
@@ -145,6 +161,11 @@ class ClipScheduler:
                 r.embeds = None                              # the KV cache holds it now
             self.active += new
             self.stats["max_concurrent"] = max(self.stats["max_concurrent"], len(self.active))
+
+    def _drop_rules(self, r: _Request):
+        if r.rules_id is not None:
+            rid, r.rules_id = r.rules_id, None
+            self.eng.rules_destroy(rid)
 
     def _retire(self) -> List[int]:
         finished, keep = [], []
@@ -161,6 +182,7 @@ class ClipScheduler:
                 if r.logprobs is not None:                   # before the slot is freed: its lists are reused by the next sequence
                     self.done_logprobs[r.rid] = self.eng.seq_read_logprobs(r.seq, 0, len(r.ids), top=r.logprobs > 0)
                 self.eng.seq_free(r.seq)                     # seq_read synchronised the stream: no step of r is in flight
+                self._drop_rules(r)
                 self.done[r.rid] = r.ids
                 finished.append(r.rid)
             else:

@@ -180,6 +180,37 @@ int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, 
  * empty: its generation count restarts at 0).  Errors: penalty not > 0 (NaN included), ngram < 0, min_new < 0. */
 int gvl_set_logits_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, int eos_id);
 int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, int min_new, int eos_id);
+/* Token rules: HF's other token-level processors (SequenceBias, NoBadWords, ForcedEOSToken, SuppressTokens, SuppressTokensAtBegin), applied by the
+ * same launch as the processors above, in HF's order:
+ *   sequence_bias -> repetition penalty -> no-repeat n-gram -> bad_words_ids -> min length -> forced eos -> suppress -> begin suppress
+ * A rule set is an immutable device-resident object made from host arrays (copied; gvl_rules_create synchronises).  A bias table is grouped
+ * BY TARGET TOKEN (the last id of an entry): targets [n_targets][3] = (target id, first entry, number of entries), the targets distinct;
+ * entry e has bias entry_bias[e] and the prefix ids prefix[entry_prefix[2e] .. + entry_prefix[2e + 1]) (the entry's ids without its last;
+ * length 0 = a single-token entry, which comes first in its group; the multi-token entries follow in the caller's dict order).  For each
+ * target the applicable entries' biases are summed in fp32 from 0.0f in that order and the sum is added to the score once; a multi-token entry
+ * applies when its prefix equals the last ids of the history and its length does not exceed the history's (HF's rule).  bias[0] runs before
+ * the penalty (sequence_bias), bias[1] after the n-gram bans (bad_words_ids: bias -inf).  force_ids (n_force > 0): when the history holds
+ * exactly force_at ids every score becomes -inf and the forced ids' scores 0.  suppress: -inf at every step; begin_suppress: -inf when the
+ * history holds exactly begin_index ids.  Ids outside the row are ignored.  Limits (GVL_ERR_ARG with a message beyond them, never truncated):
+ * 262144 ids per single-token list and single-token entries per table, 1024 multi-token entries per table, 16 ids per entry, 1024 live sets.
+ * gvl_set_token_rules sets the default (a rule-set id, or -1 = none) of every sequence allocated AFTER the call; gvl_seq_set_token_rules one
+ * live sequence; gvl_seq_fork / gvl_seq_clone copy the source's, gvl_seq_free drops it.  gvl_rules_destroy of a set that a live sequence or
+ * the default still references is GVL_ERR_STATE; it synchronises the device before the memory is released.  gvl_destroy frees every set. */
+typedef struct {
+  int32_t n_targets; const int32_t* targets;
+  int32_t n_entries; const float* entry_bias; const int32_t* entry_prefix;
+  int32_t n_prefix; const int32_t* prefix;
+} gvl_bias_table;
+typedef struct {
+  int32_t n_suppress; const int32_t* suppress;
+  int32_t n_begin_suppress; const int32_t* begin_suppress; int32_t begin_index;
+  int32_t n_force; const int32_t* force_ids; int32_t force_at;
+  gvl_bias_table bias[2];
+} gvl_rules_desc;
+int gvl_rules_create(gvl_ctx* ctx, const gvl_rules_desc* desc, int* rules_id);
+int gvl_rules_destroy(gvl_ctx* ctx, int rules_id);
+int gvl_set_token_rules(gvl_ctx* ctx, int rules_id);
+int gvl_seq_set_token_rules(gvl_ctx* ctx, int seq_id, int rules_id);
 /* Log-probabilities of the selected tokens, computed on the device by the token-selection kernel itself (prefill's first token,
  * gvl_decode_greedy*, gvl_decode_steps; greedy and sampling alike; graph-replayed steps included).  The distribution is the one the token
  * was selected from: greedy, log_softmax of the row after the logits processors, (s_tok - m) - log(sum_i exp(s_i - m)); sampling, the
@@ -368,6 +399,9 @@ int gvl_op_sample(gvl_ctx* ctx, const float* logits, int n, int batch, float tem
  * min(hist_stride, 8192)); per-row parameters are host arrays with gvl_set_logits_processors' meaning.  batch <= 16. */
 int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
                           const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, void* stream);
+/* gvl_op_logits_process plus one rule-set id per row (host array; -1 = no rules): the whole ordered pipeline on raw rows. */
+int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                                const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream);
 /* Token selection with log-probabilities on its own (operator tests): greedy (do_sample = 0; streams / steps_dev may be null) or
  * gvl_op_sample's draw; row b with top_n[b] >= 0 (host array) stores its token's log-probability at lp_dev[b], and for top_n[b] >= 1
  * its top list at top_ids_dev / top_lp_dev [b * 8 ..) (gvl_set_logprobs' meaning).  batch <= 16. */
