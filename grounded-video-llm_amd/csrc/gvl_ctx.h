@@ -2,6 +2,7 @@
 // shares: packed-weight table, resolved weight pointers, workspace arenas, paged KV pool, per-sequence state, error reporting.
 #pragma once
 #include "gvl_internal.h"
+#include "gvl_seq_table.h"
 #include "../../include/gvl.h"
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -32,18 +33,9 @@ struct LlmLayerW { const bf16_t *ln1, *ln2, *qkvw, *ow, *guw, *downw;
                    const bf16_t *qkvd, *od, *gud, *downd;      // decode copies in MFMA tile order (gvl_decode.hip; bf16, or FP8 e4m3 when cfg.decode_fp8); null on the VALU fallback
                    const float *qkvs, *os, *gus, *downs; };    // FP8 variant: per-row power-of-two scales
 
-// HF logits processors of one sequence (gvl_logits.hip); the defaults switch every one of them off
-struct LogitsProc {
-  float penalty = 1.0f; int ngram = 0, min_new = 0, eos = -1;
-  bool on() const { return penalty != 1.0f || ngram > 0 || (min_new > 0 && eos >= 0); }
-};
-
-// a token rule set (gvl_rules_create): one device blob (TokenRulesDev header + its arrays) and the sequences / default that reference it
-struct RuleSet { bool used = false; TokenRulesDev* d = nullptr; int refs = 0; };
-
-struct Seq {
-  bool used = false; int max_tokens = 0, n_pages = 0; std::vector<int> pages;
-  int* d_block_table = nullptr; int* d_pos = nullptr; int pos = 0; int n_gen = 0;
+// one sequence slot: the host state (SeqCore: capacity, pages, position, settings) plus the slot's views of the device-side tables (bind_slot)
+struct Seq : SeqCore {
+  int* d_block_table = nullptr; int* d_pos = nullptr;
   bool table_dirty = false;   // `pages` changed on the host (alloc / fork): the device table is rewritten, stream ordered, by the first prefill / decode that uses the sequence
   int* d_tok = nullptr;   // the sequence's latest greedy token (input of its next decode step)
   int* d_out = nullptr;   // [outlist_cap] generated ids, index = generation step (device view of host-mapped memory)
@@ -51,18 +43,17 @@ struct Seq {
   int* d_ngen = nullptr;  // device copy of n_gen: where the next generated id goes (a decode step carries no host counters)
   unsigned rng_stream = 0;  // sampling: which random stream this sequence draws from (assigned at its prefill)
   int* d_eos = nullptr; volatile int* h_eos = nullptr;   // host-mapped word: generation count at which this sequence produced eos (0 = not yet)
-  LogitsProc proc;          // HF logits processors of this sequence's token selection (gvl_seq_set_processors; default: gvl_ctx::proc_default)
-  int rules = -1;           // token rule set of this sequence (gvl_seq_set_token_rules; default: gvl_ctx::rules_default), counted in RuleSet::refs; -1 none
-  // log-probabilities of the selected tokens (gvl_seq_set_logprobs; default: gvl_ctx::top_n_default): -1 off, 0 the selected token's, 1 .. 8 also the
-  // top N.  Device lists of the sequence's slot, index = generation step like d_out ([outlist_cap], top lists [outlist_cap][GVL_MAX_TOP_LOGPROBS]);
+  // log-probability lists of the slot (sel.top_n >= 0), index = generation step like d_out ([outlist_cap], top lists [outlist_cap][GVL_MAX_TOP_LOGPROBS]);
   // null until the ctx allocated them (gvl_ctx::d_seq_lp / d_seq_top_*)
-  int top_n = -1;
   float* d_lp = nullptr; int* d_top_ids = nullptr; float* d_top_lp = nullptr;
 };
 
 struct ProfRec { int cat; hipEvent_t e0, e1; double work; };
 
-struct gvl_ctx {
+struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule sets and the default settings of new sequences
+  static constexpr int kMaxSeqs = 256;   // live sequences (slots of the device-side tables); the KV pool is the real limit
+  static constexpr int kMaxRuleSets = 1024;
+  gvl_ctx() : SeqTable<Seq>(kMaxSeqs, kMaxRuleSets) {}
   gvl_config cfg;
   std::string err;
   std::unordered_map<std::string, Tensor> w;
@@ -86,10 +77,7 @@ struct gvl_ctx {
   char* arena = nullptr; size_t arena_bytes = 0, arena_off = 0;          // vision towers, glue, op-level entries
   char* arena_l = nullptr; size_t arena_l_bytes = 0, arena_l_off = 0;    // LLM prefill (own arena: may overlap vision on another stream)
   // KV pool
-  bf16_t *kpool = nullptr, *vpool = nullptr; size_t layer_stride = 0; std::vector<int> free_pages;
-  std::vector<int> page_ref;             // sequences holding each page: full pages of a shared prefix are referenced, never copied (gvl_seq_fork)
-  std::vector<Seq> seqs;
-  static constexpr int kMaxSeqs = 256;   // live sequences (slots of the device-side tables); the KV pool is the real limit
+  bf16_t *kpool = nullptr, *vpool = nullptr; size_t layer_stride = 0;
   int* d_seq_tables = nullptr; int* d_seq_pos = nullptr; int seq_table_cap = 0;   // [kMaxSeqs][seq_table_cap], [kMaxSeqs]
   // decode buffers
   bf16_t *d_x = nullptr, *d_qkv = nullptr, *d_q = nullptr, *d_attn = nullptr, *d_act = nullptr;
@@ -118,15 +106,9 @@ struct gvl_ctx {
   hipEvent_t step_ev[3] = {nullptr, nullptr, nullptr};
   // token selection (gvl_set_sampling): greedy argmax unless `on`
   struct { bool on = false; float inv_temp = 1.f, top_p = 0.f; int top_k = 0; unsigned long long seed = 0; unsigned next_stream = 0; } sample;
-  // logits processors copied into every sequence allocated later (gvl_set_logits_processors); off by default
-  LogitsProc proc_default;
-  // token rule sets (gvl_rules_create) and the one every sequence allocated later starts with (gvl_set_token_rules; -1 none, counted in refs)
-  std::vector<RuleSet> rule_sets; int rules_default = -1;
-  static constexpr int kMaxRuleSets = 1024;
   // log-probability lists of every sequence slot ([kMaxSeqs][outlist_cap], top lists x GVL_MAX_TOP_LOGPROBS: ~134 MB), allocated by the first
-  // gvl_set_logprobs / gvl_seq_set_logprobs that needs them; top_n_default is copied into every sequence allocated later
+  // gvl_set_logprobs / gvl_seq_set_logprobs that needs them
   float* d_seq_lp = nullptr; int* d_seq_top_ids = nullptr; float* d_seq_top_lp = nullptr;
-  int top_n_default = -1;
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
   // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of ~165 kernel launches
   struct { int decode_attn_cpb = 0, decode_attn_hpb = 0; bool decode_graph = true; int vision_in_place = 1, prefill_group = 4, attn_ring = 0, attn_pipe = 1, attn_pipe_rows = 128, patch_fused = 1, varlen_attn = 1, norm_fused = 1, last_layer_tail = 1; } dbg;

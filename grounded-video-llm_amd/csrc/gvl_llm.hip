@@ -44,25 +44,25 @@ int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st) {
 // launch (a second instantiation of the selection kernel); with every sequence of the group off it is the kernel without them.
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
   bool any_proc = false;
-  for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->proc.on() || sqs[b]->rules >= 0;
+  for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->sel.proc.on() || sqs[b]->sel.rules >= 0;
   if (any_proc) {
     LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
     lp.logits = const_cast<float*>(am.logits); lp.n = am.n; lp.ld = am.n; lp.batch = am.batch;
     lp.cap = ctx->outlist_cap < GVL_LOGITS_HIST_CAP ? ctx->outlist_cap : GVL_LOGITS_HIST_CAP;
     for (int b = 0; b < am.batch; ++b) {
-      const LogitsProc& q = sqs[b]->proc;
+      const LogitsProc& q = sqs[b]->sel.proc;
       lp.hist[b] = sqs[b]->d_out; lp.len_ptrs[b] = sqs[b]->d_ngen;
       lp.penalty[b] = q.penalty; lp.ngram[b] = q.ngram; lp.min_new[b] = q.eos >= 0 ? q.min_new : 0; lp.eos[b] = q.eos;
-      lp.rules[b] = sqs[b]->rules >= 0 ? ctx->rule_sets[sqs[b]->rules].d : nullptr;
+      lp.rules[b] = sqs[b]->sel.rules >= 0 ? (const TokenRulesDev*)ctx->rule_sets[sqs[b]->sel.rules].d : nullptr;
     }
     const int rc = gvl_launch_logits_process(lp, st);
     if (rc) return rc;
   }
   for (int b = 0; b < am.batch; ++b) {             // log-probabilities (gvl_seq_set_logprobs): the sequence's slot lists, indexed by its device-side count
     const Seq& q = *sqs[b];
-    if (q.top_n < 0 || !q.d_lp) continue;
-    am.top_n[b] = q.top_n; am.lp_lists[b] = q.d_lp;
-    if (q.top_n > 0) { am.top_ids[b] = q.d_top_ids; am.top_lp[b] = q.d_top_lp; }
+    if (q.sel.top_n < 0 || !q.d_lp) continue;
+    am.top_n[b] = q.sel.top_n; am.lp_lists[b] = q.d_lp;
+    if (q.sel.top_n > 0) { am.top_ids[b] = q.d_top_ids; am.top_lp[b] = q.d_top_lp; }
   }
   if (!ctx->sample.on) return gvl_launch_argmax(am, st);
   am.inv_temp = ctx->sample.inv_temp; am.top_p = ctx->sample.top_p; am.top_k = ctx->sample.top_k;

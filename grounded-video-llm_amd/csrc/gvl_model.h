@@ -1,11 +1,33 @@
-// gvl_model.h -- what the three host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the C ABI of include/gvl.h),
-// gvl_vision.hip (the towers' launch sequences) and gvl_llm.hip (prefill, the decode step, the decode loop).  Internal: nothing here is part of the ABI.
+// gvl_model.h -- what the four host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the sequence / prefill / decode
+// and operator entry points of include/gvl.h), gvl_select.hip (the token-selection entry points), gvl_vision.hip (the towers' launch sequences) and
+// gvl_llm.hip (prefill, the decode step, the decode loop).  Internal: nothing here is part of the ABI.
 #pragma once
 #include "gvl_ctx.h"
 
 namespace gvlm {
 
 inline int fail(gvl_ctx* c, int code, const std::string& msg) { return gvl_fail(c, code, msg); }
+
+#define REQUIRE_READY(cond, what) do { if (!ctx) return GVL_ERR_ARG; if (!ctx->finalized || !(cond)) return fail(ctx, GVL_ERR_STATE, what ": weights not finalized or tower not configured"); } while (0)
+
+// a SeqStatus of the sequence table (gvl_seq_table.h) as the result of entry point `fn`: 0, or the status's error
+inline int seq_fail(gvl_ctx* c, const char* fn, int status) {
+  if (status >= 0) return 0;
+  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_RULES_FULL
+    {GVL_ERR_ARG, "bad seq"}, {GVL_ERR_ARG, "duplicate seq"}, {GVL_ERR_OOM, "KV pages exhausted"}, {GVL_ERR_OOM, "too many live sequences"}, {GVL_ERR_ARG, "no such rule set"},
+    {GVL_ERR_STATE, "the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)"},
+    {GVL_ERR_ARG, "too many live rule sets (limit 1024)"}};
+  const auto& x = e[status >= SEQ_RULES_FULL ? -1 - status : 0];
+  return fail(c, x.code, std::string(fn) + ": " + x.text);
+}
+
+// the log-probability lists of slot `id` (null while the ctx has not allocated them)
+inline void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
+  const size_t cap = (size_t)ctx->outlist_cap;
+  s.d_lp = ctx->d_seq_lp ? ctx->d_seq_lp + (size_t)id * cap : nullptr;
+  s.d_top_ids = ctx->d_seq_top_ids ? ctx->d_seq_top_ids + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
+  s.d_top_lp = ctx->d_seq_top_lp ? ctx->d_seq_top_lp + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
+}
 
 inline int pad_head(int dr) { return dr <= 64 ? 64 : (dr <= 96 ? 96 : (dr <= 128 ? 128 : -1)); }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

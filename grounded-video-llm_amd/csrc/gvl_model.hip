@@ -1,6 +1,6 @@
-// gvl_model.hip -- host side of libgvl.so: context, packed weights, workspace arenas, paged KV pool and the C ABI of include/gvl.h.
-// The launch sequences behind the ABI live in gvl_vision.hip (CLIP, InternVideo2, glue / projectors) and gvl_llm.hip (prefill, decode step, decode loop); gvl_model.h is what
-// the three share.  Restates (file:line in the reference):
+// gvl_model.hip -- host side of libgvl.so: context, packed weights, workspace arenas, paged KV pool and the C ABI of include/gvl.h except its token-selection part (gvl_select.hip):
+// the towers, splice, the sequence / prefill / decode entry points over the sequence table (gvl_seq_table.h), the operator-level entries.  The launch sequences behind the ABI live in gvl_vision.hip
+// (CLIP, InternVideo2, glue / projectors) and gvl_llm.hip (prefill, decode step, decode loop); gvl_model.h is what the four share.  Restates (file:line in the reference):
 //   splice          models/llava_next_video.py:568-596
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
@@ -34,9 +34,7 @@ int alloc_kv_pool(gvl_ctx* ctx, int pages) {
     return fail(ctx, GVL_ERR_OOM, "hipMalloc(kv pool) failed: " + std::to_string(pages) + " pages = " + std::to_string(2 * pool >> 20) + " MiB");
   }
   if (hipMemset(ctx->kpool, 0, pool) != hipSuccess || hipMemset(ctx->vpool, 0, pool) != hipSuccess) return fail(ctx, GVL_ERR_HIP, "hipMemset(kv pool) failed");
-  ctx->free_pages.clear();
-  for (int p = pages - 1; p >= 0; --p) ctx->free_pages.push_back(p);
-  ctx->page_ref.assign(pages, 0);
+  ctx->reset_pool(pages);
   ctx->kv_total_pages = pages;
   return 0;
 }
@@ -414,8 +412,6 @@ int gvl_finalize_weights(gvl_ctx* ctx) {
   return 0;
 }
 
-#define REQUIRE_READY(cond, what) do { if (!ctx) return GVL_ERR_ARG; if (!ctx->finalized || !(cond)) return fail(ctx, GVL_ERR_STATE, what ": weights not finalized or tower not configured"); } while (0)
-
 int gvl_clip_encode(gvl_ctx* ctx, const float* px, int n, float* out, void* stream) {
   REQUIRE_READY(ctx->has_clip, "gvl_clip_encode");
   if (!px || !out || n <= 0 || n > std::max(1, ctx->cfg.max_segs)) return fail(ctx, GVL_ERR_ARG, "gvl_clip_encode: bad n/pointers");
@@ -467,39 +463,10 @@ int gvl_splice(gvl_ctx* ctx, const int64_t* ids, int n_ids, const uint16_t* visu
   return 0;
 }
 
-// a sequence takes / drops its reference to a token rule set (-1: none)
-static void rules_ref(gvl_ctx* ctx, int id) { if (id >= 0) ++ctx->rule_sets[id].refs; }
-static void rules_unref(gvl_ctx* ctx, int id) { if (id >= 0) --ctx->rule_sets[id].refs; }
-
-// the log-probability lists of slot `id` (null while the ctx has not allocated them)
-static void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
-  const size_t cap = (size_t)ctx->outlist_cap;
-  s.d_lp = ctx->d_seq_lp ? ctx->d_seq_lp + (size_t)id * cap : nullptr;
-  s.d_top_ids = ctx->d_seq_top_ids ? ctx->d_seq_top_ids + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
-  s.d_top_lp = ctx->d_seq_top_lp ? ctx->d_seq_top_lp + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
-}
-
-int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
-  REQUIRE_READY(ctx->has_llm, "gvl_seq_alloc");
-  if (max_tokens <= 0 || !seq_id) return fail(ctx, GVL_ERR_ARG, "gvl_seq_alloc: bad arguments");
-  if (max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_alloc: max_tokens exceeds cfg.max_seq (rope tables)");
-  const int np = (max_tokens + 63) / 64;
-  if ((int)ctx->free_pages.size() < np) return fail(ctx, GVL_ERR_OOM, "gvl_seq_alloc: KV pages exhausted");
-  int id = -1;
-  for (size_t i = 0; i < ctx->seqs.size(); ++i) if (!ctx->seqs[i].used) { id = (int)i; break; }
-  if (id < 0) {
-    if ((int)ctx->seqs.size() >= gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_OOM, "gvl_seq_alloc: too many live sequences");
-    ctx->seqs.emplace_back(); id = (int)ctx->seqs.size() - 1;
-  }
-  Seq& s = ctx->seqs[id];
-  s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = 0; s.n_gen = 0; s.pages.clear();
-  s.proc = ctx->proc_default;                        // logits processors: the default of gvl_set_logits_processors
-  s.top_n = ctx->top_n_default;                      // log-probabilities: the default of gvl_set_logprobs
-  s.rules = ctx->rules_default; rules_ref(ctx, s.rules);   // token rules: the default of gvl_set_token_rules
-  for (int i = 0; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
-  // preallocated slot: no hipMalloc / hipFree / device-wide sync per clip.  Work that uses the slot is stream ordered;
-  // a freed slot or page may be handed out again only for work enqueued later on the same stream (one stream per ctx
-  // for the LLM path -- the reference is single-stream too).
+// Slot `id`'s views of the preallocated device-side tables: no hipMalloc / hipFree / device-wide sync per clip.  Work that uses the slot is stream
+// ordered; a freed slot or page may be handed out again only for work enqueued later on the same stream (one stream per ctx for the LLM path -- the
+// reference is single-stream too).
+static void bind_slot(gvl_ctx* ctx, Seq& s, int id) {
   s.d_block_table = ctx->d_seq_tables + (size_t)id * ctx->seq_table_cap;
   s.d_pos = ctx->d_seq_pos + id;
   s.d_tok = ctx->d_seq_tok + id;
@@ -508,54 +475,36 @@ int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
   bind_logprobs(ctx, s, id);
   s.d_eos = ctx->d_eos_flags + id; s.h_eos = ctx->h_eos_flags + id;
   s.table_dirty = true;                               // written by the first prefill / decode on ITS stream (upload_table); d_pos likewise
+}
+
+int gvl_seq_alloc(gvl_ctx* ctx, int max_tokens, int* seq_id) {
+  REQUIRE_READY(ctx->has_llm, "gvl_seq_alloc");
+  if (max_tokens <= 0 || !seq_id) return fail(ctx, GVL_ERR_ARG, "gvl_seq_alloc: bad arguments");
+  if (max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_alloc: max_tokens exceeds cfg.max_seq (rope tables)");
+  const int id = ctx->open(max_tokens, -1, 0);
+  if (id < 0) return seq_fail(ctx, "gvl_seq_alloc", id);
+  bind_slot(ctx, ctx->seqs[id], id);
   *seq_id = id;
   return 0;
 }
 int gvl_seq_free(gvl_ctx* ctx, int seq_id) {
-  if (!ctx || seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_free: bad seq");
-  Seq& s = ctx->seqs[seq_id];
-  for (int p : s.pages) if (--ctx->page_ref[p] == 0) ctx->free_pages.push_back(p);     // a page shared with a fork lives on until its last holder is freed
-  rules_unref(ctx, s.rules);
-  s = Seq();
-  return 0;
+  return seq_fail(ctx, "gvl_seq_free", ctx ? ctx->close(seq_id) : (int)SEQ_BAD);
 }
 int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* dst_seq) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_fork");
-  if (!dst_seq || src_seq < 0 || src_seq >= (int)ctx->seqs.size() || !ctx->seqs[src_seq].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: bad arguments");
+  if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: bad arguments");
   if (n_tokens <= 0 || (n_tokens & 63) || n_tokens > ctx->seqs[src_seq].pos) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: n_tokens must be a positive multiple of 64 within the source's tokens");
   if (max_tokens <= n_tokens || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: max_tokens must exceed n_tokens and fit cfg.max_seq");
-  const int shared = n_tokens >> 6, np = (max_tokens + 63) / 64;
-  if ((int)ctx->free_pages.size() < np - shared) return fail(ctx, GVL_ERR_OOM, "gvl_seq_fork: KV pages exhausted");
-  int id = -1;
-  for (size_t i = 0; i < ctx->seqs.size(); ++i) if (!ctx->seqs[i].used) { id = (int)i; break; }
-  if (id < 0) {
-    if ((int)ctx->seqs.size() >= gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_OOM, "gvl_seq_fork: too many live sequences");
-    ctx->seqs.emplace_back(); id = (int)ctx->seqs.size() - 1;
-  }
-  const std::vector<int> src_pages(ctx->seqs[src_seq].pages.begin(), ctx->seqs[src_seq].pages.begin() + shared);   // (emplace_back may have moved the source)
-  const LogitsProc src_proc = ctx->seqs[src_seq].proc;
-  const int src_top_n = ctx->seqs[src_seq].top_n, src_rules = ctx->seqs[src_seq].rules;
-  Seq& s = ctx->seqs[id];
-  s.proc = src_proc; s.top_n = src_top_n;
-  s.rules = src_rules; rules_ref(ctx, s.rules);
-  s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = n_tokens; s.n_gen = 0; s.pages = src_pages;
-  for (int p : s.pages) ++ctx->page_ref[p];          // whole pages of the prefix: immutable from now on for both holders (appends go to later pages)
-  for (int i = shared; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
-  s.d_block_table = ctx->d_seq_tables + (size_t)id * ctx->seq_table_cap;
-  s.d_pos = ctx->d_seq_pos + id;
-  s.d_tok = ctx->d_seq_tok + id;
-  s.d_out = ctx->d_seq_out + (size_t)id * ctx->outlist_cap; s.h_out = ctx->h_seq_out + (size_t)id * ctx->outlist_cap;
-  s.d_ngen = ctx->d_seq_ngen + id;
-  bind_logprobs(ctx, s, id);
-  s.d_eos = ctx->d_eos_flags + id; s.h_eos = ctx->h_eos_flags + id;
-  s.table_dirty = true;
+  const int id = ctx->open(max_tokens, src_seq, n_tokens);
+  if (id < 0) return seq_fail(ctx, "gvl_seq_fork", id);
+  bind_slot(ctx, ctx->seqs[id], id);
   *dst_seq = id;
   return 0;
 }
 
 int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill");
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_prefill: bad seq");
+  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_prefill", SEQ_BAD);
   Seq& sq = ctx->seqs[seq_id];
   if (!embeds || S <= 0 || S > sq.max_tokens || S > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill: bad length");
   if (sq.pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_prefill: sequence already holds tokens");
@@ -569,41 +518,18 @@ int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, float* 
 
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
-  if (!dst_seq || src_seq < 0 || src_seq >= (int)ctx->seqs.size() || !ctx->seqs[src_seq].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
+  if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
   const int pos = ctx->seqs[src_seq].pos;
   if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
-  const int shared = pos >> 6, np = (max_tokens + 63) / 64;
-  if ((int)ctx->free_pages.size() < np - shared) return fail(ctx, GVL_ERR_OOM, "gvl_seq_clone: KV pages exhausted");
-  int id = -1;
-  for (size_t i = 0; i < ctx->seqs.size(); ++i) if (!ctx->seqs[i].used) { id = (int)i; break; }
-  if (id < 0) {
-    if ((int)ctx->seqs.size() >= gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_OOM, "gvl_seq_clone: too many live sequences");
-    ctx->seqs.emplace_back(); id = (int)ctx->seqs.size() - 1;
-  }
-  const std::vector<int> src_pages = ctx->seqs[src_seq].pages;
-  const int src_ngen = ctx->seqs[src_seq].n_gen;
-  const LogitsProc src_proc = ctx->seqs[src_seq].proc;
-  const int src_top_n = ctx->seqs[src_seq].top_n, src_rules = ctx->seqs[src_seq].rules;
+  const int id = ctx->open(max_tokens, src_seq, pos);
+  if (id < 0) return seq_fail(ctx, "gvl_seq_clone", id);
   Seq& s = ctx->seqs[id];
-  s.proc = src_proc; s.top_n = src_top_n;
-  s.rules = src_rules; rules_ref(ctx, s.rules);
-  s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = pos; s.n_gen = src_ngen;
-  s.pages.assign(src_pages.begin(), src_pages.begin() + shared);
-  for (int p : s.pages) ++ctx->page_ref[p];
-  for (int i = shared; i < np; ++i) { s.pages.push_back(ctx->free_pages.back()); ctx->free_pages.pop_back(); ctx->page_ref[s.pages.back()] = 1; }
-  s.d_block_table = ctx->d_seq_tables + (size_t)id * ctx->seq_table_cap;
-  s.d_pos = ctx->d_seq_pos + id;
-  s.d_tok = ctx->d_seq_tok + id;
-  s.d_out = ctx->d_seq_out + (size_t)id * ctx->outlist_cap; s.h_out = ctx->h_seq_out + (size_t)id * ctx->outlist_cap;
-  s.d_ngen = ctx->d_seq_ngen + id;
-  bind_logprobs(ctx, s, id);
-  s.d_eos = ctx->d_eos_flags + id; s.h_eos = ctx->h_eos_flags + id;
+  bind_slot(ctx, s, id);
   hipStream_t st = (hipStream_t)stream;
-  s.table_dirty = true;
   { const int rc = upload_table(ctx, s, st); if (rc) return rc; }   // by value, on the clone's stream: ordered behind the source's pending steps there
   if (pos & 63)                                       // the partial last page is private: copy the source's (all layers, K and V^T)
     RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_copy(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers,
-                                                   src_pages[shared], s.pages[shared], st));
+                                                   ctx->seqs[src_seq].pages[pos >> 6], s.pages[pos >> 6], st));
   RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(s.d_pos, pos, st));
   RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(s.d_ngen, 0, st));
   s.n_gen = 0;
@@ -613,7 +539,7 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
 
 int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_new, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend");
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad seq");
+  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_prefill_extend", SEQ_BAD);
   Seq& sq = ctx->seqs[seq_id];
   if (sq.pos <= 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend: the sequence must hold a prefix of whole pages (gvl_seq_fork)");
   if (!embeds || n_new <= 0 || sq.pos + n_new > sq.max_tokens || n_new > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad length");
@@ -627,7 +553,7 @@ int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_n
 
 int gvl_forward_loss(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, const int64_t* labels, double* nll_sum, int* n_valid, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_forward_loss");
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_forward_loss: bad seq");
+  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_forward_loss", SEQ_BAD);
   Seq& sq = ctx->seqs[seq_id];
   if (!embeds || !labels || !nll_sum || !n_valid || S <= 0 || S > sq.max_tokens || S > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_forward_loss: bad arguments / length");
   if (sq.pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_forward_loss: sequence already holds tokens");
@@ -657,11 +583,11 @@ int gvl_prefill_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint1
   if (!seq_ids || !embeds || !seq_lens || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad arguments");
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
-    if (id < 0 || id >= (int)ctx->seqs.size() || !ctx->seqs[id].used || !embeds[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad seq / embeds");
+    if (!ctx->lookup(id) || !embeds[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad seq / embeds");
     if (seq_lens[i] <= 0 || seq_lens[i] > ctx->seqs[id].max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad length");
     if (seq_lens[i] > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: seq_len exceeds cfg.max_prefill");
     if (ctx->seqs[id].pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_varlen: sequence already holds tokens");
-    for (int j = 0; j < i; ++j) if (seq_ids[j] == id) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: duplicate seq");
+    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_prefill_varlen", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
   // groups of up to 8 sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
@@ -701,9 +627,9 @@ int gvl_decode_greedy_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int ma
     return fail(ctx, GVL_ERR_ARG, "gvl_decode_greedy_batch: bad arguments");
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
-    if (id < 0 || id >= (int)ctx->seqs.size() || !ctx->seqs[id].used) return fail(ctx, GVL_ERR_ARG, "gvl_decode_greedy_batch: bad seq");
+    if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_BAD);
     if (ctx->seqs[id].n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_greedy: call gvl_prefill first");   // members of a group must also be at the SAME step (checked per group)
-    for (int j = 0; j < i; ++j) if (seq_ids[j] == id) return fail(ctx, GVL_ERR_ARG, "gvl_decode_greedy_batch: duplicate seq");
+    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
   // groups of up to 16 (VALU fallback: 4, 2, 1): a group streams the weights once per step for all of its members
@@ -726,11 +652,11 @@ int gvl_decode_steps(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int n_steps, 
   if (!seq_ids || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs || n_steps <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: bad arguments");
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
-    if (id < 0 || id >= (int)ctx->seqs.size() || !ctx->seqs[id].used) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: bad seq");
+    if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_steps", SEQ_BAD);
     const Seq& sq = ctx->seqs[id];
     if (sq.n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_steps: call gvl_prefill first");
     if (sq.pos + n_steps > sq.max_tokens || sq.n_gen + n_steps > ctx->outlist_cap) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: sequence would exceed its capacity");
-    for (int j = 0; j < i; ++j) if (seq_ids[j] == id) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: duplicate seq");
+    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_steps", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
   for (int s = 0; s < n_steps; ++s) {
@@ -749,8 +675,7 @@ int gvl_decode_steps(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int n_steps, 
 
 int gvl_seq_read(gvl_ctx* ctx, int seq_id, int first, int32_t* out_ids, int cap, int* n_gen, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_read");
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used || !n_gen || first < 0 || cap < 0 || (cap > 0 && !out_ids))
-    return fail(ctx, GVL_ERR_ARG, "gvl_seq_read: bad arguments");
+  if (!ctx->lookup(seq_id) || !n_gen || first < 0 || cap < 0 || (cap > 0 && !out_ids)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_read: bad arguments");
   const Seq& sq = ctx->seqs[seq_id];
   *n_gen = sq.n_gen;
   int n = sq.n_gen - first; if (n > cap) n = cap;
@@ -763,7 +688,7 @@ int gvl_seq_read(gvl_ctx* ctx, int seq_id, int first, int32_t* out_ids, int cap,
 
 int gvl_decode_step_logits(gvl_ctx* ctx, int seq_id, int tok, float* logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_decode_step_logits");
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits: bad seq");
+  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_decode_step_logits", SEQ_BAD);
   Seq& sq = ctx->seqs[seq_id];
   if (tok < 0 || tok >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits: bad token / sequence full / not prefilled");
   hipStream_t st = (hipStream_t)stream;
@@ -782,10 +707,10 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
   Seq* sqs[GVL_MAX_DECODE_BATCH];
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
-    if (id < 0 || id >= (int)ctx->seqs.size() || !ctx->seqs[id].used) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: bad seq");
+    if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_BAD);
     Seq& sq = ctx->seqs[id];
     if (toks[i] < 0 || toks[i] >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: bad token / sequence full / not prefilled");
-    for (int j = 0; j < i; ++j) if (seq_ids[j] == id) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: duplicate seq");
+    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_DUPLICATE);
     sqs[i] = &sq;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -815,270 +740,6 @@ int gvl_debug_set(gvl_ctx* ctx, const char* key, int value) {
   else if (k == "gemm_narrow") gvl_gemm_set_narrow(value < 0 || value > 2 ? 1 : value);
   else if (k == "vision_in_place") { if (value < 0 || value > 2) return fail(ctx, GVL_ERR_ARG, "gvl_debug_set: vision_in_place must be 0, 1 or 2"); ctx->dbg.vision_in_place = value; }
   else return fail(ctx, GVL_ERR_ARG, "gvl_debug_set: unknown key " + k);
-  return 0;
-}
-
-int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, float top_p, uint64_t seed) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!do_sample) { ctx->sample.on = false; return 0; }
-  if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f)
-    return fail(ctx, GVL_ERR_ARG, "gvl_set_sampling: temperature must be > 0, top_k >= 0, 0 <= top_p <= 1");
-  ctx->sample.on = true; ctx->sample.inv_temp = 1.0f / temperature; ctx->sample.top_k = top_k; ctx->sample.top_p = top_p;
-  // stream numbering restarts with the call (same seed + same prefill order = same draws) -- unless sequences are LIVE: a scheduler that
-  // changes the sampling parameters mid-flight must not hand the stream ids of running sequences to newcomers
-  bool any_live = false;
-  for (const Seq& q : ctx->seqs) any_live = any_live || q.used;
-  if (!any_live || seed != ctx->sample.seed) ctx->sample.next_stream = 0;
-  ctx->sample.seed = seed;
-  return 0;
-}
-
-int gvl_op_sample(gvl_ctx* ctx, const float* logits, int n, int batch, float temperature, int top_k, float top_p, uint64_t seed,
-                  const uint32_t* streams, const int32_t* steps_dev, int32_t* tokens_dev, void* stream) {
-  if (!ctx || !logits || !streams || !steps_dev || !tokens_dev || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f)
-    return fail(ctx, GVL_ERR_ARG, "gvl_op_sample: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = logits; am.n = n; am.batch = batch;
-  am.inv_temp = 1.0f / temperature; am.top_k = top_k; am.top_p = top_p; am.seed_lo = (unsigned)seed; am.seed_hi = (unsigned)(seed >> 32);
-  am.step_override = steps_dev;
-  for (int b = 0; b < batch; ++b) { am.tok_ptrs[b] = tokens_dev + b; am.stream[b] = streams[b]; }
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
-  return 0;
-}
-
-// ---- HF logits processors (gvl_logits.hip): repetition penalty -> no-repeat n-gram -> min length, on the generated ids of each sequence
-static int check_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, const char* what) {
-  if (!(penalty > 0.f) || ngram < 0 || min_new < 0) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": penalty must be > 0, ngram >= 0, min_new >= 0");
-  return 0;
-}
-int gvl_set_logits_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, int eos_id) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (const int rc = check_processors(ctx, penalty, ngram, min_new, "gvl_set_logits_processors")) return rc;
-  ctx->proc_default.penalty = penalty; ctx->proc_default.ngram = ngram; ctx->proc_default.min_new = min_new; ctx->proc_default.eos = eos_id < 0 ? -1 : eos_id;
-  return 0;
-}
-int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, int min_new, int eos_id) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_processors: bad seq");
-  if (const int rc = check_processors(ctx, penalty, ngram, min_new, "gvl_seq_set_processors")) return rc;
-  LogitsProc& q = ctx->seqs[seq_id].proc;
-  q.penalty = penalty; q.ngram = ngram; q.min_new = min_new; q.eos = eos_id < 0 ? -1 : eos_id;
-  return 0;
-}
-int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
-                          const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, void* stream) {
-  if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
-      hist_stride < 0 || (hist_stride > 0 && !hist_dev))
-    return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
-  lp.logits = logits; lp.n = n; lp.ld = n; lp.batch = batch; lp.cap = hist_stride < GVL_LOGITS_HIST_CAP ? hist_stride : GVL_LOGITS_HIST_CAP;
-  for (int b = 0; b < batch; ++b) {
-    if (const int rc = check_processors(ctx, penalty[b], ngram[b], min_new[b], "gvl_op_logits_process")) return rc;
-    lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
-    lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
-  }
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
-  return 0;
-}
-
-// ---- token rules (TokenRulesDev, gvl_logits.hip): sequence_bias / bad_words_ids / forced eos / suppress lists as immutable device objects
-static int check_ids(gvl_ctx* ctx, const int32_t* ids, int n, const char* what) {
-  if (n < 0 || (n > 0 && !ids)) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + ": bad list");
-  if (n > GVL_RULES_MAX_IDS) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + " holds " + std::to_string(n) + " ids, the limit is " + std::to_string(GVL_RULES_MAX_IDS));
-  for (int i = 0; i < n; ++i) if (ids[i] < 0) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + ": negative token id");
-  return 0;
-}
-static int check_table(gvl_ctx* ctx, const gvl_bias_table& t, const char* what, int* n_multi) {
-  const std::string w = std::string("gvl_rules_create: ") + what;
-  if (t.n_targets < 0 || t.n_entries < 0 || t.n_prefix < 0 || (t.n_targets > 0 && !t.targets) || (t.n_entries > 0 && (!t.entry_bias || !t.entry_prefix)) || (t.n_prefix > 0 && !t.prefix))
-    return fail(ctx, GVL_ERR_ARG, w + ": bad table");
-  int multi = 0;
-  for (int e = 0; e < t.n_entries; ++e) {
-    const int po = t.entry_prefix[2 * e], pl = t.entry_prefix[2 * e + 1];
-    if (pl < 0 || po < 0) return fail(ctx, GVL_ERR_ARG, w + ": bad prefix range");
-    if (pl + 1 > GVL_RULES_MAX_SEQ_LEN) return fail(ctx, GVL_ERR_ARG, w + ": an entry holds " + std::to_string(pl + 1) + " ids, the limit is " + std::to_string(GVL_RULES_MAX_SEQ_LEN));
-    if ((int64_t)po + pl > t.n_prefix) return fail(ctx, GVL_ERR_ARG, w + ": bad prefix range");
-    multi += pl > 0;
-  }
-  if (multi > GVL_RULES_MAX_SEQS) return fail(ctx, GVL_ERR_ARG, w + " holds " + std::to_string(multi) + " multi-token entries, the limit is " + std::to_string(GVL_RULES_MAX_SEQS));
-  if (t.n_entries - multi > GVL_RULES_MAX_IDS) return fail(ctx, GVL_ERR_ARG, w + " holds " + std::to_string(t.n_entries - multi) + " single-token entries, the limit is " + std::to_string(GVL_RULES_MAX_IDS));
-  if (t.n_targets > t.n_entries) return fail(ctx, GVL_ERR_ARG, w + ": more targets than entries");
-  std::vector<int> seen; seen.reserve(t.n_targets);
-  for (int g = 0; g < t.n_targets; ++g) {
-    const int tk = t.targets[3 * g], e0 = t.targets[3 * g + 1], ne = t.targets[3 * g + 2];
-    if (tk < 0 || e0 < 0 || ne < 1 || (int64_t)e0 + ne > t.n_entries) return fail(ctx, GVL_ERR_ARG, w + ": bad target group");
-    seen.push_back(tk);
-  }
-  for (int i = 0; i < t.n_prefix; ++i) if (t.prefix[i] < 0) return fail(ctx, GVL_ERR_ARG, w + ": negative token id");
-  std::sort(seen.begin(), seen.end());
-  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(ctx, GVL_ERR_ARG, w + ": a target token appears in two groups (one thread owns one target)");
-  *n_multi += multi;
-  return 0;
-}
-int gvl_rules_create(gvl_ctx* ctx, const gvl_rules_desc* d, int* rules_id) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!d || !rules_id) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: bad arguments");
-  if (const int rc = check_ids(ctx, d->suppress, d->n_suppress, "suppress")) return rc;
-  if (const int rc = check_ids(ctx, d->begin_suppress, d->n_begin_suppress, "begin_suppress")) return rc;
-  if (const int rc = check_ids(ctx, d->force_ids, d->n_force, "force_ids")) return rc;
-  if ((d->n_begin_suppress > 0 && d->begin_index < 0) || (d->n_force > 0 && d->force_at < 0)) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: begin_index / force_at must be >= 0");
-  int n_multi = 0;
-  if (const int rc = check_table(ctx, d->bias[0], "bias[0] (sequence_bias)", &n_multi)) return rc;
-  if (const int rc = check_table(ctx, d->bias[1], "bias[1] (bad_words_ids)", &n_multi)) return rc;
-  int id = -1;
-  for (size_t i = 0; i < ctx->rule_sets.size(); ++i) if (!ctx->rule_sets[i].used) { id = (int)i; break; }
-  if (id < 0) {
-    if ((int)ctx->rule_sets.size() >= gvl_ctx::kMaxRuleSets) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: too many live rule sets (limit 1024)");
-    ctx->rule_sets.emplace_back(); id = (int)ctx->rule_sets.size() - 1;
-  }
-  // the blob: header, then every array, as 32-bit words
-  static_assert(sizeof(TokenRulesDev) % 4 == 0, "header is whole words");
-  std::vector<int32_t> w(sizeof(TokenRulesDev) / 4, 0);
-  TokenRulesDev h; memset(&h, 0, sizeof(h));
-  auto put = [&w](const int32_t* p, size_t n) { const int off = (int)w.size(); if (n) w.insert(w.end(), p, p + n); return off; };
-  h.n_suppress = d->n_suppress; h.off_suppress = put(d->suppress, d->n_suppress);
-  h.n_begin = d->n_begin_suppress; h.off_begin = put(d->begin_suppress, d->n_begin_suppress); h.begin_at = d->begin_index;
-  h.n_force = d->n_force; h.off_force = put(d->force_ids, d->n_force); h.force_at = d->force_at;
-  h.n_multi = n_multi;
-  for (int st = 0; st < 2; ++st) {
-    const gvl_bias_table& t = d->bias[st];
-    h.n_tgt[st] = t.n_targets; h.off_tgt[st] = put(t.targets, (size_t)t.n_targets * 3);
-    h.off_ent[st] = (int)w.size();
-    for (int e = 0; e < t.n_entries; ++e) {
-      int32_t bits; memcpy(&bits, &t.entry_bias[e], 4);
-      w.push_back(bits); w.push_back(t.entry_prefix[2 * e]); w.push_back(t.entry_prefix[2 * e + 1]);
-    }
-    h.off_pre[st] = put(t.prefix, t.n_prefix);
-  }
-  memcpy(w.data(), &h, sizeof(h));
-  RuleSet& r = ctx->rule_sets[id];
-  HIPCHK(ctx, hipMalloc((void**)&r.d, w.size() * 4));
-  const hipError_t e = hipMemcpy(r.d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(r.d); r.d = nullptr; return gvl_hipfail(ctx, e, "gvl_rules_create: hipMemcpy"); }
-  r.used = true; r.refs = 0;
-  *rules_id = id;
-  return 0;
-}
-static int check_rules_id(gvl_ctx* ctx, int id, const char* what) {
-  if (id < -1 || id >= (int)ctx->rule_sets.size() || (id >= 0 && !ctx->rule_sets[id].used)) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": no such rule set");
-  return 0;
-}
-int gvl_rules_destroy(gvl_ctx* ctx, int rules_id) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (rules_id < 0) return fail(ctx, GVL_ERR_ARG, "gvl_rules_destroy: no such rule set");
-  if (const int rc = check_rules_id(ctx, rules_id, "gvl_rules_destroy")) return rc;
-  RuleSet& r = ctx->rule_sets[rules_id];
-  if (r.refs > 0) return fail(ctx, GVL_ERR_STATE, "gvl_rules_destroy: the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)");
-  HIPCHK(ctx, hipDeviceSynchronize());                 // every launch that read the set has finished before its memory goes
-  hipFree(r.d);
-  r = RuleSet();
-  return 0;
-}
-int gvl_set_token_rules(gvl_ctx* ctx, int rules_id) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (const int rc = check_rules_id(ctx, rules_id, "gvl_set_token_rules")) return rc;
-  rules_ref(ctx, rules_id); rules_unref(ctx, ctx->rules_default);
-  ctx->rules_default = rules_id;
-  return 0;
-}
-int gvl_seq_set_token_rules(gvl_ctx* ctx, int seq_id, int rules_id) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_token_rules: bad seq");
-  if (const int rc = check_rules_id(ctx, rules_id, "gvl_seq_set_token_rules")) return rc;
-  rules_ref(ctx, rules_id); rules_unref(ctx, ctx->seqs[seq_id].rules);
-  ctx->seqs[seq_id].rules = rules_id;
-  return 0;
-}
-int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
-                                const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
-  if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || !rules_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
-      hist_stride < 0 || (hist_stride > 0 && !hist_dev))
-    return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process_rules: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
-  lp.logits = logits; lp.n = n; lp.ld = n; lp.batch = batch; lp.cap = hist_stride < GVL_LOGITS_HIST_CAP ? hist_stride : GVL_LOGITS_HIST_CAP;
-  for (int b = 0; b < batch; ++b) {
-    if (const int rc = check_processors(ctx, penalty[b], ngram[b], min_new[b], "gvl_op_logits_process_rules")) return rc;
-    if (const int rc = check_rules_id(ctx, rules_ids[b], "gvl_op_logits_process_rules")) return rc;
-    lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
-    lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
-    lp.rules[b] = rules_ids[b] >= 0 ? ctx->rule_sets[rules_ids[b]].d : nullptr;
-  }
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
-  return 0;
-}
-
-// ---- log-probabilities of the selected tokens (ArgmaxArgs.top_n / lp_lists / top_ids / top_lp; gvl_elem.hip)
-// the slot lists a setting needs, allocated on first use (never during a decode call: the setters run between calls); live sequences are rebound
-static int ensure_logprob_lists(gvl_ctx* ctx, int top_n, const char* what) {
-  if (top_n < -1 || top_n > GVL_MAX_TOP_LOGPROBS) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": top_n must be -1 (off), 0 (selected token) or 1 .. 8");
-  if (top_n < 0) return 0;
-  if (!ctx->has_llm) return fail(ctx, GVL_ERR_STATE, std::string(what) + ": no language model configured");
-  const size_t n = (size_t)gvl_ctx::kMaxSeqs * ctx->outlist_cap;
-  bool grew = false;
-  if (!ctx->d_seq_lp) { HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_lp, n * 4)); grew = true; }
-  if (top_n > 0 && !ctx->d_seq_top_ids) {
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_top_ids, n * GVL_MAX_TOP_LOGPROBS * 4));
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_top_lp, n * GVL_MAX_TOP_LOGPROBS * 4));
-    grew = true;
-  }
-  if (grew) for (size_t i = 0; i < ctx->seqs.size(); ++i) if (ctx->seqs[i].used) bind_logprobs(ctx, ctx->seqs[i], (int)i);
-  return 0;
-}
-int gvl_set_logprobs(gvl_ctx* ctx, int top_n) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (const int rc = ensure_logprob_lists(ctx, top_n, "gvl_set_logprobs")) return rc;
-  ctx->top_n_default = top_n;
-  return 0;
-}
-int gvl_seq_set_logprobs(gvl_ctx* ctx, int seq_id, int top_n) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_logprobs: bad seq");
-  if (const int rc = ensure_logprob_lists(ctx, top_n, "gvl_seq_set_logprobs")) return rc;
-  ctx->seqs[seq_id].top_n = top_n;
-  return 0;
-}
-int gvl_seq_read_logprobs(gvl_ctx* ctx, int seq_id, int first, int cap, float* lp, int32_t* top_ids, float* top_lp, int* n_gen, void* stream) {
-  REQUIRE_READY(ctx->has_llm, "gvl_seq_read_logprobs");
-  if (seq_id < 0 || seq_id >= (int)ctx->seqs.size() || !ctx->seqs[seq_id].used || !n_gen || first < 0 || cap < 0)
-    return fail(ctx, GVL_ERR_ARG, "gvl_seq_read_logprobs: bad arguments");
-  const Seq& sq = ctx->seqs[seq_id];
-  if (lp && (sq.top_n < 0 || !sq.d_lp)) return fail(ctx, GVL_ERR_STATE, "gvl_seq_read_logprobs: the sequence has log-probabilities off");
-  if ((top_ids || top_lp) && (sq.top_n < 1 || !sq.d_top_ids)) return fail(ctx, GVL_ERR_STATE, "gvl_seq_read_logprobs: the sequence keeps no top-N lists");
-  *n_gen = sq.n_gen;
-  int n = sq.n_gen - first; if (n > cap) n = cap;
-  if (n > 0) {
-    hipStream_t st = (hipStream_t)stream;
-    const size_t K = GVL_MAX_TOP_LOGPROBS;
-    if (lp) HIPCHK(ctx, hipMemcpyAsync(lp, sq.d_lp + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (top_ids) HIPCHK(ctx, hipMemcpyAsync(top_ids, sq.d_top_ids + (size_t)first * K, (size_t)n * K * 4, hipMemcpyDeviceToHost, st));
-    if (top_lp) HIPCHK(ctx, hipMemcpyAsync(top_lp, sq.d_top_lp + (size_t)first * K, (size_t)n * K * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-  }
-  return 0;
-}
-int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, int do_sample, float temperature, int top_k, float top_p, uint64_t seed,
-                           const uint32_t* streams, const int32_t* steps_dev, const int* top_n, int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev,
-                           float* top_lp_dev, void* stream) {
-  if (!ctx || !logits || !top_n || !tokens_dev || !lp_dev || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH)
-    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: bad arguments");
-  if (do_sample && (!streams || !steps_dev || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f))
-    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: bad sampling arguments");
-  hipStream_t st = (hipStream_t)stream;
-  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = logits; am.n = n; am.batch = batch;
-  for (int b = 0; b < batch; ++b) {
-    if (top_n[b] < -1 || top_n[b] > GVL_MAX_TOP_LOGPROBS || (top_n[b] > 0 && (!top_ids_dev || !top_lp_dev)))
-      return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: top_n must be -1 .. 8 (top lists needed for > 0)");
-    am.tok_ptrs[b] = tokens_dev + b;
-    am.top_n[b] = top_n[b]; am.lp_lists[b] = lp_dev + b;
-    if (top_n[b] > 0) { am.top_ids[b] = top_ids_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; am.top_lp[b] = top_lp_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; }
-  }
-  if (!do_sample) { RUN(GVL_PROF_OTHER, 0, gvl_launch_argmax(am, st)); return 0; }
-  am.inv_temp = 1.0f / temperature; am.top_k = top_k; am.top_p = top_p; am.seed_lo = (unsigned)seed; am.seed_hi = (unsigned)(seed >> 32);
-  am.step_override = steps_dev;
-  for (int b = 0; b < batch; ++b) am.stream[b] = streams[b];
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
   return 0;
 }
 

@@ -1,0 +1,247 @@
+// gvl_select.hip -- the token-selection part of the C ABI of include/gvl.h: sampling parameters, HF logits processors, token rule sets, log-probabilities of the selected tokens -- the settings a sequence
+// carries (SeqSelect, gvl_seq_table.h; applied per step by pick_tokens, gvl_llm.hip) and the operator-level entries of their kernels (gvl_elem.hip, gvl_logits.hip).  Host code only.
+#include "gvl_model.h"
+
+using namespace gvlm;
+extern "C" {
+
+int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, float top_p, uint64_t seed) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!do_sample) { ctx->sample.on = false; return 0; }
+  if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f)
+    return fail(ctx, GVL_ERR_ARG, "gvl_set_sampling: temperature must be > 0, top_k >= 0, 0 <= top_p <= 1");
+  ctx->sample.on = true; ctx->sample.inv_temp = 1.0f / temperature; ctx->sample.top_k = top_k; ctx->sample.top_p = top_p;
+  // stream numbering restarts with the call (same seed + same prefill order = same draws) -- unless sequences are LIVE: a scheduler that
+  // changes the sampling parameters mid-flight must not hand the stream ids of running sequences to newcomers
+  if (!ctx->any_live() || seed != ctx->sample.seed) ctx->sample.next_stream = 0;
+  ctx->sample.seed = seed;
+  return 0;
+}
+
+int gvl_op_sample(gvl_ctx* ctx, const float* logits, int n, int batch, float temperature, int top_k, float top_p, uint64_t seed,
+                  const uint32_t* streams, const int32_t* steps_dev, int32_t* tokens_dev, void* stream) {
+  if (!ctx || !logits || !streams || !steps_dev || !tokens_dev || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f)
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_sample: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = logits; am.n = n; am.batch = batch;
+  am.inv_temp = 1.0f / temperature; am.top_k = top_k; am.top_p = top_p; am.seed_lo = (unsigned)seed; am.seed_hi = (unsigned)(seed >> 32);
+  am.step_override = steps_dev;
+  for (int b = 0; b < batch; ++b) { am.tok_ptrs[b] = tokens_dev + b; am.stream[b] = streams[b]; }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
+  return 0;
+}
+
+// ---- HF logits processors (gvl_logits.hip): repetition penalty -> no-repeat n-gram -> min length, on the generated ids of each sequence
+static int check_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, const char* what) {
+  if (!(penalty > 0.f) || ngram < 0 || min_new < 0) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": penalty must be > 0, ngram >= 0, min_new >= 0");
+  return 0;
+}
+int gvl_set_logits_processors(gvl_ctx* ctx, float penalty, int ngram, int min_new, int eos_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = check_processors(ctx, penalty, ngram, min_new, "gvl_set_logits_processors")) return rc;
+  ctx->sel_default.proc = LogitsProc{penalty, ngram, min_new, eos_id < 0 ? -1 : eos_id};
+  return 0;
+}
+int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, int min_new, int eos_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  Seq* sq = ctx->lookup(seq_id);
+  if (!sq) return seq_fail(ctx, "gvl_seq_set_processors", SEQ_BAD);
+  if (const int rc = check_processors(ctx, penalty, ngram, min_new, "gvl_seq_set_processors")) return rc;
+  sq->sel.proc = LogitsProc{penalty, ngram, min_new, eos_id < 0 ? -1 : eos_id};
+  return 0;
+}
+// the processors, and with rules_ids (entry point `what` = gvl_op_logits_process_rules) the rule sets, on `batch` rows of logits
+static int op_logits_process(gvl_ctx* ctx, const char* what, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
+  if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
+      hist_stride < 0 || (hist_stride > 0 && !hist_dev))
+    return fail(ctx, GVL_ERR_ARG, std::string(what) + ": bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
+  lp.logits = logits; lp.n = n; lp.ld = n; lp.batch = batch; lp.cap = hist_stride < GVL_LOGITS_HIST_CAP ? hist_stride : GVL_LOGITS_HIST_CAP;
+  for (int b = 0; b < batch; ++b) {
+    if (const int rc = check_processors(ctx, penalty[b], ngram[b], min_new[b], what)) return rc;
+    if (const int rc = rules_ids ? ctx->check_rules(rules_ids[b]) : 0) return seq_fail(ctx, what, rc);
+    lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
+    lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
+    lp.rules[b] = rules_ids && rules_ids[b] >= 0 ? (const TokenRulesDev*)ctx->rule_sets[rules_ids[b]].d : nullptr;
+  }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
+  return 0;
+}
+int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                          const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, void* stream) {
+  return op_logits_process(ctx, "gvl_op_logits_process", logits, n, batch, hist_dev, hist_stride, lens_dev, penalty, ngram, min_new, eos_ids, nullptr, stream);
+}
+
+// ---- token rules (TokenRulesDev, gvl_logits.hip): sequence_bias / bad_words_ids / forced eos / suppress lists as immutable device objects
+static int check_ids(gvl_ctx* ctx, const int32_t* ids, int n, const char* what) {
+  if (n < 0 || (n > 0 && !ids)) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + ": bad list");
+  if (n > GVL_RULES_MAX_IDS) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + " holds " + std::to_string(n) + " ids, the limit is " + std::to_string(GVL_RULES_MAX_IDS));
+  for (int i = 0; i < n; ++i) if (ids[i] < 0) return fail(ctx, GVL_ERR_ARG, std::string("gvl_rules_create: ") + what + ": negative token id");
+  return 0;
+}
+static int check_table(gvl_ctx* ctx, const gvl_bias_table& t, const char* what, int* n_multi) {
+  const std::string w = std::string("gvl_rules_create: ") + what;
+  if (t.n_targets < 0 || t.n_entries < 0 || t.n_prefix < 0 || (t.n_targets > 0 && !t.targets) || (t.n_entries > 0 && (!t.entry_bias || !t.entry_prefix)) || (t.n_prefix > 0 && !t.prefix))
+    return fail(ctx, GVL_ERR_ARG, w + ": bad table");
+  int multi = 0;
+  for (int e = 0; e < t.n_entries; ++e) {
+    const int po = t.entry_prefix[2 * e], pl = t.entry_prefix[2 * e + 1];
+    if (pl < 0 || po < 0) return fail(ctx, GVL_ERR_ARG, w + ": bad prefix range");
+    if (pl + 1 > GVL_RULES_MAX_SEQ_LEN) return fail(ctx, GVL_ERR_ARG, w + ": an entry holds " + std::to_string(pl + 1) + " ids, the limit is " + std::to_string(GVL_RULES_MAX_SEQ_LEN));
+    if ((int64_t)po + pl > t.n_prefix) return fail(ctx, GVL_ERR_ARG, w + ": bad prefix range");
+    multi += pl > 0;
+  }
+  if (multi > GVL_RULES_MAX_SEQS) return fail(ctx, GVL_ERR_ARG, w + " holds " + std::to_string(multi) + " multi-token entries, the limit is " + std::to_string(GVL_RULES_MAX_SEQS));
+  if (t.n_entries - multi > GVL_RULES_MAX_IDS) return fail(ctx, GVL_ERR_ARG, w + " holds " + std::to_string(t.n_entries - multi) + " single-token entries, the limit is " + std::to_string(GVL_RULES_MAX_IDS));
+  if (t.n_targets > t.n_entries) return fail(ctx, GVL_ERR_ARG, w + ": more targets than entries");
+  std::vector<int> seen; seen.reserve(t.n_targets);
+  for (int g = 0; g < t.n_targets; ++g) {
+    const int tk = t.targets[3 * g], e0 = t.targets[3 * g + 1], ne = t.targets[3 * g + 2];
+    if (tk < 0 || e0 < 0 || ne < 1 || (int64_t)e0 + ne > t.n_entries) return fail(ctx, GVL_ERR_ARG, w + ": bad target group");
+    seen.push_back(tk);
+  }
+  for (int i = 0; i < t.n_prefix; ++i) if (t.prefix[i] < 0) return fail(ctx, GVL_ERR_ARG, w + ": negative token id");
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(ctx, GVL_ERR_ARG, w + ": a target token appears in two groups (one thread owns one target)");
+  *n_multi += multi;
+  return 0;
+}
+int gvl_rules_create(gvl_ctx* ctx, const gvl_rules_desc* d, int* rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!d || !rules_id) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: bad arguments");
+  if (const int rc = check_ids(ctx, d->suppress, d->n_suppress, "suppress")) return rc;
+  if (const int rc = check_ids(ctx, d->begin_suppress, d->n_begin_suppress, "begin_suppress")) return rc;
+  if (const int rc = check_ids(ctx, d->force_ids, d->n_force, "force_ids")) return rc;
+  if ((d->n_begin_suppress > 0 && d->begin_index < 0) || (d->n_force > 0 && d->force_at < 0)) return fail(ctx, GVL_ERR_ARG, "gvl_rules_create: begin_index / force_at must be >= 0");
+  int n_multi = 0;
+  if (const int rc = check_table(ctx, d->bias[0], "bias[0] (sequence_bias)", &n_multi)) return rc;
+  if (const int rc = check_table(ctx, d->bias[1], "bias[1] (bad_words_ids)", &n_multi)) return rc;
+  const int id = ctx->add_rules(nullptr);              // the slot first: its blob follows below, a failure there gives the slot back
+  if (id < 0) return seq_fail(ctx, "gvl_rules_create", id);
+  // the blob: header, then every array, as 32-bit words
+  static_assert(sizeof(TokenRulesDev) % 4 == 0, "header is whole words");
+  std::vector<int32_t> w(sizeof(TokenRulesDev) / 4, 0);
+  TokenRulesDev h; memset(&h, 0, sizeof(h));
+  auto put = [&w](const int32_t* p, size_t n) { const int off = (int)w.size(); if (n) w.insert(w.end(), p, p + n); return off; };
+  h.n_suppress = d->n_suppress; h.off_suppress = put(d->suppress, d->n_suppress);
+  h.n_begin = d->n_begin_suppress; h.off_begin = put(d->begin_suppress, d->n_begin_suppress); h.begin_at = d->begin_index;
+  h.n_force = d->n_force; h.off_force = put(d->force_ids, d->n_force); h.force_at = d->force_at;
+  h.n_multi = n_multi;
+  for (int st = 0; st < 2; ++st) {
+    const gvl_bias_table& t = d->bias[st];
+    h.n_tgt[st] = t.n_targets; h.off_tgt[st] = put(t.targets, (size_t)t.n_targets * 3);
+    h.off_ent[st] = (int)w.size();
+    for (int e = 0; e < t.n_entries; ++e) {
+      int32_t bits; memcpy(&bits, &t.entry_bias[e], 4);
+      w.push_back(bits); w.push_back(t.entry_prefix[2 * e]); w.push_back(t.entry_prefix[2 * e + 1]);
+    }
+    h.off_pre[st] = put(t.prefix, t.n_prefix);
+  }
+  memcpy(w.data(), &h, sizeof(h));
+  RuleSet& r = ctx->rule_sets[id];
+  hipError_t e = hipMalloc((void**)&r.d, w.size() * 4);
+  if (e != hipSuccess) { r = RuleSet(); return gvl_hipfail(ctx, e, "hipMalloc((void**)&r.d, w.size() * 4)"); }
+  e = hipMemcpy(r.d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(r.d); r = RuleSet(); return gvl_hipfail(ctx, e, "gvl_rules_create: hipMemcpy"); }
+  *rules_id = id;
+  return 0;
+}
+int gvl_rules_destroy(gvl_ctx* ctx, int rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = ctx->destroy_rules(rules_id, nullptr)) return seq_fail(ctx, "gvl_rules_destroy", rc);   // asks only
+  HIPCHK(ctx, hipDeviceSynchronize());                 // every launch that read the set has finished before its memory goes
+  void* blob = nullptr; ctx->destroy_rules(rules_id, &blob); hipFree(blob);
+  return 0;
+}
+int gvl_set_token_rules(gvl_ctx* ctx, int rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  return seq_fail(ctx, "gvl_set_token_rules", ctx->set_rules(ctx->sel_default, rules_id));
+}
+int gvl_seq_set_token_rules(gvl_ctx* ctx, int seq_id, int rules_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  Seq* sq = ctx->lookup(seq_id);
+  if (!sq) return seq_fail(ctx, "gvl_seq_set_token_rules", SEQ_BAD);
+  return seq_fail(ctx, "gvl_seq_set_token_rules", ctx->set_rules(sq->sel, rules_id));
+}
+int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                                const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
+  if (!rules_ids) return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process_rules: bad arguments");
+  return op_logits_process(ctx, "gvl_op_logits_process_rules", logits, n, batch, hist_dev, hist_stride, lens_dev, penalty, ngram, min_new, eos_ids, rules_ids, stream);
+}
+
+// ---- log-probabilities of the selected tokens (ArgmaxArgs.top_n / lp_lists / top_ids / top_lp; gvl_elem.hip)
+// the slot lists a setting needs, allocated on first use (never during a decode call: the setters run between calls); live sequences are rebound
+static int ensure_logprob_lists(gvl_ctx* ctx, int top_n, const char* what) {
+  if (top_n < -1 || top_n > GVL_MAX_TOP_LOGPROBS) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": top_n must be -1 (off), 0 (selected token) or 1 .. 8");
+  if (top_n < 0) return 0;
+  if (!ctx->has_llm) return fail(ctx, GVL_ERR_STATE, std::string(what) + ": no language model configured");
+  const size_t n = (size_t)gvl_ctx::kMaxSeqs * ctx->outlist_cap;
+  bool grew = false;
+  if (!ctx->d_seq_lp) { HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_lp, n * 4)); grew = true; }
+  if (top_n > 0 && !ctx->d_seq_top_ids) {
+    HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_top_ids, n * GVL_MAX_TOP_LOGPROBS * 4));
+    HIPCHK(ctx, hipMalloc((void**)&ctx->d_seq_top_lp, n * GVL_MAX_TOP_LOGPROBS * 4));
+    grew = true;
+  }
+  if (grew) for (size_t i = 0; i < ctx->seqs.size(); ++i) if (ctx->seqs[i].used) bind_logprobs(ctx, ctx->seqs[i], (int)i);
+  return 0;
+}
+int gvl_set_logprobs(gvl_ctx* ctx, int top_n) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = ensure_logprob_lists(ctx, top_n, "gvl_set_logprobs")) return rc;
+  ctx->sel_default.top_n = top_n;
+  return 0;
+}
+int gvl_seq_set_logprobs(gvl_ctx* ctx, int seq_id, int top_n) {
+  if (!ctx) return GVL_ERR_ARG;
+  Seq* sq = ctx->lookup(seq_id);
+  if (!sq) return seq_fail(ctx, "gvl_seq_set_logprobs", SEQ_BAD);
+  if (const int rc = ensure_logprob_lists(ctx, top_n, "gvl_seq_set_logprobs")) return rc;
+  sq->sel.top_n = top_n;
+  return 0;
+}
+int gvl_seq_read_logprobs(gvl_ctx* ctx, int seq_id, int first, int cap, float* lp, int32_t* top_ids, float* top_lp, int* n_gen, void* stream) {
+  REQUIRE_READY(ctx->has_llm, "gvl_seq_read_logprobs");
+  if (!ctx->lookup(seq_id) || !n_gen || first < 0 || cap < 0) return fail(ctx, GVL_ERR_ARG, "gvl_seq_read_logprobs: bad arguments");
+  const Seq& sq = ctx->seqs[seq_id];
+  if (lp && (sq.sel.top_n < 0 || !sq.d_lp)) return fail(ctx, GVL_ERR_STATE, "gvl_seq_read_logprobs: the sequence has log-probabilities off");
+  if ((top_ids || top_lp) && (sq.sel.top_n < 1 || !sq.d_top_ids)) return fail(ctx, GVL_ERR_STATE, "gvl_seq_read_logprobs: the sequence keeps no top-N lists");
+  *n_gen = sq.n_gen;
+  int n = sq.n_gen - first; if (n > cap) n = cap;
+  if (n > 0) {
+    hipStream_t st = (hipStream_t)stream;
+    const size_t K = GVL_MAX_TOP_LOGPROBS;
+    if (lp) HIPCHK(ctx, hipMemcpyAsync(lp, sq.d_lp + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (top_ids) HIPCHK(ctx, hipMemcpyAsync(top_ids, sq.d_top_ids + (size_t)first * K, (size_t)n * K * 4, hipMemcpyDeviceToHost, st));
+    if (top_lp) HIPCHK(ctx, hipMemcpyAsync(top_lp, sq.d_top_lp + (size_t)first * K, (size_t)n * K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+  }
+  return 0;
+}
+int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, int do_sample, float temperature, int top_k, float top_p, uint64_t seed,
+                           const uint32_t* streams, const int32_t* steps_dev, const int* top_n, int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev,
+                           float* top_lp_dev, void* stream) {
+  if (!ctx || !logits || !top_n || !tokens_dev || !lp_dev || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH)
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: bad arguments");
+  if (do_sample && (!streams || !steps_dev || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f))
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: bad sampling arguments");
+  hipStream_t st = (hipStream_t)stream;
+  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = logits; am.n = n; am.batch = batch;
+  for (int b = 0; b < batch; ++b) {
+    if (top_n[b] < -1 || top_n[b] > GVL_MAX_TOP_LOGPROBS || (top_n[b] > 0 && (!top_ids_dev || !top_lp_dev)))
+      return fail(ctx, GVL_ERR_ARG, "gvl_op_select_logprobs: top_n must be -1 .. 8 (top lists needed for > 0)");
+    am.tok_ptrs[b] = tokens_dev + b;
+    am.top_n[b] = top_n[b]; am.lp_lists[b] = lp_dev + b;
+    if (top_n[b] > 0) { am.top_ids[b] = top_ids_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; am.top_lp[b] = top_lp_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; }
+  }
+  if (!do_sample) { RUN(GVL_PROF_OTHER, 0, gvl_launch_argmax(am, st)); return 0; }
+  am.inv_temp = 1.0f / temperature; am.top_k = top_k; am.top_p = top_p; am.seed_lo = (unsigned)seed; am.seed_hi = (unsigned)(seed >> 32);
+  am.step_override = steps_dev;
+  for (int b = 0; b < batch; ++b) am.stream[b] = streams[b];
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,86 @@
+// gvl_seq_table.h -- host bookkeeping of the paged KV cache's sequences: slots, KV pages and their reference counts, per-sequence token-selection settings, rule-set
+// references.  Host-only, no HIP (tests/c/seq_table_check.cc drives it on a CPU); gvl_ctx derives from SeqTable<Seq> and adds the device side.
+#pragma once
+#include <utility>
+#include <vector>
+
+// HF logits processors of one sequence (gvl_logits.hip); the defaults switch every one of them off
+struct LogitsProc {
+  float penalty = 1.0f; int ngram = 0, min_new = 0, eos = -1;
+  bool on() const { return penalty != 1.0f || ngram > 0 || (min_new > 0 && eos >= 0); }
+};
+// The token-selection settings of one sequence as one value: gvl_seq_alloc copies the table's sel_default (gvl_set_logits_processors / gvl_set_logprobs / gvl_set_token_rules),
+// fork and clone copy the source's, the gvl_seq_set_* setters override.  top_n: -1 off, 0 the selected token's log-probability, 1 .. 8 also the top N.  rules: a rule set (-1 none), counted in its refs
+struct SeqSelect { LogitsProc proc; int top_n = -1; int rules = -1; };
+// a token rule set: one opaque device blob (gvl_rules_create) and how many sequences / the default reference it
+struct RuleSet { bool used = false; void* d = nullptr; int refs = 0; };
+// the host state of one sequence slot; Seq (gvl_ctx.h) adds the slot's device pointers
+struct SeqCore {
+  bool used = false; int max_tokens = 0, n_pages = 0, pos = 0, n_gen = 0;
+  std::vector<int> pages;   // KV pages in position order, 64 tokens each: whole pages of a prefix may be shared with other sequences (page_ref)
+  SeqSelect sel;
+};
+enum SeqStatus { SEQ_OK = 0, SEQ_BAD = -1, SEQ_DUPLICATE = -2, SEQ_NO_PAGES = -3, SEQ_TOO_MANY = -4, SEQ_NO_RULES = -5, SEQ_RULES_BUSY = -6, SEQ_RULES_FULL = -7 };
+
+template <class S = SeqCore>
+struct SeqTable {
+  std::vector<S> seqs; std::vector<RuleSet> rule_sets;
+  std::vector<int> free_pages, page_ref;   // page_ref: sequences holding each page -- full pages of a shared prefix are referenced, never copied (gvl_seq_fork)
+  SeqSelect sel_default;                   // what a sequence without a source starts with (off / none by default)
+  const int max_seqs, max_rule_sets;       // slots of the device-side tables; live rule sets
+
+  SeqTable(int max_seqs_, int max_rule_sets_) : max_seqs(max_seqs_), max_rule_sets(max_rule_sets_) {}
+  void reset_pool(int pages) { free_pages.clear(); page_ref.assign(pages, 0); for (int p = pages - 1; p >= 0; --p) free_pages.push_back(p); }
+  template <class V> static int first_unused(const V& v) { int i = 0; while (i < (int)v.size() && v[i].used) ++i; return i; }   // v.size(): none
+  S* lookup(int id) { return id >= 0 && id < (int)seqs.size() && seqs[id].used ? &seqs[id] : nullptr; }
+  // ids[i] names a sequence that an earlier member of the group named already
+  static bool repeats(const int* ids, int i) { for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) return true; return false; }
+  bool any_live() const { for (const S& q : seqs) if (q.used) return true; return false; }
+  // A new sequence of up to max_tokens tokens -> its id, or a negative SeqStatus with nothing changed.  src < 0 (pos 0): empty, default settings.  src >= 0: it starts with the source's
+  // first `pos` tokens and settings; the pos / 64 whole pages of that prefix are shared (immutable from now on for both holders: appends go to later pages), later pages are its own.
+  int open(int max_tokens, int src, int pos) {
+    const int shared = pos >> 6, np = (max_tokens + 63) / 64;
+    if (pos < 0 || max_tokens <= pos || (src < 0 ? pos != 0 : !lookup(src) || shared > (int)seqs[src].pages.size())) return SEQ_BAD;
+    if ((int)free_pages.size() < np - shared) return SEQ_NO_PAGES;
+    const int id = first_unused(seqs);
+    if (id >= max_seqs) return SEQ_TOO_MANY;
+    S s;                                   // built aside: growing `seqs` may move the source
+    s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = pos;
+    s.sel = src >= 0 ? seqs[src].sel : sel_default;
+    if (s.sel.rules >= 0) ++rule_sets[s.sel.rules].refs;
+    if (src >= 0) s.pages.assign(seqs[src].pages.begin(), seqs[src].pages.begin() + shared);
+    for (int p : s.pages) ++page_ref[p];
+    for (int i = shared; i < np; ++i) { s.pages.push_back(free_pages.back()); free_pages.pop_back(); page_ref[s.pages.back()] = 1; }
+    if (id == (int)seqs.size()) seqs.push_back(std::move(s)); else seqs[id] = std::move(s);
+    return id;
+  }
+  // the sequence's pages and rule set go back; a page shared with a fork lives on until its last holder is closed
+  int close(int id) {
+    S* s = lookup(id); if (!s) return SEQ_BAD;
+    for (int p : s->pages) if (--page_ref[p] == 0) free_pages.push_back(p);
+    if (s->sel.rules >= 0) --rule_sets[s->sel.rules].refs;
+    *s = S(); return SEQ_OK;
+  }
+  // -1 (none) or a live rule set
+  int check_rules(int id) const { return id < -1 || id >= (int)rule_sets.size() || (id >= 0 && !rule_sets[id].used) ? SEQ_NO_RULES : SEQ_OK; }
+  int add_rules(void* d) {
+    const int id = first_unused(rule_sets);
+    if (id >= max_rule_sets) return SEQ_RULES_FULL;
+    if (id == (int)rule_sets.size()) rule_sets.emplace_back();
+    rule_sets[id] = RuleSet{true, d, 0}; return id;
+  }
+  // `sel` (a sequence's, or sel_default) takes rule set `id` (-1: none) and drops the one it held
+  int set_rules(SeqSelect& sel, int id) {
+    if (check_rules(id)) return SEQ_NO_RULES;
+    if (id >= 0) ++rule_sets[id].refs;               // before the drop: `id` may be the set it holds
+    if (sel.rules >= 0) --rule_sets[sel.rules].refs;
+    sel.rules = id; return SEQ_OK;
+  }
+  // refused while a sequence or the default references the set.  d null: only asks; otherwise the set goes and *d is its blob, which the caller now owns
+  int destroy_rules(int id, void** d) {
+    if (id < 0 || check_rules(id)) return SEQ_NO_RULES;
+    if (rule_sets[id].refs > 0) return SEQ_RULES_BUSY;
+    if (d) { *d = rule_sets[id].d; rule_sets[id] = RuleSet(); }
+    return SEQ_OK;
+  }
+};

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import logits as LP
 from . import logprobs as LPR
 
 bf = torch.bfloat16
@@ -403,20 +404,13 @@ class Engine:
         """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  processors: a logits.Processors for this
         sequence (None: the default of set_logits_processors).  rules: a rule-set id for this sequence (None: the default of set_token_rules).  logprobs: None = ids only; -1 .. 8 = this sequence's seq_set_logprobs setting, and
         the return value is (ids, (lp, top)) as seq_read_logprobs gives them for the ids (read before the sequence is freed)."""
-        S = embeds.shape[0]
-        seq = self.seq_alloc(min(S + max_new_tokens, self.geo.max_seq))
+        opts = LP.SeqOptions(processors, logprobs, ... if rules is None else rules)
+        seq = self.seq_alloc(min(embeds.shape[0] + max_new_tokens, self.geo.max_seq))
         try:
-            if processors is not None:
-                self.seq_set_processors(seq, *processors.args())
-            if logprobs is not None:
-                self.seq_set_logprobs(seq, logprobs)
-            if rules is not None:
-                self.seq_set_token_rules(seq, rules)
+            LP.apply_seq_options(self, seq, opts)
             self.prefill(seq, embeds)
             ids = self.decode_greedy(seq, max_new_tokens, eos_id)
-            if logprobs is None:
-                return ids
-            return ids, self.seq_read_logprobs(seq, 0, len(ids), top=logprobs > 0)
+            return ids if logprobs is None else (ids, LP.read_seq_logprobs(self, seq, ids, opts))
         finally:
             self.seq_free(seq)
 

@@ -88,6 +88,32 @@ def resolve(kw: dict, eos_id: Optional[int], embed_len: int = 0) -> Processors:
     return Processors(penalty, ngram, 0, -1)
 
 
+@dataclass(frozen=True)
+class SeqOptions:
+    """One sequence's settings; per field leave what it was allocated with | off | set: processors None | OFF | a Processors; logprobs None | -1 | 0 .. 8; rules ... | None | a rules_create id"""
+    processors: Optional[Processors] = None
+    logprobs: Optional[int] = None
+    rules: object = ...
+
+
+SeqOptions.OFF = SeqOptions(OFF, -1, None)
+
+
+def apply_seq_options(eng, seq: int, opts: SeqOptions) -> None:
+    """Set what `opts` does not leave alone on the live sequence `seq` (right after its seq_alloc / seq_fork, before its prefill)."""
+    if opts.processors is not None:
+        eng.seq_set_processors(seq, *opts.processors.args())
+    if opts.logprobs is not None:
+        eng.seq_set_logprobs(seq, opts.logprobs)
+    if opts.rules is not ...:
+        eng.seq_set_token_rules(seq, opts.rules)
+
+
+def read_seq_logprobs(eng, seq: int, ids, opts: SeqOptions):
+    """(lp, top) of the generated `ids` of `seq` (Engine.seq_read_logprobs; before the sequence is freed); None when opts.logprobs left the engine's default."""
+    return None if opts.logprobs is None else eng.seq_read_logprobs(seq, 0, len(ids), top=opts.logprobs > 0)
+
+
 def padded_embed_len(ids_width: int, n_visual: int) -> int:
     """Rows of the reference's inputs_embeds for a batch whose left-padded id rows are `ids_width` wide (one image slot -> n_visual rows)."""
     return int(ids_width) - 1 + int(n_visual)

@@ -28,6 +28,19 @@ from .engine import Engine, TowerGeometry
 bf = torch.bfloat16
 
 
+def _sampling_args(kw):
+    """(temperature, top_p, seed) of a do_sample call, validated as HF's warpers do; without `seed` one is drawn from torch's CPU generator."""
+    t = kw.get("temperature", 1.0)
+    t = 1.0 if t is None else float(t)
+    if not t > 0:
+        raise ValueError("`temperature` has to be a strictly positive float")      # HF's TemperatureLogitsWarper check
+    top_p = kw.get("top_p")
+    if top_p is not None and not (0 < float(top_p) <= 1.0):
+        raise ValueError("`top_p` has to be a float > 0 and <= 1")
+    seed = kw.get("seed")
+    return t, top_p, int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
 class SyntheticTokenizer:
     """Stand-in for the HF tokenizer (tokenizer files are not available offline): whitespace words -> ids by a
     stable hash; the 302 temporal tokens map to the last 302 rows of the vocabulary like `add_tokens` does."""
@@ -286,17 +299,8 @@ class LLAVA_NEXT_VIDEO:
             # greedy -- and every kind of beam search: the steps return logits, the selection (top-2k, or the beam-sample draw) lives in beam.py
             self.engine.set_sampling(False)
             return
-        t = kw.get("temperature", 1.0)
-        t = 1.0 if t is None else float(t)
-        if not t > 0:
-            raise ValueError("`temperature` has to be a strictly positive float")      # HF's TemperatureLogitsWarper check
-        top_p = kw.get("top_p")
-        if top_p is not None and not (0 < float(top_p) <= 1.0):
-            raise ValueError("`top_p` has to be a float > 0 and <= 1")
+        t, top_p, seed = _sampling_args(kw)
         top_k = kw.get("top_k", 50)
-        seed = kw.get("seed")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.engine.set_sampling(True, t, 0 if top_k is None else int(top_k), top_p, seed)
 
     def _n_visual(self, samples) -> int:
@@ -337,16 +341,9 @@ class LLAVA_NEXT_VIDEO:
         if k > 1:                                         # HF beam search (do_sample=False), one sample at a time
             sample = None
             if generate_kwargs.get("do_sample", False):      # beam-sample (HF _beam_sample): the warpers' arguments as generate() takes them; one generator per call
-                t = generate_kwargs.get("temperature", 1.0)
-                t = 1.0 if t is None else float(t)
-                if not t > 0:
-                    raise ValueError("`temperature` has to be a strictly positive float")
-                top_p = generate_kwargs.get("top_p")
-                if top_p is not None and not (0 < float(top_p) <= 1.0):
-                    raise ValueError("`top_p` has to be a float > 0 and <= 1")
-                seed = generate_kwargs.get("seed")
+                t, top_p, seed = _sampling_args(generate_kwargs)
                 gen = torch.Generator(device=self.engine.device)
-                gen.manual_seed(int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+                gen.manual_seed(seed)
                 sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen)
             scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
@@ -392,9 +389,7 @@ class LLAVA_NEXT_VIDEO:
                     return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
                 return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules)
         try:
-            eng.seq_set_processors(beams[0], *LP.OFF.args())     # the steps must hand back raw logits (clones copy this setting)
-            eng.seq_set_token_rules(beams[0], None)
-            eng.seq_set_logprobs(beams[0], -1)                   # the scores come from the host rows (beam.py)
+            LP.apply_seq_options(eng, beams[0], LP.SeqOptions.OFF)    # the steps must hand back raw logits, the scores come from the host rows (beam.py); clones copy these settings
             first = eng.prefill(beams[0], emb, want_logits=True)
 
             def step(parents: List[int], toks: List[int]) -> torch.Tensor:
@@ -489,21 +484,19 @@ class LLAVA_NEXT_VIDEO:
             return None
         self.last_shared_prefix = prefix
         eos = getattr(self.tokenizer, "eos_token_id", None)
+        opts = [LP.SeqOptions(p, logprobs) for p in (processors or [None] * len(rows))]
         base, seqs = None, []
         try:
             base = eng.seq_alloc(prefix)
             eng.prefill(base, embs[0][:prefix])
-            for i, e in enumerate(embs):
+            for o, e in zip(opts, embs):
                 seqs.append(eng.seq_fork(base, prefix, min(e.shape[0] + max_new, self.geo.max_seq)))
-                if processors is not None:
-                    eng.seq_set_processors(seqs[-1], *processors[i].args())
-                if logprobs is not None:
-                    eng.seq_set_logprobs(seqs[-1], logprobs)
+                LP.apply_seq_options(eng, seqs[-1], o)
                 eng.prefill_extend(seqs[-1], e[prefix:])
             got = eng.decode_greedy_batch(seqs, max_new, eos)
             if logprobs is None:
                 return got
-            return got, [eng.seq_read_logprobs(s_, 0, len(g), top=logprobs > 0) for s_, g in zip(seqs, got)]
+            return got, [LP.read_seq_logprobs(eng, s_, g, o) for s_, g, o in zip(seqs, got, opts)]
         finally:
             for s_ in seqs:
                 eng.seq_free(s_)
@@ -550,11 +543,10 @@ class LLAVA_NEXT_VIDEO:
         is (ids, lps) with lps[i] = (lp, top) of row i as Engine.seq_read_logprobs reads them back before the sequence is freed."""
         eos = getattr(self.tokenizer, "eos_token_id", None)
         eng = self.engine
-        if processors is not None and not isinstance(processors, (list, tuple)):
-            processors = [processors] * ids_arr.shape[0]
+        opts = [LP.SeqOptions(p, logprobs) for p in (processors if isinstance(processors, (list, tuple)) else [processors] * ids_arr.shape[0])]
         if ids_arr.shape[0] == 1:
             row = [int(t) for t, m in zip(ids_arr[0], mask[0]) if m]
-            got = eng.generate_ids(eng.splice(row, feats[0]), max_new, eos, processors=None if processors is None else processors[0], logprobs=logprobs)
+            got = eng.generate_ids(eng.splice(row, feats[0]), max_new, eos, processors=opts[0].processors, logprobs=logprobs)
             return [got] if logprobs is None else ([got[0]], [got[1]])
         # bs > 1 (the reference left-pads the batch, llava_next_video.py:622-647): every sample keeps its own paged KV and its
         # un-padded length -- identical maths to the masked left-padded batch.  Prefill runs over the packed rows of the batch
@@ -578,15 +570,12 @@ class LLAVA_NEXT_VIDEO:
                         if e.status == ERR_OOM and seqs:
                             break                      # pool full: run what fits, the rest in the next group
                         raise
-                    if processors is not None:
-                        eng.seq_set_processors(seqs[-1], *processors[i].args())
-                    if logprobs is not None:
-                        eng.seq_set_logprobs(seqs[-1], logprobs)
+                    LP.apply_seq_options(eng, seqs[-1], opts[i])
                     embs.append(emb)
                 eng.prefill_batch(seqs, embs)
                 got = eng.decode_greedy_batch(seqs, max_new, eos)
                 if logprobs is not None:
-                    lps += [eng.seq_read_logprobs(s_, 0, len(g), top=logprobs > 0) for s_, g in zip(seqs, got)]
+                    lps += [LP.read_seq_logprobs(eng, s_, g, o) for s_, g, o in zip(seqs, got, opts[b:])]
                 out += got
             finally:
                 for seq in seqs:

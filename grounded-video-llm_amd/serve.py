@@ -18,10 +18,11 @@ on CPU against a scripted engine (tests/test_host_logic.py).
 from __future__ import annotations
 
 from collections import deque
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Deque, Dict, List, Optional, Sequence
 
 from . import lib as L
+from . import logits as LP
 
 
 @dataclass
@@ -32,10 +33,8 @@ class _Request:
     seq: int = -1
     ids: List[int] = field(default_factory=list)
     n_gen: int = 0               # tokens generated on the device so far (>= len(ids) once eos was seen)
-    processors: object = None    # logits.Processors of this request (None: the engine's default)
-    logprobs: Optional[int] = None   # gvl_seq_set_logprobs setting of this request (None: the engine's default, not read back)
-    rules: object = None         # logits.TokenRules of this request (None: the engine's default)
-    rules_id: Optional[int] = None   # its device rule set: created when the request is admitted, destroyed when it retires
+    opts: LP.SeqOptions = LP.SeqOptions()   # this request's settings (a field left alone: the engine's default); opts.rules holds its logits.TokenRules ...
+    rules_id: Optional[int] = None   # ... and this their device rule set: created when the request is admitted, destroyed when it retires
 
 
 class ClipScheduler:
@@ -69,17 +68,14 @@ class ClipScheduler:
             raise ValueError("max_new_tokens must be >= 1")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
             raise ValueError(f"logprobs must be None or an integer in 0 .. 8, not {logprobs!r}")
-        procs = None
-        if repetition_penalty is not None or no_repeat_ngram_size is not None or min_new_tokens is not None:
-            from . import logits as LP
-            procs = LP.resolve(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens), self.eos)
-        rules = None
+        pkw = dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens)
+        procs = LP.resolve(pkw, self.eos) if any(v is not None for v in pkw.values()) else None
+        rules = ...
         rkw = dict(bad_words_ids=bad_words_ids, sequence_bias=sequence_bias, suppress_tokens=suppress_tokens,
                    begin_suppress_tokens=begin_suppress_tokens, forced_eos_token_id=forced_eos_token_id)
         if any(v is not None for v in rkw.values()):
-            from . import logits as LP
             rules = LP.resolve_rules(rkw, self.eos, int(max_new_tokens), getattr(getattr(self.eng, "geo", None), "vocab", None))
-        r = _Request(self._next, embeds, int(max_new_tokens), processors=procs, logprobs=logprobs, rules=rules)
+        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules))
         self._next += 1
         self.queue.append(r)
         return r.rid
@@ -136,19 +132,14 @@ class ClipScheduler:
                 if getattr(e, "status", 0) == L.ERR_OOM:     # KV pages exhausted: wait for a retirement (FIFO, no overtaking)
                     break
                 raise
-            if r.processors is not None or r.logprobs is not None or r.rules is not None:
-                try:
-                    if r.processors is not None:
-                        self.eng.seq_set_processors(r.seq, *r.processors.args())
-                    if r.logprobs is not None:
-                        self.eng.seq_set_logprobs(r.seq, r.logprobs)
-                    if r.rules is not None:                  # an inactive set still overrides the engine's default: this request runs without rules
-                        r.rules_id = self.eng.rules_create(r.rules) if r.rules.active else None
-                        self.eng.seq_set_token_rules(r.seq, r.rules_id)
-                except Exception:
-                    self.eng.seq_free(r.seq)
-                    self._drop_rules(r)
-                    raise
+            try:
+                if r.opts.rules is not ... and r.opts.rules.active:    # an inactive set still overrides the engine's default: this request runs without rules
+                    r.rules_id = self.eng.rules_create(r.opts.rules)
+                LP.apply_seq_options(self.eng, r.seq, r.opts if r.opts.rules is ... else replace(r.opts, rules=r.rules_id))
+            except Exception:
+                self.eng.seq_free(r.seq)
+                self._drop_rules(r)
+                raise
             r.max_new = min(r.max_new, cap - S + 1)          # generate() stops at the context limit (Engine.generate_ids does too)
             self.queue.popleft()
             new.append(r)
@@ -179,8 +170,8 @@ class ClipScheduler:
                     stop = True
                     break
             if stop or len(r.ids) >= r.max_new:
-                if r.logprobs is not None:                   # before the slot is freed: its lists are reused by the next sequence
-                    self.done_logprobs[r.rid] = self.eng.seq_read_logprobs(r.seq, 0, len(r.ids), top=r.logprobs > 0)
+                if r.opts.logprobs is not None:              # before the slot is freed: its lists are reused by the next sequence
+                    self.done_logprobs[r.rid] = LP.read_seq_logprobs(self.eng, r.seq, r.ids, r.opts)
                 self.eng.seq_free(r.seq)                     # seq_read synchronised the stream: no step of r is in flight
                 self._drop_rules(r)
                 self.done[r.rid] = r.ids
