@@ -59,10 +59,13 @@ class _Hyps:
         return self.worst >= best_sum_logprobs / (cur_len ** self.lp)
 
 
-def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = None, min_keep: int = 2) -> torch.Tensor:
+def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = None, min_keep: int = 2,
+                min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                eta_cutoff: Optional[float] = None) -> torch.Tensor:
     """transformers 4.40.1 logits warpers in generate()'s order on `scores` [rows, V] (here: log-probabilities): TemperatureLogitsWarper (scores / T),
     TopKLogitsWarper (everything below the k-th largest -> -inf; k = max(top_k, min_keep)), TopPLogitsWarper (ascending sort, drop the tokens whose
-    cumulative probability stays <= 1 - top_p, never the last min_keep)."""
+    cumulative probability stays <= 1 - top_p, never the last min_keep); then HF's MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and
+    EtaLogitsWarper in that order (None / 0 = off; typical_p 1.0 = off), each on the rows the stage before left, each keeping at least min_keep."""
     s = scores.float()
     if temperature is not None and temperature != 1.0:
         s = s / float(temperature)
@@ -74,6 +77,29 @@ def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[
         remove = srt.softmax(dim=-1).cumsum(dim=-1) <= (1.0 - float(top_p))
         remove[..., -min_keep:] = False
         s = s.masked_fill(remove.scatter(-1, idx, remove), float("-inf"))
+    V = s.shape[-1]
+    if min_p:                                                # p < min_p * p_max goes, never the min_keep most probable
+        probs = torch.softmax(s, dim=-1)
+        remove = probs < float(min_p) * probs.amax(dim=-1, keepdim=True)
+        remove.scatter_(-1, torch.topk(probs, min(min_keep, V), dim=-1).indices, False)
+        s = s.masked_fill(remove, float("-inf"))
+    if typical_p and typical_p < 1.0:                        # ascending |-log p - H|: keep up to and including the first whose cumulative mass reaches typical_p
+        norm = torch.log_softmax(s, dim=-1)
+        ent = -(norm * norm.exp()).nansum(-1, keepdim=True)
+        srt, idx = torch.sort(torch.abs(-norm - ent), descending=False)
+        cum = s.gather(-1, idx).softmax(dim=-1).cumsum(dim=-1)
+        last = (cum < float(typical_p)).sum(dim=-1).clamp_(max=V - 1)
+        remove = srt > srt.gather(-1, last[..., None])
+        remove[..., :min_keep] = False
+        s = s.masked_fill(remove.scatter(-1, idx, remove), float("-inf"))
+    for cut, eta in ((epsilon_cutoff, False), (eta_cutoff, True)):
+        if not cut:
+            continue
+        c = torch.tensor(float(cut), device=s.device)
+        if eta:                                              # min(eta, sqrt(eta) * exp(-H))
+            c = torch.min(c, torch.sqrt(c) * torch.exp(-torch.distributions.Categorical(logits=s).entropy()))[..., None]
+        remove = (s.softmax(dim=-1) < c) & (s < torch.topk(s, min(min_keep, V)).values[..., -1, None])
+        s = s.masked_fill(remove, float("-inf"))
     return s
 
 
@@ -83,7 +109,7 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     """first_logits [vocab]: logits after the prompt.  step(parents, tokens) -> logits [k, vocab] of the k new running beams, where new beam j
     continues old beam parents[j] with tokens[j] (the caller reorders its KV cache accordingly; at the first call every parent is 0 = the
     prompt).  Returns the NEW ids of the best hypothesis (eos included when it ended by eos), as HF does for inputs_embeds prompts.
-    sample: None = beam search; dict(temperature, top_k, top_p, generator) = beam-sample (module docstring).
+    sample: None = beam search; dict(temperature, top_k, top_p, generator[, min_p, typical_p, epsilon_cutoff, eta_cutoff]) = beam-sample (module docstring).
     process(histories, logprobs) -> logprobs: HF's logits processors (repetition penalty, no-repeat n-gram, min length; grounded_video_llm_amd/logits.py)
     on the [k, vocab] log-softmax rows of the running beams, histories[j] = the ids beam j generated so far; applied before the warpers and before
     the beam scores are added, as HF's _beam_search / _beam_sample do.
@@ -117,7 +143,8 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
             top = torch.topk(lp.reshape(-1), 2 * k, largest=True, sorted=True)
             vals, idxs = top.values.tolist(), top.indices.tolist()
         else:
-            proc = warp_scores(lp, sample.get("temperature", 1.0), sample.get("top_k", 50), sample.get("top_p"))
+            proc = warp_scores(lp, sample.get("temperature", 1.0), sample.get("top_k", 50), sample.get("top_p"), min_p=sample.get("min_p"),
+                               typical_p=sample.get("typical_p"), epsilon_cutoff=sample.get("epsilon_cutoff"), eta_cutoff=sample.get("eta_cutoff"))
             lp = proc + scores[:, None]
             flat = lp.reshape(-1)
             n_fin = int(torch.isfinite(flat).sum())

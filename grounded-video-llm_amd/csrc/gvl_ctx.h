@@ -105,7 +105,10 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   int* h_eos_flags = nullptr; int* d_eos_flags = nullptr; int watch_eos = -1;
   hipEvent_t step_ev[3] = {nullptr, nullptr, nullptr};
   // token selection (gvl_set_sampling): greedy argmax unless `on`
-  struct { bool on = false; float inv_temp = 1.f, top_p = 0.f; int top_k = 0; unsigned long long seed = 0; unsigned next_stream = 0; } sample;
+  // (gvl_set_sampling_ex adds min_p / typical_p / eps / eta; sequences with SeqSelect::own_sampling do not follow it)
+  struct { bool on = false; float inv_temp = 1.f, top_p = 0.f; int top_k = 0; unsigned long long seed = 0; unsigned next_stream = 0;
+           float min_p = 0.f, typical_p = 0.f, eps = 0.f, eta = 0.f;
+           bool warps() const { return on && (min_p > 0.f || (typical_p > 0.f && typical_p < 1.f) || eps > 0.f || eta > 0.f); } } sample;
   // log-probability lists of every sequence slot ([kMaxSeqs][outlist_cap], top lists x GVL_MAX_TOP_LOGPROBS: ~134 MB), allocated by the first
   // gvl_set_logprobs / gvl_seq_set_logprobs that needs them
   float* d_seq_lp = nullptr; int* d_seq_top_ids = nullptr; float* d_seq_top_lp = nullptr;

@@ -874,9 +874,9 @@ __device__ __forceinline__ void lp_wave_merge(float (&tv)[GVL_MAX_TOP_LOGPROBS],
   }
 }
 // Whole block, row b on (block-uniform).  Kept set: keys >= thr (0: every entry).  Returns log(sum over the kept set of exp((s - m) * invT));
-// with LPM == 2 and top_n[b] > 0 it also stores row b's top list at generation index g.
-template <int LPM>
-__device__ float lp_row_pass(const ArgmaxArgs& a, int b, const float* l, float m, float inv_temp, unsigned thr, int g) {
+// with LPM == 2 and top_n[b] > 0 it also stores row b's top list at generation index g.  BAND (select_rows_kernel): the kept set is thr <= key <= hi.
+template <int LPM, bool BAND = false>
+__device__ float lp_row_pass(const ArgmaxArgs& a, int b, const float* l, float m, float inv_temp, unsigned thr, int g, [[maybe_unused]] unsigned hi = 0xffffffffu) {
   __shared__ float shz[16];
   const int tid = threadIdx.x, n = a.n;
   const bool top = LPM == 2 && a.top_n[b] > 0 && a.top_ids[b] && a.top_lp[b];
@@ -887,6 +887,7 @@ __device__ float lp_row_pass(const ArgmaxArgs& a, int b, const float* l, float m
   for (int i = tid; i < n; i += 1024) {
     const float v = l[i];
     if (smp_key(v) < thr) continue;
+    if constexpr (BAND) if (smp_key(v) > hi) continue;
     z += expf((v - m) * inv_temp);
     if (LPM == 2 && top && fabsf(v) < INFINITY) lp_insert(tv, ti, v, i);
   }
@@ -1099,6 +1100,238 @@ int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st) {
     case 0: hipLaunchKernelGGL(sample_kernel<0>, dim3(a.batch), dim3(1024), 0, st, a); break;
     case 1: hipLaunchKernelGGL(sample_kernel<1>, dim3(a.batch), dim3(1024), 0, st, a); break;
     case 2: hipLaunchKernelGGL(sample_kernel<2>, dim3(a.batch), dim3(1024), 0, st, a); break;
+    default: return -1;
+  }
+  return CHECK_LAUNCH();
+}
+// ---- per-row selection (SelRowsArgs): a decode group whose rows do not share one setting -- greedy rows next to sampled rows of different temperature / top-k / top-p /
+// seed -- or whose setting uses HF's further warpers (MinP, Typical, Epsilon, Eta; transformers generation/logits_process.py [ext]).  One block per row, the row's
+// parameters by value.  A greedy row runs argmax_kernel's code, a sampled row sample_kernel's up to top-p (same arithmetic, same reduction order: with the further warpers off
+// the token and log-probabilities are bit-identical to those kernels'), then, with e_i = exp((s_i - ref) / T), ref = the largest kept score, Z = sum of e over the kept set:
+//   min_p      keep e_i >= min_p                          (p_i >= min_p * p_max; p_max = 1 / Z)
+//   typical_p  xbar = sum(e x) / Z, x = (s - ref) / T; d_i = |x_i - xbar| (= |-log p_i - H|: -log p_i = log Z - x_i, H = log Z - xbar); t = the smallest d with
+//              mass{d_j <= t} >= typical_p * Z, by bisection on d's bit pattern (d >= 0: the bits order like the values); keep d_i <= t, ties at t included
+//   epsilon    keep e_i >= eps * Z, and the largest kept score
+//   eta        H = log Z - xbar over the current set, c = min(eta, sqrt(eta) exp(-H)); keep e_i >= c * Z, and the largest kept score
+// Scores are monotone in p, so every stage leaves an INTERVAL [lo, hi] of keys (typical_p alone may lower hi: it can drop the maximum); a stage is one fixed-order
+// sum pass plus one min / max pass over the keys that qualify.  min_tokens_to_keep = 1 throughout, as in sample_kernel.
+__device__ __forceinline__ float smp_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+// min of lo / max of hi over the block, in every thread (integers: the order of the reduction cannot matter)
+__device__ __forceinline__ void smp_block_minmax(unsigned& lo, unsigned& hi, unsigned* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned ol = __shfl_xor(lo, o, 64), oh = __shfl_xor(hi, o, 64);
+    lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = lo; sh[16 + (threadIdx.x >> 6)] = hi; }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 16; ++w) { lo = sh[w] < lo ? sh[w] : lo; hi = sh[16 + w] > hi ? sh[16 + w] : hi; }
+}
+template <int LPM>
+__global__ __launch_bounds__(1024) void select_rows_kernel(const SelRowsArgs sa) {
+  __shared__ float shf[16];
+  __shared__ int shi[16];
+  __shared__ int hist[256];
+  __shared__ unsigned s_sel[2];
+  __shared__ unsigned shk[32];
+  const ArgmaxArgs& a = sa.am;
+  const int b = blockIdx.x, tid = threadIdx.x, n = a.n;
+  const float* l = a.logits + (size_t)b * n;
+  if (!sa.row[b].on) {                       // ---- greedy row (block-uniform): argmax_kernel's code
+    float best = -3.4e38f; int idx = 0x7fffffff;
+    for (int i = tid; i < n; i += 1024) {
+      const float v = l[i];
+      if (v > best) { best = v; idx = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
+      if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6] = idx; }
+    __syncthreads();
+    [[maybe_unused]] float lz = 0.f;
+    if constexpr (LPM > 0) {
+      if (lp_row_on(a, b)) {
+        float m = shf[0]; int mi = shi[0];
+        for (int w = 1; w < 16; ++w) if (shf[w] > m || (shf[w] == m && shi[w] < mi)) { m = shf[w]; mi = shi[w]; }
+        lz = lp_row_pass<LPM>(a, b, l, m, 1.0f, 0u, lp_row_step(a, b));
+      }
+    }
+    if (sa.kept) for (int i = tid; i < n; i += 1024) sa.kept[(size_t)b * n + i] = fabsf(l[i]) < INFINITY ? 1 : 0;
+    if (tid == 0) {
+      for (int w = 1; w < 16; ++w) if (shf[w] > best || (shf[w] == best && shi[w] < idx)) { best = shf[w]; idx = shi[w]; }
+      *a.tok_ptrs[b] = idx;
+      if constexpr (LPM > 0) if (lp_row_on(a, b)) a.lp_lists[b][lp_row_step(a, b)] = 0.f - lz;
+      if (a.ngen_ptrs[b]) {
+        const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
+        if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
+    }
+    return;
+  }
+  // ---- sampled row.  1 - 4: sample_kernel's row maximum, top-k radix select, normaliser and top-p bisection
+  const float iT = sa.row[b].inv_temp;
+  const int top_k = sa.row[b].top_k;
+  const float top_p = sa.row[b].top_p;
+  float m = -3.4e38f;
+  for (int i = tid; i < n; i += 1024) m = fmaxf(m, l[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if ((tid & 63) == 0) shf[tid >> 6] = m;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 16; ++w) m = fmaxf(m, shf[w]);
+  unsigned kth = 0;
+  if (top_k > 0 && top_k < n) {
+    unsigned prefix = 0; int remaining = top_k;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      for (int i = tid; i < n; i += 1024) {
+        const unsigned k = smp_key(l[i]);
+        if (shift == 24 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        int c = 0, bsel = 0;
+        for (int q = 255; q >= 0; --q) { if (c + hist[q] >= remaining) { bsel = q; break; } c += hist[q]; }
+        s_sel[0] = prefix | ((unsigned)bsel << shift); s_sel[1] = (unsigned)(remaining - c);
+      }
+      __syncthreads();
+      prefix = s_sel[0]; remaining = (int)s_sel[1];
+      __syncthreads();
+    }
+    kth = prefix;
+  }
+  unsigned lo = kth, hi = smp_key(m);
+  if (top_p > 0.f && top_p < 1.f) {
+    float z = 0.f;
+    for (int i = tid; i < n; i += 1024) { const float v = l[i]; if (smp_key(v) >= kth) z += expf((v - m) * iT); }
+    const float Z = smp_block_sum(z, shf);
+    const float target = top_p * Z;
+    unsigned blo = kth, bhi = smp_key(m);
+    while (blo < bhi) {
+      const unsigned mid = blo + ((bhi - blo) >> 1);
+      float s = 0.f;
+      for (int i = tid; i < n; i += 1024) { const float v = l[i]; if (smp_key(v) > mid) s += expf((v - m) * iT); }
+      const float S = smp_block_sum(s, shf);
+      if (S < target) bhi = mid; else blo = mid + 1;
+    }
+    lo = blo;
+  }
+  // ---- the further warpers on the interval [lo, hi]; ref = the largest kept score (the row maximum until typical_p drops it)
+  float ref = m;
+  // Z = sum of e, S1 = sum of e * x over the current set, fixed order (-inf entries: e = 0, left out of S1)
+  auto set_sums = [&](float& Z, float& S1) {
+    float z = 0.f, s1 = 0.f;
+    for (int i = tid; i < n; i += 1024) {
+      const float v = l[i]; const unsigned k = smp_key(v);
+      if (k < lo || k > hi) continue;
+      const float x = (v - ref) * iT, e = expf(x);
+      z += e; if (x > -INFINITY) s1 += e * x;
+    }
+    Z = smp_block_sum(z, shf); S1 = smp_block_sum(s1, shf);
+  };
+  // lo <- the smallest key of the current set with e >= cut (the largest kept score always stays)
+  auto raise_lo = [&](float cut) {
+    unsigned kl = hi, kh = 0u;
+    for (int i = tid; i < n; i += 1024) {
+      const float v = l[i]; const unsigned k = smp_key(v);
+      if (k < lo || k > hi) continue;
+      if (expf((v - ref) * iT) >= cut && k < kl) kl = k;
+    }
+    smp_block_minmax(kl, kh, shk);
+    lo = kl;
+  };
+  const float min_p = sa.row[b].min_p, typ = sa.row[b].typical_p, eps = sa.row[b].eps, eta = sa.row[b].eta;
+  if (min_p > 0.f) raise_lo(min_p);
+  if (typ > 0.f && typ < 1.f) {
+    float Z, S1; set_sums(Z, S1);
+    const float xbar = S1 / Z, target = typ * Z;
+    unsigned dl = 0u, dh = 0x7f800000u;
+    while (dl < dh) {
+      const unsigned mid = dl + ((dh - dl) >> 1);
+      float s = 0.f;
+      for (int i = tid; i < n; i += 1024) {
+        const float v = l[i]; const unsigned k = smp_key(v);
+        if (k < lo || k > hi) continue;
+        const float x = (v - ref) * iT;
+        if (__float_as_uint(fabsf(x - xbar)) <= mid) s += expf(x);
+      }
+      const float S = smp_block_sum(s, shf);
+      if (S >= target) dh = mid; else dl = mid + 1;
+    }
+    unsigned kl = 0xffffffffu, kh = 0u;
+    for (int i = tid; i < n; i += 1024) {
+      const float v = l[i]; const unsigned k = smp_key(v);
+      if (k < lo || k > hi) continue;
+      if (__float_as_uint(fabsf((v - ref) * iT - xbar)) <= dl) { kl = k < kl ? k : kl; kh = k > kh ? k : kh; }
+    }
+    smp_block_minmax(kl, kh, shk);
+    if (kl <= kh) { lo = kl; hi = kh; ref = smp_unkey(hi); }     // (an all-NaN band cannot empty the set)
+  }
+  if (eps > 0.f) { float Z, S1; set_sums(Z, S1); raise_lo(eps * Z); }
+  if (eta > 0.f) {
+    float Z, S1; set_sums(Z, S1);
+    const float H = logf(Z) - S1 / Z;
+    raise_lo(fminf(eta, sqrtf(eta) * expf(-H)) * Z);
+  }
+  // ---- Gumbel-max draw over [lo, hi]: sample_kernel's hash and score, the row's own seed and stream
+  const int step = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] : (a.step_override ? a.step_override[b] : 0);
+  const unsigned k0 = smp_fmix32(sa.row[b].seed_lo ^ 0x9e3779b9u), k1 = smp_fmix32(sa.row[b].seed_hi ^ k0 ^ 0x85ebca77u);
+  const unsigned kk = smp_fmix32(k1 ^ smp_fmix32(sa.row[b].stream * 0x9e3779b1u + 0x7f4a7c15u) ^ smp_fmix32((unsigned)step * 0x85ebca77u + 0x165667b1u));
+  const unsigned kk2 = smp_fmix32(kk + 0x632be5abu);
+  float best = -3.4e38f; int idx = 0x7fffffff;
+  for (int i = tid; i < n; i += 1024) {
+    const float v = l[i]; const unsigned k = smp_key(v);
+    if (k < lo || k > hi) continue;
+    const unsigned h = smp_fmix32(smp_fmix32((unsigned)i + kk) ^ kk2);
+    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float sc = (v - ref) * iT - logf(-logf(u));
+    if (sc > best) { best = sc; idx = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
+    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+  }
+  __syncthreads();
+  if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6] = idx; }
+  __syncthreads();
+  if (sa.kept) for (int i = tid; i < n; i += 1024) { const float v = l[i]; const unsigned k = smp_key(v); sa.kept[(size_t)b * n + i] = k >= lo && k <= hi && fabsf(v) < INFINITY ? 1 : 0; }
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w) if (shf[w] > best || (shf[w] == best && shi[w] < idx)) { best = shf[w]; idx = shi[w]; }
+    *a.tok_ptrs[b] = idx;
+    if (a.ngen_ptrs[b]) {
+      const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
+      if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
+  }
+  if constexpr (LPM > 0) {                   // after the selection, over the FINAL kept set (sample_kernel's order)
+    if (lp_row_on(a, b)) {
+      __syncthreads();
+      const int g = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] - 1 : 0;
+      const float lz = lp_row_pass<LPM, true>(a, b, l, ref, iT, lo, g, hi);
+      if (tid == 0) { const int tok = *a.tok_ptrs[b]; a.lp_lists[b][g] = tok >= 0 && tok < n ? (l[tok] - ref) * iT - lz : -INFINITY; }
+    }
+  }
+}
+int gvl_launch_select_rows(const SelRowsArgs& sa, hipStream_t st) {
+  const ArgmaxArgs& a = sa.am;
+  if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH) return -1;
+  for (int b = 0; b < a.batch; ++b) {
+    const SelRow& r = sa.row[b];
+    if (r.on && (!(r.inv_temp > 0.f) || r.top_k < 0 || !(r.top_p >= 0.f) || !(r.min_p >= 0.f) || !(r.typical_p >= 0.f) || !(r.eps >= 0.f) || !(r.eta >= 0.f))) return -1;
+  }
+  switch (lp_mode(a)) {
+    case 0: hipLaunchKernelGGL(select_rows_kernel<0>, dim3(a.batch), dim3(1024), 0, st, sa); break;
+    case 1: hipLaunchKernelGGL(select_rows_kernel<1>, dim3(a.batch), dim3(1024), 0, st, sa); break;
+    case 2: hipLaunchKernelGGL(select_rows_kernel<2>, dim3(a.batch), dim3(1024), 0, st, sa); break;
     default: return -1;
   }
   return CHECK_LAUNCH();

@@ -371,6 +371,14 @@ struct ArgmaxArgs { const float* logits; int n, batch; int* tok_ptrs[GVL_MAX_DEC
 constexpr int GVL_MAX_TOP_LOGPROBS = 8;
 int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st);
 int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
+// Per-row selection (select_rows_kernel, gvl_elem.hip): every row of one launch is greedy (on = 0) or sampled with its OWN settings, seed and stream.  A sampled row runs HF's
+// warpers in HF's order -- scores / T -> top-k -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff (0 = off each; top_p / typical_p also off at 1) -> one Gumbel-max
+// draw -- each stage's softmax over what the stage before left.  The kept set is an interval [lo, hi] of smp_key() keys after every stage.  `am` carries the rows'
+// pointers and log-probability outputs with ArgmaxArgs' meaning; its inv_temp / top_k / top_p / seed / stream fields are not read.  kept (operator tests, may be null):
+// kept[b * n + i] = 1 iff entry i of row b is finite and in the final kept set (a greedy row keeps every finite entry).
+struct SelRow { int on; float inv_temp; int top_k; float top_p, min_p, typical_p, eps, eta; unsigned seed_lo, seed_hi, stream; };
+struct SelRowsArgs { ArgmaxArgs am; SelRow row[GVL_MAX_DECODE_BATCH]; unsigned char* kept; };
+int gvl_launch_select_rows(const SelRowsArgs& a, hipStream_t st);
 // HF logits processors (repetition penalty -> no-repeat n-gram -> min length) on `batch` fp32 rows (stride ld), in place (gvl_logits.hip).  Row b's
 // history is hist[b][0 .. *len_ptrs[b]) (clamped to cap <= GVL_LOGITS_HIST_CAP; a null len_ptrs[b] = empty history); penalty 1 / ngram 0 /
 // min_new 0 switch a processor off; eos < 0 switches the min-length ban off.

@@ -64,6 +64,27 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
     am.top_n[b] = q.sel.top_n; am.lp_lists[b] = q.d_lp;
     if (q.sel.top_n > 0) { am.top_ids[b] = q.d_top_ids; am.top_lp[b] = q.d_top_lp; }
   }
+  // Sampling: a sequence follows the ctx setting unless it has its own (gvl_seq_set_sampling).  With no own setting in the group and none of the warpers past top-p in
+  // the ctx setting the launch is exactly the one below, as before; otherwise ONE launch of the per-row kernel selects for every row with that row's setting -- an own
+  // setting draws from its own (seed, stream), a follower from (ctx seed, its prefill-order stream), so a row's token does not depend on the group it travels in.
+  bool per_row = ctx->sample.warps();
+  for (int b = 0; b < am.batch; ++b) per_row = per_row || sqs[b]->sel.own_sampling;
+  if (per_row) {
+    SelRowsArgs sa; memset(&sa, 0, sizeof(sa)); sa.am = am;
+    for (int b = 0; b < am.batch; ++b) {
+      SelRow& r = sa.row[b];
+      if (sqs[b]->sel.own_sampling) {
+        const Sampling& q = sqs[b]->sel.sampling;
+        r.on = q.on; r.inv_temp = q.inv_temp; r.top_k = q.top_k; r.top_p = q.top_p; r.min_p = q.min_p; r.typical_p = q.typical_p; r.eps = q.eps; r.eta = q.eta;
+        r.seed_lo = (unsigned)q.seed; r.seed_hi = (unsigned)(q.seed >> 32); r.stream = q.stream;
+      } else {
+        const auto& q = ctx->sample;
+        r.on = q.on; r.inv_temp = q.inv_temp; r.top_k = q.top_k; r.top_p = q.top_p; r.min_p = q.min_p; r.typical_p = q.typical_p; r.eps = q.eps; r.eta = q.eta;
+        r.seed_lo = (unsigned)q.seed; r.seed_hi = (unsigned)(q.seed >> 32); r.stream = sqs[b]->rng_stream;
+      }
+    }
+    return gvl_launch_select_rows(sa, st);
+  }
   if (!ctx->sample.on) return gvl_launch_argmax(am, st);
   am.inv_temp = ctx->sample.inv_temp; am.top_p = ctx->sample.top_p; am.top_k = ctx->sample.top_k;
   am.seed_lo = (unsigned)ctx->sample.seed; am.seed_hi = (unsigned)(ctx->sample.seed >> 32);

@@ -11,10 +11,46 @@ int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, 
   if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f) || top_p > 1.f)
     return fail(ctx, GVL_ERR_ARG, "gvl_set_sampling: temperature must be > 0, top_k >= 0, 0 <= top_p <= 1");
   ctx->sample.on = true; ctx->sample.inv_temp = 1.0f / temperature; ctx->sample.top_k = top_k; ctx->sample.top_p = top_p;
+  ctx->sample.min_p = ctx->sample.typical_p = ctx->sample.eps = ctx->sample.eta = 0.f;
   // stream numbering restarts with the call (same seed + same prefill order = same draws) -- unless sequences are LIVE: a scheduler that
   // changes the sampling parameters mid-flight must not hand the stream ids of running sequences to newcomers
   if (!ctx->any_live() || seed != ctx->sample.seed) ctx->sample.next_stream = 0;
   ctx->sample.seed = seed;
+  return 0;
+}
+// a gvl_sampling as the entry point `what` takes it -> `out`; every bad value is an error with a message, never a clamp (NaN fails every range test)
+static int check_sampling(gvl_ctx* ctx, const gvl_sampling& g, const char* what, Sampling* out) {
+  Sampling q;
+  if (!g.do_sample) { *out = q; return 0; }
+  const std::string w = std::string(what) + ": ";
+  if (!(g.temperature > 0.f)) return fail(ctx, GVL_ERR_ARG, w + "temperature must be > 0");
+  if (g.top_k < 0) return fail(ctx, GVL_ERR_ARG, w + "top_k must be >= 0");
+  if (!(g.top_p >= 0.f && g.top_p <= 1.f)) return fail(ctx, GVL_ERR_ARG, w + "top_p must be in [0, 1]");
+  if (!(g.min_p >= 0.f && g.min_p <= 1.f)) return fail(ctx, GVL_ERR_ARG, w + "min_p must be in [0, 1]");
+  if (!(g.typical_p >= 0.f && g.typical_p < 1.f)) return fail(ctx, GVL_ERR_ARG, w + "typical_p must be in [0, 1) (0 = off)");
+  if (!(g.epsilon_cutoff >= 0.f && g.epsilon_cutoff < 1.f)) return fail(ctx, GVL_ERR_ARG, w + "epsilon_cutoff must be in [0, 1) (0 = off)");
+  if (!(g.eta_cutoff >= 0.f && g.eta_cutoff < 1.f)) return fail(ctx, GVL_ERR_ARG, w + "eta_cutoff must be in [0, 1) (0 = off)");
+  q.on = true; q.inv_temp = 1.0f / g.temperature; q.top_k = g.top_k; q.top_p = g.top_p; q.min_p = g.min_p; q.typical_p = g.typical_p;
+  q.eps = g.epsilon_cutoff; q.eta = g.eta_cutoff; q.seed = g.seed; q.stream = g.stream;
+  *out = q; return 0;
+}
+int gvl_set_sampling_ex(gvl_ctx* ctx, const gvl_sampling* g) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!g) return fail(ctx, GVL_ERR_ARG, "gvl_set_sampling_ex: bad arguments");
+  Sampling q;
+  if (const int rc = check_sampling(ctx, *g, "gvl_set_sampling_ex", &q)) return rc;
+  if (const int rc = gvl_set_sampling(ctx, g->do_sample, g->temperature, g->top_k, g->top_p, g->seed)) return rc;   // the stream numbering rule lives there
+  if (q.on) { ctx->sample.min_p = q.min_p; ctx->sample.typical_p = q.typical_p; ctx->sample.eps = q.eps; ctx->sample.eta = q.eta; }
+  return 0;
+}
+int gvl_seq_set_sampling(gvl_ctx* ctx, int seq_id, const gvl_sampling* g) {
+  if (!ctx) return GVL_ERR_ARG;
+  Seq* sq = ctx->lookup(seq_id);
+  if (!sq) return seq_fail(ctx, "gvl_seq_set_sampling", SEQ_BAD);
+  if (!g) { ctx->set_sampling(sq->sel, nullptr); return 0; }
+  Sampling q;
+  if (const int rc = check_sampling(ctx, *g, "gvl_seq_set_sampling", &q)) return rc;
+  ctx->set_sampling(sq->sel, &q);
   return 0;
 }
 
@@ -241,6 +277,31 @@ int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, 
   am.step_override = steps_dev;
   for (int b = 0; b < batch; ++b) am.stream[b] = streams[b];
   RUN(GVL_PROF_OTHER, 0, gvl_launch_sample(am, st));
+  return 0;
+}
+
+// per-row selection on raw rows (select_rows_kernel): row b is greedy or sampled with rows[b]; outputs as gvl_op_select_logprobs, plus the kept mask
+int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, const gvl_sampling* rows, const int32_t* steps_dev, const int* top_n,
+                       int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, uint8_t* kept_dev, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!logits || !rows || !top_n || !tokens_dev || !lp_dev || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH)
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_select_rows: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  SelRowsArgs sa; memset(&sa, 0, sizeof(sa));
+  ArgmaxArgs& am = sa.am; am.logits = logits; am.n = n; am.batch = batch; am.step_override = steps_dev; sa.kept = kept_dev;
+  for (int b = 0; b < batch; ++b) {
+    if (top_n[b] < -1 || top_n[b] > GVL_MAX_TOP_LOGPROBS || (top_n[b] > 0 && (!top_ids_dev || !top_lp_dev)))
+      return fail(ctx, GVL_ERR_ARG, "gvl_op_select_rows: top_n must be -1 .. 8 (top lists needed for > 0)");
+    Sampling q;
+    if (const int rc = check_sampling(ctx, rows[b], "gvl_op_select_rows", &q)) return rc;
+    if (q.on && !steps_dev) return fail(ctx, GVL_ERR_ARG, "gvl_op_select_rows: a sampled row needs steps_dev");
+    SelRow& r = sa.row[b];
+    r.on = q.on; r.inv_temp = q.inv_temp; r.top_k = q.top_k; r.top_p = q.top_p; r.min_p = q.min_p; r.typical_p = q.typical_p; r.eps = q.eps; r.eta = q.eta;
+    r.seed_lo = (unsigned)q.seed; r.seed_hi = (unsigned)(q.seed >> 32); r.stream = q.stream;
+    am.tok_ptrs[b] = tokens_dev + b; am.top_n[b] = top_n[b]; am.lp_lists[b] = lp_dev + b;
+    if (top_n[b] > 0) { am.top_ids[b] = top_ids_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; am.top_lp[b] = top_lp_dev + (size_t)b * GVL_MAX_TOP_LOGPROBS; }
+  }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_select_rows(sa, st));
   return 0;
 }
 

@@ -10,8 +10,16 @@ struct LogitsProc {
   bool on() const { return penalty != 1.0f || ngram > 0 || (min_new > 0 && eos >= 0); }
 };
 // The token-selection settings of one sequence as one value: gvl_seq_alloc copies the table's sel_default (gvl_set_logits_processors / gvl_set_logprobs / gvl_set_token_rules),
-// fork and clone copy the source's, the gvl_seq_set_* setters override.  top_n: -1 off, 0 the selected token's log-probability, 1 .. 8 also the top N.  rules: a rule set (-1 none), counted in its refs
-struct SeqSelect { LogitsProc proc; int top_n = -1; int rules = -1; };
+// fork and clone copy the source's (an own sampling setting included), the gvl_seq_set_* setters override.  top_n: -1 off, 0 the selected token's log-probability, 1 .. 8 also the top N.  rules: a rule set (-1 none), counted in its refs
+// Sampling of one sequence, or the table-wide setting the others follow: greedy unless `on`; then scores * inv_temp -> top-k -> top-p -> min_p -> typical_p -> epsilon -> eta
+// (0 = off each; top_p / typical_p are also off at 1) -> one draw from random stream `stream` of `seed`
+struct Sampling {
+  bool on = false; float inv_temp = 1.0f; int top_k = 0; float top_p = 0.f, min_p = 0.f, typical_p = 0.f, eps = 0.f, eta = 0.f;
+  unsigned long long seed = 0; unsigned stream = 0;
+  bool warps() const { return on && (min_p > 0.f || (typical_p > 0.f && typical_p < 1.f) || eps > 0.f || eta > 0.f); }   // uses a warper past top-p
+};
+// own_sampling: the sequence has its own `sampling` (gvl_seq_set_sampling) instead of following the table-wide setting at every selection
+struct SeqSelect { LogitsProc proc; int top_n = -1; int rules = -1; bool own_sampling = false; Sampling sampling; };
 // a token rule set: one opaque device blob (gvl_rules_create) and how many sequences / the default reference it
 struct RuleSet { bool used = false; void* d = nullptr; int refs = 0; };
 // the host state of one sequence slot; Seq (gvl_ctx.h) adds the slot's device pointers
@@ -61,6 +69,8 @@ struct SeqTable {
     if (s->sel.rules >= 0) --rule_sets[s->sel.rules].refs;
     *s = S(); return SEQ_OK;
   }
+  // `sel` (a sequence's) takes its own sampling setting; q null: back to following the table-wide setting, as a new sequence does
+  static void set_sampling(SeqSelect& sel, const Sampling* q) { sel.own_sampling = q != nullptr; sel.sampling = q ? *q : Sampling(); }
   // -1 (none) or a live rule set
   int check_rules(int id) const { return id < -1 || id >= (int)rule_sets.size() || (id >= 0 && !rule_sets[id].used) ? SEQ_NO_RULES : SEQ_OK; }
   int add_rules(void* d) {

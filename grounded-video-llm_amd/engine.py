@@ -99,6 +99,20 @@ class TowerGeometry:
         return TowerGeometry(**base)
 
 
+def _on(v) -> bool:
+    """A warper argument that switches its warper on (None / 0 = off)."""
+    return v is not None and float(v) != 0.0
+
+
+def sampling_struct(do_sample=True, temperature=1.0, top_k=50, top_p=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, seed=0,
+                    stream=0) -> "L.GvlSampling":
+    """One gvl_sampling (include/gvl.h) from generate()-style arguments: None = off; top_k 50 is HF's GenerationConfig default; typical_p 1.0 (HF's off) = 0."""
+    f = lambda v: 0.0 if v is None else float(v)
+    tp = f(typical_p)
+    return L.GvlSampling(int(bool(do_sample)), float(temperature), int(top_k or 0), f(top_p), f(min_p), 0.0 if tp == 1.0 else tp, f(epsilon_cutoff),
+                         f(eta_cutoff), int(seed) & (2 ** 64 - 1), int(stream) & 0xffffffff)
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -488,11 +502,45 @@ class Engine:
         """gvl_debug_set: result-neutral launch parameters ("decode_attn_cpb", "decode_attn_hpb", "decode_graph"); 0 = the launcher's choice."""
         self._chk(self.lib.gvl_debug_set(self.ctx, key.encode(), int(value)), "gvl_debug_set")
 
-    def set_sampling(self, do_sample, temperature=1.0, top_k=50, top_p=None, seed=0):
-        """Token selection of every later prefill / decode call: greedy argmax (do_sample False) or temperature / top-k / top-p sampling
-        on the device (HF generate's do_sample=True; `top_k` 50 is HF's GenerationConfig default, `top_p` None / 1.0 = off)."""
-        self._chk(self.lib.gvl_set_sampling(self.ctx, int(bool(do_sample)), float(temperature), int(top_k or 0),
-                                            float(top_p) if top_p is not None else 0.0, int(seed) & (2 ** 64 - 1)), "gvl_set_sampling")
+    def set_sampling(self, do_sample, temperature=1.0, top_k=50, top_p=None, seed=0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+        """Token selection of every later prefill / decode call, for the sequences without a setting of their own: greedy argmax (do_sample False) or
+        temperature / top-k / top-p sampling on the device (HF generate's do_sample=True; `top_k` 50 is HF's GenerationConfig default, `top_p` None / 1.0 =
+        off), then HF's min_p / typical_p / epsilon_cutoff / eta_cutoff warpers (None / 0 = off; typical_p 1.0 = off) -- gvl_set_sampling_ex when one is on."""
+        if not do_sample or not any(_on(v) for v in (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
+            self._chk(self.lib.gvl_set_sampling(self.ctx, int(bool(do_sample)), float(temperature), int(top_k or 0),
+                                                float(top_p) if top_p is not None else 0.0, int(seed) & (2 ** 64 - 1)), "gvl_set_sampling")
+            return
+        g = sampling_struct(True, temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed, 0)
+        self._chk(self.lib.gvl_set_sampling_ex(self.ctx, C.byref(g)), "gvl_set_sampling_ex")
+
+    def seq_set_sampling(self, seq: int, sampling: Optional[dict] = None, **kw):
+        """gvl_seq_set_sampling: one live sequence's OWN setting -- a dict / keywords of do_sample, temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff,
+        eta_cutoff, seed, stream (sampling_struct's defaults) -- from the next prefill / decode call on: the sequence is greedy or sampled by it whatever the
+        engine's setting and its neighbours in a decode group are, and its draws depend on (seed, stream, step, logits) alone.  None (and no keywords): back to
+        following the engine's setting.  Forks and clones copy it, stream included."""
+        if sampling is None and not kw:
+            self._chk(self.lib.gvl_seq_set_sampling(self.ctx, int(seq), None), "gvl_seq_set_sampling")
+            return
+        g = sampling_struct(**{**(sampling or {}), **kw})
+        self._chk(self.lib.gvl_seq_set_sampling(self.ctx, int(seq), C.byref(g)), "gvl_seq_set_sampling")
+
+    def op_select_rows(self, logits: torch.Tensor, rows, top_n=-1, steps=None, kept: bool = False):
+        """gvl_op_select_rows on fp32 rows [B, n] (B <= 16): row b is selected by rows[b] (a dict as seq_set_sampling takes it; None = greedy) at generation
+        step steps[b].  Returns op_select_logprobs' (tokens, lp, top_ids, top_lp), and with kept=True also the uint8 [B, n] mask of each row's final kept set."""
+        B, n = logits.shape
+        if len(rows) != B:
+            raise ValueError(f"op_select_rows: {len(rows)} settings for {B} rows")
+        tn = [int(x) for x in (top_n if isinstance(top_n, (list, tuple)) else [top_n] * B)]
+        arr = (L.GvlSampling * B)(*[sampling_struct(**(r or {"do_sample": False})) for r in rows])
+        toks = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        lp = torch.full((B,), float("nan"), dtype=torch.float32, device=self.device)
+        ti = torch.full((B, LPR.MAX_TOP), -2, dtype=torch.int32, device=self.device)
+        tv = torch.full((B, LPR.MAX_TOP), float("nan"), dtype=torch.float32, device=self.device)
+        km = torch.full((B, n), 255, dtype=torch.uint8, device=self.device) if kept else None
+        steps_d = torch.tensor(list(steps) if steps is not None else [0] * B, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.gvl_op_select_rows(self.ctx, _ptr(logits.contiguous()), n, B, arr, _ptr(steps_d), (C.c_int * B)(*tn), _ptr(toks), _ptr(lp),
+                                              _ptr(ti), _ptr(tv), _ptr(km), self.stream), "gvl_op_select_rows")
+        return (toks, lp, ti, tv, km) if kept else (toks, lp, ti, tv)
 
     def op_sample(self, logits, temperature, top_k, top_p, seed, streams, steps):
         """logits f32 [B, n] -> int32 [B] drawn tokens (row b: random stream streams[b], generation step steps[b])."""

@@ -45,6 +45,12 @@ class GvlRulesDesc(C.Structure):
                 ("begin_index", C.c_int32), ("n_force", C.c_int32), ("force_ids", C.POINTER(C.c_int32)), ("force_at", C.c_int32), ("bias", GvlBiasTable * 2)]
 
 
+class GvlSampling(C.Structure):
+    """gvl_sampling (include/gvl.h): one sampling setting, greedy when do_sample is 0."""
+    _fields_ = [("do_sample", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float),
+                ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("seed", C.c_uint64), ("stream", C.c_uint32)]
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "gvl_create": (C.c_int, [C.POINTER(GvlConfig), C.POINTER(C.c_void_p)]),
@@ -98,6 +104,10 @@ _SIGS = {
     "gvl_op_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "gvl_debug_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "gvl_set_sampling": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64]),
+    "gvl_set_sampling_ex": (C.c_int, [C.c_void_p, C.POINTER(GvlSampling)]),
+    "gvl_seq_set_sampling": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GvlSampling)]),
+    "gvl_op_select_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GvlSampling), C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvl_op_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvl_set_logits_processors": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int]),
     "gvl_seq_set_processors": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]),

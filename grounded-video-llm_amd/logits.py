@@ -88,12 +88,63 @@ def resolve(kw: dict, eos_id: Optional[int], embed_len: int = 0) -> Processors:
     return Processors(penalty, ngram, 0, -1)
 
 
+WARPER_KWARGS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+
+
+def resolve_sampling(kw: dict) -> dict:
+    """HF's warpers past top-p among generate()'s kwargs -> {min_p, typical_p, epsilon_cutoff, eta_cutoff}, None where a warper is off (absent, None, 0; typical_p
+    1.0), as Engine.set_sampling / seq_set_sampling take them.  Raises the ValueErrors of HF's MinP / Typical / Epsilon / Eta warpers for values outside their ranges."""
+    out = dict.fromkeys(WARPER_KWARGS)
+    v = kw.get("min_p")
+    if v is not None:
+        if not (0 <= v <= 1.0):                                              # MinPLogitsWarper.__init__
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {v}")
+        out["min_p"] = float(v) or None
+    v = kw.get("typical_p")
+    if v is not None and float(v) != 1.0:
+        v = float(v)
+        if not (v > 0 and v < 1):                                            # TypicalLogitsWarper.__init__
+            raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {v}")
+        out["typical_p"] = v
+    for name in ("epsilon_cutoff", "eta_cutoff"):
+        v = kw.get(name)
+        if v is not None and float(v) != 0.0:
+            v = float(v)
+            if v <= 0 or v >= 1:                                             # EpsilonLogitsWarper / EtaLogitsWarper.__init__
+                raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
+            out[name] = v
+    return out
+
+
+def request_sampling(do_sample=None, temperature=None, top_k=None, top_p=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, seed=None):
+    """One request's OWN sampling setting for SeqOptions.sampling: ... when every argument is None (the request follows the engine's setting), else a dict for
+    Engine.seq_set_sampling with stream 0 -- greedy for do_sample=False; otherwise sampled (do_sample None counts as True once another argument is given) with HF's
+    defaults for what is absent (temperature 1.0, top_k 50, seed 0).  Raises HF's ValueErrors."""
+    given = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, seed=seed)
+    if do_sample is None and all(v is None for v in given.values()):
+        return ...
+    warp = resolve_sampling(given)
+    if do_sample is not None and not do_sample:
+        return dict(do_sample=False)
+    t = 1.0 if temperature is None else temperature
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not t > 0:      # TemperatureLogitsWarper.__init__
+        raise ValueError(f"`temperature` (={t}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
+    k = 50 if top_k is None else top_k
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:                   # 0 = off, as GenerationConfig takes it; TopKLogitsWarper rejects the rest
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {k}")
+    if top_p is not None and not (0 <= float(top_p) <= 1.0):                     # TopPLogitsWarper.__init__
+        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+    return dict(do_sample=True, temperature=float(t), top_k=int(k), top_p=None if top_p is None else float(top_p), seed=0 if seed is None else int(seed), stream=0, **warp)
+
+
 @dataclass(frozen=True)
 class SeqOptions:
-    """One sequence's settings; per field leave what it was allocated with | off | set: processors None | OFF | a Processors; logprobs None | -1 | 0 .. 8; rules ... | None | a rules_create id"""
+    """One sequence's settings; per field leave what it was allocated with | off | set: processors None | OFF | a Processors; logprobs None | -1 | 0 .. 8; rules ... | None | a rules_create id;
+    sampling ... | None (follow the engine's setting) | a dict as Engine.seq_set_sampling takes it (the sequence's own setting)"""
     processors: Optional[Processors] = None
     logprobs: Optional[int] = None
     rules: object = ...
+    sampling: object = ...
 
 
 SeqOptions.OFF = SeqOptions(OFF, -1, None)
@@ -107,6 +158,8 @@ def apply_seq_options(eng, seq: int, opts: SeqOptions) -> None:
         eng.seq_set_logprobs(seq, opts.logprobs)
     if opts.rules is not ...:
         eng.seq_set_token_rules(seq, opts.rules)
+    if opts.sampling is not ...:
+        eng.seq_set_sampling(seq, opts.sampling)
 
 
 def read_seq_logprobs(eng, seq: int, ids, opts: SeqOptions):

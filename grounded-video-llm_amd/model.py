@@ -293,15 +293,18 @@ class LLAVA_NEXT_VIDEO:
 
     def _select_tokens(self, kw):
         """HF generate's token selection for the kwargs the reference forwards (inference.py:170-176 -> llava_next_video.py:655-661):
-        greedy, or temperature -> top-k (HF default 50) -> top-p sampling on the device; `seed` (extra) makes a run reproducible,
-        otherwise every call draws a fresh seed from torch's CPU generator (so torch.manual_seed governs it, as it does HF's)."""
+        greedy, or temperature -> top-k (HF default 50) -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff sampling on the device
+        (logits.resolve_sampling validates the last four as HF does; they are ignored without do_sample, as in HF); `seed` (extra) makes a run reproducible,
+        otherwise every call draws a fresh seed from torch's CPU generator (so torch.manual_seed governs it, as it does HF's).  Set on EVERY generate
+        call, so nothing carries over from one call to the next."""
+        LP.resolve_sampling(kw)                           # HF validates the warpers' arguments whether or not the call samples
         if not kw.get("do_sample", False) or kw.get("num_beams", 1) not in (1, None):
             # greedy -- and every kind of beam search: the steps return logits, the selection (top-2k, or the beam-sample draw) lives in beam.py
             self.engine.set_sampling(False)
             return
         t, top_p, seed = _sampling_args(kw)
         top_k = kw.get("top_k", 50)
-        self.engine.set_sampling(True, t, 0 if top_k is None else int(top_k), top_p, seed)
+        self.engine.set_sampling(True, t, 0 if top_k is None else int(top_k), top_p, seed, **{k: v for k, v in LP.resolve_sampling(kw).items() if v is not None})
 
     def _n_visual(self, samples) -> int:
         return int(samples["spatial_pixel_values"].shape[1]) * self.engine.tokens_per_seg
@@ -314,7 +317,8 @@ class LLAVA_NEXT_VIDEO:
         in HF's order (logits.py), with HF's validation errors; a rule set beyond the device capacities raises ValueError.  Still not supported
         and ignored: bad_words_ids=None, prefix_allowed_tokens_fn, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
         remove_invalid_values, exponential_decay_length_penalty, guidance_scale, diversity / constrained beams (num_beam_groups, constraints,
-        force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p.
+        force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
+        typical_p / epsilon_cutoff / eta_cutoff (those seven run on the device in HF's order; top_h, custom logits_warper lists stay ignored).
         return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
         log-probabilities; logprobs.py) instead of the list of texts."""
         if any(v == "text" for v in samples.get("video_ids", [])):
@@ -344,7 +348,7 @@ class LLAVA_NEXT_VIDEO:
                 t, top_p, seed = _sampling_args(generate_kwargs)
                 gen = torch.Generator(device=self.engine.device)
                 gen.manual_seed(seed)
-                sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen)
+                sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen, **LP.resolve_sampling(generate_kwargs))
             scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,

@@ -55,7 +55,9 @@ class ClipScheduler:
     # ---- public ------------------------------------------------------------------------------------------
     def submit(self, embeds, max_new_tokens: int, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                min_new_tokens: Optional[int] = None, logprobs: Optional[int] = None, bad_words_ids=None, sequence_bias=None, suppress_tokens=None,
-               begin_suppress_tokens=None, forced_eos_token_id=None) -> int:
+               begin_suppress_tokens=None, forced_eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
+               top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
+               epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None) -> int:
         """Queue one request.  repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors for THIS request (HF's validation;
         applied on the device to its generated ids; min_new_tokens needs the scheduler's eos id).  Requests with different settings share one
         decode group.  None for all three: the sequence keeps the engine's default (Engine.set_logits_processors).
@@ -63,7 +65,11 @@ class ClipScheduler:
         with logprobs(rid) once the request finished.
         bad_words_ids / sequence_bias / suppress_tokens / begin_suppress_tokens / forced_eos_token_id: HF's token rules for THIS request
         (logits.resolve_rules: HF's validation; forced eos at this request's max_new_tokens); its device rule set lives from admission to
-        retirement.  None for all five: the sequence keeps the engine's default (Engine.set_token_rules)."""
+        retirement.  None for all five: the sequence keeps the engine's default (Engine.set_token_rules).
+        do_sample / temperature / top_k / top_p / min_p / typical_p / epsilon_cutoff / eta_cutoff / seed: THIS request's own token selection
+        (logits.request_sampling: HF's validation and defaults; Engine.seq_set_sampling at admission, random stream 0 of `seed`): greedy next to
+        sampled neighbours, or sampled with its own warpers.  Its ids are a function of its own settings and logits alone -- not of max_active,
+        chunk, or the other requests.  None for all nine: the request follows the engine's setting (Engine.set_sampling)."""
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
@@ -75,7 +81,8 @@ class ClipScheduler:
                    begin_suppress_tokens=begin_suppress_tokens, forced_eos_token_id=forced_eos_token_id)
         if any(v is not None for v in rkw.values()):
             rules = LP.resolve_rules(rkw, self.eos, int(max_new_tokens), getattr(getattr(self.eng, "geo", None), "vocab", None))
-        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules))
+        sampling = LP.request_sampling(do_sample, temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed)
+        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling))
         self._next += 1
         self.queue.append(r)
         return r.rid

@@ -155,7 +155,7 @@ int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int seq_len, f
                 void* stream);
 int gvl_decode_greedy(gvl_ctx* ctx, int seq_id, int max_new, int eos_id, int32_t* out_ids_host,
                       int* n_out, void* stream);
-/* Token selection of every later gvl_prefill* / gvl_decode_* call on this ctx.  The reference forwards do_sample / temperature /
+/* Token selection of every later gvl_prefill* / gvl_decode_* call on this ctx, for every sequence without a sampling setting of its own (gvl_seq_set_sampling below).  The reference forwards do_sample / temperature /
  * top_p from generate(**kw) to HF generate (models/llava_next_video.py:655-661; inference.py:45-49 defaults: do_sample True,
  * temperature 0.2, top_p None; HF's GenerationConfig adds top_k 50 [ext]).  do_sample = 0: greedy argmax (the default of a new ctx).
  * do_sample = 1: scores / temperature -> top-k (0 = off; ties with the k-th score are kept) -> top-p (0 or 1 = off; a token is kept
@@ -168,6 +168,36 @@ int gvl_decode_greedy(gvl_ctx* ctx, int seq_id, int max_new, int eos_id, int32_t
  * bookkeeping over gvl_seq_clone + gvl_decode_step_logits_batch (grounded_video_llm_amd/beam.py); beam-sample (num_beams > 1, do_sample = 1) is the
  * same bookkeeping with the 2 x num_beams candidates of a step drawn on the host from the warped beam distributions (beam.py). */
 int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, float top_p, uint64_t seed);
+/* Sampling as one value, with HF's remaining warpers.  A sampled selection runs, in HF's order (transformers _get_logits_processor [ext]), each stage's softmax taken over
+ * what the stage before left, min_tokens_to_keep = 1:
+ *   scores / temperature -> top_k -> top_p                  as gvl_set_sampling (same arithmetic: with the four fields below off, the same tokens bit for bit)
+ *   min_p            MinPLogitsWarper: remove p_i < min_p * p_max
+ *   typical_p        TypicalLogitsWarper: with H the entropy and d_i = |-log p_i - H|, keep the smallest d first until their mass reaches typical_p; ties at the cut stay
+ *   epsilon_cutoff   EpsilonLogitsWarper: remove p_i < epsilon_cutoff, the largest kept score always stays
+ *   eta_cutoff       EtaLogitsWarper: remove p_i < min(eta, sqrt(eta) * exp(-H)), the largest kept score always stays
+ * then one draw from the softmax of what is left.  The kept set is an interval of scores after every stage (typical_p alone may drop the maximum).
+ * gvl_set_sampling_ex sets the ctx setting (its `stream` field is ignored: followers keep gvl_set_sampling's numbering in prefill order); with the four new fields 0 it is
+ * gvl_set_sampling.  gvl_seq_set_sampling gives ONE live sequence its own setting: from then on it is greedy or sampled by that value whatever the ctx setting is and whatever
+ * its neighbours in a decode group use, and a sampled draw is a pure function of (seed, stream, generation step, logits) -- not of what else was prefilled or decoded, nor of
+ * the group it travels in.  NULL: back to following the ctx setting at every selection (what a new sequence does).  gvl_seq_fork / gvl_seq_clone copy the source's own setting,
+ * stream included: a caller that wants distinct draws sets a different `stream` afterwards.
+ * Settings are HOST values read when a step is enqueued (or captured: step graphs are built per call, nothing is baked in across calls): a setter takes effect from the next
+ * gvl_prefill* / gvl_decode_* call and must not race one in flight on another thread.
+ * Errors (GVL_ERR_ARG with a message; nothing is clamped; NaN fails): temperature not > 0, top_k < 0, top_p or min_p outside [0, 1], typical_p / epsilon_cutoff / eta_cutoff
+ * outside [0, 1), unknown sequence.  With do_sample = 0 every other field is ignored. */
+typedef struct {
+  int32_t do_sample;          /* 0: greedy (every other field ignored) */
+  float temperature;          /* > 0 */
+  int32_t top_k;              /* 0 = off */
+  float top_p;                /* 0 or 1 = off */
+  float min_p;                /* 0 = off; in [0, 1] */
+  float typical_p;            /* 0 = off; the mass to keep, in (0, 1) */
+  float epsilon_cutoff;       /* 0 = off; in (0, 1) */
+  float eta_cutoff;           /* 0 = off; in (0, 1) */
+  uint64_t seed; uint32_t stream;
+} gvl_sampling;
+int gvl_set_sampling_ex(gvl_ctx* ctx, const gvl_sampling* sampling);
+int gvl_seq_set_sampling(gvl_ctx* ctx, int seq_id, const gvl_sampling* sampling);
 /* HF generate()'s logits processors, applied on the device to a sequence's fp32 logits row at every token selection (prefill's first
  * token, gvl_decode_greedy*, gvl_decode_steps; greedy and sampling alike), before the warpers / argmax, in HF's order:
  *   penalty != 1   RepetitionPenaltyLogitsProcessor: every DISTINCT generated id t: s[t] = s[t] < 0 ? s[t] * penalty : s[t] / penalty
@@ -408,6 +438,11 @@ int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, c
 int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, int do_sample, float temperature, int top_k, float top_p,
                            uint64_t seed, const uint32_t* streams, const int32_t* steps_dev, const int* top_n, int32_t* tokens_dev,
                            float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, void* stream);
+/* Per-row token selection on its own (operator tests): row b is greedy or sampled by rows[b] (host array of `batch` <= 16 settings, each with its own seed and stream) at
+ * generation step steps_dev[b] (device array; may be null when every row is greedy); tokens / lp / top lists as gvl_op_select_logprobs.  kept_dev (device, batch * n bytes,
+ * may be null): 1 where an entry is finite and in the row's final kept set (a greedy row keeps every finite entry), else 0. */
+int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, const gvl_sampling* rows, const int32_t* steps_dev, const int* top_n,
+                       int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, uint8_t* kept_dev, void* stream);
 /* y[b][N] = W[N,K] x[b][K] (+bias) for b < batch <= 16 -- the decode projections as ONE skinny MFMA GEMM (the weight stream is
  * read once for all sequences; K % 256 == 0).  x bf16 [batch][K], y f32 [batch][N]. */
 int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch,
