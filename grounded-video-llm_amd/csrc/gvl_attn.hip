@@ -21,6 +21,7 @@
 //   registers: K rows are read in a permuted order so that the 8 scores a lane holds per 16-key step
 //   are exactly the 8 k-slots the MFMA B operand wants -- no cross-lane movement of P at all).
 #include "gvl_internal.h"
+#include "gvl_attn_plan.h"
 #include <cstdlib>
 
 template <int D> struct KSwz;
@@ -944,38 +945,30 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_iv2_pipe_kernel(const AttnArg
       }
   }
 }
-static int launch_attn_iv2_pipe(const AttnArgs& a_in, hipStream_t st) {
-  constexpr int LDS = 2 * 2 * 64 * 96 * 2 + 64 * 96 * 2;      // the ring + the partial-last-tile V slot: 60 KB
-  static GvlDevOnce once4, once8;
-  if (gvl_set_max_lds(once4, (const void*)attn_iv2_pipe_kernel<4>, LDS) || gvl_set_max_lds(once8, (const void*)attn_iv2_pipe_kernel<8>, LDS)) return -3;
-  // a.pipe_rows == 256 (gvl_debug_set "attn_pipe_rows", tests / A-B): whole 256-row query blocks go to the 8-wave form (half the DMA pieces per MFMA), the
-  // remaining rows (S = 2049: one) to the 4-wave form in a second launch.  MEASURED SLOWER and therefore not the default: 106.5-106.8 against 95.3-95.9 ms
-  // per 39 launches, same box (profiles/r04_attention_pipe_lab.txt) -- eight waves in lock-step behind one barrier and one block per CU lose more than the
-  // halved DMA issue gives back (round 2 saw the same with 6-wave blocks).  A row's arithmetic does not depend on which form computes it (asserted).
-  const int rows8 = a_in.pipe_rows == 256 ? (a_in.S / 256) * 256 : 0;
-  const int groups8 = ((a_in.KV * a_in.B + 7) / 8) * 8;
-  if (rows8 > 0) {
-    AttnArgs a = a_in; a.q_begin = 0; a.q_rows = rows8;
-    hipLaunchKernelGGL(attn_iv2_pipe_kernel<8>, dim3((unsigned)(groups8 * (rows8 / 256))), dim3(512), LDS, st, a);
-  }
-  if (rows8 < a_in.S) {
-    AttnArgs a = a_in; a.q_begin = rows8; a.q_rows = a_in.S - rows8;
-    hipLaunchKernelGGL(attn_iv2_pipe_kernel<4>, dim3((unsigned)(groups8 * ((a.q_rows + 127) / 128))), dim3(256), LDS, st, a);
-  }
+// ---- launchers: read the knobs, plan (gvl_attn_plan.h: mode, instantiation, grid, LDS), dispatch on the planned instantiation ------------------------------
+template <class Kern>
+static int launch_planned(Kern kern, GvlDevOnce& once, const AttnArgs& a, const AttnLaunch& l, hipStream_t st) {
+  if (gvl_set_max_lds(once, (const void*)kern, l.lds)) return -3;
+  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds, st, a);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
-
-template <int D, int NWAVES, int NS, int ONES = 0, int VROW = 0, int VL = 0>
-static int launch_attn(const AttnArgs& a, hipStream_t st) {
-  constexpr int LDS = NS * 2 * 64 * D * 2 + 1024;   // ring + page-id table (256 pages)
-  static GvlDevOnce once;
-  auto kern = attn_fwd_kernel<D, NWAVES, NS, ONES, VROW, VL>;
-  if (gvl_set_max_lds(once, (const void*)kern, LDS)) return -3;
-  int nq = (a.S + NWAVES * 32 - 1) / (NWAVES * 32);
-  if (VL) { nq = 0; for (int u = 0; u < a.vl_n; ++u) nq += (a.vl_rows[u + 1] - a.vl_rows[u] + NWAVES * 32 - 1) / (NWAVES * 32); }
-  dim3 grid((unsigned)(((a.KV * a.B + 7) / 8) * 8 * (a.H / a.KV) * nq));
-  hipLaunchKernelGGL(kern, grid, dim3(NWAVES * 64), LDS, st, a);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+static int launch_attn(const AttnArgs& a, const AttnLaunch& l, hipStream_t st) {
+  switch (attn_fwd_key(l.D, l.NWAVES, l.NS, l.ONES, l.VROW, l.VL)) {
+#define GVL_CASE(D, NWAVES, NS, ONES, VROW, VL) \
+    case attn_fwd_key(D, NWAVES, NS, ONES, VROW, VL): { static GvlDevOnce once; return launch_planned(attn_fwd_kernel<D, NWAVES, NS, ONES, VROW, VL>, once, a, l, st); }
+    GVL_ATTN_FWD_LIST(GVL_CASE)
+#undef GVL_CASE
+    default: return -1;
+  }
+}
+static int launch_attn_iv2_pipe(const AttnArgs& a, const AttnLaunch& l, hipStream_t st) {
+  switch (l.NWAVES) {
+#define GVL_CASE(NW) \
+    case NW: { static GvlDevOnce once; return launch_planned(attn_iv2_pipe_kernel<NW>, once, a, l, st); }
+    GVL_ATTN_IV2_PIPE_LIST(GVL_CASE)
+#undef GVL_CASE
+    default: return -1;
+  }
 }
 
 double gvl_attn_flops(const AttnArgs& a) {
@@ -986,48 +979,32 @@ double gvl_attn_flops(const AttnArgs& a) {
 }
 
 int gvl_launch_attention(const AttnArgs& a_in, hipStream_t st) {
+  static const AttnKnobs knobs = [] {                    // LAB, A/B
+    AttnKnobs k = GVL_ATTN_KNOBS_DEFAULT;
+    if (const char* e = gvl_lab_env("GVL_ATTN_LAZY")) k.lazy = (float)atof(e);      // 0 = move the reference whenever a max grows
+    k.no_ones = gvl_lab_env("GVL_ATTN_NO_ONES") != nullptr;
+    return k;
+  }();
   AttnArgs a = a_in;
-  static const float lazy = [] { const char* e = gvl_lab_env("GVL_ATTN_LAZY"); return e ? (float)atof(e) : 8.f; }();      // A/B: 0 = move the reference whenever a max grows
-  a.lazy = lazy >= 0.f && lazy <= 64.f ? lazy : 8.f;
-  if (a.Sk < 0 || a.qpos0 < 0 || (a.Sk > 0 && (a.Sk < a.S + a.qpos0 || !a.block_table)) || (a.Sk == 0 && a.qpos0 != 0)) return -1;   // a context longer than the queries lives in pages of a block table
-  if (a.Vrows && (a.block_table || a.Sk || a.v_ld < a.KV * a.Dout || (a.v_ld & 7) || ((uintptr_t)a.Vrows & 15) || (size_t)64 * a.v_ld * 2 >= 0xffffffffull)) return -1;
-  if ((a.q_rs != nullptr) != (a.q_nw != nullptr) || (a.q_rs && (!a.Qrows || a.Krows || !a.Vrows || a.D != 96 || a.q_ld < a.H * a.Dout || (a.q_ld & 7) || (((uintptr_t)a.Qrows | (uintptr_t)a.q_nw) & 15)))) return -1;
-  if ((!a.q_rs && (a.Krows != nullptr) != (a.Qrows != nullptr)) || (a.Krows && (!a.Vrows || a.D != 64 || a.Dout != a.D || a.k_ld < a.KV * a.D || a.q_ld < a.H * a.D || ((a.k_ld | a.q_ld) & 7) ||
-                                                              (((uintptr_t)a.Krows | (uintptr_t)a.Qrows) & 15) || (size_t)64 * a.k_ld * 2 >= 0xffffffffull))) return -1;
-  if (a.B <= 0 || a.S <= 0 || a.S > 256 * 64 || a.Sk > 256 * 64 || a.H % a.KV != 0 || a.Dout > a.D || (a.Dout & 7) || ((uintptr_t)a.O & 15)) return -1;   // 16-byte O stores
-  const int ring = a.ring == 3 && !a.Vrows ? 3 : 2;
-  if (a.vl_n) {                                                  // ragged causal prefill: one grid for all sequences of the group
-    if (a.vl_n < 1 || a.vl_n > GVL_MAX_PREFILL_BATCH || a.B != 1 || !a.causal || a.Sk || a.qpos0 || a.Vrows || a.Qrows || a.Krows || a.q_rs || a.block_table) return -1;
-    for (int u = 0; u < a.vl_n; ++u) if (!a.vl_tables[u] || a.vl_rows[u + 1] <= a.vl_rows[u] || a.vl_rows[u + 1] - a.vl_rows[u] > a.S) return -1;
-    switch (a.D) {
-      case 64: return launch_attn<64, 4, 2, 0, 0, 1>(a, st);
-      case 96: return launch_attn<96, 4, 2, 0, 0, 1>(a, st);
-      case 128: return launch_attn<128, 4, 2, 0, 0, 1>(a, st);
-      default: return -1;
-    }
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  AttnGeometry g{};
+  g.B = a.B; g.H = a.H; g.KV = a.KV; g.S = a.S; g.D = a.D; g.Dout = a.Dout; g.Sk = a.Sk; g.qpos0 = a.qpos0; g.causal = a.causal; g.ones_row = a.ones_row; g.k_ones = a.k_ones;
+  g.ring = a.ring; g.pipe = a.pipe; g.pipe_rows = a.pipe_rows; g.v_ld = a.v_ld; g.q_ld = a.q_ld; g.k_ld = a.k_ld; g.max_pages = a.max_pages; g.vl_n = a.vl_n;
+  for (int u = 0; u <= GVL_MAX_PREFILL_BATCH; ++u) g.vl_rows[u] = a.vl_rows[u];
+  for (int u = 0; u < GVL_MAX_PREFILL_BATCH; ++u) g.vl_tables[u] = a.vl_tables[u] != nullptr;
+  g.block_table = a.block_table; g.Vrows = a.Vrows; g.Qrows = a.Qrows; g.Krows = a.Krows; g.q_rs = a.q_rs; g.q_nw = a.q_nw;
+  g.O16 = al16(a.O); g.Vrows16 = al16(a.Vrows); g.Qrows16 = al16(a.Qrows); g.Krows16 = al16(a.Krows); g.q_nw16 = al16(a.q_nw);
+  AttnLaunch plan[GVL_ATTN_MAX_LAUNCHES];
+  const int n = attn_plan(g, knobs, plan);
+  if (n < 0) return -1;
+  for (int i = 0; i < n; ++i) {
+    const AttnLaunch& l = plan[i];
+    a.lazy = l.lazy;
+    if (l.family == GVL_ATTN_IV2_PIPE) { a.q_begin = l.q_begin; a.q_rows = l.q_rows; }
+    const int rc = l.family == GVL_ATTN_IV2_PIPE ? launch_attn_iv2_pipe(a, l, st) : launch_attn(a, l, st);
+    if (rc) return rc;
   }
-  switch (a.D) {
-    // ring depth 2: 48 KB (D=96) -> 3 blocks / CU at 151 VGPRs (measured 427 us vs 461 us for the 73 KB depth-3 ring, which
-    // caps residency at 2 blocks / CU; DMA latency is not the limiter -- PMC shows the kernel is VALU-issue-bound)
-    case 64: return a.Krows ? launch_attn<64, 4, 2, 0, 2>(a, st) : a.Vrows ? launch_attn<64, 4, 2, 0, 1>(a, st) : launch_attn<64, 4, 2>(a, st);
-    case 96: {
-      static const bool no_ones = gvl_lab_env("GVL_ATTN_NO_ONES") != nullptr;                       // A/B
-      // (192-query blocks of 6 waves -- 3 % instead of 5.9 % tail waste at S = 2049, K/V tiles shared by more waves -- measured 24.6 ms
-      //  of attention per clip against 18.0: two 98 KB blocks per CU hide less latency than three 49 KB ones.  Round 2, dropped.)
-      const int lr = a.Dout - 64;
-      const bool ones = a.ones_row && !no_ones && a.Dout < 96 && lr >= 0 && (lr & 7) < 4 && !a.causal;
-      if (a.Vrows && a.q_rs) {
-        if (a.Dout != 88 || !a.k_ones) return -1;
-        if (ones && a.pipe && a.H == a.KV) return launch_attn_iv2_pipe(a, st);      // hand-placed pipelined loop (round 4); bit-identical to the kernel below
-        return ones ? launch_attn<96, 4, 2, 1, 3>(a, st) : launch_attn<96, 4, 2, 0, 3>(a, st);
-      }
-      if (a.Vrows) return ones ? launch_attn<96, 4, 2, 1, 1>(a, st) : launch_attn<96, 4, 2, 0, 1>(a, st);
-      if (!ones && ring == 3) return launch_attn<96, 4, 3>(a, st);
-      return ones ? launch_attn<96, 4, 2, 1>(a, st) : launch_attn<96, 4, 2>(a, st);
-    }
-    case 128: return a.Vrows ? -1 : (ring == 3 ? launch_attn<128, 4, 3>(a, st) : launch_attn<128, 4, 2>(a, st));     // row-major V is the vision towers' mode (head dims 64 and 88)
-    default: return -1;
-  }
+  return 0;
 }
 
 // =====================================================================================================
@@ -1511,48 +1488,29 @@ __global__ __launch_bounds__(256, 2) void decode_attn_gqa_kernel(const DecodeAtt
   if (tid == 0) __hip_atomic_store(counters_b + head0, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int D>
-static int launch_decode_g(const DecodeAttnArgs& a, hipStream_t st) {
-  static const bool no_gqa = gvl_lab_env("GVL_DECODE_ATTN_NOGQA") != nullptr;      // A/B: the round-1 grid for GQA models
-  const int G = a.H / a.KV;
-  static const bool gqa_valu = gvl_lab_env("GVL_DECODE_ATTN_GQA_VALU") != nullptr;  // A/B: the per-head VALU kernel on the XCD-aware grid
-  if (G > 1 && G <= 16 && !no_gqa && !gqa_valu && D % 32 == 0) {
-    DecodeAttnArgs b = a;
-    if (b.hpb < 1 || b.hpb > G || G % b.hpb) b.hpb = G;
-    const int units = (b.H / b.hpb) * b.gsplit * b.batch;
-    static const bool direct_env = gvl_lab_env("GVL_DECODE_ATTN_GQA_DIRECT") != nullptr;   // A/B: operands straight from global memory
-    const bool direct = direct_env || (D & (D - 1)) != 0;                            // the staged tiles need power-of-two rows (64 / 128)
-    if (direct) {
-      if (b.hpb <= 4) hipLaunchKernelGGL((decode_attn_gqa_kernel<D, 4, 0>), dim3(units), dim3(256), 0, st, b);
-      else hipLaunchKernelGGL((decode_attn_gqa_kernel<D, 16, 0>), dim3(units), dim3(256), 0, st, b);
-    } else {
-      if (b.hpb <= 4) hipLaunchKernelGGL((decode_attn_gqa_kernel<D, 4, 1>), dim3(units), dim3(256), 0, st, b);
-      else hipLaunchKernelGGL((decode_attn_gqa_kernel<D, 16, 1>), dim3(units), dim3(256), 0, st, b);
+// read the knobs, plan (gvl_attn_plan.h: normalised batch / cpb / gsplit / hpb, instantiation, grid), dispatch on the planned instantiation
+int gvl_launch_decode_attention(const DecodeAttnArgs& a_in, hipStream_t st) {
+  static const DecodeAttnKnobs knobs{gvl_lab_env("GVL_DECODE_ATTN_NOGQA") != nullptr, gvl_lab_env("GVL_DECODE_ATTN_GQA_VALU") != nullptr,
+                                     gvl_lab_env("GVL_DECODE_ATTN_GQA_DIRECT") != nullptr};      // LAB, A/B
+  DecodeAttnLaunch l;
+  if (decode_attn_plan(DecodeAttnGeometry{a_in.H, a_in.KV, a_in.D, a_in.nsplit, a_in.batch, a_in.hpb, a_in.cpb, a_in.gsplit}, knobs, &l) < 0) return -1;
+  DecodeAttnArgs a = a_in;
+  a.batch = l.batch; a.cpb = l.cpb; a.gsplit = l.gsplit; a.hpb = l.hpb;
+  const dim3 grid(l.grid_x, l.grid_y, l.grid_z);
+  if (l.family == GVL_DECODE_ATTN_GQA) {
+    switch (decode_attn_key(l.D, l.t1, l.t2)) {
+#define GVL_CASE(D, GM, STG) case decode_attn_key(D, GM, STG): hipLaunchKernelGGL((decode_attn_gqa_kernel<D, GM, STG>), grid, dim3(256), 0, st, a); break;
+      GVL_DECODE_ATTN_GQA_LIST(GVL_CASE)
+#undef GVL_CASE
+      default: return -1;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-  }
-  if (G == 1 || no_gqa) {
-    if (G == 1) hipLaunchKernelGGL((decode_attn_kernel<D, 1, 0>), dim3(a.H, a.gsplit, a.batch), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((decode_attn_kernel<D, 1, 2>), dim3(a.H, a.gsplit, a.batch), dim3(256), 0, st, a);
   } else {
-    const int units = a.KV * a.gsplit * a.batch;
-    hipLaunchKernelGGL((decode_attn_kernel<D, 1, 1>), dim3(8, (units + 7) / 8 * G), dim3(256), 0, st, a);
+    switch (decode_attn_key(l.D, l.t1, 0)) {
+#define GVL_CASE(D, PH) case decode_attn_key(D, PH, 0): hipLaunchKernelGGL((decode_attn_kernel<D, 1, PH>), grid, dim3(256), 0, st, a); break;
+      GVL_DECODE_ATTN_HEAD_LIST(GVL_CASE)
+#undef GVL_CASE
+      default: return -1;
+    }
   }
   return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-int gvl_launch_decode_attention(const DecodeAttnArgs& a_in, hipStream_t st) {
-  DecodeAttnArgs a = a_in;
-  if (a.batch <= 0) a.batch = 1;
-  if (a.batch > GVL_MAX_DECODE_BATCH) return -1;
-  if (a.H % a.KV) return -1;
-  if (a.cpb < 1) a.cpb = 1;
-  if (a.nsplit < 1 || a.nsplit > 16) return -1;      // the merge buffers hold 16 partial records
-  if (a.gsplit <= 0 || a.gsplit > a.nsplit) a.gsplit = (a.nsplit + a.cpb - 1) / a.cpb;
-  switch (a.D) {
-    case 64: return launch_decode_g<64>(a, st);
-    case 96: return launch_decode_g<96>(a, st);
-    case 128: return launch_decode_g<128>(a, st);
-    default: return -1;
-  }
 }

@@ -22,11 +22,9 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 
 #define GVL_KV_PAGE 64          // tokens per KV page == key tile of the attention kernels
-constexpr int GVL_MAX_DECODE_BATCH = 16;  // sequences decoded together: the weight stream is read ONCE for all of them;
-                                          // = the 16 columns of the MFMA B operand of the skinny decode GEMM (gvl_decode.hip)
+#include "gvl_limits.h"       // GVL_MAX_DECODE_BATCH, GVL_MAX_PREFILL_BATCH (shared with the host-only launch plans)
 constexpr int GVL_MAX_VALU_BATCH = 4;     // the round-1 VALU GEMV (fallback for K % 256 != 0 geometries) holds B vectors in LDS: 1, 2 or 4
 constexpr int GVL_GEMM_ROT_LEN = 64;     // GemmArgs.rot entries (a power of two; longer walks repeat the table)
-constexpr int GVL_MAX_PREFILL_BATCH = 8;  // most sequences whose rows share one pass of the prefill GEMMs (gvl_debug_set prefill_group picks 1 .. 8; default 4)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a host may hold one gvl_ctx per device in ONE process
 // (include/gvl.h allows it), so "set once" means once per device ordinal -- a process-global flag would leave the second device at the
@@ -220,7 +218,7 @@ struct AttnArgs {
   int vl_rows[GVL_MAX_PREFILL_BATCH + 1];
   const int* vl_tables[GVL_MAX_PREFILL_BATCH];
 };
-int gvl_launch_attention(const AttnArgs& a, hipStream_t st);
+int gvl_launch_attention(const AttnArgs& a, hipStream_t st);   // attn_plan (gvl_attn_plan.h: operand mode, instantiation, grid, LDS) + dispatch on the planned instantiation
 double gvl_attn_flops(const AttnArgs& a);
 
 // ---- decode attention -----------------------------------------------------------------------------
@@ -239,7 +237,7 @@ struct DecodeAttnArgs {
   int gsplit;             // block slots along the context actually launched (0 = ceil(nsplit / cpb)): the host may pass min(nsplit, ceil(longest context in pages / 4)) -- a
                           // sequence uses ceil(its pages / 4) splits whatever the grid offers, so this only trims blocks that would leave at once
 };
-int gvl_launch_decode_attention(const DecodeAttnArgs& a, hipStream_t st);
+int gvl_launch_decode_attention(const DecodeAttnArgs& a, hipStream_t st);   // decode_attn_plan (gvl_attn_plan.h: normalised batch / cpb / gsplit / hpb, instantiation, grid) + dispatch
 
 // ---- elementwise / norm / glue kernels (gvl_elem.hip) ----------------------------------------------
 int gvl_launch_layernorm_f32(const float* x, const float* w, const float* b, bf16_t* y, int rows, int cols, float eps, hipStream_t st);

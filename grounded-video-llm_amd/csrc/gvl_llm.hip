@@ -3,6 +3,7 @@
 //   LLM             models/modeling_phi3.py:1034-1095,1249-1383,1512-1526 / models/modeling_llama.py:699-760
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
+#include "gvl_attn_plan.h"
 
 namespace gvlm {
 
@@ -282,32 +283,15 @@ int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st) {
   if (fused_norm) RUN(GVL_PROF_OTHER, 0, gvl_launch_gather_tok_rows(ctx->l_embed, tp, ctx->d_x, Hd, st));
   else RUN(GVL_PROF_OTHER, 0, gvl_launch_embed_norm(ctx->l_embed, tp, ctx->d_x, ctx->d_xn, ctx->ll[0].ln1, Hd, f.rms_eps, st));
   double ctx_tokens = 0; for (int b = 0; b < B; ++b) ctx_tokens += sqs[b]->pos + 1;
-  // Decode-attention launch shape.  A sequence always uses one context split per 4 pages of ITS OWN length and one partial per split
-  // (its arithmetic never depends on the batch); how many block slots the grid offers (gsplit) and how many consecutive splits one
-  // block works through (cpb) are free.  cpb stays 1: letting a block amortise its publish -> ticket tail over 8 / 16 pages was
-  // measured neutral to slower (Phi-3.5, 3.5 k context, 16 sequences: 2631 tok/s at cpb 1, 2613 at 2, 2574 at 4; one sequence:
-  // 455 / 445 / 408) -- at 5.5 TB/s over pages scattered through a 244 GB pool the page reads, not the tail, are the limit.
-  // gvl_debug_set("decode_attn_cpb") overrides (tests).  Under stream capture the shape must stay valid for later steps: every slot.
-  int gsplit = ctx->nsplit, cpb = 1, hpb = 0;
+  // Decode-attention launch shape (decode_attn_shape, gvl_attn_plan.h): block slots along the context, splits and heads per block -- from the sequences' positions and
+  // the gvl_debug_set overrides; under stream capture the shape that stays valid for later steps
+  int gsplit, cpb, hpb;
   { hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (st == nullptr || hipStreamIsCapturing(st, &cs) != hipSuccess || cs == hipStreamCaptureStatusNone) {
-      int nsb[GVL_MAX_DECODE_BATCH];
-      for (int b = 0; b < B; ++b) { const int np = (sqs[b]->pos + 1 + 63) >> 6; const int n = (np + 3) >> 2; nsb[b] = n < 1 ? 1 : (n > ctx->nsplit ? ctx->nsplit : n); }
-      const int force_cpb = ctx->dbg.decode_attn_cpb;          // gvl_debug_set: tests vary this result-neutral launch parameter
-      if (force_cpb >= 1 && force_cpb <= 16) cpb = force_cpb;
-      gsplit = 1; for (int b = 0; b < B; ++b) { const int g = (nsb[b] + cpb - 1) / cpb; gsplit = g > gsplit ? g : gsplit; }
-      // grouped-query models: the whole group per block when that still gives >= ~1.5 blocks per CU, else fewer heads per block
-      // (measured, Llama-3-8B at 3.5 k context: one sequence 268 / 278 / 273 tok/s at 4 / 2 / 1 heads per block, two sequences 520 / 525)
-      const int G = H / KV;
-      if (G > 1) {
-        long splits = 0; for (int b = 0; b < B; ++b) splits += (nsb[b] + cpb - 1) / cpb;
-        hpb = G;
-        while (hpb > 2 && hpb % 2 == 0 && (long)(H / hpb) * splits < 400) hpb >>= 1;
-        if (hpb == 2 && (long)(H / 2) * splits < 200) hpb = 1;
-        const int fh = ctx->dbg.decode_attn_hpb;                 // gvl_debug_set
-        if (fh >= 1 && G % fh == 0) hpb = fh;
-      }
-    } }
+    const bool capturing = st != nullptr && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    int positions[GVL_MAX_DECODE_BATCH];
+    for (int b = 0; b < B; ++b) positions[b] = sqs[b]->pos;
+    const DecodeAttnShape s = decode_attn_shape(positions, B, H, KV, ctx->nsplit, ctx->dbg.decode_attn_cpb, ctx->dbg.decode_attn_hpb, capturing);
+    gsplit = s.gsplit; cpb = s.cpb; hpb = s.hpb; }
   auto proj = [&](GemvArgs& g, const float* wscale) {
     if (!mfma) return gvl_launch_gemv(g, st);
     if (ctx->fp8) { g.w_fp8 = ctx->fp8; g.wscale = wscale; }

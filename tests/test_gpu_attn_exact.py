@@ -27,6 +27,7 @@ pytestmark = pytest.mark.gpu
 from gpu_util import DEV, bf, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, lib as L  # noqa: E402
 import attn_ref as R  # noqa: E402
+import attn_plan as A  # noqa: E402
 
 GUARD = 160
 NAN_ROWS = 64
@@ -66,15 +67,27 @@ def run(eng, c, S=None):
 
 
 def forms(c):
-    """(label, vision_in_place, attn_ring) of every form the operator reaches for this case"""
+    """(label, vision_in_place, attn_ring) of every form the operator reaches for this case.  What each setting claims -- its operand mode, and ring depth 3 wherever
+    a depth-3 kernel exists (paged operands, head dim > 64) -- is asserted against the library's own plan for gvl_op_attention's launch (tests/attn_plan.py), and the
+    label names the instantiation that plan gives"""
     paged_only = c.causal or c.Dr > 96
     out = []
     for vip in ((1,) if paged_only else (1, 0, 2)):
-        paged = paged_only or vip == 0
-        for ring in ((0, 2, 3) if paged else (0,)):
-            kind = "pages" if paged else ("q,k,v in place" if vip == 1 and c.Dr == 64 else "v in place")
-            out.append((f"vision_in_place {vip} attn_ring {ring} ({kind})", vip, ring))
+        mode = A.PAGED if paged_only or vip == 0 else (A.QKV_ROWS if vip == 1 and c.Dr == 64 else A.V_ROWS)
+        for ring in ((0, 2, 3) if mode == A.PAGED else (0,)):
+            (l,) = A.op_attention(c.B, c.S, c.H, c.KV, c.Dr, int(c.causal), vip, ring)
+            assert l.family == A.FWD and l.mode == mode and l.NS == (3 if ring == 3 and l.D > 64 else 2) and l.ONES == 0, f"{c} vision_in_place {vip} attn_ring {ring}: the plan is {l}"
+            out.append((f"vision_in_place {vip} attn_ring {ring} ({A.MODE_NAMES[l.mode]}: attn_fwd_kernel<{l.D}, {l.NWAVES}, {l.NS}, {l.ONES}, {l.VROW}, {l.VL}>)", vip, ring))
     return out
+
+
+def kernels(c):
+    return {A.kernel_of(A.op_attention(c.B, c.S, c.H, c.KV, c.Dr, int(c.causal), vip, ring)[0]) for _, vip, ring in forms(c)}
+
+
+# every attn_fwd_kernel instantiation that gvl_op_attention can reach (it sets neither ones_row nor a ragged group): (D, NWAVES, NS, ONES, VROW, VL)
+REACHABLE = {0: {("fwd", 64, 4, 2, 0, v, 0) for v in (0, 1, 2)} | {("fwd", 96, 4, 2, 0, v, 0) for v in (0, 1)} | {("fwd", 96, 4, 3, 0, 0, 0), ("fwd", 128, 4, 2, 0, 0, 0), ("fwd", 128, 4, 3, 0, 0, 0)},
+             1: {("fwd", 64, 4, 2, 0, 0, 0)} | {("fwd", D, 4, ns, 0, 0, 0) for D in (96, 128) for ns in (2, 3)}}
 
 
 def for_every_form(eng, c, judge):
@@ -108,9 +121,10 @@ def pairs(maps):
 
 def exact_sweep(eng, causal):
     maps = R.CAUSAL_MAPS if causal else R.FULL_MAPS
-    n = 0
+    n, reached = 0, set()
     for B, S, H, KV, Dr, target in pairs(maps):
         c = R.onehot_case(B, S, H, KV, Dr, causal, target, seed=S + Dr + B, device=DEV)
+        reached |= kernels(c)
 
         def judge(label, out, c=c):
             msg = R.onehot_mismatch(out, c, f"{c} [{label}]")
@@ -118,6 +132,7 @@ def exact_sweep(eng, causal):
 
         for_every_form(eng, c, judge)
         n += len(forms(c))
+    assert reached == REACHABLE[causal], f"the sweep misses {sorted(REACHABLE[causal] - reached)} / reaches unexpected {sorted(reached - REACHABLE[causal])}"
     print(f"[parity] attention one-hot causal{causal}: {len(pairs(maps))} cases, {n} launches, every one bit for bit")
 
 

@@ -18,6 +18,7 @@ import gvl_oracle as O  # noqa: E402
 from conftest import load_golden  # noqa: E402
 from gpu_util import DEV, bf, check, check_bf16_class, llm_engine, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, synth  # noqa: E402
+import attn_plan as A  # noqa: E402
 
 
 def _ocfg(geo):
@@ -663,6 +664,15 @@ def test_decode_attention_result_is_independent_of_the_launch_shape(kind):
 
     ref_ids, ref_lg = run()
     shapes = [(cpb, None) for cpb in (1, 2, 3, 4, 16)] + ([(1, 1), (1, 2), (1, 4), (4, 2)] if kind == "gqa" else [])
+    # What reaches the kernel, from the library's own plan for the decode step (tests/attn_plan.py) at the prompts' positions: an eager step launches the forced cpb / hpb
+    # with ceil(16 / cpb) block slots (the 4090-token context uses all 16 splits); a step recorded into a graph takes the shape that stays valid for later steps whatever
+    # is forced -- there (graph 1: decode_greedy_batch) the overrides reach only the eager decode_step_logits calls
+    pos, dims = tuple(e.shape[0] for e in embs), (c["heads"], c["kv_heads"], c["hidden"] // c["heads"])
+    for cpb, hpb in shapes:
+        shp, l = A.decode_step(pos, *dims, cpb, hpb or 0)
+        assert (l.cpb, l.gsplit, l.batch) == (cpb, -(-16 // cpb), 3) and (hpb is None or l.hpb == hpb), f"cpb {cpb} hpb {hpb}: the plan is {l}"
+        assert A.kernel_of(l) == (("gqa", 64, 4, 1) if kind == "gqa" else ("head", 64, 0)), l
+        assert A.decode_step(pos, *dims, cpb, hpb or 0, capturing=True) == A.decode_step(pos, *dims, capturing=True)
     for graph in (1, 0):                            # replayed (default) and eager decode steps
         eng.debug_set("decode_graph", graph)
         for cpb, hpb in shapes:
@@ -742,14 +752,31 @@ def test_grouped_query_decode_attention_other_group_sizes(heads, kv_heads, head_
     O.llm_forward(ocfg, W, x, False, cache32, 0, last_only=True)
     e = W["model.embed_tokens.weight"].to(bf).float()
     n = x.shape[0]
+    # the kernels, from the library's own plan for the decode step (tests/attn_plan.py): the steps recorded into a graph (generate_ids, decode_greedy_batch below) serve the
+    # whole group per block -- groups of 8 on the 16-row variant; an eager step of ONE sequence (decode_step_logits) takes fewer heads per block, unless the group is odd
+    G, Dp = heads // kv_heads, A.pad_head(head_dim)
+    eager, replay = A.decode_step((300,), heads, kv_heads, head_dim)[1], A.decode_step((300,), heads, kv_heads, head_dim, capturing=True)[1]
+    whole = A.decode_step((300,), heads, kv_heads, head_dim, force_hpb=G)[1]
+    assert A.kernel_of(replay) == A.kernel_of(whole) == ("gqa", Dp, 16 if G > 4 else 4, 1) and replay.hpb == whole.hpb == G and replay.gsplit == 16 and eager.gsplit == 2
+    assert A.kernel_of(eager) == ("gqa", Dp, 4, 1) and eager.hpb == (G if G % 2 else 1)
+    eager_lg = []
     for step in range(6):
         tok = 7 + 3 * step
         lg = eng.decode_step_logits(seq, tok)
+        eager_lg.append(lg.clone())
         ref = O.llm_forward(ocfg, W, e[tok][None], True, cache, n, last_only=True)[0]
         ref32 = O.llm_forward(ocfg, W, e[tok][None], False, cache32, n, last_only=True)[0]
         n += 1
         check_bf16_class(lg, ref32, ref, 1e-2, f"GQA {heads}/{kv_heads} x {head_dim}: decode step {step} vs fp32 oracle")
     eng.seq_free(seq)
+    if A.kernel_of(whole) != A.kernel_of(eager):       # groups of 8: the steps above ran the 4-row variant -- the same steps on the 16-row one (the whole group per block), bit for bit
+        eng.debug_set("decode_attn_hpb", G)
+        seq = eng.seq_alloc(320)
+        eng.prefill(seq, x.to(DEV).to(bf))
+        for step in range(6):
+            assert torch.equal(eng.decode_step_logits(seq, 7 + 3 * step), eager_lg[step]), f"GQA {heads}/{kv_heads} x {head_dim}: step {step} on the 16-row variant differs"
+        eng.seq_free(seq)
+        eng.debug_set("decode_attn_hpb", 0)
     xs = [x[:n_].to(DEV).to(bf) for n_ in (300, 65, 130)]
     single = [eng.generate_ids(xx, 8, None) for xx in xs]
     seqs = [eng.seq_alloc(xx.shape[0] + 9) for xx in xs]

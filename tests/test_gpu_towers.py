@@ -13,6 +13,14 @@ import gvl_oracle as O  # noqa: E402
 from conftest import load_golden  # noqa: E402
 from gpu_util import DEV, bf, check, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, weights as Wt, synth  # noqa: E402
+import attn_plan as A  # noqa: E402
+
+FWD_IV2 = ("fwd", 96, 4, 2, 1, 3, 0)        # attn_fwd_kernel on q normalised on load, V in place, ones-row sum: what attn_iv2_pipe_kernel must equal
+
+
+def iv2_attn_kernels(c, n, **dbg):
+    """the kernels one InternVideo2 block's attention runs for n segments of the tower c under the gvl_debug_set values dbg, from the library's own plan"""
+    return [A.kernel_of(l) for l in A.iv2_block(n, c["frames"] * (c["image"] // 14) ** 2 + 1, c["heads"], c["dim"] // c["heads"], **dbg)]
 
 
 def _clip_engine(c, seed):
@@ -78,6 +86,10 @@ def test_iv2(name, tol_g, tol_o):
     # 1 (default, `got`) = q in place too, normalised, scaled and rounded ONCE in the attention prologue with the softmax shift folded into
     # the S^T MFMAs: a different (not larger) set of rounding points, held to the same goldens above and to path 0 within bf16 noise
     eng.debug_set("attn_pipe", 0)              # the plain tile loop (attn_fwd_kernel) instead of the pipelined one: bit-identical
+    if c["dim"] // c["heads"] == 88:
+        assert iv2_attn_kernels(c, px.shape[0], attn_pipe=1) == [("iv2_pipe", 4)] and iv2_attn_kernels(c, px.shape[0], attn_pipe=0) == [FWD_IV2]
+    else:                                      # other head dims have no pipelined form: the switch changes nothing
+        assert iv2_attn_kernels(c, px.shape[0], attn_pipe=1) == iv2_attn_kernels(c, px.shape[0], attn_pipe=0) == [("fwd", 64, 4, 2, 0, 1, 0)]
     assert torch.equal(eng.iv2_encode(px.to(DEV)), got)
     eng.debug_set("attn_pipe", 1)
     # round 5: `got` ran with the RMSNorms fused into the GEMMs around them (row statistics from the producing epilogue, norm weight folded into the
@@ -165,6 +177,8 @@ def test_iv2_pipelined_attention_against_the_plain_kernel(image, frames, sharp):
     eng.finalize()
     px = synth.det_tensor(seed + ".px", (3, 3, frames, image, image))
     S = frames * (image // 14) ** 2 + 1
+    # which kernel each setting below runs, from the library's own plan: the default and attn_pipe 2 the 4-wave pipelined kernel, attn_pipe 0 attn_fwd_kernel
+    assert iv2_attn_kernels(c, 3) == iv2_attn_kernels(c, 3, attn_pipe=2) == [("iv2_pipe", 4)] and iv2_attn_kernels(c, 3, attn_pipe=0) == [FWD_IV2]
     got = eng.iv2_encode(px.to(DEV))
     eng.debug_set("attn_pipe", 0)
     plain = eng.iv2_encode(px.to(DEV))
@@ -180,6 +194,9 @@ def test_iv2_pipelined_attention_against_the_plain_kernel(image, frames, sharp):
     assert torch.equal(got, again), f"S = {S}, sharp x{sharp}: the pipelined kernel is not reproducible ({int((got != again).sum())} values differ between two runs)"
     # opt-in: whole 256-row query blocks on the 8-wave form of the kernel (half the DMA pieces per MFMA; measured slower), the rest on the 4-wave form;
     # a row's arithmetic does not depend on the form
+    # (the plan: S < 256 has no whole 256-row block, the 8-wave form does not run there and `eight` repeats `got`'s launch; S = 256 and 512 run it alone)
+    l8 = A.iv2_block(3, S, c["heads"], 88, attn_pipe_rows=256)
+    assert [(A.kernel_of(l), l.q_begin, l.q_rows) for l in l8] == [x for x in ((("iv2_pipe", 8), 0, S // 256 * 256), (("iv2_pipe", 4), S // 256 * 256, S % 256)) if x[2]]
     eng.debug_set("attn_pipe_rows", 256)
     eight = eng.iv2_encode(px.to(DEV))
     eng.debug_set("attn_pipe_rows", 128)
