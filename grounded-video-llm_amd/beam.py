@@ -105,7 +105,8 @@ def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[
 
 def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logits: torch.Tensor, num_beams: int, max_new_tokens: int,
                 eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None,
-                process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None, with_scores: bool = False):
+                process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None, with_scores: bool = False,
+                candidates: Optional[Callable[[torch.Tensor, torch.Tensor], Tuple[Sequence[float], Sequence[int], Sequence[float]]]] = None):
     """first_logits [vocab]: logits after the prompt.  step(parents, tokens) -> logits [k, vocab] of the k new running beams, where new beam j
     continues old beam parents[j] with tokens[j] (the caller reorders its KV cache accordingly; at the first call every parent is 0 = the
     prompt).  Returns the NEW ids of the best hypothesis (eos included when it ended by eos), as HF does for inputs_embeds prompts.
@@ -116,7 +117,10 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     with_scores: return (ids, sequences_score, transition_scores) instead -- HF's definitions: sequences_score = the hypothesis score (sum of the
     processed log-probabilities / generated_len ** length_penalty), transition_scores = compute_transition_scores(seq, scores, beam_indices,
     normalize_logits=False), i.e. per new id the processed (beam-sample: warped) log-probability it had in the row of the beam it extended, before
-    the beam score was added -- tracked per running beam through the parent chain."""
+    the beam score was added -- tracked per running beam through the parent chain.
+    candidates (beam search only): a callable (processed rows [k, vocab], beam scores [k]) -> (vals, idxs, proc_vals), the step's 2k candidates best first -- value
+    (processed log-probability + beam score), flat index beam * vocab + token, the processed log-probability alone.  It replaces the torch top-2k below and the
+    gather of the transition scores: Engine.op_beam_candidates (the library's own kernels) plugs in here, and tests record every step's list through it."""
     k = int(num_beams)
     if k < 2:
         raise ValueError("beam_search needs num_beams >= 2")
@@ -138,7 +142,10 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
         if process is not None:
             lp = process([list(q) for q in seqs], lp)
         proc = lp                                        # (beam-sample: warped below) the rows HF reports as `scores`
-        if sample is None:
+        hooked = None
+        if sample is None and candidates is not None:
+            vals, idxs, hooked = (list(x) for x in candidates(lp, scores))
+        elif sample is None:
             lp = lp + scores[:, None]
             top = torch.topk(lp.reshape(-1), 2 * k, largest=True, sorted=True)
             vals, idxs = top.values.tolist(), top.indices.tolist()
@@ -155,7 +162,10 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
             pv, order = torch.sort(flat[picks], descending=True)
             vals, idxs = pv.tolist(), picks[order].tolist()
         cur_len = len(seqs[0]) + 1
-        pv_tok = proc.reshape(-1)[torch.as_tensor(idxs, device=proc.device)].tolist() if with_scores else [0.0] * len(idxs)
+        if hooked is not None:
+            pv_tok = hooked
+        else:
+            pv_tok = proc.reshape(-1)[torch.as_tensor(idxs, device=proc.device)].tolist() if with_scores else [0.0] * len(idxs)
         nxt: List[Tuple[float, int, int, float]] = []
         for rank, (v, ix, t_sc) in enumerate(zip(vals, idxs, pv_tok)):
             b, tok = ix // V, ix % V

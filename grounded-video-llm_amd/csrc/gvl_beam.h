@@ -1,0 +1,142 @@
+// gvl_beam.h -- host bookkeeping of beam search (gvl_beam_search): transformers 4.40.1 GenerationMixin._beam_search + BeamSearchScorer / BeamHypotheses [ext] for a
+// batch of one and one beam group, as grounded_video_llm_amd/beam.py restates them (`_Hyps` and the loop body of `beam_search` with sample = None).  Host-only, no HIP
+// (tests/c/beam_check.cc drives it on a CPU and tests/test_beam_host_cpu.py compares it with beam.py step by step); the per-step candidates -- the best 2k of the k x vocab
+// grid -- come from the device (gvl_beam.hip).
+//   * every score is a double: a candidate value is the fp32 the device added, widened; a hypothesis scores sum / pow((double)generated_len, length_penalty)
+//   * an eos candidate of rank < k closes a hypothesis (generated_len counts the eos), of rank >= k is skipped; the first k non-eos candidates are the next beams
+//   * done: k hypotheses exist and (early_stopping True, or the worst of them >= max(candidate values) / pow(cur_len, length_penalty)); "never" with a positive
+//     length_penalty is an error at the moment the rule would be evaluated, as in beam.py
+//   * at max_new_tokens the open beams become hypotheses; among equal best scores the LAST added wins; eos is appended while the output is shorter than max_new_tokens
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <vector>
+
+namespace gvl_beam {
+
+enum Status { BEAM_CONTINUE = 0, BEAM_FINISHED = 1, BEAM_ERR_NEVER = -1, BEAM_ERR_FEW = -2, BEAM_ERR_ARG = -3 };
+enum EarlyStopping { EARLY_FALSE = 0, EARLY_TRUE = 1, EARLY_NEVER = 2 };
+
+inline const char* status_text(int s) {
+  switch (s) {
+    case BEAM_ERR_NEVER: return "early_stopping \"never\" with length_penalty > 0 needs a maximum length: not supported";
+    case BEAM_ERR_FEW: return "fewer than num_beams non-eos candidates among the top 2 x num_beams";
+    case BEAM_ERR_ARG: return "bad beam-search arguments or candidate list";
+    default: return "";
+  }
+}
+
+struct Hyp { double score = 0.0; std::vector<int> ids; bool by_eos = false; std::vector<float> token_scores; };
+
+// BeamHypotheses: at most k hypotheses; `worst` as beam.py's _Hyps.add updates it
+struct Hyps {
+  int k = 0; double length_penalty = 1.0; int early = EARLY_FALSE;
+  std::vector<Hyp> beams; double worst = 1e9;
+
+  void add(const std::vector<int>& ids, double sum_logprobs, int generated_len, bool by_eos, const std::vector<float>& token_scores) {
+    const double score = sum_logprobs / std::pow((double)generated_len, length_penalty);
+    if ((int)beams.size() >= k && !(score > worst)) return;
+    Hyp h; h.score = score; h.ids = ids; h.by_eos = by_eos; h.token_scores = token_scores;
+    beams.push_back(std::move(h));
+    if ((int)beams.size() > k) {
+      // sorted((score, index)): the lowest score goes, the earliest added among equals; the second lowest is the new worst
+      size_t lo = 0;
+      for (size_t i = 1; i < beams.size(); ++i) if (beams[i].score < beams[lo].score) lo = i;
+      size_t lo2 = lo == 0 ? 1 : 0;
+      for (size_t i = 0; i < beams.size(); ++i) if (i != lo && beams[i].score < beams[lo2].score) lo2 = i;
+      worst = beams[lo2].score;
+      beams.erase(beams.begin() + (std::ptrdiff_t)lo);
+    } else {
+      worst = score < worst ? score : worst;
+    }
+  }
+  // BEAM_CONTINUE (not done), BEAM_FINISHED (done) or BEAM_ERR_NEVER
+  int is_done(double best_sum_logprobs, int cur_len) const {
+    if ((int)beams.size() < k) return BEAM_CONTINUE;
+    if (early == EARLY_TRUE) return BEAM_FINISHED;
+    if (early == EARLY_NEVER && length_penalty > 0.0) return BEAM_ERR_NEVER;
+    return worst >= best_sum_logprobs / std::pow((double)cur_len, length_penalty) ? BEAM_FINISHED : BEAM_CONTINUE;
+  }
+};
+
+struct BeamState {
+  int k = 0, vocab = 0, max_new = 0, eos = -1;
+  Hyps hyps;
+  std::vector<std::vector<int>> seqs;            // the ids every running beam generated so far
+  std::vector<std::vector<float>> tsc;           // ... and the processed log-probability each of them had in its parent's row
+  std::vector<float> scores;                     // running sums, fp32 as the device adds them: [0, -1e9, ...] before the first step
+  bool done = false, finished = false;
+
+  // eos_id < 0: none.  BEAM_CONTINUE or BEAM_ERR_ARG
+  int init(int num_beams, int vocab_, int max_new_tokens, int eos_id, double length_penalty, int early_stopping) {
+    if (num_beams < 2 || vocab_ < 2 * num_beams || max_new_tokens < 1 || early_stopping < EARLY_FALSE || early_stopping > EARLY_NEVER) return BEAM_ERR_ARG;
+    k = num_beams; vocab = vocab_; max_new = max_new_tokens; eos = eos_id < 0 ? -1 : eos_id;
+    hyps = Hyps(); hyps.k = k; hyps.length_penalty = length_penalty; hyps.early = early_stopping;
+    seqs.assign(k, std::vector<int>()); tsc.assign(k, std::vector<float>());
+    scores.assign(k, -1e9f); scores[0] = 0.f;
+    done = finished = false;
+    return BEAM_CONTINUE;
+  }
+  int cur_len() const { return (int)seqs[0].size() + 1; }
+
+  // One step's candidates, best first: n (value, flat index beam * vocab + token, processed log-probability) triples, n = 2k from the device.
+  // parents / tokens [k]: new beam j continues old beam parents[j] with tokens[j] (first step: parent 0).  BEAM_CONTINUE: advance the beams and come back;
+  // BEAM_FINISHED: the search is over (parents / tokens still describe the last beams); < 0: error, nothing usable.
+  int step(const float* vals, const int* idx, const float* proc, int n, int* parents, int* tokens) {
+    if (finished || n < k || !vals || !idx || !proc) return BEAM_ERR_ARG;
+    const int len = cur_len();
+    struct Next { float v; int tok, b; float t; };
+    std::vector<Next> nxt;
+    double best = (double)vals[0];
+    for (int r = 0; r < n; ++r) {
+      if ((double)vals[r] > best) best = (double)vals[r];
+      if (idx[r] < 0 || idx[r] / vocab >= k) return BEAM_ERR_ARG;
+    }
+    for (int r = 0; r < n && (int)nxt.size() < k; ++r) {
+      const int b = idx[r] / vocab, tok = idx[r] % vocab;
+      if (eos >= 0 && tok == eos) {
+        if (r >= k) continue;
+        std::vector<float> ts = tsc[b]; ts.push_back(proc[r]);
+        hyps.add(seqs[b], (double)vals[r], len, true, ts);
+      } else {
+        nxt.push_back(Next{vals[r], tok, b, proc[r]});
+      }
+    }
+    if ((int)nxt.size() < k) return BEAM_ERR_FEW;
+    if (!done) {
+      const int d = hyps.is_done(best, len);
+      if (d < 0) return d;
+      done = d == BEAM_FINISHED;
+    }
+    std::vector<std::vector<int>> s2(k); std::vector<std::vector<float>> t2(k);
+    for (int j = 0; j < k; ++j) {
+      parents[j] = len == 1 ? 0 : nxt[j].b; tokens[j] = nxt[j].tok;
+      s2[j] = seqs[nxt[j].b]; s2[j].push_back(nxt[j].tok);
+      t2[j] = tsc[nxt[j].b]; t2[j].push_back(nxt[j].t);
+      scores[j] = nxt[j].v;
+    }
+    seqs.swap(s2); tsc.swap(t2);
+    if (done || (int)seqs[0].size() >= max_new) { finished = true; return BEAM_FINISHED; }
+    return BEAM_CONTINUE;
+  }
+
+  // The best hypothesis after BEAM_FINISHED: its new ids (eos included when it ended by eos and there is room), its score, one transition score per id
+  void finalize(std::vector<int>* ids, double* score, std::vector<float>* transition) {
+    if (!done) for (int j = 0; j < k; ++j) hyps.add(seqs[j], (double)scores[j], (int)seqs[j].size(), false, tsc[j]);
+    Hyp best; best.ids = seqs[0]; best.token_scores = tsc[0];
+    if (!hyps.beams.empty()) {
+      size_t bi = 0;
+      for (size_t i = 1; i < hyps.beams.size(); ++i) if (hyps.beams[i].score >= hyps.beams[bi].score) bi = i;   // >=: among equal scores the last added wins
+      best = hyps.beams[bi];
+    }
+    std::vector<int> out = best.ids;
+    if (best.by_eos && eos >= 0 && (int)out.size() < max_new) out.push_back(eos);
+    std::vector<float> ts = best.token_scores;
+    if (ts.size() > out.size()) ts.resize(out.size());
+    if (ids) *ids = out;
+    if (score) *score = best.score;
+    if (transition) *transition = ts;
+  }
+};
+
+}  // namespace gvl_beam

@@ -112,6 +112,9 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   // log-probability lists of every sequence slot ([kMaxSeqs][outlist_cap], top lists x GVL_MAX_TOP_LOGPROBS: ~134 MB), allocated by the first
   // gvl_set_logprobs / gvl_seq_set_logprobs that needs them
   float* d_seq_lp = nullptr; int* d_seq_top_ids = nullptr; float* d_seq_top_lp = nullptr;
+  // beam search (gvl_beam.hip), allocated by the first call that needs them: the per-row survivors between the two candidate launches, one step's candidates in HOST-MAPPED
+  // memory (h_ / d_ views), [GVL_MAX_DECODE_BATCH][vocab] work rows, and the beams' histories + lengths for the logits processors
+  void* d_beam_scratch = nullptr; void* h_beam_cand = nullptr; void* d_beam_cand = nullptr; float* d_beam_rows = nullptr; int* d_beam_hist = nullptr;
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
   // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of ~165 kernel launches
   struct { int decode_attn_cpb = 0, decode_attn_hpb = 0; bool decode_graph = true; int vision_in_place = 1, prefill_group = 4, attn_ring = 0, attn_pipe = 1, attn_pipe_rows = 128, patch_fused = 1, varlen_attn = 1, norm_fused = 1, last_layer_tail = 1; } dbg;

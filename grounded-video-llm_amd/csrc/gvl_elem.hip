@@ -1336,6 +1336,147 @@ int gvl_launch_select_rows(const SelRowsArgs& sa, hipStream_t st) {
   }
   return CHECK_LAUNCH();
 }
+// ---- beam search: the 2k candidates of one step (BeamCandArgs; HF _beam_search [ext]: log-softmax -> processors -> + beam score -> top-2k over the k x vocab grid).
+// Two launches; the kernel boundary is the only hand-off between workgroups.
+//   beam_rows_kernel<NORM>   one block per running beam.  NORM: the row holds raw logits; m = its maximum, lz = logf(sum exp(l - m)) summed strided per thread and
+//                            finished with smp_block_sum -- the quantity lp_row_pass<1> computes, so lp = (l - m) - lz is bit for bit what greedy selection reports for
+//                            the token.  !NORM: the row holds processed log-probabilities already (beam_normalize_kernel, then the logits processors).  The candidate
+//                            value is t = lp + score[b], ONE fp32 add, and the selection runs on t, not on lp: distinct lp can collide after the add (at a score of
+//                            -1e9 every entry does).  Order: the strict total order (t descending, index ascending) over ALL entries, -inf included.  The key of the
+//                            2k-th largest t comes from the sampler's 8-bit radix select over smp_key(t) (integer counts: exact); the entries above it are taken, and
+//                            of the ties AT it the lowest indices -- when there are more ties than places a second radix select, over ~index among the ties, finds
+//                            the last index taken.  The <= 32 survivors are ordered by counting in LDS and stored as (t, token, lp).
+//   beam_merge_kernel        one wave: the best 2k of the k x 2k row survivors in the same order -- an entry's rank = the sum over the (sorted) rows of how many of
+//                            their entries beat it, a binary search per row; flat index = beam * n + token.
+//   beam_normalize_kernel    the NORM arithmetic alone, in place (when processors or token rules sit between the log-softmax and the beam scores): normalize followed by
+//                            beam_rows_kernel<false> is bit-identical to beam_rows_kernel<true>.
+// Keys, not float compares, order everything: every count is an integer and every store index is bounded whatever the row holds (NaN rows are outside the contract: their
+// order is the keys', not IEEE's).  t + 0.0f folds -0.0 onto +0.0 before the key is taken, so the two compare equal as floats do.
+__device__ __forceinline__ unsigned beam_key(float t) { return smp_key(t + 0.0f); }
+template <bool NORM> __device__ __forceinline__ float beam_lp(float l, float m, float lz) { if constexpr (NORM) return __fsub_rn(__fsub_rn(l, m), lz); else return l; }
+// row maximum and log of the normaliser, in every thread (sample_kernel's maximum, lp_row_pass's sum: fixed order, a pure function of the row)
+__device__ __forceinline__ void beam_row_norm(const float* l, int n, float* shf, float& m, float& lz) {
+  const int tid = threadIdx.x;
+  float best = -3.4e38f;
+  for (int i = tid; i < n; i += 1024) best = fmaxf(best, l[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+  if ((tid & 63) == 0) shf[tid >> 6] = best;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 16; ++w) best = fmaxf(best, shf[w]);
+  m = best;
+  float z = 0.f;
+  for (int i = tid; i < n; i += 1024) z += expf((l[i] - m) * 1.0f);
+  lz = logf(smp_block_sum(z, shf));
+}
+// Whole block: the key of the `want`-th largest of the keys keyf hands out for i in [0, n) (keyf returns false for an entry outside the set), `take` = how many entries AT
+// that key belong to the best `want`, `ties` = how many entries hold it.  sel: three words of LDS.
+template <class F>
+__device__ __forceinline__ void beam_radix_select(int n, int want, F keyf, int* hist, unsigned* sel, unsigned& kth, int& take, int& ties) {
+  const int tid = threadIdx.x;
+  unsigned prefix = 0; int remaining = want;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) {
+      unsigned k;
+      if (!keyf(i, k)) continue;
+      if (shift == 24 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int c = 0, bsel = 0;
+      for (int q = 255; q >= 0; --q) { if (c + hist[q] >= remaining) { bsel = q; break; } c += hist[q]; }
+      sel[0] = prefix | ((unsigned)bsel << shift); sel[1] = (unsigned)(remaining - c); sel[2] = (unsigned)hist[bsel];
+    }
+    __syncthreads();
+    prefix = sel[0]; remaining = (int)sel[1]; ties = (int)sel[2];
+    __syncthreads();
+  }
+  kth = prefix; take = remaining;
+}
+constexpr int GVL_BEAM_MAX_CAND = 2 * GVL_MAX_DECODE_BATCH;
+template <bool NORM>
+__global__ __launch_bounds__(1024) void beam_rows_kernel(const BeamCandArgs a) {
+  __shared__ float shf[16];
+  __shared__ int hist[256];
+  __shared__ unsigned s_sel[3];
+  __shared__ float c_t[GVL_BEAM_MAX_CAND], c_lp[GVL_BEAM_MAX_CAND];
+  __shared__ int c_i[GVL_BEAM_MAX_CAND];
+  __shared__ int s_cnt;
+  const int b = blockIdx.x, tid = threadIdx.x, n = a.n, K2 = 2 * a.k;
+  const float* l = a.rows + (size_t)b * (size_t)a.row_stride;
+  const float sc = a.scores[b];
+  float m = 0.f, lz = 0.f;
+  if constexpr (NORM) beam_row_norm(l, n, shf, m, lz);
+  unsigned kth, ikey = 0; int take, ties;
+  beam_radix_select(n, K2, [&](int i, unsigned& k) { k = beam_key(__fadd_rn(beam_lp<NORM>(l[i], m, lz), sc)); return true; }, hist, s_sel, kth, take, ties);
+  if (ties > take) {                         // block-uniform: more entries at the 2k-th key than places -> the lowest indices among them
+    int t2, n2;
+    beam_radix_select(n, take, [&](int i, unsigned& k) { k = ~(unsigned)i; return beam_key(__fadd_rn(beam_lp<NORM>(l[i], m, lz), sc)) == kth; }, hist, s_sel, ikey, t2, n2);
+  }
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  for (int i = tid; i < n; i += 1024) {
+    const float lp = beam_lp<NORM>(l[i], m, lz), t = __fadd_rn(lp, sc);
+    const unsigned k = beam_key(t);
+    if (k > kth || (k == kth && ~(unsigned)i >= ikey)) {
+      const int s = atomicAdd(&s_cnt, 1);
+      if (s < GVL_BEAM_MAX_CAND) { c_t[s] = t; c_lp[s] = lp; c_i[s] = i; }
+    }
+  }
+  __syncthreads();
+  const int cnt = s_cnt < K2 ? s_cnt : K2;   // == K2: integer counts
+  if (tid < cnt) {
+    const unsigned mk = beam_key(c_t[tid]); const int mi = c_i[tid];
+    int rank = 0;
+    for (int j = 0; j < cnt; ++j) { const unsigned kj = beam_key(c_t[j]); rank += (kj > mk || (kj == mk && c_i[j] < mi)) ? 1 : 0; }
+    const size_t o = (size_t)b * K2 + rank;
+    a.row_v[o] = c_t[tid]; a.row_i[o] = mi; a.row_lp[o] = c_lp[tid];
+  }
+}
+__global__ __launch_bounds__(64) void beam_merge_kernel(const BeamCandArgs a) {
+  __shared__ unsigned mk[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+  __shared__ int mi[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+  const int lane = threadIdx.x, K2 = 2 * a.k, total = a.k * K2;
+  for (int e = lane; e < total; e += 64) { mk[e] = beam_key(a.row_v[e]); mi[e] = (e / K2) * a.n + a.row_i[e]; }
+  __syncthreads();
+  for (int e = lane; e < total; e += 64) {
+    const unsigned ke = mk[e]; const int ie = mi[e];
+    int rank = 0;
+    for (int r = 0; r < a.k; ++r) {          // a row's survivors are sorted in this very order: those better than e are a prefix of the row -> binary search
+      const int base = r * K2;
+      int lo = 0, hi = K2;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (mk[base + mid] > ke || (mk[base + mid] == ke && mi[base + mid] < ie)) lo = mid + 1; else hi = mid;
+      }
+      rank += lo;
+    }
+    if (rank < K2) { a.vals[rank] = a.row_v[e]; a.idx[rank] = ie; a.proc[rank] = a.row_lp[e]; }
+  }
+}
+__global__ __launch_bounds__(1024) void beam_normalize_kernel(float* rows, int n) {
+  __shared__ float shf[16];
+  float* l = rows + (size_t)blockIdx.x * n;
+  float m, lz;
+  beam_row_norm(l, n, shf, m, lz);           // every thread has read the entries it is about to overwrite, and the block sum is behind its barriers
+  for (int i = threadIdx.x; i < n; i += 1024) l[i] = beam_lp<true>(l[i], m, lz);
+}
+static bool beam_shape_ok(int n, int k) { return k >= 2 && k <= GVL_MAX_DECODE_BATCH && n >= 2 * k && (long long)n * k <= 0x7fffffffLL; }
+int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st) {
+  if (!beam_shape_ok(a.n, a.k) || !a.rows || a.row_stride < 0 || !a.row_v || !a.row_i || !a.row_lp || !a.vals || !a.idx || !a.proc) return -1;
+  if (a.norm) hipLaunchKernelGGL(beam_rows_kernel<true>, dim3(a.k), dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL(beam_rows_kernel<false>, dim3(a.k), dim3(1024), 0, st, a);
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(1), dim3(64), 0, st, a);
+  return CHECK_LAUNCH();
+}
+int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st) {
+  if (!rows || n < 1 || k < 1 || k > GVL_MAX_DECODE_BATCH) return -1;
+  hipLaunchKernelGGL(beam_normalize_kernel, dim3(k), dim3(1024), 0, st, rows, n);
+  return CHECK_LAUNCH();
+}
 __global__ void gather_tok_rows_kernel(const bf16_t* __restrict__ table, const TokPtrs toks, bf16_t* __restrict__ dst, int cols) {
   const int r = blockIdx.y;
   const int tok = *toks.p[r];

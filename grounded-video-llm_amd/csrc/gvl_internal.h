@@ -377,6 +377,12 @@ int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
 struct SelRow { int on; float inv_temp; int top_k; float top_p, min_p, typical_p, eps, eta; unsigned seed_lo, seed_hi, stream; };
 struct SelRowsArgs { ArgmaxArgs am; SelRow row[GVL_MAX_DECODE_BATCH]; unsigned char* kept; };
 int gvl_launch_select_rows(const SelRowsArgs& a, hipStream_t st);
+// Beam search, one step's candidates (beam_rows_kernel + beam_merge_kernel, gvl_elem.hip): rows [k] of n fp32 entries, row b at rows + b * row_stride (0: every beam reads
+// row 0 -- the first step); norm != 0: raw logits, log-softmax inside; 0: processed log-probabilities.  row_* [k][2k]: device scratch between the two launches.  vals / idx /
+// proc [2k]: the best 2k of the k x n grid in the order (value descending, flat index beam * n + token ascending) -- value = fp32(log-prob + scores[beam]), proc = the log-prob.
+struct BeamCandArgs { const float* rows; int n, k, row_stride, norm; float scores[GVL_MAX_DECODE_BATCH]; float* row_v; int* row_i; float* row_lp; float* vals; int* idx; float* proc; };
+int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st);
+int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st);      // rows [k][n] raw logits -> log-softmax, in place (beam_rows_kernel<true>'s arithmetic)
 // HF logits processors (repetition penalty -> no-repeat n-gram -> min length) on `batch` fp32 rows (stride ld), in place (gvl_logits.hip).  Row b's
 // history is hist[b][0 .. *len_ptrs[b]) (clamped to cap <= GVL_LOGITS_HIST_CAP; a null len_ptrs[b] = empty history); penalty 1 / ngram 0 /
 // min_new 0 switch a processor off; eos < 0 switches the min-length ban off.

@@ -170,6 +170,7 @@ int gvl_destroy(gvl_ctx* ctx) {
   hipDeviceSynchronize();
   if (ctx->h_eos_flags) hipHostFree(ctx->h_eos_flags);
   if (ctx->h_seq_out) hipHostFree(ctx->h_seq_out);
+  if (ctx->h_beam_cand) hipHostFree(ctx->h_beam_cand);
   for (int i = 0; i < 3; ++i) if (ctx->step_ev[i]) hipEventDestroy(ctx->step_ev[i]);
   for (auto& kv : ctx->w) if (kv.second.p) hipFree(kv.second.p);
   for (void* p : ctx->dw_allocs) if (p) hipFree(p);
@@ -179,7 +180,7 @@ int gvl_destroy(gvl_ctx* ctx) {
   ctx->nf_allocs.clear();
   if (ctx->comm) gvl_comm_destroy(ctx);
   for (RuleSet& r : ctx->rule_sets) if (r.used && r.d) hipFree(r.d);
-  void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch};
+  void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch, ctx->d_beam_scratch, ctx->d_beam_rows, ctx->d_beam_hist};
   for (void* p : ptrs) if (p) hipFree(p);
   for (auto& r : ctx->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   delete ctx;

@@ -413,6 +413,49 @@ class Engine:
         self._chk(self.lib.gvl_decode_step_logits_batch(self.ctx, ids, n, tk, _ptr(logits), self.stream), "gvl_decode_step_logits_batch")
         return logits
 
+    # ---- beam search in the library (gvl_beam_search; csrc/gvl_beam.h + the candidate kernels) -------------------
+    def op_beam_candidates(self, rows: torch.Tensor, scores, logprobs: bool = False, stride0: bool = False):
+        """gvl_op_beam_candidates: one beam-search step's 2k candidates of fp32 rows [k, n] with beam scores [k] -> (vals f32 [2k], idx int32 [2k] flat
+        beam * n + token, proc f32 [2k]) on the device, ordered by (value descending, flat index ascending).  logprobs: the rows are processed
+        log-probabilities already (otherwise raw logits: the log-softmax runs inside).  stride0: rows is ONE row [n] every beam reads (the first step)."""
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.device == self.device
+        sc = [float(x) for x in (scores.tolist() if isinstance(scores, torch.Tensor) else scores)]
+        k = len(sc)
+        n = rows.shape[-1]
+        if not stride0 and (rows.dim() != 2 or rows.shape[0] != k):
+            raise ValueError(f"op_beam_candidates: {k} scores for rows of shape {tuple(rows.shape)}")
+        vals = torch.full((2 * k,), float("nan"), dtype=torch.float32, device=self.device)
+        idx = torch.full((2 * k,), -1, dtype=torch.int32, device=self.device)
+        proc = torch.full((2 * k,), float("nan"), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.gvl_op_beam_candidates(self.ctx, _ptr(rows), n, k, 0 if stride0 else n, (C.c_float * k)(*sc), int(bool(logprobs)), _ptr(vals), _ptr(idx),
+                                                  _ptr(proc), self.stream), "gvl_op_beam_candidates")
+        return vals, idx, proc
+
+    def op_beam_normalize(self, rows: torch.Tensor) -> torch.Tensor:
+        """gvl_op_beam_normalize: fp32 rows [k, n] of raw logits -> their log-softmax IN PLACE (the candidate kernel's own arithmetic); returns rows."""
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 2 and rows.device == self.device
+        self._chk(self.lib.gvl_op_beam_normalize(self.ctx, _ptr(rows), rows.shape[1], rows.shape[0], self.stream), "gvl_op_beam_normalize")
+        return rows
+
+    def beam_search(self, seq: int, first_logits: torch.Tensor, num_beams: int, max_new: int, eos: Optional[int], length_penalty: float = 1.0, early_stopping=False,
+                    processors=None, rules: Optional[int] = None, with_scores: bool = False):
+        """gvl_beam_search: HF beam search (num_beams = k, do_sample = False) from the PREFILLED sequence `seq` and its prefill logits, inside the library; `seq` is not
+        consumed.  processors: a logits.Processors (None = off); rules: a rule-set id (None = none); early_stopping: False / True / "never".  Returns the new ids, or with
+        with_scores (ids, sequences_score, transition_scores) as beam.beam_search does."""
+        if early_stopping not in (False, True, "never"):
+            raise ValueError("early_stopping must be False, True or 'never'")
+        assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.device == self.device
+        pe, ng, mn, pe_eos = processors.args() if processors is not None else (1.0, 0, 0, None)
+        prm = L.GvlBeamParams(int(num_beams), int(max_new), -1 if eos is None else int(eos), float(length_penalty), {False: 0, True: 1, "never": 2}[early_stopping],
+                              float(pe), int(ng), int(mn), -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
+        cap = max(int(max_new), 1)
+        ids = (C.c_int32 * cap)()
+        ts = (C.c_float * cap)()
+        n, score = C.c_int(0), C.c_double(0.0)
+        self._chk(self.lib.gvl_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, C.byref(n), C.byref(score), ts, self.stream), "gvl_beam_search")
+        out = [int(ids[i]) for i in range(n.value)]
+        return (out, score.value, [float(ts[i]) for i in range(n.value)]) if with_scores else out
+
     def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None,
                      rules: Optional[int] = None):
         """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  processors: a logits.Processors for this

@@ -51,6 +51,12 @@ class GvlSampling(C.Structure):
                 ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("seed", C.c_uint64), ("stream", C.c_uint32)]
 
 
+class GvlBeamParams(C.Structure):
+    """gvl_beam_params (include/gvl.h)."""
+    _fields_ = [("num_beams", C.c_int), ("max_new_tokens", C.c_int), ("eos_id", C.c_int), ("length_penalty", C.c_double), ("early_stopping", C.c_int),
+                ("penalty", C.c_float), ("ngram", C.c_int), ("min_new", C.c_int), ("proc_eos_id", C.c_int), ("rules_id", C.c_int)]
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "gvl_create": (C.c_int, [C.POINTER(GvlConfig), C.POINTER(C.c_void_p)]),
@@ -128,6 +134,10 @@ _SIGS = {
     "gvl_op_decode_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "gvl_probe_mfma": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "gvl_trace_marker": (C.c_int, [C.c_int, C.c_void_p]),
+    "gvl_beam_search": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GvlBeamParams), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_float), C.c_void_p]),
+    "gvl_op_beam_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gvl_op_beam_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "gvl_op_gemv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)

@@ -320,11 +320,15 @@ class LLAVA_NEXT_VIDEO:
         force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
         typical_p / epsilon_cutoff / eta_cutoff (those seven run on the device in HF's order; top_h, custom logits_warper lists stay ignored).
         return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
-        log-probabilities; logprobs.py) instead of the list of texts."""
+        log-probabilities; logprobs.py) instead of the list of texts.
+        beam_impl (extra; num_beams > 1): "host" (default) = beam.py's bookkeeping with torch's log-softmax / top-2k per step; "device" = gvl_beam_search, the whole
+        search inside the library (its own kernels select the candidates; sequences_scores / transition scores come from it).  "device" with do_sample=True raises
+        ValueError: beam-sample stays on beam.py, its draws are torch's."""
         if any(v == "text" for v in samples.get("video_ids", [])):
             # prepare_multimodal_inputs' `video_ids == 'text'` branch (llava_next_video.py:583-586) is a TRAINING device (dummy visual
             # rows appended with mask 0 so FSDP sees every parameter); the reference's inference never produces it.  forward() handles it.
             raise ValueError("generate(): 'text' samples are a training-only construct of the reference; use forward() for them")
+        _beam_impl(generate_kwargs)                       # a bad beam_impl fails before any work
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
@@ -352,7 +356,7 @@ class LLAVA_NEXT_VIDEO:
             scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs, with_scores=scored, rules=rid)
+                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs))
                        for b in range(ids_arr.shape[0])]
             if scored:
                 lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
@@ -368,16 +372,33 @@ class LLAVA_NEXT_VIDEO:
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
                           sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
-                          rules: Optional[int] = None):
+                          rules: Optional[int] = None, impl: str = "host"):
         """generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
         teacher-forced batched decode step per token (gvl_decode_step_logits_batch: one stream of the weights for the k beams); log-softmax / top-2k of the step run on the device (torch), the bookkeeping on
         the host.  processors: HF's logits processors, applied by gvl_op_logits_process to every step's log-softmax rows before the beam scores
         are added (HF _beam_search / _beam_sample); the beams' own sequences select their tokens without them (their raw logits are what the
-        steps return).  rules: a rule-set id (Engine.rules_create) applied in the same pass, in HF's order.  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them."""
+        steps return).  rules: a rule-set id (Engine.rules_create) applied in the same pass, in HF's order.  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them.
+        impl = "device": the same search inside the library (Engine.beam_search = gvl_beam_search: bookkeeping in C++, every step's log-softmax and top-2k in the
+        library's kernels, the processors / rules by the same launch); beam search only (sample must be None)."""
         from . import beam as B
         eng = self.engine
+        if impl not in ("host", "device"):
+            raise ValueError(f"beam search: impl must be 'host' or 'device', not {impl!r}")
+        if impl == "device":
+            if sample is not None:
+                raise ValueError("beam-sample runs on the host path only (its draws are torch's): impl='device' needs sample=None")
+            eos = getattr(self.tokenizer, "eos_token_id", None)
+            emb = eng.splice(row, vis)
+            seq = eng.seq_alloc(min(emb.shape[0], self.geo.max_seq))
+            try:
+                LP.apply_seq_options(eng, seq, LP.SeqOptions.OFF)
+                first = eng.prefill(seq, emb, want_logits=True)
+                return eng.beam_search(seq, first, num_beams, max_new, eos, length_penalty, early_stopping,
+                                       processors if processors is not None and processors.active else None, rules, with_scores)
+            finally:
+                eng.seq_free(seq)
         gi = eng.decode_group_info()                     # which group sizes ONE batched step takes: asked from the library, not restated here
         eos = getattr(self.tokenizer, "eos_token_id", None)
         emb = eng.splice(row, vis)
@@ -586,6 +607,16 @@ class LLAVA_NEXT_VIDEO:
                     eng.seq_free(seq)
             b += len(seqs)
         return out if logprobs is None else (out, lps)
+
+
+def _beam_impl(kw) -> str:
+    """generate()'s beam_impl: "host" (default) or "device"; "device" is beam search only."""
+    impl = kw.get("beam_impl", "host")
+    if impl not in ("host", "device"):
+        raise ValueError(f"beam_impl must be 'host' or 'device', not {impl!r}")
+    if impl == "device" and kw.get("do_sample", False) and kw.get("num_beams", 1) not in (1, None):
+        raise ValueError("beam_impl='device' is beam search (do_sample=False); beam-sample runs on the host path: its draws are torch's")
+    return impl
 
 
 BASE_VOCAB = {"phi3.5": 32064, "llama3": 128256, "vicuna": 32000}     # tokenizer sizes before reset_embeddings [ext]

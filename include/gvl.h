@@ -164,9 +164,10 @@ int gvl_decode_greedy(gvl_ctx* ctx, int seq_id, int max_new, int eos_id, int32_t
  * this call, generation step, logits): reproducible, and independent of how sequences are grouped into decode batches.  (A call
  * that repeats the current seed while sequences are live continues the numbering instead, so newcomers never share a stream with
  * a running sequence; callers that make several generate() calls per request pass a different seed per call.)
- * torch.multinomial's random stream is not reproduced (parity = same kept set + same distribution).  Beam search (num_beams > 1, do_sample = 0) is host
- * bookkeeping over gvl_seq_clone + gvl_decode_step_logits_batch (grounded_video_llm_amd/beam.py); beam-sample (num_beams > 1, do_sample = 1) is the
- * same bookkeeping with the 2 x num_beams candidates of a step drawn on the host from the warped beam distributions (beam.py). */
+ * torch.multinomial's random stream is not reproduced (parity = same kept set + same distribution).  Beam search (num_beams > 1, do_sample = 0) is
+ * gvl_beam_search below: bookkeeping on the host (csrc/gvl_beam.h), every step's log-softmax and top 2 x num_beams candidates in the library's kernels; beam-sample
+ * (num_beams > 1, do_sample = 1) stays host bookkeeping over gvl_seq_clone + gvl_decode_step_logits_batch with the candidates of a step DRAWN on the host from the warped
+ * beam distributions (grounded_video_llm_amd/beam.py: its draws are torch's). */
 int gvl_set_sampling(gvl_ctx* ctx, int do_sample, float temperature, int top_k, float top_p, uint64_t seed);
 /* Sampling as one value, with HF's remaining warpers.  A sampled selection runs, in HF's order (transformers _get_logits_processor [ext]), each stage's softmax taken over
  * what the stage before left, min_tokens_to_keep = 1:
@@ -289,6 +290,41 @@ int gvl_decode_step_logits(gvl_ctx* ctx, int seq_id, int tok, float* logits, voi
 /* The same for up to 16 sequences in ONE step (one stream of the weights): sequence i takes toks[i]; logits (may be null) receives
  * [n_seqs][vocab] fp32.  Row i is bit-identical to gvl_decode_step_logits on sequence i alone.  Beam search advances its k beams with it. */
 int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const int32_t* toks, float* logits, void* stream);
+
+/* Beam search: HF generate(num_beams = k, do_sample = False) (inference.py:46,170-176 -> models/llava_next_video.py:655-661 -> transformers 4.40.1
+ * GenerationMixin._beam_search + BeamSearchScorer [ext]; batch of one, one beam group) inside the library.  seq_id is a PREFILLED sequence and first_logits (device,
+ * f32 [vocab]) the last_logits its gvl_prefill* returned.  The sequence is NOT consumed: the k running beams are gvl_seq_clone's of it (capacity min(tokens +
+ * max_new_tokens + 1, cfg.max_seq); whole KV pages shared by reference, HF's per-step cache reorder = clone / free), their selection options are switched off so every
+ * step yields raw logits, and every sequence the call made is freed on every return path -- on return seq_id is where it was (the KV pool too) and can be decoded or
+ * searched again.  Per step: the k beams advance by ONE teacher-forced decode step (one stream of the weights; on the VALU-fallback geometries in parts of 4 / 2 / 1
+ * sequences -- a row does not depend on its part), then two launches give the best 2k of the k x vocab grid:
+ *     lp = (l - max) - logf(sum exp(l - max))      fp32, the fixed-order sum of gvl_set_logprobs: bit for bit the log-probability greedy selection reports for the token
+ *     t  = lp + beam_score                         ONE fp32 add; the beam scores start as [0, -1e9, ...] (the first step expands the prompt's row only)
+ *     order: t descending, then flat index beam * vocab + token ascending -- a strict total order over ALL entries, -inf included (torch.topk leaves ties unspecified)
+ * With processors (penalty / ngram / min_new / proc_eos_id: gvl_set_logits_processors' meaning, history = the beam's generated ids) or a rule set (gvl_rules_create), HF's
+ * order holds: log-softmax -> sequence_bias -> processors -> ... -> + beam score -> top 2k.  The candidates land in host-mapped memory; after one stream synchronise per
+ * step the host bookkeeping (csrc/gvl_beam.h, all score arithmetic in double: sum / pow((double)generated_len, length_penalty)) consumes them: an eos candidate of rank < k
+ * closes a hypothesis (generated_len counts the eos), of rank >= k is skipped; done = k hypotheses and (early_stopping 1, or the worst of them >= max candidate /
+ * cur_len ** length_penalty); at max_new_tokens the open beams become hypotheses; among equal best scores the last added wins.  Output: the NEW ids of the best hypothesis
+ * (eos appended when it ended by eos and there is room) in out_ids_host [cap >= max_new_tokens], their number in *n_out, the hypothesis score in *sequences_score (may be
+ * NULL) and per id the processed log-probability it had in its beam's row, before the beam score (HF compute_transition_scores(normalize_logits = False)), in
+ * transition_scores_host [cap] (may be NULL).  Synchronises `stream`.
+ * Errors (a message via gvl_last_error; nothing is leaked): num_beams outside 2 .. 16, vocab < 2 x num_beams, max_new_tokens < 1 or > 8192, cap < max_new_tokens, an
+ * unknown rule set, bad processor values, an unknown or not prefilled sequence (GVL_ERR_STATE), early_stopping 2 ("never") with length_penalty > 0 (it needs a maximum
+ * length the reference never passes), KV pages exhausted (GVL_ERR_OOM), fewer than num_beams non-eos candidates among a step's 2 x num_beams (GVL_ERR_STATE).
+ * NaN logits are outside the contract: the candidate order is then that of the order-preserving integer keys, not IEEE's (no store goes out of bounds).
+ * Diverse / constrained beams and num_return_sequences > 1 are not supported. */
+typedef struct gvl_beam_params {
+  int num_beams;            /* 2 .. 16 (GVL_MAX_DECODE_BATCH) */
+  int max_new_tokens;       /* >= 1 */
+  int eos_id;               /* -1: none */
+  double length_penalty;
+  int early_stopping;       /* 0 False, 1 True, 2 "never" */
+  float penalty; int ngram; int min_new; int proc_eos_id;  /* gvl_set_logits_processors' meaning; 1.0 / 0 / 0 / -1 = off */
+  int rules_id;             /* -1: none */
+} gvl_beam_params;
+int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_beam_params* params, int32_t* out_ids_host, int cap, int* n_out,
+                    double* sequences_score, float* transition_scores_host, void* stream);
 
 /* ---- multi-GPU exchange (SURVEY.md §8 e) -------------------------------------------------------------------------------------
  * The reference's inference is single-GPU (inference.py:17); sharding the frame batch over the GPUs of a node is this build's
@@ -443,6 +479,14 @@ int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, 
  * may be null): 1 where an entry is finite and in the row's final kept set (a greedy row keeps every finite entry), else 0. */
 int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, const gvl_sampling* rows, const int32_t* steps_dev, const int* top_n,
                        int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, uint8_t* kept_dev, void* stream);
+/* One beam-search step's candidates on their own (operator tests; hosts that keep their own books): rows f32 device, row b of n entries at rows + b * row_stride
+ * (row_stride 0: every beam reads row 0, as the first step does; otherwise >= n), k = num_beams 2 .. 16, n >= 2 k; beam_scores_host [k].  rows_are_logprobs = 0: raw
+ * logits, the log-softmax runs inside; 1: processed log-probabilities.  vals_dev / idx_dev / proc_dev [2 k] (device): value t, flat index beam * n + token, and the
+ * log-probability before the score was added, in gvl_beam_search's order.  gvl_op_beam_normalize: rows [k][n] (k 1 .. 16) raw logits -> log-softmax IN PLACE; normalize
+ * followed by candidates with rows_are_logprobs = 1 is bit-identical to candidates with 0.  NaN rows are outside the contract. */
+int gvl_op_beam_candidates(gvl_ctx* ctx, const float* rows, int n, int k, int row_stride, const float* beam_scores_host, int rows_are_logprobs, float* vals_dev,
+                           int32_t* idx_dev, float* proc_dev, void* stream);
+int gvl_op_beam_normalize(gvl_ctx* ctx, float* rows, int n, int k, void* stream);
 /* y[b][N] = W[N,K] x[b][K] (+bias) for b < batch <= 16 -- the decode projections as ONE skinny MFMA GEMM (the weight stream is
  * read once for all sequences; K % 256 == 0).  x bf16 [batch][K], y f32 [batch][N]. */
 int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch,
