@@ -1,5 +1,5 @@
 // gvl_elem.hip -- HBM-bound kernels of the hot path: norms, patch im2col, embeddings, qkv re-tiling
-// (+ qk-RMSNorm / RoPE), HD-merge / pooling glue, decode GEMV, argmax.   gfx950 only.
+// (+ qk-RMSNorm / RoPE), HD-merge / pooling glue, decode GEMV (token selection: gvl_pick.hip).   gfx950 only.
 // Every kernel moves 8/16 bytes per lane (guide G13) and keeps statistics in fp32.
 #include "gvl_internal.h"
 #include <cstring>
@@ -824,659 +824,6 @@ int gvl_launch_gemv(const GemvArgs& a_in, hipStream_t st) {
   }
 }
 
-// ---- log-probabilities of the selected token and the best N alternatives (ArgmaxArgs.top_n / lp_lists / top_ids / top_lp).  The selection
-// kernels take a mode LPM: 0 = off (today's kernels, instruction for instruction), 1 = the selected token's log-probability, 2 = also the top N.
-// The distribution is the one the token was selected from: log_softmax of the (processed) row for greedy, the warped distribution for sampling
-// ((s - m) * invT over the final kept set, everything else -inf).  One extra pass over the row (in L2 by then): a fixed-order sum of
-// exp((s - m) * invT) over the kept set (strided per thread, then the smp_block_sum butterfly -- a pure function of the row), and a per-thread
-// register list of the best 8 finite kept entries, merged per wave (8 rounds of a butterfly max over the list heads) and across the 16 waves
-// through LDS.  The order is (value descending, lower id first), a strict total order: the merged list does not depend on who held what.
-// The token path is untouched: the pass runs after the selection's own passes and never feeds them.
-// (the sampler's helpers smp_* are shared with the sampling section below)
-__device__ __forceinline__ unsigned smp_fmix32(unsigned h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
-__device__ __forceinline__ unsigned smp_key(float v) { const unsigned b = __float_as_uint(v); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }   // order-preserving
-__device__ __forceinline__ float smp_block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);          // butterfly: bitwise the same total in every lane
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) t += sh[w];
-  return t;
-}
-__device__ __forceinline__ bool lp_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-// (v, i) into a thread's descending list: the carried entry swaps with every slot it beats (the list stays sorted, the last entry drops out)
-__device__ __forceinline__ void lp_insert(float (&tv)[GVL_MAX_TOP_LOGPROBS], int (&ti)[GVL_MAX_TOP_LOGPROBS], float v, int i) {
-  if (!lp_better(v, i, tv[GVL_MAX_TOP_LOGPROBS - 1], ti[GVL_MAX_TOP_LOGPROBS - 1])) return;
-#pragma unroll
-  for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j)
-    if (lp_better(v, i, tv[j], ti[j])) { const float t = tv[j]; const int u = ti[j]; tv[j] = v; ti[j] = i; v = t; i = u; }
-}
-// the best GVL_MAX_TOP_LOGPROBS entries of the 64 lists of a wave, in order, in every lane (wv / wi); the lists are consumed
-__device__ __forceinline__ void lp_wave_merge(float (&tv)[GVL_MAX_TOP_LOGPROBS], int (&ti)[GVL_MAX_TOP_LOGPROBS], float (&wv)[GVL_MAX_TOP_LOGPROBS],
-                                              int (&wi)[GVL_MAX_TOP_LOGPROBS]) {
-#pragma unroll
-  for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) {
-    float bv = tv[0]; int bi = ti[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (lp_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    wv[r] = bv; wi[r] = bi;
-    if (bi >= 0 && ti[0] == bi) {          // ids are unique across lanes: exactly the owner pops its head
-#pragma unroll
-      for (int j = 0; j + 1 < GVL_MAX_TOP_LOGPROBS; ++j) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
-      tv[GVL_MAX_TOP_LOGPROBS - 1] = -INFINITY; ti[GVL_MAX_TOP_LOGPROBS - 1] = -1;
-    }
-  }
-}
-// Whole block, row b on (block-uniform).  Kept set: keys >= thr (0: every entry).  Returns log(sum over the kept set of exp((s - m) * invT));
-// with LPM == 2 and top_n[b] > 0 it also stores row b's top list at generation index g.  BAND (select_rows_kernel): the kept set is thr <= key <= hi.
-template <int LPM, bool BAND = false>
-__device__ float lp_row_pass(const ArgmaxArgs& a, int b, const float* l, float m, float inv_temp, unsigned thr, int g, [[maybe_unused]] unsigned hi = 0xffffffffu) {
-  __shared__ float shz[16];
-  const int tid = threadIdx.x, n = a.n;
-  const bool top = LPM == 2 && a.top_n[b] > 0 && a.top_ids[b] && a.top_lp[b];
-  float tv[GVL_MAX_TOP_LOGPROBS]; int ti[GVL_MAX_TOP_LOGPROBS];
-#pragma unroll
-  for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j) { tv[j] = -INFINITY; ti[j] = -1; }
-  float z = 0.f;
-  for (int i = tid; i < n; i += 1024) {
-    const float v = l[i];
-    if (smp_key(v) < thr) continue;
-    if constexpr (BAND) if (smp_key(v) > hi) continue;
-    z += expf((v - m) * inv_temp);
-    if (LPM == 2 && top && fabsf(v) < INFINITY) lp_insert(tv, ti, v, i);
-  }
-  const float lz = logf(smp_block_sum(z, shz));
-  if constexpr (LPM == 2) {
-    if (top) {
-      __shared__ float s_tv[16 * GVL_MAX_TOP_LOGPROBS];
-      __shared__ int s_ti[16 * GVL_MAX_TOP_LOGPROBS];
-      float wv[GVL_MAX_TOP_LOGPROBS]; int wi[GVL_MAX_TOP_LOGPROBS];
-      lp_wave_merge(tv, ti, wv, wi);
-      if ((tid & 63) == 0) {
-#pragma unroll
-        for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) { s_tv[(tid >> 6) * GVL_MAX_TOP_LOGPROBS + r] = wv[r]; s_ti[(tid >> 6) * GVL_MAX_TOP_LOGPROBS + r] = wi[r]; }
-      }
-      __syncthreads();
-      if (tid < 64) {
-        const int lane = tid;
-#pragma unroll
-        for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j) {
-          tv[j] = lane < 16 ? s_tv[lane * GVL_MAX_TOP_LOGPROBS + j] : -INFINITY; ti[j] = lane < 16 ? s_ti[lane * GVL_MAX_TOP_LOGPROBS + j] : -1;
-        }
-        lp_wave_merge(tv, ti, wv, wi);
-        float v = -INFINITY; int id = -1;
-#pragma unroll
-        for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) if (lane == r) { v = wv[r]; id = wi[r]; }
-        if (lane < GVL_MAX_TOP_LOGPROBS) {
-          const bool ok = lane < a.top_n[b] && id >= 0;
-          a.top_ids[b][(size_t)g * GVL_MAX_TOP_LOGPROBS + lane] = ok ? id : -1;
-          a.top_lp[b][(size_t)g * GVL_MAX_TOP_LOGPROBS + lane] = ok ? (v - m) * inv_temp - lz : -INFINITY;
-        }
-      }
-    }
-  }
-  return lz;
-}
-__device__ __forceinline__ bool lp_row_on(const ArgmaxArgs& a, int b) { return a.top_n[b] >= 0 && a.lp_lists[b] != nullptr; }
-__device__ __forceinline__ int lp_row_step(const ArgmaxArgs& a, int b) { return a.ngen_ptrs[b] ? *a.ngen_ptrs[b] : 0; }
-
-// greedy sampling: first index of the maximum (torch.argmax tie rule); one block per logit row
-template <int LPM>
-__global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a) {
-  __shared__ float bv[16];
-  __shared__ int bi[16];
-  const int b = blockIdx.x;
-  const float* logits = a.logits + (size_t)b * a.n;
-  float best = -3.4e38f; int idx = 0x7fffffff;
-  for (int i = threadIdx.x; i < a.n; i += 1024) {
-    const float v = logits[i];
-    if (v > best) { best = v; idx = i; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-  __syncthreads();
-  [[maybe_unused]] float lz = 0.f;
-  if constexpr (LPM > 0) {
-    if (lp_row_on(a, b)) {                   // every thread needs the row maximum: the same scan thread 0 makes below
-      float m = bv[0]; int mi = bi[0];
-      for (int w = 1; w < 16; ++w) if (bv[w] > m || (bv[w] == m && bi[w] < mi)) { m = bv[w]; mi = bi[w]; }
-      lz = lp_row_pass<LPM>(a, b, logits, m, 1.0f, 0u, lp_row_step(a, b));
-    }
-  }
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 16; ++w) if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-    *a.tok_ptrs[b] = idx;
-    if constexpr (LPM > 0) if (lp_row_on(a, b)) a.lp_lists[b][lp_row_step(a, b)] = 0.f - lz;   // s_tok - m = 0
-    if (a.ngen_ptrs[b]) {
-      const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
-      if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
-  }
-}
-// 0: no row wants log-probabilities (the launch is today's), 1: chosen tokens only, 2: some row wants its top N as well; -1: bad top_n
-static int lp_mode(const ArgmaxArgs& a) {
-  int mode = 0;
-  for (int b = 0; b < a.batch; ++b) {
-    if (a.top_n[b] > GVL_MAX_TOP_LOGPROBS) return -1;
-    if (a.top_n[b] < 0 || !a.lp_lists[b]) continue;
-    const int m = a.top_n[b] > 0 && a.top_ids[b] && a.top_lp[b] ? 2 : 1;
-    mode = m > mode ? m : mode;
-  }
-  return mode;
-}
-int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st) {
-  if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH) return -1;
-  switch (lp_mode(a)) {
-    case 0: hipLaunchKernelGGL(argmax_kernel<0>, dim3(a.batch), dim3(1024), 0, st, a); break;
-    case 1: hipLaunchKernelGGL(argmax_kernel<1>, dim3(a.batch), dim3(1024), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(argmax_kernel<2>, dim3(a.batch), dim3(1024), 0, st, a); break;
-    default: return -1;
-  }
-  return CHECK_LAUNCH();
-}
-// ---- sampling (do_sample=True): the reference forwards do_sample / temperature / top_p to HF generate (models/llava_next_video.py:655-661;
-// inference.py:45-49 defaults do_sample=True, T=0.2, top_p=None; HF's GenerationConfig adds top_k=50).  HF order [ext: transformers
-// generation/logits_process.py]: scores / T -> top-k (keep scores >= the k-th largest, ties kept) -> top-p (sorted ascending, drop while
-// the cumulative probability <= 1 - top_p, i.e. keep a token iff the mass of strictly larger scores is < top_p) -> softmax -> one draw.
-// The draw is Gumbel-max, token = argmax_i (l_i - max) / T - log(-log u_i), u_i = counter hash of (seed, stream, step, i): a sample of
-// exactly softmax(l / T) restricted to the kept set, with no sort and no prefix sum.  torch.multinomial's Philox stream cannot be
-// reproduced, so parity is: same kept set and same token as the CPU restatement `sample_token` used by the tests (same hash), and the right distribution.
-// One block per row; every pass re-reads the row from L2 (32 k - 128 k floats).  All reductions run in a fixed order and every
-// thread sees the same totals, so the thresholds are wave-uniform and the result does not depend on the batch a row travels in.
-template <int LPM>
-__global__ __launch_bounds__(1024) void sample_kernel(const ArgmaxArgs a) {
-  __shared__ float shf[16];
-  __shared__ int shi[16];
-  __shared__ int hist[256];
-  __shared__ unsigned s_sel[2];
-  const int b = blockIdx.x, tid = threadIdx.x, n = a.n;
-  const float* l = a.logits + (size_t)b * n;
-  // 1. row maximum
-  float m = -3.4e38f;
-  for (int i = tid; i < n; i += 1024) m = fmaxf(m, l[i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((tid & 63) == 0) shf[tid >> 6] = m;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 16; ++w) m = fmaxf(m, shf[w]);
-  // 2. top-k: key of the k-th largest score by an 8-bit radix select over the order-preserving keys (integer counts: exact)
-  unsigned kth = 0;
-  if (a.top_k > 0 && a.top_k < n) {
-    unsigned prefix = 0; int remaining = a.top_k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (tid < 256) hist[tid] = 0;
-      __syncthreads();
-      for (int i = tid; i < n; i += 1024) {
-        const unsigned k = smp_key(l[i]);
-        if (shift == 24 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int c = 0, bsel = 0;
-        for (int q = 255; q >= 0; --q) { if (c + hist[q] >= remaining) { bsel = q; break; } c += hist[q]; }
-        s_sel[0] = prefix | ((unsigned)bsel << shift); s_sel[1] = (unsigned)(remaining - c);
-      }
-      __syncthreads();
-      prefix = s_sel[0]; remaining = (int)s_sel[1];
-      __syncthreads();
-    }
-    kth = prefix;
-  }
-  // 3. normaliser of the kept scores
-  float z = 0.f;
-  for (int i = tid; i < n; i += 1024) { const float v = l[i]; if (smp_key(v) >= kth) z += expf((v - m) * a.inv_temp); }
-  const float Z = smp_block_sum(z, shf);
-  // 4. top-p: smallest key t such that the mass of keys > t is < top_p * Z (the maximum itself always qualifies: min_tokens_to_keep = 1)
-  unsigned thr = kth;
-  if (a.top_p > 0.f && a.top_p < 1.f) {
-    const float target = a.top_p * Z;
-    unsigned lo = kth, hi = smp_key(m);
-    while (lo < hi) {
-      const unsigned mid = lo + ((hi - lo) >> 1);
-      float s = 0.f;
-      for (int i = tid; i < n; i += 1024) { const float v = l[i]; if (smp_key(v) > mid) s += expf((v - m) * a.inv_temp); }
-      const float S = smp_block_sum(s, shf);
-      if (S < target) hi = mid; else lo = mid + 1;
-    }
-    thr = lo;
-  }
-  // 5. Gumbel-max draw over the kept set
-  const int step = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] : (a.step_override ? a.step_override[b] : 0);
-  const unsigned k0 = smp_fmix32(a.seed_lo ^ 0x9e3779b9u), k1 = smp_fmix32(a.seed_hi ^ k0 ^ 0x85ebca77u);
-  const unsigned kk = smp_fmix32(k1 ^ smp_fmix32(a.stream[b] * 0x9e3779b1u + 0x7f4a7c15u) ^ smp_fmix32((unsigned)step * 0x85ebca77u + 0x165667b1u));
-  const unsigned kk2 = smp_fmix32(kk + 0x632be5abu);
-  float best = -3.4e38f; int idx = 0x7fffffff;
-  for (int i = tid; i < n; i += 1024) {
-    const float v = l[i];
-    if (smp_key(v) < thr) continue;
-    const unsigned h = smp_fmix32(smp_fmix32((unsigned)i + kk) ^ kk2);
-    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float sc = (v - m) * a.inv_temp - logf(-logf(u));
-    if (sc > best) { best = sc; idx = i; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6] = idx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 16; ++w) if (shf[w] > best || (shf[w] == best && shi[w] < idx)) { best = shf[w]; idx = shi[w]; }
-    *a.tok_ptrs[b] = idx;
-    if (a.ngen_ptrs[b]) {
-      const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
-      if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
-  }
-  // log-probabilities, AFTER the selection (whose code is then the LPM = 0 kernel's, instruction for instruction): the normaliser and top N over
-  // the FINAL kept set, keys >= thr -- Z above is summed before top-p.  Thread 0's token / counter stores are visible to the block after the barrier.
-  if constexpr (LPM > 0) {
-    if (lp_row_on(a, b)) {
-      __syncthreads();
-      const int g = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] - 1 : 0;
-      const float lz = lp_row_pass<LPM>(a, b, l, m, a.inv_temp, thr, g);
-      if (tid == 0) { const int tok = *a.tok_ptrs[b]; a.lp_lists[b][g] = tok >= 0 && tok < n ? (l[tok] - m) * a.inv_temp - lz : -INFINITY; }
-    }
-  }
-}
-int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st) {
-  if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH || !(a.inv_temp > 0.f) || a.top_k < 0 || a.top_p < 0.f) return -1;
-  switch (lp_mode(a)) {
-    case 0: hipLaunchKernelGGL(sample_kernel<0>, dim3(a.batch), dim3(1024), 0, st, a); break;
-    case 1: hipLaunchKernelGGL(sample_kernel<1>, dim3(a.batch), dim3(1024), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(sample_kernel<2>, dim3(a.batch), dim3(1024), 0, st, a); break;
-    default: return -1;
-  }
-  return CHECK_LAUNCH();
-}
-// ---- per-row selection (SelRowsArgs): a decode group whose rows do not share one setting -- greedy rows next to sampled rows of different temperature / top-k / top-p /
-// seed -- or whose setting uses HF's further warpers (MinP, Typical, Epsilon, Eta; transformers generation/logits_process.py [ext]).  One block per row, the row's
-// parameters by value.  A greedy row runs argmax_kernel's code, a sampled row sample_kernel's up to top-p (same arithmetic, same reduction order: with the further warpers off
-// the token and log-probabilities are bit-identical to those kernels'), then, with e_i = exp((s_i - ref) / T), ref = the largest kept score, Z = sum of e over the kept set:
-//   min_p      keep e_i >= min_p                          (p_i >= min_p * p_max; p_max = 1 / Z)
-//   typical_p  xbar = sum(e x) / Z, x = (s - ref) / T; d_i = |x_i - xbar| (= |-log p_i - H|: -log p_i = log Z - x_i, H = log Z - xbar); t = the smallest d with
-//              mass{d_j <= t} >= typical_p * Z, by bisection on d's bit pattern (d >= 0: the bits order like the values); keep d_i <= t, ties at t included
-//   epsilon    keep e_i >= eps * Z, and the largest kept score
-//   eta        H = log Z - xbar over the current set, c = min(eta, sqrt(eta) exp(-H)); keep e_i >= c * Z, and the largest kept score
-// Scores are monotone in p, so every stage leaves an INTERVAL [lo, hi] of keys (typical_p alone may lower hi: it can drop the maximum); a stage is one fixed-order
-// sum pass plus one min / max pass over the keys that qualify.  min_tokens_to_keep = 1 throughout, as in sample_kernel.
-__device__ __forceinline__ float smp_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
-// min of lo / max of hi over the block, in every thread (integers: the order of the reduction cannot matter)
-__device__ __forceinline__ void smp_block_minmax(unsigned& lo, unsigned& hi, unsigned* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned ol = __shfl_xor(lo, o, 64), oh = __shfl_xor(hi, o, 64);
-    lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = lo; sh[16 + (threadIdx.x >> 6)] = hi; }
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 16; ++w) { lo = sh[w] < lo ? sh[w] : lo; hi = sh[16 + w] > hi ? sh[16 + w] : hi; }
-}
-template <int LPM>
-__global__ __launch_bounds__(1024) void select_rows_kernel(const SelRowsArgs sa) {
-  __shared__ float shf[16];
-  __shared__ int shi[16];
-  __shared__ int hist[256];
-  __shared__ unsigned s_sel[2];
-  __shared__ unsigned shk[32];
-  const ArgmaxArgs& a = sa.am;
-  const int b = blockIdx.x, tid = threadIdx.x, n = a.n;
-  const float* l = a.logits + (size_t)b * n;
-  if (!sa.row[b].on) {                       // ---- greedy row (block-uniform): argmax_kernel's code
-    float best = -3.4e38f; int idx = 0x7fffffff;
-    for (int i = tid; i < n; i += 1024) {
-      const float v = l[i];
-      if (v > best) { best = v; idx = i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
-      if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6] = idx; }
-    __syncthreads();
-    [[maybe_unused]] float lz = 0.f;
-    if constexpr (LPM > 0) {
-      if (lp_row_on(a, b)) {
-        float m = shf[0]; int mi = shi[0];
-        for (int w = 1; w < 16; ++w) if (shf[w] > m || (shf[w] == m && shi[w] < mi)) { m = shf[w]; mi = shi[w]; }
-        lz = lp_row_pass<LPM>(a, b, l, m, 1.0f, 0u, lp_row_step(a, b));
-      }
-    }
-    if (sa.kept) for (int i = tid; i < n; i += 1024) sa.kept[(size_t)b * n + i] = fabsf(l[i]) < INFINITY ? 1 : 0;
-    if (tid == 0) {
-      for (int w = 1; w < 16; ++w) if (shf[w] > best || (shf[w] == best && shi[w] < idx)) { best = shf[w]; idx = shi[w]; }
-      *a.tok_ptrs[b] = idx;
-      if constexpr (LPM > 0) if (lp_row_on(a, b)) a.lp_lists[b][lp_row_step(a, b)] = 0.f - lz;
-      if (a.ngen_ptrs[b]) {
-        const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
-        if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
-    }
-    return;
-  }
-  // ---- sampled row.  1 - 4: sample_kernel's row maximum, top-k radix select, normaliser and top-p bisection
-  const float iT = sa.row[b].inv_temp;
-  const int top_k = sa.row[b].top_k;
-  const float top_p = sa.row[b].top_p;
-  float m = -3.4e38f;
-  for (int i = tid; i < n; i += 1024) m = fmaxf(m, l[i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((tid & 63) == 0) shf[tid >> 6] = m;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 16; ++w) m = fmaxf(m, shf[w]);
-  unsigned kth = 0;
-  if (top_k > 0 && top_k < n) {
-    unsigned prefix = 0; int remaining = top_k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (tid < 256) hist[tid] = 0;
-      __syncthreads();
-      for (int i = tid; i < n; i += 1024) {
-        const unsigned k = smp_key(l[i]);
-        if (shift == 24 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int c = 0, bsel = 0;
-        for (int q = 255; q >= 0; --q) { if (c + hist[q] >= remaining) { bsel = q; break; } c += hist[q]; }
-        s_sel[0] = prefix | ((unsigned)bsel << shift); s_sel[1] = (unsigned)(remaining - c);
-      }
-      __syncthreads();
-      prefix = s_sel[0]; remaining = (int)s_sel[1];
-      __syncthreads();
-    }
-    kth = prefix;
-  }
-  unsigned lo = kth, hi = smp_key(m);
-  if (top_p > 0.f && top_p < 1.f) {
-    float z = 0.f;
-    for (int i = tid; i < n; i += 1024) { const float v = l[i]; if (smp_key(v) >= kth) z += expf((v - m) * iT); }
-    const float Z = smp_block_sum(z, shf);
-    const float target = top_p * Z;
-    unsigned blo = kth, bhi = smp_key(m);
-    while (blo < bhi) {
-      const unsigned mid = blo + ((bhi - blo) >> 1);
-      float s = 0.f;
-      for (int i = tid; i < n; i += 1024) { const float v = l[i]; if (smp_key(v) > mid) s += expf((v - m) * iT); }
-      const float S = smp_block_sum(s, shf);
-      if (S < target) bhi = mid; else blo = mid + 1;
-    }
-    lo = blo;
-  }
-  // ---- the further warpers on the interval [lo, hi]; ref = the largest kept score (the row maximum until typical_p drops it)
-  float ref = m;
-  // Z = sum of e, S1 = sum of e * x over the current set, fixed order (-inf entries: e = 0, left out of S1)
-  auto set_sums = [&](float& Z, float& S1) {
-    float z = 0.f, s1 = 0.f;
-    for (int i = tid; i < n; i += 1024) {
-      const float v = l[i]; const unsigned k = smp_key(v);
-      if (k < lo || k > hi) continue;
-      const float x = (v - ref) * iT, e = expf(x);
-      z += e; if (x > -INFINITY) s1 += e * x;
-    }
-    Z = smp_block_sum(z, shf); S1 = smp_block_sum(s1, shf);
-  };
-  // lo <- the smallest key of the current set with e >= cut (the largest kept score always stays)
-  auto raise_lo = [&](float cut) {
-    unsigned kl = hi, kh = 0u;
-    for (int i = tid; i < n; i += 1024) {
-      const float v = l[i]; const unsigned k = smp_key(v);
-      if (k < lo || k > hi) continue;
-      if (expf((v - ref) * iT) >= cut && k < kl) kl = k;
-    }
-    smp_block_minmax(kl, kh, shk);
-    lo = kl;
-  };
-  const float min_p = sa.row[b].min_p, typ = sa.row[b].typical_p, eps = sa.row[b].eps, eta = sa.row[b].eta;
-  if (min_p > 0.f) raise_lo(min_p);
-  if (typ > 0.f && typ < 1.f) {
-    float Z, S1; set_sums(Z, S1);
-    const float xbar = S1 / Z, target = typ * Z;
-    unsigned dl = 0u, dh = 0x7f800000u;
-    while (dl < dh) {
-      const unsigned mid = dl + ((dh - dl) >> 1);
-      float s = 0.f;
-      for (int i = tid; i < n; i += 1024) {
-        const float v = l[i]; const unsigned k = smp_key(v);
-        if (k < lo || k > hi) continue;
-        const float x = (v - ref) * iT;
-        if (__float_as_uint(fabsf(x - xbar)) <= mid) s += expf(x);
-      }
-      const float S = smp_block_sum(s, shf);
-      if (S >= target) dh = mid; else dl = mid + 1;
-    }
-    unsigned kl = 0xffffffffu, kh = 0u;
-    for (int i = tid; i < n; i += 1024) {
-      const float v = l[i]; const unsigned k = smp_key(v);
-      if (k < lo || k > hi) continue;
-      if (__float_as_uint(fabsf((v - ref) * iT - xbar)) <= dl) { kl = k < kl ? k : kl; kh = k > kh ? k : kh; }
-    }
-    smp_block_minmax(kl, kh, shk);
-    if (kl <= kh) { lo = kl; hi = kh; ref = smp_unkey(hi); }     // (an all-NaN band cannot empty the set)
-  }
-  if (eps > 0.f) { float Z, S1; set_sums(Z, S1); raise_lo(eps * Z); }
-  if (eta > 0.f) {
-    float Z, S1; set_sums(Z, S1);
-    const float H = logf(Z) - S1 / Z;
-    raise_lo(fminf(eta, sqrtf(eta) * expf(-H)) * Z);
-  }
-  // ---- Gumbel-max draw over [lo, hi]: sample_kernel's hash and score, the row's own seed and stream
-  const int step = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] : (a.step_override ? a.step_override[b] : 0);
-  const unsigned k0 = smp_fmix32(sa.row[b].seed_lo ^ 0x9e3779b9u), k1 = smp_fmix32(sa.row[b].seed_hi ^ k0 ^ 0x85ebca77u);
-  const unsigned kk = smp_fmix32(k1 ^ smp_fmix32(sa.row[b].stream * 0x9e3779b1u + 0x7f4a7c15u) ^ smp_fmix32((unsigned)step * 0x85ebca77u + 0x165667b1u));
-  const unsigned kk2 = smp_fmix32(kk + 0x632be5abu);
-  float best = -3.4e38f; int idx = 0x7fffffff;
-  for (int i = tid; i < n; i += 1024) {
-    const float v = l[i]; const unsigned k = smp_key(v);
-    if (k < lo || k > hi) continue;
-    const unsigned h = smp_fmix32(smp_fmix32((unsigned)i + kk) ^ kk2);
-    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float sc = (v - ref) * iT - logf(-logf(u));
-    if (sc > best) { best = sc; idx = i; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6] = idx; }
-  __syncthreads();
-  if (sa.kept) for (int i = tid; i < n; i += 1024) { const float v = l[i]; const unsigned k = smp_key(v); sa.kept[(size_t)b * n + i] = k >= lo && k <= hi && fabsf(v) < INFINITY ? 1 : 0; }
-  if (tid == 0) {
-    for (int w = 1; w < 16; ++w) if (shf[w] > best || (shf[w] == best && shi[w] < idx)) { best = shf[w]; idx = shi[w]; }
-    *a.tok_ptrs[b] = idx;
-    if (a.ngen_ptrs[b]) {
-      const int g = *a.ngen_ptrs[b]; if (a.out_lists[b]) a.out_lists[b][g] = idx; *a.ngen_ptrs[b] = g + 1;
-      if (a.eos_flags[b] && idx == a.eos_id && *a.eos_flags[b] == 0) __hip_atomic_store(a.eos_flags[b], g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (a.pos_ptrs[b]) (*a.pos_ptrs[b])++;
-  }
-  if constexpr (LPM > 0) {                   // after the selection, over the FINAL kept set (sample_kernel's order)
-    if (lp_row_on(a, b)) {
-      __syncthreads();
-      const int g = a.ngen_ptrs[b] ? *a.ngen_ptrs[b] - 1 : 0;
-      const float lz = lp_row_pass<LPM, true>(a, b, l, ref, iT, lo, g, hi);
-      if (tid == 0) { const int tok = *a.tok_ptrs[b]; a.lp_lists[b][g] = tok >= 0 && tok < n ? (l[tok] - ref) * iT - lz : -INFINITY; }
-    }
-  }
-}
-int gvl_launch_select_rows(const SelRowsArgs& sa, hipStream_t st) {
-  const ArgmaxArgs& a = sa.am;
-  if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH) return -1;
-  for (int b = 0; b < a.batch; ++b) {
-    const SelRow& r = sa.row[b];
-    if (r.on && (!(r.inv_temp > 0.f) || r.top_k < 0 || !(r.top_p >= 0.f) || !(r.min_p >= 0.f) || !(r.typical_p >= 0.f) || !(r.eps >= 0.f) || !(r.eta >= 0.f))) return -1;
-  }
-  switch (lp_mode(a)) {
-    case 0: hipLaunchKernelGGL(select_rows_kernel<0>, dim3(a.batch), dim3(1024), 0, st, sa); break;
-    case 1: hipLaunchKernelGGL(select_rows_kernel<1>, dim3(a.batch), dim3(1024), 0, st, sa); break;
-    case 2: hipLaunchKernelGGL(select_rows_kernel<2>, dim3(a.batch), dim3(1024), 0, st, sa); break;
-    default: return -1;
-  }
-  return CHECK_LAUNCH();
-}
-// ---- beam search: the 2k candidates of one step (BeamCandArgs; HF _beam_search [ext]: log-softmax -> processors -> + beam score -> top-2k over the k x vocab grid).
-// Two launches; the kernel boundary is the only hand-off between workgroups.
-//   beam_rows_kernel<NORM>   one block per running beam.  NORM: the row holds raw logits; m = its maximum, lz = logf(sum exp(l - m)) summed strided per thread and
-//                            finished with smp_block_sum -- the quantity lp_row_pass<1> computes, so lp = (l - m) - lz is bit for bit what greedy selection reports for
-//                            the token.  !NORM: the row holds processed log-probabilities already (beam_normalize_kernel, then the logits processors).  The candidate
-//                            value is t = lp + score[b], ONE fp32 add, and the selection runs on t, not on lp: distinct lp can collide after the add (at a score of
-//                            -1e9 every entry does).  Order: the strict total order (t descending, index ascending) over ALL entries, -inf included.  The key of the
-//                            2k-th largest t comes from the sampler's 8-bit radix select over smp_key(t) (integer counts: exact); the entries above it are taken, and
-//                            of the ties AT it the lowest indices -- when there are more ties than places a second radix select, over ~index among the ties, finds
-//                            the last index taken.  The <= 32 survivors are ordered by counting in LDS and stored as (t, token, lp).
-//   beam_merge_kernel        one wave: the best 2k of the k x 2k row survivors in the same order -- an entry's rank = the sum over the (sorted) rows of how many of
-//                            their entries beat it, a binary search per row; flat index = beam * n + token.
-//   beam_normalize_kernel    the NORM arithmetic alone, in place (when processors or token rules sit between the log-softmax and the beam scores): normalize followed by
-//                            beam_rows_kernel<false> is bit-identical to beam_rows_kernel<true>.
-// Keys, not float compares, order everything: every count is an integer and every store index is bounded whatever the row holds (NaN rows are outside the contract: their
-// order is the keys', not IEEE's).  t + 0.0f folds -0.0 onto +0.0 before the key is taken, so the two compare equal as floats do.
-__device__ __forceinline__ unsigned beam_key(float t) { return smp_key(t + 0.0f); }
-template <bool NORM> __device__ __forceinline__ float beam_lp(float l, float m, float lz) { if constexpr (NORM) return __fsub_rn(__fsub_rn(l, m), lz); else return l; }
-// row maximum and log of the normaliser, in every thread (sample_kernel's maximum, lp_row_pass's sum: fixed order, a pure function of the row)
-__device__ __forceinline__ void beam_row_norm(const float* l, int n, float* shf, float& m, float& lz) {
-  const int tid = threadIdx.x;
-  float best = -3.4e38f;
-  for (int i = tid; i < n; i += 1024) best = fmaxf(best, l[i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
-  if ((tid & 63) == 0) shf[tid >> 6] = best;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 16; ++w) best = fmaxf(best, shf[w]);
-  m = best;
-  float z = 0.f;
-  for (int i = tid; i < n; i += 1024) z += expf((l[i] - m) * 1.0f);
-  lz = logf(smp_block_sum(z, shf));
-}
-// Whole block: the key of the `want`-th largest of the keys keyf hands out for i in [0, n) (keyf returns false for an entry outside the set), `take` = how many entries AT
-// that key belong to the best `want`, `ties` = how many entries hold it.  sel: three words of LDS.
-template <class F>
-__device__ __forceinline__ void beam_radix_select(int n, int want, F keyf, int* hist, unsigned* sel, unsigned& kth, int& take, int& ties) {
-  const int tid = threadIdx.x;
-  unsigned prefix = 0; int remaining = want;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) {
-      unsigned k;
-      if (!keyf(i, k)) continue;
-      if (shift == 24 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int c = 0, bsel = 0;
-      for (int q = 255; q >= 0; --q) { if (c + hist[q] >= remaining) { bsel = q; break; } c += hist[q]; }
-      sel[0] = prefix | ((unsigned)bsel << shift); sel[1] = (unsigned)(remaining - c); sel[2] = (unsigned)hist[bsel];
-    }
-    __syncthreads();
-    prefix = sel[0]; remaining = (int)sel[1]; ties = (int)sel[2];
-    __syncthreads();
-  }
-  kth = prefix; take = remaining;
-}
-constexpr int GVL_BEAM_MAX_CAND = 2 * GVL_MAX_DECODE_BATCH;
-template <bool NORM>
-__global__ __launch_bounds__(1024) void beam_rows_kernel(const BeamCandArgs a) {
-  __shared__ float shf[16];
-  __shared__ int hist[256];
-  __shared__ unsigned s_sel[3];
-  __shared__ float c_t[GVL_BEAM_MAX_CAND], c_lp[GVL_BEAM_MAX_CAND];
-  __shared__ int c_i[GVL_BEAM_MAX_CAND];
-  __shared__ int s_cnt;
-  const int b = blockIdx.x, tid = threadIdx.x, n = a.n, K2 = 2 * a.k;
-  const float* l = a.rows + (size_t)b * (size_t)a.row_stride;
-  const float sc = a.scores[b];
-  float m = 0.f, lz = 0.f;
-  if constexpr (NORM) beam_row_norm(l, n, shf, m, lz);
-  unsigned kth, ikey = 0; int take, ties;
-  beam_radix_select(n, K2, [&](int i, unsigned& k) { k = beam_key(__fadd_rn(beam_lp<NORM>(l[i], m, lz), sc)); return true; }, hist, s_sel, kth, take, ties);
-  if (ties > take) {                         // block-uniform: more entries at the 2k-th key than places -> the lowest indices among them
-    int t2, n2;
-    beam_radix_select(n, take, [&](int i, unsigned& k) { k = ~(unsigned)i; return beam_key(__fadd_rn(beam_lp<NORM>(l[i], m, lz), sc)) == kth; }, hist, s_sel, ikey, t2, n2);
-  }
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  for (int i = tid; i < n; i += 1024) {
-    const float lp = beam_lp<NORM>(l[i], m, lz), t = __fadd_rn(lp, sc);
-    const unsigned k = beam_key(t);
-    if (k > kth || (k == kth && ~(unsigned)i >= ikey)) {
-      const int s = atomicAdd(&s_cnt, 1);
-      if (s < GVL_BEAM_MAX_CAND) { c_t[s] = t; c_lp[s] = lp; c_i[s] = i; }
-    }
-  }
-  __syncthreads();
-  const int cnt = s_cnt < K2 ? s_cnt : K2;   // == K2: integer counts
-  if (tid < cnt) {
-    const unsigned mk = beam_key(c_t[tid]); const int mi = c_i[tid];
-    int rank = 0;
-    for (int j = 0; j < cnt; ++j) { const unsigned kj = beam_key(c_t[j]); rank += (kj > mk || (kj == mk && c_i[j] < mi)) ? 1 : 0; }
-    const size_t o = (size_t)b * K2 + rank;
-    a.row_v[o] = c_t[tid]; a.row_i[o] = mi; a.row_lp[o] = c_lp[tid];
-  }
-}
-__global__ __launch_bounds__(64) void beam_merge_kernel(const BeamCandArgs a) {
-  __shared__ unsigned mk[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
-  __shared__ int mi[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
-  const int lane = threadIdx.x, K2 = 2 * a.k, total = a.k * K2;
-  for (int e = lane; e < total; e += 64) { mk[e] = beam_key(a.row_v[e]); mi[e] = (e / K2) * a.n + a.row_i[e]; }
-  __syncthreads();
-  for (int e = lane; e < total; e += 64) {
-    const unsigned ke = mk[e]; const int ie = mi[e];
-    int rank = 0;
-    for (int r = 0; r < a.k; ++r) {          // a row's survivors are sorted in this very order: those better than e are a prefix of the row -> binary search
-      const int base = r * K2;
-      int lo = 0, hi = K2;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (mk[base + mid] > ke || (mk[base + mid] == ke && mi[base + mid] < ie)) lo = mid + 1; else hi = mid;
-      }
-      rank += lo;
-    }
-    if (rank < K2) { a.vals[rank] = a.row_v[e]; a.idx[rank] = ie; a.proc[rank] = a.row_lp[e]; }
-  }
-}
-__global__ __launch_bounds__(1024) void beam_normalize_kernel(float* rows, int n) {
-  __shared__ float shf[16];
-  float* l = rows + (size_t)blockIdx.x * n;
-  float m, lz;
-  beam_row_norm(l, n, shf, m, lz);           // every thread has read the entries it is about to overwrite, and the block sum is behind its barriers
-  for (int i = threadIdx.x; i < n; i += 1024) l[i] = beam_lp<true>(l[i], m, lz);
-}
-static bool beam_shape_ok(int n, int k) { return k >= 2 && k <= GVL_MAX_DECODE_BATCH && n >= 2 * k && (long long)n * k <= 0x7fffffffLL; }
-int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st) {
-  if (!beam_shape_ok(a.n, a.k) || !a.rows || a.row_stride < 0 || !a.row_v || !a.row_i || !a.row_lp || !a.vals || !a.idx || !a.proc) return -1;
-  if (a.norm) hipLaunchKernelGGL(beam_rows_kernel<true>, dim3(a.k), dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL(beam_rows_kernel<false>, dim3(a.k), dim3(1024), 0, st, a);
-  hipLaunchKernelGGL(beam_merge_kernel, dim3(1), dim3(64), 0, st, a);
-  return CHECK_LAUNCH();
-}
-int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st) {
-  if (!rows || n < 1 || k < 1 || k > GVL_MAX_DECODE_BATCH) return -1;
-  hipLaunchKernelGGL(beam_normalize_kernel, dim3(k), dim3(1024), 0, st, rows, n);
-  return CHECK_LAUNCH();
-}
 __global__ void gather_tok_rows_kernel(const bf16_t* __restrict__ table, const TokPtrs toks, bf16_t* __restrict__ dst, int cols) {
   const int r = blockIdx.y;
   const int tok = *toks.p[r];

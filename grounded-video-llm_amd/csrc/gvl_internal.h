@@ -369,7 +369,7 @@ struct ArgmaxArgs { const float* logits; int n, batch; int* tok_ptrs[GVL_MAX_DEC
 constexpr int GVL_MAX_TOP_LOGPROBS = 8;
 int gvl_launch_argmax(const ArgmaxArgs& a, hipStream_t st);
 int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
-// Per-row selection (select_rows_kernel, gvl_elem.hip): every row of one launch is greedy (on = 0) or sampled with its OWN settings, seed and stream.  A sampled row runs HF's
+// Per-row selection (select_rows_kernel, gvl_pick.hip): every row of one launch is greedy (on = 0) or sampled with its OWN settings, seed and stream.  A sampled row runs HF's
 // warpers in HF's order -- scores / T -> top-k -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff (0 = off each; top_p / typical_p also off at 1) -> one Gumbel-max
 // draw -- each stage's softmax over what the stage before left.  The kept set is an interval [lo, hi] of smp_key() keys after every stage.  `am` carries the rows'
 // pointers and log-probability outputs with ArgmaxArgs' meaning; its inv_temp / top_k / top_p / seed / stream fields are not read.  kept (operator tests, may be null):
@@ -377,7 +377,7 @@ int gvl_launch_sample(const ArgmaxArgs& a, hipStream_t st);
 struct SelRow { int on; float inv_temp; int top_k; float top_p, min_p, typical_p, eps, eta; unsigned seed_lo, seed_hi, stream; };
 struct SelRowsArgs { ArgmaxArgs am; SelRow row[GVL_MAX_DECODE_BATCH]; unsigned char* kept; };
 int gvl_launch_select_rows(const SelRowsArgs& a, hipStream_t st);
-// Beam search, one step's candidates (beam_rows_kernel + beam_merge_kernel, gvl_elem.hip): rows [k] of n fp32 entries, row b at rows + b * row_stride (0: every beam reads
+// Beam search, one step's candidates (beam_rows_kernel + beam_merge_kernel, gvl_pick.hip): rows [k] of n fp32 entries, row b at rows + b * row_stride (0: every beam reads
 // row 0 -- the first step); norm != 0: raw logits, log-softmax inside; 0: processed log-probabilities.  row_* [k][2k]: device scratch between the two launches.  vals / idx /
 // proc [2k]: the best 2k of the k x n grid in the order (value descending, flat index beam * n + token ascending) -- value = fp32(log-prob + scores[beam]), proc = the log-prob.
 struct BeamCandArgs { const float* rows; int n, k, row_stride, norm; float scores[GVL_MAX_DECODE_BATCH]; float* row_v; int* row_i; float* row_lp; float* vals; int* idx; float* proc; };

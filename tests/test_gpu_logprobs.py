@@ -1,4 +1,4 @@
-"""-m gpu: log-probabilities of the selected tokens (argmax_kernel / sample_kernel with a logprob mode, csrc/gvl_elem.hip): the operator against fp64
+"""-m gpu: log-probabilities of the selected tokens (argmax_kernel / sample_kernel with a logprob mode, csrc/gvl_pick.hip): the operator against fp64
 log_softmax of the (warped) row, tokens unchanged by the mode, and every decode path (graph replay, batch, scheduler, shared prefix) giving the
 same lists bit for bit, each entry matching the teacher-forced row."""
 import math

@@ -1,4 +1,4 @@
-"""-m gpu: the per-row selection kernel (select_rows_kernel, csrc/gvl_elem.hip) through gvl_op_select_rows: every row of a launch has its own setting, some
+"""-m gpu: the per-row selection kernel (select_rows_kernel, csrc/gvl_pick.hip) through gvl_op_select_rows: every row of a launch has its own setting, some
 greedy, the sampled ones running HF's warpers temperature -> top-k -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff.  Against the fp64
 restatement tests/warpers_ref.py (pinned to transformers by test_warpers_cpu.py): the kept set exactly, the drawn token, the log-probabilities and top
 lists; bit identity with today's kernels for greedy rows and for sampled rows without the new warpers; bad arguments.

@@ -1,4 +1,4 @@
-"""fp64 restatement of a sampled token selection (select_rows_kernel, csrc/gvl_elem.hip): the seven stages in HF's order -- scores / T -> top-k -> top-p ->
+"""fp64 restatement of a sampled token selection (select_rows_kernel, csrc/gvl_pick.hip): the seven stages in HF's order -- scores / T -> top-k -> top-p ->
 min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -- each stage's softmax over what the stage before left, and the Gumbel-max draw over the final kept set.
 Pinned against the installed transformers' warper classes by test_warpers_cpu.py; the GPU tests compare the kernel with it.  Besides the kept set it reports,
 per stage, how far the row's entries are from the stage's cut, so that a test can place its cuts where fp32 rounding cannot move them.

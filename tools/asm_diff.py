@@ -6,22 +6,30 @@ without a GPU.  Listing recipe: hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllv
 import re
 import sys
 
+PADDING = ("s_nop", "s_code_end")          # what the assembler may put between the last instruction and .Lfunc_end<N>
+
 
 def kernels(path, key):
     out, cur, buf = {}, None, []
     for line in open(path):
         m = re.match(r"^(_Z\w+):", line)
+        if m and cur:
+            raise SystemExit(f"{path}: {cur} has no .Lfunc_end label before {m.group(1)} (truncated listing?)")
         if m and key in m.group(1):
             cur, buf = m.group(1), []
             continue
         if cur:
-            if "s_endpgm" in line:
+            if re.match(r"^\.Lfunc_end\d+:", line):          # the whole body: a kernel with an early exit has more than one s_endpgm
+                while buf and buf[-1].split()[0] in PADDING:
+                    buf.pop()
                 out[cur] = buf
                 cur = None
             else:
                 t = re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r";.*", "", line).strip())
                 if t and not t.startswith("."):
                     buf.append(t)
+    if cur:
+        raise SystemExit(f"{path}: {cur} has no .Lfunc_end label (truncated listing?)")
     return out
 
 

@@ -1,4 +1,4 @@
-"""Decode step time with log-probabilities off / chosen token only / top-8 (argmax_kernel's logprob modes, csrc/gvl_elem.hip): full-width Phi-3.5
+"""Decode step time with log-probabilities off / chosen token only / top-8 (argmax_kernel's logprob modes, csrc/gvl_pick.hip): full-width Phi-3.5
 (synthetic weights), the bench's decode context (3.5 k tokens at the measured steps), groups of B = 1 and 8 sequences; the three modes rotate
 within one process (same box, same engine, same sequences), timed with device events around graph-replayed decode calls (gvl_decode_greedy_batch).
   python tools/decode_logprobs_ab.py [--reps 4] [--steps 32] [--batches 1,8]"""

@@ -1,5 +1,5 @@
 """Time of one token-selection launch on a 16 x 32064 group of fp32 rows (the Phi-3.5 vocabulary, the decode group size): sample_kernel at T / top-k / top-p
-(gvl_op_sample) against the per-row kernel select_rows_kernel (gvl_op_select_rows; csrc/gvl_elem.hip) with the same T / k / p per row and with every warper on
+(gvl_op_sample) against the per-row kernel select_rows_kernel (gvl_op_select_rows; csrc/gvl_pick.hip) with the same T / k / p per row and with every warper on
 (min_p, typical_p, epsilon_cutoff, eta_cutoff as well), and a half-greedy group.  The variants rotate within one process (same box, same rows), each timed with
 device events around `--iters` back-to-back launches, `--reps` times; the output is one JSON line with the per-launch microseconds of every repetition.
 A record only: token selection is one launch per decode step (bench.py decodes greedily and never reaches these kernels).
