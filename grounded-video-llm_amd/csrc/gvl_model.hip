@@ -868,6 +868,90 @@ int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float
   if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, "gvl_op_dgemm: launch failed");
   return 0;
 }
+// operator-level entry for the WHOLE GemvArgs surface (tests/test_gpu_decode_proj.py): row-major operands in, private tiled / quantised copies made here, every launcher
+// refusal returned as GVL_ERR_ARG before anything is written.  See include/gvl.h for the fields.
+int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: null descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const char* bad = nullptr;
+  const int N = p->N, K = p->K, B = p->batch;
+  if (N <= 0 || K <= 0 || !p->W || !p->x) bad = "N, K > 0 and W, x set";
+  else if (B < 1 || B > GVL_MAX_DECODE_BATCH) bad = "1 <= batch <= 16";
+  else if (p->path < 0 || p->path > 1 || p->w_fmt < 0 || p->w_fmt > 2) bad = "path 0 / 1, w_fmt 0 / 1 / 2";
+  else if (K % (p->path == 0 ? 32 : 8)) bad = "K % 32 == 0 (tile order; the VALU GEMV: K % 8 == 0)";
+  else if (p->act != GVL_ACT_NONE && p->act != GVL_ACT_SILU_MUL) bad = "act is NONE or SILU_MUL";
+  else if (p->x_is_tiled && (p->norm_w || p->path == 1)) bad = "a tiled x feeds the skinny GEMM without norm_w only";
+  else if (p->path == 1 && (p->variant || p->w_fmt || p->out_tiled || p->sq_in || p->sq_out || p->out_tiled2)) bad = "the VALU GEMV has no variants, quantised weights, tiled outputs or fused-norm sums";
+  else if (p->out_stride < 0 || (p->out_stride && p->out_stride < (p->act == GVL_ACT_SILU_MUL ? N / 2 : N))) bad = "out_stride >= the output row length";
+  else if (!p->rope_on && !p->out_bf16 && !p->out_f32) bad = "an output buffer";
+  else if (p->path == 0 && B > 1 && !p->rope_on && (p->out_f32 || p->resid || (p->out_bf16 && !p->out_tiled)) && (p->out_stride ? p->out_stride : (p->act == GVL_ACT_SILU_MUL ? N / 2 : N)) % 4) bad = "out_stride % 4 == 0 for batch > 1 (8- and 16-byte epilogue stores)";
+  else if (p->rope_on) {
+    if (p->H < 1 || p->KV < 1 || p->Dr < 2 || (p->Dr & 1) || p->D < p->Dr || (long)N != (long)(p->H + 2 * p->KV) * p->Dr) bad = "rope: Dr even, D >= Dr, N == (H + 2 KV) Dr";
+    else if (!p->cos_s || !p->sin_s || !p->pos || !p->tables || !p->Q || !p->Kt || !p->Vt) bad = "rope: tables, pos, page tables, Q, Kt, Vt set";
+    else if (p->rope_switch > 0 && (!p->cos_l || !p->sin_l)) bad = "rope: long tables set when rope_switch > 0";
+    else if (p->max_pos < 1 || p->n_pages < 1 || p->table_stride < 1 || p->q_stride < p->H * p->D) bad = "rope: max_pos, n_pages, table_stride >= 1, q_stride >= H D";
+    else if (p->act || p->bias || p->resid) bad = "rope: no other epilogue";
+  }
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_decode_proj: ") + bad);
+  if (p->rope_on) {                                // the kernel trusts positions and page numbers: check them here, on the host
+    std::vector<int> pos(B), tab((size_t)B * p->table_stride);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpy(pos.data(), p->pos, sizeof(int) * B, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(tab.data(), p->tables, sizeof(int) * tab.size(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) {
+      if (pos[b] < 0 || pos[b] >= p->max_pos || (pos[b] >> 6) >= p->table_stride) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: position outside the tables");
+      const int page = tab[(size_t)b * p->table_stride + (pos[b] >> 6)];
+      if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: page outside the pools");
+    }
+  }
+  struct Bufs { void* v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Bufs() { for (void* q : v) if (q) hipFree(q); } } bufs;
+  void *&wc = bufs.v[0], *&wt = bufs.v[1], *&ws = bufs.v[2], *&xt = bufs.v[3];
+  const size_t nb16 = (size_t)((N + 15) / 16);
+  const int Dr = p->rope_on ? p->Dr : 0, nqk = p->rope_on ? p->H + p->KV : 0;
+  GemvArgs g; memset(&g, 0, sizeof(g));
+  int rc = 0;
+  if (p->path == 0) {
+    if (p->w_fmt) {                                // the quantisers rewrite their row-major source: work on a copy
+      if (K % (p->w_fmt == 2 ? 1024 : 512)) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: FP8 needs K % 512 == 0, MXFP4 K % 1024 == 0");
+      HIPCHK(ctx, hipMalloc(&wc, (size_t)N * K * 2));
+      HIPCHK(ctx, hipMemcpyAsync(wc, p->W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st));
+      HIPCHK(ctx, hipMalloc(&wt, nb16 * 16 * K));
+      HIPCHK(ctx, hipMalloc(&ws, p->w_fmt == 1 ? (size_t)N * 4 : nb16 * (K / 128) * 16 * 4));
+      rc = p->w_fmt == 1 ? gvl_fp8_quantise_decode_weight((bf16_t*)wc, (unsigned char*)wt, (float*)ws, N, K, Dr, nqk, st)
+                         : gvl_mxfp4_quantise_decode_weight((bf16_t*)wc, (unsigned char*)wt, (unsigned*)ws, N, K, Dr, nqk, st);
+      g.wscale = (const float*)ws;
+    } else {
+      HIPCHK(ctx, hipMalloc(&wt, nb16 * 16 * K * 2));
+      rc = gvl_retile_decode_weight(p->W, (bf16_t*)wt, N, K, Dr, nqk, st);
+    }
+    g.W = (const bf16_t*)wt; g.w_fp8 = p->w_fmt;
+    if (!rc && !p->x_is_tiled && !p->norm_w) {
+      HIPCHK(ctx, hipMalloc(&xt, (size_t)16 * K * 2));
+      HIPCHK(ctx, hipMemsetAsync(xt, 0, (size_t)16 * K * 2, st));
+      rc = gvl_launch_rows_to_tiled(p->x, (bf16_t*)xt, B, K, K, st);
+      g.x = (const bf16_t*)xt;
+    } else g.x = p->x;
+  } else { g.W = p->W; g.x = p->x; }
+  g.N = N; g.K = K; g.batch = B; g.x_stride = K;
+  g.out_stride = p->out_stride ? p->out_stride : (p->act == GVL_ACT_SILU_MUL ? N / 2 : N);
+  g.norm_w = p->norm_w; g.eps = p->eps; g.bias = p->bias; g.resid = p->resid; g.act = p->act; g.out_bf16 = p->out_bf16; g.out_f32 = p->out_f32;
+  g.variant = p->variant; g.out_tiled = p->out_tiled; g.sq_in = p->sq_in; g.sq_n = p->sq_n; g.sq_out = p->sq_out; g.out_tiled2 = p->out_tiled2;
+  if (p->rope_on) {
+    g.rope_on = 1; g.cos_s = p->cos_s; g.sin_s = p->sin_s; g.cos_l = p->cos_l; g.sin_l = p->sin_l; g.rope_switch = p->rope_switch;
+    for (int b = 0; b < B; ++b) { g.pos_ptrs[b] = p->pos + b; g.tables[b] = p->tables + (size_t)b * p->table_stride; }
+    g.Q = p->Q; g.Kt = p->Kt; g.Vt = p->Vt; g.H = p->H; g.KV = p->KV; g.Dr = p->Dr; g.D = p->D; g.q_stride = p->q_stride;
+  }
+  if (!rc) { ProfScope _ps(ctx, GVL_PROF_GEMV, 2.0 * N * K, st); rc = p->path == 0 ? gvl_launch_dgemm(g, st) : gvl_launch_gemv(g, st); }
+  if (!rc && p->w_fmt) {                           // read back what the quantiser left, only once the launcher has accepted the call
+    if (p->w_deq) HIPCHK(ctx, hipMemcpyAsync(p->w_deq, wc, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st));
+    if (p->w_scale) HIPCHK(ctx, hipMemcpyAsync(p->w_scale, ws, p->w_fmt == 1 ? (size_t)N * 4 : nb16 * (K / 128) * 16 * 4, hipMemcpyDeviceToDevice, st));
+  }
+  const hipError_t se = hipStreamSynchronize(st);
+  if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, rc == -1 ? "gvl_op_decode_proj: the launcher does not serve this combination" : "gvl_op_decode_proj: launch failed");
+  if (se != hipSuccess) return gvl_hipfail(ctx, se, "gvl_op_decode_proj: hipStreamSynchronize");
+  return 0;
+}
 // micro-benchmark of the decode projection kernels on synthetic operands (tools/decode_bench.py): mode 0 = skinny MFMA GEMM (variant:
 // see gvl_launch_dgemm), 1 = round-1 VALU GEMV (batch 1, 2, 4), 2 / 3 = the same two with the fused RMSNorm prologue (batch <= 4).  `rounds` distinct weight matrices are cycled so that the
 // Infinity Cache cannot hold the stream; returns the average microseconds per launch.

@@ -729,6 +729,29 @@ class Engine:
         self._chk(self.lib.gvl_op_dgemm(self.ctx, _ptr(W.contiguous()), _ptr(x.contiguous()), _ptr(bias), _ptr(y), N, K, B, self.stream), "gvl_op_dgemm")
         return y
 
+    def op_decode_proj(self, W, x, **kw):
+        """gvl_op_decode_proj (include/gvl.h): one decode projection with any prologue / epilogue.  W bf16 [N, K], x bf16 [B, K] (or the tiled
+        stream with x_is_tiled=1); every other field of gvl_decode_proj by keyword -- tensors for the pointer fields (outputs are written in
+        place, the caller allocates and pre-fills them), ints / floats for the rest.  Raises GvlError (status ERR_ARG) on a refusal."""
+        d = L.GvlDecodeProj()
+        names = {n: t for n, t in L.GvlDecodeProj._fields_}
+        N, K = W.shape
+        keep = [W.contiguous(), x.contiguous()]
+        d.N, d.K, d.W, d.x = N, K, keep[0].data_ptr(), keep[1].data_ptr()
+        d.batch = int(kw.pop("batch", x.shape[0]))
+        for k, v in kw.items():
+            if k not in names or k in ("W", "x", "N", "K"):
+                raise TypeError(f"op_decode_proj: unknown field {k}")
+            if v is None:
+                continue
+            if names[k] is C.c_void_p:
+                assert v.is_contiguous() and v.device.type == "cuda", k
+                keep.append(v)
+                setattr(d, k, v.data_ptr())
+            else:
+                setattr(d, k, v)
+        self._chk(self.lib.gvl_op_decode_proj(self.ctx, C.byref(d), self.stream), "gvl_op_decode_proj")
+
     def op_gemv(self, W, x, bias=None):
         N, K = W.shape
         y = torch.empty((N,), dtype=torch.float32, device=self.device)

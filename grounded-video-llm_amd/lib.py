@@ -57,6 +57,18 @@ class GvlBeamParams(C.Structure):
                 ("penalty", C.c_float), ("ngram", C.c_int), ("min_new", C.c_int), ("proc_eos_id", C.c_int), ("rules_id", C.c_int)]
 
 
+class GvlDecodeProj(C.Structure):
+    """gvl_decode_proj (include/gvl.h): one decode projection with any prologue / epilogue, for the operator tests."""
+    _fields_ = [("path", C.c_int32), ("variant", C.c_int32), ("w_fmt", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("batch", C.c_int32),
+                ("W", C.c_void_p), ("x", C.c_void_p), ("x_is_tiled", C.c_int32), ("act", C.c_int32), ("bias", C.c_void_p), ("resid", C.c_void_p),
+                ("out_bf16", C.c_void_p), ("out_f32", C.c_void_p), ("out_tiled", C.c_int32), ("out_stride", C.c_int32), ("norm_w", C.c_void_p),
+                ("eps", C.c_float), ("sq_n", C.c_int32), ("sq_in", C.c_void_p), ("sq_out", C.c_void_p), ("out_tiled2", C.c_void_p),
+                ("rope_on", C.c_int32), ("rope_switch", C.c_int32), ("cos_s", C.c_void_p), ("sin_s", C.c_void_p), ("cos_l", C.c_void_p), ("sin_l", C.c_void_p),
+                ("max_pos", C.c_int32), ("n_pages", C.c_int32), ("pos", C.c_void_p), ("tables", C.c_void_p), ("table_stride", C.c_int32), ("q_stride", C.c_int32),
+                ("Q", C.c_void_p), ("Kt", C.c_void_p), ("Vt", C.c_void_p), ("H", C.c_int32), ("KV", C.c_int32), ("Dr", C.c_int32), ("D", C.c_int32),
+                ("w_deq", C.c_void_p), ("w_scale", C.c_void_p)]
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "gvl_create": (C.c_int, [C.POINTER(GvlConfig), C.POINTER(C.c_void_p)]),
@@ -131,6 +143,7 @@ _SIGS = {
     "gvl_op_select_logprobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_void_p,
                                          C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvl_op_dgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_decode_proj": (C.c_int, [C.c_void_p, C.POINTER(GvlDecodeProj), C.c_void_p]),
     "gvl_op_decode_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "gvl_probe_mfma": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "gvl_trace_marker": (C.c_int, [C.c_int, C.c_void_p]),

@@ -491,6 +491,56 @@ int gvl_op_beam_normalize(gvl_ctx* ctx, float* rows, int n, int k, void* stream)
  * read once for all sequences; K % 256 == 0).  x bf16 [batch][K], y f32 [batch][N]. */
 int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch,
                  void* stream);
+/* One decode projection with every prologue / epilogue of the two decode kernels (operator tests: tests/test_gpu_decode_proj.py).  All pointers are device
+ * memory; W and x arrive ROW-MAJOR and the call tiles / quantises private copies as the chosen path needs (W itself is never written).  Zero / NULL = off.
+ *   path 0 = the skinny MFMA GEMM, 1 = the VALU GEMV (serves batch 1, 2, 4 and none of variant, w_fmt, x_is_tiled, out_tiled, sq_in, sq_out, out_tiled2).
+ *   variant: 0 = the launcher's default, else rb * 1000 + nw * 100 + u * 10 + nt.   w_fmt: 0 bf16, 1 FP8 (e4m3, power-of-two row scale), 2 MXFP4.
+ *   K % 256 == 0 on path 0 (FP8: K % 512, MXFP4: K % 1024), K % 8 == 0 on path 1.  x [batch][K] bf16; x_is_tiled: x is already in the decode activation tile order (16 K elements; a producer's out_tiled2).
+ *   act: GVL_ACT_NONE or GVL_ACT_SILU_MUL (interleaved gate / up rows, N / 2 outputs).  out_stride: elements between two sequences' rows of out_bf16 /
+ *   out_f32 / resid (0: N, or N / 2 with SILU_MUL); on path 0 with batch > 1 it must be a multiple of 4 (the epilogue stores 8 and 16 bytes at a time).  out_tiled: the SILU_MUL out_bf16 is written in tile order (16 * N / 2 elements).
+ *   norm_w [K] bf16 + eps: x is RMS-normalised inside the kernel (batch <= 4; on path 0 also K <= 4096; x rows are K elements apart, so K % 4 == 0 holds).  sq_in [batch][sq_n] f32 + eps: the consumer side of the fused norm (W is
+ *   expected to carry the norm weight already: gvl_op_fold_gamma).  sq_out [batch][N / 16] f32 and out_tiled2 (16 N elements): the producer side.
+ *   rope_on: the qkv epilogue; N == (H + 2 KV) Dr, W in the model's row order (the rotate-half row permutation is applied to the private copy).  cos / sin
+ *   tables [max_pos][Dr / 2] f32 (the _l pair is used when pos + 1 > rope_switch > 0), pos [batch] int32, tables [batch][table_stride] int32 page numbers,
+ *   Q [batch][q_stride], Kt / Vt [n_pages][KV][64][D] / [n_pages][KV][D][64].  The call reads pos and tables back and refuses any position >= max_pos,
+ *   any page index outside table_stride and any page >= n_pages before it launches.
+ *   w_deq [N][K] bf16 (w_fmt != 0, or NULL): receives the de-quantised weight the quantiser leaves behind, in W's row order.  w_scale (or NULL): FP8: [N] f32
+ *   row scales by LOGICAL row (pair order with rope_on); MXFP4: the scale words [ceil(N / 16)][K / 128][16] u32, byte j of word (row block, k / 128, row % 16)
+ *   = the E8M0 scale of k step 4 (k / 128) + j of that logical row.
+ * MXFP4 convention: a block of 32 whose largest magnitude has an fp32 exponent field <= 2 (below 2^-124) gets scale byte 0, and scale byte 0 means "a block
+ * of zeros" (2^-127 is not a normal fp32): every element of such a block de-quantises to +0.
+ * Whatever the chosen launcher refuses comes back as GVL_ERR_ARG with a message and nothing is written to any output.  Synchronises the stream. */
+typedef struct {
+  int32_t path, variant, w_fmt;
+  int32_t N, K, batch;
+  const uint16_t* W;
+  const uint16_t* x;
+  int32_t x_is_tiled;
+  int32_t act;
+  const float* bias;
+  const uint16_t* resid;
+  uint16_t* out_bf16;
+  float* out_f32;
+  int32_t out_tiled;
+  int32_t out_stride;
+  const uint16_t* norm_w;
+  float eps;
+  int32_t sq_n;
+  const float* sq_in;
+  float* sq_out;
+  uint16_t* out_tiled2;
+  int32_t rope_on, rope_switch;
+  const float* cos_s; const float* sin_s; const float* cos_l; const float* sin_l;
+  int32_t max_pos, n_pages;
+  const int32_t* pos;
+  const int32_t* tables;
+  int32_t table_stride, q_stride;
+  uint16_t* Q; uint16_t* Kt; uint16_t* Vt;
+  int32_t H, KV, Dr, D;
+  uint16_t* w_deq;
+  void* w_scale;
+} gvl_decode_proj;
+int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream);
 /* measurement only (tools/decode_bench.py): average microseconds per launch of one decode projection [N,K] x `batch` sequences on
  * synthetic operands; mode 0 = skinny MFMA GEMM (variant 0 = default), 1 = VALU GEMV; `rounds` distinct weight copies are cycled. */
 int gvl_op_decode_bench(gvl_ctx* ctx, int N, int K, int batch, int mode, int variant, int rounds, int iters, double* us_per_launch,

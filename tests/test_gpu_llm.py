@@ -531,7 +531,8 @@ def test_fp8_weight_variant_matches_the_dequantised_model(fmt):
     the device -- FP8: OCP e4m3 with a per-row power-of-two scale, decode streams half the bytes; MXFP4: OCP Microscaling E2M1 elements
     with one E8M0 scale per 32 consecutive k, a quarter of the bytes -- and prefill uses the de-quantised bf16 values: ONE model.
     Checked against the ordinary oracle forward on W_q = oracle.fp8_weight_model(W) / mxfp4_weight_model(W): prefill logits,
-    teacher-forced decode steps through the quantised stream, and greedy ids; and the quantisation must actually change the logits."""
+    teacher-forced decode steps through the quantised stream, and greedy ids; and the quantisation must actually change the logits.
+    The quantiser kernels' rounding rules on every bf16 input, and the quantised streams per operator: tests/test_gpu_decode_proj.py"""
     if fmt == "fp8":
         c = dict(hidden=512, inter=1024, layers=2, heads=8, kv_heads=8, vocab=640)
     else:                       # the MXFP4 tile copy needs every K to be a multiple of 1024

@@ -250,6 +250,7 @@ def test_attention_spike_forces_rescale(eng):
 
 @pytest.mark.parametrize("N,K", [(1000, 512), (32366, 3072), (9216, 3072), (3072, 8192), (7, 64)])
 def test_gemv(eng, N, K):
+    """the plain form of the VALU decode GEMV; every other prologue / epilogue, exactly and per element: tests/test_gpu_decode_proj.py"""
     W = _rand(f"gv{N}", (N, K), K ** -0.5).to(bf)
     x = _rand(f"gx{K}", (K,), 1.0).to(bf)
     b = _rand(f"gb{N}", (N,), 0.3)
@@ -261,7 +262,8 @@ def test_gemv(eng, N, K):
 def test_decode_skinny_mfma_gemm(eng, N, K, B):
     """gvl_decode.hip dgemm_kernel (v_mfma_f32_16x16x32_bf16, A = weights, B = activations of up to 16 sequences) vs fp32 torch:
     asymmetric operands (a row / column swap in the D mapping would fail), ragged N (32366 = lm_head + 302 rows), K remainders
-    (11008 / 256 = 43 steps: the non-multiple-of-4 tail loop), both row-block widths (N >= 8192: 32 rows per block)."""
+    (11008 / 256 = 43 steps: the non-multiple-of-4 tail loop), both row-block widths (N >= 8192: 32 rows per block).
+    The plain form only; every other prologue / epilogue, weight format and variant, exactly and per element: tests/test_gpu_decode_proj.py"""
     W = _rand(f"dw{N}.{K}", (N, K), K ** -0.5).to(bf)
     x = _rand(f"dx{K}.{B}", (B, K), 1.0).to(bf)
     b = _rand(f"db{N}", (N,), 0.3)
