@@ -1010,6 +1010,72 @@ int gvl_launch_attention(const AttnArgs& a_in, hipStream_t st) {
 // =====================================================================================================
 // decode attention: one new query per head against the paged cache, split over the context
 // =====================================================================================================
+// ---- split-KV merge: the stages both decode attention kernels share ----------------------------------------------------------------------------------------
+// A block's 4 waves leave, per head, their running (acc[D], m, l) in red[wave][0 .. D + 1] (LDS).  A sequence with ONE split finishes from there; otherwise the block
+// publishes one record [D acc, m, l] per (head, split) with write-through stores, takes a ticket, and the LAST block of the head (group) merges the ns records.
+// The ORDER is what makes the protocol correct without fences (guide G16 recipe R1; placement independent): record stores (sc1) -> every storing wave drains vmcnt ->
+// barrier -> ticket -> the merging block reads the records with sc1 loads (bypass the stale L1) -> re-arm.  It exists once, here.  Sums run over waves 0..3 and over
+// splits 0..ns-1 in index order.  The loops around the stages stay in the kernels: tid < D per head against (head, d) work items, one head per round trip against MGH.
+// So does the output store out[bz][head][d] (out_tiled: B-operand tile order, gvl_xt_index, for the skinny decode GEMM), written out at its four sites in the same
+// words: as a function -- of DecodeAttnArgs, of a small struct or of scalars alike -- it reorders the argument loads in front of decode_attn_gqa_kernel's page loop,
+// + 0.5 .. 1.5 % per launch at 1.7 k - 3.5 k tokens (profiles/decode_refactor_asm.txt).
+template <int D>
+__device__ __forceinline__ float split_wave_max(const float (*red)[D + 2]) { return fmaxf(fmaxf(red[0][D], red[1][D]), fmaxf(red[2][D], red[3][D])); }
+// element e of the block's record: the four waves' red[w][e] (e < D: accumulator, e == D + 1: l) rescaled to the common maximum mm
+template <int D>
+__device__ __forceinline__ float split_wave_sum(const float (*red)[D + 2], int e, float mm) {
+  float s = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) s += red[w][e] * __builtin_amdgcn_exp2f(red[w][D] - mm);
+  return s;
+}
+// ns == 1, the only split of its head: element d < D is finished from red (same arithmetic as a merge of one record): acc / l
+template <int D>
+__device__ __forceinline__ float split_finish_one(const float (*red)[D + 2], int d) {
+  const float mm = split_wave_max<D>(red);
+  const float l = split_wave_sum<D>(red, D + 1, mm);
+  return split_wave_sum<D>(red, d, mm) / l;
+}
+// publish one head's record of this split; called by the whole block (threads 0 .. D-1 store, thread 0 also m and l)
+template <int D>
+__device__ __forceinline__ void split_publish(float* rec, const float (*red)[D + 2], int tid) {
+  const float mm = split_wave_max<D>(red);
+  if (tid < D) __hip_atomic_store(rec + tid, split_wave_sum<D>(red, tid, mm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) {
+    const float l = split_wave_sum<D>(red, D + 1, mm);
+    __hip_atomic_store(rec + D, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(rec + D + 1, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// drain + barrier + ticket + broadcast, ONE step: called by EVERY thread of the block at a block-uniform point (it holds two barriers) after the block's last
+// split_publish.  EVERY storing wave drains its write-through stores before the barrier, so all of the block's records are visible at agent scope when thread 0
+// takes the ticket.  True in every thread of the block that took the last of the nblk tickets -- the one that merges.
+__device__ __forceinline__ bool split_take_ticket(int* counter, int nblk, int* last_s, int tid) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const int t = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *last_s = (t == nblk - 1);
+  }
+  __syncthreads();
+  return *last_s != 0;
+}
+// merge of the ns records of one head (mg: LDS copy, (D + 2) words apart) at element d < D: acc / l
+template <int D>
+__device__ __forceinline__ float split_merge_one(const float* mg, int ns, int d) {
+  float gm = -1e30f;
+  for (int s2 = 0; s2 < ns; ++s2) gm = fmaxf(gm, mg[s2 * (D + 2) + D]);
+  float l = 0.f, acc = 0.f;
+  for (int s2 = 0; s2 < ns; ++s2) {
+    const float w = __builtin_amdgcn_exp2f(mg[s2 * (D + 2) + D] - gm);
+    l += mg[s2 * (D + 2) + D + 1] * w;
+    acc += mg[s2 * (D + 2) + d] * w;
+  }
+  return acc / l;
+}
+// the merging block re-arms the ticket for the next launch (one thread)
+__device__ __forceinline__ void split_rearm(int* counter) { __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 // One block per (query head, context split, sequence).  Grouped-query attention (Llama-3: 32 query heads on 8 KV heads): the G = H / KV
 // heads of a group read the SAME pages.  Round 1 launched grid (H, nsplit, batch): consecutive query heads are consecutive workgroup
 // ids, which the dispatcher deals round-robin over the 8 XCDs -- the 4 heads of a group landed on 4 different L2s and every page crossed
@@ -1143,52 +1209,21 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const DecodeAttnArg
     if (lane == 0) { red_s[g][wave][D] = m_run[g]; red_s[g][wave][D + 1] = l_run[g]; }
   }
   __syncthreads();
-  if (ns == 1) {                                      // the only split of its head: finish here (same arithmetic as a merge of one partial)
+  if (ns == 1) {                                      // the only split of its head: finish here
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       const int head = head0 + g;
-      const float mm = fmaxf(fmaxf(red_s[g][0][D], red_s[g][1][D]), fmaxf(red_s[g][2][D], red_s[g][3][D]));
-      float l = 0.f, acc = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const float e = __builtin_amdgcn_exp2f(red_s[g][w][D] - mm);
-        l += red_s[g][w][D + 1] * e;
-        if (tid < D) acc += red_s[g][w][tid] * e;
+      if (tid < D) {
+        const float o = split_finish_one<D>(red_s[g], tid);      // the store: same words at the merge below and at both sites of decode_attn_gqa_kernel
+        if (tid < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + tid) : (size_t)bz * a.out_stride + head * a.Dout + tid] = f2bf(o);
       }
-      if (tid < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + tid) : (size_t)bz * a.out_stride + head * a.Dout + tid] = f2bf(acc / l);
     }
     return;
   }
-  // ---- publish this block's partials with write-through (sc1) stores, take a ticket; the last block of the KV group
-  //      merges the partials reading them with sc1 loads (bypass the stale L1): no release/acquire fences needed
-  //      (guide G16 recipe R1; placement independent) ---------------------------------------------------------
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    float* outp = part_b + ((size_t)(head0 + g) * a.nsplit + chunk) * (D + 2);
-    const float mm = fmaxf(fmaxf(red_s[g][0][D], red_s[g][1][D]), fmaxf(red_s[g][2][D], red_s[g][3][D]));
-    if (tid < D) {
-      float acc = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) acc += red_s[g][w][tid] * __builtin_amdgcn_exp2f(red_s[g][w][D] - mm);
-      __hip_atomic_store(outp + tid, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (tid == 0) {
-      float l = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) l += red_s[g][w][D + 1] * __builtin_amdgcn_exp2f(red_s[g][w][D] - mm);
-      __hip_atomic_store(outp + D, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(outp + D + 1, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  for (int g = 0; g < G; ++g) split_publish<D>(part_b + ((size_t)(head0 + g) * a.nsplit + chunk) * (D + 2), red_s[g], tid);
   }                                                  // next split of this block
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // EVERY storing wave drains its write-through stores
-  __syncthreads();
-  if (tid == 0) {
-    const int t = __hip_atomic_fetch_add(counters_b + head0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_s = (t == nblk - 1);
-  }
-  __syncthreads();
-  if (!last_s) return;
+  if (!split_take_ticket(counters_b + head0, nblk, &last_s, tid)) return;
   // one round trip per head: every thread fetches its share of the nsplit*(D+2) partial words (sc1 loads, all independent)
   // into LDS (the score scratch is free by now), then the merge runs out of LDS
   float* mg = &part_s[0][0];
@@ -1198,18 +1233,13 @@ __global__ __launch_bounds__(256, 2) void decode_attn_kernel(const DecodeAttnArg
     const float* pp = part_b + (size_t)head * a.nsplit * (D + 2);
     for (int i = tid; i < nword; i += 256) mg[i] = __hip_atomic_load(pp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    float gm = -1e30f;
-    for (int s2 = 0; s2 < ns; ++s2) gm = fmaxf(gm, mg[s2 * (D + 2) + D]);
-    float l = 0.f, acc = 0.f;
-    for (int s2 = 0; s2 < ns; ++s2) {
-      const float w = __builtin_amdgcn_exp2f(mg[s2 * (D + 2) + D] - gm);
-      l += mg[s2 * (D + 2) + D + 1] * w;
-      if (tid < D) acc += mg[s2 * (D + 2) + tid] * w;
+    if (tid < D) {
+      const float o = split_merge_one<D>(mg, ns, tid);             // the store: see the ns == 1 finish above
+      if (tid < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + tid) : (size_t)bz * a.out_stride + head * a.Dout + tid] = f2bf(o);
     }
-    if (tid < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + tid) : (size_t)bz * a.out_stride + head * a.Dout + tid] = f2bf(acc / l);
     __syncthreads();                                  // mg is refilled for the next head of the group
   }
-  if (tid == 0) __hip_atomic_store(counters_b + head0, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next launch
+  if (tid == 0) split_rearm(counters_b + head0);
 }
 
 // =====================================================================================================
@@ -1421,45 +1451,16 @@ __global__ __launch_bounds__(256, 2) void decode_attn_gqa_kernel(const DecodeAtt
     if (ns == 1) {                                  // the only split of this sequence: finish here, all heads of the group at once
       for (int idx = tid; idx < G * D; idx += 256) {
         const int g = idx / D, d = idx - g * D, head = head0 + g;
-        const float mm = fmaxf(fmaxf(red_s[g][0][D], red_s[g][1][D]), fmaxf(red_s[g][2][D], red_s[g][3][D]));
-        float l = 0.f, acc = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const float e = __builtin_amdgcn_exp2f(red_s[g][w][D] - mm);
-          l += red_s[g][w][D + 1] * e;
-          acc += red_s[g][w][d] * e;
-        }
-        if (d < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + d) : (size_t)bz * a.out_stride + head * a.Dout + d] = f2bf(acc / l);
+        const float o = split_finish_one<D>(red_s[g], d);          // the store: same words at the merge below and at both sites of decode_attn_kernel
+        if (d < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + d) : (size_t)bz * a.out_stride + head * a.Dout + d] = f2bf(o);
       }
       return;
     }
-    for (int g = 0; g < G; ++g) {                    // one partial record per head (same format as the per-head kernel)
-      float* outp = part_b + ((size_t)(head0 + g) * a.nsplit + chunk) * (D + 2);
-      const float mm = fmaxf(fmaxf(red_s[g][0][D], red_s[g][1][D]), fmaxf(red_s[g][2][D], red_s[g][3][D]));
-      if (tid < D) {
-        float acc = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc += red_s[g][w][tid] * __builtin_amdgcn_exp2f(red_s[g][w][D] - mm);
-        __hip_atomic_store(outp + tid, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (tid == 0) {
-        float l = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) l += red_s[g][w][D + 1] * __builtin_amdgcn_exp2f(red_s[g][w][D] - mm);
-        __hip_atomic_store(outp + D, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(outp + D + 1, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    for (int g = 0; g < G; ++g)                      // one partial record per head (same format as the per-head kernel)
+      split_publish<D>(part_b + ((size_t)(head0 + g) * a.nsplit + chunk) * (D + 2), red_s[g], tid);
     if (STG && chunk + 1 < c_end) __syncthreads();   // the next split's staging tiles overwrite red_s
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const int t = __hip_atomic_fetch_add(counters_b + head0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_s = (t == nblk - 1);
-  }
-  __syncthreads();
-  if (!last_s) return;
+  if (!split_take_ticket(counters_b + head0, nblk, &last_s, tid)) return;
   // merge: the partial records of up to MGH heads are fetched in ONE round trip (sc1 loads, all independent) and merged by (head, d)
   // work items -- a group of 4 heads costs one round trip instead of four
   const int nword = ns * (D + 2);
@@ -1472,20 +1473,12 @@ __global__ __launch_bounds__(256, 2) void decode_attn_gqa_kernel(const DecodeAtt
     __syncthreads();
     for (int idx = tid; idx < gn * D; idx += 256) {
       const int g = idx / D, d = idx - g * D, head = head0 + g0 + g;
-      const float* mg = mg_s + g * 16 * (D + 2);
-      float gm = -1e30f;
-      for (int s2 = 0; s2 < ns; ++s2) gm = fmaxf(gm, mg[s2 * (D + 2) + D]);
-      float l = 0.f, acc = 0.f;
-      for (int s2 = 0; s2 < ns; ++s2) {
-        const float w = __builtin_amdgcn_exp2f(mg[s2 * (D + 2) + D] - gm);
-        l += mg[s2 * (D + 2) + D + 1] * w;
-        acc += mg[s2 * (D + 2) + d] * w;
-      }
-      if (d < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + d) : (size_t)bz * a.out_stride + head * a.Dout + d] = f2bf(acc / l);
+      const float o = split_merge_one<D>(mg_s + g * 16 * (D + 2), ns, d);   // the store: see the ns == 1 finish above
+      if (d < a.Dout) a.out[a.out_tiled ? gvl_xt_index(bz, head * a.Dout + d) : (size_t)bz * a.out_stride + head * a.Dout + d] = f2bf(o);
     }
     __syncthreads();
   }
-  if (tid == 0) __hip_atomic_store(counters_b + head0, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) split_rearm(counters_b + head0);
 }
 
 // read the knobs, plan (gvl_attn_plan.h: normalised batch / cpb / gsplit / hpb, instantiation, grid), dispatch on the planned instantiation

@@ -34,6 +34,7 @@
 // Phi-3.5, 15 GB for Llama-3-8B); the prefill GEMM keeps the row-major copy its DMA needs.  Activations travel between the decode
 // kernels in the matching B-operand tile order ([k step][64 lanes][8], lane = 16 (k chunk) + sequence): gvl_xt_index.
 #include "gvl_internal.h"
+#include "gvl_decode_epi.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -121,7 +122,6 @@ __global__ __launch_bounds__(NW * 64, U >= 8 ? 2 : 4) void dgemm_kernel(const Ge
   const int i = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * (16 * RB);
   const int kw = a.K / NW;                       // k range of one wave
-  const int halfd = a.Dr >> 1, npair_qk = (a.H + a.KV) * halfd;
 
   // operands in tile order: step s of this wave is the 1 KiB tile (row block, wave * steps + s); lane l reads bytes [16 l, 16 l + 16)
   const int steps = kw >> 5;
@@ -323,38 +323,14 @@ __global__ __launch_bounds__(NW * 64, U >= 8 ? 2 : 4) void dgemm_kernel(const Ge
     const int b = i;                             // this lane's sequence
     const int nr = n0 + rb * 16 + g * 4;         // its 4 consecutive logical rows nr .. nr + 3
     if (b < a.batch && nr < a.N) {
-      if (a.rope_on) {
-        // fused decode epilogue of the qkv projection: RoPE at the sequence's position (apply_rotary_pos_emb modeling_phi3.py:421-445,
-        // short / long factors by kv length :382-385), q -> Q[b][H][D], k / v appended to the sequence's pages
-        const int pos = *a.pos_ptrs[b];
-        const float* cosp = a.cos_s; const float* sinp = a.sin_s;
-        if (a.rope_switch > 0 && pos + 1 > a.rope_switch) { cosp = a.cos_l; sinp = a.sin_l; }
-        const int page = a.tables[b][pos >> 6], slot = pos & 63;
-        bf16_t* Qb = a.Q + (size_t)b * a.q_stride;
+      if (a.rope_on) {                           // the stages of gvl_decode_epi.h, shared with gemv_kernel
+        const DecodeRopeView rv = GVL_DECODE_ROPE_VIEW(a);
+        const DecodeRopeRow rr = decode_rope_row(rv, a.pos_ptrs[b], a.tables[b], b);
 #pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const int n = nr + r;
-          if (n + 1 < a.N) {
-            const int j = n >> 1;
-            if (j < npair_qk) {
-              const int hd = j / halfd, d = j - hd * halfd;
-              const float x1 = rbf(v[r]), x2 = rbf(v[r + 1]);
-              const float c = cosp[(size_t)pos * halfd + d], sn = sinp[(size_t)pos * halfd + d];
-              const bf16_t o1 = f2bf(rbf(x1 * c) + rbf(-x2 * sn)), o2 = f2bf(rbf(x2 * c) + rbf(x1 * sn));
-              bf16_t* dst = hd < a.H ? Qb + (size_t)hd * a.D + d
-                                     : a.Kt + (((size_t)page * a.KV + (hd - a.H)) * 64 + slot) * a.D + d;
-              dst[0] = o1; dst[halfd] = o2;
-            } else {
-              const int vi = n - 2 * npair_qk, hv = vi / a.Dr, d = vi - hv * a.Dr;
-              bf16_t* dst = a.Vt + (((size_t)page * a.KV + hv) * a.D + d) * 64 + slot;
-              dst[0] = f2bf(v[r]); dst[64] = f2bf(v[r + 1]);
-            }
-          }
-        }
-      } else if (a.act == GVL_ACT_SILU_MUL) {    // interleaved (gate, up) rows: up * silu(gate), each op rounded to bf16 (Phi3MLP :458-464)
-        float o[2];
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) { const float gt = rbf(v[r]), u = rbf(v[r + 1]); o[r >> 1] = u * rbf(gt * fast_sigmoid(gt)); }
+        for (int r = 0; r < 4; r += 2)
+          if (nr + r + 1 < a.N) decode_rope_pair(rv, rr, nr + r, v[r], v[r + 1]);
+      } else if (a.act == GVL_ACT_SILU_MUL) {
+        const float o[2] = {decode_swiglu_pair(v[0], v[1]), decode_swiglu_pair(v[2], v[3])};
         if (nr + 3 < a.N) {
           if (a.out_bf16) *(unsigned*)(a.out_bf16 + (a.out_tiled ? gvl_xt_index(b, nr >> 1) : (size_t)b * a.out_stride + (nr >> 1))) = pack2bf(o[0], o[1]);
           if (a.out_f32) { a.out_f32[(size_t)b * a.out_stride + (nr >> 1)] = o[0]; a.out_f32[(size_t)b * a.out_stride + (nr >> 1) + 1] = o[1]; }
@@ -362,42 +338,34 @@ __global__ __launch_bounds__(NW * 64, U >= 8 ? 2 : 4) void dgemm_kernel(const Ge
           if (a.out_bf16) a.out_bf16[a.out_tiled ? gvl_xt_index(b, nr >> 1) : (size_t)b * a.out_stride + (nr >> 1)] = f2bf(o[0]);
           if (a.out_f32) a.out_f32[(size_t)b * a.out_stride + (nr >> 1)] = o[0];
         }
-      } else {
+      } else if (nr + 3 < a.N) {                 // four whole rows: vector loads and stores (a ragged last quad: decode_store_scalar per row)
         if (a.bias) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) if (nr + r < a.N) v[r] += a.bias[nr + r];
+          for (int r = 0; r < 4; ++r) v[r] += a.bias[nr + r];
         }
-        if (nr + 3 < a.N) {
-          if (a.resid) {
-            const u32x2_t rv = *(const u32x2_t*)(a.resid + (size_t)b * a.out_stride + nr);
-            v[0] = lo_bf(rv[0]) + rbf(v[0]); v[1] = hi_bf(rv[0]) + rbf(v[1]); v[2] = lo_bf(rv[1]) + rbf(v[2]); v[3] = hi_bf(rv[1]) + rbf(v[3]);
+        if (a.resid) {
+          const u32x2_t rv = *(const u32x2_t*)(a.resid + (size_t)b * a.out_stride + nr);
+          v[0] = lo_bf(rv[0]) + rbf(v[0]); v[1] = hi_bf(rv[0]) + rbf(v[1]); v[2] = lo_bf(rv[1]) + rbf(v[2]); v[3] = hi_bf(rv[1]) + rbf(v[3]);
+        }
+        if (a.out_bf16) {
+          const unsigned p01 = pack2bf(v[0], v[1]), p23 = pack2bf(v[2], v[3]);
+          const unsigned long long o = (unsigned long long)p01 | ((unsigned long long)p23 << 32);
+          unsigned long long* dst = (unsigned long long*)(a.out_bf16 + (size_t)b * a.out_stride + nr);
+          *dst = o;
+          if (a.out_tiled2) *(unsigned long long*)(a.out_tiled2 + gvl_xt_index(b, nr)) = o;   // 4 consecutive k of one sequence: 8 contiguous bytes of the tile
+          if (a.sq_out) {                      // fused RMSNorm, producer side: sum of squares of the ROUNDED outputs of this 16-row block, per sequence
+            float ss = lo_bf(p01) * lo_bf(p01);
+            ss += hi_bf(p01) * hi_bf(p01); ss += lo_bf(p23) * lo_bf(p23); ss += hi_bf(p23) * hi_bf(p23);
+            const float q0 = __shfl(ss, i, 64), q1 = __shfl(ss, 16 + i, 64), q2 = __shfl(ss, 32 + i, 64), q3 = __shfl(ss, 48 + i, 64);   // the 4 lanes of sequence i
+            if (g == 0) a.sq_out[(size_t)b * (a.N >> 4) + (blockIdx.x * RB + rb)] = (q0 + q1) + (q2 + q3);
           }
-          if (a.out_bf16) {
-            const unsigned p01 = pack2bf(v[0], v[1]), p23 = pack2bf(v[2], v[3]);
-            const unsigned long long o = (unsigned long long)p01 | ((unsigned long long)p23 << 32);
-            unsigned long long* dst = (unsigned long long*)(a.out_bf16 + (size_t)b * a.out_stride + nr);
-            *dst = o;
-            if (a.out_tiled2) *(unsigned long long*)(a.out_tiled2 + gvl_xt_index(b, nr)) = o;   // 4 consecutive k of one sequence: 8 contiguous bytes of the tile
-            if (a.sq_out) {                      // fused RMSNorm, producer side: sum of squares of the ROUNDED outputs of this 16-row block, per sequence
-              float ss = lo_bf(p01) * lo_bf(p01);
-              ss += hi_bf(p01) * hi_bf(p01); ss += lo_bf(p23) * lo_bf(p23); ss += hi_bf(p23) * hi_bf(p23);
-              const float q0 = __shfl(ss, i, 64), q1 = __shfl(ss, 16 + i, 64), q2 = __shfl(ss, 32 + i, 64), q3 = __shfl(ss, 48 + i, 64);   // the 4 lanes of sequence i
-              if (g == 0) a.sq_out[(size_t)b * (a.N >> 4) + (blockIdx.x * RB + rb)] = (q0 + q1) + (q2 + q3);
-            }
-          }
-          if (a.out_f32) *(f32x4v_t*)(a.out_f32 + (size_t)b * a.out_stride + nr) = f32x4v_t{v[0], v[1], v[2], v[3]};
-        } else {
+        }
+        if (a.out_f32) *(f32x4v_t*)(a.out_f32 + (size_t)b * a.out_stride + nr) = f32x4v_t{v[0], v[1], v[2], v[3]};
+      } else {
+        const DecodeOutView ov = GVL_DECODE_OUT_VIEW(a);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int n = nr + r;
-            if (n < a.N) {
-              float y = v[r];
-              if (a.resid) y = bf2f(a.resid[(size_t)b * a.out_stride + n]) + rbf(y);
-              if (a.out_bf16) a.out_bf16[(size_t)b * a.out_stride + n] = f2bf(y);
-              if (a.out_f32) a.out_f32[(size_t)b * a.out_stride + n] = y;
-            }
-          }
-        }
+        for (int r = 0; r < 4; ++r)
+          if (nr + r < a.N) decode_store_scalar(ov, b, nr + r, v[r]);
       }
     }
   }
@@ -447,22 +415,18 @@ int gvl_launch_dgemm(const GemvArgs& a_in, hipStream_t st) {
 
 // ---- tile-order copies --------------------------------------------------------------------------------------------------------
 // W [N][K] row-major -> Wt [ceil(N/16)][K/32][64][8]: lane l of tile (rbk, s) = row rbk*16 + (l & 15) (through the rotate_half pair
-// permutation when Dr > 0: logical rows (2j, 2j+1) = weight rows (hd*Dr + d, hd*Dr + d + Dr/2) for the q and k heads), k chunk l >> 4.
+// permutation decode_row_perm when Dr > 0: logical rows (2j, 2j+1) = weight rows (hd*Dr + d, hd*Dr + d + Dr/2) for the q and k heads), k chunk l >> 4.
 // Rows >= N are zero.
 __global__ void retile_weight_kernel(const bf16_t* __restrict__ W, bf16_t* __restrict__ Wt, int N, int K, int Dr, int n_qk_heads) {
   const long total = (long)((N + 15) / 16) * (K / 32) * 64;
-  const int halfd = Dr >> 1, npair_qk = n_qk_heads * halfd;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int l = (int)(idx & 63);
     const long tile = idx >> 6;
     const int s = (int)(tile % (K / 32));
     const int rbk = (int)(tile / (K / 32));
-    int n = rbk * 16 + (l & 15);
+    const int n = rbk * 16 + (l & 15);
     u32x4_t v = {0u, 0u, 0u, 0u};
-    if (n < N) {
-      if (Dr > 0) { const int j = n >> 1; if (j < npair_qk) { const int hd = j / halfd, d = j - hd * halfd; n = hd * Dr + d + (n & 1) * halfd; } }
-      v = *(const u32x4_t*)(W + (size_t)n * K + s * 32 + (l >> 4) * 8);
-    }
+    if (n < N) v = *(const u32x4_t*)(W + (size_t)decode_row_perm(n, Dr, n_qk_heads) * K + s * 32 + (l >> 4) * 8);
     *(u32x4_t*)(Wt + (size_t)idx * 8) = v;
   }
 }
@@ -491,13 +455,9 @@ int gvl_launch_rows_to_tiled(const bf16_t* x, bf16_t* xt, int batch, int cols, i
 // Per LOGICAL row n (rotate_half pair order when Dr > 0): scale = 2^ceil(log2(max|w| / 448)) -- a power of two, so w_q = fp8(w / scale)
 // * scale is exactly representable in bf16 and the row-major bf16 weight is REPLACED by it: prefill (bf16 GEMM) and decode (FP8 stream)
 // then evaluate the same model, and every invariant of the bf16 path (decode == prefill, batch invariance) carries over.
-__device__ __forceinline__ int decode_row_perm(int n, int N, int Dr, int n_qk_heads) {
-  if (Dr > 0) { const int halfd = Dr >> 1, j = n >> 1; if (j < n_qk_heads * halfd) { const int hd = j / halfd, d = j - hd * halfd; return hd * Dr + d + (n & 1) * halfd; } }
-  return n;
-}
 __global__ __launch_bounds__(64) void fp8_row_scale_kernel(const bf16_t* __restrict__ W, float* __restrict__ scale, int N, int K, int Dr, int n_qk_heads) {
   const int n = blockIdx.x, lane = threadIdx.x;
-  const bf16_t* row = W + (size_t)decode_row_perm(n, N, Dr, n_qk_heads) * K;
+  const bf16_t* row = W + (size_t)decode_row_perm(n, Dr, n_qk_heads) * K;
   float m = 0.f;
   for (int c = lane; c < (K >> 3); c += 64) {
     const u32x4_t v = *(const u32x4_t*)(row + c * 8);
@@ -524,7 +484,7 @@ __global__ void fp8_requant_retile_kernel(bf16_t* __restrict__ W, unsigned char*
     u32x4_t out = {0u, 0u, 0u, 0u};
     if (n < N) {
       const float sc = scale[n], inv = 1.f / sc;                       // powers of two: both exact
-      bf16_t* row = W + (size_t)decode_row_perm(n, N, Dr, n_qk_heads) * K;
+      bf16_t* row = W + (size_t)decode_row_perm(n, Dr, n_qk_heads) * K;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         bf16_t* src = row + (2 * p + h) * 32 + (l >> 4) * 8;
@@ -568,7 +528,7 @@ __global__ void mxfp4_scale_kernel(const bf16_t* __restrict__ W, unsigned char* 
     const int s = (int)(idx % nkt); const int n = (int)(idx / nkt);
     unsigned e = 0;
     if (n < N) {
-      const bf16_t* src = W + (size_t)decode_row_perm(n, N, Dr, n_qk_heads) * K + s * 32;
+      const bf16_t* src = W + (size_t)decode_row_perm(n, Dr, n_qk_heads) * K + s * 32;
       float m = 0.f;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -595,7 +555,7 @@ __global__ void mxfp4_requant_retile_kernel(bf16_t* __restrict__ W, unsigned cha
     u32x4_t out = {0u, 0u, 0u, 0u};
     if (n < N) {
       const unsigned sw = scale[((size_t)rbk * nsg + sg) * 16 + (l & 15)];
-      bf16_t* row = W + (size_t)decode_row_perm(n, N, Dr, n_qk_heads) * K;
+      bf16_t* row = W + (size_t)decode_row_perm(n, Dr, n_qk_heads) * K;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const unsigned e = (sw >> (8 * j)) & 255u;

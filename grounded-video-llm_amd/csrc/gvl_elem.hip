@@ -2,6 +2,7 @@
 // (+ qk-RMSNorm / RoPE), HD-merge / pooling glue, decode GEMV (token selection: gvl_pick.hip).   gfx950 only.
 // Every kernel moves 8/16 bytes per lane (guide G13) and keeps statistics in fp32.
 #include "gvl_internal.h"
+#include "gvl_decode_epi.h"
 #include <cstring>
 
 #define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
@@ -279,18 +280,15 @@ int gvl_launch_iv2_embed(const bf16_t* patch, const bf16_t* cls, const bf16_t* p
 }
 
 // =====================================================================================================
-// qkv_post: fused-qkv row -> Q [B][H][S][D], K pages [page][KV][64][D] (+ V^T column for the decode row)
+// qkv_post: fused-qkv row -> Q [B][H][S][D], K pages [page][KV][64][D]; V^T pages: v_transpose_kernel
 //   mode 1: IV2 q/k RMSNorm over the full width (models/internvideo2.py:560-561,590-598)
 //   mode 2: RoPE (models/modeling_phi3.py:413-445; cos/sin tables hold the bf16-rounded values of :397-409)
-// one block per token row.
+// one wave per token row, 4 rows per block.  (The decode step's single row has its RoPE / KV append in the projection epilogue: gvl_decode_epi.h.)
 // =====================================================================================================
-template <int WPR>   // waves per token row: 1 -> 4 rows per block (bulk), 4 -> one row per block (decode)
 __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row = WPR == 1 ? blockIdx.x * 4 + wave : blockIdx.x;
+  const int row = blockIdx.x * 4 + wave;
   if (row >= (a.vl_n ? a.vl_rows[a.vl_n] : a.B * a.S)) return;                     // no block-level barrier below
-  constexpr int TEAM = 64 * WPR;
-  const int lt = WPR == 1 ? lane : tid;
   // ragged group (vl_n > 0): the row's sequence u by <= 8 prefix sums; after that it is that sequence's own single-sequence launch (b = 0, its table, its length)
   int S_ = a.S, b = 0, s_in = 0, row0 = 0;
   const int* table = a.block_table;
@@ -302,16 +300,15 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostArgs a) {
   } else { b = row / a.S; s_in = row - b * a.S; }
   const bf16_t* qr = a.qkv + (size_t)row * a.ld;
   const bf16_t* kr = qr + a.H * a.Dr;
-  const bf16_t* vr = kr + a.KV * a.Dr;
   const int half = a.Dr >> 1, cpr = a.Dr >> 3, cpd = a.D >> 3, hc = half >> 3;
   const int nq = a.H * cpr, nk = a.KV * cpr;
 
   float q_rs = 1.f, k_rs = 1.f;
-  // mode 1 (WPR == 1: one wave owns the row): the row's q and k chunks (<= 3 per lane each, i.e. rows up to 1536 wide) are
+  // mode 1: the row's q and k chunks (<= 3 per lane each, i.e. rows up to 1536 wide) are
   // requested up front and stay in registers between the full-width RMS statistics and the transform -- one pass over the row
   constexpr int RC = 3;
   u32x4_t qreg[RC], kreg[RC];
-  const bool in_regs = WPR == 1 && a.mode == 1 && nq <= RC * 64 && nk <= RC * 64;
+  const bool in_regs = a.mode == 1 && nq <= RC * 64 && nk <= RC * 64;
   if (a.mode == 1) {
     float sq = 0.f, sk = 0.f;
     if (in_regs) {
@@ -340,12 +337,10 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostArgs a) {
     }
     q_rs = rsqrtf(wave_sum(sq) / (a.H * a.Dr) + a.eps);
     k_rs = rsqrtf(wave_sum(sk) / (a.KV * a.Dr) + a.eps);
-    if (a.q_rs && lt == 0) a.q_rs[row] = q_rs;
+    if (a.q_rs && lane == 0) a.q_rs[row] = q_rs;
   }
-  int pos = a.pos0 + s_in;                          // token position (RoPE, cache slot)
-  if (a.pos_ptr) pos = *a.pos_ptr;
+  const int pos = a.pos0 + s_in;                    // token position (RoPE, cache slot)
   const float* cosp = a.cos; const float* sinp = a.sin;
-  if (a.mode == 2 && a.rope_switch > 0 && pos + 1 > a.rope_switch) { cosp = a.cos_l; sinp = a.sin_l; }
   const int n_tiles = (S_ + 63) >> 6;
   const int tile = pos >> 6, slot = pos & 63;
   const int page = table ? table[b * a.max_pages + tile] : b * n_tiles + tile;
@@ -398,30 +393,22 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostArgs a) {
       if (c < nk) { const int hd = c / cpr, dc = c - hd * cpr; *(u32x4_t*)(Kb + (size_t)hd * (64 * a.D) + dc * 8) = norm_chunk(kreg[i], c, k_rs, a.kn); }
     }
   } else {
-    if (!a.q_rs) for (int c = lt; c < nq; c += TEAM) {
+    if (!a.q_rs) for (int c = lane; c < nq; c += 64) {
       const int hd = c / cpr, dc = c - hd * cpr;
       *(u32x4_t*)(Qb + (size_t)hd * S_ * a.D + dc * 8) = xform(qr, c, q_rs, a.qn);
     }
-    for (int c = lt; c < nk; c += TEAM) {
+    for (int c = lane; c < nk; c += 64) {
       const int hd = c / cpr, dc = c - hd * cpr;
       *(u32x4_t*)(Kb + (size_t)hd * (64 * a.D) + dc * 8) = xform(kr, c, k_rs, a.kn);
     }
   }
   if (cpd > cpr) {                                   // zero the head-dim padding (88 -> 96)
     const int np = cpd - cpr;
-    if (!a.q_rs) for (int c = lt; c < a.H * np; c += TEAM) { const int hd = c / np; *(u32x4_t*)(Qb + (size_t)hd * S_ * a.D + (cpr + c % np) * 8) = zero; }
-    for (int c = lt; c < a.KV * np; c += TEAM) {
+    if (!a.q_rs) for (int c = lane; c < a.H * np; c += 64) { const int hd = c / np; *(u32x4_t*)(Qb + (size_t)hd * S_ * a.D + (cpr + c % np) * 8) = zero; }
+    for (int c = lane; c < a.KV * np; c += 64) {
       const int hd = c / np;
       u32x4_t v = zero; if (a.k_ones && c % np == 0) v[0] = 0x3F80u;      // bf16 1.0 in column Dr
       *(u32x4_t*)(Kb + (size_t)hd * (64 * a.D) + (cpr + c % np) * 8) = v;
-    }
-  }
-  // V^T column of this single row (decode).  Bulk rows go through v_transpose_kernel.
-  if (a.pos_ptr) {
-    bf16_t* Vbase = a.Vt + ((size_t)page * a.KV) * (64 * a.D) + slot;
-    for (int i = lt; i < a.KV * a.Dr; i += TEAM) {
-      const int hd = i / a.Dr, d = i - hd * a.Dr;
-      Vbase[(size_t)hd * (64 * a.D) + d * 64] = vr[i];
     }
   }
 }
@@ -469,16 +456,11 @@ __global__ __launch_bounds__(256) void v_transpose_kernel(const QkvPostArgs a) {
 
 int gvl_launch_qkv_post(const QkvPostArgs& a, hipStream_t st) {
   if ((a.Dr & 7) || (a.mode == 2 && (a.Dr & 15)) || (a.D & 7) || a.D < a.Dr || a.Dr > 128 || (a.ld & 7)) return -1;   // 16-byte chunks; rotate_half partner chunk-aligned
-  if (a.vl_n && (a.mode != 2 || a.B != 1 || a.pos0 != 0 || a.pos_ptr || a.vl_n > GVL_MAX_PREFILL_BATCH)) return -1;
+  if (a.vl_n && (a.mode != 2 || a.B != 1 || a.pos0 != 0 || a.vl_n > GVL_MAX_PREFILL_BATCH)) return -1;
   const int rows = a.vl_n ? a.vl_rows[a.vl_n] : a.B * a.S;
-  if (a.q_rs && (a.mode != 1 || a.pos_ptr)) return -1;
-  if (a.pos_ptr) {
-    if (rows != 1 || a.mode != 2) return -1;
-    hipLaunchKernelGGL(qkv_post_kernel<4>, dim3(1), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(qkv_post_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, st, a);
-  }
-  if (!a.pos_ptr && a.Vt) {                          // Vt == null: the attention kernel reads V in place (AttnArgs.Vrows)
+  if (a.q_rs && a.mode != 1) return -1;
+  hipLaunchKernelGGL(qkv_post_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a);
+  if (a.Vt) {                          // Vt == null: the attention kernel reads V in place (AttnArgs.Vrows)
     int n_tiles = (a.S + 63) >> 6;
     if (a.vl_n) { n_tiles = 0; for (int u = 0; u < a.vl_n; ++u) n_tiles += (a.vl_rows[u + 1] - a.vl_rows[u] + 63) >> 6; }
     hipLaunchKernelGGL(v_transpose_kernel, dim3(n_tiles, a.KV, a.B), dim3(256), 0, st, a);
@@ -568,15 +550,6 @@ int gvl_launch_pool_temporal(const bf16_t* f, bf16_t* out, int n, int T, int C, 
   return CHECK_LAUNCH();
 }
 
-__global__ void f32_to_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = f2bf(x[i]);
-}
-int gvl_launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t st) {
-  int blocks = (int)((n + 255) / 256); if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(blocks), dim3(256), 0, st, x, y, (long)n);
-  return CHECK_LAUNCH();
-}
-
 __global__ void bcast_row_kernel(const bf16_t* __restrict__ row, bf16_t* __restrict__ dst, int n, int stride_rows, int row_off, int cols) {
   const long total = (long)n * cols;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -644,14 +617,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
   const int K8 = a.K >> 3;
   const int n0 = (blockIdx.x * 4 + wave) * R;
   const bf16_t* wp[R];
-  const int halfd = a.Dr >> 1, npair_qk = (a.H + a.KV) * halfd;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     int n = n0 + r; if (n > a.N - 1) n = a.N - 1;
-    if (a.rope_on) {                        // logical row -> weight row: pairs (2j, 2j+1) = rotate_half partners
-      const int j = n >> 1;
-      if (j < npair_qk) { const int hd = j / halfd, d = j - hd * halfd; n = hd * a.Dr + d + (n & 1) * halfd; }
-    }
+    if (a.rope_on) n = decode_row_perm(n, a.Dr, a.H + a.KV);   // logical row -> weight row: pairs (2j, 2j+1) = rotate_half partners
     wp[r] = a.W + (size_t)n * a.K;
   }
   // the first weight chunks do not depend on x: request them before the (latency-bound) x / RMSNorm prologue
@@ -728,34 +697,14 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
     for (int b = 0; b < B; ++b) acc[r][b] = wave_sum(acc[r][b]);
   if (lane != 0) return;
 #pragma unroll
-  for (int b = 0; b < B; ++b) {
+  for (int b = 0; b < B; ++b) {                // the stages of gvl_decode_epi.h, shared with dgemm_kernel
     if (a.rope_on) {
       if constexpr ((R & 1) == 0) {
-        const int pos = *a.pos_ptrs[b];
-        const float* cosp = a.cos_s; const float* sinp = a.sin_s;
-        if (a.rope_switch > 0 && pos + 1 > a.rope_switch) { cosp = a.cos_l; sinp = a.sin_l; }
-        const int page = a.tables[b][pos >> 6], slot = pos & 63;
-        bf16_t* Qb = a.Q + (size_t)b * a.q_stride;
+        const DecodeRopeView rv = GVL_DECODE_ROPE_VIEW(a);
+        const DecodeRopeRow rr = decode_rope_row(rv, a.pos_ptrs[b], a.tables[b], b);
 #pragma unroll
-        for (int r = 0; r < R; r += 2) {
-          const int i = n0 + r;
-          if (i + 1 < a.N) {
-            const int j = i >> 1;
-            if (j < npair_qk) {
-              const int hd = j / halfd, d = j - hd * halfd;
-              const float x1 = rbf(acc[r][b]), x2 = rbf(acc[r + 1][b]);
-              const float c = cosp[(size_t)pos * halfd + d], sn = sinp[(size_t)pos * halfd + d];
-              const bf16_t o1 = f2bf(rbf(x1 * c) + rbf(-x2 * sn)), o2 = f2bf(rbf(x2 * c) + rbf(x1 * sn));
-              bf16_t* dst = hd < a.H ? Qb + (size_t)hd * a.D + d
-                                     : a.Kt + (((size_t)page * a.KV + (hd - a.H)) * 64 + slot) * a.D + d;
-              dst[0] = o1; dst[halfd] = o2;
-            } else {
-              const int vi = i - 2 * npair_qk, hv = vi / a.Dr, d = vi - hv * a.Dr;
-              bf16_t* dst = a.Vt + (((size_t)page * a.KV + hv) * a.D + d) * 64 + slot;
-              dst[0] = f2bf(acc[r][b]); dst[64] = f2bf(acc[r + 1][b]);
-            }
-          }
-        }
+        for (int r = 0; r < R; r += 2)
+          if (n0 + r + 1 < a.N) decode_rope_pair(rv, rr, n0 + r, acc[r][b], acc[r + 1][b]);
       }
     } else if (a.act == GVL_ACT_SILU_MUL) {
       if constexpr ((R & 1) == 0) {
@@ -763,25 +712,17 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
         for (int r = 0; r < R; r += 2) {
           const int n = n0 + r;
           if (n + 1 < a.N) {
-            const float g = rbf(acc[r][b]), u = rbf(acc[r + 1][b]);
-            const float o = u * rbf(g * fast_sigmoid(g));
+            const float o = decode_swiglu_pair(acc[r][b], acc[r + 1][b]);
             if (a.out_bf16) a.out_bf16[(size_t)b * a.out_stride + (n >> 1)] = f2bf(o);
             if (a.out_f32) a.out_f32[(size_t)b * a.out_stride + (n >> 1)] = o;
           }
         }
       }
     } else {
+      const DecodeOutView ov = GVL_DECODE_OUT_VIEW(a);
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int n = n0 + r;
-        if (n < a.N) {
-          float v = acc[r][b];
-          if (a.bias) v += a.bias[n];
-          if (a.resid) v = bf2f(a.resid[(size_t)b * a.out_stride + n]) + rbf(v);
-          if (a.out_bf16) a.out_bf16[(size_t)b * a.out_stride + n] = f2bf(v);
-          if (a.out_f32) a.out_f32[(size_t)b * a.out_stride + n] = v;
-        }
-      }
+      for (int r = 0; r < R; ++r)
+        if (n0 + r < a.N) decode_store_scalar(ov, b, n0 + r, acc[r][b]);
     }
   }
 }
@@ -890,17 +831,6 @@ __global__ __launch_bounds__(256) void kv_page_copy_kernel(bf16_t* kpool, bf16_t
 int gvl_launch_kv_page_copy(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int layers, int src_page, int dst_page, hipStream_t st) {
   if (layers < 1 || (page_elems & 7) || src_page == dst_page) return -1;
   hipLaunchKernelGGL(kv_page_copy_kernel, dim3(layers, 2), dim3(256), 0, st, kpool, vpool, layer_stride, page_elems, src_page, dst_page);
-  return CHECK_LAUNCH();
-}
-__global__ void inc_many_kernel(const IntPtrs ptrs) { if ((int)threadIdx.x < ptrs.n) (*ptrs.p[threadIdx.x])++; }
-int gvl_launch_inc_many(const IntPtrs& ptrs, hipStream_t st) {
-  if (ptrs.n < 1 || ptrs.n > GVL_MAX_DECODE_BATCH) return -1;
-  hipLaunchKernelGGL(inc_many_kernel, dim3(1), dim3(64), 0, st, ptrs);
-  return CHECK_LAUNCH();
-}
-__global__ void inc_kernel(int* p) { if (threadIdx.x == 0) (*p)++; }
-int gvl_launch_inc(int* p, hipStream_t st) {
-  hipLaunchKernelGGL(inc_kernel, dim3(1), dim3(64), 0, st, p);
   return CHECK_LAUNCH();
 }
 __global__ void set_int_kernel(int* p, int v) { if (threadIdx.x == 0) *p = v; }

@@ -277,8 +277,6 @@ struct QkvPostArgs {
   int mode;
   const bf16_t* qn; const bf16_t* kn; float eps;     // mode 1
   const float* cos; const float* sin; int pos0;      // mode 2: tables [max_seq][Dr/2] (already bf16-rounded values)
-  const int* pos_ptr;              // mode 2 decode: device position of the (single) row, overrides pos0 when non-null
-  const float* cos_l; const float* sin_l; int rope_switch;   // decode: long-factor tables used when pos+1 > rope_switch (>0)
   int ones_row;                    // V^T pad row Dr (needs D > Dr) is filled with 1.0 instead of 0: see AttnArgs.ones_row
   int k_ones;                      // K pad column Dr (needs D > Dr) is 1.0 instead of 0 (harmless while q's pad is 0; see AttnArgs.k_ones)
   float* q_rs;                     // mode 1, or null: [B*S] -- the q rows are NOT written; their RMS factor rsqrt(mean q^2 + eps) is, and the attention
@@ -296,7 +294,6 @@ int gvl_launch_hd_merge(const float* f, const float* sub_gn, bf16_t* out, int n,
 int gvl_launch_pool_spatial(const float* f, bf16_t* out, int n, int C, hipStream_t st);
 // temporal 4x4 block mean: bf16 [n,T*256,C] -> bf16 [n,T*16,C]
 int gvl_launch_pool_temporal(const bf16_t* f, bf16_t* out, int n, int T, int C, hipStream_t st);
-int gvl_launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t st);
 // broadcast one row to rows row_off + s*stride, s in [0,n)
 int gvl_launch_bcast_row(const bf16_t* row, bf16_t* dst, int n, int stride_rows, int row_off, int cols, hipStream_t st);
 // embedding gather: ids (device int32) -> rows of dst
@@ -402,16 +399,13 @@ struct LogitsProcArgs { float* logits; int n, ld, batch, cap; const int* hist[GV
                         float penalty[GVL_MAX_DECODE_BATCH]; int ngram[GVL_MAX_DECODE_BATCH], min_new[GVL_MAX_DECODE_BATCH], eos[GVL_MAX_DECODE_BATCH];
                         const TokenRulesDev* rules[GVL_MAX_DECODE_BATCH]; };
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st);
-// x[b][:] = table[*tok_ptrs[b]][:]  and  (*pos_ptrs[b])++ helpers of the batched decode loop
+// x[b][:] = table[*tok_ptrs[b]][:] for the sequences of the batched decode loop
 struct TokPtrs { const int* p[GVL_MAX_DECODE_BATCH]; int n; };
 int gvl_launch_gather_tok_rows(const bf16_t* table, const TokPtrs& toks, bf16_t* dst, int cols, hipStream_t st);
 // x[b] = table[*toks.p[b]] and xn[b] = bf16(w * bf16(x[b] * rstd)): embedding gather + the first layer's input RMSNorm (gvl_decode.hip)
 int gvl_launch_embed_norm(const bf16_t* table, const TokPtrs& toks, bf16_t* x, bf16_t* xn, const bf16_t* w, int cols, float eps, hipStream_t st);
 // xn (B-operand tile order) = rmsnorm(x[b]) * w for the row-major residual rows x [batch][cols]: one wave per sequence (gvl_decode.hip)
 int gvl_launch_norm_tiled(bf16_t* x, bf16_t* xn, const bf16_t* w, int batch, int cols, float eps, hipStream_t st);
-struct IntPtrs { int* p[GVL_MAX_DECODE_BATCH]; int n; };
-int gvl_launch_inc_many(const IntPtrs& ptrs, hipStream_t st);
-int gvl_launch_inc(int* p, hipStream_t st);
 int gvl_launch_kv_page_copy(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int layers, int src_page, int dst_page, hipStream_t st);
 int gvl_launch_set_int(int* p, int v, hipStream_t st);
 

@@ -851,25 +851,9 @@ int gvl_op_rmsnorm(gvl_ctx* ctx, const uint16_t* x, const uint16_t* w, uint16_t*
   RUN(GVL_PROF_OTHER, 0, gvl_launch_rmsnorm_bf16(x, w, y, rows, cols, eps, st));
   return 0;
 }
-int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (N <= 0 || K <= 0 || K % 256 || batch < 1 || batch > GVL_MAX_DECODE_BATCH) return fail(ctx, GVL_ERR_ARG, "gvl_op_dgemm: K % 256 == 0 and 1 <= batch <= 16");
-  // operator-level entry (tests / microbenchmarks): the operands arrive row-major and are re-tiled here; the model keeps tiled copies
-  void *wt = nullptr, *xt = nullptr;
-  HIPCHK(ctx, hipMalloc(&wt, (size_t)((N + 15) / 16) * 16 * K * 2));
-  if (hipMalloc(&xt, (size_t)16 * K * 2) != hipSuccess) { hipFree(wt); return fail(ctx, GVL_ERR_OOM, "gvl_op_dgemm: hipMalloc"); }
-  int rc = gvl_retile_decode_weight(W, (bf16_t*)wt, N, K, 0, 0, st);
-  if (!rc) rc = gvl_launch_rows_to_tiled(x, (bf16_t*)xt, batch, K, K, st);
-  GemvArgs g; memset(&g, 0, sizeof(g)); g.W = (const bf16_t*)wt; g.N = N; g.K = K; g.x = (const bf16_t*)xt; g.bias = bias; g.out_f32 = y; g.batch = batch; g.x_stride = K; g.out_stride = N;
-  if (!rc) { ProfScope _ps(ctx, GVL_PROF_GEMV, 2.0 * N * K, st); rc = gvl_launch_dgemm(g, st); }
-  hipStreamSynchronize(st);
-  hipFree(wt); hipFree(xt);
-  if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, "gvl_op_dgemm: launch failed");
-  return 0;
-}
 // operator-level entry for the WHOLE GemvArgs surface (tests/test_gpu_decode_proj.py): row-major operands in, private tiled / quantised copies made here, every launcher
-// refusal returned as GVL_ERR_ARG before anything is written.  See include/gvl.h for the fields.
+// refusal returned as GVL_ERR_ARG before anything is written.  See include/gvl.h for the fields.  gvl_op_decode_proj checks the descriptor, decode_proj_run does the work.
+static int decode_proj_run(gvl_ctx* ctx, const gvl_decode_proj* p, hipStream_t st, const char* who);
 int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream) {
   if (!ctx) return GVL_ERR_ARG;
   if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: null descriptor");
@@ -905,6 +889,10 @@ int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream) {
       if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: page outside the pools");
     }
   }
+  return decode_proj_run(ctx, p, st, "gvl_op_decode_proj");
+}
+static int decode_proj_run(gvl_ctx* ctx, const gvl_decode_proj* p, hipStream_t st, const char* who) {
+  const int N = p->N, K = p->K, B = p->batch;
   struct Bufs { void* v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Bufs() { for (void* q : v) if (q) hipFree(q); } } bufs;
   void *&wc = bufs.v[0], *&wt = bufs.v[1], *&ws = bufs.v[2], *&xt = bufs.v[3];
   const size_t nb16 = (size_t)((N + 15) / 16);
@@ -913,7 +901,7 @@ int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream) {
   int rc = 0;
   if (p->path == 0) {
     if (p->w_fmt) {                                // the quantisers rewrite their row-major source: work on a copy
-      if (K % (p->w_fmt == 2 ? 1024 : 512)) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: FP8 needs K % 512 == 0, MXFP4 K % 1024 == 0");
+      if (K % (p->w_fmt == 2 ? 1024 : 512)) return fail(ctx, GVL_ERR_ARG, std::string(who) + ": FP8 needs K % 512 == 0, MXFP4 K % 1024 == 0");
       HIPCHK(ctx, hipMalloc(&wc, (size_t)N * K * 2));
       HIPCHK(ctx, hipMemcpyAsync(wc, p->W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st));
       HIPCHK(ctx, hipMalloc(&wt, nb16 * 16 * K));
@@ -948,9 +936,17 @@ int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream) {
     if (p->w_scale) HIPCHK(ctx, hipMemcpyAsync(p->w_scale, ws, p->w_fmt == 1 ? (size_t)N * 4 : nb16 * (K / 128) * 16 * 4, hipMemcpyDeviceToDevice, st));
   }
   const hipError_t se = hipStreamSynchronize(st);
-  if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, rc == -1 ? "gvl_op_decode_proj: the launcher does not serve this combination" : "gvl_op_decode_proj: launch failed");
-  if (se != hipSuccess) return gvl_hipfail(ctx, se, "gvl_op_decode_proj: hipStreamSynchronize");
+  if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, std::string(who) + (rc == -1 ? ": the launcher does not serve this combination" : ": launch failed"));
+  if (se != hipSuccess) return gvl_hipfail(ctx, se, (std::string(who) + ": hipStreamSynchronize").c_str());
   return 0;
+}
+// y f32 [batch][N] = x W^T + bias on the skinny GEMM: the plain form of the descriptor above, under this entry's own precondition (any N; K % 256 == 0)
+int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (N <= 0 || K <= 0 || K % 256 || batch < 1 || batch > GVL_MAX_DECODE_BATCH) return fail(ctx, GVL_ERR_ARG, "gvl_op_dgemm: K % 256 == 0 and 1 <= batch <= 16");
+  gvl_decode_proj p; memset(&p, 0, sizeof(p));
+  p.W = W; p.x = x; p.bias = bias; p.out_f32 = y; p.N = N; p.K = K; p.batch = batch;
+  return decode_proj_run(ctx, &p, (hipStream_t)stream, "gvl_op_dgemm");
 }
 // micro-benchmark of the decode projection kernels on synthetic operands (tools/decode_bench.py): mode 0 = skinny MFMA GEMM (variant:
 // see gvl_launch_dgemm), 1 = round-1 VALU GEMV (batch 1, 2, 4), 2 / 3 = the same two with the fused RMSNorm prologue (batch <= 4).  `rounds` distinct weight matrices are cycled so that the
