@@ -87,6 +87,8 @@ __device__ __forceinline__ int kperm(int i) {
 // (sequence u: rows [vl_rows[u], vl_rows[u + 1]) of Q / O, its own block table vl_tables[u]); a workgroup id decodes to (sequence, query
 // block) through the <= 8 prefix sums, everything after that is the single-sequence kernel on that sequence's (S, Q, O, table) -- the
 // same instructions on the same values, so every row is bit-identical to a launch of its sequence alone.
+// VL = 2: the ragged form where sequence u already holds a.vl_pos0[u] cached tokens (whole pages; 0 = empty): the decode also sets that sequence's qpos0 / Sk, after
+// which it is the single-sequence EXTEND kernel (tile count, causal tile skip and masks unchanged) -- bit-identical per row to gvl_prefill_extend of its sequence alone.
 template <int D, int NWAVES, int NS, int ONES = 0, int VROW = 0, int VL = 0>
 __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnArgs a) {
   constexpr int NT = NWAVES * 64;
@@ -110,6 +112,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnArgs a)
   // (With grouped-query attention the unit is the (batch, KV head) GROUP: its H/KV query heads share the pages too.)
   int S_ = a.S;                                       // queries of THIS block's sequence (VL: decoded below)
   const bf16_t* Qp_ = a.Q; bf16_t* Op_ = a.O; const int* tbl_ = a.block_table;
+  int vl_q0 = 0;                                      // VL = 2: tokens sequence u already holds
   int nq = (a.S + NWAVES * 32 - 1) / (NWAVES * 32);
   const int rep = a.H / a.KV;
   if constexpr (VL) { nq = 0; for (int u = 0; u < a.vl_n; ++u) nq += (a.vl_rows[u + 1] - a.vl_rows[u] + NWAVES * 32 - 1) / (NWAVES * 32); }   // query blocks of all sequences
@@ -126,11 +129,13 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnArgs a)
     Qp_ = a.Q + (size_t)r0 * a.H * D;                // sequence u's [H][S_u][D] block starts at its first packed row
     Op_ = a.O + (size_t)r0 * (size_t)(a.H * a.Dout);
     tbl_ = a.vl_tables[u];
+    if constexpr (VL == 2) vl_q0 = a.vl_pos0[u];
   }
   const int hkv = head / (a.H / a.KV);
   const int q0 = qb * (NWAVES * 32);
   const int qw = q0 + wave * 32;
-  const int Sk = a.Sk > 0 ? a.Sk : S_, qpos0 = a.qpos0;    // keys of the context; absolute position of query 0 (extend-prefill: the cached prefix comes first)
+  // keys of the context; absolute position of query 0 (extend-prefill: the cached prefix comes first; VL = 2: the sequence's own prefix)
+  const int Sk = VL == 2 ? vl_q0 + S_ : a.Sk > 0 ? a.Sk : S_, qpos0 = VL == 2 ? vl_q0 : a.qpos0;
   const int n_tiles_all = (Sk + 63) >> 6;
   int last_q = q0 + NWAVES * 32 - 1; if (last_q > S_ - 1) last_q = S_ - 1;
   const int n_tiles = a.causal ? ((qpos0 + last_q) >> 6) + 1 : n_tiles_all;
@@ -978,13 +983,40 @@ double gvl_attn_flops(const AttnArgs& a) {
   return a.causal ? f * (a.qpos0 + 0.5 * a.S) / Sk : f;      // causal: query i sees qpos0 + i + 1 keys
 }
 
-int gvl_launch_attention(const AttnArgs& a_in, hipStream_t st) {
+static const AttnKnobs& attn_knobs() {
   static const AttnKnobs knobs = [] {                    // LAB, A/B
     AttnKnobs k = GVL_ATTN_KNOBS_DEFAULT;
     if (const char* e = gvl_lab_env("GVL_ATTN_LAZY")) k.lazy = (float)atof(e);      // 0 = move the reference whenever a max grows
     k.no_ones = gvl_lab_env("GVL_ATTN_NO_ONES") != nullptr;
     return k;
   }();
+  return knobs;
+}
+
+// the ragged EXTEND form (AttnArgs.vl_pos0): its own plan and list (gvl_attn_plan.h, attn_ext_plan); everything but vl_* / vl_pos0 and the paged operands must be unset
+int gvl_launch_attention_ext(const AttnArgs& a_in, hipStream_t st) {
+  AttnArgs a = a_in;
+  if (a.B != 1 || a.Sk || a.qpos0 || a.Vrows || a.Qrows || a.Krows || a.q_rs || a.q_nw || a.block_table || !a.Q || !a.Kt || !a.Vt || !a.O) return -1;
+  AttnExtGeometry g{};
+  g.H = a.H; g.KV = a.KV; g.D = a.D; g.Dout = a.Dout; g.causal = a.causal; g.vl_n = a.vl_n; g.O16 = ((uintptr_t)a.O & 15) == 0;
+  for (int u = 0; u <= GVL_MAX_PREFILL_BATCH; ++u) g.vl_rows[u] = a.vl_rows[u];
+  for (int u = 0; u < GVL_MAX_PREFILL_BATCH; ++u) { g.vl_tables[u] = a.vl_tables[u] != nullptr; g.vl_pos0[u] = a.vl_pos0[u]; }
+  AttnExtLaunch l;
+  if (attn_ext_plan(g, attn_knobs(), &l) < 0) return -1;
+  a.lazy = l.lazy;
+  switch (attn_ext_key(l.D, l.NWAVES, l.NS)) {
+#define GVL_CASE(D, NWAVES, NS) \
+    case attn_ext_key(D, NWAVES, NS): { static GvlDevOnce once; if (gvl_set_max_lds(once, (const void*)attn_fwd_kernel<D, NWAVES, NS, 0, 0, 2>, l.lds)) return -3; \
+      hipLaunchKernelGGL((attn_fwd_kernel<D, NWAVES, NS, 0, 0, 2>), dim3(l.grid), dim3(l.block), l.lds, st, a); break; }
+    GVL_ATTN_EXT_LIST(GVL_CASE)
+#undef GVL_CASE
+    default: return -1;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int gvl_launch_attention(const AttnArgs& a_in, hipStream_t st) {
+  const AttnKnobs& knobs = attn_knobs();
   AttnArgs a = a_in;
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   AttnGeometry g{};

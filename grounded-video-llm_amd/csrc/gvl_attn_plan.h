@@ -146,6 +146,54 @@ inline int attn_plan(const AttnGeometry& g, const AttnKnobs& k, AttnLaunch out[G
 }
 
 // =================================================================================================================================================================
+// ragged EXTEND prefill (gvl_prefill_extend_varlen): the ragged form with a cached prefix per sequence
+// =================================================================================================================================================================
+// One causal grid for vl_n sequences packed back to back; sequence u already holds vl_pos0[u] tokens (whole pages: a multiple of 64, 0 = empty), its S_u = vl_rows[u + 1] -
+// vl_rows[u] queries sit at positions vl_pos0[u] + i and see the vl_pos0[u] + S_u keys of vl_tables[u].  attn_fwd_kernel<D, NWAVES, NS, 0, 0, 2>: the VL = 1 decode of
+// (sequence, query block) plus that sequence's own qpos0 / Sk, after which it is the single-sequence extend kernel -- bit-identical per row to a launch of its sequence alone.
+// Paged K / V only; grid, block and LDS are the ragged form's formulas.  A list of its own (the four above are pinned by recorded plans): a new form = one entry + one rule here.
+//   X(D, NWAVES, NS)
+#define GVL_ATTN_EXT_LIST(X) X(64, 4, 2) X(96, 4, 2) X(128, 4, 2)
+constexpr int attn_ext_key(int D, int NWAVES, int NS) { return (D * 16 + NWAVES) * 4 + NS; }
+
+struct AttnExtGeometry {         // only what the decision reads
+  int H, KV, D, Dout, causal;
+  int vl_n, vl_rows[GVL_MAX_PREFILL_BATCH + 1], vl_pos0[GVL_MAX_PREFILL_BATCH];
+  bool vl_tables[GVL_MAX_PREFILL_BATCH];   // which block tables are present
+  bool O16;                                // 16-byte alignment of O
+};
+struct AttnExtLaunch {
+  int D, NWAVES, NS;             // template arguments (ONES = VROW = 0, VL = 2)
+  unsigned grid; int block, lds; // blocks, threads per block, dynamic LDS bytes
+  float lazy;                    // the clamped knob (AttnArgs.lazy)
+};
+// What the kernel assumes: whole query groups per KV head, 16-byte O stores, causal, and per sequence a table, at least one query, a prefix of whole pages and at most
+// 256 key tiles (the LDS page-id table) -- every member checked, a refusal names no member.
+inline bool attn_ext_ok(const AttnExtGeometry& g) {
+  if (g.H <= 0 || g.KV <= 0 || g.H % g.KV || g.Dout <= 0 || g.Dout > g.D || (g.Dout & 7) || !g.O16 || !g.causal) return false;
+  if (g.vl_n < 1 || g.vl_n > GVL_MAX_PREFILL_BATCH || g.vl_rows[0] != 0) return false;
+  for (int u = 0; u < g.vl_n; ++u) {
+    const long long S = (long long)g.vl_rows[u + 1] - g.vl_rows[u];
+    if (!g.vl_tables[u] || S <= 0 || g.vl_pos0[u] < 0 || (g.vl_pos0[u] & 63) || g.vl_pos0[u] + S > 256 * 64) return false;
+  }
+  return true;
+}
+// Returns 0, or -1: the arguments are not served (that includes a grid of more than 2^31 - 1 blocks).
+inline int attn_ext_plan(const AttnExtGeometry& g, const AttnKnobs& k, AttnExtLaunch* out) {
+  if (g.D != 64 && g.D != 96 && g.D != 128) return -1;
+  if (!attn_ext_ok(g)) return -1;
+  const int nwaves = 4, rows = 32 * nwaves, ns = 2;                       // as the ragged form: query rows per block, ring depth 2
+  const long long groups8 = (((long long)g.KV + 7) / 8) * 8;              // KV heads, padded to the 8 XCDs
+  long long nq = 0;
+  for (int u = 0; u < g.vl_n; ++u) nq += (g.vl_rows[u + 1] - g.vl_rows[u] + rows - 1) / rows;
+  const long long grid = groups8 * (g.H / g.KV) * nq;
+  if (grid > 0x7fffffffll) return -1;
+  *out = AttnExtLaunch{g.D, nwaves, ns, (unsigned)grid, 64 * nwaves, ns * 2 * 64 * g.D * 2 + 1024 /* ring + page-id table (256 pages) */,
+                       k.lazy >= 0.f && k.lazy <= 64.f ? k.lazy : GVL_ATTN_KNOBS_DEFAULT.lazy};
+  return 0;
+}
+
+// =================================================================================================================================================================
 // decode attention
 // =================================================================================================================================================================
 enum DecodeAttnFamily : int { GVL_DECODE_ATTN_GQA = 0, GVL_DECODE_ATTN_HEAD };   // decode_attn_gqa_kernel<D, GM, STG> / decode_attn_kernel<D, 1, PH>

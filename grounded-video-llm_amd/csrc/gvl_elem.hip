@@ -454,6 +454,111 @@ __global__ __launch_bounds__(256) void v_transpose_kernel(const QkvPostArgs a) {
   }
 }
 
+// ---- ragged EXTEND group (gvl_prefill_extend_varlen): the mode-2 ragged launches where sequence u already holds a.vl_pos0[u] tokens (whole pages) ---------------
+// Kernels of their own, so that qkv_post_kernel / v_transpose_kernel keep their code objects (as template forms of those two they did not: profiles/
+// extend_varlen_asm.txt).  Only what the decoder's prefill uses: RoPE, a block table per sequence, V^T pages.  Per row the arithmetic is qkv_post_kernel's mode 2
+// at pos0 = vl_pos0[u] -- the same expressions on the same values, so K / Q / V^T come out bit-identical to that sequence's own extend launch.
+__global__ __launch_bounds__(256) void qkv_post_ext_kernel(const QkvPostArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= a.vl_rows[a.vl_n]) return;                // no block-level barrier below
+  // the row's sequence by <= 8 compares, as qkv_post_kernel; each compare selects that sequence's rows, prefix and table: constant indices into the by-value argument only
+  int row0 = 0, row1 = a.vl_rows[1], pos0 = a.vl_pos0[0];
+  const int* table = a.vl_tables[0];
+#pragma unroll
+  for (int i = 1; i < GVL_MAX_PREFILL_BATCH; ++i) {
+    const bool past = i < a.vl_n && row >= a.vl_rows[i];
+    row0 = past ? a.vl_rows[i] : row0; row1 = past ? a.vl_rows[i + 1] : row1; pos0 = past ? a.vl_pos0[i] : pos0; table = past ? a.vl_tables[i] : table;
+  }
+  const int S_ = row1 - row0, s_in = row - row0;
+  const bf16_t* qr = a.qkv + (size_t)row * a.ld;
+  const bf16_t* kr = qr + a.H * a.Dr;
+  const int half = a.Dr >> 1, cpr = a.Dr >> 3, cpd = a.D >> 3, hc = half >> 3;
+  const int nq = a.H * cpr, nk = a.KV * cpr;
+  const int pos = pos0 + s_in;                         // token position (RoPE, cache slot)
+  const int page = table[pos >> 6], slot = pos & 63;
+  auto rope = [&](const bf16_t* src, int c) -> u32x4_t {   // one 16-byte chunk (8 elements) of q or k: qkv_post_kernel's xform, mode 2
+    const u32x4_t v = *(const u32x4_t*)(src + c * 8);
+    const int dc = c % cpr;                            // chunk inside the head
+    const bool first = dc < hc;
+    const u32x4_t p = *(const u32x4_t*)(src + (first ? c + hc : c - hc) * 8);   // rotate_half partner
+    const int j0 = (first ? dc : dc - hc) * 8;
+    const float* cp = a.cos + (size_t)pos * half + j0;
+    const float* sp = a.sin + (size_t)pos * half + j0;
+    const f32x4_t c0 = *(const f32x4_t*)cp, c1 = *(const f32x4_t*)(cp + 4), s0 = *(const f32x4_t*)sp, s1 = *(const f32x4_t*)(sp + 4);
+    const float sg = first ? -1.f : 1.f;
+    const float cc[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+    const float ss[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+    u32x4_t o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x0 = lo_bf(v[e]), x1 = hi_bf(v[e]), p0 = sg * lo_bf(p[e]), p1 = sg * hi_bf(p[e]);
+      o[e] = pack2bf(rbf(x0 * cc[2 * e]) + rbf(p0 * ss[2 * e]), rbf(x1 * cc[2 * e + 1]) + rbf(p1 * ss[2 * e + 1]));
+    }
+    return o;
+  };
+  const u32x4_t zero = {0u, 0u, 0u, 0u};
+  bf16_t* Qb = a.Q + (size_t)row0 * a.H * a.D + (size_t)s_in * a.D;                  // Q [H][S_u][D] of sequence u, at its first packed row
+  bf16_t* Kb = a.Kt + ((size_t)page * a.KV) * (64 * a.D) + (size_t)slot * a.D;       // K page row [page][KV][64][D]
+  for (int c = lane; c < nq; c += 64) { const int hd = c / cpr, dc = c - hd * cpr; *(u32x4_t*)(Qb + (size_t)hd * S_ * a.D + dc * 8) = rope(qr, c); }
+  for (int c = lane; c < nk; c += 64) { const int hd = c / cpr, dc = c - hd * cpr; *(u32x4_t*)(Kb + (size_t)hd * (64 * a.D) + dc * 8) = rope(kr, c); }
+  if (cpd > cpr) {                                     // zero the head-dim padding
+    const int np = cpd - cpr;
+    for (int c = lane; c < a.H * np; c += 64) { const int hd = c / np; *(u32x4_t*)(Qb + (size_t)hd * S_ * a.D + (cpr + c % np) * 8) = zero; }
+    for (int c = lane; c < a.KV * np; c += 64) {
+      const int hd = c / np;
+      u32x4_t v = zero; if (a.k_ones && c % np == 0) v[0] = 0x3F80u;      // bf16 1.0 in column Dr
+      *(u32x4_t*)(Kb + (size_t)hd * (64 * a.D) + (cpr + c % np) * 8) = v;
+    }
+  }
+}
+// v_transpose_kernel's ragged form with tile t of sequence u starting at token vl_pos0[u] + 64 t (tokens past the sequence's new rows are zero filled, as there).
+__global__ __launch_bounds__(256) void v_transpose_ext_kernel(const QkvPostArgs a) {
+  __shared__ __attribute__((aligned(16))) bf16_t tile[64][136];          // 272-byte rows (16-byte aligned, bank-staggered)
+  int t = blockIdx.x, u = 0, t0 = 0;                    // blockIdx.x runs over the 64-token tiles of all sequences; block-uniform scalar loop
+  for (; u + 1 < a.vl_n; ++u) { const int nt = (a.vl_rows[u + 1] - a.vl_rows[u] + 63) >> 6; if (t < t0 + nt) break; t0 += nt; }
+  t -= t0;
+  const int row0 = a.vl_rows[u], S_ = a.vl_rows[u + 1] - row0, hkv = blockIdx.y, tid = threadIdx.x;
+  const int page = a.vl_tables[u][(a.vl_pos0[u] >> 6) + t];
+  const int voff = (a.H + a.KV) * a.Dr + hkv * a.Dr;
+  const int cpr = a.Dr >> 3;
+  for (int i = tid; i < 64 * cpr; i += 256) {
+    const int r = i / cpr, c = i - r * cpr;
+    const int s_in = t * 64 + r;
+    u32x4_t v = {0u, 0u, 0u, 0u};
+    if (s_in < S_) v = *(const u32x4_t*)(a.qkv + ((size_t)row0 + s_in) * a.ld + voff + c * 8);
+    *(u32x4_t*)&tile[r][c * 8] = v;
+  }
+  __syncthreads();
+  bf16_t* dst = a.Vt + ((size_t)page * a.KV + hkv) * (64 * a.D);
+  for (int i = tid; i < a.D * 8; i += 256) {
+    const int d = i >> 3, k8 = (i & 7) * 8;
+    u32x4_t o = {0u, 0u, 0u, 0u};
+    if (d < a.Dr) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (unsigned)tile[k8 + 2 * e][d] | ((unsigned)tile[k8 + 2 * e + 1][d] << 16);
+    } else if (a.ones_row && d == a.Dr) {
+      o = u32x4_t{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};     // bf16 1.0: O^T[Dr] = sum_k P[k] (masked keys carry P = 0)
+    }
+    *(u32x4_t*)(dst + d * 64 + k8) = o;
+  }
+}
+
+// The two launches above for one group; refuses what the kernels do not check: every member needs a table, at least one row and a prefix of whole pages.
+int gvl_launch_qkv_post_ext(const QkvPostArgs& a, hipStream_t st) {
+  if ((a.Dr & 15) || (a.D & 7) || a.D < a.Dr || a.Dr > 128 || (a.ld & 7)) return -1;          // as gvl_launch_qkv_post, mode 2
+  if (a.mode != 2 || a.B != 1 || a.pos0 != 0 || a.block_table || a.q_rs || !a.Vt || !a.cos || !a.sin) return -1;
+  if (a.vl_n < 1 || a.vl_n > GVL_MAX_PREFILL_BATCH || a.vl_rows[0] != 0) return -1;
+  int n_tiles = 0;
+  for (int u = 0; u < a.vl_n; ++u) {
+    if (!a.vl_tables[u] || a.vl_rows[u + 1] <= a.vl_rows[u] || a.vl_pos0[u] < 0 || (a.vl_pos0[u] & 63)) return -1;
+    n_tiles += (a.vl_rows[u + 1] - a.vl_rows[u] + 63) >> 6;
+  }
+  hipLaunchKernelGGL(qkv_post_ext_kernel, dim3((a.vl_rows[a.vl_n] + 3) / 4), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(v_transpose_ext_kernel, dim3(n_tiles, a.KV, 1), dim3(256), 0, st, a);
+  return CHECK_LAUNCH();
+}
+
 int gvl_launch_qkv_post(const QkvPostArgs& a, hipStream_t st) {
   if ((a.Dr & 7) || (a.mode == 2 && (a.Dr & 15)) || (a.D & 7) || a.D < a.Dr || a.Dr > 128 || (a.ld & 7)) return -1;   // 16-byte chunks; rotate_half partner chunk-aligned
   if (a.vl_n && (a.mode != 2 || a.B != 1 || a.pos0 != 0 || a.vl_n > GVL_MAX_PREFILL_BATCH)) return -1;

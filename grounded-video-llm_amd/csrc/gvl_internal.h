@@ -217,8 +217,12 @@ struct AttnArgs {
   int vl_n;
   int vl_rows[GVL_MAX_PREFILL_BATCH + 1];
   const int* vl_tables[GVL_MAX_PREFILL_BATCH];
+  // ragged EXTEND prefill (gvl_launch_attention_ext only; every other launch ignores it): sequence u already holds vl_pos0[u] tokens (a multiple of 64, 0 = empty) --
+  // its query i sits at position vl_pos0[u] + i and sees the vl_pos0[u] + S_u keys of vl_tables[u]
+  int vl_pos0[GVL_MAX_PREFILL_BATCH];
 };
 int gvl_launch_attention(const AttnArgs& a, hipStream_t st);   // attn_plan (gvl_attn_plan.h: operand mode, instantiation, grid, LDS) + dispatch on the planned instantiation
+int gvl_launch_attention_ext(const AttnArgs& a, hipStream_t st);   // attn_ext_plan + dispatch: the ragged form (vl_*) with a cached prefix per sequence (vl_pos0)
 double gvl_attn_flops(const AttnArgs& a);
 
 // ---- decode attention -----------------------------------------------------------------------------
@@ -286,8 +290,12 @@ struct QkvPostArgs {
   int vl_n;
   int vl_rows[GVL_MAX_PREFILL_BATCH + 1];
   const int* vl_tables[GVL_MAX_PREFILL_BATCH];
+  // ragged EXTEND group (gvl_launch_qkv_post_ext only; qkv_post_kernel / v_transpose_kernel never read it): sequence u already holds vl_pos0[u] tokens (a multiple
+  // of 64) -- RoPE position, page and slot of its row i come from vl_pos0[u] + i, its V^T tile t starts at token vl_pos0[u] + 64 t
+  int vl_pos0[GVL_MAX_PREFILL_BATCH];
 };
 int gvl_launch_qkv_post(const QkvPostArgs& a, hipStream_t st);
+int gvl_launch_qkv_post_ext(const QkvPostArgs& a, hipStream_t st);   // mode 2 ragged group with vl_pos0: qkv_post_ext_kernel + v_transpose_ext_kernel, one launch each
 // HD 2x2 merge + sub_GN newline (Phi): f32 [n,576,C] -> bf16 [n,156,4C]
 int gvl_launch_hd_merge(const float* f, const float* sub_gn, bf16_t* out, int n, int C, hipStream_t st);
 // 3x3 block mean (Llama): f32 [n,576,C] -> bf16 [n,64,C]

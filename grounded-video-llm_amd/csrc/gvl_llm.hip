@@ -97,18 +97,24 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
 // (packed back to back, no padding); RoPE / KV append / causal attention run per sequence on its own pages -- as ONE launch with a
 // batch dimension when the lengths are equal, as nb launches otherwise.  Every kernel is batch-invariant, so each sequence's
 // result is bit-identical to a prefill on its own.
-// pos0 > 0 (one sequence only): EXTEND -- the sequence already holds pos0 tokens (a multiple of 64: whole pages, possibly shared with other
-// sequences); the new rows take positions pos0 .. pos0 + len - 1 and attend to the cached prefix plus themselves.
-int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, int pos0) {
+// pos0s (null = all 0): EXTEND -- sequence b already holds pos0s[b] tokens (a multiple of 64: whole pages, possibly shared with other sequences; 0 = empty); its new
+// rows take positions pos0s[b] .. pos0s[b] + lens[b] - 1 and attend to the cached prefix plus themselves.  One sequence: the single-sequence kernels at (qpos0, Sk).
+// A group with any prefix: the ragged launches with a prefix per sequence (gvl_launch_qkv_post_ext / gvl_launch_attention_ext, one grid each per layer), or, under
+// gvl_debug_set("varlen_extend", 0), one launch per sequence of the single-sequence kernels -- the GEMMs shared either way, every row bit-identical to the sequence's
+// own extend.  A group whose members are all empty takes exactly the launches it took before prefixes existed.
+int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, const int* pos0s) {
   const gvl_config& f = ctx->cfg;
   const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
   const int qkvw = (H + 2 * KV) * Dr;
   if (nb < 1 || nb > GVL_MAX_PREFILL_BATCH) return fail(ctx, GVL_ERR_ARG, "llm_prefill: batch must be 1 .. 8 sequences");
-  if (pos0 != 0 && (nb != 1 || (pos0 & 63) || loss)) return fail(ctx, GVL_ERR_ARG, "llm_prefill: extend takes one sequence whose cached prefix is whole pages");
+  int p0[GVL_MAX_PREFILL_BATCH] = {};
+  bool ext = false;                                   // some member sits behind a cached prefix
+  for (int b = 0; b < nb; ++b) { p0[b] = pos0s ? pos0s[b] : 0; ext = ext || p0[b] != 0; if (p0[b] < 0 || (p0[b] & 63)) return fail(ctx, GVL_ERR_ARG, "llm_prefill: a cached prefix is whole pages"); }
+  if (ext && loss) return fail(ctx, GVL_ERR_ARG, "llm_prefill: no loss tail behind a cached prefix");
   for (int b = 0; b < nb; ++b) { const int rc = upload_table(ctx, *sqs[b], st); if (rc) return rc; }
   int off[GVL_MAX_PREFILL_BATCH + 1]; off[0] = 0;
   bool uniform = true;
-  for (int b = 0; b < nb; ++b) { off[b + 1] = off[b] + lens[b]; uniform = uniform && lens[b] == lens[0]; }
+  for (int b = 0; b < nb; ++b) { off[b + 1] = off[b] + lens[b]; uniform = uniform && lens[b] == lens[0] && !ext; }   // the batched launch shares one qpos0: empty sequences only
   const int M = off[nb], S0 = lens[0], P0 = (S0 + 63) / 64;
   if (nb > 1 && uniform && nb * P0 > (int)(sizeof(IntList::v) / sizeof(int))) uniform = false;   // page-id list below holds 256 entries
   ArenaScope arena_scope(ctx->arena_l_off);
@@ -144,7 +150,23 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
     }
     // ragged group: RoPE / KV append per sequence (HBM-bound passes), then ONE causal-attention grid over the query blocks of all sequences
     // (AttnArgs.vl_*; 8 launches of ~900 blocks on 768 block slots each -> one of ~7 000: the causal tail is paid once) -- bit-identical per row
-    const bool vl_attn = n_att > 1 && ctx->dbg.varlen_attn && pos0 == 0;
+    const bool vl_attn = n_att > 1 && ctx->dbg.varlen_attn && !ext;
+    // a group behind cached prefixes: the same two steps with a prefix per sequence (vl_pos0); one LongRoPE table per launch, judged by where a member ENDS -- a group
+    // on both sides of rope_orig_max_pos keeps RoPE / KV append per sequence and still shares the attention grid
+    const bool vl_ext = n_att > 1 && ext && ctx->dbg.varlen_extend;
+    bool vl_post_ext = vl_ext;
+    if (vl_post_ext && f.rope_orig_max_pos > 0 && ctx->cos_l) {
+      const bool l0 = p0[0] + lens[0] > f.rope_orig_max_pos;
+      for (int u = 1; u < nb; ++u) vl_post_ext = vl_post_ext && (p0[u] + lens[u] > f.rope_orig_max_pos) == l0;
+    }
+    if (vl_post_ext) {
+      const bool use_long = f.rope_orig_max_pos > 0 && p0[0] + lens[0] > f.rope_orig_max_pos && ctx->cos_l;
+      QkvPostArgs q; memset(&q, 0, sizeof(q)); q.qkv = qkv; q.ld = qkvw; q.Q = Q; q.Kt = Kt; q.Vt = Vt; q.B = 1; q.H = H; q.KV = KV; q.Dr = Dr; q.D = D; q.mode = 2;
+      q.cos = use_long ? ctx->cos_l : ctx->cos_s; q.sin = use_long ? ctx->sin_l : ctx->sin_s; q.vl_n = nb;
+      for (int u = 0; u < nb; ++u) { q.vl_rows[u] = off[u]; q.vl_tables[u] = sqs[u]->d_block_table; q.vl_pos0[u] = p0[u]; q.S = lens[u] > q.S ? lens[u] : q.S; }
+      q.vl_rows[nb] = off[nb];
+      RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post_ext(q, st));
+    }
     // round 6: RoPE / KV append / V^T pages of the group in ONE launch each as well (QkvPostArgs.vl_*: 2 launches per layer instead of 2 per sequence -- 25 + 14 us
     // launches of 3.5 k rows each, bit-identical per row); varlen_attn = 2 keeps them per sequence (round 5).  One table choice (LongRoPE short / long) per launch.
     bool vl_post = vl_attn && ctx->dbg.varlen_attn == 1;
@@ -160,17 +182,18 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
       q.vl_rows[nb] = off[nb];
       RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(q, st));
     }
-    for (int u = 0; u < n_att && !vl_post; ++u) {
+    for (int u = 0; u < n_att && !vl_post && !vl_post_ext; ++u) {
       const int S = lens[u], B = n_att == 1 ? nb : 1;
       const int* tbl = n_att == 1 ? table : sqs[u]->d_block_table;
       const int tstride = n_att == 1 ? table_stride : sqs[u]->n_pages;
       // LongRoPE: short factors up to the original context, long factors past it (modeling_phi3.py:381-385), per sequence
+      const int pos0 = p0[u];
       const bool use_long = f.rope_orig_max_pos > 0 && pos0 + S > f.rope_orig_max_pos && ctx->cos_l;
       bf16_t* Qu = Q + (size_t)off[u] * H * D;
       { QkvPostArgs q; memset(&q, 0, sizeof(q)); q.qkv = qkv + (size_t)off[u] * qkvw; q.ld = qkvw; q.Q = Qu; q.Kt = Kt; q.Vt = Vt; q.block_table = tbl; q.max_pages = tstride;
         q.B = B; q.S = S; q.H = H; q.KV = KV; q.Dr = Dr; q.D = D; q.mode = 2; q.cos = use_long ? ctx->cos_l : ctx->cos_s; q.sin = use_long ? ctx->sin_l : ctx->sin_s; q.pos0 = pos0;
         RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(q, st)); }
-      if (vl_attn) continue;
+      if (vl_attn || vl_ext) continue;
       { AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Qu; a.Kt = Kt; a.Vt = Vt; a.O = att + (size_t)off[u] * H * Dr; a.block_table = tbl; a.max_pages = tstride;
         a.B = B; a.H = H; a.KV = KV; a.S = S; a.D = D; a.Dout = Dr; a.scale = 1.0f / sqrtf((float)Dr); a.causal = 1;
         if (pos0) { a.Sk = pos0 + S; a.qpos0 = pos0; }
@@ -185,6 +208,15 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
         AttnArgs one = a; one.S = lens[u]; one.vl_n = 0; fl += gvl_attn_flops(one); }
       a.vl_rows[nb] = off[nb]; a.max_pages = 0;
       RUN(GVL_PROF_ATTN, fl, gvl_launch_attention(a, st));
+    }
+    if (vl_ext) {
+      AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Q; a.Kt = Kt; a.Vt = Vt; a.O = att; a.B = 1; a.H = H; a.KV = KV; a.D = D; a.Dout = Dr;
+      a.scale = 1.0f / sqrtf((float)Dr); a.causal = 1; a.vl_n = nb;
+      double fl = 0;
+      for (int u = 0; u < nb; ++u) { a.vl_rows[u] = off[u]; a.vl_tables[u] = sqs[u]->d_block_table; a.vl_pos0[u] = p0[u]; a.S = lens[u] > a.S ? lens[u] : a.S;
+        AttnArgs one = a; one.S = lens[u]; one.vl_n = 0; one.Sk = p0[u] + lens[u]; one.qpos0 = p0[u]; fl += gvl_attn_flops(one); }
+      a.vl_rows[nb] = off[nb];
+      RUN(GVL_PROF_ATTN, fl, gvl_launch_attention_ext(a, st));
     }
     { GemmArgs g = gemm(att, H * Dr, w.ow, x, Hd, M, Hd, H * Dr); g.resid = x; g.ldr = Hd; if (nf) { g.rowsq = sq; g.rowsq_ld = NBLK; }
       RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st)); }
@@ -260,8 +292,8 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
     for (int b = 0; b < nb; ++b) sqs[b]->rng_stream = ctx->sample.next_stream++;     // a fresh random stream per prefilled sequence
     RUN(GVL_PROF_OTHER, 0, pick_tokens(ctx, am, sqs, st)); }
   for (int b = 0; b < nb; ++b) {
-    RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sqs[b]->d_pos, pos0 + lens[b], st));
-    sqs[b]->pos = pos0 + lens[b]; sqs[b]->n_gen = 1;
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sqs[b]->d_pos, p0[b] + lens[b], st));
+    sqs[b]->pos = p0[b] + lens[b]; sqs[b]->n_gen = 1;
   }
   return 0;
 }

@@ -88,7 +88,7 @@ int build_visual(gvl_ctx* ctx, const float* clip_feats, const bf16_t* iv2_feats,
 // gvl_llm.hip
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
-int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, int pos0 = 0);
+int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr);   // pos0s: tokens each sequence already holds (null = none)
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st);
 int decode_group_size(const gvl_ctx* ctx, int left);
 int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, int32_t* const* out_ids, int* const* n_out, hipStream_t st);

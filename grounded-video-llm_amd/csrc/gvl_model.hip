@@ -546,7 +546,8 @@ int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_n
   if (!embeds || n_new <= 0 || sq.pos + n_new > sq.max_tokens || n_new > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad length");
   hipStream_t st = (hipStream_t)stream;
   Seq* one[1] = {&sq}; const bf16_t* e1[1] = {embeds};
-  int rc = llm_prefill(ctx, one, 1, e1, &n_new, st, nullptr, sq.pos);
+  const int pos0 = sq.pos;
+  int rc = llm_prefill(ctx, one, 1, e1, &n_new, st, nullptr, &pos0);
   if (rc) return rc;
   if (last_logits) HIPCHK(ctx, hipMemcpyAsync(last_logits, ctx->d_logits, (size_t)ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
   return 0;
@@ -605,6 +606,38 @@ int gvl_prefill_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint1
     for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds[i + b]; }
     const int rc = llm_prefill(ctx, sqs, B, es, seq_lens + i, st);
     if (rc) return rc;
+    i += B;
+  }
+  return 0;
+}
+
+// Ragged prefill where every member sits behind its own cached prefix (0 = none).  Everything is checked before the first launch, so an error leaves every sequence
+// as it was (the pool is never touched: a sequence owns its pages from gvl_seq_alloc / gvl_seq_fork on).
+int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds_new, const int* n_new, float* last_logits, void* stream) {
+  REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend_varlen");
+  if (!seq_ids || !embeds_new || !n_new || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad arguments");
+  for (int i = 0; i < n_seqs; ++i) {
+    const int id = seq_ids[i];
+    if (!ctx->lookup(id) || !embeds_new[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad seq / embeds");
+    const Seq& sq = ctx->seqs[id];
+    if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
+    if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad length");
+    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_prefill_extend_varlen", SEQ_DUPLICATE);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // groups of up to GVL_MAX_PREFILL_BATCH sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
+  for (int i = 0; i < n_seqs;) {
+    int B = n_seqs - i < GVL_MAX_PREFILL_BATCH ? n_seqs - i : GVL_MAX_PREFILL_BATCH;
+    for (;;) {
+      long rows = 0; for (int b = 0; b < B; ++b) rows += n_new[i + b];
+      if (B == 1 || rows <= ctx->cfg.max_prefill) break;
+      --B;
+    }
+    Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH]; int pos0[GVL_MAX_PREFILL_BATCH];
+    for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds_new[i + b]; pos0[b] = sqs[b]->pos; }
+    const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0);
+    if (rc) return rc;
+    if (last_logits) HIPCHK(ctx, hipMemcpyAsync(last_logits + (size_t)i * ctx->cfg.vocab, ctx->d_logits, (size_t)B * ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
     i += B;
   }
   return 0;
@@ -734,6 +767,7 @@ int gvl_debug_set(gvl_ctx* ctx, const char* key, int value) {
   else if (k == "attn_pipe_rows") { if (value != 128 && value != 256) return fail(ctx, GVL_ERR_ARG, "gvl_debug_set: attn_pipe_rows must be 128 (default) or 256"); ctx->dbg.attn_pipe_rows = value; }
   else if (k == "patch_fused") ctx->dbg.patch_fused = value != 0;
   else if (k == "varlen_attn") ctx->dbg.varlen_attn = value < 0 || value > 2 ? 1 : value;
+  else if (k == "varlen_extend") ctx->dbg.varlen_extend = value != 0;
   else if (k == "norm_fused") ctx->dbg.norm_fused = value != 0;
   else if (k == "last_layer_tail") ctx->dbg.last_layer_tail = value != 0;
   else if (k == "gemm_band") { if (value < 0 || value > 64) return fail(ctx, GVL_ERR_ARG, "gvl_debug_set: gemm_band must be 0 (automatic) .. 64"); gvl_gemm_set_band(value); }

@@ -341,6 +341,19 @@ class Engine:
         self._chk(self.lib.gvl_prefill_extend(self.ctx, int(seq), _ptr(embeds_new), embeds_new.shape[0], _ptr(lg), self.stream), "gvl_prefill_extend")
         return lg
 
+    def prefill_extend_batch(self, seqs: Sequence[int], embeds_new: Sequence[torch.Tensor], want_logits: bool = False) -> Optional[torch.Tensor]:
+        """Ragged prefill where every sequence sits behind its own cached prefix (gvl_prefill_extend_varlen): each holds a multiple of 64 tokens (0 = empty) and gets
+        its own new rows; one decoder pass per group of up to 8.  Every member ends exactly as after its own prefill_extend / prefill.  -> [n][vocab] logits if asked."""
+        es = [e.contiguous() for e in embeds_new]
+        assert all(e.dtype == bf and e.dim() == 2 for e in es) and len(es) == len(seqs)
+        n = len(seqs)
+        ids = (C.c_int * n)(*[int(s) for s in seqs])
+        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in es])
+        lens = (C.c_int * n)(*[int(e.shape[0]) for e in es])
+        lg = torch.empty((n, self.geo.vocab), dtype=torch.float32, device=self.device) if want_logits else None
+        self._chk(self.lib.gvl_prefill_extend_varlen(self.ctx, ids, n, ptrs, lens, _ptr(lg), self.stream), "gvl_prefill_extend_varlen")
+        return lg
+
     def prefill(self, seq: int, embeds: torch.Tensor, want_logits: bool = False) -> Optional[torch.Tensor]:
         embeds = embeds.contiguous()
         logits = torch.empty((self.geo.vocab,), dtype=torch.float32, device=self.device) if want_logits else None

@@ -482,7 +482,8 @@ class LLAVA_NEXT_VIDEO:
                                 processors: Optional[List["LP.Processors"]] = None, logprobs: Optional[int] = None):
         """Prompts about one video share the system prompt and the visual tokens: the common prefix (rounded down to 128 tokens = whole KV pages AND
         whole query blocks, so that every later row is computed exactly as in a full prefill) is prefilled ONCE; every prompt forks it
-        (gvl_seq_fork: pages referenced, not copied) and prefills only its own tail (gvl_prefill_extend); the answers are decoded together.
+        (gvl_seq_fork: pages referenced, not copied) and only its own tail is prefilled -- the tails of up to 8 prompts in one ragged decoder pass
+        (gvl_prefill_extend_varlen: the weights are streamed once per group, not once per prompt); the answers are decoded together.
         Ids are bit-identical to one full prefill per prompt.  logprobs: as in generate_ids (then (ids, lps) is returned)."""
         eng = self.engine
         self.last_shared_prefix = 0                      # tokens prefilled once for all prompts in the last generate_shared call (0 = not shared)
@@ -517,7 +518,8 @@ class LLAVA_NEXT_VIDEO:
             for o, e in zip(opts, embs):
                 seqs.append(eng.seq_fork(base, prefix, min(e.shape[0] + max_new, self.geo.max_seq)))
                 LP.apply_seq_options(eng, seqs[-1], o)
-                eng.prefill_extend(seqs[-1], e[prefix:])
+            for g in range(0, len(seqs), 8):                 # all tails of a group in ONE decoder pass (each exactly as its own gvl_prefill_extend)
+                eng.prefill_extend_batch(seqs[g:g + 8], [e[prefix:] for e in embs[g:g + 8]])
             got = eng.decode_greedy_batch(seqs, max_new, eos)
             if logprobs is None:
                 return got

@@ -7,6 +7,10 @@ lets requests join and leave between decode chunks:
 
   admit    queued requests take a free slot: splice -> KV pages (gvl_seq_alloc) -> ONE ragged prefill for all newcomers
            (gvl_prefill_varlen: packed rows through the decoder GEMMs)
+  prefix   another question about a clip that is already resident: add_prefix() prefills the clip's rows once into a holder
+           sequence; a request submitted with prefix=pid forks the holder (gvl_seq_fork: pages referenced, not copied) and
+           prefills only the rows behind it -- newcomers with and without a prefix share ONE ragged pass
+           (gvl_prefill_extend_varlen).  Same ids as without the prefix.
   decode   every active sequence advances `chunk` tokens (gvl_decode_steps: members at different generation steps share
            one weight stream per step in groups of up to 16)
   retire   ids are read back (gvl_seq_read), sequences that produced eos / reached max_new free their pages at once
@@ -35,10 +39,20 @@ class _Request:
     n_gen: int = 0               # tokens generated on the device so far (>= len(ids) once eos was seen)
     opts: LP.SeqOptions = LP.SeqOptions()   # this request's settings (a field left alone: the engine's default); opts.rules holds its logits.TokenRules ...
     rules_id: Optional[int] = None   # ... and this their device rule set: created when the request is admitted, destroyed when it retires
+    prefix: Optional[int] = None     # add_prefix() id whose rows are the first rows of embeds (None: prefill everything)
+
+
+@dataclass
+class _Prefix:
+    seq: int                     # the holder sequence: owns the prefix's KV pages until drop_prefix and the last queued request that names it
+    rows: int                    # P, a multiple of 128
+    queued: int = 0              # requests in the queue that name it
+    dropped: bool = False
 
 
 class ClipScheduler:
-    """engine: anything with seq_alloc / seq_free / prefill_batch / decode_steps / seq_read (grounded_video_llm_amd.engine.Engine)."""
+    """engine: anything with seq_alloc / seq_free / prefill_batch / decode_steps / seq_read (grounded_video_llm_amd.engine.Engine); requests that
+    name a prefix also need seq_fork / prefill_extend_batch -- neither is called while no request does."""
 
     def __init__(self, engine, eos_id: Optional[int], max_active: int = 8, chunk: int = 8, max_prefill_rows: Optional[int] = None):
         if max_active < 1 or chunk < 1:
@@ -50,15 +64,47 @@ class ClipScheduler:
         self.done: Dict[int, List[int]] = {}
         self.done_logprobs: Dict[int, tuple] = {}    # rid -> (lp, top) of a finished request that asked for them (logprobs())
         self._next = 0
-        self.stats = {"prefill_calls": 0, "decode_chunks": 0, "decode_seq_steps": 0, "wasted_seq_steps": 0, "max_concurrent": 0}
+        self.prefixes: Dict[int, _Prefix] = {}
+        self._next_prefix = 0
+        self.stats = {"prefill_calls": 0, "decode_chunks": 0, "decode_seq_steps": 0, "wasted_seq_steps": 0, "max_concurrent": 0, "prefix_rows_saved": 0}
 
     # ---- public ------------------------------------------------------------------------------------------
+    def add_prefix(self, embeds) -> int:
+        """Prefill the first P = len(embeds) // 128 * 128 rows of `embeds` (a clip's system prompt + visual rows, or a whole spliced prompt about it) once, into a
+        holder sequence, and return an id for submit(..., prefix=).  128 rather than the 64 of a KV page: whole query blocks too, so that the rows behind the
+        prefix are computed exactly as in a full prefill and a request's ids do not depend on whether it named the prefix (generate_shared's rule).
+        The holder's pages stay resident until drop_prefix."""
+        P = int(embeds.shape[0]) // 128 * 128
+        if P < 128:
+            raise ValueError(f"a shared prefix needs at least 128 rows, not {int(embeds.shape[0])}")
+        seq = self.eng.seq_alloc(P)
+        try:
+            self.eng.prefill_batch([seq], [embeds[:P]])
+        except Exception:
+            self.eng.seq_free(seq)
+            raise
+        self.prefixes[self._next_prefix] = _Prefix(seq, P)
+        self._next_prefix += 1
+        return self._next_prefix - 1
+
+    def drop_prefix(self, pid: int):
+        """No new request may name `pid`.  Its holder is freed as soon as no QUEUED request names it (now, if none does); requests already admitted keep the
+        pages alive through their own references."""
+        p = self.prefixes.get(pid)
+        if p is None or p.dropped:
+            raise KeyError(f"prefix {pid}: unknown or already dropped")
+        p.dropped = True
+        self._release_prefix(pid)
+
     def submit(self, embeds, max_new_tokens: int, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                min_new_tokens: Optional[int] = None, logprobs: Optional[int] = None, bad_words_ids=None, sequence_bias=None, suppress_tokens=None,
                begin_suppress_tokens=None, forced_eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
                top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
-               epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None) -> int:
-        """Queue one request.  repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors for THIS request (HF's validation;
+               epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None) -> int:
+        """Queue one request.  embeds: the full spliced prompt.  prefix: an add_prefix() id -- the caller promises that the prompt's first P rows ARE the registered
+        ones; only embeds[P:] (at least one row) is then prefilled.  An optimisation only: the result is the same without it.  (It is ignored for a request that
+        LongRoPE forbids to share: P <= rope_orig_max_pos < len(embeds) -- a full prefill of that prompt ropes the shared rows with the long factors.)
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors for THIS request (HF's validation;
         applied on the device to its generated ids; min_new_tokens needs the scheduler's eos id).  Requests with different settings share one
         decode group.  None for all three: the sequence keeps the engine's default (Engine.set_logits_processors).
         logprobs: 0 = the log-probability of every generated id, 1 .. 8 = also its top N alternatives (Engine.seq_set_logprobs); read back
@@ -82,7 +128,20 @@ class ClipScheduler:
         if any(v is not None for v in rkw.values()):
             rules = LP.resolve_rules(rkw, self.eos, int(max_new_tokens), getattr(getattr(self.eng, "geo", None), "vocab", None))
         sampling = LP.request_sampling(do_sample, temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed)
-        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling))
+        if prefix is not None:
+            p = self.prefixes.get(prefix)
+            if p is None or p.dropped:
+                raise KeyError(f"prefix {prefix}: unknown or dropped")
+            S = int(embeds.shape[0])
+            if S <= p.rows:
+                raise ValueError(f"a request behind a prefix of {p.rows} rows needs at least one row of its own, not {S} in all")
+            geo = getattr(self.eng, "geo", None)
+            omax = getattr(geo, "rope_orig_max_pos", 0) if getattr(geo, "rope_long", None) is not None else 0
+            if omax > 0 and p.rows <= omax < S:
+                prefix = None
+            else:
+                p.queued += 1
+        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling), prefix=prefix)
         self._next += 1
         self.queue.append(r)
         return r.rid
@@ -127,14 +186,15 @@ class ClipScheduler:
         while self.queue and len(self.active) + len(new) < self.max_active:
             r = self.queue[0]
             S = int(r.embeds.shape[0])
-            if self.max_prefill_rows is not None and new and rows + S > self.max_prefill_rows:
+            P = self.prefixes[r.prefix].rows if r.prefix is not None else 0     # rows the request does not prefill
+            if self.max_prefill_rows is not None and new and rows + S - P > self.max_prefill_rows:
                 break                                        # next iteration: keep the newcomers' prefill inside the workspace
             max_seq = getattr(getattr(self.eng, "geo", None), "max_seq", None)
             cap = S + r.max_new if max_seq is None else min(S + r.max_new, int(max_seq))
             if cap < S:
                 raise ValueError(f"request {r.rid}: {S} prefill tokens exceed the engine's max_seq {max_seq}")
             try:
-                r.seq = self.eng.seq_alloc(cap)
+                r.seq = self.eng.seq_fork(self.prefixes[r.prefix].seq, P, cap) if P else self.eng.seq_alloc(cap)
             except L.GvlError as e:
                 if getattr(e, "status", 0) == L.ERR_OOM:     # KV pages exhausted: wait for a retirement (FIFO, no overtaking)
                     break
@@ -150,15 +210,29 @@ class ClipScheduler:
             r.max_new = min(r.max_new, cap - S + 1)          # generate() stops at the context limit (Engine.generate_ids does too)
             self.queue.popleft()
             new.append(r)
-            rows += S
+            rows += S - P
+            if P:                                            # the fork holds the pages now
+                self.prefixes[r.prefix].queued -= 1
+                self._release_prefix(r.prefix)
+                self.stats["prefix_rows_saved"] += P
+                r.embeds = r.embeds[P:]
         if new:
-            self.eng.prefill_batch([r.seq for r in new], [r.embeds for r in new])
+            if any(r.prefix is not None for r in new):       # one ragged pass for all newcomers, each behind its own prefix (none = empty)
+                self.eng.prefill_extend_batch([r.seq for r in new], [r.embeds for r in new])
+            else:
+                self.eng.prefill_batch([r.seq for r in new], [r.embeds for r in new])
             self.stats["prefill_calls"] += 1
             for r in new:
                 r.n_gen = 1
                 r.embeds = None                              # the KV cache holds it now
             self.active += new
             self.stats["max_concurrent"] = max(self.stats["max_concurrent"], len(self.active))
+
+    def _release_prefix(self, pid: int):
+        p = self.prefixes[pid]
+        if p.dropped and p.queued == 0:
+            del self.prefixes[pid]
+            self.eng.seq_free(p.seq)
 
     def _drop_rules(self, r: _Request):
         if r.rules_id is not None:

@@ -142,6 +142,16 @@ int gvl_seq_free(gvl_ctx* ctx, int seq_id);
  * prefills). */
 int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* dst_seq);
 int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds_new, int n_new, float* last_logits, void* stream);
+/* The ragged form of gvl_prefill_extend: n_seqs sequences, each behind its OWN cached prefix, in one decoder pass per group (the weights are streamed once
+ * for all tails; RoPE / KV append, V^T pages and causal attention are one launch each per layer for the whole group).  Every sequence must hold a multiple of
+ * 64 tokens -- 0 is allowed: such a member is prefilled from scratch -- with pos + n_new[i] <= its max_tokens and 1 <= n_new[i] <= cfg.max_prefill; no sequence
+ * twice.  Groups of up to 8 sequences (GVL_MAX_PREFILL_BATCH) and cfg.max_prefill rows are formed in call order, as gvl_prefill_varlen forms them.
+ * last_logits: [n_seqs][vocab] on the device, or NULL.  Every member ends in exactly the state its own gvl_prefill_extend (or, when empty, gvl_prefill) leaves it
+ * in, bit for bit: logits, first token, KV pages, and, with sampling on, the random stream it would get from n_seqs such calls in call order.
+ * GVL_ERR_ARG / GVL_ERR_STATE (gvl_last_error says which member rule) are raised before anything runs: every sequence and the pool stay as they were.
+ * gvl_debug_set("varlen_extend", 0) (tests, A/B): one launch per sequence of the single-sequence kernels instead, the GEMMs still shared; same results. */
+int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds_new, const int* n_new,
+                              float* last_logits /* [n_seqs][vocab] device, may be NULL */, void* stream);
 /* A copy of a sequence AT ITS CURRENT LENGTH (beam search: HF's cache reorder, transformers GenerationMixin._reorder_cache [ext]): whole pages
  * are shared by reference, the partial last page is copied on `stream` (one launch over all layers); the clone then appends to its own pages. */
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream);
@@ -393,6 +403,8 @@ int gvl_prof_read(gvl_ctx* ctx, int category, double* total_ms, int64_t* launche
  *   "varlen_attn"      1 (default): the causal attention of a ragged prefill group (gvl_prefill_varlen) runs as ONE grid over the query blocks of all its sequences,
  *                      and so do its RoPE / KV-append and V^T-page passes (one launch each per layer); 2: the attention only (round 5), the passes per sequence;
  *                      0: one launch per sequence for all of them (rounds 2-4) -- bit-identical
+ *   "varlen_extend"    1 (default): a gvl_prefill_extend_varlen group with a cached prefix runs RoPE / KV append, the V^T pages and causal attention as ONE launch each
+ *                      per layer (a prefix per sequence inside the kernels); 0: one launch per sequence of the single-sequence extend kernels, GEMMs still shared -- bit-identical
  *   "norm_fused"       1 (default): RMSNorm in front of qkv / fc1 (InternVideo2) and qkv_proj / gate_up_proj / lm_head (LLM prefill AND, with bf16 decode weights,
  *                      the decode step) is fused into the GEMMs around it
  *                      (row statistics from the producing GEMM's epilogue, norm weight folded into the consuming GEMM's weight, row scale in its epilogue); 0: the
