@@ -1,9 +1,11 @@
 // gvl_llm.hip -- the decoder's launch sequences: ragged / batched prefill (+ the training-forward loss tail), the decode step and its hipGraph replay, the greedy decode
-// loop over a group of sequences (host code; the kernels live in gvl_gemm*.hip, gvl_attn.hip, gvl_decode.hip, gvl_elem.hip).  Restates (file:line in the reference):
+// loop over a group of sequences (host code; the kernels live in gvl_gemm*.hip, gvl_attn.hip, gvl_decode.hip, gvl_elem.hip).  Which launches a prefill group takes is
+// decided in gvl_prefill_plan.h, the decode-attention launch shape in gvl_attn_plan.h (both host-only, tested on the CPU).  Restates (file:line in the reference):
 //   LLM             models/modeling_phi3.py:1034-1095,1249-1383,1512-1526 / models/modeling_llama.py:699-760
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
 #include "gvl_attn_plan.h"
+#include "gvl_prefill_plan.h"
 
 namespace gvlm {
 
@@ -94,50 +96,78 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
 }
 
 // Prefill of nb = 1 .. 8 sequences together (lens[b] tokens each).  The decoder GEMMs run over the rows of all of them
-// (packed back to back, no padding); RoPE / KV append / causal attention run per sequence on its own pages -- as ONE launch with a
-// batch dimension when the lengths are equal, as nb launches otherwise.  Every kernel is batch-invariant, so each sequence's
-// result is bit-identical to a prefill on its own.
+// (packed back to back, no padding); RoPE / KV append / causal attention run per sequence on its own pages.  Every kernel is
+// batch-invariant, so each sequence's result is bit-identical to a prefill on its own.
 // pos0s (null = all 0): EXTEND -- sequence b already holds pos0s[b] tokens (a multiple of 64: whole pages, possibly shared with other sequences; 0 = empty); its new
 // rows take positions pos0s[b] .. pos0s[b] + lens[b] - 1 and attend to the cached prefix plus themselves.  One sequence: the single-sequence kernels at (qpos0, Sk).
-// A group with any prefix: the ragged launches with a prefix per sequence (gvl_launch_qkv_post_ext / gvl_launch_attention_ext, one grid each per layer), or, under
-// gvl_debug_set("varlen_extend", 0), one launch per sequence of the single-sequence kernels -- the GEMMs shared either way, every row bit-identical to the sequence's
-// own extend.  A group whose members are all empty takes exactly the launches it took before prefixes existed.
+// WHICH launches a group takes -- one per member, one with a batch dimension, one ragged grid, the same behind prefixes -- is prefill_plan's decision
+// (gvl_prefill_plan.h: pure, tested on the CPU); this function is plan, allocate, walk.  The GEMMs are shared whatever the form, and every row is bit-identical to the
+// sequence's own prefill / extend.  Everything the plan refuses is refused before the first launch.
 int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, const int* pos0s) {
   const gvl_config& f = ctx->cfg;
   const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
   const int qkvw = (H + 2 * KV) * Dr;
-  if (nb < 1 || nb > GVL_MAX_PREFILL_BATCH) return fail(ctx, GVL_ERR_ARG, "llm_prefill: batch must be 1 .. 8 sequences");
-  int p0[GVL_MAX_PREFILL_BATCH] = {};
-  bool ext = false;                                   // some member sits behind a cached prefix
-  for (int b = 0; b < nb; ++b) { p0[b] = pos0s ? pos0s[b] : 0; ext = ext || p0[b] != 0; if (p0[b] < 0 || (p0[b] & 63)) return fail(ctx, GVL_ERR_ARG, "llm_prefill: a cached prefix is whole pages"); }
-  if (ext && loss) return fail(ctx, GVL_ERR_ARG, "llm_prefill: no loss tail behind a cached prefix");
+  PrefillGeometry geo{};
+  geo.nb = nb;
+  for (int b = 0; b < nb && b < GVL_MAX_PREFILL_BATCH; ++b) { geo.lens[b] = lens[b]; geo.pos0[b] = pos0s ? pos0s[b] : 0; }
+  geo.rope_orig_max_pos = f.rope_orig_max_pos; geo.long_table = ctx->cos_l != nullptr; geo.loss = loss != nullptr; geo.page_id_cap = (int)(sizeof(IntList::v) / sizeof(int));
+  geo.hidden = Hd; geo.qkv_width = qkvw; geo.gate_up_width = 2 * I; geo.fused_weights = !ctx->ll.empty() && ctx->ll[0].qkvw_f;
+  PrefillPlan plan;
+  { const int rc = prefill_plan(geo, PrefillKnobs{ctx->dbg.varlen_attn, ctx->dbg.varlen_extend != 0, ctx->dbg.last_layer_tail != 0, ctx->dbg.norm_fused != 0}, &plan);
+    if (rc) return fail(ctx, GVL_ERR_ARG, prefill_refusal_reason(rc)); }
   for (int b = 0; b < nb; ++b) { const int rc = upload_table(ctx, *sqs[b], st); if (rc) return rc; }
-  int off[GVL_MAX_PREFILL_BATCH + 1]; off[0] = 0;
-  bool uniform = true;
-  for (int b = 0; b < nb; ++b) { off[b + 1] = off[b] + lens[b]; uniform = uniform && lens[b] == lens[0] && !ext; }   // the batched launch shares one qpos0: empty sequences only
-  const int M = off[nb], S0 = lens[0], P0 = (S0 + 63) / 64;
-  if (nb > 1 && uniform && nb * P0 > (int)(sizeof(IntList::v) / sizeof(int))) uniform = false;   // page-id list below holds 256 entries
+  const int* off = plan.off; const int* p0 = geo.pos0;
+  const int M = plan.M, S0 = lens[0], P0 = (S0 + 63) / 64;
   ArenaScope arena_scope(ctx->arena_l_off);
   LALLOC(x, bf16_t, (size_t)M * Hd); LALLOC(h, bf16_t, (size_t)M * Hd); LALLOC(qkv, bf16_t, (size_t)M * qkvw);
   LALLOC(att, bf16_t, (size_t)M * H * Dr); LALLOC(act, bf16_t, (size_t)M * I); LALLOC(Q, bf16_t, (size_t)M * H * D);
-  const int* table = sqs[0]->d_block_table;
-  int table_stride = sqs[0]->n_pages;
-  if (nb > 1 && uniform) {   // [nb][P] page ids of the batch, written by a stream-ordered kernel (ids passed by value: no host buffer lifetime)
+  const int* group_table = nullptr;
+  if (plan.batched_table) {   // [nb][P0] page ids of the batch, written by a stream-ordered kernel (ids passed by value: no host buffer lifetime)
     LALLOC(tb, int, (size_t)nb * P0);
     IntList l; l.n = nb * P0;
     for (int b = 0; b < nb; ++b) for (int p = 0; p < P0; ++p) l.v[b * P0 + p] = sqs[b]->pages[p];
     hipLaunchKernelGGL(fill_ints_kernel, dim3(1), dim3(256), 0, st, tb, l);
-    table = tb; table_stride = P0;
+    group_table = tb;
   }
   for (int b = 0; b < nb; ++b) RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(embeds[b], x + (size_t)off[b] * Hd, (size_t)lens[b] * Hd * 2, st));
   // fused RMSNorm (see iv2_encode): o_proj / down_proj leave the row statistics of the new residual stream, qkv_proj / gate_up_proj consume the raw
   // stream with the norm weight folded in and scale their accumulator rows; layer 0's input norm keeps the pass
   const int NBLK = Hd / 64;
-  const bool nf = ctx->dbg.norm_fused && Hd % 64 == 0 && ((f.heads + 2 * f.kv_heads) * ctx->l_Dr) % 16 == 0 && (2 * f.inter) % 16 == 0 && !ctx->ll.empty() && ctx->ll[0].qkvw_f;   // widths the staged epilogue takes
+  const bool nf = plan.nf;
   LALLOC(sq, float, (size_t)M * (nf ? NBLK : 1)); LALLOC(nrs, float, (size_t)M);
   const bf16_t* tail_rows = nullptr;                  // [nb][Hd]: the sequences' last rows after the last layer, when only they went through its MLP
-  // one (RoPE + KV append, attention) launch for the whole batch when the lengths agree, one per sequence otherwise
-  const int n_att = (nb == 1 || uniform) ? 1 : nb;
+  // The arguments of a planned launch.  Whose pages: the member's own block table (ONE), the group's [nb][P0] table (BATCHED), or a table, a row range and a prefix per
+  // member (RAGGED*: the whole group, rows packed back to back).
+  auto members = [&](auto& a, const PrefillStep& s) {
+    if (s.form == GVL_PREFILL_ONE) { a.block_table = sqs[s.first]->d_block_table; a.max_pages = sqs[s.first]->n_pages; }
+    else if (s.form == GVL_PREFILL_BATCHED) { a.block_table = group_table; a.max_pages = P0; }
+    else {
+      a.vl_n = s.count;
+      for (int u = 0; u < s.count; ++u) { a.vl_rows[u] = off[u]; a.vl_tables[u] = sqs[u]->d_block_table; a.vl_pos0[u] = p0[u]; }
+      a.vl_rows[s.count] = off[s.count];
+    }
+  };
+  auto post_args = [&](const PrefillStep& s, bf16_t* Kt, bf16_t* Vt) {
+    QkvPostArgs q; memset(&q, 0, sizeof(q)); q.qkv = qkv + (size_t)off[s.first] * qkvw; q.ld = qkvw; q.Q = Q + (size_t)off[s.first] * H * D; q.Kt = Kt; q.Vt = Vt;
+    q.B = s.B; q.S = s.S; q.H = H; q.KV = KV; q.Dr = Dr; q.D = D; q.mode = 2; q.cos = s.use_long ? ctx->cos_l : ctx->cos_s; q.sin = s.use_long ? ctx->sin_l : ctx->sin_s; q.pos0 = s.pos0;
+    members(q, s);
+    return q;
+  };
+  auto attn_args = [&](const PrefillStep& s, const bf16_t* Kt, const bf16_t* Vt) {
+    AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Q + (size_t)off[s.first] * H * D; a.Kt = Kt; a.Vt = Vt; a.O = att + (size_t)off[s.first] * H * Dr;
+    a.B = s.B; a.H = H; a.KV = KV; a.S = s.S; a.D = D; a.Dout = Dr; a.scale = 1.0f / sqrtf((float)Dr); a.causal = 1; a.Sk = s.Sk; a.qpos0 = s.pos0;
+    if (s.form == GVL_PREFILL_ONE || s.form == GVL_PREFILL_BATCHED) a.ring = ctx->dbg.attn_ring;   // the ring depth is a knob of the single-sequence kernels only
+    members(a, s);
+    return a;
+  };
+  // the work an attention launch is booked with: its members' own sums, whatever grid serves them
+  double attn_flops[GVL_PREFILL_MAX_STEPS] = {};
+  for (int i = 0; i < plan.n_steps; ++i) {
+    const PrefillStep& s = plan.steps[i];
+    if (s.kind != GVL_PREFILL_ATTN) continue;
+    if (s.form == GVL_PREFILL_ONE || s.form == GVL_PREFILL_BATCHED) attn_flops[i] = gvl_attn_flops(attn_args(s, nullptr, nullptr));
+    else for (int u = s.first; u < s.first + s.count; ++u) attn_flops[i] += gvl_attn_flops(attn_args(prefill_member_step(geo, GVL_PREFILL_ATTN, u), nullptr, nullptr));
+  }
   for (int l = 0; l < f.layers; ++l) {
     const LlmLayerW& w = ctx->ll[l];
     bf16_t* Kt = ctx->kpool + (size_t)l * ctx->layer_stride; bf16_t* Vt = ctx->vpool + (size_t)l * ctx->layer_stride;
@@ -148,83 +178,28 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
       RUN(GVL_PROF_OTHER, 0, gvl_launch_rmsnorm_bf16(x, w.ln1, h, M, Hd, f.rms_eps, st));
       GemmArgs g = gemm(h, Hd, w.qkvw, qkv, qkvw, M, qkvw, Hd); RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st));
     }
-    // ragged group: RoPE / KV append per sequence (HBM-bound passes), then ONE causal-attention grid over the query blocks of all sequences
-    // (AttnArgs.vl_*; 8 launches of ~900 blocks on 768 block slots each -> one of ~7 000: the causal tail is paid once) -- bit-identical per row
-    const bool vl_attn = n_att > 1 && ctx->dbg.varlen_attn && !ext;
-    // a group behind cached prefixes: the same two steps with a prefix per sequence (vl_pos0); one LongRoPE table per launch, judged by where a member ENDS -- a group
-    // on both sides of rope_orig_max_pos keeps RoPE / KV append per sequence and still shares the attention grid
-    const bool vl_ext = n_att > 1 && ext && ctx->dbg.varlen_extend;
-    bool vl_post_ext = vl_ext;
-    if (vl_post_ext && f.rope_orig_max_pos > 0 && ctx->cos_l) {
-      const bool l0 = p0[0] + lens[0] > f.rope_orig_max_pos;
-      for (int u = 1; u < nb; ++u) vl_post_ext = vl_post_ext && (p0[u] + lens[u] > f.rope_orig_max_pos) == l0;
-    }
-    if (vl_post_ext) {
-      const bool use_long = f.rope_orig_max_pos > 0 && p0[0] + lens[0] > f.rope_orig_max_pos && ctx->cos_l;
-      QkvPostArgs q; memset(&q, 0, sizeof(q)); q.qkv = qkv; q.ld = qkvw; q.Q = Q; q.Kt = Kt; q.Vt = Vt; q.B = 1; q.H = H; q.KV = KV; q.Dr = Dr; q.D = D; q.mode = 2;
-      q.cos = use_long ? ctx->cos_l : ctx->cos_s; q.sin = use_long ? ctx->sin_l : ctx->sin_s; q.vl_n = nb;
-      for (int u = 0; u < nb; ++u) { q.vl_rows[u] = off[u]; q.vl_tables[u] = sqs[u]->d_block_table; q.vl_pos0[u] = p0[u]; q.S = lens[u] > q.S ? lens[u] : q.S; }
-      q.vl_rows[nb] = off[nb];
-      RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post_ext(q, st));
-    }
-    // round 6: RoPE / KV append / V^T pages of the group in ONE launch each as well (QkvPostArgs.vl_*: 2 launches per layer instead of 2 per sequence -- 25 + 14 us
-    // launches of 3.5 k rows each, bit-identical per row); varlen_attn = 2 keeps them per sequence (round 5).  One table choice (LongRoPE short / long) per launch.
-    bool vl_post = vl_attn && ctx->dbg.varlen_attn == 1;
-    if (vl_post && f.rope_orig_max_pos > 0 && ctx->cos_l) {
-      const bool l0 = lens[0] > f.rope_orig_max_pos;
-      for (int u = 1; u < nb; ++u) vl_post = vl_post && (lens[u] > f.rope_orig_max_pos) == l0;
-    }
-    if (vl_post) {
-      const bool use_long = f.rope_orig_max_pos > 0 && lens[0] > f.rope_orig_max_pos && ctx->cos_l;
-      QkvPostArgs q; memset(&q, 0, sizeof(q)); q.qkv = qkv; q.ld = qkvw; q.Q = Q; q.Kt = Kt; q.Vt = Vt; q.B = 1; q.H = H; q.KV = KV; q.Dr = Dr; q.D = D; q.mode = 2;
-      q.cos = use_long ? ctx->cos_l : ctx->cos_s; q.sin = use_long ? ctx->sin_l : ctx->sin_s; q.vl_n = nb;
-      for (int u = 0; u < nb; ++u) { q.vl_rows[u] = off[u]; q.vl_tables[u] = sqs[u]->d_block_table; q.S = lens[u] > q.S ? lens[u] : q.S; }
-      q.vl_rows[nb] = off[nb];
-      RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(q, st));
-    }
-    for (int u = 0; u < n_att && !vl_post && !vl_post_ext; ++u) {
-      const int S = lens[u], B = n_att == 1 ? nb : 1;
-      const int* tbl = n_att == 1 ? table : sqs[u]->d_block_table;
-      const int tstride = n_att == 1 ? table_stride : sqs[u]->n_pages;
-      // LongRoPE: short factors up to the original context, long factors past it (modeling_phi3.py:381-385), per sequence
-      const int pos0 = p0[u];
-      const bool use_long = f.rope_orig_max_pos > 0 && pos0 + S > f.rope_orig_max_pos && ctx->cos_l;
-      bf16_t* Qu = Q + (size_t)off[u] * H * D;
-      { QkvPostArgs q; memset(&q, 0, sizeof(q)); q.qkv = qkv + (size_t)off[u] * qkvw; q.ld = qkvw; q.Q = Qu; q.Kt = Kt; q.Vt = Vt; q.block_table = tbl; q.max_pages = tstride;
-        q.B = B; q.S = S; q.H = H; q.KV = KV; q.Dr = Dr; q.D = D; q.mode = 2; q.cos = use_long ? ctx->cos_l : ctx->cos_s; q.sin = use_long ? ctx->sin_l : ctx->sin_s; q.pos0 = pos0;
-        RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(q, st)); }
-      if (vl_attn || vl_ext) continue;
-      { AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Qu; a.Kt = Kt; a.Vt = Vt; a.O = att + (size_t)off[u] * H * Dr; a.block_table = tbl; a.max_pages = tstride;
-        a.B = B; a.H = H; a.KV = KV; a.S = S; a.D = D; a.Dout = Dr; a.scale = 1.0f / sqrtf((float)Dr); a.causal = 1;
-        if (pos0) { a.Sk = pos0 + S; a.qpos0 = pos0; }
-        a.ring = ctx->dbg.attn_ring;
-        RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st)); }
-    }
-    if (vl_attn) {
-      AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Q; a.Kt = Kt; a.Vt = Vt; a.O = att; a.B = 1; a.H = H; a.KV = KV; a.D = D; a.Dout = Dr;
-      a.scale = 1.0f / sqrtf((float)Dr); a.causal = 1; a.vl_n = nb;
-      double fl = 0;
-      for (int u = 0; u < nb; ++u) { a.vl_rows[u] = off[u]; a.vl_tables[u] = sqs[u]->d_block_table; a.S = lens[u] > a.S ? lens[u] : a.S;
-        AttnArgs one = a; one.S = lens[u]; one.vl_n = 0; fl += gvl_attn_flops(one); }
-      a.vl_rows[nb] = off[nb]; a.max_pages = 0;
-      RUN(GVL_PROF_ATTN, fl, gvl_launch_attention(a, st));
-    }
-    if (vl_ext) {
-      AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Q; a.Kt = Kt; a.Vt = Vt; a.O = att; a.B = 1; a.H = H; a.KV = KV; a.D = D; a.Dout = Dr;
-      a.scale = 1.0f / sqrtf((float)Dr); a.causal = 1; a.vl_n = nb;
-      double fl = 0;
-      for (int u = 0; u < nb; ++u) { a.vl_rows[u] = off[u]; a.vl_tables[u] = sqs[u]->d_block_table; a.vl_pos0[u] = p0[u]; a.S = lens[u] > a.S ? lens[u] : a.S;
-        AttnArgs one = a; one.S = lens[u]; one.vl_n = 0; one.Sk = p0[u] + lens[u]; one.qpos0 = p0[u]; fl += gvl_attn_flops(one); }
-      a.vl_rows[nb] = off[nb];
-      RUN(GVL_PROF_ATTN, fl, gvl_launch_attention_ext(a, st));
+    // RoPE + KV append + V^T pages (post) and causal attention, as planned: the same steps in every layer
+    for (int i = 0; i < plan.n_steps; ++i) {
+      const PrefillStep& s = plan.steps[i];
+      if (s.kind == GVL_PREFILL_POST) {
+        const QkvPostArgs q = post_args(s, Kt, Vt);
+        switch (s.form) {
+          case GVL_PREFILL_RAGGED_EXT: RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post_ext(q, st)); break;
+          default: RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(q, st));
+        }
+      } else {
+        const AttnArgs a = attn_args(s, Kt, Vt);
+        switch (s.form) {
+          case GVL_PREFILL_RAGGED_EXT: RUN(GVL_PROF_ATTN, attn_flops[i], gvl_launch_attention_ext(a, st)); break;
+          default: RUN(GVL_PROF_ATTN, attn_flops[i], gvl_launch_attention(a, st));
+        }
+      }
     }
     { GemmArgs g = gemm(att, H * Dr, w.ow, x, Hd, M, Hd, H * Dr); g.resid = x; g.ldr = Hd; if (nf) { g.rowsq = sq; g.rowsq_ld = NBLK; }
       RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st)); }
-    // LAST layer, no loss request: nothing downstream reads the MLP output of any row but a sequence's last (the KV cache is complete after qkv_post, the
-    // lm_head takes last rows only) -- gate_up / down run on the nb last rows alone: -2 x M x hidden x 3 inter flops (2.1 % of the prefill's GEMM work at
-    // S = 3.5 k).  The rows are gathered (x and, fused norm, their row statistics); GEMM rows do not depend on their neighbours, so the logits are
-    // bit-identical to the full pass (asserted; gvl_debug_set("last_layer_tail", 0) = the full pass).
-    if (l == f.layers - 1 && !loss && ctx->dbg.last_layer_tail && (!nf || NBLK % 4 == 0)) {
+    // LAST layer's tail (PrefillPlan.tail says when): gate_up / down on the nb last rows alone.  The rows are gathered (x and, fused norm, their row statistics); GEMM
+    // rows do not depend on their neighbours, so the logits are bit-identical to the full pass (asserted; gvl_debug_set("last_layer_tail", 0) = the full pass).
+    if (l == f.layers - 1 && plan.tail) {
       int ids[GVL_MAX_PREFILL_BATCH];
       for (int b = 0; b < nb; ++b) ids[b] = off[b + 1] - 1;
       LALLOC(xl, bf16_t, (size_t)nb * Hd); LALLOC(actl, bf16_t, (size_t)nb * I);
@@ -257,7 +232,6 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
     // training forward (llava_next_video.py:598-614 -> Phi3ForCausalLM.forward labels branch, modeling_phi3.py:1512-1539): only rows
     // whose NEXT token carries a label need logits.  gather -> final RMSNorm -> lm_head GEMM (+bias, bf16 logits as under
     // autocast) -> f32 cross entropy per row; the host adds the rows up in order (deterministic).
-    if (nb != 1) return fail(ctx, GVL_ERR_ARG, "llm_prefill: loss tail takes one sequence");
     LALLOC(d_rows, int, loss->n); LALLOC(d_tgt, int, loss->n); LALLOC(d_nll, float, loss->n);
     LALLOC(hs, bf16_t, (size_t)kLossChunk * Hd); LALLOC(lg, bf16_t, (size_t)kLossChunk * f.vocab);
     HIPCHK(ctx, hipMemcpyAsync(d_rows, loss->h_rows, (size_t)loss->n * 4, hipMemcpyHostToDevice, st));
@@ -274,13 +248,13 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
   // last-row-only lm_head: final RMSNorm fused into the GEMV; one weight stream for the nb last rows
   const bf16_t* last = x + (size_t)(S0 - 1) * Hd;
   int last_stride = S0 * Hd;
-  if (tail_rows) { last = tail_rows; last_stride = Hd; }
-  else if (n_att > 1) {                    // ragged: gather the nb last rows (h is free by now)
+  if (plan.last_rows == GVL_PREFILL_LAST_TAIL) { last = tail_rows; last_stride = Hd; }
+  else if (plan.last_rows == GVL_PREFILL_LAST_GATHERED) {   // ragged: gather the nb last rows (h is free by now)
     for (int b = 0; b < nb; ++b) RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(x + (size_t)(off[b + 1] - 1) * Hd, h + (size_t)b * Hd, (size_t)Hd * 2, st));
     last = h; last_stride = Hd;
   }
-  for (int b0 = 0; b0 < nb;) {             // the GEMV holds 1, 2 or 4 vectors in LDS: chunks of 4 / 2 / 1 last rows (row results do not depend on the chunking)
-    const int nbc = nb - b0 >= 4 ? 4 : (nb - b0 >= 2 ? 2 : 1);
+  for (int c = 0, b0 = 0; c < plan.n_chunks; ++c) {   // the GEMV holds 1, 2 or 4 vectors in LDS: chunks of 4 / 2 / 1 last rows
+    const int nbc = plan.chunks[c];
     GemvArgs g; memset(&g, 0, sizeof(g)); g.W = ctx->l_headw; g.N = f.vocab; g.K = Hd; g.x = last + (size_t)b0 * last_stride; g.norm_w = ctx->l_norm; g.eps = f.rms_eps;
     g.batch = nbc; g.x_stride = last_stride; g.out_stride = f.vocab;
     g.bias = ctx->l_headb; g.out_f32 = ctx->d_logits + (size_t)b0 * f.vocab; RUN(GVL_PROF_GEMV, 2.0 * f.vocab * Hd, gvl_launch_gemv(g, st));

@@ -88,6 +88,7 @@ int build_visual(gvl_ctx* ctx, const float* clip_feats, const bf16_t* iv2_feats,
 // gvl_llm.hip
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
+// one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan
 int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr);   // pos0s: tokens each sequence already holds (null = none)
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st);
 int decode_group_size(const gvl_ctx* ctx, int left);

@@ -4,6 +4,7 @@
 //   splice          models/llava_next_video.py:568-596
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
+#include "gvl_prefill_plan.h"   // prefill_group_size: how the *_varlen entry points cut their sequences into llm_prefill groups
 
 std::string& gvl_create_error() { static std::string e; return e; }
 
@@ -592,16 +593,9 @@ int gvl_prefill_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint1
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_prefill_varlen", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
-  // groups of up to 8 sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
-  int i = 0;
-  while (i < n_seqs) {
-    const int left = n_seqs - i;
-    int B = left >= ctx->dbg.prefill_group ? ctx->dbg.prefill_group : left;
-    for (;;) {
-      long rows = 0; for (int b = 0; b < B; ++b) rows += seq_lens[i + b];
-      if (B == 1 || rows <= ctx->cfg.max_prefill) break;
-      --B;
-    }
+  // groups of up to prefill_group (gvl_debug_set) sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
+  for (int i = 0; i < n_seqs;) {
+    const int B = prefill_group_size(seq_lens + i, n_seqs - i, ctx->dbg.prefill_group, ctx->cfg.max_prefill);
     Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH];
     for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds[i + b]; }
     const int rc = llm_prefill(ctx, sqs, B, es, seq_lens + i, st);
@@ -627,12 +621,7 @@ int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, cons
   hipStream_t st = (hipStream_t)stream;
   // groups of up to GVL_MAX_PREFILL_BATCH sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
   for (int i = 0; i < n_seqs;) {
-    int B = n_seqs - i < GVL_MAX_PREFILL_BATCH ? n_seqs - i : GVL_MAX_PREFILL_BATCH;
-    for (;;) {
-      long rows = 0; for (int b = 0; b < B; ++b) rows += n_new[i + b];
-      if (B == 1 || rows <= ctx->cfg.max_prefill) break;
-      --B;
-    }
+    const int B = prefill_group_size(n_new + i, n_seqs - i, GVL_MAX_PREFILL_BATCH, ctx->cfg.max_prefill);
     Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH]; int pos0[GVL_MAX_PREFILL_BATCH];
     for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds_new[i + b]; pos0[b] = sqs[b]->pos; }
     const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0);

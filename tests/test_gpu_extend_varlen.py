@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from gpu_util import DEV, bf, check, llm_engine, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, prompts as P, serve, synth  # noqa: E402
+import prefill_plan as PP  # noqa: E402
 
 NEW = 9                      # greedy continuation tokens
 MODELS = {
@@ -46,7 +47,7 @@ def make_engine(name, **geo_kw):
 def make_ctx(name, **geo_kw):
     eng, geo = make_engine(name, **geo_kw)
     g = torch.Generator(device=DEV); g.manual_seed(17)
-    c = SimpleNamespace(eng=eng, geo=geo, name=name, refs={}, free0=eng.kv_info()["free_pages"])
+    c = SimpleNamespace(eng=eng, geo=geo, name=name, refs={}, work={}, free0=eng.kv_info()["free_pages"])
     c.commons = [(torch.randn((400, geo.hidden), device=DEV, generator=g) * 0.5).to(bf) for _ in range(2)]
     c.pool = (torch.randn((2048, geo.hidden), device=DEV, generator=g) * 0.5).to(bf)
     c.bases = open_bases(c)
@@ -101,6 +102,19 @@ def ragged(c, members, bases=None):
     return seqs, lg, [c.eng.seq_read(s, 0, 1) for s in seqs]
 
 
+def assert_planned_launches(c, members, form, want):
+    """The results cannot say which launches a group took (every form is bit-identical): the plan can, and the library's own count of attention launches must agree
+    with it -- booked with the same work whatever the form.  One extra prefill of the group, with gvl_prof_enable on."""
+    assert sum(k[2] for k in members) <= c.geo.max_prefill                   # one group
+    p = PP.of_geometry(c.geo, [k[2] for k in members], [k[1] for k in members], varlen_extend=form)
+    assert PP.forms(p) == want, (c.name, members, form, PP.forms(p))
+    (seqs, _, _), launches, work = PP.profiled_attn(c.eng, lambda: ragged(c, members))
+    for s in seqs:
+        c.eng.seq_free(s)
+    assert launches == c.geo.layers * PP.n_attn(p), f"{c.name} {members} varlen_extend {form}: {launches} attention launches, planned {PP.n_attn(p)} per layer"
+    assert c.work.setdefault(tuple(members), work) == work, f"{c.name} {members} varlen_extend {form}: attention work {work} vs {c.work[tuple(members)]} under the other form"
+
+
 def assert_members_equal_their_own_extend(c, members, what):
     want = [own(c, k) for k in members]
     seqs, lg, firsts = ragged(c, members)
@@ -120,6 +134,7 @@ def test_bit_identical_to_each_members_own_extend(ctx, n, form):
     ctx.eng.debug_set("varlen_extend", form)
     try:
         assert_members_equal_their_own_extend(ctx, GROUPS[n], f"group of {n}, varlen_extend {form}")
+        assert_planned_launches(ctx, GROUPS[n], form, (("RAGGED_EXT",),) * 2 if form else (("ONE",) * n,) * 2)
     finally:
         ctx.eng.debug_set("varlen_extend", 1)
     assert ctx.eng.kv_info()["free_pages"] == free
@@ -240,6 +255,10 @@ def test_members_on_both_sides_of_the_longrope_switch():
             assert_members_equal_their_own_extend(c, mixed, f"straddling rope_orig_max_pos, varlen_extend {form}")
             assert_members_equal_their_own_extend(c, [k for k in mixed if k[1] + k[2] > 200], f"all past rope_orig_max_pos, varlen_extend {form}")
             assert_members_equal_their_own_extend(c, [k for k in mixed if k[1] + k[2] <= 200], f"all within rope_orig_max_pos, varlen_extend {form}")
+            # the straddling group keeps RoPE / KV append per member (one factor set per launch) and still shares the attention grid
+            assert_planned_launches(c, mixed, form, ((("ONE",) * 6, ("RAGGED_EXT",)) if form else (("ONE",) * 6,) * 2))
+            for side in ([k for k in mixed if k[1] + k[2] > 200], [k for k in mixed if k[1] + k[2] <= 200]):
+                assert_planned_launches(c, side, form, (("RAGGED_EXT",),) * 2 if form else (("ONE",) * 3,) * 2)
         # the two factor sets do differ at these positions: the same rows behind the same prefix, ending on either side of the switch
         a, b = own(c, (1, 64, 136))[0], own(c, (1, 64, 137))[0]
         assert not torch.equal(a, b)

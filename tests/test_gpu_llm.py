@@ -19,6 +19,7 @@ from conftest import load_golden  # noqa: E402
 from gpu_util import DEV, bf, check, check_bf16_class, llm_engine, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, synth  # noqa: E402
 import attn_plan as A  # noqa: E402
+import prefill_plan as PP  # noqa: E402
 
 
 def _ocfg(geo):
@@ -246,7 +247,11 @@ def test_prefill_batch_is_bit_identical_to_single(which):
         single = [eng.generate_ids(x, new, None) for x in xs]
         for n in (2, 3, 4, 5, 7, 8):                           # one pass of the decoder GEMMs for up to 8 sequences; lm_head in chunks of 4 / 2 / 1 rows
             seqs = [eng.seq_alloc(S + new) for _ in range(n)]
-            eng.prefill_batch(seqs, xs[:n])
+            # the results cannot say which launches the group took: the plan can, and the library's own launch count must agree with it
+            p = PP.of_geometry(geo, (S,) * n)
+            assert PP.forms(p) == (("BATCHED",), ("BATCHED",)) and sum(p.chunks) == n, (S, n, p)
+            _, launches, _ = PP.profiled_attn(eng, lambda: eng.prefill_batch(seqs, xs[:n]))
+            assert launches == c["layers"] * PP.n_attn(p) == c["layers"], f"{which} S={S}: prefill_batch({n}) made {launches} attention launches"
             got = eng.decode_greedy_batch(seqs, new, None)
             for s in seqs:
                 eng.seq_free(s)
@@ -274,13 +279,22 @@ def test_prefill_varlen_is_bit_identical_to_single(which):
     for lens in ((7, 64, 61, 65, 3, 128, 66, 63), (1, 130, 2, 129, 1, 64, 5, 200), (33, 33, 40, 33, 33, 33, 33, 34)):   # page boundaries, single-token prompts, a near-uniform batch
         xs = [synth.det_tensor(f"pvar.{which}.{S}.{i}", (S, c["hidden"]), 0.5).to(DEV).to(bf) for i, S in enumerate(lens)]
         single = [eng.generate_ids(x, new, None) for x in xs]
+        work = {}
         for n, va in ((2, 1), (3, 1), (4, 1), (5, 1), (6, 1), (8, 1), (5, 2), (8, 2), (5, 0), (8, 0)):
             # varlen_attn = 1 (default): ONE causal-attention grid over the query blocks of all sequences (attn_fwd_kernel<.., VL = 1>) and ONE RoPE / KV-append
             # and V^T-page launch for the group (QkvPostArgs.vl_*); 2: the attention grid only; 0: one launch per sequence for everything.
             # Either way every row must carry the bits of its sequence's own prefill (single-sequence launches of the VL = 0 kernels).
             eng.debug_set("varlen_attn", va)
             seqs = [eng.seq_alloc(lens[i] + new) for i in range(n)]
-            eng.prefill_batch(seqs, xs[:n])
+            # ... so the results cannot say which launches the group took: the plan can (one group: its rows fit the workspace), and the library's own count of
+            # attention launches must agree with it -- booked with the same work whatever the form
+            assert sum(lens[:n]) <= geo.max_prefill
+            p = PP.of_geometry(geo, lens[:n], varlen_attn=va)
+            want = (("BATCHED",),) * 2 if len(set(lens[:n])) == 1 else {1: (("RAGGED",), ("RAGGED",)), 2: (("ONE",) * n, ("RAGGED",)), 0: (("ONE",) * n,) * 2}[va]
+            assert PP.forms(p) == want, (lens[:n], va, PP.forms(p))
+            _, launches, w = PP.profiled_attn(eng, lambda: eng.prefill_batch(seqs, xs[:n]))
+            assert launches == c["layers"] * PP.n_attn(p), f"{which} lens={lens[:n]} varlen_attn={va}: {launches} attention launches, planned {PP.n_attn(p)} per layer"
+            assert work.setdefault(n, w) == w, f"{which} lens={lens[:n]} varlen_attn={va}: attention work {w} vs {work[n]} under varlen_attn=1"
             got = eng.decode_greedy_batch(seqs, new, None)
             for s in seqs:
                 eng.seq_free(s)
