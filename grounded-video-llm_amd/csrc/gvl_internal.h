@@ -388,6 +388,13 @@ int gvl_launch_select_rows(const SelRowsArgs& a, hipStream_t st);
 struct BeamCandArgs { const float* rows; int n, k, row_stride, norm; float scores[GVL_MAX_DECODE_BATCH]; float* row_v; int* row_i; float* row_lp; float* vals; int* idx; float* proc; };
 int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st);
 int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st);      // rows [k][n] raw logits -> log-softmax, in place (beam_rows_kernel<true>'s arithmetic)
+// Teacher-forced scoring (score_rows_kernel, gvl_pick.hip): `rows` rows of n fp32 logits, ld floats apart, any number of them; targets [rows] on the device.  Per row: lp [rows]
+// the target's log-probability under the raw row, rank [rows] how many entries beat it (value descending, lower id first), and with top_n 1 .. 8 the best top_n finite
+// entries as top_ids / top_lp [rows][GVL_MAX_TOP_LOGPROBS], padded with (-1, -inf) (top_n == 0: never touched, may be null).
+struct ScoreRowsArgs { const float* logits; int n, ld, rows, top_n; const int* targets; float* lp; int* rank; int* top_ids; float* top_lp; };
+int gvl_launch_score_rows(const ScoreRowsArgs& a, hipStream_t st);
+// fp32 out[r][c0 + j] = x[r] . W[c0 + j] (+ bias[c0 + j]), r < rows, j < nc: the few lm_head columns past the last multiple of 16, which the score tail's GEMM does not take
+int gvl_launch_head_cols(const bf16_t* x, int ldx, const bf16_t* W, int K, const float* bias, float* out, int ld, int c0, int nc, int rows, hipStream_t st);
 // HF logits processors (repetition penalty -> no-repeat n-gram -> min length) on `batch` fp32 rows (stride ld), in place (gvl_logits.hip).  Row b's
 // history is hist[b][0 .. *len_ptrs[b]) (clamped to cap <= GVL_LOGITS_HIST_CAP; a null len_ptrs[b] = empty history); penalty 1 / ngram 0 /
 // min_new 0 switch a processor off; eos < 0 switches the min-length ban off.

@@ -15,7 +15,7 @@ size_t prefill_bytes(const gvl_ctx* c, int S) {
   size_t b = 0;
   b += 2 * al256((size_t)S * f.hidden * 2) + al256((size_t)S * qkvw * 2) + al256((size_t)S * f.heads * c->l_Dr * 2);
   b += al256((size_t)S * f.inter * 2) + al256((size_t)f.heads * S * c->l_D * 2);
-  b += al256((size_t)kLossChunk * f.vocab * 2) + al256((size_t)kLossChunk * f.hidden * 2) + 3 * al256((size_t)S * 4);   // loss tail (gvl_forward_loss)
+  b += al256((size_t)kLossChunk * f.vocab * 2 + kScoreChunk * 12) + al256((size_t)kLossChunk * f.hidden * 2) + 3 * al256((size_t)S * 4);   // loss tail (gvl_forward_loss) / score tail (fp32 rows, pitch rounded up to 4)
   b += al256((size_t)S * ((f.hidden + 63) / 64) * 4) + al256((size_t)S * 4);                                          // fused RMSNorm: row statistics + row scale
   b += (size_t)GVL_MAX_PREFILL_BATCH * (al256((size_t)f.hidden * 2) * 2 + al256((size_t)f.inter * 2) + al256(((f.hidden + 63) / 64) * 4) + 256) + 1024;   // last-layer tail rows
   return b + 4096;
@@ -103,7 +103,7 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
 // WHICH launches a group takes -- one per member, one with a batch dimension, one ragged grid, the same behind prefixes -- is prefill_plan's decision
 // (gvl_prefill_plan.h: pure, tested on the CPU); this function is plan, allocate, walk.  The GEMMs are shared whatever the form, and every row is bit-identical to the
 // sequence's own prefill / extend.  Everything the plan refuses is refused before the first launch.
-int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, const int* pos0s) {
+int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, const int* pos0s, const ScoreReq* score) {
   const gvl_config& f = ctx->cfg;
   const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
   const int qkvw = (H + 2 * KV) * Dr;
@@ -111,7 +111,7 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
   geo.nb = nb;
   for (int b = 0; b < nb && b < GVL_MAX_PREFILL_BATCH; ++b) { geo.lens[b] = lens[b]; geo.pos0[b] = pos0s ? pos0s[b] : 0; }
   geo.rope_orig_max_pos = f.rope_orig_max_pos; geo.long_table = ctx->cos_l != nullptr; geo.loss = loss != nullptr; geo.page_id_cap = (int)(sizeof(IntList::v) / sizeof(int));
-  geo.hidden = Hd; geo.qkv_width = qkvw; geo.gate_up_width = 2 * I; geo.fused_weights = !ctx->ll.empty() && ctx->ll[0].qkvw_f;
+  geo.hidden = Hd; geo.qkv_width = qkvw; geo.gate_up_width = 2 * I; geo.fused_weights = !ctx->ll.empty() && ctx->ll[0].qkvw_f; geo.score = score != nullptr;
   PrefillPlan plan;
   { const int rc = prefill_plan(geo, PrefillKnobs{ctx->dbg.varlen_attn, ctx->dbg.varlen_extend != 0, ctx->dbg.last_layer_tail != 0, ctx->dbg.norm_fused != 0}, &plan);
     if (rc) return fail(ctx, GVL_ERR_ARG, prefill_refusal_reason(rc)); }
@@ -244,6 +244,37 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
       RUN(GVL_PROF_OTHER, 0, gvl_launch_ce_rows(lg, f.vocab, d_tgt + r0, d_nll + r0, n, f.vocab, st));
     }
     HIPCHK(ctx, hipMemcpyAsync(loss->h_nll, d_nll, (size_t)loss->n * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (score && score->n > 0) {
+    // score tail (gvl_score_extend_varlen): the loss tail's walk over the scored rows of the whole group -- gather -> final RMSNorm -> lm_head GEMM -- with fp32 logits (+bias),
+    // the format the generate path selects from, and score_rows_kernel on every chunk.  ONE weight stream per kScoreChunk rows (the last-row GEMV below would take one per 4).
+    // A GEMM row does not depend on its neighbours, so a row's results do not depend on the chunk or the group it travels in.  The indices and targets go by value in the
+    // arguments of a stream-ordered fill (no host buffer lifetime); lg is the loss tail's reservation (kLossChunk bf16 rows = kScoreChunk fp32 rows) plus the row pitch's
+    // rounding up to 4 floats (prefill_bytes: kScoreChunk * 12 bytes).
+    // gvl_launch_gemm takes N % 4 == 0 and stages whole rows for N % 16 == 0; the fine-tuned vocabularies are 32 366 and 128 558: the GEMM computes the columns up to
+    // the last multiple of 16, head_cols_kernel the up to 15 behind it.
+    static_assert(kScoreChunk * 4 == kLossChunk * 2, "score tail: the fp32 logits chunk is the loss tail's reservation");
+    const int ldv = (f.vocab + 3) & ~3, n16 = f.vocab & ~15;
+    LALLOC(d_rows, int, score->n); LALLOC(d_tgt, int, score->n);
+    LALLOC(hs, bf16_t, (size_t)kScoreChunk * Hd); LALLOC(lg, float, (size_t)kScoreChunk * ldv);
+    for (int r0 = 0; r0 < score->n; r0 += 256) {
+      IntList lr, lt; lr.n = lt.n = score->n - r0 < 256 ? score->n - r0 : 256;
+      for (int i = 0; i < lr.n; ++i) { lr.v[i] = score->h_rows[r0 + i]; lt.v[i] = score->h_targets[r0 + i]; }
+      hipLaunchKernelGGL(fill_ints_kernel, dim3(1), dim3(256), 0, st, d_rows + r0, lr);
+      hipLaunchKernelGGL(fill_ints_kernel, dim3(1), dim3(256), 0, st, d_tgt + r0, lt);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(ctx, GVL_ERR_HIP, "score tail: row list upload failed");
+    for (int r0 = 0; r0 < score->n; r0 += kScoreChunk) {
+      const int n = score->n - r0 < kScoreChunk ? score->n - r0 : kScoreChunk;
+      RUN(GVL_PROF_OTHER, 0, gvl_launch_gather_rows(x, d_rows + r0, hs, n, Hd, st));
+      RUN(GVL_PROF_OTHER, 0, gvl_launch_rmsnorm_bf16(hs, ctx->l_norm, h, n, Hd, f.rms_eps, st));      // h is free by now; n <= M rows
+      if (n16 > 0) { GemmArgs g = gemm(h, Hd, ctx->l_headw, lg, ldv, n, n16, Hd); g.bias = ctx->l_headb; g.out_f32 = 1; RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st)); }
+      if (n16 < f.vocab) RUN(GVL_PROF_OTHER, 0, gvl_launch_head_cols(h, Hd, ctx->l_headw, Hd, ctx->l_headb, lg, ldv, n16, f.vocab - n16, n, st));
+      ScoreRowsArgs sr; memset(&sr, 0, sizeof(sr)); sr.logits = lg; sr.n = f.vocab; sr.ld = ldv; sr.rows = n; sr.top_n = score->top_n; sr.targets = d_tgt + r0;
+      sr.lp = score->d_lp + r0; sr.rank = score->d_rank + r0;
+      if (score->top_n > 0) { sr.top_ids = score->d_top_ids + (size_t)r0 * GVL_MAX_TOP_LOGPROBS; sr.top_lp = score->d_top_lp + (size_t)r0 * GVL_MAX_TOP_LOGPROBS; }
+      RUN(GVL_PROF_OTHER, 0, gvl_launch_score_rows(sr, st));
+    }
   }
   // last-row-only lm_head: final RMSNorm fused into the GEMV; one weight stream for the nb last rows
   const bf16_t* last = x + (size_t)(S0 - 1) * Hd;

@@ -72,6 +72,10 @@ inline GemmArgs gemm(const bf16_t* A, int lda, const bf16_t* W, void* C, int ldc
 constexpr int kLossChunk = 128;    // rows of logits materialised at a time by the training-forward loss tail
 // labelled rows of a training forward: device lists (row index into the sequence, target id) and the per-row nll output
 struct LossReq { int n; const int* h_rows; const int* h_targets; float* h_nll; };
+constexpr int kScoreChunk = 64;    // rows of fp32 logits a score tail materialises at a time: kScoreChunk * 4 bytes = kLossChunk * 2, the loss tail's reservation serves both
+// scored rows of a prefill group (gvl_score_extend_varlen): host lists of n packed row indices (into the group's rows) and their target ids, read before the call returns;
+// device outputs [n] (lists [n][GVL_MAX_TOP_LOGPROBS], top_n 1 .. 8 only), written on the call's stream
+struct ScoreReq { int n; const int* h_rows; const int* h_targets; int top_n; float* d_lp; int* d_rank; int* d_top_ids; float* d_top_lp; };
 
 // workspace sizes of one call (gvl_create sizes the arenas from them)
 size_t clip_bytes(const gvl_ctx* c, int n);
@@ -89,7 +93,8 @@ int build_visual(gvl_ctx* ctx, const float* clip_feats, const bf16_t* iv2_feats,
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
 // one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan
-int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr);   // pos0s: tokens each sequence already holds (null = none)
+int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr,
+                const ScoreReq* score = nullptr);   // pos0s: tokens each sequence already holds (null = none); score: rows of the group to score on the way (not with loss)
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st);
 int decode_group_size(const gvl_ctx* ctx, int left);
 int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, int32_t* const* out_ids, int* const* n_out, hipStream_t st);

@@ -632,6 +632,50 @@ int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, cons
   return 0;
 }
 
+// gvl_prefill_extend_varlen that also scores given next ids on the way: the same members, groups, refusals and final states; per group the scored rows' packed indices and
+// targets go to llm_prefill as a ScoreReq.  The targets and top_n are checked with everything else, before the first launch.
+int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds_new, const int* n_new, const int32_t* const* next_ids_host, int top_n,
+                            float* lp_dev, int32_t* rank_dev, int32_t* top_ids_dev, float* top_lp_dev, int* n_scored, float* last_logits, void* stream) {
+  REQUIRE_READY(ctx->has_llm, "gvl_score_extend_varlen");
+  if (!seq_ids || !embeds_new || !n_new || !next_ids_host || !lp_dev || !rank_dev || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs)
+    return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad arguments");
+  if (top_n < 0 || top_n > GVL_MAX_TOP_LOGPROBS || (top_n > 0 && (!top_ids_dev || !top_lp_dev)))
+    return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: top_n must be 0 .. 8 (top lists needed for > 0)");
+  for (int i = 0; i < n_seqs; ++i) {
+    const int id = seq_ids[i];
+    if (!ctx->lookup(id) || !embeds_new[i] || !next_ids_host[i]) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad seq / embeds / next ids");
+    const Seq& sq = ctx->seqs[id];
+    if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_score_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
+    if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad length");
+    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_score_extend_varlen", SEQ_DUPLICATE);
+    for (int r = 0; r < n_new[i]; ++r) {
+      const int32_t y = next_ids_host[i][r];
+      if (y != -100 && (y < 0 || y >= ctx->cfg.vocab)) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: next id out of range");
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int done = 0;                                        // scored rows of the groups before this one: where its packed outputs start
+  std::vector<int> rows, tgt;
+  for (int i = 0; i < n_seqs;) {
+    const int B = prefill_group_size(n_new + i, n_seqs - i, GVL_MAX_PREFILL_BATCH, ctx->cfg.max_prefill);
+    Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH]; int pos0[GVL_MAX_PREFILL_BATCH];
+    rows.clear(); tgt.clear();
+    for (int b = 0, off = 0; b < B; off += n_new[i + b], ++b) {
+      sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds_new[i + b]; pos0[b] = sqs[b]->pos;
+      for (int r = 0; r < n_new[i + b]; ++r) if (next_ids_host[i + b][r] != -100) { rows.push_back(off + r); tgt.push_back(next_ids_host[i + b][r]); }
+    }
+    ScoreReq sr{(int)rows.size(), rows.data(), tgt.data(), top_n, lp_dev + done, rank_dev + done,
+                top_n > 0 ? top_ids_dev + (size_t)done * GVL_MAX_TOP_LOGPROBS : nullptr, top_n > 0 ? top_lp_dev + (size_t)done * GVL_MAX_TOP_LOGPROBS : nullptr};
+    const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0, &sr);
+    if (rc) return rc;
+    if (last_logits) HIPCHK(ctx, hipMemcpyAsync(last_logits + (size_t)i * ctx->cfg.vocab, ctx->d_logits, (size_t)B * ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
+    done += sr.n;
+    i += B;
+  }
+  if (n_scored) *n_scored = done;
+  return 0;
+}
+
 int gvl_prefill_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds, int S, void* stream) {
   if (!ctx) return GVL_ERR_ARG;
   if (n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_batch: bad arguments");

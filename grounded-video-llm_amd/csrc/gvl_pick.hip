@@ -1,5 +1,5 @@
 // gvl_pick.hip -- token selection of a decode step: greedy argmax, the sampler, per-row selection with HF's further warpers, the log-probability pass and the beam-search
-// candidates.  gfx950 only.  One block of 1024 threads per logit row; every pass re-reads the row from L2.
+// candidates; and, at the end of the file, the scores of GIVEN ids (score_rows_kernel).  gfx950 only.  One block of 1024 threads per logit row; every pass re-reads the row from L2.
 // Shared stages, each a __device__ __forceinline__ function that exists once: pick_row_max (both samplers, beam_row_norm), pick_greedy_row (argmax_kernel and the greedy
 // rows of select_rows_kernel; pick_wave_pair / pick_pair_finish inside it), pick_radix_select (top-k in both samplers, the beam candidates), pick_commit (all four
 // selections), lp_after_draw (both samplers) and the launcher launch_lp_mode.  The kernel declares its LDS and tid and hands them in; inputs go by value, results come
@@ -579,5 +579,104 @@ int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st) {
 int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st) {
   if (!rows || n < 1 || k < 1 || k > GVL_MAX_DECODE_BATCH) return -1;
   hipLaunchKernelGGL(beam_normalize_kernel, dim3(k), dim3(1024), 0, st, rows, n);
+  return CHECK_LAUNCH();
+}
+// ---- teacher-forced scoring (ScoreRowsArgs; gvl_score_extend_varlen's tail and gvl_op_score_rows): what the raw distribution of a row says about a GIVEN id.  One block
+// per row of fp32 logits, any number of rows.  Per row, with t the target, m the row maximum and lz = logf(sum exp(s - m)):
+//   lp    (s_t - m) - lz.  m is pick_row_max's, the sum is strided per thread and finished by smp_block_sum -- lp_row_pass<1>'s order at thr = 0, inv_temp = 1 (beam_row_norm's
+//         too) -- so lp is bit for bit what greedy selection reports for the row when t is its argmax (s_t - m = 0), and the top list's entry for t when t is listed.
+//   rank  how many entries beat t in the strict order (value descending, lower id first): an integer count over keys (beam_key: -0.0 folded onto +0.0, as float compares see
+//         them) and indices, over ALL entries, -inf included.  0: t is the greedy choice.  A target at -inf gets lp = -inf and its rank by the same order.
+//   top   TOP only: the best top_n finite entries as (id, log-probability), padded with (-1, -inf): lp_insert per thread, lp_wave_merge per wave and across the waves -- argmax_kernel<2>'s lists.  The
+//         merge-and-store is WRITTEN OUT below in lp_row_pass's words: as a function shared with lp_row_pass it changed the instruction streams of argmax_kernel<2>,
+//         sample_kernel<2> and select_rows_kernel<2> (profiles/score_rows_asm.txt), the rule the sampled row's stages already live by (file header).
+// A target outside [0, n) never indexes the row: lp = -inf, rank = -1 (the entry points refuse such a target on the host where they see it).  Every barrier is reached by
+// the whole block: TOP is a template parameter and nothing else guards one.
+template <bool TOP>
+__global__ __launch_bounds__(1024) void score_rows_kernel(const ScoreRowsArgs a) {
+  __shared__ float shf[16];
+  __shared__ int shc[16];
+  const int b = blockIdx.x, tid = threadIdx.x, n = a.n;
+  const float* l = a.logits + (size_t)b * (size_t)a.ld;
+  const int t = a.targets[b];
+  const bool in = t >= 0 && t < n;
+  const float st = in ? l[t] : -INFINITY;
+  const unsigned kt = beam_key(st);
+  const float m = pick_row_max(l, n, tid, shf);
+  [[maybe_unused]] float tv[GVL_MAX_TOP_LOGPROBS]; [[maybe_unused]] int ti[GVL_MAX_TOP_LOGPROBS];
+  if constexpr (TOP) {
+#pragma unroll
+    for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j) { tv[j] = -INFINITY; ti[j] = -1; }
+  }
+  float z = 0.f; int c = 0;
+  for (int i = tid; i < n; i += 1024) {
+    const float v = l[i];
+    z += expf((v - m) * 1.0f);
+    const unsigned k = beam_key(v);
+    c += (k > kt || (k == kt && i < t)) ? 1 : 0;
+    if constexpr (TOP) if (fabsf(v) < INFINITY) lp_insert(tv, ti, v, i);
+  }
+  const float lz = logf(smp_block_sum(z, shf));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);          // integers: the order of the reduction cannot matter
+  if ((tid & 63) == 0) shc[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) r += shc[w];
+    a.lp[b] = in ? __fsub_rn(__fsub_rn(st, m), lz) : -INFINITY;
+    a.rank[b] = in ? r : -1;
+  }
+  if constexpr (TOP) {          // lp_row_pass<2>'s merge and store, in its words
+    __shared__ float s_tv[16 * GVL_MAX_TOP_LOGPROBS];
+    __shared__ int s_ti[16 * GVL_MAX_TOP_LOGPROBS];
+    float wv[GVL_MAX_TOP_LOGPROBS]; int wi[GVL_MAX_TOP_LOGPROBS];
+    lp_wave_merge(tv, ti, wv, wi);
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) { s_tv[(tid >> 6) * GVL_MAX_TOP_LOGPROBS + r] = wv[r]; s_ti[(tid >> 6) * GVL_MAX_TOP_LOGPROBS + r] = wi[r]; }
+    }
+    __syncthreads();
+    if (tid < 64) {
+      const int lane = tid;
+#pragma unroll
+      for (int j = 0; j < GVL_MAX_TOP_LOGPROBS; ++j) {
+        tv[j] = lane < 16 ? s_tv[lane * GVL_MAX_TOP_LOGPROBS + j] : -INFINITY; ti[j] = lane < 16 ? s_ti[lane * GVL_MAX_TOP_LOGPROBS + j] : -1;
+      }
+      lp_wave_merge(tv, ti, wv, wi);
+      float v = -INFINITY; int id = -1;
+#pragma unroll
+      for (int r = 0; r < GVL_MAX_TOP_LOGPROBS; ++r) if (lane == r) { v = wv[r]; id = wi[r]; }
+      if (lane < GVL_MAX_TOP_LOGPROBS) {
+        const bool ok = lane < a.top_n && id >= 0;
+        a.top_ids[(size_t)b * GVL_MAX_TOP_LOGPROBS + lane] = ok ? id : -1;
+        a.top_lp[(size_t)b * GVL_MAX_TOP_LOGPROBS + lane] = ok ? (v - m) * 1.0f - lz : -INFINITY;
+      }
+    }
+  }
+}
+int gvl_launch_score_rows(const ScoreRowsArgs& a, hipStream_t st) {
+  if (!a.logits || !a.targets || !a.lp || !a.rank || a.n < 1 || a.ld < a.n || a.rows < 0 || a.top_n < 0 || a.top_n > GVL_MAX_TOP_LOGPROBS ||
+      (a.top_n > 0 && (!a.top_ids || !a.top_lp))) return -1;
+  if (a.rows == 0) return 0;
+  if (a.top_n > 0) hipLaunchKernelGGL(score_rows_kernel<true>, dim3(a.rows), dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL(score_rows_kernel<false>, dim3(a.rows), dim3(1024), 0, st, a);
+  return CHECK_LAUNCH();
+}
+// The lm_head columns the GEMM leaves to the score tail: gvl_launch_gemm's contract is N % 4 == 0 and its whole-row epilogue wants N % 16 == 0, the fine-tuned vocabularies
+// are 32 366 and 128 558.  out[r][c0 + j] = sum_k x[r][k] * W[c0 + j][k] (+ bias[c0 + j]) for r < rows, j < nc: one wave per (row, column), bf16 operands, fp32
+// accumulation in a fixed order (strided per lane, then the butterfly) -- a pure function of the row, like the GEMM's columns beside it.
+__global__ __launch_bounds__(64) void head_cols_kernel(const bf16_t* x, int ldx, const bf16_t* W, int K, const float* bias, float* out, int ld, int c0, int nc) {
+  const int r = blockIdx.x / nc, c = c0 + blockIdx.x % nc, lane = threadIdx.x;
+  const bf16_t* xr = x + (size_t)r * ldx; const bf16_t* wc = W + (size_t)c * K;
+  float acc = 0.f;
+  for (int k = lane; k < K; k += 64) acc += bf2f(xr[k]) * bf2f(wc[k]);
+  acc = wave_sum(acc);
+  if (lane == 0) out[(size_t)r * ld + c] = bias ? acc + bias[c] : acc;
+}
+int gvl_launch_head_cols(const bf16_t* x, int ldx, const bf16_t* W, int K, const float* bias, float* out, int ld, int c0, int nc, int rows, hipStream_t st) {
+  if (!x || !W || !out || K < 1 || ldx < K || c0 < 0 || nc < 1 || ld < c0 + nc || rows < 1) return -1;
+  hipLaunchKernelGGL(head_cols_kernel, dim3(rows * nc), dim3(64), 0, st, x, ldx, W, K, bias, out, ld, c0, nc);
   return CHECK_LAUNCH();
 }

@@ -19,13 +19,14 @@ enum PrefillLastRows : int {   // where the lm_head reads the members' last rows
   GVL_PREFILL_LAST_GATHERED,      // copied together first (ragged rows are not equally spaced)
   GVL_PREFILL_LAST_TAIL,          // the rows the last layer's tail left
 };
-enum PrefillRefusal : int { GVL_PREFILL_BAD_BATCH = -1, GVL_PREFILL_BAD_PREFIX = -2, GVL_PREFILL_LOSS_BEHIND_PREFIX = -3, GVL_PREFILL_LOSS_GROUP = -4 };
+enum PrefillRefusal : int { GVL_PREFILL_BAD_BATCH = -1, GVL_PREFILL_BAD_PREFIX = -2, GVL_PREFILL_LOSS_BEHIND_PREFIX = -3, GVL_PREFILL_LOSS_GROUP = -4, GVL_PREFILL_SCORE_AND_LOSS = -5 };
 inline const char* prefill_refusal_reason(int rc) {
   switch (rc) {
     case GVL_PREFILL_BAD_BATCH: return "llm_prefill: batch must be 1 .. 8 sequences";
     case GVL_PREFILL_BAD_PREFIX: return "llm_prefill: a cached prefix is whole pages";
     case GVL_PREFILL_LOSS_BEHIND_PREFIX: return "llm_prefill: no loss tail behind a cached prefix";
     case GVL_PREFILL_LOSS_GROUP: return "llm_prefill: loss tail takes one sequence";
+    case GVL_PREFILL_SCORE_AND_LOSS: return "llm_prefill: a score tail and a loss tail exclude each other";
     default: return "";
   }
 }
@@ -38,6 +39,7 @@ struct PrefillGeometry {         // only what the decision reads
   int page_id_cap;               // page ids one by-value list carries (IntList: 256)
   int hidden, qkv_width, gate_up_width;   // the fused RMSNorm's widths: hidden, (H + 2 KV) * Dr, 2 * inter
   bool fused_weights;            // the norm-folded weights were loaded
+  bool score;                    // a score tail is requested (gvl_score_extend_varlen): any group, behind any prefixes.  LAST member: a value-initialised geometry reads false
 };
 struct PrefillKnobs { int varlen_attn; bool varlen_extend, last_layer_tail, norm_fused; };   // gvl_debug_set
 
@@ -76,6 +78,7 @@ inline int prefill_plan(const PrefillGeometry& g, const PrefillKnobs& k, Prefill
   const int nb = g.nb;
   bool ext = false;                                    // some member sits behind a cached prefix
   for (int b = 0; b < nb; ++b) { if (g.pos0[b] < 0 || (g.pos0[b] & 63)) return GVL_PREFILL_BAD_PREFIX; ext = ext || g.pos0[b] != 0; }
+  if (g.score && g.loss) return GVL_PREFILL_SCORE_AND_LOSS;
   if (ext && g.loss) return GVL_PREFILL_LOSS_BEHIND_PREFIX;
   if (g.loss && nb != 1) return GVL_PREFILL_LOSS_GROUP;
   PrefillPlan p{};
@@ -122,8 +125,9 @@ inline int prefill_plan(const PrefillGeometry& g, const PrefillKnobs& k, Prefill
 
   // LAST layer, no loss request: nothing downstream reads the MLP output of any row but a member's last (the KV cache is complete after the post launches, the
   // lm_head takes last rows only) -- gate_up / down run on the nb last rows alone: -2 x M x hidden x 3 inter flops (2.1 % of the prefill's GEMM work at S = 3.5 k).
-  // The gathered row statistics of the fused norm are finished four partial sums at a time.
-  p.tail = !g.loss && k.last_layer_tail && (!p.nf || (g.hidden / 64) % 4 == 0);
+  // The gathered row statistics of the fused norm are finished four partial sums at a time.  A score tail reads rows anywhere in the group, so it keeps the full pass
+  // (the MLP on scored rows + last rows only is left out on purpose: DESIGN.md 3.9).
+  p.tail = !g.loss && !g.score && k.last_layer_tail && (!p.nf || (g.hidden / 64) % 4 == 0);
   p.last_rows = p.tail ? GVL_PREFILL_LAST_TAIL : (nb == 1 || uniform) ? GVL_PREFILL_LAST_STRIDED : GVL_PREFILL_LAST_GATHERED;
   for (int b0 = 0; b0 < nb; b0 += p.chunks[p.n_chunks - 1]) p.chunks[p.n_chunks++] = nb - b0 >= 4 ? 4 : (nb - b0 >= 2 ? 2 : 1);   // row results do not depend on the chunking
   *out = p;

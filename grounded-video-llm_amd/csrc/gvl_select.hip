@@ -305,4 +305,19 @@ int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, cons
   return 0;
 }
 
+// score_rows_kernel on raw rows, any number of them (the targets live on the device: one outside [0, n) scores lp = -inf, rank = -1 and never indexes its row)
+int gvl_op_score_rows(gvl_ctx* ctx, const float* logits_dev, int n, int ld, int rows, const int32_t* targets_dev, int top_n, float* lp_dev, int32_t* rank_dev,
+                      int32_t* top_ids_dev, float* top_lp_dev, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!logits_dev || !targets_dev || !lp_dev || !rank_dev || n < 1 || ld < n || rows < 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_score_rows: bad arguments");
+  if (top_n < 0 || top_n > GVL_MAX_TOP_LOGPROBS || (top_n > 0 && (!top_ids_dev || !top_lp_dev)))
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_score_rows: top_n must be 0 .. 8 (top lists needed for > 0)");
+  hipStream_t st = (hipStream_t)stream;
+  ScoreRowsArgs sr; memset(&sr, 0, sizeof(sr));
+  sr.logits = logits_dev; sr.n = n; sr.ld = ld; sr.rows = rows; sr.top_n = top_n; sr.targets = targets_dev; sr.lp = lp_dev; sr.rank = rank_dev;
+  if (top_n > 0) { sr.top_ids = top_ids_dev; sr.top_lp = top_lp_dev; }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_score_rows(sr, st));
+  return 0;
+}
+
 }  // extern "C"

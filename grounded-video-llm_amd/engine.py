@@ -354,6 +354,56 @@ class Engine:
         self._chk(self.lib.gvl_prefill_extend_varlen(self.ctx, ids, n, ptrs, lens, _ptr(lg), self.stream), "gvl_prefill_extend_varlen")
         return lg
 
+    def score_extend_batch(self, seqs: Sequence[int], embeds_new: Sequence[torch.Tensor], next_ids: Sequence[Sequence[int]], top_n: int = 0, want_logits: bool = False):
+        """prefill_extend_batch that also scores given ids (gvl_score_extend_varlen): next_ids[i][r] is the id that new row r of member i must predict (the token fed at
+        r + 1), -100 = not scored.  -> (lp f32 [n], rank int32 [n], top_ids int32 [n, 8] | None, top_lp f32 [n, 8] | None) on the device, packed: members in call
+        order, scored rows in row order (top lists with top_n 1 .. 8 only); with want_logits also the members' last-row logits [len(seqs), vocab].  Asynchronous.
+        Every member ends as after prefill_extend_batch of the same rows."""
+        es = [e.contiguous() for e in embeds_new]
+        assert all(e.dtype == bf and e.dim() == 2 for e in es) and len(es) == len(seqs) == len(next_ids)
+        assert all(len(t) == e.shape[0] for t, e in zip(next_ids, es)), "next_ids must cover every new row"
+        n = len(seqs)
+        ids = (C.c_int * n)(*[int(s) for s in seqs])
+        ptrs = (C.c_void_p * n)(*[e.data_ptr() for e in es])
+        lens = (C.c_int * n)(*[int(e.shape[0]) for e in es])
+        tg = [(C.c_int32 * max(len(t), 1))(*[int(v) for v in t]) for t in next_ids]
+        tgp = (C.POINTER(C.c_int32) * n)(*[C.cast(t, C.POINTER(C.c_int32)) for t in tg])
+        ns = sum(1 for t in next_ids for v in t if int(v) != -100)
+        cap = max(ns, 1)                                    # (an empty tensor has no address to hand over)
+        lp = torch.empty((cap,), dtype=torch.float32, device=self.device)[:ns]
+        rank = torch.empty((cap,), dtype=torch.int32, device=self.device)[:ns]
+        ti = torch.empty((cap, LPR.MAX_TOP), dtype=torch.int32, device=self.device)[:ns] if top_n else None
+        tv = torch.empty((cap, LPR.MAX_TOP), dtype=torch.float32, device=self.device)[:ns] if top_n else None
+        lg = torch.empty((n, self.geo.vocab), dtype=torch.float32, device=self.device) if want_logits else None
+        got = C.c_int(-1)
+        self._chk(self.lib.gvl_score_extend_varlen(self.ctx, ids, n, ptrs, lens, tgp, int(top_n), _ptr(lp), _ptr(rank), _ptr(ti), _ptr(tv), C.byref(got), _ptr(lg),
+                                                   self.stream), "gvl_score_extend_varlen")
+        assert got.value == ns
+        return (lp, rank, ti, tv, lg) if want_logits else (lp, rank, ti, tv)
+
+    def op_score_rows(self, logits: torch.Tensor, targets, top_n: int = 0, out=None):
+        """gvl_op_score_rows on fp32 rows [R, n] (any R; the row stride is taken from the tensor): (lp f32 [R], rank int32 [R], top_ids int32 [R, 8], top_lp f32 [R, 8]) on
+        the device.  targets: a host sequence -- one outside [0, n) raises ValueError before anything runs -- or an int32 device tensor, taken as it is (the kernel scores
+        such a target lp = -inf, rank = -1 and never indexes its row).  out: the four output tensors to write into (default: fresh ones filled with NaN / -2; what a call
+        does not produce keeps its fill -- with top_n = 0 both lists)."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.device.type == "cuda"
+        R, n = logits.shape
+        if isinstance(targets, torch.Tensor) and targets.device.type == "cuda":
+            tg = targets.to(torch.int32).contiguous()
+        else:
+            tl = [int(t) for t in targets]
+            if any(t < 0 or t >= n for t in tl):
+                raise ValueError(f"op_score_rows: a target outside [0, {n})")
+            tg = torch.tensor(tl, dtype=torch.int32, device=self.device)
+        assert tg.shape == (R,)
+        if out is None:
+            out = (torch.full((R,), float("nan"), dtype=torch.float32, device=self.device), torch.full((R,), -2, dtype=torch.int32, device=self.device),
+                   torch.full((R, LPR.MAX_TOP), -2, dtype=torch.int32, device=self.device), torch.full((R, LPR.MAX_TOP), float("nan"), dtype=torch.float32, device=self.device))
+        lp, rank, ti, tv = out
+        self._chk(self.lib.gvl_op_score_rows(self.ctx, _ptr(logits), n, int(logits.stride(0)) if R > 1 else n, R, _ptr(tg), int(top_n), _ptr(lp), _ptr(rank), _ptr(ti), _ptr(tv),
+                                             self.stream), "gvl_op_score_rows")
+        return lp, rank, ti, tv
+
     def prefill(self, seq: int, embeds: torch.Tensor, want_logits: bool = False) -> Optional[torch.Tensor]:
         embeds = embeds.contiguous()
         logits = torch.empty((self.geo.vocab,), dtype=torch.float32, device=self.device) if want_logits else None

@@ -478,6 +478,30 @@ class LLAVA_NEXT_VIDEO:
             return texts
         return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps)
 
+    def _shared_prefix(self, rows: Sequence[Sequence[int]], n_vis: int, lens: Sequence[int], limit: int) -> int:
+        """THE shared-prefix rule of generate_shared and score: how many leading EMBEDDING rows the id rows `rows` (one image slot each, n_vis visual rows) have in
+        common, at most `limit`, rounded down to 128 (whole KV pages AND whole query blocks, so that every later row is computed exactly as in a full prefill); 0 =
+        nothing worth sharing (one row, rows that part ways before 128, or the LongRoPE condition below).  lens: the rows each sequence will hold in the end."""
+        if len(rows) < 2:
+            return 0
+        # common prefix in EMBEDDING rows: ids before the image slot must agree, then the visual rows, then the ids after it
+        k = list(rows[0]).index(P.IMAGE_TOKEN_INDEX)
+        if any(list(r[:k + 1]) != list(rows[0][:k + 1]) for r in rows):
+            return 0
+        tail = 0
+        while all(k + 1 + tail < len(r) for r in rows) and len({r[k + 1 + tail] for r in rows}) == 1:
+            tail += 1
+        prefix = min(k + n_vis + tail, limit) // 128 * 128
+        if prefix < 128:
+            return 0
+        # LongRoPE (modeling_phi3.py:381-385) picks ONE factor set per forward from the TOTAL length: a full prefill of a prompt longer than
+        # original_max_position_embeddings ropes every row -- the shared ones too -- with the long factors, while a base prefill of a prefix
+        # that still fits the original context would cache its K with the short ones.  Share only when base and forks agree.
+        omax = self.geo.rope_orig_max_pos if self.geo.rope_long is not None else 0
+        if omax > 0 and prefix <= omax and any(n > omax for n in lens):
+            return 0
+        return prefix
+
     def _generate_shared_prefix(self, rows: List[List[int]], vis: torch.Tensor, max_new: int,
                                 processors: Optional[List["LP.Processors"]] = None, logprobs: Optional[int] = None):
         """Prompts about one video share the system prompt and the visual tokens: the common prefix (rounded down to 128 tokens = whole KV pages AND
@@ -490,23 +514,9 @@ class LLAVA_NEXT_VIDEO:
         if len(rows) < 2:
             return None
         embs = [eng.splice(r, vis) for r in rows]
-        # common prefix in EMBEDDING rows: ids before the image slot must agree, then the visual rows, then the ids after it
-        k = rows[0].index(P.IMAGE_TOKEN_INDEX)
-        if any(r[:k + 1] != rows[0][:k + 1] for r in rows):
-            return None
-        n_vis = vis.shape[0]
-        tail = 0
-        while all(k + 1 + tail < len(r) for r in rows) and len({r[k + 1 + tail] for r in rows}) == 1:
-            tail += 1
-        shared = min(k + n_vis + tail, min(e.shape[0] for e in embs) - 1)     # every prompt keeps at least one row of its own (its last row feeds the first token)
-        prefix = shared // 128 * 128
-        if prefix < 128:
-            return None
-        # LongRoPE (modeling_phi3.py:381-385) picks ONE factor set per forward from the TOTAL length: a full prefill of a prompt longer than
-        # original_max_position_embeddings ropes every row -- the shared ones too -- with the long factors, while a base prefill of a prefix
-        # that still fits the original context would cache its K with the short ones.  Share only when base and forks agree.
-        omax = self.geo.rope_orig_max_pos if self.geo.rope_long is not None else 0
-        if omax > 0 and prefix <= omax and any(e.shape[0] > omax for e in embs):
+        lens = [e.shape[0] for e in embs]
+        prefix = self._shared_prefix(rows, vis.shape[0], lens, min(lens) - 1)     # every prompt keeps at least one row of its own (its last row feeds the first token)
+        if not prefix:
             return None
         self.last_shared_prefix = prefix
         eos = getattr(self.tokenizer, "eos_token_id", None)
@@ -529,6 +539,75 @@ class LLAVA_NEXT_VIDEO:
                 eng.seq_free(s_)
             if base is not None:
                 eng.seq_free(base)
+
+    @torch.inference_mode()
+    def score(self, samples, prompts: Sequence[str], continuations: Optional[Sequence[str]] = None, continuation_ids: Optional[Sequence[Sequence[int]]] = None,
+              top_logprobs: Optional[int] = None, append_eos: bool = False, *, share_prefix: bool = True) -> List["SC.ScoreOutput"]:
+        """How likely the model finds GIVEN answers about ONE video: pair i = (prompts[i], continuations[i]) -> a scoring.ScoreOutput (per-token log-probabilities
+        and ranks of the continuation's ids under teacher forcing, their sum and mean, and with top_logprobs = N the N best alternatives per position).  A
+        multiple-choice question passes the same prompt k times with the k options; ranking needs no sampling.  continuations are tokenised without BOS (or pass
+        continuation_ids); append_eos also scores the closing EOS.  The distribution is the raw model's: no logits processors, token rules or warpers.
+        One vision encode; the pairs share their common prefix as generate_shared's prompts do (_shared_prefix: one base prefill, forks), then up to 8 pairs run
+        their remaining rows in ONE ragged decoder pass that scores on the way (Engine.score_extend_batch); with nothing to share the same call runs on empty
+        sequences.  A pair's numbers do not depend on the other pairs or on sharing (share_prefix=False: never share; same numbers).  prompt + continuation beyond
+        max_seq (or the prefill workspace) raises ValueError: truncation is never applied, it would score another text."""
+        from . import scoring as SC
+        if samples["spatial_pixel_values"].shape[0] != 1:
+            raise ValueError("score takes the pixel tensors of one video")
+        if (continuations is None) == (continuation_ids is None):
+            raise ValueError("score: pass exactly one of continuations and continuation_ids")
+        top_n = SC.resolve_top(top_logprobs)
+        tk = self.tokenizer
+        eos, bos = getattr(tk, "eos_token_id", None), getattr(tk, "bos_token_id", None)
+        if continuations is not None:
+            tok = (lambda s: tk(s).input_ids) if hasattr(tk("x"), "input_ids") else tk
+            conts = [SC.continuation_ids(tok, c, bos, append_eos, eos) for c in continuations]
+        else:
+            conts = [SC.with_eos(c, append_eos, eos) for c in continuation_ids]
+        if len(conts) != len(prompts) or not conts:
+            raise ValueError("score: one continuation per prompt, at least one pair")
+        if any(t < 0 or t >= self.geo.vocab for c in conts for t in c):
+            raise ValueError("score: a continuation id outside the vocabulary")
+        rows = [self.tokenizer_image_token(t) for t in prompts]          # never truncated
+        n_vis = self._n_visual(samples)
+        n_prompt = [len(r) - 1 + n_vis for r in rows]
+        for p_, c in zip(n_prompt, conts):                               # the over-length error comes before any device work
+            SC.assemble(p_, c, 0, self.geo.max_seq)
+        full = [list(r) + c for r, c in zip(rows, conts)]
+        lens = [p_ + len(c) for p_, c in zip(n_prompt, conts)]
+        prefix = self._shared_prefix(full, n_vis, lens, min(n_prompt) - 1) if share_prefix else 0
+        if max(lens) - prefix > self.geo.max_prefill:
+            raise ValueError(f"score: {max(lens) - prefix} rows of one pair exceed the prefill workspace (max_prefill = {self.geo.max_prefill})")
+        self.last_shared_prefix = prefix
+        eng = self.engine
+        eng.set_sampling(False)                                          # the members' first tokens (never read here) are picked by the defaults: all off
+        eng.set_logits_processors(*LP.OFF.args())
+        eng.set_token_rules(None)
+        eng.set_logprobs(-1)
+        vis = self.encode_images(samples)[0]
+        parts, base = [], None
+        try:
+            if prefix:
+                base = eng.seq_alloc(prefix)
+                eng.prefill(base, eng.splice(full[0], vis)[:prefix])
+            for g in range(0, len(full), 8):                             # a group: its remaining rows in ONE decoder pass, scored on the way
+                seqs = []
+                try:
+                    embs, nxt = [], []
+                    for i in range(g, min(g + 8, len(full))):
+                        sl, ids = SC.assemble(n_prompt[i], conts[i], prefix, self.geo.max_seq)
+                        embs.append(eng.splice(full[i], vis)[sl])
+                        nxt.append(ids)
+                        seqs.append(eng.seq_fork(base, prefix, lens[i]) if prefix else eng.seq_alloc(lens[i]))
+                    parts.append(eng.score_extend_batch(seqs, embs, nxt, top_n))
+                finally:
+                    for s_ in seqs:
+                        eng.seq_free(s_)
+        finally:
+            if base is not None:
+                eng.seq_free(base)
+        cat = lambda j: torch.cat([p_[j] for p_ in parts]).cpu().tolist()    # (the copy synchronises)
+        return SC.fold(conts, cat(0), cat(1), cat(2) if top_n else None, cat(3) if top_n else None, top_n)
 
     # training forward (SURVEY.md §8 f4) --------------------------------------------------------------------------
     @torch.inference_mode()

@@ -152,6 +152,25 @@ int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds_new, int
  * gvl_debug_set("varlen_extend", 0) (tests, A/B): one launch per sequence of the single-sequence kernels instead, the GEMMs still shared; same results. */
 int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds_new, const int* n_new,
                               float* last_logits /* [n_seqs][vocab] device, may be NULL */, void* stream);
+/* gvl_prefill_extend_varlen that also SCORES given ids on the way (teacher forcing): how likely the model finds a given continuation, without sampling.  Member rules,
+ * group formation, the refusals before anything runs and the final state of every member (logits, first token, KV pages, random stream) are gvl_prefill_extend_varlen's; a
+ * member holding 0 tokens is scored from scratch.
+ * next_ids_host[i][r], r < n_new[i] (host arrays, read before the call returns): the id that new row r of member i must PREDICT -- the next-token convention: row r's target
+ * is the token fed at r + 1 (the last row's is whatever follows the rows of this call, if the caller knows it) -- or -100 = row r is not scored.  HF's label convention
+ * (labels aligned with the rows and shifted inside) cannot be used: behind a cached prefix the hidden state in front of the first new row is not there to predict it.
+ * Per scored row, from the fp32 logits of the row (final norm, lm_head + bias; the raw distribution: no processors, rules or warpers):
+ *   lp_dev    log-softmax at the target.  Bit for bit what greedy selection's log-probability reports for such a row when the target is its argmax.
+ *   rank_dev  how many entries beat the target in the order (value descending, lower id first); 0 = the target is the greedy choice.
+ *   top_n 1 .. 8: top_ids_dev / top_lp_dev [.][8], the best top_n finite entries, padded with (-1, -inf) -- gvl_set_logprobs' lists; top_n = 0: both may be NULL, untouched.
+ * The outputs are PACKED device arrays: members in call order, each member's scored rows in row order; *n_scored (may be NULL) = their count, which the caller can also
+ * count from next_ids_host and must size the arrays for.  A scored row's values do not depend on the group or the call it travels in.  Its logits come from a GEMM over
+ * the scored rows (one stream of the head's weights per 64 rows), so they differ from gvl_prefill's last_logits of the prompt truncated at that row by rounding (a
+ * separate bf16 norm pass against the fused one), not bitwise.  Every row of the group runs the last layer's MLP (the default prefill runs it on last rows only).
+ * GVL_ERR_ARG also for a target other than -100 outside [0, vocab) and for top_n outside 0 .. 8 -- raised, like every refusal, with every sequence and the pool untouched.
+ * All work is enqueued on `stream`; nothing is synchronised. */
+int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds_new, const int* n_new, const int32_t* const* next_ids_host,
+                            int top_n, float* lp_dev, int32_t* rank_dev, int32_t* top_ids_dev, float* top_lp_dev, int* n_scored,
+                            float* last_logits /* [n_seqs][vocab] device, may be NULL */, void* stream);
 /* A copy of a sequence AT ITS CURRENT LENGTH (beam search: HF's cache reorder, transformers GenerationMixin._reorder_cache [ext]): whole pages
  * are shared by reference, the partial last page is copied on `stream` (one launch over all layers); the clone then appends to its own pages. */
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream);
@@ -491,6 +510,11 @@ int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, 
  * may be null): 1 where an entry is finite and in the row's final kept set (a greedy row keeps every finite entry), else 0. */
 int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, const gvl_sampling* rows, const int32_t* steps_dev, const int* top_n,
                        int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, uint8_t* kept_dev, void* stream);
+/* gvl_score_extend_varlen's row kernel on its own (operator tests): `rows` rows (any number) of n fp32 logits, ld >= n floats apart, targets_dev [rows]; lp_dev / rank_dev
+ * [rows] and, top_n 1 .. 8, top_ids_dev / top_lp_dev [rows][8] as described there (top_n = 0: untouched, may be NULL).  A target outside [0, n) never indexes its row:
+ * lp = -inf, rank = -1. */
+int gvl_op_score_rows(gvl_ctx* ctx, const float* logits_dev, int n, int ld, int rows, const int32_t* targets_dev, int top_n, float* lp_dev, int32_t* rank_dev,
+                      int32_t* top_ids_dev, float* top_lp_dev, void* stream);
 /* One beam-search step's candidates on their own (operator tests; hosts that keep their own books): rows f32 device, row b of n entries at rows + b * row_stride
  * (row_stride 0: every beam reads row 0, as the first step does; otherwise >= n), k = num_beams 2 .. 16, n >= 2 k; beam_scores_host [k].  rows_are_logprobs = 0: raw
  * logits, the log-softmax runs inside; 1: processed log-probabilities.  vals_dev / idx_dev / proc_dev [2 k] (device): value t, flat index beam * n + token, and the
