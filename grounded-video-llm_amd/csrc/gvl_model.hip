@@ -870,6 +870,20 @@ int gvl_op_gemm_rows(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, uint16_
   RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st));
   return 0;
 }
+// The row-remapping store of build_visual at operator level: GEMM row m lands at row (m / grp_rows) * grp_stride + m % grp_rows + row_off of C.
+int gvl_op_gemm_grouped(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, void* C, int M, int N, int K, const float* bias, const float* gamma,
+                        const void* resid, int act, int out_f32, float* rowsq, int rowsq_ld, int grp_rows, int grp_stride, int row_off, int tile_cfg,
+                        void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!A || !W || !C) return fail(ctx, GVL_ERR_ARG, "gvl_op_gemm_grouped: null operand");
+  if (grp_rows < 1 || row_off < 0 || (long)row_off + grp_rows > grp_stride) return fail(ctx, GVL_ERR_ARG, "gvl_op_gemm_grouped: needs grp_rows >= 1, row_off >= 0 and row_off + grp_rows <= grp_stride");
+  hipStream_t st = (hipStream_t)stream;
+  GemmArgs g = gemm(A, K, W, C, act == GVL_ACT_SILU_MUL ? N / 2 : N, M, N, K);
+  g.bias = bias; g.gamma = gamma; g.resid = resid; g.ldr = N; g.act = act; g.out_f32 = out_f32; g.round_pre_resid = 1; g.tile_cfg = tile_cfg;
+  g.rowsq = rowsq; g.rowsq_ld = rowsq_ld; g.grp_rows = grp_rows; g.grp_stride = grp_stride; g.row_off = row_off;
+  RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st));
+  return 0;
+}
 // W' = bf16(W diag(gamma)) and rs = rsqrt(sum of the blocks [b0, b0 + nblk) / cols + eps): the two small kernels around those epilogues
 int gvl_op_fold_gamma(gvl_ctx* ctx, const uint16_t* W, const uint16_t* gamma, uint16_t* Wo, int64_t rows, int cols, void* stream) {
   if (!ctx) return GVL_ERR_ARG;
@@ -916,6 +930,95 @@ int gvl_op_rmsnorm(gvl_ctx* ctx, const uint16_t* x, const uint16_t* w, uint16_t*
   if (!ctx) return GVL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   RUN(GVL_PROF_OTHER, 0, gvl_launch_rmsnorm_bf16(x, w, y, rows, cols, eps, st));
+  return 0;
+}
+// ---- the vision front end and the glue of the visual prefix at operator level (tests/test_gpu_vision_ops.py; fields and geometry: include/gvl.h) ----------------
+// The patch embedding of either tower by EITHER path, chosen by the caller: a geometry the fused launcher refuses is an error here, not a fall-back.
+int gvl_op_patch_embed(gvl_ctx* ctx, const gvl_patch_embed* p, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_patch_embed: null descriptor");
+  const char* bad = nullptr;
+  if (p->mode != 0 && p->mode != 1) bad = "mode is 0 (CLIP) or 1 (InternVideo2)";
+  else if (p->path != 0 && p->path != 1) bad = "path is 0 (fused) or 1 (three passes)";
+  else if (p->n <= 0 || p->T <= 0 || p->image <= 0 || p->patch <= 0 || p->C <= 0 || p->Kp <= 0) bad = "n, T, image, patch, C and Kp must be positive";
+  else if (p->image % p->patch) bad = "image must be a multiple of patch";
+  else if (p->Kp % 8 || p->Kp < 3 * p->patch * p->patch) bad = "Kp must be a multiple of 8 and hold 3 patch^2 columns";
+  else if (!p->px || !p->W || !p->cls || !p->pos || !p->out) bad = "px, W, cls, pos and out are required";
+  else if (p->mode == 0 && (!p->lnw || !p->lnb)) bad = "CLIP needs lnw and lnb";
+  else if (p->mode == 0 && p->T != 1) bad = "CLIP has one frame per image (T = 1)";
+  else if (p->mode == 1 && !p->bias) bad = "InternVideo2 needs the conv bias";
+  else if (p->path == 0 && p->im2col) bad = "the fused path forms no im2col matrix";
+  else if (p->path == 1 && (p->Kp % 64 || p->C % 8 || (p->mode == 0 && p->C > 4096))) bad = "the three passes need Kp % 64 == 0 and C % 8 == 0 (CLIP: C <= 4096)";
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_patch_embed: ") + bad);
+  const int g = p->image / p->patch;
+  const long M_l = (long)p->n * p->T * g * g;
+  if (M_l > (1l << 30)) return fail(ctx, GVL_ERR_ARG, "gvl_op_patch_embed: too many patch rows");
+  const int M = (int)M_l, TL = p->T * g * g, C = p->C;
+  hipStream_t st = (hipStream_t)stream;
+  ArenaScope arena_scope(ctx->arena_off);
+  if (p->path == 0) {
+    if (C % 16 || p->patch > 16 || (p->patch & 1)) return fail(ctx, GVL_ERR_ARG, "gvl_op_patch_embed: geometry outside the fused kernel");
+    AALLOC(Wt, bf16_t, (size_t)(C / 16) * (3 * p->patch / 2) * 512);
+    PatchEmbedArgs e; memset(&e, 0, sizeof(e)); e.px = p->px; e.Wt = Wt; e.n_img = p->n; e.T = p->T; e.image = p->image; e.patch = p->patch; e.C = C;
+    e.M = M; e.S = TL + 1; e.mode = p->mode; e.eps = p->eps;
+    if (p->mode == 0) { e.cls_f32 = (const float*)p->cls; e.pos_f32 = (const float*)p->pos; e.lnw = p->lnw; e.lnb = p->lnb; e.x_f32 = (float*)p->out; }
+    else { e.bias = p->bias; e.cls_bf = (const bf16_t*)p->cls; e.pos_bf = (const bf16_t*)p->pos; e.x_bf = (bf16_t*)p->out; }
+    RUN(GVL_PROF_OTHER, 0, gvl_retile_patch_weight(p->W, Wt, C, p->Kp, p->patch, st));
+    const int rc = gvl_launch_patch_embed(e, st);
+    if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, rc == -1 ? "gvl_op_patch_embed: geometry outside the fused kernel" : "gvl_op_patch_embed: launch failed");
+    return 0;
+  }
+  bf16_t* pA = p->im2col;
+  if (!pA) { AALLOC(pA_, bf16_t, (size_t)M * p->Kp); pA = pA_; }
+  AALLOC(pO, bf16_t, (size_t)M * C);
+  GemmArgs gm = gemm(pA, p->Kp, p->W, pO, C, M, C, p->Kp);
+  if (p->mode == 1) gm.bias = p->bias;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_patchify(p->px, pA, p->n, p->T, p->image, p->patch, p->Kp, st));
+  RUN(GVL_PROF_GEMM, gvl_gemm_flops(gm), gvl_launch_gemm(gm, st));
+  if (p->mode == 0) RUN(GVL_PROF_OTHER, 0, gvl_launch_clip_embed_ln(pO, (const float*)p->cls, (const float*)p->pos, p->lnw, p->lnb, (float*)p->out, p->n, TL, C, p->eps, st));
+  else RUN(GVL_PROF_OTHER, 0, gvl_launch_iv2_embed(pO, (const bf16_t*)p->cls, (const bf16_t*)p->pos, (bf16_t*)p->out, p->n, TL, C, st));
+  return 0;
+}
+int gvl_op_patchify(gvl_ctx* ctx, const float* px, uint16_t* A, int n, int T, int image, int patch, int Kp, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!px || !A || n <= 0 || T <= 0 || image <= 0 || patch <= 0 || Kp <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_patchify: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_patchify(px, A, n, T, image, patch, Kp, st));
+  return 0;
+}
+int gvl_op_hd_merge(gvl_ctx* ctx, const float* f, const float* sub_gn, uint16_t* out, int n, int C, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!f || !sub_gn || !out || n <= 0 || C <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_hd_merge: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_hd_merge(f, sub_gn, out, n, C, st));
+  return 0;
+}
+int gvl_op_pool_spatial(gvl_ctx* ctx, const float* f, uint16_t* out, int n, int C, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!f || !out || n <= 0 || C <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_pool_spatial: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_pool_spatial(f, out, n, C, st));
+  return 0;
+}
+int gvl_op_pool_temporal(gvl_ctx* ctx, const uint16_t* f, uint16_t* out, int n, int T, int C, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!f || !out || n <= 0 || T <= 0 || C <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_pool_temporal: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_pool_temporal(f, out, n, T, C, st));
+  return 0;
+}
+int gvl_op_strip_cls(gvl_ctx* ctx, const void* x, void* y, int n, int S, int C, int elem_bytes, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!x || !y || n <= 0 || S < 2 || C <= 0 || (elem_bytes != 2 && elem_bytes != 4)) return fail(ctx, GVL_ERR_ARG, "gvl_op_strip_cls: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_strip_cls(x, y, n, S, C, elem_bytes, st));
+  return 0;
+}
+int gvl_op_bcast_row(gvl_ctx* ctx, const uint16_t* row, uint16_t* dst, int n, int stride_rows, int row_off, int cols, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!row || !dst || n <= 0 || cols <= 0 || row_off < 0 || row_off >= stride_rows) return fail(ctx, GVL_ERR_ARG, "gvl_op_bcast_row: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_bcast_row(row, dst, n, stride_rows, row_off, cols, st));
   return 0;
 }
 // operator-level entry for the WHOLE GemvArgs surface (tests/test_gpu_decode_proj.py): row-major operands in, private tiled / quantised copies made here, every launcher

@@ -570,6 +570,63 @@ class Engine:
                                             _ptr(rowscale), _ptr(sq), N // 64 if want_rowsq else 0, tile_cfg, self.stream), "gvl_op_gemm_rows")
         return (Cc, sq) if want_rowsq else Cc
 
+    def op_gemm_grouped(self, A, W, out, grp_rows, grp_stride, row_off, bias=None, gamma=None, resid=None, act=L.ACT_NONE, rowsq=None, tile_cfg=0):
+        """gvl_op_gemm_grouped: GEMM row m is stored at row (m / grp_rows) * grp_stride + m % grp_rows + row_off of `out` (bf16 or f32, contiguous,
+        ceil(M / grp_rows) * grp_stride rows, written in place: the caller pre-fills it).  rowsq [M, N // 64] f32: refused by the library."""
+        M, K = A.shape
+        N = W.shape[0]
+        assert out.is_contiguous() and out.dtype in (bf, torch.float32)
+        self._chk(self.lib.gvl_op_gemm_grouped(self.ctx, _ptr(A.contiguous()), _ptr(W.contiguous()), _ptr(out), M, N, K, _ptr(bias), _ptr(gamma), _ptr(resid), act,
+                                               1 if out.dtype == torch.float32 else 0, _ptr(rowsq), N // 64 if rowsq is not None else 0, int(grp_rows),
+                                               int(grp_stride), int(row_off), tile_cfg, self.stream), "gvl_op_gemm_grouped")
+        return out
+
+    def op_patch_embed(self, mode, path, px, W, cls, pos, out, patch, bias=None, lnw=None, lnb=None, eps=1e-5, im2col=None):
+        """gvl_op_patch_embed (include/gvl.h): mode 0 CLIP / 1 InternVideo2, path 0 fused / 1 three passes.  px f32 [n, 3, T, image, image], W bf16 [C, Kp];
+        `out` (and `im2col`, path 1) are written in place: the caller allocates and pre-fills them.  Raises GvlError (status ERR_ARG) on a refusal."""
+        d = L.GvlPatchEmbed()
+        n, _, T, image, _ = px.shape
+        keep = [t if t is None else t.contiguous() for t in (px, W, bias, cls, pos, lnw, lnb)]
+        assert out.is_contiguous() and (im2col is None or im2col.is_contiguous())
+        d.mode, d.path, d.n, d.T, d.image, d.patch, d.C, d.Kp, d.eps = mode, path, n, T, image, patch, W.shape[0], W.shape[1], float(eps)
+        for name, t in zip(("px", "W", "bias", "cls", "pos", "lnw", "lnb"), keep):
+            setattr(d, name, None if t is None else t.data_ptr())
+        d.out, d.im2col = out.data_ptr(), None if im2col is None else im2col.data_ptr()
+        self._chk(self.lib.gvl_op_patch_embed(self.ctx, C.byref(d), self.stream), "gvl_op_patch_embed")
+        return out
+
+    def op_patchify(self, px, out, patch):
+        """px f32 [n, 3, T, image, image] -> out bf16 [n T (image / patch)^2, Kp] (in place)."""
+        n, _, T, image, _ = px.shape
+        self._chk(self.lib.gvl_op_patchify(self.ctx, _ptr(px.contiguous()), _ptr(out), n, T, image, patch, out.shape[-1], self.stream), "gvl_op_patchify")
+        return out
+
+    def op_hd_merge(self, f, sub_gn, out):
+        """f f32 [n, 576, C], sub_gn f32 [4 C] -> out bf16 [n, 156, 4 C] (in place)."""
+        self._chk(self.lib.gvl_op_hd_merge(self.ctx, _ptr(f.contiguous()), _ptr(sub_gn.contiguous()), _ptr(out), f.shape[0], f.shape[2], self.stream), "gvl_op_hd_merge")
+        return out
+
+    def op_pool_spatial(self, f, out):
+        """f f32 [n, 576, C] -> out bf16 [n, 64, C] (in place)."""
+        self._chk(self.lib.gvl_op_pool_spatial(self.ctx, _ptr(f.contiguous()), _ptr(out), f.shape[0], f.shape[2], self.stream), "gvl_op_pool_spatial")
+        return out
+
+    def op_pool_temporal(self, f, out):
+        """f bf16 [n, T, 256, C] -> out bf16 [n, T, 16, C] (in place)."""
+        self._chk(self.lib.gvl_op_pool_temporal(self.ctx, _ptr(f.contiguous()), _ptr(out), f.shape[0], f.shape[1], f.shape[3], self.stream), "gvl_op_pool_temporal")
+        return out
+
+    def op_strip_cls(self, x, out):
+        """x [n, S, C] f32 or bf16 -> out [n, S - 1, C] (in place)."""
+        self._chk(self.lib.gvl_op_strip_cls(self.ctx, _ptr(x.contiguous()), _ptr(out), x.shape[0], x.shape[1], x.shape[2], x.element_size(), self.stream),
+                  "gvl_op_strip_cls")
+        return out
+
+    def op_bcast_row(self, row, dst, n, stride_rows, row_off):
+        """dst bf16 [n * stride_rows, cols]: rows s * stride_rows + row_off receive `row` (in place)."""
+        self._chk(self.lib.gvl_op_bcast_row(self.ctx, _ptr(row.contiguous()), _ptr(dst), n, stride_rows, row_off, row.shape[-1], self.stream), "gvl_op_bcast_row")
+        return dst
+
     def op_fold_gamma(self, W, gamma):
         W = W.contiguous()
         out = torch.empty_like(W)

@@ -69,6 +69,13 @@ class GvlDecodeProj(C.Structure):
                 ("w_deq", C.c_void_p), ("w_scale", C.c_void_p)]
 
 
+class GvlPatchEmbed(C.Structure):
+    """gvl_patch_embed (include/gvl.h): the patch embedding of either vision tower by either path, for the operator tests."""
+    _fields_ = [("mode", C.c_int32), ("path", C.c_int32), ("n", C.c_int32), ("T", C.c_int32), ("image", C.c_int32), ("patch", C.c_int32), ("C", C.c_int32),
+                ("Kp", C.c_int32), ("eps", C.c_float), ("px", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("cls", C.c_void_p), ("pos", C.c_void_p),
+                ("lnw", C.c_void_p), ("lnb", C.c_void_p), ("out", C.c_void_p), ("im2col", C.c_void_p)]
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "gvl_create": (C.c_int, [C.POINTER(GvlConfig), C.POINTER(C.c_void_p)]),
@@ -117,6 +124,15 @@ _SIGS = {
                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gvl_op_gemm_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_gemm_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_patch_embed": (C.c_int, [C.c_void_p, C.POINTER(GvlPatchEmbed), C.c_void_p]),
+    "gvl_op_patchify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_hd_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_pool_spatial": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_pool_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_strip_cls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_bcast_row": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gvl_op_fold_gamma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "gvl_op_rowsq_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "gvl_op_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -474,6 +474,14 @@ int gvl_op_gemm(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, void* C, int
  * [b0, b0 + nblk) of row m) / cols + eps). */
 int gvl_op_gemm_rows(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, uint16_t* C, int M, int N, int K, const float* bias, const float* gamma,
                      const uint16_t* resid, int act, const float* rowscale, float* rowsq, int rowsq_ld, int tile_cfg, void* stream);
+/* gvl_op_gemm with the row-remapping store of the visual prefix (operator tests: tests/test_gpu_vision_ops.py): GEMM row m is stored at row
+ *   (m / grp_rows) * grp_stride + m % grp_rows + row_off
+ * of C (and read from there in resid), so C and resid hold ceil(M / grp_rows) * grp_stride rows of N columns; the rows between the groups are not touched.
+ * grp_rows >= 1, row_off >= 0 and row_off + grp_rows <= grp_stride, else GVL_ERR_ARG.  rowsq / rowsq_ld as in gvl_op_gemm_rows: no kernel serves the row
+ * statistics together with a remap, a non-NULL rowsq is refused (GVL_ERR_ARG, nothing written). */
+int gvl_op_gemm_grouped(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, void* C, int M, int N, int K, const float* bias, const float* gamma,
+                        const void* resid, int act, int out_f32, float* rowsq, int rowsq_ld, int grp_rows, int grp_stride, int row_off, int tile_cfg,
+                        void* stream);
 int gvl_op_fold_gamma(gvl_ctx* ctx, const uint16_t* W, const uint16_t* gamma, uint16_t* Wo, int64_t rows, int cols, void* stream);
 int gvl_op_rowsq_finish(gvl_ctx* ctx, const float* rowsq, int ld, int b0, int nblk, float* rs, int rows, int cols, float eps, void* stream);
 /* attention over q/k/v bf16 [B,S,H|KV,D] (plain layout; the library re-tiles internally).
@@ -484,6 +492,47 @@ int gvl_op_layernorm(gvl_ctx* ctx, const float* x, const float* w, const float* 
                      int cols, float eps, void* stream);
 int gvl_op_rmsnorm(gvl_ctx* ctx, const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int cols,
                    float eps, void* stream);
+/* The patch embedding of either vision tower on its own (operator tests: tests/test_gpu_vision_ops.py).  All pointers are device memory.
+ *   mode 0 = CLIP:         out f32  [n][1 + L][C]    = LayerNorm(cat(cls, bf16(conv(px))) + pos; lnw, lnb, eps), T must be 1
+ *   mode 1 = InternVideo2: out bf16 [n][1 + T L][C]  = bf16(cat(cls, bf16(conv(px) + bias)) + pos)
+ *   with L = (image / patch)^2 and conv = a convolution of stride = kernel = patch over px f32 [n][3][T][image][image]; W bf16 [C][Kp] row-major,
+ *   k = (c * patch + py) * patch + px, columns [3 patch^2, Kp) ignored.  cls [C] and pos [1 + T L][C] are f32 (mode 0) or bf16 (mode 1); bias [C] f32 (mode 1);
+ *   lnw, lnb [C] f32 and eps (mode 0).
+ *   path 0 = the fused kernel (gvl_patch.hip; patch 14, C 1024 or 1408 -- CLIP: 1024): the call makes its own tile-order copy of W in the workspace arena.
+ *            A geometry the fused launcher refuses comes back as GVL_ERR_ARG: there is NO fall-back to path 1 here, the caller knows which kernel ran.
+ *   path 1 = the three passes: im2col (patchify), the patch GEMM, the embedding kernel.  Kp % 64 == 0, C % 8 == 0 (mode 0: C <= 4096).  im2col (or NULL)
+ *            receives the bf16 im2col matrix [n T L][Kp], zero in the columns [3 patch^2, Kp).  im2col must be NULL on path 0.
+ * Refusals (GVL_ERR_ARG; GVL_ERR_OOM when the workspace arena cannot hold the copies) are returned before anything is written to out or im2col. */
+typedef struct {
+  int32_t mode, path;
+  int32_t n, T, image, patch, C, Kp;
+  float eps;
+  const float* px;
+  const uint16_t* W;
+  const float* bias;
+  const void* cls;
+  const void* pos;
+  const float* lnw;
+  const float* lnb;
+  void* out;
+  uint16_t* im2col;
+} gvl_patch_embed;
+int gvl_op_patch_embed(gvl_ctx* ctx, const gvl_patch_embed* p, void* stream);
+/* im2col alone (any patch size): px f32 [n][3][T][image][image] -> A bf16 [n T (image / patch)^2][Kp], Kp % 8 == 0, Kp >= 3 patch^2, image % patch == 0. */
+int gvl_op_patchify(gvl_ctx* ctx, const float* px, uint16_t* A, int n, int T, int image, int patch, int Kp, void* stream);
+/* The glue kernels of the visual prefix on their own.  Their token geometry is FIXED (it is the model's: gvl_build_visual refuses any other tower geometry):
+ *   gvl_op_hd_merge      f f32 [n][576 = 24 x 24][C], sub_gn f32 [4 C] -> out bf16 [n][156 = 12 x 13][4 C]: row (h, w < 12) = the 2 x 2 block (2h + dy, 2w + dx) of f,
+ *                        channel chunks in (dy, dx) order; row (h, 12) = sub_gn.  C % 4 == 0.
+ *   gvl_op_pool_spatial  f f32 [n][576][C] -> out bf16 [n][64 = 8 x 8][C]: the mean of each 3 x 3 window, summed in fp32, divided by 9.  C % 4 == 0.
+ *   gvl_op_pool_temporal f bf16 [n][T][256 = 16 x 16][C] -> out bf16 [n][T][16 = 4 x 4][C]: the mean of each 4 x 4 window, summed in fp32, times 2^-4.  C % 8 == 0.
+ *   gvl_op_strip_cls     y[n][s][:] = x[n][s + 1][:], x [n][S][C] of elem_bytes 2 or 4, S >= 2, C * elem_bytes % 4 == 0.
+ *   gvl_op_bcast_row     dst[(s * stride_rows + row_off)][:] = row[:] for s < n; row, dst bf16, dst [n * stride_rows][cols], 0 <= row_off < stride_rows.
+ * n >= 1, T >= 1, C >= 1; anything else is GVL_ERR_ARG before a launch. */
+int gvl_op_hd_merge(gvl_ctx* ctx, const float* f, const float* sub_gn, uint16_t* out, int n, int C, void* stream);
+int gvl_op_pool_spatial(gvl_ctx* ctx, const float* f, uint16_t* out, int n, int C, void* stream);
+int gvl_op_pool_temporal(gvl_ctx* ctx, const uint16_t* f, uint16_t* out, int n, int T, int C, void* stream);
+int gvl_op_strip_cls(gvl_ctx* ctx, const void* x, void* y, int n, int S, int C, int elem_bytes, void* stream);
+int gvl_op_bcast_row(gvl_ctx* ctx, const uint16_t* row, uint16_t* dst, int n, int stride_rows, int row_off, int cols, void* stream);
 /* y[N] = W[N,K] x[K] (+bias) -- the decode GEMV; x,W bf16, y f32. */
 int gvl_op_gemv(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K,
                 void* stream);
