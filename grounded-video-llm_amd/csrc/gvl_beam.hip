@@ -169,9 +169,11 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
       if (sqs[j]->pos >= sqs[j]->max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: the context is full (cfg.max_seq) before max_new_tokens");
       RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sqs[j]->d_tok, toks[j], st));
     }
-    const bool one_part = decode_group_size(ctx, k) == k;
-    for (int o = 0; o < k;) {
-      const int nb = decode_group_size(ctx, k - o);
+    int sizes[GVL_MAX_DECODE_BATCH];
+    const int n_parts = decode_parts(ctx->decode_mfma, k, sizes);
+    const bool one_part = n_parts == 1;
+    for (int p = 0, o = 0; p < n_parts; ++p) {
+      const int nb = sizes[p];
       if (const int drc = decode_step(ctx, sqs + o, nb, st)) return drc;
       if (!one_part) HIPCHK(ctx, hipMemcpyAsync(ctx->d_beam_rows + (size_t)o * V, ctx->d_logits, (size_t)nb * V * 4, hipMemcpyDeviceToDevice, st));
       o += nb;

@@ -116,7 +116,8 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   // memory (h_ / d_ views), [GVL_MAX_DECODE_BATCH][vocab] work rows, and the beams' histories + lengths for the logits processors
   void* d_beam_scratch = nullptr; void* h_beam_cand = nullptr; void* d_beam_cand = nullptr; float* d_beam_rows = nullptr; int* d_beam_hist = nullptr;
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
-  // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of ~165 kernel launches
+  // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of the step's kernel launches
+  // (decode_plan, gvl_decode_plan.h: 4 * layers + 1 projections + `layers` attention launches + 1 or 1 + 2 * layers in front + token selection)
   struct { int decode_attn_cpb = 0, decode_attn_hpb = 0; bool decode_graph = true; int vision_in_place = 1, prefill_group = 4, attn_ring = 0, attn_pipe = 1, attn_pipe_rows = 128, patch_fused = 1, varlen_attn = 1, varlen_extend = 1, norm_fused = 1, last_layer_tail = 1; } dbg;
   // RCCL communicator owned by the ctx (gvl_comm_init); the library is dlopen'ed on first use
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;

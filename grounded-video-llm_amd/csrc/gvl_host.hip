@@ -4,6 +4,7 @@
 // Reference counterparts: torch.load + load_state_dict (inference.py:156-162, models/llava_next_video.py:117-151); the exchange has
 // none (the reference's inference is single-GPU, inference.py:17; SURVEY.md §8 e).
 #include "gvl_ctx.h"
+#include "gvl_decode_plan.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -26,8 +27,8 @@ int gvl_kv_info(const gvl_ctx* ctx, int* total_pages, int* free_pages, int64_t* 
 
 int gvl_decode_group_info(const gvl_ctx* ctx, int* max_group, int* any_size) {
   if (!ctx) return GVL_ERR_ARG;
-  if (max_group) *max_group = ctx->decode_mfma ? GVL_MAX_DECODE_BATCH : GVL_MAX_VALU_BATCH;
-  if (any_size) *any_size = ctx->decode_mfma ? 1 : 0;
+  if (max_group) *max_group = decode_group_size(ctx->decode_mfma, GVL_MAX_DECODE_BATCH);
+  if (any_size) *any_size = decode_batch_ok(ctx->decode_mfma, 3) ? 1 : 0;
   return 0;
 }
 

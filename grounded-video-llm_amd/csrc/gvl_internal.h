@@ -22,8 +22,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 
 #define GVL_KV_PAGE 64          // tokens per KV page == key tile of the attention kernels
-#include "gvl_limits.h"       // GVL_MAX_DECODE_BATCH, GVL_MAX_PREFILL_BATCH (shared with the host-only launch plans)
-constexpr int GVL_MAX_VALU_BATCH = 4;     // the round-1 VALU GEMV (fallback for K % 256 != 0 geometries) holds B vectors in LDS: 1, 2 or 4
+#include "gvl_limits.h"       // GVL_MAX_DECODE_BATCH, GVL_MAX_VALU_BATCH, GVL_MAX_PREFILL_BATCH (shared with the host-only launch plans)
 constexpr int GVL_GEMM_ROT_LEN = 64;     // GemmArgs.rot entries (a power of two; longer walks repeat the table)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a host may hold one gvl_ctx per device in ONE process

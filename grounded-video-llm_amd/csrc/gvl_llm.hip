@@ -1,6 +1,7 @@
 // gvl_llm.hip -- the decoder's launch sequences: ragged / batched prefill (+ the training-forward loss tail), the decode step and its hipGraph replay, the greedy decode
 // loop over a group of sequences (host code; the kernels live in gvl_gemm*.hip, gvl_attn.hip, gvl_decode.hip, gvl_elem.hip).  Which launches a prefill group takes is
-// decided in gvl_prefill_plan.h, the decode-attention launch shape in gvl_attn_plan.h (both host-only, tested on the CPU).  Restates (file:line in the reference):
+// decided in gvl_prefill_plan.h, which launches a decode step takes and what its projections read in gvl_decode_plan.h, the decode-attention launch shape in
+// gvl_attn_plan.h (all three host-only, tested on the CPU).  Restates (file:line in the reference):
 //   LLM             models/modeling_phi3.py:1034-1095,1249-1383,1512-1526 / models/modeling_llama.py:699-760
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
@@ -303,22 +304,68 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
   return 0;
 }
 
+// The GemvArgs of one decode projection: the kind's own operands and constants, and what the plan's entry decides about it (gvl_decode_plan.h: which weight copy, with
+// or without scales, which input, what it leaves behind).  `l` is the layer (any for lm_head); qkv carries the fused epilogue RoPE + Q write + paged-KV append.
+static GemvArgs proj_args(const gvl_ctx* ctx, int kind, int l, const DecodeProjPlan& e, Seq* const* sqs, int B) {
+  const gvl_config& f = ctx->cfg;
+  const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
+  const LlmLayerW& w = ctx->ll[l];
+  GemvArgs g; memset(&g, 0, sizeof(g)); g.batch = B;
+  struct { const bf16_t *row_major, *tiled, *folded; } W{};   // by DecodeWeight
+  const float* scales = nullptr; const bf16_t* norm_w = nullptr;
+  switch (kind) {
+    case GVL_DPROJ_QKV0: case GVL_DPROJ_QKV:
+      W = {w.qkvw, w.qkvd, w.qkvd_f}; scales = w.qkvs; norm_w = w.ln1; g.N = (H + 2 * KV) * Dr; g.K = Hd;
+      g.rope_on = 1; g.cos_s = ctx->cos_s; g.sin_s = ctx->sin_s; g.cos_l = ctx->cos_l; g.sin_l = ctx->sin_l;
+      g.rope_switch = ctx->cos_l ? f.rope_orig_max_pos : 0;
+      for (int b = 0; b < B; ++b) { g.pos_ptrs[b] = sqs[b]->d_pos; g.tables[b] = sqs[b]->d_block_table; }
+      g.Q = ctx->d_q; g.q_stride = H * D; g.Kt = ctx->kpool + (size_t)l * ctx->layer_stride; g.Vt = ctx->vpool + (size_t)l * ctx->layer_stride;
+      g.H = H; g.KV = KV; g.Dr = Dr; g.D = D;
+      break;
+    case GVL_DPROJ_O:
+      W = {w.ow, w.od, nullptr}; scales = w.os; g.N = Hd; g.K = H * Dr; g.resid = ctx->d_x; g.out_bf16 = ctx->d_x; g.out_stride = Hd;
+      break;
+    case GVL_DPROJ_GATE_UP:
+      W = {w.guw, w.gud, w.gud_f}; scales = w.gus; norm_w = w.ln2; g.N = 2 * I; g.K = Hd; g.act = GVL_ACT_SILU_MUL; g.out_bf16 = ctx->d_act; g.out_stride = I;
+      break;
+    case GVL_DPROJ_DOWN:
+      W = {w.downw, w.downd, nullptr}; scales = w.downs; g.N = Hd; g.K = I; g.resid = ctx->d_x; g.out_bf16 = ctx->d_x; g.out_stride = Hd;
+      break;
+    default:   // GVL_DPROJ_HEAD
+      W = {ctx->l_headw, ctx->l_headd, ctx->l_headd_f}; scales = ctx->l_heads; norm_w = ctx->l_norm; g.N = f.vocab; g.K = Hd; g.bias = ctx->l_headb;
+      g.out_f32 = ctx->d_logits; g.out_stride = f.vocab;
+  }
+  g.x_stride = g.K;
+  g.W = e.weight == GVL_DW_ROW_MAJOR ? W.row_major : e.weight == GVL_DW_TILED ? W.tiled : W.folded;
+  if (e.scales) { g.w_fp8 = ctx->fp8; g.wscale = scales; }
+  switch (e.input) {
+    case GVL_DIN_X_NORM: g.x = ctx->d_x; g.norm_w = norm_w; g.eps = f.rms_eps; break;
+    case GVL_DIN_XN: g.x = ctx->d_xn; break;
+    case GVL_DIN_XT_SQ: g.x = ctx->d_xt; g.sq_in = ctx->d_sqpart; g.sq_n = Hd >> 4; g.eps = f.rms_eps; break;
+    case GVL_DIN_ATTN: g.x = ctx->d_attn; break;
+    default: g.x = ctx->d_act;   // GVL_DIN_ACT
+  }
+  if (e.sq_out) { g.sq_out = ctx->d_sqpart; g.out_tiled2 = ctx->d_xt; }
+  g.out_tiled = e.out_tiled ? 1 : 0;
+  return g;
+}
+
 // One greedy decode step for B sequences together (1..16 on the skinny-GEMM path, 1 / 2 / 4 on the VALU fallback): each weight
 // matrix is streamed ONCE for the whole batch, attention / RoPE / KV append run per sequence on its own pages.  Every launch
 // argument is a device pointer or a constant of the group: the step can be replayed (hipGraph) without host-side counters.
+// WHICH launches it takes and what each projection reads is decode_plan's decision (gvl_decode_plan.h: pure, tested on the CPU): 4 * layers + 1 projections, `layers`
+// attention launches, 1 launch in front (+ 2 * layers norm launches for an unfused group of more than 4), then token selection.  This function is plan, then walk.
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st) {
   const gvl_config& f = ctx->cfg;
   const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
   const int qkvw = (H + 2 * KV) * Dr;
-  const bool mfma = ctx->decode_mfma;
-  if (mfma ? (B < 1 || B > GVL_MAX_DECODE_BATCH) : (B != 1 && B != 2 && B != 4)) return fail(ctx, GVL_ERR_ARG, "decode_step: unsupported batch");
+  DecodePlan plan;
+  { const int rc = decode_plan(DecodeGeometry{B, f.layers, Hd, ctx->decode_mfma, ctx->fp8, ctx->l_headd_f != nullptr}, DecodeKnobs{ctx->dbg.norm_fused != 0}, &plan);
+    if (rc) return fail(ctx, GVL_ERR_ARG, decode_refusal_reason(rc)); }
   for (int b = 0; b < B; ++b) { const int rc = upload_table(ctx, *sqs[b], st); if (rc) return rc; }   // (a no-op after the sequence's prefill; under capture it would be part of the graph -- never dirty there)
   TokPtrs tp; memset(&tp, 0, sizeof(tp)); tp.n = B; for (int b = 0; b < B; ++b) tp.p[b] = sqs[b]->d_tok;
-  // RMSNorm in front of qkv / gate_up / lm_head: groups of <= 4 normalise inside the consumer (LDS, like the VALU kernel), larger
-  // groups run one norm launch per projection whose output every block of the consumer shares (gvl_decode.hip header)
-  const bool fused_norm = !mfma || B <= GVL_MAX_VALU_BATCH;
-  if (fused_norm) RUN(GVL_PROF_OTHER, 0, gvl_launch_gather_tok_rows(ctx->l_embed, tp, ctx->d_x, Hd, st));
-  else RUN(GVL_PROF_OTHER, 0, gvl_launch_embed_norm(ctx->l_embed, tp, ctx->d_x, ctx->d_xn, ctx->ll[0].ln1, Hd, f.rms_eps, st));
+  if (plan.embed_norm) RUN(GVL_PROF_OTHER, 0, gvl_launch_embed_norm(ctx->l_embed, tp, ctx->d_x, ctx->d_xn, ctx->ll[0].ln1, Hd, f.rms_eps, st));
+  else RUN(GVL_PROF_OTHER, 0, gvl_launch_gather_tok_rows(ctx->l_embed, tp, ctx->d_x, Hd, st));
   double ctx_tokens = 0; for (int b = 0; b < B; ++b) ctx_tokens += sqs[b]->pos + 1;
   // Decode-attention launch shape (decode_attn_shape, gvl_attn_plan.h): block slots along the context, splits and heads per block -- from the sequences' positions and
   // the gvl_debug_set overrides; under stream capture the shape that stays valid for later steps
@@ -329,56 +376,28 @@ int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st) {
     for (int b = 0; b < B; ++b) positions[b] = sqs[b]->pos;
     const DecodeAttnShape s = decode_attn_shape(positions, B, H, KV, ctx->nsplit, ctx->dbg.decode_attn_cpb, ctx->dbg.decode_attn_hpb, capturing);
     gsplit = s.gsplit; cpb = s.cpb; hpb = s.hpb; }
-  auto proj = [&](GemvArgs& g, const float* wscale) {
-    if (!mfma) return gvl_launch_gemv(g, st);
-    if (ctx->fp8) { g.w_fp8 = ctx->fp8; g.wscale = wscale; }
-    return gvl_launch_dgemm(g, st);
+  auto project = [&](int kind, int l, double flops) -> int {
+    const DecodeProjPlan& e = plan.proj[kind];
+    const GemvArgs g = proj_args(ctx, kind, l, e, sqs, B);
+    RUN(GVL_PROF_GEMV, flops, e.launcher == GVL_DLAUNCH_DGEMM ? gvl_launch_dgemm(g, st) : gvl_launch_gemv(g, st));
+    return 0;
   };
-  auto normed_input = [&](GemvArgs& g, const bf16_t* w) {       // the projection reads rmsnorm(d_x) * w
-    if (fused_norm) { g.x = ctx->d_x; g.norm_w = w; g.eps = f.rms_eps; } else g.x = ctx->d_xn;
-  };
-  // Fused RMSNorm on the decode path (round 5; GemvArgs.sq_*): o_proj / down_proj leave per-sequence partial sums of squares of the new residual rows and a
-  // raw tile-order copy of them; qkv_proj (layers >= 1), gate_up_proj and lm_head run on that raw copy with the norm weight folded into their (tile-order)
-  // weights and scale their accumulators per sequence.  No norm launch (groups > 4: two per layer) and no in-block normalisation (groups <= 4) any more;
-  // layer 0's input norm (no producer projection) keeps the old path.  bf16 decode weights only.
-  const int nblk = Hd >> 4;
-  const bool rs = mfma && !ctx->fp8 && ctx->dbg.norm_fused && ctx->l_headd_f && Hd % 64 == 0 && (nblk & 31) == 0 && nblk <= 256;
-  auto rs_input = [&](GemvArgs& g) { g.x = ctx->d_xt; g.sq_in = ctx->d_sqpart; g.sq_n = nblk; g.eps = f.rms_eps; };
-  auto rs_output = [&](GemvArgs& g) { if (rs) { g.sq_out = ctx->d_sqpart; g.out_tiled2 = ctx->d_xt; } };
   for (int l = 0; l < f.layers; ++l) {
-    const LlmLayerW& w = ctx->ll[l];
-    bf16_t* Kt = ctx->kpool + (size_t)l * ctx->layer_stride; bf16_t* Vt = ctx->vpool + (size_t)l * ctx->layer_stride;
-    { GemvArgs g; memset(&g, 0, sizeof(g)); g.W = mfma ? w.qkvd : w.qkvw; g.N = qkvw; g.K = Hd; g.batch = B; g.x_stride = Hd;
-      if (rs && l > 0) { g.W = w.qkvd_f; rs_input(g); } else normed_input(g, w.ln1);
-      // fused epilogue: RoPE + Q write + paged-KV append (replaces a separate qkv_post launch per layer per token)
-      g.rope_on = 1; g.cos_s = ctx->cos_s; g.sin_s = ctx->sin_s; g.cos_l = ctx->cos_l; g.sin_l = ctx->sin_l;
-      g.rope_switch = ctx->cos_l ? f.rope_orig_max_pos : 0;
-      for (int b = 0; b < B; ++b) { g.pos_ptrs[b] = sqs[b]->d_pos; g.tables[b] = sqs[b]->d_block_table; }
-      g.Q = ctx->d_q; g.q_stride = H * D; g.Kt = Kt; g.Vt = Vt; g.H = H; g.KV = KV; g.Dr = Dr; g.D = D;
-      RUN(GVL_PROF_GEMV, 2.0 * qkvw * Hd, proj(g, w.qkvs)); }
-    { DecodeAttnArgs a; memset(&a, 0, sizeof(a)); a.q = ctx->d_q; a.q_stride = H * D; a.Kt = Kt; a.Vt = Vt;
+    if (const int rc = project(l ? GVL_DPROJ_QKV : GVL_DPROJ_QKV0, l, 2.0 * qkvw * Hd)) return rc;
+    { DecodeAttnArgs a; memset(&a, 0, sizeof(a)); a.q = ctx->d_q; a.q_stride = H * D;
+      a.Kt = ctx->kpool + (size_t)l * ctx->layer_stride; a.Vt = ctx->vpool + (size_t)l * ctx->layer_stride;
       for (int b = 0; b < B; ++b) { a.tables[b] = sqs[b]->d_block_table; a.pos_ptrs[b] = sqs[b]->d_pos; }
       a.part = ctx->d_part; a.counters = ctx->d_counters; a.batch = B; a.gsplit = gsplit; a.cpb = cpb; a.hpb = hpb;
-      a.out = ctx->d_attn; a.out_stride = H * Dr; a.out_tiled = mfma ? 1 : 0; a.H = H; a.KV = KV; a.D = D; a.Dout = Dr; a.nsplit = ctx->nsplit; a.scale = 1.0f / sqrtf((float)Dr);
+      a.out = ctx->d_attn; a.out_stride = H * Dr; a.out_tiled = plan.attn_out_tiled ? 1 : 0; a.H = H; a.KV = KV; a.D = D; a.Dout = Dr; a.nsplit = ctx->nsplit; a.scale = 1.0f / sqrtf((float)Dr);
       RUN(GVL_PROF_DECODE_ATTN, 4.0 * ctx_tokens * (double)KV * D, gvl_launch_decode_attention(a, st)); }
-    { GemvArgs g; memset(&g, 0, sizeof(g)); g.W = mfma ? w.od : w.ow; g.N = Hd; g.K = H * Dr; g.x = ctx->d_attn; g.resid = ctx->d_x; g.out_bf16 = ctx->d_x;
-      g.batch = B; g.x_stride = H * Dr; g.out_stride = Hd; rs_output(g);
-      RUN(GVL_PROF_GEMV, 2.0 * Hd * H * Dr, proj(g, w.os)); }
-    if (!fused_norm && !rs) RUN(GVL_PROF_OTHER, 0, gvl_launch_norm_tiled(ctx->d_x, ctx->d_xn, w.ln2, B, Hd, f.rms_eps, st));     // post_attention_layernorm
-    { GemvArgs g; memset(&g, 0, sizeof(g)); g.W = mfma ? w.gud : w.guw; g.N = 2 * I; g.K = Hd; g.act = GVL_ACT_SILU_MUL; g.out_bf16 = ctx->d_act;
-      g.batch = B; g.x_stride = Hd; g.out_stride = I; g.out_tiled = mfma ? 1 : 0;
-      if (rs) { g.W = w.gud_f; rs_input(g); } else normed_input(g, w.ln2);
-      RUN(GVL_PROF_GEMV, 4.0 * I * Hd, proj(g, w.gus)); }
-    { GemvArgs g; memset(&g, 0, sizeof(g)); g.W = mfma ? w.downd : w.downw; g.N = Hd; g.K = I; g.x = ctx->d_act; g.resid = ctx->d_x; g.out_bf16 = ctx->d_x;
-      g.batch = B; g.x_stride = I; g.out_stride = Hd; rs_output(g);
-      RUN(GVL_PROF_GEMV, 2.0 * Hd * I, proj(g, w.downs)); }
-    if (!fused_norm && !rs)   // the next layer's input_layernorm, or the final norm in front of lm_head
+    if (const int rc = project(GVL_DPROJ_O, l, 2.0 * Hd * H * Dr)) return rc;
+    if (plan.norm_launches) RUN(GVL_PROF_OTHER, 0, gvl_launch_norm_tiled(ctx->d_x, ctx->d_xn, ctx->ll[l].ln2, B, Hd, f.rms_eps, st));     // post_attention_layernorm
+    if (const int rc = project(GVL_DPROJ_GATE_UP, l, 4.0 * I * Hd)) return rc;
+    if (const int rc = project(GVL_DPROJ_DOWN, l, 2.0 * Hd * I)) return rc;
+    if (plan.norm_launches)   // the next layer's input_layernorm, or the final norm in front of lm_head
       RUN(GVL_PROF_OTHER, 0, gvl_launch_norm_tiled(ctx->d_x, ctx->d_xn, l + 1 < f.layers ? ctx->ll[l + 1].ln1 : ctx->l_norm, B, Hd, f.rms_eps, st));
   }
-  { GemvArgs g; memset(&g, 0, sizeof(g)); g.W = mfma ? ctx->l_headd : ctx->l_headw; g.N = f.vocab; g.K = Hd; g.bias = ctx->l_headb;
-    g.batch = B; g.x_stride = Hd; g.out_stride = f.vocab;
-    if (rs) { g.W = ctx->l_headd_f; rs_input(g); } else normed_input(g, ctx->l_norm);
-    g.out_f32 = ctx->d_logits; RUN(GVL_PROF_GEMV, 2.0 * f.vocab * Hd, proj(g, ctx->l_heads)); }
+  if (const int rc = project(GVL_DPROJ_HEAD, 0, 2.0 * f.vocab * Hd)) return rc;
   { ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = ctx->d_logits; am.n = f.vocab; am.batch = B;   // token, output list, n_gen++ and pos++ on the device
     for (int b = 0; b < B; ++b) { am.tok_ptrs[b] = sqs[b]->d_tok; am.out_lists[b] = sqs[b]->d_out; am.ngen_ptrs[b] = sqs[b]->d_ngen; am.pos_ptrs[b] = sqs[b]->d_pos; }
     if (ctx->watch_eos >= 0) { am.eos_id = ctx->watch_eos; for (int b = 0; b < B; ++b) am.eos_flags[b] = sqs[b]->d_eos; }
@@ -386,14 +405,10 @@ int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st) {
   for (int b = 0; b < B; ++b) { sqs[b]->pos += 1; sqs[b]->n_gen += 1; }
   return 0;
 }
-// largest group the decode path takes at once, and the group size for `left` waiting sequences
-int decode_group_size(const gvl_ctx* ctx, int left) {
-  if (ctx->decode_mfma) return left < GVL_MAX_DECODE_BATCH ? left : GVL_MAX_DECODE_BATCH;
-  return left >= 4 ? 4 : (left >= 2 ? 2 : 1);
-}
 
 // A decode step's launches carry device pointers and group constants only, so ONE captured step can be replayed for the following
-// tokens of the same group (hipGraph): the host pays one graph launch instead of ~165 kernel launches per token.
+// tokens of the same group (hipGraph): the host pays one graph launch instead of the step's kernel launches per token
+// (decode_plan: 4 * layers + 1 projections, `layers` attention launches, 1 or 1 + 2 * layers in front, then token selection: 162 + selection at 32 layers).
 struct StepGraph {
   hipGraph_t g = nullptr; hipGraphExec_t e = nullptr; bool failed = false;
   ~StepGraph() { if (e) hipGraphExecDestroy(e); if (g) hipGraphDestroy(g); }
@@ -443,7 +458,7 @@ int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, 
   // Only LIVE members are stepped: a sequence that produced eos (seen two steps late) or reached its own capacity / max_new leaves the
   // group, so it can neither truncate the answers of longer-running members nor append past its pages.  A sequence's ids do not depend
   // on the group it is decoded in (gvl_decode.hip), so shrinking the group changes no result; the captured step is re-recorded.
-  // The live set is stepped as PARTS of sizes the decode path takes (decode_group_size: any size up to 16 on the skinny-MFMA path;
+  // The live set is stepped as PARTS of sizes the decode path takes (decode_parts, gvl_decode_plan.h: any size up to 16 on the skinny-MFMA path;
   // 4 / 2 / 1 on the VALU fallback, so three survivors of a group of four run as 2 + 1), one captured step graph per part.
   // Retired graphs are destroyed after the final synchronise only: up to two replays may still be in flight when a member leaves.
   struct Part { Seq* m[GVL_MAX_DECODE_BATCH]; int n; std::unique_ptr<StepGraph> sg; };
@@ -462,8 +477,9 @@ int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, 
     if (n_now != n_live || memcmp(now, live, sizeof(Seq*) * n_now) != 0) {
       for (auto& p : parts) retired.push_back(std::move(p.sg));
       parts.clear();
-      for (int o = 0; o < n_now;) {
-        Part p; p.n = decode_group_size(ctx, n_now - o);
+      int sizes[GVL_MAX_DECODE_BATCH];
+      for (int k = 0, o = 0, nk = decode_parts(ctx->decode_mfma, n_now, sizes); k < nk; ++k) {
+        Part p; p.n = sizes[k];
         memcpy(p.m, now + o, sizeof(Seq*) * p.n); p.sg.reset(new StepGraph());
         o += p.n; parts.push_back(std::move(p));
       }

@@ -1,8 +1,9 @@
 // gvl_model.h -- what the four host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the sequence / prefill / decode
 // and operator entry points of include/gvl.h), gvl_select.hip (the token-selection entry points), gvl_vision.hip (the towers' launch sequences) and
-// gvl_llm.hip (prefill, the decode step, the decode loop).  Internal: nothing here is part of the ABI.
+// gvl_llm.hip (prefill, the decode step -- planned in gvl_decode_plan.h --, the decode loop).  Internal: nothing here is part of the ABI.
 #pragma once
 #include "gvl_ctx.h"
+#include "gvl_decode_plan.h"   // the decode path's predicates, batch admission and grouping, and decode_step's launch plan (host-only, tested on the CPU)
 
 namespace gvlm {
 
@@ -95,8 +96,8 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
 // one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan
 int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr,
                 const ScoreReq* score = nullptr);   // pos0s: tokens each sequence already holds (null = none); score: rows of the group to score on the way (not with loss)
+// one step of B sequences (decode_batch_ok): plans its launches (decode_plan, gvl_decode_plan.h -- it refuses before the first launch), then walks the plan
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st);
-int decode_group_size(const gvl_ctx* ctx, int left);
 int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, int32_t* const* out_ids, int* const* n_out, hipStream_t st);
 
 }  // namespace gvlm

@@ -141,7 +141,7 @@ int gvl_create(const gvl_config* cfg, gvl_ctx** out) {
     for (int i = 0; i < 3 && ok; ++i) ok &= hipEventCreateWithFlags(&ctx->step_ev[i], hipEventDisableTiming) == hipSuccess;
     {   // the skinny-GEMM decode path needs every projection's K to split over 8 waves x 32-wide MFMA steps, and rows that one wave normalises
       const char* e = gvl_lab_env("GVL_DECODE_VALU");
-      ctx->decode_mfma = !(e && atoi(e)) && f.hidden % 256 == 0 && f.inter % 256 == 0 && (f.heads * ctx->l_Dr) % 256 == 0 && f.hidden <= 4096 && (ctx->l_Dr & 1) == 0;
+      ctx->decode_mfma = !(e && atoi(e)) && decode_mfma_ok(f.hidden, f.inter, f.heads, ctx->l_Dr);
     }
     ok &= hipMalloc((void**)&ctx->d_qkv, (size_t)qkvw * 2) == hipSuccess;
     ok &= hipMalloc((void**)&ctx->d_q, NB * f.heads * ctx->l_D * 2) == hipSuccess && hipMemset(ctx->d_q, 0, NB * f.heads * ctx->l_D * 2) == hipSuccess;
@@ -324,8 +324,7 @@ int gvl_finalize_weights(gvl_ctx* ctx) {
     ctx->fp8 = 0;
     if (f.decode_fp8) {
       if (f.decode_fp8 != 1 && f.decode_fp8 != 2) return fail(ctx, GVL_ERR_ARG, "cfg.decode_fp8: 0 = bf16, 1 = FP8 e4m3, 2 = MXFP4");
-      const int mult = f.decode_fp8 == 2 ? 1024 : 512;
-      if (!ctx->decode_mfma || Hd % mult || I % mult || (f.heads * Dr) % mult)
+      if (!ctx->decode_mfma || !decode_quant_ok(f.decode_fp8, Hd, I, f.heads * Dr))
         return fail(ctx, GVL_ERR_ARG, "cfg.decode_fp8 needs hidden, inter and heads*head_dim to be multiples of 512 (FP8) / 1024 (MXFP4) (skinny-GEMM decode path)");
       ctx->fp8 = f.decode_fp8;
     }
@@ -700,9 +699,9 @@ int gvl_decode_greedy_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int ma
   }
   hipStream_t st = (hipStream_t)stream;
   // groups of up to 16 (VALU fallback: 4, 2, 1): a group streams the weights once per step for all of its members
-  int i = 0;
-  while (i < n_seqs) {
-    const int left = n_seqs - i, B = decode_group_size(ctx, left);
+  int sizes[gvl_ctx::kMaxSeqs];
+  for (int k = 0, i = 0, nk = decode_parts(ctx->decode_mfma, n_seqs, sizes); k < nk; ++k) {
+    const int B = sizes[k];
     Seq* sqs[GVL_MAX_DECODE_BATCH]; int32_t* outs[GVL_MAX_DECODE_BATCH]; int* nouts[GVL_MAX_DECODE_BATCH];
     for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; outs[b] = out_ids + (size_t)(i + b) * max_new; nouts[b] = n_out + i + b; }
     const int rc = decode_group(ctx, sqs, B, max_new, eos_id, outs, nouts, st);
@@ -726,10 +725,11 @@ int gvl_decode_steps(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int n_steps, 
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_steps", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
+  int sizes[gvl_ctx::kMaxSeqs];
+  const int nk = decode_parts(ctx->decode_mfma, n_seqs, sizes);   // groups of up to 16 (VALU fallback: 4, 2, 1): one weight stream per step per group
   for (int s = 0; s < n_steps; ++s) {
-    int i = 0;
-    while (i < n_seqs) {                   // groups of up to 16 (VALU fallback: 4, 2, 1): one weight stream per step per group
-      const int left = n_seqs - i, B = decode_group_size(ctx, left);
+    for (int k = 0, i = 0; k < nk; ++k) {
+      const int B = sizes[k];
       Seq* sqs[GVL_MAX_DECODE_BATCH];
       for (int b = 0; b < B; ++b) sqs[b] = &ctx->seqs[seq_ids[i + b]];
       const int rc = decode_step(ctx, sqs, B, st);
@@ -769,7 +769,7 @@ int gvl_decode_step_logits(gvl_ctx* ctx, int seq_id, int tok, float* logits, voi
 
 int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const int32_t* toks, float* logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_decode_step_logits_batch");
-  if (!seq_ids || !toks || n_seqs < 1 || n_seqs > decode_group_size(ctx, GVL_MAX_DECODE_BATCH) || (!ctx->decode_mfma && n_seqs == 3))
+  if (!seq_ids || !toks || !decode_batch_ok(ctx->decode_mfma, n_seqs))
     return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: 1 .. 16 sequences (VALU fallback geometries: 1, 2 or 4)");
   Seq* sqs[GVL_MAX_DECODE_BATCH];
   for (int i = 0; i < n_seqs; ++i) {

@@ -20,6 +20,7 @@ from gpu_util import DEV, bf, check, check_bf16_class, llm_engine, tiny_geo  # n
 from grounded_video_llm_amd import engine as E, synth  # noqa: E402
 import attn_plan as A  # noqa: E402
 import prefill_plan as PP  # noqa: E402
+import decode_plan as DP  # noqa: E402
 
 
 def _ocfg(geo):
@@ -223,6 +224,23 @@ def test_decode_batch_is_bit_identical_to_single(which):
     for ids, ref in zip(got, single[:2]):
         cut = ref.index(eos) + 1 if eos in ref else new
         assert ids == ref[:cut]
+    # WHICH steps ran, from the library's own plan (tests/decode_plan.py): hidden = 64 decodes on the VALU path, whose groups are cut 2; 2 + 1; 4; 4 + 2 + 1 -- and the
+    # library's own count of projection and decode-attention launches for two decode_steps of the seven equals the plan's, part by part
+    mfma, _ = DP.of_geometry(geo, 1)
+    assert not mfma and eng.decode_group_info() == {"max_group": DP.group_size(False, DP.MAX_BATCH), "any_size": int(DP.batch_ok(False, 3))} == {"max_group": 4, "any_size": 0}
+    assert [DP.parts(False, n) for n in (2, 3, 4, 7)] == [(2,), (2, 1), (4,), (4, 2, 1)]
+    seqs = []
+    for x in xs:
+        s = eng.seq_alloc(x.shape[0] + new)
+        eng.prefill(s, x)
+        seqs.append(s)
+    _, gemv, attn, other = DP.profiled(eng, lambda: eng.decode_steps(seqs, 2))
+    plans = [DP.of_geometry(geo, B)[1] for B in DP.parts(False, len(seqs))]
+    assert (gemv, attn, other) == (2 * sum(p.n_gemv for p in plans), 2 * sum(p.n_attn for p in plans), 2 * sum(p.n_other + 1 for p in plans)), (gemv, attn, other, plans)
+    assert all(p.n_gemv == 4 * geo.layers + 1 and p.n_attn == geo.layers and p.n_other == 1 for p in plans)
+    assert [eng.seq_read(s) for s in seqs] == [ids[:3] for ids in single]
+    for s in seqs:
+        eng.seq_free(s)
     eng.close()
 
 
@@ -523,7 +541,14 @@ def test_decode_groups_up_to_16_are_bit_identical_to_single_at_full_width():
     assert len({tuple(ids) for ids in got}) > 1
     # the batched teacher-forced step (beam search's per-token step): ONE weight stream, row i == the single-sequence call bit for bit
     toks = [7] * len(seqs)
-    lgb = eng.decode_step_logits_batch(seqs, toks)
+    # WHICH form ran, from the library's own plan (tests/decode_plan.py): the skinny-GEMM path with the fused RMSNorm -- the consumers read the raw tile-order copy
+    # against the norm-folded tile weights, no norm launch -- and the library's own launch counts for this step equal the plan's
+    mfma, plan = DP.of_geometry(geo, len(seqs))
+    assert mfma and eng.decode_group_info() == {"max_group": DP.group_size(True, DP.MAX_BATCH), "any_size": int(DP.batch_ok(True, 3))} == {"max_group": 16, "any_size": 1}
+    assert DP.rs(plan) and not plan.norm_launches and plan.embed_norm and plan.n_other == 1 and DP.parts(True, len(seqs)) == (len(seqs),)
+    assert all(plan.proj[k].weight == DP.TILED_FOLDED and plan.proj[k].input == DP.XT_SQ for k in (DP.QKV, DP.GATE_UP, DP.HEAD)) and plan.proj[DP.QKV0].input == DP.XN
+    lgb, gemv, attn, other = DP.profiled(eng, lambda: eng.decode_step_logits_batch(seqs, toks))
+    assert (gemv, attn) == (plan.n_gemv, plan.n_attn) == (4 * geo.layers + 1, geo.layers) and other == len(seqs) + plan.n_other + 1   # + one set_int per token, + selection
     for i, (_, lg) in enumerate(single):
         assert torch.equal(lgb[i], lg), i
     toks2 = [(3 * i + 1) % c["vocab"] for i in range(len(seqs))]          # a second step with different tokens per sequence, against per-sequence calls on clones
@@ -536,6 +561,48 @@ def test_decode_groups_up_to_16_are_bit_identical_to_single_at_full_width():
         eng.decode_step_logits_batch([seqs[0], seqs[0]], [1, 2])           # duplicate sequence
     for s in seqs:
         eng.seq_free(s)
+    eng.close()
+
+
+@pytest.mark.parametrize("hidden", [256, 512])
+def test_decode_forms_at_the_smallest_geometries(hidden):
+    """The decode step's forms (csrc/gvl_decode_plan.h) at the smallest geometries that have them, 2 layers of 4 heads: hidden = 256 is the smallest on the skinny-GEMM
+    path and has NO fused RMSNorm (hidden / 16 = 16 partial sums are no multiple of 32), hidden = 512 is the smallest that has it.  A group of 3 normalises in the
+    consumer, a group of 5 runs separate norm launches where the fused form is off.  Every group generates the ids of the one-at-a-time runs, the planned forms are those,
+    and the library's own launch counts equal the plan's -- the separate norm launches are told apart by the GVL_PROF_OTHER count alone."""
+    c = dict(hidden=hidden, inter=hidden, layers=2, heads=4, kv_heads=4, vocab=128)
+    geo = _phi_geo(c, max_seq=256, max_prefill=128, kv_pages=16)
+    W = synth.llm_weights("phi3", hidden, hidden, 2, 4, 4, 128, True, seed="t.dforms", device=DEV)
+    eng = llm_engine(geo, W)
+    g = torch.Generator(device=DEV); g.manual_seed(11)
+    embs = [(torch.randn((n, hidden), device=DEV, generator=g) * 0.5).to(bf) for n in (5, 70, 33, 64, 17)]
+    new = 4
+    for nf in ((1, 0) if hidden == 512 else (1,)):
+        eng.debug_set("norm_fused", nf)
+        single = [eng.generate_ids(e, new, None) for e in embs]
+        assert all(len(ids) == new for ids in single)
+        for n in (3, 5):
+            mfma, plan = DP.of_geometry(geo, n, norm_fused=nf)
+            rs = hidden == 512 and nf == 1
+            assert mfma and DP.parts(True, n) == (n,) and DP.rs(plan) == rs and DP.rs_ok(True, 0, nf, True, hidden) == rs
+            assert all(e.launcher == DP.DGEMM and e.weight == (DP.TILED_FOLDED if rs and k in (DP.QKV, DP.GATE_UP, DP.HEAD) else DP.TILED) for k, e in enumerate(plan.proj))
+            assert plan.proj[DP.QKV0].input == (DP.X_NORM if n == 3 else DP.XN) and plan.embed_norm == (n == 5)
+            assert plan.proj[DP.GATE_UP].input == (DP.XT_SQ if rs else plan.proj[DP.QKV0].input) and plan.norm_launches == (n == 5 and not rs)
+            assert plan.n_other == (1 + 2 * geo.layers if n == 5 and not rs else 1)
+            for profiled in (False, True):                       # the captured step graph, then eager steps the library counts
+                seqs = [eng.seq_alloc(e.shape[0] + new) for e in embs[:n]]
+                for s, e in zip(seqs, embs):
+                    eng.prefill(s, e)
+                if profiled:
+                    got, gemv, attn, other = DP.profiled(eng, lambda: eng.decode_greedy_batch(seqs, new, None))
+                    steps = new - 1                              # the prefill chose the first token
+                    assert (gemv, attn, other) == (steps * plan.n_gemv, steps * plan.n_attn, steps * (plan.n_other + 1)), (hidden, nf, n, gemv, attn, other)
+                else:
+                    got = eng.decode_greedy_batch(seqs, new, None)
+                for s in seqs:
+                    eng.seq_free(s)
+                assert got == single[:n], f"hidden {hidden}, norm_fused {nf}: the group of {n} differs from the one-at-a-time runs"
+    eng.debug_set("norm_fused", 1)
     eng.close()
 
 
