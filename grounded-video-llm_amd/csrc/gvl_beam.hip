@@ -95,7 +95,11 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
   hipStream_t st = (hipStream_t)stream;
 
   LogitsProc proc{p->penalty, p->ngram, p->min_new, p->proc_eos_id < 0 ? -1 : p->proc_eos_id};
-  const bool processed = proc.on() || p->rules_id >= 0;
+  // the grammar the caller's sequence carries (gvl_seq_set_grammar) constrains every beam; read here, before the clones' options go off below.  The sequence holds
+  // its reference for the whole call, so the blob outlives every launch
+  const int grammar_id = ctx->seqs[seq_id].sel.grammar;
+  const GrammarDev* grammar = grammar_id >= 0 ? (const GrammarDev*)ctx->grammars[grammar_id].d : nullptr;
+  const bool processed = proc.on() || p->rules_id >= 0 || grammar;
   const TokenRulesDev* rules = p->rules_id >= 0 ? (const TokenRulesDev*)ctx->rule_sets[p->rules_id].d : nullptr;
   const int seq_cap = std::min(pos0 + max_new + 1, (int)ctx->cfg.max_seq);
 
@@ -106,14 +110,14 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
   // own token pick leaves the logits rows raw; the scores come from the candidate kernels below.
   Owned own(ctx);
   auto clone = [&](int src, int* dst) {
-    const int rc = gvl_seq_clone(ctx, src, seq_cap, dst, stream);
+    const int rc = seq_clone(ctx, src, seq_cap, dst, (hipStream_t)stream, false);   // the search keeps the beams' histories itself (d_beam_hist)
     if (rc == 0) own.ids.push_back(*dst);
     return rc;
   };
   std::vector<int> beams(1, -1);
   if (const int rc = clone(seq_id, &beams[0])) return rc;
   { SeqSelect& sel = ctx->seqs[beams[0]].sel;
-    sel.proc = LogitsProc(); ctx->set_rules(sel, -1); sel.top_n = -1;
+    sel.proc = LogitsProc(); ctx->set_rules(sel, -1); ctx->set_grammar(sel, -1); sel.top_n = -1;
     const Sampling greedy; ctx->set_sampling(sel, &greedy); }
 
   float* h_vals = (float*)ctx->h_beam_cand; int* h_idx = (int*)(h_vals + kMaxCand); float* h_proc = h_vals + 2 * kMaxCand;
@@ -138,7 +142,7 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
       lp.logits = work; lp.n = V; lp.ld = V; lp.batch = n_rows; lp.cap = hs;
       for (int b = 0; b < n_rows; ++b) {
         lp.hist[b] = d_hist + (size_t)b * hs; lp.len_ptrs[b] = d_lens + b;
-        lp.penalty[b] = proc.penalty; lp.ngram[b] = proc.ngram; lp.eos[b] = proc.eos; lp.min_new[b] = proc.eos >= 0 ? proc.min_new : 0; lp.rules[b] = rules;
+        lp.penalty[b] = proc.penalty; lp.ngram[b] = proc.ngram; lp.eos[b] = proc.eos; lp.min_new[b] = proc.eos >= 0 ? proc.min_new : 0; lp.rules[b] = rules; lp.grammar[b] = grammar;
       }
       RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
     }

@@ -53,7 +53,8 @@ struct ProfRec { int cat; hipEvent_t e0, e1; double work; };
 struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule sets and the default settings of new sequences
   static constexpr int kMaxSeqs = 256;   // live sequences (slots of the device-side tables); the KV pool is the real limit
   static constexpr int kMaxRuleSets = 1024;
-  gvl_ctx() : SeqTable<Seq>(kMaxSeqs, kMaxRuleSets) {}
+  static constexpr int kMaxGrammars = 64;
+  gvl_ctx() : SeqTable<Seq>(kMaxSeqs, kMaxRuleSets, kMaxGrammars) {}
   gvl_config cfg;
   std::string err;
   std::unordered_map<std::string, Tensor> w;

@@ -943,3 +943,12 @@ int gvl_launch_set_int(int* p, int v, hipStream_t st) {
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, st, p, v);
   return CHECK_LAUNCH();
 }
+__global__ __launch_bounds__(256) void copy_ints_kernel(const int* __restrict__ src, int* __restrict__ dst, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+int gvl_launch_copy_ints(const int* src, int* dst, int n, hipStream_t st) {
+  if (n <= 0) return n < 0 ? -1 : 0;
+  int blocks = (n + 255) / 256; if (blocks > 256) blocks = 256;
+  hipLaunchKernelGGL(copy_ints_kernel, dim3(blocks), dim3(256), 0, st, src, dst, n);
+  return CHECK_LAUNCH();
+}

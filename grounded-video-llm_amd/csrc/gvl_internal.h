@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gvl_grammar.h"   // decoding grammars: blob header and walk, shared with the host
 
 typedef uint16_t bf16_t;  // raw bf16 bits
 
@@ -408,10 +409,16 @@ constexpr int GVL_RULES_MAX_SEQS = 1024;       // multi-token entries of one tab
 constexpr int GVL_RULES_MAX_SEQ_LEN = 16;      // ids of one multi-token entry
 struct TokenRulesDev { int n_suppress, off_suppress, n_begin, off_begin, begin_at, n_force, off_force, force_at, n_multi;
                        int n_tgt[2], off_tgt[2], off_ent[2], off_pre[2]; };
+// A decoding grammar of a row (gvl_grammar_create; gvl_grammar.h holds the blob's layout and the walk): after the min-length ban, before forced eos -- HF's
+// PrefixConstrainedLogitsProcessor.  The mask is a pure function of the blob and the row's history; no state is kept between launches.
+using GrammarDev = gvl_grammar::Header;
+static_assert(gvl_grammar::HIST_CAP == GVL_LOGITS_HIST_CAP, "the walk covers exactly the staged history");
 // rules[b]: null = row b has no token rules; any row non-null selects the kernel's second instantiation (after every field the first one reads)
+// grammar[b]: null = row b has no grammar; any row non-null selects the third instantiation (after every field the other two read)
 struct LogitsProcArgs { float* logits; int n, ld, batch, cap; const int* hist[GVL_MAX_DECODE_BATCH]; const int* len_ptrs[GVL_MAX_DECODE_BATCH];
                         float penalty[GVL_MAX_DECODE_BATCH]; int ngram[GVL_MAX_DECODE_BATCH], min_new[GVL_MAX_DECODE_BATCH], eos[GVL_MAX_DECODE_BATCH];
-                        const TokenRulesDev* rules[GVL_MAX_DECODE_BATCH]; };
+                        const TokenRulesDev* rules[GVL_MAX_DECODE_BATCH];
+                        const GrammarDev* grammar[GVL_MAX_DECODE_BATCH]; };
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st);
 // x[b][:] = table[*tok_ptrs[b]][:] for the sequences of the batched decode loop
 struct TokPtrs { const int* p[GVL_MAX_DECODE_BATCH]; int n; };
@@ -422,6 +429,7 @@ int gvl_launch_embed_norm(const bf16_t* table, const TokPtrs& toks, bf16_t* x, b
 int gvl_launch_norm_tiled(bf16_t* x, bf16_t* xn, const bf16_t* w, int batch, int cols, float eps, hipStream_t st);
 int gvl_launch_kv_page_copy(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int layers, int src_page, int dst_page, hipStream_t st);
 int gvl_launch_set_int(int* p, int v, hipStream_t st);
+int gvl_launch_copy_ints(const int* src, int* dst, int n, hipStream_t st);   // n 4-byte words, device -> device, any alignment (a clone's generated ids)
 
 // ---- frame pre-processing (gvl_pre.hip) -------------------------------------------------------------------------
 // frames uint8, layout 0 = [n][H][W][3] / 1 = [n][3][H][W] -> out f32 [n][3][size][size]; *scratch grows on demand (caller-owned).

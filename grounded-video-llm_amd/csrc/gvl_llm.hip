@@ -44,11 +44,11 @@ int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st) {
 // group has logits processors (gvl_seq_set_processors), one launch applies them to the rows first; its history is the sequence's output list
 // (host-mapped) up to its device-side generation count, so a captured decode step replays with nothing baked in per step.  With every processor
 // off the launch sequence is the one without processors.  A sequence's token rules (gvl_seq_set_token_rules) ride in the same launch: it runs
-// when a member has processors OR rules, and with neither nothing changes.  Sequences with log-probabilities on (gvl_seq_set_logprobs) get them from the same
+// when a member has processors OR rules OR a grammar (gvl_seq_set_grammar), and with none of them nothing changes.  Sequences with log-probabilities on (gvl_seq_set_logprobs) get them from the same
 // launch (a second instantiation of the selection kernel); with every sequence of the group off it is the kernel without them.
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
   bool any_proc = false;
-  for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->sel.proc.on() || sqs[b]->sel.rules >= 0;
+  for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->sel.proc.on() || sqs[b]->sel.rules >= 0 || sqs[b]->sel.grammar >= 0;
   if (any_proc) {
     LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
     lp.logits = const_cast<float*>(am.logits); lp.n = am.n; lp.ld = am.n; lp.batch = am.batch;
@@ -58,6 +58,7 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
       lp.hist[b] = sqs[b]->d_out; lp.len_ptrs[b] = sqs[b]->d_ngen;
       lp.penalty[b] = q.penalty; lp.ngram[b] = q.ngram; lp.min_new[b] = q.eos >= 0 ? q.min_new : 0; lp.eos[b] = q.eos;
       lp.rules[b] = sqs[b]->sel.rules >= 0 ? (const TokenRulesDev*)ctx->rule_sets[sqs[b]->sel.rules].d : nullptr;
+      lp.grammar[b] = sqs[b]->sel.grammar >= 0 ? (const GrammarDev*)ctx->grammars[sqs[b]->sel.grammar].d : nullptr;
     }
     const int rc = gvl_launch_logits_process(lp, st);
     if (rc) return rc;

@@ -8,7 +8,8 @@
 //   SequenceBiasLogitsProcessor        BEFORE the penalty: s[t] += the fp32 sum (from 0.0f) of t's length-1 bias, then of every multi-token entry
 //                                      ending in t whose first len - 1 ids equal the last len - 1 history ids; entries longer than the history are skipped
 //   NoBadWordsLogitsProcessor          after the n-gram bans: the same mechanism with bias -inf
-//   ForcedEOSTokenLogitsProcessor      after the min-length ban, when the history holds force_at ids: every score -inf, the forced ids 0
+//   PrefixConstrainedLogitsProcessor   after the min-length ban: a decoding grammar (gvl_grammar_create, gvl_grammar.h) -- allowed s[t] += 0.0f, forbidden -inf
+//   ForcedEOSTokenLogitsProcessor      after the grammar, when the history holds force_at ids: every score -inf, the forced ids 0
 //   SuppressTokens / ...AtBegin        the listed scores -inf (at every step / when the history holds begin_at ids)
 // The history is the GENERATED ids only: the reference calls generate(inputs_embeds=...) without input_ids, so HF's input_ids start empty.
 // gfx950 only.
@@ -42,8 +43,47 @@ __device__ __forceinline__ void bias_stage(float* s, int n, const int* blob, con
   }
 }
 
-template <bool RULES>
+// GRAMMAR = true (with RULES) is the instantiation for launches in which a row has a decoding grammar (a null grammar[b] = a row without): HF's
+// PrefixConstrainedLogitsProcessor, after the min-length ban and before forced eos.  The mask is a pure function of the grammar blob and the staged history
+// (gvl_grammar.h: the same pack_id / step / edge_allows / is_end as the host's reference walk): the history is rewritten in place as class | ordinal << 8
+// (no earlier stage reads it afterwards), the transition table is copied to LDS, thread 0 walks the L entries, and every thread sweeps the row:
+// allowed s[t] = s[t] + 0.0f (HF's `scores + mask`: -0.0 becomes +0.0), forbidden -inf.  An OFF walk or an END state leaves the row untouched.
+// The barriers are uniform per block: grammar[b] is per row.
+__device__ __forceinline__ void grammar_stage(float* s, int n, const GrammarDev* G, int* h, int Lraw, int L, int cap, int tid) {
+  namespace gg = gvl_grammar;
+  __shared__ unsigned short tr[gg::MAX_TRANS];
+  __shared__ int base[gg::MAX_CLASSES];
+  __shared__ int at[2];                                      // (state, reg) after the walk; state -1: OFF or END
+  const int* blob = reinterpret_cast<const int*>(G);
+  const gg::Header H = *G;
+  const unsigned char* cls = reinterpret_cast<const unsigned char*>(blob + H.off_class);
+  const int* gbase = blob + H.off_base;
+  const unsigned short* gtr = reinterpret_cast<const unsigned short*>(blob + H.off_trans);
+  const int nt = H.n_states * H.n_classes;
+  for (int i = tid; i < L; i += 1024) h[i] = gg::pack_id(h[i], H.vocab, cls, gbase);
+  for (int i = tid; i < nt; i += 1024) tr[i] = gtr[i];
+  if (tid < H.n_classes) base[tid] = gbase[tid];
+  __syncthreads();
+  if (tid == 0) {
+    int state = H.start, reg = 0;
+    bool on = Lraw <= cap;                                   // a history longer than the staged window cannot be walked
+    for (int i = 0; on && i < L; ++i) on = gg::step(tr, H.n_classes, state, reg, h[i]);
+    at[0] = on && !gg::is_end(tr, H.n_classes, state) ? state : -1; at[1] = reg;
+  }
+  __syncthreads();
+  const int state = at[0], reg = at[1];
+  if (state < 0) return;
+  const unsigned short* row = tr + state * H.n_classes;
+  for (int t = tid; t < n; t += 1024) {
+    bool ok = false;
+    if (t < H.vocab) { const int c = cls[t], bs = base[c]; ok = gg::edge_allows(row[c], bs >= 0 ? t - bs : 0, reg); }
+    s[t] = ok ? __fadd_rn(s[t], 0.0f) : -INFINITY;
+  }
+}
+
+template <bool RULES, bool GRAMMAR>
 __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcArgs a) {
+  static_assert(RULES || !GRAMMAR, "the grammar instantiation carries the rules");
   __shared__ int h[GVL_LOGITS_HIST_CAP];
   const int b = blockIdx.x, tid = threadIdx.x;
   float* s = a.logits + (size_t)b * a.ld;
@@ -55,7 +95,9 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcAr
   const float p = a.penalty[b];
   const int ng = a.ngram[b];
   const bool pen = p != 1.0f && L > 0, ban = ng > 0 && L >= ng;
-  if (pen || ban || R.n_multi > 0)
+  const GrammarDev* G = nullptr;
+  if constexpr (GRAMMAR) G = a.grammar[b];
+  if (pen || ban || R.n_multi > 0 || G)
     for (int i = tid; i < L; i += 1024) h[i] = a.hist[b][i];
   __syncthreads();
   if constexpr (RULES) {                                     // sequence_bias lands before the penalty's gather
@@ -94,6 +136,10 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcAr
     __syncthreads();
   }
   if (tid == 0 && L < a.min_new[b] && a.eos[b] >= 0 && a.eos[b] < a.n) s[a.eos[b]] = -INFINITY;
+  if constexpr (GRAMMAR) {
+    __syncthreads();                                         // the min-length ban has landed; every reader of the raw history is done
+    if (G) grammar_stage(s, a.n, G, h, Lraw, L, a.cap, tid);
+  }
   if constexpr (RULES) {
     const bool force = R.n_force > 0 && Lraw == R.force_at;
     __syncthreads();
@@ -109,13 +155,15 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcAr
 
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st) {
   if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH || !a.logits || a.n < 1 || a.ld < a.n || a.cap < 0 || a.cap > GVL_LOGITS_HIST_CAP) return -1;
-  bool rules = false;
+  bool rules = false, grammar = false;
   for (int b = 0; b < a.batch; ++b) {
     if (!(a.penalty[b] > 0.f) || a.ngram[b] < 0 || a.min_new[b] < 0) return -1;
-    if (a.cap > 0 && (a.penalty[b] != 1.0f || a.ngram[b] > 0 || a.rules[b]) && a.len_ptrs[b] && !a.hist[b]) return -1;
+    if (a.cap > 0 && (a.penalty[b] != 1.0f || a.ngram[b] > 0 || a.rules[b] || a.grammar[b]) && a.len_ptrs[b] && !a.hist[b]) return -1;
     rules = rules || a.rules[b];
+    grammar = grammar || a.grammar[b];
   }
-  if (rules) hipLaunchKernelGGL(logits_process_kernel<true>, dim3(a.batch), dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL(logits_process_kernel<false>, dim3(a.batch), dim3(1024), 0, st, a);
+  if (grammar) hipLaunchKernelGGL((logits_process_kernel<true, true>), dim3(a.batch), dim3(1024), 0, st, a);
+  else if (rules) hipLaunchKernelGGL((logits_process_kernel<true, false>), dim3(a.batch), dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL((logits_process_kernel<false, false>), dim3(a.batch), dim3(1024), 0, st, a);
   return CHECK_LAUNCH();
 }

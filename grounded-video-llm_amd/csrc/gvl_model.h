@@ -14,11 +14,13 @@ inline int fail(gvl_ctx* c, int code, const std::string& msg) { return gvl_fail(
 // a SeqStatus of the sequence table (gvl_seq_table.h) as the result of entry point `fn`: 0, or the status's error
 inline int seq_fail(gvl_ctx* c, const char* fn, int status) {
   if (status >= 0) return 0;
-  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_RULES_FULL
+  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_GRAMMAR_FULL
     {GVL_ERR_ARG, "bad seq"}, {GVL_ERR_ARG, "duplicate seq"}, {GVL_ERR_OOM, "KV pages exhausted"}, {GVL_ERR_OOM, "too many live sequences"}, {GVL_ERR_ARG, "no such rule set"},
     {GVL_ERR_STATE, "the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)"},
-    {GVL_ERR_ARG, "too many live rule sets (limit 1024)"}};
-  const auto& x = e[status >= SEQ_RULES_FULL ? -1 - status : 0];
+    {GVL_ERR_ARG, "too many live rule sets (limit 1024)"}, {GVL_ERR_ARG, "no such grammar"},
+    {GVL_ERR_STATE, "the grammar is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_grammar(-1) first)"},
+    {GVL_ERR_ARG, "too many live grammars (limit 64)"}};
+  const auto& x = e[status >= SEQ_GRAMMAR_FULL ? -1 - status : 0];
   return fail(c, x.code, std::string(fn) + ": " + x.text);
 }
 
@@ -89,6 +91,10 @@ size_t prefill_bytes(const gvl_ctx* c, int S);
 int clip_encode(gvl_ctx* ctx, const float* px, int n, float* out, hipStream_t st);
 int iv2_encode(gvl_ctx* ctx, const float* px, int n, bf16_t* out, hipStream_t st);
 int build_visual(gvl_ctx* ctx, const float* clip_feats, const bf16_t* iv2_feats, int n, bf16_t* visual, hipStream_t st);
+
+// gvl_model.hip: gvl_seq_clone.  carry_generated: the clone also takes the source's generated ids, their count and the id to feed next (what gvl_seq_clone does for a
+// source with a grammar); false: its history starts empty (gvl_beam_search's beams, whose histories the search keeps itself)
+int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated);
 
 // gvl_llm.hip
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);

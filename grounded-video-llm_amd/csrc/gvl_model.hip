@@ -181,6 +181,7 @@ int gvl_destroy(gvl_ctx* ctx) {
   ctx->nf_allocs.clear();
   if (ctx->comm) gvl_comm_destroy(ctx);
   for (RuleSet& r : ctx->rule_sets) if (r.used && r.d) hipFree(r.d);
+  for (GrammarSet& g : ctx->grammars) if (g.used && g.d) hipFree(g.d);
   void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch, ctx->d_beam_scratch, ctx->d_beam_rows, ctx->d_beam_hist};
   for (void* p : ptrs) if (p) hipFree(p);
   for (auto& r : ctx->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
@@ -496,6 +497,9 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
   if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: bad arguments");
   if (n_tokens <= 0 || (n_tokens & 63) || n_tokens > ctx->seqs[src_seq].pos) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: n_tokens must be a positive multiple of 64 within the source's tokens");
   if (max_tokens <= n_tokens || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: max_tokens must exceed n_tokens and fit cfg.max_seq");
+  if (ctx->fork_cuts_answer(ctx->seqs[src_seq], n_tokens))
+    return fail(ctx, GVL_ERR_STATE, "gvl_seq_fork: the source has a grammar and the prefix holds ids it generated; the rows appended behind a fork are embeddings, so its walk "
+                                    "could not continue (fork within the prompt, gvl_seq_clone, or gvl_seq_set_grammar(src, -1) first)");
   const int id = ctx->open(max_tokens, src_seq, n_tokens);
   if (id < 0) return seq_fail(ctx, "gvl_seq_fork", id);
   bind_slot(ctx, ctx->seqs[id], id);
@@ -518,25 +522,48 @@ int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, float* 
 }
 
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream) {
+  // A source with a grammar hands its answer so far to the clone: the mask is a function of the generated ids, so without them the clone's walk would start over
+  // mid-answer.  Without a grammar a clone's history starts empty, as ever.
+  Seq* src = ctx ? ctx->lookup(src_seq) : nullptr;
+  return seq_clone(ctx, src_seq, max_tokens, dst_seq, (hipStream_t)stream, src && src->sel.grammar >= 0);
+}
+}  // extern "C"
+
+int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
   if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
   const int pos = ctx->seqs[src_seq].pos;
   if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
+  if (carry_generated && ctx->seqs[src_seq].n_gen > ctx->outlist_cap) return fail(ctx, GVL_ERR_STATE, "gvl_seq_clone: the source generated more ids than an output list holds");
   const int id = ctx->open(max_tokens, src_seq, pos);
   if (id < 0) return seq_fail(ctx, "gvl_seq_clone", id);
   Seq& s = ctx->seqs[id];
   bind_slot(ctx, s, id);
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = stream;
   { const int rc = upload_table(ctx, s, st); if (rc) return rc; }   // by value, on the clone's stream: ordered behind the source's pending steps there
   if (pos & 63)                                       // the partial last page is private: copy the source's (all layers, K and V^T)
     RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_copy(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers,
                                                    ctx->seqs[src_seq].pages[pos >> 6], s.pages[pos >> 6], st));
   RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(s.d_pos, pos, st));
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(s.d_ngen, 0, st));
-  s.n_gen = 0;
+  const Seq& from = ctx->seqs[src_seq];
+  const int n = carry_generated ? from.n_gen : 0;
+  if (n > 0) {   // the ids generated so far, the one to feed next and, where the source keeps them, their log-probabilities: the clone stands where the source stands
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_ints(from.d_out, s.d_out, n, st));
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_ints(from.d_tok, s.d_tok, 1, st));
+    if (from.sel.top_n >= 0 && from.d_lp && s.d_lp) {   // (floats travel as their 4-byte words)
+      RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_ints((const int*)from.d_lp, (int*)s.d_lp, n, st));
+      if (from.sel.top_n > 0) {
+        RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_ints(from.d_top_ids, s.d_top_ids, n * GVL_MAX_TOP_LOGPROBS, st));
+        RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_ints((const int*)from.d_top_lp, (int*)s.d_top_lp, n * GVL_MAX_TOP_LOGPROBS, st));
+      }
+    }
+  }
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(s.d_ngen, n, st));
+  s.n_gen = n;
   *dst_seq = id;
   return 0;
 }
+extern "C" {
 
 int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_new, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend");

@@ -86,9 +86,9 @@ int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, i
   sq->sel.proc = LogitsProc{penalty, ngram, min_new, eos_id < 0 ? -1 : eos_id};
   return 0;
 }
-// the processors, and with rules_ids (entry point `what` = gvl_op_logits_process_rules) the rule sets, on `batch` rows of logits
+// the processors, with rules_ids (entry points gvl_op_logits_process_rules / _ex) the rule sets and with grammar_ids (gvl_op_logits_process_ex) the grammars, on `batch` rows of logits
 static int op_logits_process(gvl_ctx* ctx, const char* what, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
-                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
+                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream, const int* grammar_ids = nullptr) {
   if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
       hist_stride < 0 || (hist_stride > 0 && !hist_dev))
     return fail(ctx, GVL_ERR_ARG, std::string(what) + ": bad arguments");
@@ -101,6 +101,12 @@ static int op_logits_process(gvl_ctx* ctx, const char* what, float* logits, int 
     lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
     lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
     lp.rules[b] = rules_ids && rules_ids[b] >= 0 ? (const TokenRulesDev*)ctx->rule_sets[rules_ids[b]].d : nullptr;
+    if (grammar_ids && grammar_ids[b] != -1) {
+      if (const int rc = ctx->check_grammar(grammar_ids[b])) return seq_fail(ctx, what, rc);
+      const GrammarSet& g = ctx->grammars[grammar_ids[b]];
+      if (g.vocab != n) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": the grammar classifies " + std::to_string(g.vocab) + " ids, the rows hold " + std::to_string(n));
+      lp.grammar[b] = (const GrammarDev*)g.d;
+    }
   }
   RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
   return 0;
@@ -205,6 +211,55 @@ int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, c
                                 const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
   if (!rules_ids) return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process_rules: bad arguments");
   return op_logits_process(ctx, "gvl_op_logits_process_rules", logits, n, batch, hist_dev, hist_stride, lens_dev, penalty, ngram, min_new, eos_ids, rules_ids, stream);
+}
+int gvl_op_logits_process_ex(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, const int* grammar_ids, void* stream) {
+  return op_logits_process(ctx, "gvl_op_logits_process_ex", logits, n, batch, hist_dev, hist_stride, lens_dev, penalty, ngram, min_new, eos_ids, rules_ids, stream, grammar_ids);
+}
+
+// ---- decoding grammars (gvl_grammar.h; the GRAMMAR stage of gvl_logits.hip): a DFA over token classes with one register, an immutable device object
+int gvl_grammar_create(gvl_ctx* ctx, const gvl_grammar_desc* d, int* grammar_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!d || !grammar_id) return fail(ctx, GVL_ERR_ARG, "gvl_grammar_create: bad arguments");
+  const gvl_grammar::Desc desc{d->n_states, d->n_classes, d->start, d->vocab, d->token_class, d->class_base, d->trans};
+  const std::string bad = gvl_grammar::check(desc);
+  if (!bad.empty()) return fail(ctx, GVL_ERR_ARG, "gvl_grammar_create: " + bad);
+  const int id = ctx->add_grammar(nullptr, d->vocab);   // the slot first: its blob follows below, a failure there gives the slot back
+  if (id < 0) return seq_fail(ctx, "gvl_grammar_create", id);
+  const std::vector<uint32_t> w = gvl_grammar::pack(desc);
+  GrammarSet& g = ctx->grammars[id];
+  hipError_t e = hipMalloc((void**)&g.d, w.size() * 4);
+  if (e != hipSuccess) { g = GrammarSet(); return gvl_hipfail(ctx, e, "gvl_grammar_create: hipMalloc"); }
+  e = hipMemcpy(g.d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(g.d); g = GrammarSet(); return gvl_hipfail(ctx, e, "gvl_grammar_create: hipMemcpy"); }
+  *grammar_id = id;
+  return 0;
+}
+int gvl_grammar_destroy(gvl_ctx* ctx, int grammar_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = ctx->destroy_grammar(grammar_id, nullptr)) return seq_fail(ctx, "gvl_grammar_destroy", rc);   // asks only
+  HIPCHK(ctx, hipDeviceSynchronize());                 // every launch that read the grammar has finished before its memory goes
+  void* blob = nullptr; ctx->destroy_grammar(grammar_id, &blob); hipFree(blob);
+  return 0;
+}
+// a grammar bound to sequences classifies exactly the model's vocabulary: the rows it masks are cfg.vocab wide
+static int check_seq_grammar(gvl_ctx* ctx, const char* what, int grammar_id) {
+  if (const int rc = ctx->check_grammar(grammar_id)) return seq_fail(ctx, what, rc);
+  if (grammar_id >= 0 && ctx->grammars[grammar_id].vocab != ctx->cfg.vocab)
+    return fail(ctx, GVL_ERR_ARG, std::string(what) + ": the grammar classifies " + std::to_string(ctx->grammars[grammar_id].vocab) + " ids, the model's vocabulary holds " + std::to_string(ctx->cfg.vocab));
+  return 0;
+}
+int gvl_set_grammar(gvl_ctx* ctx, int grammar_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (const int rc = check_seq_grammar(ctx, "gvl_set_grammar", grammar_id)) return rc;
+  return seq_fail(ctx, "gvl_set_grammar", ctx->set_grammar(ctx->sel_default, grammar_id));
+}
+int gvl_seq_set_grammar(gvl_ctx* ctx, int seq_id, int grammar_id) {
+  if (!ctx) return GVL_ERR_ARG;
+  Seq* sq = ctx->lookup(seq_id);
+  if (!sq) return seq_fail(ctx, "gvl_seq_set_grammar", SEQ_BAD);
+  if (const int rc = check_seq_grammar(ctx, "gvl_seq_set_grammar", grammar_id)) return rc;
+  return seq_fail(ctx, "gvl_seq_set_grammar", ctx->set_grammar(sq->sel, grammar_id));
 }
 
 // ---- log-probabilities of the selected tokens (ArgmaxArgs.top_n / lp_lists / top_ids / top_lp; gvl_elem.hip)

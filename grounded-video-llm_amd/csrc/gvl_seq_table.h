@@ -19,25 +19,30 @@ struct Sampling {
   bool warps() const { return on && (min_p > 0.f || (typical_p > 0.f && typical_p < 1.f) || eps > 0.f || eta > 0.f); }   // uses a warper past top-p
 };
 // own_sampling: the sequence has its own `sampling` (gvl_seq_set_sampling) instead of following the table-wide setting at every selection
-struct SeqSelect { LogitsProc proc; int top_n = -1; int rules = -1; bool own_sampling = false; Sampling sampling; };
+// grammar: a decoding grammar (gvl_grammar_create; -1 none), counted in its refs exactly like rules
+struct SeqSelect { LogitsProc proc; int top_n = -1; int rules = -1; bool own_sampling = false; Sampling sampling; int grammar = -1; };
 // a token rule set: one opaque device blob (gvl_rules_create) and how many sequences / the default reference it
 struct RuleSet { bool used = false; void* d = nullptr; int refs = 0; };
+// a decoding grammar (gvl_grammar.h): one opaque device blob, the vocabulary it classifies, and how many sequences / the default reference it
+struct GrammarSet { bool used = false; void* d = nullptr; int refs = 0; int vocab = 0; };
 // the host state of one sequence slot; Seq (gvl_ctx.h) adds the slot's device pointers
 struct SeqCore {
   bool used = false; int max_tokens = 0, n_pages = 0, pos = 0, n_gen = 0;
   std::vector<int> pages;   // KV pages in position order, 64 tokens each: whole pages of a prefix may be shared with other sequences (page_ref)
   SeqSelect sel;
 };
-enum SeqStatus { SEQ_OK = 0, SEQ_BAD = -1, SEQ_DUPLICATE = -2, SEQ_NO_PAGES = -3, SEQ_TOO_MANY = -4, SEQ_NO_RULES = -5, SEQ_RULES_BUSY = -6, SEQ_RULES_FULL = -7 };
+enum SeqStatus { SEQ_OK = 0, SEQ_BAD = -1, SEQ_DUPLICATE = -2, SEQ_NO_PAGES = -3, SEQ_TOO_MANY = -4, SEQ_NO_RULES = -5, SEQ_RULES_BUSY = -6, SEQ_RULES_FULL = -7,
+                 SEQ_NO_GRAMMAR = -8, SEQ_GRAMMAR_BUSY = -9, SEQ_GRAMMAR_FULL = -10 };
 
 template <class S = SeqCore>
 struct SeqTable {
-  std::vector<S> seqs; std::vector<RuleSet> rule_sets;
+  std::vector<S> seqs; std::vector<RuleSet> rule_sets; std::vector<GrammarSet> grammars;
   std::vector<int> free_pages, page_ref;   // page_ref: sequences holding each page -- full pages of a shared prefix are referenced, never copied (gvl_seq_fork)
   SeqSelect sel_default;                   // what a sequence without a source starts with (off / none by default)
   const int max_seqs, max_rule_sets;       // slots of the device-side tables; live rule sets
+  const int max_grammars;                  // live grammars
 
-  SeqTable(int max_seqs_, int max_rule_sets_) : max_seqs(max_seqs_), max_rule_sets(max_rule_sets_) {}
+  SeqTable(int max_seqs_, int max_rule_sets_, int max_grammars_ = 64) : max_seqs(max_seqs_), max_rule_sets(max_rule_sets_), max_grammars(max_grammars_) {}
   void reset_pool(int pages) { free_pages.clear(); page_ref.assign(pages, 0); for (int p = pages - 1; p >= 0; --p) free_pages.push_back(p); }
   template <class V> static int first_unused(const V& v) { int i = 0; while (i < (int)v.size() && v[i].used) ++i; return i; }   // v.size(): none
   S* lookup(int id) { return id >= 0 && id < (int)seqs.size() && seqs[id].used ? &seqs[id] : nullptr; }
@@ -56,17 +61,19 @@ struct SeqTable {
     s.used = true; s.max_tokens = max_tokens; s.n_pages = np; s.pos = pos;
     s.sel = src >= 0 ? seqs[src].sel : sel_default;
     if (s.sel.rules >= 0) ++rule_sets[s.sel.rules].refs;
+    if (s.sel.grammar >= 0) ++grammars[s.sel.grammar].refs;
     if (src >= 0) s.pages.assign(seqs[src].pages.begin(), seqs[src].pages.begin() + shared);
     for (int p : s.pages) ++page_ref[p];
     for (int i = shared; i < np; ++i) { s.pages.push_back(free_pages.back()); free_pages.pop_back(); page_ref[s.pages.back()] = 1; }
     if (id == (int)seqs.size()) seqs.push_back(std::move(s)); else seqs[id] = std::move(s);
     return id;
   }
-  // the sequence's pages and rule set go back; a page shared with a fork lives on until its last holder is closed
+  // the sequence's pages, rule set and grammar go back; a page shared with a fork lives on until its last holder is closed
   int close(int id) {
     S* s = lookup(id); if (!s) return SEQ_BAD;
     for (int p : s->pages) if (--page_ref[p] == 0) free_pages.push_back(p);
     if (s->sel.rules >= 0) --rule_sets[s->sel.rules].refs;
+    if (s->sel.grammar >= 0) --grammars[s->sel.grammar].refs;
     *s = S(); return SEQ_OK;
   }
   // `sel` (a sequence's) takes its own sampling setting; q null: back to following the table-wide setting, as a new sequence does
@@ -91,6 +98,35 @@ struct SeqTable {
     if (id < 0 || check_rules(id)) return SEQ_NO_RULES;
     if (rule_sets[id].refs > 0) return SEQ_RULES_BUSY;
     if (d) { *d = rule_sets[id].d; rule_sets[id] = RuleSet(); }
+    return SEQ_OK;
+  }
+  // ---- grammars: the same life cycle as rule sets
+  // -1 (none) or a live grammar
+  int check_grammar(int id) const { return id < -1 || id >= (int)grammars.size() || (id >= 0 && !grammars[id].used) ? SEQ_NO_GRAMMAR : SEQ_OK; }
+  int add_grammar(void* d, int vocab) {
+    const int id = first_unused(grammars);
+    if (id >= max_grammars) return SEQ_GRAMMAR_FULL;
+    if (id == (int)grammars.size()) grammars.emplace_back();
+    grammars[id] = GrammarSet{true, d, 0, vocab}; return id;
+  }
+  // `sel` (a sequence's, or sel_default) takes grammar `id` (-1: none) and drops the one it held
+  int set_grammar(SeqSelect& sel, int id) {
+    if (check_grammar(id)) return SEQ_NO_GRAMMAR;
+    if (id >= 0) ++grammars[id].refs;                // before the drop: `id` may be the grammar it holds
+    if (sel.grammar >= 0) --grammars[sel.grammar].refs;
+    sel.grammar = id; return SEQ_OK;
+  }
+  // A grammar's mask is a function of the sequence's generated ids, so a copy taken mid-answer must know them.  Generated id i of `s` sits at position
+  // first_generated(s) + i once it is fed (prefill leaves n_gen = 1 with id 0 picked and not yet fed; every step adds one position and one id).
+  static int first_generated(const SeqCore& s) { return s.n_gen > 0 ? s.pos - s.n_gen + 1 : s.pos; }
+  // a fork's shared prefix of n_tokens would hold generated ids of a source with a grammar: the rows gvl_prefill_extend appends behind it are embeddings whose
+  // ids nobody tells the library, so the fork's walk could not be continued -- such a fork is refused (gvl_seq_clone carries the ids instead)
+  static bool fork_cuts_answer(const SeqCore& s, int n_tokens) { return s.sel.grammar >= 0 && s.n_gen > 0 && n_tokens > first_generated(s); }
+  // refused while a sequence or the default references the grammar.  d null: only asks; otherwise the grammar goes and *d is its blob, which the caller now owns
+  int destroy_grammar(int id, void** d) {
+    if (id < 0 || check_grammar(id)) return SEQ_NO_GRAMMAR;
+    if (grammars[id].refs > 0) return SEQ_GRAMMAR_BUSY;
+    if (d) { *d = grammars[id].d; grammars[id] = GrammarSet(); }
     return SEQ_OK;
   }
 };

@@ -328,7 +328,8 @@ class Engine:
         return sid.value
 
     def seq_clone(self, src: int, max_tokens: int) -> int:
-        """A copy of `src` at its current length: whole pages shared by reference, the partial last page copied (gvl_seq_clone; beam search)."""
+        """A copy of `src` at its current length: whole pages shared by reference, the partial last page copied (gvl_seq_clone; beam search).
+        Its generated ids (seq_read) start empty; a clone of a sequence WITH a grammar takes the source's generated ids along and continues its answer."""
         sid = C.c_int(-1)
         self._chk(self.lib.gvl_seq_clone(self.ctx, int(src), int(max_tokens), C.byref(sid), self.stream), "gvl_seq_clone")
         return sid.value
@@ -520,11 +521,12 @@ class Engine:
         return (out, score.value, [float(ts[i]) for i in range(n.value)]) if with_scores else out
 
     def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None,
-                     rules: Optional[int] = None):
-        """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  processors: a logits.Processors for this
+                     rules: Optional[int] = None, grammar: Optional[int] = None):
+        """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  grammar: a grammar_create id for this sequence (None: the
+        default of set_grammar).  processors: a logits.Processors for this
         sequence (None: the default of set_logits_processors).  rules: a rule-set id for this sequence (None: the default of set_token_rules).  logprobs: None = ids only; -1 .. 8 = this sequence's seq_set_logprobs setting, and
         the return value is (ids, (lp, top)) as seq_read_logprobs gives them for the ids (read before the sequence is freed)."""
-        opts = LP.SeqOptions(processors, logprobs, ... if rules is None else rules)
+        opts = LP.SeqOptions(processors, logprobs, ... if rules is None else rules, grammar=... if grammar is None else grammar)
         seq = self.seq_alloc(min(embeds.shape[0] + max_new_tokens, self.geo.max_seq))
         try:
             LP.apply_seq_options(self, seq, opts)
@@ -728,11 +730,12 @@ class Engine:
         self._chk(self.lib.gvl_seq_set_processors(self.ctx, int(seq), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
                                                   -1 if eos_id is None else int(eos_id)), "gvl_seq_set_processors")
 
-    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos, rules=None):
+    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos, rules=None, grammar=None):
         """gvl_op_logits_process on fp32 rows [B, n] (any B; 16 rows per launch): row b gets the processors (penalty[b], ngram[b], min_new[b],
         eos[b]) over the history histories[b].  `logits` must be a contiguous fp32 device tensor: it is changed IN PLACE and returned.
         rules: None, one rule-set id (rules_create) for every row, or a list with an id or None per row -- then gvl_op_logits_process_rules
-        runs the whole ordered pipeline (token rules around the processors)."""
+        runs the whole ordered pipeline (token rules around the processors).  grammar: the same for grammar ids (grammar_create; the grammar's
+        vocab must equal n) -- then gvl_op_logits_process_ex runs the pipeline with the grammar stage in HF's place."""
         assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2 and logits.device == self.device
         B, n = logits.shape
         assert len(histories) == B
@@ -746,12 +749,16 @@ class Engine:
         per_row = lambda v, t: [t(x) for x in (v if isinstance(v, (list, tuple)) else [v] * B)]
         pe, ng, mn, eo = per_row(penalty, float), per_row(ngram, int), per_row(min_new, int), per_row(eos, lambda x: -1 if x is None else int(x))
         ru = None if rules is None else per_row(rules, lambda x: -1 if x is None else int(x))
+        gr = None if grammar is None else per_row(grammar, lambda x: -1 if x is None else int(x))
         for b0 in range(0, B, 16):
             nb = min(16, B - b0)
             args = (self.ctx, C.c_void_p(logits.data_ptr() + b0 * n * 4), n, nb, C.c_void_p(hist.data_ptr() + b0 * width * 4),
                     width, C.c_void_p(lens.data_ptr() + b0 * 4), (C.c_float * nb)(*pe[b0:b0 + nb]), (C.c_int * nb)(*ng[b0:b0 + nb]),
                     (C.c_int * nb)(*mn[b0:b0 + nb]), (C.c_int * nb)(*eo[b0:b0 + nb]))
-            if ru is None:
+            if gr is not None:
+                rr = None if ru is None else (C.c_int * nb)(*ru[b0:b0 + nb])
+                self._chk(self.lib.gvl_op_logits_process_ex(*args, rr, (C.c_int * nb)(*gr[b0:b0 + nb]), self.stream), "gvl_op_logits_process_ex")
+            elif ru is None:
                 self._chk(self.lib.gvl_op_logits_process(*args, self.stream), "gvl_op_logits_process")
             else:
                 self._chk(self.lib.gvl_op_logits_process_rules(*args, (C.c_int * nb)(*ru[b0:b0 + nb]), self.stream), "gvl_op_logits_process_rules")
@@ -797,6 +804,31 @@ class Engine:
     def seq_set_token_rules(self, seq: int, rules_id: Optional[int]):
         """gvl_seq_set_token_rules: the rule set of one live sequence (None / -1: none)."""
         self._chk(self.lib.gvl_seq_set_token_rules(self.ctx, int(seq), -1 if rules_id is None else int(rules_id)), "gvl_seq_set_token_rules")
+
+    # ---- decoding grammars (grammar.Grammar -> a device grammar) ---------------------------------------------------
+    def grammar_create(self, grammar) -> int:
+        """gvl_grammar_create: a grammar.Grammar (or anything with its fields) as an immutable device grammar; returns its id.  Raises GvlError
+        (status ERR_ARG, with the library's message) for a description the library's checker refuses."""
+        tc = np.ascontiguousarray(np.asarray(grammar.token_class, dtype=np.uint8).reshape(-1))
+        cb = np.ascontiguousarray(np.asarray(grammar.class_base, dtype=np.int32).reshape(-1))
+        tr = np.ascontiguousarray(np.asarray(grammar.trans, dtype=np.uint16).reshape(-1))
+        d = L.GvlGrammarDesc(int(grammar.n_states), int(grammar.n_classes), int(grammar.start), int(grammar.vocab), tc.ctypes.data_as(C.POINTER(C.c_uint8)),
+                             cb.ctypes.data_as(C.POINTER(C.c_int32)), tr.ctypes.data_as(C.POINTER(C.c_uint16)))
+        gid = C.c_int(-1)
+        self._chk(self.lib.gvl_grammar_create(self.ctx, C.byref(d), C.byref(gid)), "gvl_grammar_create")
+        return gid.value
+
+    def grammar_destroy(self, grammar_id: int):
+        """gvl_grammar_destroy: GvlError (ERR_STATE) while a live sequence or the default still references the grammar."""
+        self._chk(self.lib.gvl_grammar_destroy(self.ctx, int(grammar_id)), "gvl_grammar_destroy")
+
+    def set_grammar(self, grammar_id: Optional[int] = None):
+        """gvl_set_grammar: the grammar of every sequence allocated AFTER this call (None / -1: none)."""
+        self._chk(self.lib.gvl_set_grammar(self.ctx, -1 if grammar_id is None else int(grammar_id)), "gvl_set_grammar")
+
+    def seq_set_grammar(self, seq: int, grammar_id: Optional[int]):
+        """gvl_seq_set_grammar: the grammar of one live sequence (None / -1: none)."""
+        self._chk(self.lib.gvl_seq_set_grammar(self.ctx, int(seq), -1 if grammar_id is None else int(grammar_id)), "gvl_seq_set_grammar")
 
     def set_logprobs(self, top_n: Optional[int] = -1):
         """gvl_set_logprobs: log-probabilities of the selected tokens for every sequence allocated AFTER this call.  None / -1 = off, 0 = the selected

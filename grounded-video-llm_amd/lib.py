@@ -45,6 +45,12 @@ class GvlRulesDesc(C.Structure):
                 ("begin_index", C.c_int32), ("n_force", C.c_int32), ("force_ids", C.POINTER(C.c_int32)), ("force_at", C.c_int32), ("bias", GvlBiasTable * 2)]
 
 
+class GvlGrammarDesc(C.Structure):
+    """gvl_grammar_desc (include/gvl.h): a DFA over token classes with one register."""
+    _fields_ = [("n_states", C.c_int32), ("n_classes", C.c_int32), ("start", C.c_int32), ("vocab", C.c_int32), ("token_class", C.POINTER(C.c_uint8)),
+                ("class_base", C.POINTER(C.c_int32)), ("trans", C.POINTER(C.c_uint16))]
+
+
 class GvlSampling(C.Structure):
     """gvl_sampling (include/gvl.h): one sampling setting, greedy when do_sample is 0."""
     _fields_ = [("do_sample", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float),
@@ -156,6 +162,12 @@ _SIGS = {
     "gvl_seq_set_token_rules": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gvl_op_logits_process_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float),
                                               C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "gvl_grammar_create": (C.c_int, [C.c_void_p, C.POINTER(GvlGrammarDesc), C.POINTER(C.c_int)]),
+    "gvl_grammar_destroy": (C.c_int, [C.c_void_p, C.c_int]),
+    "gvl_set_grammar": (C.c_int, [C.c_void_p, C.c_int]),
+    "gvl_seq_set_grammar": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "gvl_op_logits_process_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "gvl_set_logprobs": (C.c_int, [C.c_void_p, C.c_int]),
     "gvl_seq_set_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gvl_seq_read_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

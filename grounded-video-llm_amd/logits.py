@@ -140,14 +140,15 @@ def request_sampling(do_sample=None, temperature=None, top_k=None, top_p=None, m
 @dataclass(frozen=True)
 class SeqOptions:
     """One sequence's settings; per field leave what it was allocated with | off | set: processors None | OFF | a Processors; logprobs None | -1 | 0 .. 8; rules ... | None | a rules_create id;
-    sampling ... | None (follow the engine's setting) | a dict as Engine.seq_set_sampling takes it (the sequence's own setting)"""
+    sampling ... | None (follow the engine's setting) | a dict as Engine.seq_set_sampling takes it (the sequence's own setting); grammar ... | None | a grammar_create id"""
     processors: Optional[Processors] = None
     logprobs: Optional[int] = None
     rules: object = ...
     sampling: object = ...
+    grammar: object = ...
 
 
-SeqOptions.OFF = SeqOptions(OFF, -1, None)
+SeqOptions.OFF = SeqOptions(OFF, -1, None, grammar=None)
 
 
 def apply_seq_options(eng, seq: int, opts: SeqOptions) -> None:
@@ -160,6 +161,8 @@ def apply_seq_options(eng, seq: int, opts: SeqOptions) -> None:
         eng.seq_set_token_rules(seq, opts.rules)
     if opts.sampling is not ...:
         eng.seq_set_sampling(seq, opts.sampling)
+    if opts.grammar is not ...:
+        eng.seq_set_grammar(seq, opts.grammar)
 
 
 def read_seq_logprobs(eng, seq: int, ids, opts: SeqOptions):

@@ -19,6 +19,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import dist as gdist
+from . import grammar as GR
 from . import logits as LP
 from . import logprobs as LPR
 from . import prompts as P
@@ -283,6 +284,32 @@ class LLAVA_NEXT_VIDEO:
         if rid is not None:
             self.engine.rules_destroy(rid)
 
+    def _select_grammar(self, kw) -> Optional[int]:
+        """generate(grammar=g): a grammar.Grammar that constrains every answer of the call (HF's prefix_allowed_tokens_fn as a device object; the callback
+        itself cannot run inside a multi-token decode call and raises ValueError).  Sets the engine's default on EVERY generate call -- none when absent,
+        and none for beam search, whose own processing of the log-softmax rows takes the grammar -- so nothing carries over.  Returns the device grammar's
+        id (None: no grammar); the caller clears the default and destroys it in a `finally` (_drop_grammar)."""
+        if kw.get("prefix_allowed_tokens_fn") is not None:
+            raise ValueError("generate(): prefix_allowed_tokens_fn is a Python callback and cannot run inside the device's decode loop; pass grammar= "
+                             "(grounded_video_llm_amd.grammar: GrammarBuilder / grounding_grammar; Grammar.as_prefix_allowed_tokens_fn gives HF the same language)")
+        g = kw.get("grammar")
+        self.engine.set_grammar(None)
+        if g is None:
+            return None
+        if not isinstance(g, GR.Grammar):
+            raise ValueError(f"generate(): grammar must be a grounded_video_llm_amd.grammar.Grammar, not {type(g).__name__}")
+        if g.vocab != self.geo.vocab:
+            raise ValueError(f"generate(): the grammar classifies {g.vocab} ids, the model's vocabulary holds {self.geo.vocab}")
+        gid = self.engine.grammar_create(g)
+        if kw.get("num_beams", 1) in (1, None):
+            self.engine.set_grammar(gid)
+        return gid
+
+    def _drop_grammar(self, gid: Optional[int]):
+        self.engine.set_grammar(None)
+        if gid is not None:
+            self.engine.grammar_destroy(gid)
+
     def _select_logprobs(self, kw) -> "LPR.Options":
         """return_dict_in_generate / output_scores / top_logprobs (logprobs.py; raises its ValueErrors).  Sets the engine's default on EVERY generate
         call -- the call's setting, off for beam search (its scores come from beam.py) -- so nothing carries over from one call to the next."""
@@ -314,8 +341,12 @@ class LLAVA_NEXT_VIDEO:
         """The reference's generate(samples, **generate_kwargs).  Besides greedy / sampling / beam search it honours HF's repetition_penalty,
         no_repeat_ngram_size and min_new_tokens / min_length (logits.py; applied on the device to the generated ids only, as HF does for an
         inputs_embeds prompt), and the token rules sequence_bias, bad_words_ids, forced_eos_token_id, suppress_tokens and begin_suppress_tokens,
-        in HF's order (logits.py), with HF's validation errors; a rule set beyond the device capacities raises ValueError.  Still not supported
-        and ignored: bad_words_ids=None, prefix_allowed_tokens_fn, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
+        in HF's order (logits.py), with HF's validation errors; a rule set beyond the device capacities raises ValueError.
+        grammar (extra): a grammar.Grammar (GrammarBuilder, grounding_grammar) that keeps every answer inside its language -- HF's PrefixConstrainedLogitsProcessor
+        in HF's place (after the min-length ban, before forced eos), evaluated on the device at every step of greedy decoding, sampling and both beam_impls;
+        log-probabilities are then those of the masked distribution.  prefix_allowed_tokens_fn itself raises ValueError: a Python callback cannot run inside the
+        decode loop.  Still not supported
+        and ignored: bad_words_ids=None, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
         remove_invalid_values, exponential_decay_length_penalty, guidance_scale, diversity / constrained beams (num_beam_groups, constraints,
         force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
         typical_p / epsilon_cutoff / eta_cutoff (those seven run on the device in HF's order; top_h, custom logits_warper lists stay ignored).
@@ -337,12 +368,15 @@ class LLAVA_NEXT_VIDEO:
         self._select_tokens(generate_kwargs)
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
         rid = self._select_rules(generate_kwargs, max_new)
+        gid = None
         try:
-            return self._generate(samples, generate_kwargs, ids_arr, mask, opts, procs, max_new, rid)
+            gid = self._select_grammar(generate_kwargs)
+            return self._generate(samples, generate_kwargs, ids_arr, mask, opts, procs, max_new, rid, gid)
         finally:
+            self._drop_grammar(gid)
             self._drop_rules(rid)
 
-    def _generate(self, samples, generate_kwargs, ids_arr, mask, opts, procs, max_new: int, rid: Optional[int]):
+    def _generate(self, samples, generate_kwargs, ids_arr, mask, opts, procs, max_new: int, rid: Optional[int], gid: Optional[int] = None):
         feats = self.encode_images(samples)
         k = generate_kwargs.get("num_beams", 1) or 1
         lps, beam_scores = None, None
@@ -356,7 +390,7 @@ class LLAVA_NEXT_VIDEO:
             scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs))
+                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs), grammar=gid)
                        for b in range(ids_arr.shape[0])]
             if scored:
                 lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
@@ -372,14 +406,15 @@ class LLAVA_NEXT_VIDEO:
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
                           sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
-                          rules: Optional[int] = None, impl: str = "host"):
+                          rules: Optional[int] = None, impl: str = "host", grammar: Optional[int] = None):
         """generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
         teacher-forced batched decode step per token (gvl_decode_step_logits_batch: one stream of the weights for the k beams); log-softmax / top-2k of the step run on the device (torch), the bookkeeping on
         the host.  processors: HF's logits processors, applied by gvl_op_logits_process to every step's log-softmax rows before the beam scores
         are added (HF _beam_search / _beam_sample); the beams' own sequences select their tokens without them (their raw logits are what the
-        steps return).  rules: a rule-set id (Engine.rules_create) applied in the same pass, in HF's order.  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them.
+        steps return).  rules: a rule-set id (Engine.rules_create) applied in the same pass, in HF's order; grammar: a grammar id (Engine.grammar_create), likewise --
+        every beam's row is masked by the walk over that beam's own ids (impl = "device": the search sequence carries the grammar, gvl_beam_search reads it).  with_scores: (ids, sequences_score, transition_scores) as beam.beam_search returns them.
         impl = "device": the same search inside the library (Engine.beam_search = gvl_beam_search: bookkeeping in C++, every step's log-softmax and top-2k in the
         library's kernels, the processors / rules by the same launch); beam search only (sample must be None)."""
         from . import beam as B
@@ -393,7 +428,7 @@ class LLAVA_NEXT_VIDEO:
             emb = eng.splice(row, vis)
             seq = eng.seq_alloc(min(emb.shape[0], self.geo.max_seq))
             try:
-                LP.apply_seq_options(eng, seq, LP.SeqOptions.OFF)
+                LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
                 first = eng.prefill(seq, emb, want_logits=True)
                 return eng.beam_search(seq, first, num_beams, max_new, eos, length_penalty, early_stopping,
                                        processors if processors is not None and processors.active else None, rules, with_scores)
@@ -406,10 +441,12 @@ class LLAVA_NEXT_VIDEO:
         beams: List[Optional[int]] = [eng.seq_alloc(cap)]
         fresh: List[int] = []                            # clones of the step in progress: owned here until they are installed in `beams`
         process = None
-        if (processors is not None and processors.active) or rules is not None:
+        if (processors is not None and processors.active) or rules is not None or grammar is not None:
             pa = (processors if processors is not None else LP.OFF).args()
 
             def process(histories: List[List[int]], logprobs: torch.Tensor) -> torch.Tensor:
+                if grammar is not None:
+                    return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules, grammar=grammar)
                 if rules is None:
                     return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
                 return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules)
@@ -464,13 +501,16 @@ class LLAVA_NEXT_VIDEO:
         self._select_tokens(generate_kwargs)
         procs = [LP.resolve(generate_kwargs, getattr(self.tokenizer, "eos_token_id", None), LP.padded_embed_len(len(r), n_vis)) for r in rows]
         rid = self._select_rules(dict(generate_kwargs, num_beams=1), max_new)    # token rules: every sequence allocated below starts with them
+        gid = None
         try:
+            gid = self._select_grammar(dict(generate_kwargs, num_beams=1))       # ... and with the grammar
             feats = self.encode_images(samples)
             want = opts.top_n if opts.top_n >= 0 else None
             res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want)
             if res is None:                              # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
                 res = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs, logprobs=want)
         finally:
+            self._drop_grammar(gid)
             self._drop_rules(rid)
         out_ids, lps = res if want is not None else (res, None)
         texts = [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
@@ -583,6 +623,7 @@ class LLAVA_NEXT_VIDEO:
         eng.set_sampling(False)                                          # the members' first tokens (never read here) are picked by the defaults: all off
         eng.set_logits_processors(*LP.OFF.args())
         eng.set_token_rules(None)
+        eng.set_grammar(None)
         eng.set_logprobs(-1)
         vis = self.encode_images(samples)[0]
         parts, base = [], None

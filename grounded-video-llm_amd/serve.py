@@ -100,7 +100,8 @@ class ClipScheduler:
                min_new_tokens: Optional[int] = None, logprobs: Optional[int] = None, bad_words_ids=None, sequence_bias=None, suppress_tokens=None,
                begin_suppress_tokens=None, forced_eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
                top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
-               epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None) -> int:
+               epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None,
+               grammar: Optional[int] = None) -> int:
         """Queue one request.  embeds: the full spliced prompt.  prefix: an add_prefix() id -- the caller promises that the prompt's first P rows ARE the registered
         ones; only embeds[P:] (at least one row) is then prefilled.  An optimisation only: the result is the same without it.  (It is ignored for a request that
         LongRoPE forbids to share: P <= rope_orig_max_pos < len(embeds) -- a full prefill of that prompt ropes the shared rows with the long factors.)
@@ -115,7 +116,9 @@ class ClipScheduler:
         do_sample / temperature / top_k / top_p / min_p / typical_p / epsilon_cutoff / eta_cutoff / seed: THIS request's own token selection
         (logits.request_sampling: HF's validation and defaults; Engine.seq_set_sampling at admission, random stream 0 of `seed`): greedy next to
         sampled neighbours, or sampled with its own warpers.  Its ids are a function of its own settings and logits alone -- not of max_active,
-        chunk, or the other requests.  None for all nine: the request follows the engine's setting (Engine.set_sampling)."""
+        chunk, or the other requests.  None for all nine: the request follows the engine's setting (Engine.set_sampling).
+        grammar: an Engine.grammar_create id that constrains THIS request's answer (the caller owns the grammar and destroys it after the request
+        retired); None: the sequence keeps the engine's default (Engine.set_grammar)."""
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
@@ -141,7 +144,7 @@ class ClipScheduler:
                 prefix = None
             else:
                 p.queued += 1
-        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling), prefix=prefix)
+        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling, ... if grammar is None else int(grammar)), prefix=prefix)
         self._next += 1
         self.queue.append(r)
         return r.rid

@@ -172,7 +172,8 @@ int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const 
                             int top_n, float* lp_dev, int32_t* rank_dev, int32_t* top_ids_dev, float* top_lp_dev, int* n_scored,
                             float* last_logits /* [n_seqs][vocab] device, may be NULL */, void* stream);
 /* A copy of a sequence AT ITS CURRENT LENGTH (beam search: HF's cache reorder, transformers GenerationMixin._reorder_cache [ext]): whole pages
- * are shared by reference, the partial last page is copied on `stream` (one launch over all layers); the clone then appends to its own pages. */
+ * are shared by reference, the partial last page is copied on `stream` (one launch over all layers); the clone then appends to its own pages.
+ * Its list of generated ids starts empty -- unless the source has a grammar (gvl_seq_set_grammar): then the clone takes the source's generated ids along, see there. */
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream);
 int gvl_kv_info(const gvl_ctx* ctx, int* total_pages, int* free_pages, int64_t* pool_bytes, int* max_live_seqs);
 /* The group sizes ONE batched decode step takes (gvl_decode_step_logits_batch, and the parts gvl_decode_greedy_batch / gvl_decode_steps
@@ -271,6 +272,40 @@ int gvl_rules_create(gvl_ctx* ctx, const gvl_rules_desc* desc, int* rules_id);
 int gvl_rules_destroy(gvl_ctx* ctx, int rules_id);
 int gvl_set_token_rules(gvl_ctx* ctx, int rules_id);
 int gvl_seq_set_token_rules(gvl_ctx* ctx, int seq_id, int rules_id);
+/* Decoding grammars: HF's PrefixConstrainedLogitsProcessor (prefix_allowed_tokens_fn) as a device-resident object -- a DFA over token classes with
+ * one integer register, applied by the same launch as the processors and rules above, in HF's place: ... -> min length -> GRAMMAR -> forced eos ->
+ * suppress -> begin suppress.  No state is kept per sequence: every launch recomputes the mask from the grammar and the sequence's generated ids.
+ * Walk: start from state = start, reg = 0 and feed the generated ids in order.  The walk turns OFF for good on any of: an id outside [0, vocab), a
+ * forbidden transition, a GE transition with ordinal < reg, a history longer than 8192 ids.  A state whose whole row is forbidden is an END state.
+ * Mask: in an OFF or END state the logits row is left untouched, bit for bit (tokens after eos inside a multi-step chunk, which the caller discards).
+ * Otherwise, for every id t: allowed gives s[t] = s[t] + 0.0f, forbidden gives s[t] = -inf -- HF's `scores + mask`, which turns -0.0 into +0.0.  +inf
+ * and NaN logits are outside the contract.  On an edge with both flags GE reads the register before SET overwrites it.
+ * gvl_grammar_create checks (GVL_ERR_ARG with a message, nothing is clamped): the limits below; every token's class < n_classes; an ordinal class is
+ * exactly a contiguous id range; SET and GE only on ordinal classes; reserved bits clear; next states in range; every non-END state keeps a token
+ * allowed whatever reg holds (an edge without GE on a non-empty class, or a GE edge on a class at least as large as every class that has a SET edge).
+ * At most 64 live grammars.  The arrays are copied; gvl_grammar_create synchronises.  A grammar bound to sequences (gvl_set_grammar: the default of
+ * sequences allocated AFTER the call, -1 none; gvl_seq_set_grammar: one live sequence) must have vocab == cfg.vocab (GVL_ERR_ARG otherwise);
+ * gvl_op_logits_process_ex takes any grammar whose vocab equals its row width.  gvl_seq_fork / gvl_seq_clone copy the source's grammar, gvl_seq_free
+ * drops it.  Copies taken MID-ANSWER: the mask depends on the generated ids, so a copy must know the ones its tokens contain.
+ *   gvl_seq_clone of a source WITH a grammar also copies the source's generated ids, their count, the id to feed next and (where on) their log-probability lists:
+ *     the clone stands exactly where the source stands, gvl_decode_steps continues it at once, and gvl_seq_read returns the source's ids followed by the clone's
+ *     own -- the answer so far plus a continuation in the language.  (Without a grammar a clone's list starts empty and the caller feeds its next id, as before.)
+ *   gvl_seq_fork shares prompt pages: a fork at or before the source's first generated position holds none of its ids, starts its walk at (start, 0) behind its
+ *     own gvl_prefill_extend and gives a whole answer.  A fork whose n_tokens would reach past that position is GVL_ERR_STATE while the source has a grammar: the
+ *     rows appended behind a fork are embeddings whose ids the library is not told, so the walk could not go on (fork within the prompt, clone, or take the
+ *     grammar off the source first).
+ * gvl_grammar_destroy of a grammar that a live sequence or the default references is GVL_ERR_STATE, and it synchronises the device before
+ * the memory is released.  gvl_destroy frees every grammar.  gvl_beam_search applies the grammar that its seq_id carries to every beam. */
+typedef struct {
+  int32_t n_states, n_classes, start, vocab;   /* 1..256, 1..64, n_states*n_classes <= 4096, vocab 1 .. 2^23 */
+  const uint8_t*  token_class;  /* [vocab]: the class of every id */
+  const int32_t*  class_base;   /* [n_classes]: -1 plain; >= 0: ORDINAL class = exactly the ids base .. base+size-1, ordinal(t) = t - base */
+  const uint16_t* trans;        /* [n_states][n_classes]: 0xFFFF forbidden; else bits 0-7 next state, bit 8 SET (reg = ordinal), bit 9 GE (allowed iff ordinal >= reg) */
+} gvl_grammar_desc;
+int gvl_grammar_create(gvl_ctx* ctx, const gvl_grammar_desc* desc, int* grammar_id);
+int gvl_grammar_destroy(gvl_ctx* ctx, int grammar_id);
+int gvl_set_grammar(gvl_ctx* ctx, int grammar_id);
+int gvl_seq_set_grammar(gvl_ctx* ctx, int seq_id, int grammar_id);
 /* Log-probabilities of the selected tokens, computed on the device by the token-selection kernel itself (prefill's first token,
  * gvl_decode_greedy*, gvl_decode_steps; greedy and sampling alike; graph-replayed steps included).  The distribution is the one the token
  * was selected from: greedy, log_softmax of the row after the logits processors, (s_tok - m) - log(sum_i exp(s_i - m)); sampling, the
@@ -331,7 +366,8 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
  *     t  = lp + beam_score                         ONE fp32 add; the beam scores start as [0, -1e9, ...] (the first step expands the prompt's row only)
  *     order: t descending, then flat index beam * vocab + token ascending -- a strict total order over ALL entries, -inf included (torch.topk leaves ties unspecified)
  * With processors (penalty / ngram / min_new / proc_eos_id: gvl_set_logits_processors' meaning, history = the beam's generated ids) or a rule set (gvl_rules_create), HF's
- * order holds: log-softmax -> sequence_bias -> processors -> ... -> + beam score -> top 2k.  The candidates land in host-mapped memory; after one stream synchronise per
+ * order holds: log-softmax -> sequence_bias -> processors -> ... -> + beam score -> top 2k.  A grammar that seq_id carries (gvl_seq_set_grammar) is applied to every
+ * beam's row in the same launch, on the beam's own generated ids.  The candidates land in host-mapped memory; after one stream synchronise per
  * step the host bookkeeping (csrc/gvl_beam.h, all score arithmetic in double: sum / pow((double)generated_len, length_penalty)) consumes them: an eos candidate of rank < k
  * closes a hypothesis (generated_len counts the eos), of rank >= k is skipped; done = k hypotheses and (early_stopping 1, or the worst of them >= max candidate /
  * cur_len ** length_penalty); at max_new_tokens the open beams become hypotheses; among equal best scores the last added wins.  Output: the NEW ids of the best hypothesis
@@ -548,6 +584,10 @@ int gvl_op_logits_process(gvl_ctx* ctx, float* logits, int n, int batch, const i
 /* gvl_op_logits_process plus one rule-set id per row (host array; -1 = no rules): the whole ordered pipeline on raw rows. */
 int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
                                 const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream);
+/* ... plus one grammar id per row (host arrays; rules_ids / grammar_ids may be null, -1 = none): a grammar's vocab must equal n. */
+int gvl_op_logits_process_ex(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, const int* grammar_ids,
+                             void* stream);
 /* Token selection with log-probabilities on its own (operator tests): greedy (do_sample = 0; streams / steps_dev may be null) or
  * gvl_op_sample's draw; row b with top_n[b] >= 0 (host array) stores its token's log-probability at lp_dev[b], and for top_n[b] >= 1
  * its top list at top_ids_dev / top_lp_dev [b * 8 ..) (gvl_set_logprobs' meaning).  batch <= 16. */

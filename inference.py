@@ -61,10 +61,23 @@ def parse_args(argv=None):
     p.add_argument("--no_repeat_ngram_size", type=int, default=None, help="HF NoRepeatNGramLogitsProcessor on the generated ids (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=None, help="HF MinNewTokensLengthLogitsProcessor: no eos before this many new ids")
     p.add_argument("--output_scores", action="store_true", help="print each answer's mean token log-prob and, for the grounding answer, every temporal token's probability")
+    p.add_argument("--constrain_grounding", action="store_true", help="keep the grounding answer inside 'From <s> to <e>.' with s <= e (generate(grammar=...); not with --share_visual, whose one call answers all three prompts)")
     p.add_argument("--share_visual", type=_bool, default=False, help="encode the video ONCE for the three prompts and batch them (the reference re-encodes per prompt)")
     p.add_argument("--synthetic", action="store_true", help="seeded random weights / frames / tokenizer (offline image)")
     p.add_argument("--synthetic_scale", type=str, default="small", choices=["small", "full"])
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.constrain_grounding and args.share_visual:
+        p.error("--constrain_grounding constrains the grounding answer only: it cannot be combined with --share_visual")
+    return args
+
+
+def grounding_constraint(args, model) -> dict:
+    """The generate() kwargs of the grounding call: --constrain_grounding adds the "interval" grammar over the MODEL's vocabulary (its embedding rows, which
+    may outnumber the tokenizer's entries: Phi-3.5 has 32 064 + 302 rows for about 32 011 + 302 tokens)."""
+    if not args.constrain_grounding:
+        return {}
+    from grounded_video_llm_amd.grammar import grounding_grammar
+    return {"grammar": grounding_grammar(model.tokenizer, args.num_temporal_tokens, model.tokenizer.eos_token_id, "interval", vocab=model.geo.vocab)}
 
 
 def read_frames(video_path: str, num_frames: int):
@@ -140,6 +153,7 @@ def main(argv=None):
         kw.update(return_dict_in_generate=True, output_scores=True)
     outs, scored = {}, {}
     modes = ("grounding", "qa", "referring")
+    grounding_kw = grounding_constraint(args, model)
     if args.share_visual:
         # one pre-processing + one vision encode for the three prompts (the reference re-encodes the video per prompt)
         per_mode = [create_inputs(args, mode, frames, duration, model.engine) for mode in modes[:1]]
@@ -154,7 +168,7 @@ def main(argv=None):
             samples = create_inputs(args, mode, frames, duration, model.engine)
             # one sampler seed per call (HF's generator state advances between the reference's three generate() calls; the same seed
             # for all three would make their draws perfectly correlated)
-            res = model.generate(samples, **{**kw, "seed": args.seed + i})
+            res = model.generate(samples, **{**kw, "seed": args.seed + i, **(grounding_kw if mode == "grounding" else {})})
             outs[mode] = (samples["prompts"][0], (res.texts if args.output_scores else res)[0])
             if args.output_scores:
                 scored[mode] = (res.sequences[0], res.transition_scores[0])
