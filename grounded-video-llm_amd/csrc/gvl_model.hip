@@ -5,6 +5,7 @@
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
 #include "gvl_prefill_plan.h"   // prefill_group_size: how the *_varlen entry points cut their sequences into llm_prefill groups
+#include "gvl_attn_plan.h"      // decode_attn_plan: gvl_op_decode_attention refuses what the plan refuses, before anything is launched
 
 std::string& gvl_create_error() { static std::string e; return e; }
 
@@ -1144,6 +1145,49 @@ int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float
   gvl_decode_proj p; memset(&p, 0, sizeof(p));
   p.W = W; p.x = x; p.bias = bias; p.out_f32 = y; p.N = N; p.K = K; p.batch = batch;
   return decode_proj_run(ctx, &p, (hipStream_t)stream, "gvl_op_dgemm");
+}
+// operator-level entry for the WHOLE DecodeAttnArgs surface (tests/test_gpu_decode_attn_exact.py): the caller supplies every device tensor, the workspace (part, counters)
+// included, so a test can poison it before a launch and look at it afterwards.  The kernels trust positions and page numbers: they are read back and checked here, on
+// the host, and every refusal comes back as GVL_ERR_ARG before anything is launched or written.  Otherwise DecodeAttnArgs is filled as decode_step fills it.
+int gvl_op_decode_attention(gvl_ctx* ctx, const gvl_decode_attn* p, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: null descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = p->batch;
+  const char* bad = nullptr;
+  DecodeAttnLaunch l;
+  if (!p->q || !p->Kt || !p->Vt || !p->tables || !p->pos || !p->part || !p->counters || !p->out) bad = "q, Kt, Vt, tables, pos, part, counters, out set";
+  else if (B < 1 || B > GVL_MAX_DECODE_BATCH) bad = "1 <= batch <= 16";
+  else if (decode_attn_plan(DecodeAttnGeometry{p->H, p->KV, p->D, p->nsplit, B, p->hpb, p->cpb, p->gsplit}, GVL_DECODE_ATTN_KNOBS_DEFAULT, &l) < 0)
+    bad = "the launch plan does not serve this geometry (H % KV == 0, D 64 / 96 / 128, 1 <= nsplit <= 16)";
+  else if (p->Dout < 1 || p->Dout > p->D) bad = "1 <= Dout <= D";
+  else if (p->q_stride < p->H * p->D || (p->q_stride & 7) || ((uintptr_t)p->q & 15)) bad = "q_stride >= H D, q rows 16-byte aligned";
+  else if (!p->out_tiled && p->out_stride < p->H * p->Dout) bad = "out_stride >= H Dout";
+  else if (p->n_pages < 1 || p->table_stride < 1) bad = "n_pages, table_stride >= 1";
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_decode_attention: ") + bad);
+  std::vector<int> pos(B), tab((size_t)B * p->table_stride);
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpy(pos.data(), p->pos, sizeof(int) * B, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(tab.data(), p->tables, sizeof(int) * tab.size(), hipMemcpyDeviceToHost));
+  int longest = 1;                                   // split count of the longest sequence: one per 4 pages of its own length, at most nsplit
+  for (int b = 0; b < B; ++b) {
+    if (pos[b] < 0 || (long long)pos[b] >= (long long)p->table_stride * 64) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: position outside the tables");
+    const int np = (pos[b] + 1 + 63) >> 6, n4 = (np + 3) >> 2, ns = n4 > p->nsplit ? p->nsplit : n4;
+    for (int i = 0; i < np; ++i) {
+      const int page = tab[(size_t)b * p->table_stride + i];
+      if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: page outside the pools");
+    }
+    longest = ns > longest ? ns : longest;
+  }
+  if ((long long)l.gsplit * l.cpb < longest) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: gsplit * cpb is smaller than the longest sequence's split count (the ticket would never complete)");
+  DecodeAttnArgs a; memset(&a, 0, sizeof(a));
+  a.q = p->q; a.q_stride = p->q_stride; a.Kt = p->Kt; a.Vt = p->Vt;
+  for (int b = 0; b < B; ++b) { a.tables[b] = p->tables + (size_t)b * p->table_stride; a.pos_ptrs[b] = p->pos + b; }
+  a.part = p->part; a.counters = p->counters; a.batch = B; a.gsplit = p->gsplit; a.cpb = p->cpb; a.hpb = p->hpb;
+  a.out = p->out; a.out_stride = p->out_stride; a.out_tiled = p->out_tiled ? 1 : 0; a.H = p->H; a.KV = p->KV; a.D = p->D; a.Dout = p->Dout; a.nsplit = p->nsplit; a.scale = p->scale;
+  RUN(GVL_PROF_DECODE_ATTN, 0, gvl_launch_decode_attention(a, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return 0;
 }
 // micro-benchmark of the decode projection kernels on synthetic operands (tools/decode_bench.py): mode 0 = skinny MFMA GEMM (variant:
 // see gvl_launch_dgemm), 1 = round-1 VALU GEMV (batch 1, 2, 4), 2 / 3 = the same two with the fused RMSNorm prologue (batch <= 4).  `rounds` distinct weight matrices are cycled so that the

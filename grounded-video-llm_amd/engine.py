@@ -904,6 +904,26 @@ class Engine:
                 setattr(d, k, v)
         self._chk(self.lib.gvl_op_decode_proj(self.ctx, C.byref(d), self.stream), "gvl_op_decode_proj")
 
+    def op_decode_attention(self, **kw):
+        """gvl_op_decode_attention (include/gvl.h): one decode-attention launch.  Every field of gvl_decode_attn by keyword -- device tensors for the
+        pointer fields (out, part and counters are written in place: the caller allocates and pre-fills them), ints / floats for the rest.  Raises
+        GvlError (status ERR_ARG) on a refusal."""
+        d = L.GvlDecodeAttn()
+        names = {n: t for n, t in L.GvlDecodeAttn._fields_}
+        keep = []
+        for k, v in kw.items():
+            if k not in names:
+                raise TypeError(f"op_decode_attention: unknown field {k}")
+            if v is None:
+                continue
+            if names[k] is C.c_void_p:
+                assert v.is_contiguous() and v.device.type == "cuda", k
+                keep.append(v)
+                setattr(d, k, v.data_ptr())
+            else:
+                setattr(d, k, v)
+        self._chk(self.lib.gvl_op_decode_attention(self.ctx, C.byref(d), self.stream), "gvl_op_decode_attention")
+
     def op_gemv(self, W, x, bias=None):
         N, K = W.shape
         y = torch.empty((N,), dtype=torch.float32, device=self.device)

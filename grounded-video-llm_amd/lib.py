@@ -75,6 +75,14 @@ class GvlDecodeProj(C.Structure):
                 ("w_deq", C.c_void_p), ("w_scale", C.c_void_p)]
 
 
+class GvlDecodeAttn(C.Structure):
+    """gvl_decode_attn (include/gvl.h): one decode-attention launch on caller-owned tensors, for the operator tests."""
+    _fields_ = [("q", C.c_void_p), ("Kt", C.c_void_p), ("Vt", C.c_void_p), ("tables", C.c_void_p), ("pos", C.c_void_p), ("part", C.c_void_p),
+                ("counters", C.c_void_p), ("out", C.c_void_p), ("q_stride", C.c_int32), ("n_pages", C.c_int32), ("table_stride", C.c_int32),
+                ("out_stride", C.c_int32), ("out_tiled", C.c_int32), ("batch", C.c_int32), ("H", C.c_int32), ("KV", C.c_int32), ("D", C.c_int32),
+                ("Dout", C.c_int32), ("nsplit", C.c_int32), ("hpb", C.c_int32), ("cpb", C.c_int32), ("gsplit", C.c_int32), ("scale", C.c_float)]
+
+
 class GvlPatchEmbed(C.Structure):
     """gvl_patch_embed (include/gvl.h): the patch embedding of either vision tower by either path, for the operator tests."""
     _fields_ = [("mode", C.c_int32), ("path", C.c_int32), ("n", C.c_int32), ("T", C.c_int32), ("image", C.c_int32), ("patch", C.c_int32), ("C", C.c_int32),
@@ -176,6 +184,7 @@ _SIGS = {
     "gvl_op_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvl_op_dgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gvl_op_decode_proj": (C.c_int, [C.c_void_p, C.POINTER(GvlDecodeProj), C.c_void_p]),
+    "gvl_op_decode_attention": (C.c_int, [C.c_void_p, C.POINTER(GvlDecodeAttn), C.c_void_p]),
     "gvl_op_decode_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "gvl_probe_mfma": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "gvl_trace_marker": (C.c_int, [C.c_int, C.c_void_p]),

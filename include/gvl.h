@@ -666,6 +666,37 @@ typedef struct {
   void* w_scale;
 } gvl_decode_proj;
 int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream);
+/* One decode-attention launch: one new query per head against a paged cache (operator tests: tests/test_gpu_decode_attn_exact.py).  All pointers are
+ * device memory and the caller owns every buffer, the split workspace included.
+ *   q        bf16 [batch][H][D], q_stride elements between two sequences (>= H D, a multiple of 8; q 16-byte aligned); columns Dout .. D - 1 of a head are 0
+ *   Kt, Vt   the pools of ONE layer: bf16 [n_pages][KV][64][D] (key rows) and [n_pages][KV][D][64] (V transposed); token t of a sequence is slot t % 64 of
+ *            page tables[b][t / 64]
+ *   tables   int32 [batch][table_stride] page numbers;  pos int32 [batch]: the index of each sequence's newest token (its cache holds pos + 1 tokens)
+ *   part     f32 [batch][H][nsplit][D + 2] partial records (D accumulators, running maximum in log2 units, sum), any contents before the launch
+ *   counters int32 [batch][H] tickets: ZERO before the launch, zero again after it
+ *   out      bf16 [batch][H Dout], out_stride elements between two sequences (>= H Dout), or -- out_tiled -- the decode activation tile order: element
+ *            (b, k) at ((k >> 5) * 64 + ((k >> 3) & 3) * 16 + b) * 8 + (k & 7)
+ *   D        64, 96 or 128 (the padded head dim), Dout <= D the real one;  H % KV == 0;  1 <= nsplit <= 16;  scale: the softmax scale
+ *   A sequence of n = ceil((pos + 1) / 64) pages uses ns = min(nsplit, ceil(n / 4)) context splits of ceil(n / ns) pages and one record per split.
+ *   cpb      consecutive splits per block (0 = 1), gsplit  block slots along the context (0 = ceil(nsplit / cpb)), hpb  query heads of a group per block
+ *            on the grouped-query kernel (0 or no divisor of H / KV = all): launch shape only, no value may change an output bit.
+ * The call reads pos and tables back and returns GVL_ERR_ARG with a message, before anything is launched or written, when the launch plan does not serve
+ * the geometry, a position is outside [0, 64 table_stride), one of a sequence's first ceil((pos + 1) / 64) pages is outside [0, n_pages), gsplit * cpb is
+ * smaller than the longest sequence's split count (blocks would be missing and the ticket would never complete), Dout > D or a stride is shorter than its
+ * row.  Synchronises the stream. */
+typedef struct {
+  const uint16_t* q;
+  const uint16_t* Kt; const uint16_t* Vt;
+  const int32_t* tables;
+  const int32_t* pos;
+  float* part;
+  int32_t* counters;
+  uint16_t* out;
+  int32_t q_stride, n_pages, table_stride, out_stride, out_tiled;
+  int32_t batch, H, KV, D, Dout, nsplit, hpb, cpb, gsplit;
+  float scale;
+} gvl_decode_attn;
+int gvl_op_decode_attention(gvl_ctx* ctx, const gvl_decode_attn* p, void* stream);
 /* measurement only (tools/decode_bench.py): average microseconds per launch of one decode projection [N,K] x `batch` sequences on
  * synthetic operands; mode 0 = skinny MFMA GEMM (variant 0 = default), 1 = VALU GEMV; `rounds` distinct weight copies are cycled. */
 int gvl_op_decode_bench(gvl_ctx* ctx, int N, int K, int batch, int mode, int variant, int rounds, int iters, double* us_per_launch,

@@ -718,7 +718,8 @@ def test_decode_attention_result_is_independent_of_the_launch_shape(kind):
     head) -- how many of the group's heads share a block (hpb: the host takes the whole group for large launches, fewer heads per
     block for a single sequence; gvl_debug_set("decode_attn_hpb") overrides) are free choices of the host.  The ids and logits must not depend on
     them: contexts of 9 and 17 splits (one past a page boundary, one crossing 4096 tokens where the split count is clamped to 16),
-    forced cpb = 1, 2, 3, 4, 16 (and hpb = 1, 2, 4 for the GQA model: 8 query heads on 2 KV heads) against the default choice."""
+    forced cpb = 1, 2, 3, 4, 16 (and hpb = 1, 2, 4 for the GQA model: 8 query heads on 2 KV heads) against the default choice.
+    Per-key correctness of the kernels themselves (mask, split rule, records, merge): tests/test_gpu_decode_attn_exact.py."""
     import os
     if kind == "mha":
         c = dict(hidden=256, inter=512, layers=2, heads=4, kv_heads=4, vocab=320)
@@ -818,7 +819,8 @@ def test_grouped_query_decode_attention_other_group_sizes(heads, kv_heads, head_
     """The grouped-query decode kernel beyond Llama-3's 4-heads-per-KV-head case: groups of 8 (the 16-row variant of the kernel: MFMA
     rows 4..15 live in the upper lane groups), group of 3 (odd: heads-per-block stays the whole group), head dims 64 (padded from 16 /
     32) and 128 -- a context of 300 tokens (two splits, partial last page) decoded for 6 teacher-forced steps against the oracle, and
-    the same sequences decoded as one group against one at a time (bit-identical)."""
+    the same sequences decoded as one group against one at a time (bit-identical).
+    Per-key correctness of the kernels themselves (mask, split rule, records, merge): tests/test_gpu_decode_attn_exact.py."""
     hidden = heads * head_dim
     c = dict(hidden=hidden, inter=2 * hidden, layers=2, heads=heads, kv_heads=kv_heads, vocab=200)
     geo = tiny_geo(llm="llama3", hidden=c["hidden"], inter=c["inter"], layers=c["layers"], heads=heads, kv_heads=kv_heads, vocab=c["vocab"],
