@@ -1189,6 +1189,150 @@ int gvl_op_decode_attention(gvl_ctx* ctx, const gvl_decode_attn* p, void* stream
   HIPCHK(ctx, hipStreamSynchronize(st));
   return 0;
 }
+// operator-level entry for the WHOLE QkvPostArgs surface and both launchers (tests/test_gpu_qkv_post.py).  The kernels trust page numbers, positions and the ragged
+// row offsets: the tables are read back and everything is checked here, on the host; every refusal comes back as GVL_ERR_ARG before anything is launched or written.
+int gvl_op_qkv_post(gvl_ctx* ctx, const gvl_qkv_post* p, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: null descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const int n = p->vl_n;
+  const char* bad = nullptr;
+  if (!p->qkv || !p->Kt || (!p->Q && !p->q_rs)) bad = "qkv, Kt and Q (or q_rs) set";
+  else if (p->mode < 0 || p->mode > 2) bad = "mode 0, 1 or 2";
+  else if (p->H < 1 || p->KV < 1 || p->B < 1 || p->n_pages < 1) bad = "H, KV, B, n_pages >= 1";
+  else if ((p->Dr & 7) || (p->mode == 2 && (p->Dr & 15)) || (p->D & 7) || p->D < p->Dr || p->Dr < 8 || p->Dr > 128) bad = "Dr % 8 == 0 (mode 2: % 16), 8 <= Dr <= 128, D % 8 == 0, D >= Dr";
+  else if ((p->ld & 7) || (long long)p->ld < (long long)(p->H + 2 * p->KV) * p->Dr) bad = "ld % 8 == 0, ld >= (H + 2 KV) Dr";
+  else if (p->mode == 1 && (!p->qn || !p->kn)) bad = "mode 1 needs qn and kn";
+  else if (p->mode == 2 && (!p->cos || !p->sin || p->max_pos < 1)) bad = "mode 2 needs cos, sin and max_pos";
+  else if (p->q_rs && p->mode != 1) bad = "q_rs is a mode 1 form";
+  else if (p->q_rs && !p->k_ones) bad = "q_rs needs k_ones";
+  else if ((p->ones_row || p->k_ones) && p->D == p->Dr) bad = "ones_row / k_ones need D > Dr";
+  else if (n < 0 || n > GVL_MAX_PREFILL_BATCH) bad = "0 <= vl_n <= 8";
+  else if (p->ext && (n < 1 || p->q_rs || !p->Vt)) bad = "ext needs a ragged group, Vt and no q_rs";
+  else if (n && (p->mode != 2 || p->B != 1 || p->pos0 != 0 || p->block_table)) bad = "a ragged group needs mode 2, B == 1, pos0 == 0 and no block_table";
+  else if (!n && (p->S < 1 || p->pos0 < 0)) bad = "S >= 1, pos0 >= 0";
+  else if (!n && p->Vt && (p->pos0 & 63)) bad = "Vt needs pos0 % 64 == 0 (V^T pages are written whole)";
+  else if (!n && !p->block_table && p->pos0) bad = "pos0 > 0 needs a block table";
+  else if (!n && p->block_table && p->max_pages < 1) bad = "max_pages >= 1";
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_qkv_post: ") + bad);
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  // per sequence: first position, rows and the table as the launch will index it (null: implicit pages)
+  struct Member { long long pos0, rows, page0; std::vector<int> tab; bool has_tab; };
+  std::vector<Member> ms;
+  if (n) {
+    if (p->vl_rows[0] != 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: vl_rows[0] must be 0");
+    for (int u = 0; u < n; ++u) {
+      const long long rows = (long long)p->vl_rows[u + 1] - p->vl_rows[u];
+      if (rows < 1) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: an empty ragged member");
+      if (!p->vl_tables[u] || p->table_len[u] < 1) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: every ragged member needs a block table");
+      const int pos0 = p->ext ? p->vl_pos0[u] : 0;
+      if (pos0 < 0 || (pos0 & 63)) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: vl_pos0 must be a multiple of 64");
+      Member m{pos0, rows, 0, std::vector<int>((size_t)p->table_len[u]), true};
+      HIPCHK(ctx, hipMemcpy(m.tab.data(), p->vl_tables[u], sizeof(int) * m.tab.size(), hipMemcpyDeviceToHost));
+      ms.push_back(std::move(m));
+    }
+  } else {
+    std::vector<int> all;
+    if (p->block_table) { all.resize((size_t)p->B * p->max_pages); HIPCHK(ctx, hipMemcpy(all.data(), p->block_table, sizeof(int) * all.size(), hipMemcpyDeviceToHost)); }
+    const long long nt = ((long long)p->S + 63) >> 6;
+    for (int b = 0; b < p->B; ++b) {
+      Member m{p->pos0, p->S, b * nt, {}, p->block_table != nullptr};
+      if (p->block_table) m.tab.assign(all.begin() + (size_t)b * p->max_pages, all.begin() + (size_t)(b + 1) * p->max_pages);
+      ms.push_back(std::move(m));
+    }
+  }
+  std::vector<char> used((size_t)p->n_pages, 0);
+  for (const Member& m : ms) {
+    const long long end = m.pos0 + m.rows;                                   // one past the last position written
+    if (p->mode == 2 && end > p->max_pos) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: a position outside the cos / sin tables");
+    const long long t0 = m.pos0 >> 6, t1 = (end + 63) >> 6;
+    if (m.has_tab && t1 > (long long)m.tab.size()) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: a block table shorter than ceil((pos0 + S) / 64)");
+    for (long long t = t0; t < t1; ++t) {
+      const long long page = m.has_tab ? m.tab[(size_t)t] : m.page0 + t;
+      if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: page outside the pools");
+      if (used[(size_t)page]) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: a page named twice among the pages the launch writes");
+      used[(size_t)page] = 1;
+    }
+  }
+  QkvPostArgs a; memset(&a, 0, sizeof(a));
+  a.qkv = p->qkv; a.ld = p->ld; a.Q = p->Q; a.Kt = p->Kt; a.Vt = p->Vt; a.block_table = p->block_table; a.max_pages = p->max_pages;
+  a.B = p->B; a.S = p->S; a.H = p->H; a.KV = p->KV; a.Dr = p->Dr; a.D = p->D; a.mode = p->mode; a.qn = p->qn; a.kn = p->kn; a.eps = p->eps;
+  a.cos = p->cos; a.sin = p->sin; a.pos0 = p->pos0; a.ones_row = p->ones_row ? 1 : 0; a.k_ones = p->k_ones ? 1 : 0; a.q_rs = p->q_rs; a.vl_n = n;
+  for (int u = 0; u <= n; ++u) a.vl_rows[u] = p->vl_rows[u];
+  for (int u = 0; u < n; ++u) { a.vl_tables[u] = p->vl_tables[u]; a.vl_pos0[u] = p->vl_pos0[u]; }
+  if (p->ext) RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post_ext(a, st));
+  else RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(a, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+// operator-level entry for the paged forms of attn_fwd_kernel behind a cached prefix (tests/test_gpu_prefill_attn.py): a caller-supplied block table with qpos0 / Sk, the
+// ragged grid and the ragged-extend grid, on caller-owned pages.  The plans are asked first (a refusal names them), then the tables are read back and every page the
+// launch will read is checked: GVL_ERR_ARG before anything is launched or written.
+int gvl_op_prefill_attention(gvl_ctx* ctx, const gvl_prefill_attn* p, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_prefill_attention: null descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const int n = p->vl_n;
+  const bool O16 = ((uintptr_t)p->O & 15) == 0;
+  const char* bad = nullptr;
+  if (!p->Q || !p->Kt || !p->Vt || !p->O) bad = "Q, Kt, Vt, O set";
+  else if (p->n_pages < 1) bad = "n_pages >= 1";
+  else if (n < 0 || n > GVL_MAX_PREFILL_BATCH) bad = "0 <= vl_n <= 8";
+  else if (p->ext && n < 1) bad = "ext needs a ragged group";
+  else if (!n && (!p->block_table || p->max_pages < 1)) bad = "the single form needs a block table (implicit pages: gvl_op_attention)";
+  else if (p->ring != 0 && p->ring != 2 && p->ring != 3) bad = "ring 0, 2 or 3";
+  else if (p->ext) {
+    AttnExtGeometry g{};
+    g.H = p->H; g.KV = p->KV; g.D = p->D; g.Dout = p->Dout; g.causal = p->causal; g.vl_n = n; g.O16 = O16;
+    for (int u = 0; u <= n; ++u) g.vl_rows[u] = p->vl_rows[u];
+    for (int u = 0; u < n; ++u) { g.vl_tables[u] = p->vl_tables[u] != nullptr; g.vl_pos0[u] = p->vl_pos0[u]; }
+    AttnExtLaunch l;
+    if (p->B != 1 || p->Sk || p->qpos0 || p->block_table || attn_ext_plan(g, GVL_ATTN_KNOBS_DEFAULT, &l) < 0)
+      bad = "attn_ext_plan does not serve this launch (causal, B == 1, Sk == qpos0 == 0, no block_table, vl_rows[0] == 0, per member a table, >= 1 query, vl_pos0 % 64 == 0)";
+  } else {
+    AttnGeometry g{};
+    g.B = p->B; g.H = p->H; g.KV = p->KV; g.S = p->S; g.D = p->D; g.Dout = p->Dout; g.Sk = p->Sk; g.qpos0 = p->qpos0; g.causal = p->causal; g.ring = p->ring;
+    g.max_pages = p->max_pages; g.vl_n = n; g.block_table = p->block_table != nullptr; g.O16 = O16;
+    for (int u = 0; u <= n; ++u) g.vl_rows[u] = p->vl_rows[u];
+    for (int u = 0; u < n; ++u) g.vl_tables[u] = p->vl_tables[u] != nullptr;
+    AttnLaunch l[GVL_ATTN_MAX_LAUNCHES];
+    if (attn_plan(g, GVL_ATTN_KNOBS_DEFAULT, l) < 0 || (n && p->vl_rows[0] != 0))
+      bad = "attn_plan does not serve this launch (D 64 / 96 / 128, Dout % 8 == 0, H % KV == 0, Sk == 0 or Sk >= qpos0 + S; ragged: causal, B == 1, Sk == qpos0 == 0, no block_table, per member a table and 1 .. S queries)";
+  }
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_prefill_attention: ") + bad);
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  auto check = [&](const std::vector<int>& tab, long long qpos0, long long S, long long Sk) -> const char* {   // one sequence: the key tiles its blocks read
+    const long long tiles = p->causal ? ((qpos0 + S - 1) >> 6) + 1 : (Sk + 63) >> 6;
+    if (tiles > (long long)tab.size()) return "a block table shorter than the key tiles the launch reads";
+    for (long long t = 0; t < tiles; ++t) if (tab[(size_t)t] < 0 || tab[(size_t)t] >= p->n_pages) return "page outside the pools";
+    return nullptr;
+  };
+  if (n) {
+    for (int u = 0; u < n && !bad; ++u) {
+      if (p->table_len[u] < 1) { bad = "table_len >= 1"; break; }
+      std::vector<int> tab((size_t)p->table_len[u]);
+      HIPCHK(ctx, hipMemcpy(tab.data(), p->vl_tables[u], sizeof(int) * tab.size(), hipMemcpyDeviceToHost));
+      const long long S = (long long)p->vl_rows[u + 1] - p->vl_rows[u], q0 = p->ext ? p->vl_pos0[u] : 0;
+      bad = check(tab, q0, S, q0 + S);
+    }
+  } else {
+    std::vector<int> all((size_t)p->B * p->max_pages);
+    HIPCHK(ctx, hipMemcpy(all.data(), p->block_table, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < p->B && !bad; ++b)
+      bad = check(std::vector<int>(all.begin() + (size_t)b * p->max_pages, all.begin() + (size_t)(b + 1) * p->max_pages), p->qpos0, p->S, p->Sk > 0 ? p->Sk : p->S);
+  }
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_prefill_attention: ") + bad);
+  AttnArgs a; memset(&a, 0, sizeof(a));
+  a.Q = p->Q; a.Kt = p->Kt; a.Vt = p->Vt; a.O = p->O; a.block_table = p->block_table; a.max_pages = p->max_pages;
+  a.B = p->B; a.H = p->H; a.KV = p->KV; a.S = p->S; a.D = p->D; a.Dout = p->Dout; a.Sk = p->Sk; a.qpos0 = p->qpos0; a.scale = p->scale; a.causal = p->causal ? 1 : 0; a.ring = p->ring;
+  a.vl_n = n;
+  for (int u = 0; u <= n; ++u) a.vl_rows[u] = p->vl_rows[u];
+  for (int u = 0; u < n; ++u) { a.vl_tables[u] = p->vl_tables[u]; a.vl_pos0[u] = p->ext ? p->vl_pos0[u] : 0; }
+  if (p->ext) RUN(GVL_PROF_ATTN, 0, gvl_launch_attention_ext(a, st));
+  else RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return 0;
+}
 // micro-benchmark of the decode projection kernels on synthetic operands (tools/decode_bench.py): mode 0 = skinny MFMA GEMM (variant:
 // see gvl_launch_dgemm), 1 = round-1 VALU GEMV (batch 1, 2, 4), 2 / 3 = the same two with the fused RMSNorm prologue (batch <= 4).  `rounds` distinct weight matrices are cycled so that the
 // Infinity Cache cannot hold the stream; returns the average microseconds per launch.

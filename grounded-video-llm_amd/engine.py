@@ -924,6 +924,46 @@ class Engine:
                 setattr(d, k, v)
         self._chk(self.lib.gvl_op_decode_attention(self.ctx, C.byref(d), self.stream), "gvl_op_decode_attention")
 
+    def _op_paged(self, struct, fn, what, kw):
+        """fill a descriptor that carries a ragged group (vl_rows / vl_tables / vl_pos0 / table_len arrays) from keywords and call fn"""
+        d = struct()
+        names = {n: t for n, t in struct._fields_}
+        keep = []
+        if kw.get("vl_tables") is not None and "table_len" not in kw:
+            kw = dict(kw, table_len=[int(t.numel()) for t in kw["vl_tables"]])
+        for k, v in kw.items():
+            if k not in names:
+                raise TypeError(f"{what}: unknown field {k}")
+            if v is None:
+                continue
+            if k == "vl_tables":
+                for u, t in enumerate(v):
+                    if t is not None:
+                        assert t.is_contiguous() and t.device.type == "cuda" and t.dtype == torch.int32, k
+                        keep.append(t)
+                        d.vl_tables[u] = t.data_ptr()
+            elif k in ("vl_rows", "vl_pos0", "table_len"):
+                for u, x in enumerate(v):
+                    getattr(d, k)[u] = int(x)
+            elif names[k] is C.c_void_p:
+                assert v.is_contiguous() and v.device.type == "cuda", k
+                keep.append(v)
+                setattr(d, k, v.data_ptr())
+            else:
+                setattr(d, k, v)
+        self._chk(fn(self.ctx, C.byref(d), self.stream), what)
+
+    def op_qkv_post(self, **kw):
+        """gvl_op_qkv_post (include/gvl.h): one launch of the qkv_post pass.  Every field of gvl_qkv_post by keyword -- device tensors for the pointer fields (Q, Kt,
+        Vt and q_rs are written in place: the caller allocates and pre-fills them), ints / floats for the rest; vl_rows, vl_pos0 and table_len take lists of ints,
+        vl_tables a list of device int32 tensors (table_len defaults to their lengths).  Raises GvlError (status ERR_ARG) on a refusal."""
+        self._op_paged(L.GvlQkvPost, self.lib.gvl_op_qkv_post, "gvl_op_qkv_post", kw)
+
+    def op_prefill_attention(self, **kw):
+        """gvl_op_prefill_attention (include/gvl.h): one paged prefill-attention launch on caller-owned pages.  Every field of gvl_prefill_attn by keyword, as
+        op_qkv_post takes them (O is written in place).  Raises GvlError (status ERR_ARG) on a refusal."""
+        self._op_paged(L.GvlPrefillAttn, self.lib.gvl_op_prefill_attention, "gvl_op_prefill_attention", kw)
+
     def op_gemv(self, W, x, bias=None):
         N, K = W.shape
         y = torch.empty((N,), dtype=torch.float32, device=self.device)

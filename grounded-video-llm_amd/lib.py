@@ -83,6 +83,23 @@ class GvlDecodeAttn(C.Structure):
                 ("Dout", C.c_int32), ("nsplit", C.c_int32), ("hpb", C.c_int32), ("cpb", C.c_int32), ("gsplit", C.c_int32), ("scale", C.c_float)]
 
 
+class GvlQkvPost(C.Structure):
+    """gvl_qkv_post (include/gvl.h): one launch of gvl_launch_qkv_post / gvl_launch_qkv_post_ext on caller-owned tensors, for the operator tests."""
+    _fields_ = [("qkv", C.c_void_p), ("ld", C.c_int32), ("Q", C.c_void_p), ("Kt", C.c_void_p), ("Vt", C.c_void_p), ("block_table", C.c_void_p), ("max_pages", C.c_int32),
+                ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("KV", C.c_int32), ("Dr", C.c_int32), ("D", C.c_int32), ("mode", C.c_int32),
+                ("qn", C.c_void_p), ("kn", C.c_void_p), ("eps", C.c_float), ("cos", C.c_void_p), ("sin", C.c_void_p), ("pos0", C.c_int32),
+                ("ones_row", C.c_int32), ("k_ones", C.c_int32), ("q_rs", C.c_void_p), ("vl_n", C.c_int32), ("vl_rows", C.c_int32 * 9), ("vl_tables", C.c_void_p * 8),
+                ("vl_pos0", C.c_int32 * 8), ("table_len", C.c_int32 * 8), ("n_pages", C.c_int32), ("max_pos", C.c_int32), ("ext", C.c_int32)]
+
+
+class GvlPrefillAttn(C.Structure):
+    """gvl_prefill_attn (include/gvl.h): one paged prefill-attention launch (block table with qpos0 / Sk, ragged, ragged-extend) on caller-owned pages."""
+    _fields_ = [("Q", C.c_void_p), ("Kt", C.c_void_p), ("Vt", C.c_void_p), ("O", C.c_void_p), ("block_table", C.c_void_p), ("max_pages", C.c_int32),
+                ("B", C.c_int32), ("H", C.c_int32), ("KV", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("Dout", C.c_int32), ("Sk", C.c_int32), ("qpos0", C.c_int32),
+                ("scale", C.c_float), ("causal", C.c_int32), ("ring", C.c_int32), ("vl_n", C.c_int32), ("vl_rows", C.c_int32 * 9), ("vl_tables", C.c_void_p * 8),
+                ("vl_pos0", C.c_int32 * 8), ("table_len", C.c_int32 * 8), ("ext", C.c_int32), ("n_pages", C.c_int32)]
+
+
 class GvlPatchEmbed(C.Structure):
     """gvl_patch_embed (include/gvl.h): the patch embedding of either vision tower by either path, for the operator tests."""
     _fields_ = [("mode", C.c_int32), ("path", C.c_int32), ("n", C.c_int32), ("T", C.c_int32), ("image", C.c_int32), ("patch", C.c_int32), ("C", C.c_int32),
@@ -185,6 +202,8 @@ _SIGS = {
     "gvl_op_dgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gvl_op_decode_proj": (C.c_int, [C.c_void_p, C.POINTER(GvlDecodeProj), C.c_void_p]),
     "gvl_op_decode_attention": (C.c_int, [C.c_void_p, C.POINTER(GvlDecodeAttn), C.c_void_p]),
+    "gvl_op_qkv_post": (C.c_int, [C.c_void_p, C.POINTER(GvlQkvPost), C.c_void_p]),
+    "gvl_op_prefill_attention": (C.c_int, [C.c_void_p, C.POINTER(GvlPrefillAttn), C.c_void_p]),
     "gvl_op_decode_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "gvl_probe_mfma": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "gvl_trace_marker": (C.c_int, [C.c_int, C.c_void_p]),

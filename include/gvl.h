@@ -697,6 +697,75 @@ typedef struct {
   float scale;
 } gvl_decode_attn;
 int gvl_op_decode_attention(gvl_ctx* ctx, const gvl_decode_attn* p, void* stream);
+/* One launch of the pass between the prefill QKV GEMM and attention: a fused qkv matrix -> Q, K pages and V^T pages (operator tests: tests/test_gpu_qkv_post.py).
+ * All pointers are device memory and the caller owns every buffer; block tables are device int32.
+ *   qkv      bf16 rows of [H Dr | KV Dr | KV Dr] (q, k, v), ld elements apart (>= (H + 2 KV) Dr, a multiple of 8); B S rows, or -- a ragged group -- vl_rows[vl_n]
+ *   Q        bf16 [B][H][S][D]; ragged: member u's block [H][S_u][D] starts at element vl_rows[u] H D.  Not written (may be NULL) when q_rs is set
+ *   Kt, Vt   page pools bf16 [n_pages][KV][64][D] (key rows) and [n_pages][KV][D][64] (V transposed): the token at position p of a sequence is slot p % 64 of the
+ *            sequence's page p / 64.  Vt NULL: keys and queries only (pos0 need not be a multiple of 64 then)
+ *   pages    block_table NULL (needs pos0 == 0): page(b, t) = b ceil(S / 64) + t;  else int32 [B][max_pages];  ragged: vl_tables[u], int32 [table_len[u]]
+ *   Dr, D    the real and the padded head dim: Dr % 8 == 0 (mode 2: % 16), Dr <= 128, D % 8 == 0, D >= Dr.  Columns Dr .. D - 1 of every Q and K row written are 0,
+ *            but K column Dr is 1.0 under k_ones;  of a V^T page that is written ALL 64 slots of all D rows are: rows >= Dr and the slots of tokens behind the
+ *            sequence's last new token are 0, but row Dr is 1.0 in every slot under ones_row (both need D > Dr)
+ *   mode 0   q, k copied.
+ *   mode 1   q' [c] = bf16(qn[c] * bf16(q[c] * rs)), rs = rsqrt(sum of the row's H Dr squares / (H Dr) + eps) in fp32 (InternVideo2's full-width RMSNorm), k likewise
+ *            with kn over KV Dr;  q_rs set (f32 [B S]; needs k_ones): q's rs is stored there and Q is not written
+ *   mode 2   RoPE at position p = pos0 + i (ragged extend: vl_pos0[u] + i) from cos / sin f32 [max_pos][Dr / 2] holding bf16-representable values, per head with
+ *            half = Dr / 2:  d < half: bf16(bf16(x[d] cos[p][d]) + bf16(-x[d + half] sin[p][d]));  d >= half: bf16(bf16(x[d] cos[p][d - half]) + bf16(x[d - half] sin[p][d - half]))
+ *   ragged   vl_n in 1 .. 8 (mode 2, B == 1, pos0 == 0, block_table NULL): member u owns rows [vl_rows[u], vl_rows[u + 1]), vl_rows[0] == 0, no member empty
+ *   ext      0: gvl_launch_qkv_post;  1: gvl_launch_qkv_post_ext -- the ragged group where member u already holds vl_pos0[u] tokens (a multiple of 64, whole pages):
+ *            needs vl_n >= 1, Vt and no q_rs
+ * The call reads the tables back and returns GVL_ERR_ARG with a message, before anything is launched or written, for whatever the launcher refuses and for: a page
+ * outside [0, n_pages) or named twice among the pages the launch writes, a position >= max_pos in mode 2, a table shorter than ceil((pos0 + S_u) / 64), Vt with
+ * pos0 % 64 != 0, pos0 > 0 without a table, vl_rows[0] != 0 or an empty member, q_rs without k_ones, ones_row / k_ones with D == Dr, mode 1 without qn / kn.
+ * Synchronises the stream. */
+typedef struct {
+  const uint16_t* qkv; int32_t ld;
+  uint16_t* Q; uint16_t* Kt; uint16_t* Vt;
+  const int32_t* block_table; int32_t max_pages;
+  int32_t B, S, H, KV, Dr, D;
+  int32_t mode;
+  const uint16_t* qn; const uint16_t* kn; float eps;
+  const float* cos; const float* sin; int32_t pos0;
+  int32_t ones_row, k_ones;
+  float* q_rs;
+  int32_t vl_n;
+  int32_t vl_rows[9];
+  const int32_t* vl_tables[8];
+  int32_t vl_pos0[8];
+  int32_t table_len[8];
+  int32_t n_pages, max_pos, ext;
+} gvl_qkv_post;
+int gvl_op_qkv_post(gvl_ctx* ctx, const gvl_qkv_post* p, void* stream);
+/* One prefill-attention launch on caller-owned pages: the paged forms of attn_fwd_kernel behind a cached prefix (operator tests: tests/test_gpu_prefill_attn.py).
+ * The in-place and InternVideo2 forms and implicit pages stay with gvl_op_attention.  All pointers are device memory; block tables are device int32.
+ *   Q        bf16 [B][H][S][D], columns Dout .. D - 1 zero; ragged: member u's block [H][S_u][D] starts at element vl_rows[u] H D
+ *   Kt, Vt   the page pools as gvl_op_qkv_post writes them: bf16 [n_pages][KV][64][D] and [n_pages][KV][D][64]; key j of a sequence is slot j % 64 of its page j / 64.
+ *            K slots of keys >= Sk may hold anything (the kernel masks by index); V^T slots of keys >= Sk and the pad rows / columns must be FINITE
+ *   O        bf16 [B S][H Dout] (ragged: row vl_rows[u] + i), 16-byte aligned
+ *   single   vl_n == 0: B sequences of S queries, query i at position qpos0 + i of a context of Sk keys (0 = S; else Sk >= qpos0 + S), pages block_table
+ *            [B][max_pages];  causal: query i sees keys 0 .. qpos0 + i, else all Sk.  ring: K / V LDS ring depth 0 (launcher's choice), 2 or 3 -- no value may change a bit
+ *   ragged   vl_n in 1 .. 8 (causal, B == 1, Sk == qpos0 == 0, block_table NULL; S = the longest member): member u owns rows [vl_rows[u], vl_rows[u + 1]) and the table
+ *            vl_tables[u] (int32 [table_len[u]]);  ext = 1 (gvl_launch_attention_ext): member u's query i sits at position vl_pos0[u] + i (a multiple of 64) and sees
+ *            the vl_pos0[u] + S_u keys of its table.  ext = 0: gvl_launch_attention, vl_pos0 ignored
+ *   D        64, 96 or 128, Dout <= D a multiple of 8, H % KV == 0, at most 256 key tiles
+ * The call reads the tables back and returns GVL_ERR_ARG with a message, before anything is launched or written, for whatever attn_plan / attn_ext_plan refuse, a
+ * missing table, a table shorter than the key tiles the launch reads (causal: ceil((qpos0 + S_u) / 64), else ceil(Sk / 64)) and a page outside [0, n_pages) among
+ * them.  Synchronises the stream. */
+typedef struct {
+  const uint16_t* Q; const uint16_t* Kt; const uint16_t* Vt; uint16_t* O;
+  const int32_t* block_table; int32_t max_pages;
+  int32_t B, H, KV, S, D, Dout, Sk, qpos0;
+  float scale;
+  int32_t causal, ring;
+  int32_t vl_n;
+  int32_t vl_rows[9];
+  const int32_t* vl_tables[8];
+  int32_t vl_pos0[8];
+  int32_t table_len[8];
+  int32_t ext, n_pages;
+} gvl_prefill_attn;
+int gvl_op_prefill_attention(gvl_ctx* ctx, const gvl_prefill_attn* p, void* stream);
 /* measurement only (tools/decode_bench.py): average microseconds per launch of one decode projection [N,K] x `batch` sequences on
  * synthetic operands; mode 0 = skinny MFMA GEMM (variant 0 = default), 1 = VALU GEMV; `rounds` distinct weight copies are cycled. */
 int gvl_op_decode_bench(gvl_ctx* ctx, int N, int K, int batch, int mode, int variant, int rounds, int iters, double* us_per_launch,
