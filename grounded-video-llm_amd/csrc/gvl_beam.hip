@@ -89,6 +89,7 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
   if (!(p->penalty > 0.f) || p->ngram < 0 || p->min_new < 0) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: penalty must be > 0, ngram >= 0, min_new >= 0");
   if (p->rules_id != -1 && (p->rules_id < 0 || ctx->check_rules(p->rules_id))) return seq_fail(ctx, "gvl_beam_search", SEQ_NO_RULES);
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_beam_search", SEQ_BAD);
+  if (const int rc = pair_refuse(ctx, "gvl_beam_search", seq_id, true)) return rc;
   const int pos0 = ctx->seqs[seq_id].pos;
   if (pos0 <= 0) return fail(ctx, GVL_ERR_STATE, "gvl_beam_search: the sequence is not prefilled");
   if (const int rc = ensure_beam_search_buffers(ctx)) return rc;

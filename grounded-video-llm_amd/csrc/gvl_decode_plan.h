@@ -40,6 +40,22 @@ inline int decode_parts(bool mfma, int n, int* sizes) {
   for (int o = 0; o < n; o += sizes[k++]) sizes[k] = decode_group_size(mfma, n - o);
   return k;
 }
+// The same cut when some of the waiting sequences lead a guided PAIR (gvl_seq_set_guidance): unit i takes rows[i] rows of a step -- 1 for a plain sequence, 2 for a
+// leader, whose follower rides in the same step -- and a unit is never split.  In order, each step takes the longest run of units whose row total is an admitted size:
+// up to 16 rows (8 pairs, or any mix) on the MFMA path; 1 / 2 / 4 rows on the VALU path, where a pair and a plain sequence run as 2 + 1.  units[] holds up to n counts of
+// UNITS per step, returns how many.  With every rows[i] == 1 the cut is decode_parts'.  (A unit of 2 is itself admitted on both paths, so every step takes at least one.)
+inline int decode_parts_paired(bool mfma, const int* rows, int n, int* units) {
+  int k = 0;
+  for (int o = 0; o < n; o += units[k++]) {
+    int best = 1, total = 0;
+    for (int j = o; j < n && total + rows[j] <= GVL_MAX_DECODE_BATCH; ++j) {
+      total += rows[j];
+      if (decode_batch_ok(mfma, total)) best = j - o + 1;
+    }
+    units[k] = best;
+  }
+  return k;
+}
 
 // ---- the step ---------------------------------------------------------------------------------------------------------------------------------------------------------
 enum DecodeProj : int { GVL_DPROJ_QKV0 = 0, GVL_DPROJ_QKV, GVL_DPROJ_O, GVL_DPROJ_GATE_UP, GVL_DPROJ_DOWN, GVL_DPROJ_HEAD, GVL_DPROJ_KINDS };   // QKV0: layer 0's, QKV: later layers'

@@ -388,6 +388,17 @@ int gvl_launch_select_rows(const SelRowsArgs& a, hipStream_t st);
 struct BeamCandArgs { const float* rows; int n, k, row_stride, norm; float scores[GVL_MAX_DECODE_BATCH]; float* row_v; int* row_i; float* row_lp; float* vals; int* idx; float* proc; };
 int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st);
 int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st);      // rows [k][n] raw logits -> log-softmax, in place (beam_rows_kernel<true>'s arithmetic)
+// Classifier-free guidance (guidance_rows_kernel, gvl_pick.hip): pair p overwrites the n fp32 entries at cond[p] with scale[p] * (lc - lu) + lu, lc / lu the log-softmax
+// of cond[p] / neg[p] in beam_normalize_kernel's arithmetic; neg[p] is only read.  The conditional rows of one launch are distinct and none is another pair's negative row.
+// follow_commit_kernel: follower p takes the token at lead_tok[p] (its leader's, just selected) into tok[p] and out[p][*ngen[p]], then (*ngen[p])++ and, when non-null,
+// (*pos[p])++.  Both launches carry device pointers and by-value constants only: a captured decode step replays them.
+constexpr int GVL_MAX_GUIDANCE_PAIRS = GVL_MAX_DECODE_BATCH / 2;
+struct GuidanceArgs { int n, n_pairs; float* cond[GVL_MAX_GUIDANCE_PAIRS]; const float* neg[GVL_MAX_GUIDANCE_PAIRS]; float scale[GVL_MAX_GUIDANCE_PAIRS]; };
+struct FollowArgs { int n; const int* lead_tok[GVL_MAX_GUIDANCE_PAIRS]; int* tok[GVL_MAX_GUIDANCE_PAIRS]; int* out[GVL_MAX_GUIDANCE_PAIRS]; int* ngen[GVL_MAX_GUIDANCE_PAIRS];
+                    int* pos[GVL_MAX_GUIDANCE_PAIRS]; };
+struct PairLaunches { GuidanceArgs g; FollowArgs f; };   // what a group with pairs adds around its selection (pick_tokens, gvl_llm.hip)
+int gvl_launch_guidance_rows(const GuidanceArgs& a, hipStream_t st);
+int gvl_launch_follow_commit(const FollowArgs& a, hipStream_t st);
 // Teacher-forced scoring (score_rows_kernel, gvl_pick.hip): `rows` rows of n fp32 logits, ld floats apart, any number of them; targets [rows] on the device.  Per row: lp [rows]
 // the target's log-probability under the raw row, rank [rows] how many entries beat it (value descending, lower id first), and with top_n 1 .. 8 the best top_n finite
 // entries as top_ids / top_lp [rows][GVL_MAX_TOP_LOGPROBS], padded with (-1, -inf) (top_n == 0: never touched, may be null).

@@ -46,7 +46,23 @@ int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st) {
 // off the launch sequence is the one without processors.  A sequence's token rules (gvl_seq_set_token_rules) ride in the same launch: it runs
 // when a member has processors OR rules OR a grammar (gvl_seq_set_grammar), and with none of them nothing changes.  Sequences with log-probabilities on (gvl_seq_set_logprobs) get them from the same
 // launch (a second instantiation of the selection kernel); with every sequence of the group off it is the kernel without them.
-int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
+// Guided pairs (gvl_seq_set_guidance; `pairs` non-null): am / sqs cover the rows a token is selected for -- the followers' rows are not among them.  ONE guidance launch
+// rewrites the leaders' rows first (HF runs classifier-free guidance as the first processor), everything below then applies to the guided rows, and ONE launch behind
+// the selection hands every follower its leader's token.  Without pairs neither launch exists and the sequence of launches is the one it was.
+static int pick_tokens_rows(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
+int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st, const PairLaunches* pairs) {
+  if (!pairs) return pick_tokens_rows(ctx, am, sqs, st);
+  if (const int rc = gvl_launch_guidance_rows(pairs->g, st)) return rc;
+  if (const int rc = pick_tokens_rows(ctx, am, sqs, st)) return rc;
+  return gvl_launch_follow_commit(pairs->f, st);
+}
+int step_rows(gvl_ctx* ctx, Seq* const* named, int n, Seq** rows) {
+  int k = 0;
+  for (int b = 0; b < n; ++b) rows[k++] = named[b];
+  for (int b = 0; b < n; ++b) if (named[b]->follow >= 0) rows[k++] = &ctx->seqs[named[b]->follow];
+  return k;
+}
+static int pick_tokens_rows(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
   bool any_proc = false;
   for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->sel.proc.on() || sqs[b]->sel.rules >= 0 || sqs[b]->sel.grammar >= 0;
   if (any_proc) {
@@ -356,6 +372,8 @@ static GemvArgs proj_args(const gvl_ctx* ctx, int kind, int l, const DecodeProjP
 // argument is a device pointer or a constant of the group: the step can be replayed (hipGraph) without host-side counters.
 // WHICH launches it takes and what each projection reads is decode_plan's decision (gvl_decode_plan.h: pure, tested on the CPU): 4 * layers + 1 projections, `layers`
 // attention launches, 1 launch in front (+ 2 * layers norm launches for an unfused group of more than 4), then token selection.  This function is plan, then walk.
+// Guided pairs: the rows are step_rows' -- plain sequences and leaders first, then the followers (a row's results do not depend on its place).  The forward pass treats
+// a follower like any row; the selection covers the rows in front only, with the pairs' two launches around it (pick_tokens).
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st) {
   const gvl_config& f = ctx->cfg;
   const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
@@ -399,10 +417,26 @@ int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st) {
       RUN(GVL_PROF_OTHER, 0, gvl_launch_norm_tiled(ctx->d_x, ctx->d_xn, l + 1 < f.layers ? ctx->ll[l + 1].ln1 : ctx->l_norm, B, Hd, f.rms_eps, st));
   }
   if (const int rc = project(GVL_DPROJ_HEAD, 0, 2.0 * f.vocab * Hd)) return rc;
-  { ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = ctx->d_logits; am.n = f.vocab; am.batch = B;   // token, output list, n_gen++ and pos++ on the device
-    for (int b = 0; b < B; ++b) { am.tok_ptrs[b] = sqs[b]->d_tok; am.out_lists[b] = sqs[b]->d_out; am.ngen_ptrs[b] = sqs[b]->d_ngen; am.pos_ptrs[b] = sqs[b]->d_pos; }
-    if (ctx->watch_eos >= 0) { am.eos_id = ctx->watch_eos; for (int b = 0; b < B; ++b) am.eos_flags[b] = sqs[b]->d_eos; }
-    RUN(GVL_PROF_OTHER, 0, pick_tokens(ctx, am, sqs, st)); }
+  int nsel = B;                                        // rows a token is selected for: everything in front of the followers
+  while (nsel > 0 && sqs[nsel - 1]->lead >= 0) --nsel;
+  PairLaunches pl;
+  if (nsel < B) {                                      // any pair in this group
+    memset(&pl, 0, sizeof(pl)); pl.g.n = f.vocab;
+    for (int b = 0; b < nsel; ++b) {
+      if (sqs[b]->follow < 0) continue;
+      int r = nsel; while (r < B && sqs[r] != &ctx->seqs[sqs[b]->follow]) ++r;
+      if (r == B || pl.g.n_pairs >= GVL_MAX_GUIDANCE_PAIRS) return fail(ctx, GVL_ERR_STATE, "decode_step: a guided leader without its follower's row");
+      const int p = pl.g.n_pairs++;
+      pl.g.cond[p] = ctx->d_logits + (size_t)b * f.vocab; pl.g.neg[p] = ctx->d_logits + (size_t)r * f.vocab; pl.g.scale[p] = sqs[b]->guide;
+      pl.f.lead_tok[p] = sqs[b]->d_tok; pl.f.tok[p] = sqs[r]->d_tok; pl.f.out[p] = sqs[r]->d_out; pl.f.ngen[p] = sqs[r]->d_ngen; pl.f.pos[p] = sqs[r]->d_pos;
+    }
+    pl.f.n = pl.g.n_pairs;
+    if (pl.g.n_pairs != B - nsel) return fail(ctx, GVL_ERR_STATE, "decode_step: a follower's row without its leader");
+  }
+  { ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = ctx->d_logits; am.n = f.vocab; am.batch = nsel;   // token, output list, n_gen++ and pos++ on the device
+    for (int b = 0; b < nsel; ++b) { am.tok_ptrs[b] = sqs[b]->d_tok; am.out_lists[b] = sqs[b]->d_out; am.ngen_ptrs[b] = sqs[b]->d_ngen; am.pos_ptrs[b] = sqs[b]->d_pos; }
+    if (ctx->watch_eos >= 0) { am.eos_id = ctx->watch_eos; for (int b = 0; b < nsel; ++b) am.eos_flags[b] = sqs[b]->d_eos; }
+    RUN(GVL_PROF_OTHER, 0, pick_tokens(ctx, am, sqs, st, nsel < B ? &pl : nullptr)); }
   for (int b = 0; b < B; ++b) { sqs[b]->pos += 1; sqs[b]->n_gen += 1; }
   return 0;
 }
@@ -461,6 +495,8 @@ int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, 
   // on the group it is decoded in (gvl_decode.hip), so shrinking the group changes no result; the captured step is re-recorded.
   // The live set is stepped as PARTS of sizes the decode path takes (decode_parts, gvl_decode_plan.h: any size up to 16 on the skinny-MFMA path;
   // 4 / 2 / 1 on the VALU fallback, so three survivors of a group of four run as 2 + 1), one captured step graph per part.
+  // A guided pair (gvl_seq_set_guidance) is one member here: the leader is named, its follower is the part's extra row and leaves with it -- the follower's own eos,
+  // capacity and count are never looked at (its capacity was checked when the pair was bound, its ids are the leader's).
   // Retired graphs are destroyed after the final synchronise only: up to two replays may still be in flight when a member leaves.
   struct Part { Seq* m[GVL_MAX_DECODE_BATCH]; int n; std::unique_ptr<StepGraph> sg; };
   std::vector<Part> parts;
@@ -478,11 +514,11 @@ int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, 
     if (n_now != n_live || memcmp(now, live, sizeof(Seq*) * n_now) != 0) {
       for (auto& p : parts) retired.push_back(std::move(p.sg));
       parts.clear();
-      int sizes[GVL_MAX_DECODE_BATCH];
-      for (int k = 0, o = 0, nk = decode_parts(ctx->decode_mfma, n_now, sizes); k < nk; ++k) {
-        Part p; p.n = sizes[k];
-        memcpy(p.m, now + o, sizeof(Seq*) * p.n); p.sg.reset(new StepGraph());
-        o += p.n; parts.push_back(std::move(p));
+      int sizes[GVL_MAX_DECODE_BATCH], rows[GVL_MAX_DECODE_BATCH];   // a leader takes two rows of its part: its follower's comes with it (decode_parts_paired never splits them)
+      for (int b = 0; b < n_now; ++b) rows[b] = now[b]->follow >= 0 ? 2 : 1;
+      for (int k = 0, o = 0, nk = decode_parts_paired(ctx->decode_mfma, rows, n_now, sizes); k < nk; ++k) {
+        Part p; p.n = step_rows(ctx, now + o, sizes[k], p.m); p.sg.reset(new StepGraph());
+        o += sizes[k]; parts.push_back(std::move(p));
       }
       memcpy(live, now, sizeof(Seq*) * n_now); n_live = n_now;
     }

@@ -14,16 +14,25 @@ inline int fail(gvl_ctx* c, int code, const std::string& msg) { return gvl_fail(
 // a SeqStatus of the sequence table (gvl_seq_table.h) as the result of entry point `fn`: 0, or the status's error
 inline int seq_fail(gvl_ctx* c, const char* fn, int status) {
   if (status >= 0) return 0;
-  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_GRAMMAR_FULL
+  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_FOLLOWER
     {GVL_ERR_ARG, "bad seq"}, {GVL_ERR_ARG, "duplicate seq"}, {GVL_ERR_OOM, "KV pages exhausted"}, {GVL_ERR_OOM, "too many live sequences"}, {GVL_ERR_ARG, "no such rule set"},
     {GVL_ERR_STATE, "the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)"},
     {GVL_ERR_ARG, "too many live rule sets (limit 1024)"}, {GVL_ERR_ARG, "no such grammar"},
     {GVL_ERR_STATE, "the grammar is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_grammar(-1) first)"},
-    {GVL_ERR_ARG, "too many live grammars (limit 64)"}};
-  const auto& x = e[status >= SEQ_GRAMMAR_FULL ? -1 - status : 0];
+    {GVL_ERR_ARG, "too many live grammars (limit 64)"},
+    {GVL_ERR_STATE, "the sequence follows a guided leader (gvl_seq_set_guidance): free or unbind the leader first"}};
+  const auto& x = e[status >= SEQ_FOLLOWER ? -1 - status : 0];
   return fail(c, x.code, std::string(fn) + ": " + x.text);
 }
 
+// Guided pairs (gvl_seq_set_guidance): entry point `fn` cannot take sequence `id` -- a bound follower always (it is stepped as its leader's extra row and nowhere else),
+// a leader too where `leader_too` (entries that would copy one member or move it without the other).  0, or GVL_ERR_STATE with nothing changed.
+inline int pair_refuse(gvl_ctx* c, const char* fn, int id, bool leader_too) {
+  const Seq* s = c->lookup(id);
+  if (s && s->lead >= 0) return fail(c, GVL_ERR_STATE, std::string(fn) + ": sequence " + std::to_string(id) + " follows guided leader " + std::to_string(s->lead) + "; name the leader");
+  if (s && leader_too && s->follow >= 0) return fail(c, GVL_ERR_STATE, std::string(fn) + ": sequence " + std::to_string(id) + " leads a guided pair (gvl_seq_set_guidance(seq, -1, ...) unbinds)");
+  return 0;
+}
 // the log-probability lists of slot `id` (null while the ctx has not allocated them)
 inline void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
   const size_t cap = (size_t)ctx->outlist_cap;
@@ -98,7 +107,10 @@ int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream
 
 // gvl_llm.hip
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);
-int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
+// pairs (null: none): the guidance launch in front of the processors and the followers' commit behind the selection -- a group without pairs takes neither
+int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st, const PairLaunches* pairs = nullptr);
+// the rows of one step for `n` named sequences (plain ones and leaders): rows[] = the named ones in order, then the leaders' followers in order; returns how many
+int step_rows(gvl_ctx* ctx, Seq* const* named, int n, Seq** rows);
 // one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan
 int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr,
                 const ScoreReq* score = nullptr);   // pos0s: tokens each sequence already holds (null = none); score: rows of the group to score on the way (not with loss)

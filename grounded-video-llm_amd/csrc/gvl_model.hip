@@ -496,6 +496,7 @@ int gvl_seq_free(gvl_ctx* ctx, int seq_id) {
 int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* dst_seq) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_fork");
   if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: bad arguments");
+  if (const int rc = pair_refuse(ctx, "gvl_seq_fork", src_seq, true)) return rc;
   if (n_tokens <= 0 || (n_tokens & 63) || n_tokens > ctx->seqs[src_seq].pos) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: n_tokens must be a positive multiple of 64 within the source's tokens");
   if (max_tokens <= n_tokens || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: max_tokens must exceed n_tokens and fit cfg.max_seq");
   if (ctx->fork_cuts_answer(ctx->seqs[src_seq], n_tokens))
@@ -533,6 +534,7 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
 int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
   if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
+  if (const int rc = pair_refuse(ctx, "gvl_seq_clone", src_seq, true)) return rc;
   const int pos = ctx->seqs[src_seq].pos;
   if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
   if (carry_generated && ctx->seqs[src_seq].n_gen > ctx->outlist_cap) return fail(ctx, GVL_ERR_STATE, "gvl_seq_clone: the source generated more ids than an output list holds");
@@ -569,6 +571,7 @@ extern "C" {
 int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_new, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend");
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_prefill_extend", SEQ_BAD);
+  if (const int rc = pair_refuse(ctx, "gvl_prefill_extend", seq_id, false)) return rc;
   Seq& sq = ctx->seqs[seq_id];
   if (sq.pos <= 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend: the sequence must hold a prefix of whole pages (gvl_seq_fork)");
   if (!embeds || n_new <= 0 || sq.pos + n_new > sq.max_tokens || n_new > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad length");
@@ -640,6 +643,7 @@ int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, cons
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
     if (!ctx->lookup(id) || !embeds_new[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad seq / embeds");
+    if (const int rc = pair_refuse(ctx, "gvl_prefill_extend_varlen", id, false)) return rc;
     const Seq& sq = ctx->seqs[id];
     if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
     if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad length");
@@ -671,6 +675,7 @@ int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const 
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
     if (!ctx->lookup(id) || !embeds_new[i] || !next_ids_host[i]) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad seq / embeds / next ids");
+    if (const int rc = pair_refuse(ctx, "gvl_score_extend_varlen", id, false)) return rc;
     const Seq& sq = ctx->seqs[id];
     if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_score_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
     if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad length");
@@ -722,13 +727,16 @@ int gvl_decode_greedy_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int ma
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
     if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_BAD);
+    if (const int rc = pair_refuse(ctx, "gvl_decode_greedy_batch", id, false)) return rc;
     if (ctx->seqs[id].n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_greedy: call gvl_prefill first");   // members of a group must also be at the SAME step (checked per group)
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
-  // groups of up to 16 (VALU fallback: 4, 2, 1): a group streams the weights once per step for all of its members
-  int sizes[gvl_ctx::kMaxSeqs];
-  for (int k = 0, i = 0, nk = decode_parts(ctx->decode_mfma, n_seqs, sizes); k < nk; ++k) {
+  // groups of up to 16 rows (VALU fallback: 4, 2, 1): a group streams the weights once per step for all of its members.  A guided leader counts two rows: its follower
+  // is stepped with it (decode_parts_paired; without pairs the cut is decode_parts')
+  int sizes[gvl_ctx::kMaxSeqs], rows[gvl_ctx::kMaxSeqs];
+  for (int i = 0; i < n_seqs; ++i) rows[i] = ctx->seqs[seq_ids[i]].follow >= 0 ? 2 : 1;
+  for (int k = 0, i = 0, nk = decode_parts_paired(ctx->decode_mfma, rows, n_seqs, sizes); k < nk; ++k) {
     const int B = sizes[k];
     Seq* sqs[GVL_MAX_DECODE_BATCH]; int32_t* outs[GVL_MAX_DECODE_BATCH]; int* nouts[GVL_MAX_DECODE_BATCH];
     for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; outs[b] = out_ids + (size_t)(i + b) * max_new; nouts[b] = n_out + i + b; }
@@ -747,20 +755,22 @@ int gvl_decode_steps(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int n_steps, 
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
     if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_steps", SEQ_BAD);
+    if (const int rc = pair_refuse(ctx, "gvl_decode_steps", id, false)) return rc;
     const Seq& sq = ctx->seqs[id];
     if (sq.n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_steps: call gvl_prefill first");
     if (sq.pos + n_steps > sq.max_tokens || sq.n_gen + n_steps > ctx->outlist_cap) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: sequence would exceed its capacity");
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_steps", SEQ_DUPLICATE);
   }
   hipStream_t st = (hipStream_t)stream;
-  int sizes[gvl_ctx::kMaxSeqs];
-  const int nk = decode_parts(ctx->decode_mfma, n_seqs, sizes);   // groups of up to 16 (VALU fallback: 4, 2, 1): one weight stream per step per group
+  int sizes[gvl_ctx::kMaxSeqs], rows[gvl_ctx::kMaxSeqs];
+  for (int i = 0; i < n_seqs; ++i) rows[i] = ctx->seqs[seq_ids[i]].follow >= 0 ? 2 : 1;   // a guided leader brings its follower's row (bound with at least the leader's capacity left)
+  const int nk = decode_parts_paired(ctx->decode_mfma, rows, n_seqs, sizes);   // groups of up to 16 rows (VALU fallback: 4, 2, 1): one weight stream per step per group
   for (int s = 0; s < n_steps; ++s) {
     for (int k = 0, i = 0; k < nk; ++k) {
       const int B = sizes[k];
-      Seq* sqs[GVL_MAX_DECODE_BATCH];
-      for (int b = 0; b < B; ++b) sqs[b] = &ctx->seqs[seq_ids[i + b]];
-      const int rc = decode_step(ctx, sqs, B, st);
+      Seq* named[GVL_MAX_DECODE_BATCH]; Seq* sqs[GVL_MAX_DECODE_BATCH];
+      for (int b = 0; b < B; ++b) named[b] = &ctx->seqs[seq_ids[i + b]];
+      const int rc = decode_step(ctx, sqs, step_rows(ctx, named, B, sqs), st);
       if (rc) return rc;
       i += B;
     }
@@ -784,6 +794,7 @@ int gvl_seq_read(gvl_ctx* ctx, int seq_id, int first, int32_t* out_ids, int cap,
 int gvl_decode_step_logits(gvl_ctx* ctx, int seq_id, int tok, float* logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_decode_step_logits");
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_decode_step_logits", SEQ_BAD);
+  if (const int rc = pair_refuse(ctx, "gvl_decode_step_logits", seq_id, true)) return rc;
   Seq& sq = ctx->seqs[seq_id];
   if (tok < 0 || tok >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits: bad token / sequence full / not prefilled");
   hipStream_t st = (hipStream_t)stream;
@@ -803,6 +814,7 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
     if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_BAD);
+    if (const int rc = pair_refuse(ctx, "gvl_decode_step_logits_batch", id, true)) return rc;
     Seq& sq = ctx->seqs[id];
     if (toks[i] < 0 || toks[i] >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: bad token / sequence full / not prefilled");
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_DUPLICATE);

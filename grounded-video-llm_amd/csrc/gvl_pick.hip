@@ -581,6 +581,54 @@ int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st) {
   hipLaunchKernelGGL(beam_normalize_kernel, dim3(k), dim3(1024), 0, st, rows, n);
   return CHECK_LAUNCH();
 }
+// ---- classifier-free guidance against a negative sequence (GuidanceArgs / FollowArgs; HF UnbatchedClassifierFreeGuidanceLogitsProcessor [ext]: the FIRST processor, so
+// it runs in front of gvl_launch_logits_process and the selection, which then see the guided row where they saw the raw one).
+//   guidance_rows_kernel   one block per PAIR: cond[p] <- scale * (log_softmax(cond[p]) - log_softmax(neg[p])) + log_softmax(neg[p]), the negative row only read.  Per row
+//                          m and lz are beam_row_norm's (pick_row_max, the strided sum, smp_block_sum, logf) and lc / lu are beam_lp<true>'s two subtractions, so each is bit
+//                          for bit what beam_normalize_kernel leaves; then ONE fp32 subtract, ONE multiply, ONE add, each rounded (no FMA contraction: the exact test compares
+//                          against three separate device ops).  A pair's result is a pure function of its two rows and its scale.  Rows are finite by contract (gvl.h).
+//   follow_commit_kernel   after the selection, one thread per follower: the leader's just-selected token into the follower's token word and output list, its generation
+//                          count and position bumped -- pick_commit's stores for a row nobody selected for.  Not part of pick_commit or the selection kernels: their
+//                          instruction streams are pinned (profiles/pick_refactor_asm.txt), and a group without pairs launches neither kernel.
+__global__ __launch_bounds__(1024) void guidance_rows_kernel(const GuidanceArgs a) {
+  __shared__ float shf[16];
+  const int p = blockIdx.x, tid = threadIdx.x, n = a.n;
+  float* c = a.cond[p]; const float* u = a.neg[p];
+  float mc, zc, mu, zu;
+  beam_row_norm(c, n, tid, shf, mc, zc);
+  __syncthreads();                          // every thread has read the first row's wave sums before the second row's maxima overwrite them
+  beam_row_norm(u, n, tid, shf, mu, zu);
+  const float s = a.scale[p];
+  for (int i = tid; i < n; i += 1024) {     // every thread has read the entries it is about to overwrite (beam_normalize_kernel's argument)
+    // __fadd_rn(__fmul_rn(s, __fsub_rn(lc, lu)), lu) in plain operators with contraction OFF for this block: the _rn wrappers are ordinary operators compiled where
+    // they are defined, contraction allowed, and the multiply and the add then fuse into one FMA -- one rounding instead of two, 1 ulp off the three separate ops
+#pragma clang fp contract(off)
+    const float lc = beam_lp<true>(c[i], mc, zc), lu = beam_lp<true>(u[i], mu, zu);
+    const float d = lc - lu;
+    const float t = s * d;
+    c[i] = t + lu;
+  }
+}
+int gvl_launch_guidance_rows(const GuidanceArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n_pairs < 1 || a.n_pairs > GVL_MAX_GUIDANCE_PAIRS) return -1;
+  for (int p = 0; p < a.n_pairs; ++p) if (!a.cond[p] || !a.neg[p] || !(fabsf(a.scale[p]) < INFINITY)) return -1;
+  hipLaunchKernelGGL(guidance_rows_kernel, dim3(a.n_pairs), dim3(1024), 0, st, a);
+  return CHECK_LAUNCH();
+}
+__global__ __launch_bounds__(64) void follow_commit_kernel(const FollowArgs a) {
+  const int p = threadIdx.x;
+  if (p >= a.n) return;
+  const int t = *a.lead_tok[p];
+  *a.tok[p] = t;
+  const int g = *a.ngen[p]; a.out[p][g] = t; *a.ngen[p] = g + 1;
+  if (a.pos[p]) (*a.pos[p])++;
+}
+int gvl_launch_follow_commit(const FollowArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > GVL_MAX_GUIDANCE_PAIRS) return -1;
+  for (int p = 0; p < a.n; ++p) if (!a.lead_tok[p] || !a.tok[p] || !a.out[p] || !a.ngen[p]) return -1;
+  hipLaunchKernelGGL(follow_commit_kernel, dim3(1), dim3(64), 0, st, a);
+  return CHECK_LAUNCH();
+}
 // ---- teacher-forced scoring (ScoreRowsArgs; gvl_score_extend_varlen's tail and gvl_op_score_rows): what the raw distribution of a row says about a GIVEN id.  One block
 // per row of fp32 logits, any number of rows.  Per row, with t the target, m the row maximum and lz = logf(sum exp(s - m)):
 //   lp    (s_t - m) - lz.  m is pick_row_max's, the sum is strided per thread and finished by smp_block_sum -- lp_row_pass<1>'s order at thr = 0, inv_temp = 1 (beam_row_norm's

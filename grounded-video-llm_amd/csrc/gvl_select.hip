@@ -360,6 +360,61 @@ int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, cons
   return 0;
 }
 
+// ---- classifier-free guidance against a negative sequence (guidance_rows_kernel / follow_commit_kernel, gvl_pick.hip; the per-step side is decode_step's, gvl_llm.hip)
+// Everything is checked before the first launch: a refusal leaves both sequences as their prefills left them.
+int gvl_seq_set_guidance(gvl_ctx* ctx, int seq_id, int neg_seq_id, float scale, float* cond_logits, float* neg_logits, void* stream) {
+  REQUIRE_READY(ctx->has_llm, "gvl_seq_set_guidance");
+  Seq* lead = ctx->lookup(seq_id);
+  if (!lead) return seq_fail(ctx, "gvl_seq_set_guidance", SEQ_BAD);
+  if (neg_seq_id == -1) {                              // unbind: both members go on as plain sequences
+    if (lead->lead >= 0) return pair_refuse(ctx, "gvl_seq_set_guidance", seq_id, false);
+    ctx->unpair(seq_id);
+    return 0;
+  }
+  Seq* fol = ctx->lookup(neg_seq_id);
+  if (!fol) return seq_fail(ctx, "gvl_seq_set_guidance", SEQ_BAD);
+  if (seq_id == neg_seq_id) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_guidance: the negative sequence must be another sequence");
+  if (!cond_logits || !neg_logits || cond_logits == neg_logits) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_guidance: the two prefills' last_logits are needed (two device buffers)");
+  if (!std::isfinite(scale)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_guidance: scale must be finite");
+  if (lead->lead >= 0 || lead->follow >= 0 || fol->lead >= 0 || fol->follow >= 0) return fail(ctx, GVL_ERR_STATE, "gvl_seq_set_guidance: a sequence is already part of a guided pair");
+  if (lead->n_gen != 1 || fol->n_gen != 1)
+    return fail(ctx, GVL_ERR_STATE, "gvl_seq_set_guidance: both sequences must be freshly prefilled (exactly the one token their own prefill selected)");
+  if (fol->max_tokens - fol->pos < lead->max_tokens - lead->pos)
+    return fail(ctx, GVL_ERR_STATE, "gvl_seq_set_guidance: the negative sequence has less capacity left than the conditional one");
+  hipStream_t st = (hipStream_t)stream;
+  // The FIRST token again, from the guided row: the counters go back to 0, so the processors see an empty history, the draw is the one of step 0 and slot 0 of every
+  // list is rewritten -- both sequences end where a prefill that had selected from the guided row would have left them (the positions never moved: a prefill's
+  // selection carries no position pointer either).
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(lead->d_ngen, 0, st));
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(fol->d_ngen, 0, st));
+  PairLaunches pl; memset(&pl, 0, sizeof(pl));
+  pl.g.n = ctx->cfg.vocab; pl.g.n_pairs = 1; pl.g.cond[0] = cond_logits; pl.g.neg[0] = neg_logits; pl.g.scale[0] = scale;
+  pl.f.n = 1; pl.f.lead_tok[0] = lead->d_tok; pl.f.tok[0] = fol->d_tok; pl.f.out[0] = fol->d_out; pl.f.ngen[0] = fol->d_ngen;
+  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = cond_logits; am.n = ctx->cfg.vocab; am.batch = 1;
+  am.tok_ptrs[0] = lead->d_tok; am.out_lists[0] = lead->d_out; am.ngen_ptrs[0] = lead->d_ngen;
+  Seq* one[1] = {lead};
+  RUN(GVL_PROF_OTHER, 0, pick_tokens(ctx, am, one, st, &pl));
+  lead->follow = neg_seq_id; lead->guide = scale; fol->lead = seq_id;
+  return 0;
+}
+// guidance_rows_kernel on caller rows: pair p overwrites row pairs[2p] with the guided row against row pairs[2p + 1] (row r = logits + r * ld), scale scales[p]
+int gvl_op_guidance(gvl_ctx* ctx, float* logits, int n, int ld, const int* pairs, int n_pairs, const float* scales, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!logits || !pairs || !scales || n < 1 || ld < n || n_pairs < 1 || n_pairs > GVL_MAX_GUIDANCE_PAIRS)
+    return fail(ctx, GVL_ERR_ARG, "gvl_op_guidance: bad arguments (1 .. 8 pairs)");
+  GuidanceArgs g; memset(&g, 0, sizeof(g)); g.n = n; g.n_pairs = n_pairs;
+  for (int p = 0; p < n_pairs; ++p) {
+    const int c = pairs[2 * p], u = pairs[2 * p + 1];
+    if (c < 0 || u < 0 || c == u || !std::isfinite(scales[p])) return fail(ctx, GVL_ERR_ARG, "gvl_op_guidance: a pair needs two different rows >= 0 and a finite scale");
+    for (int q = 0; q < n_pairs; ++q)                  // a conditional row is written: no other pair may read or write it
+      if (q != p && (pairs[2 * q] == c || pairs[2 * q + 1] == c)) return fail(ctx, GVL_ERR_ARG, "gvl_op_guidance: a conditional row appears in another pair");
+    g.cond[p] = logits + (size_t)c * ld; g.neg[p] = logits + (size_t)u * ld; g.scale[p] = scales[p];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_guidance_rows(g, st));
+  return 0;
+}
+
 // score_rows_kernel on raw rows, any number of them (the targets live on the device: one outside [0, n) scores lp = -inf, rank = -1 and never indexes its row)
 int gvl_op_score_rows(gvl_ctx* ctx, const float* logits_dev, int n, int ld, int rows, const int32_t* targets_dev, int top_n, float* lp_dev, int32_t* rank_dev,
                       int32_t* top_ids_dev, float* top_lp_dev, void* stream) {

@@ -30,9 +30,12 @@ struct SeqCore {
   bool used = false; int max_tokens = 0, n_pages = 0, pos = 0, n_gen = 0;
   std::vector<int> pages;   // KV pages in position order, 64 tokens each: whole pages of a prefix may be shared with other sequences (page_ref)
   SeqSelect sel;
+  // classifier-free guidance (gvl_seq_set_guidance): a LEADER names its follower in `follow` and carries the pair's scale; the FOLLOWER names its leader in `lead`.
+  // A follower takes its leader's token every step and is stepped only as the leader's extra row.  -1: not part of a pair.  A copy (fork / clone) starts unpaired.
+  int lead = -1, follow = -1; float guide = 1.0f;
 };
 enum SeqStatus { SEQ_OK = 0, SEQ_BAD = -1, SEQ_DUPLICATE = -2, SEQ_NO_PAGES = -3, SEQ_TOO_MANY = -4, SEQ_NO_RULES = -5, SEQ_RULES_BUSY = -6, SEQ_RULES_FULL = -7,
-                 SEQ_NO_GRAMMAR = -8, SEQ_GRAMMAR_BUSY = -9, SEQ_GRAMMAR_FULL = -10 };
+                 SEQ_NO_GRAMMAR = -8, SEQ_GRAMMAR_BUSY = -9, SEQ_GRAMMAR_FULL = -10, SEQ_FOLLOWER = -11 };
 
 template <class S = SeqCore>
 struct SeqTable {
@@ -68,13 +71,22 @@ struct SeqTable {
     if (id == (int)seqs.size()) seqs.push_back(std::move(s)); else seqs[id] = std::move(s);
     return id;
   }
-  // the sequence's pages, rule set and grammar go back; a page shared with a fork lives on until its last holder is closed
+  // the sequence's pages, rule set and grammar go back; a page shared with a fork lives on until its last holder is closed.  A bound follower is refused with nothing
+  // changed (its leader's steps write its pages); closing a leader unbinds the pair, and the follower lives on as a plain sequence
   int close(int id) {
     S* s = lookup(id); if (!s) return SEQ_BAD;
+    if (s->lead >= 0) return SEQ_FOLLOWER;
+    if (s->follow >= 0) unpair(id);
     for (int p : s->pages) if (--page_ref[p] == 0) free_pages.push_back(p);
     if (s->sel.rules >= 0) --rule_sets[s->sel.rules].refs;
     if (s->sel.grammar >= 0) --grammars[s->sel.grammar].refs;
     *s = S(); return SEQ_OK;
+  }
+  // leader `id` and its follower become plain sequences again (a no-op for a sequence that leads nobody)
+  void unpair(int id) {
+    S* s = lookup(id); if (!s || s->follow < 0) return;
+    if (S* f = lookup(s->follow)) f->lead = -1;
+    s->follow = -1; s->guide = 1.0f;
   }
   // `sel` (a sequence's) takes its own sampling setting; q null: back to following the table-wide setting, as a new sequence does
   static void set_sampling(SeqSelect& sel, const Sampling* q) { sel.own_sampling = q != nullptr; sel.sampling = q ? *q : Sampling(); }

@@ -313,6 +313,12 @@ class Engine:
         assert S.value == out.shape[0]
         return out
 
+    def embed_ids(self, input_ids: Sequence[int]) -> torch.Tensor:
+        """The embedding rows of plain token ids [len, hidden] -- a text-only prompt (no image slot): gvl_splice with the slot behind the last id and no visual rows."""
+        if len(input_ids) == 0 or any(int(i) < 0 for i in input_ids):
+            raise ValueError("embed_ids: a non-empty list of token ids >= 0 (no image slot)")
+        return self.splice(list(input_ids) + [-200], torch.empty((0, self.geo.hidden), dtype=bf, device=self.device))
+
     def seq_alloc(self, max_tokens: int) -> int:
         s = C.c_int(-1)
         self._chk(self.lib.gvl_seq_alloc(self.ctx, int(max_tokens), C.byref(s)), "gvl_seq_alloc")
@@ -475,6 +481,36 @@ class Engine:
         logits = torch.empty((n, self.geo.vocab), dtype=torch.float32, device=self.device)
         ids = (C.c_int * n)(*[int(s) for s in seqs]); tk = (C.c_int32 * n)(*[int(t) for t in toks])
         self._chk(self.lib.gvl_decode_step_logits_batch(self.ctx, ids, n, tk, _ptr(logits), self.stream), "gvl_decode_step_logits_batch")
+        return logits
+
+    # ---- classifier-free guidance against a negative sequence (gvl_seq_set_guidance; the guidance / follow kernels of csrc/gvl_pick.hip) ----
+    def seq_set_guidance(self, seq: int, neg_seq: Optional[int], scale: float = 1.0, cond_logits: Optional[torch.Tensor] = None,
+                         neg_logits: Optional[torch.Tensor] = None) -> None:
+        """gvl_seq_set_guidance: bind the freshly prefilled sequence `seq` (the leader) to the freshly prefilled negative sequence `neg_seq` (its follower); HF
+        generate(guidance_scale=scale, negative_prompt_ids=...).  cond_logits / neg_logits: the two prefills' last-row logits (prefill(..., want_logits=True)); they are
+        scratch for the call, which re-selects the first token from the guided row and writes it to both sequences; they must be RAW rows -- set the leader's processors,
+        rules and grammar between its prefill and this call.  From then on only `seq` is named in decode_greedy /
+        decode_greedy_batch / decode_steps; the follower rides as one more row of the same step.  neg_seq None: unbind."""
+        if neg_seq is None:
+            self._chk(self.lib.gvl_seq_set_guidance(self.ctx, int(seq), -1, 1.0, None, None, self.stream), "gvl_seq_set_guidance")
+            return
+        for t in (cond_logits, neg_logits):
+            if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.geo.vocab or t.device != self.device:
+                raise ValueError("seq_set_guidance: cond_logits / neg_logits must be contiguous fp32 [vocab] device tensors (the prefills' last logits)")
+        self._chk(self.lib.gvl_seq_set_guidance(self.ctx, int(seq), int(neg_seq), float(scale), _ptr(cond_logits), _ptr(neg_logits), self.stream), "gvl_seq_set_guidance")
+
+    def op_guidance(self, logits: torch.Tensor, pairs, scales) -> torch.Tensor:
+        """gvl_op_guidance on fp32 rows [R, n] IN PLACE (the row stride is taken from the tensor): pairs = [(conditional row, negative row), ...] (1 .. 8), one scale per
+        pair; a pair's conditional row becomes scale * (log_softmax(cond) - log_softmax(neg)) + log_softmax(neg), every other row is untouched.  Returns logits."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.device.type == "cuda"
+        R, n = logits.shape
+        pr = [(int(c), int(u)) for c, u in pairs]
+        sc = [float(s) for s in scales]
+        if len(sc) != len(pr) or any(not (0 <= r < R) for p in pr for r in p):
+            raise ValueError(f"op_guidance: one scale per pair and rows inside [0, {R})")
+        flat = (C.c_int * (2 * len(pr)))(*[r for p in pr for r in p])
+        self._chk(self.lib.gvl_op_guidance(self.ctx, _ptr(logits), n, int(logits.stride(0)) if R > 1 else n, flat, len(pr), (C.c_float * len(sc))(*sc), self.stream),
+                  "gvl_op_guidance")
         return logits
 
     # ---- beam search in the library (gvl_beam_search; csrc/gvl_beam.h + the candidate kernels) -------------------

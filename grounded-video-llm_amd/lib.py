@@ -193,6 +193,8 @@ _SIGS = {
     "gvl_seq_set_grammar": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gvl_op_logits_process_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float),
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "gvl_seq_set_guidance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gvl_op_guidance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "gvl_set_logprobs": (C.c_int, [C.c_void_p, C.c_int]),
     "gvl_seq_set_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gvl_seq_read_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -116,6 +116,43 @@ def resolve_sampling(kw: dict) -> dict:
     return out
 
 
+GUIDANCE_KWARGS = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "negative_prompts")
+
+
+def resolve_guidance(kw: dict) -> Optional[float]:
+    """HF's `guidance_scale` among generate()'s kwargs -> the scale of classifier-free guidance, or None when it is off.  HF's rule (`_get_logits_processor`): the
+    processor exists only when guidance_scale is not None and != 1.  HF itself checks nothing else and would compute with whatever it is given; here the value must
+    be a finite real number (an int is taken as its float), since it travels to the device as one fp32 constant."""
+    s = kw.get("guidance_scale")
+    if s is None:
+        return None
+    if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(float(s)):
+        raise ValueError(f"`guidance_scale` has to be a finite float, but is {s!r}")
+    return None if s == 1 else float(s)
+
+
+def negative_id_rows(ids, mask=None) -> list:
+    """HF's negative_prompt_ids (+ negative_prompt_attention_mask) -> one plain list of token ids per row: a tensor / array / list of rows (or one flat row), the ids
+    whose mask is 0 (padding) dropped.  Raises ValueError for an empty row, a negative id or a mask of another shape."""
+    rows = ids.tolist() if hasattr(ids, "tolist") else list(ids)
+    if rows and not isinstance(rows[0], (list, tuple)):
+        rows = [rows]
+    mrows = None
+    if mask is not None:
+        mrows = mask.tolist() if hasattr(mask, "tolist") else list(mask)
+        if mrows and not isinstance(mrows[0], (list, tuple)):
+            mrows = [mrows]
+        if len(mrows) != len(rows) or any(len(m) != len(r) for m, r in zip(mrows, rows)):
+            raise ValueError("`negative_prompt_attention_mask` must have the shape of `negative_prompt_ids`")
+    out = []
+    for i, r in enumerate(rows):
+        keep = [int(t) for j, t in enumerate(r) if mrows is None or mrows[i][j]]
+        if not keep or any(t < 0 for t in keep):
+            raise ValueError("`negative_prompt_ids`: every row needs at least one (unmasked) token id, all >= 0")
+        out.append(keep)
+    return out
+
+
 def request_sampling(do_sample=None, temperature=None, top_k=None, top_p=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, seed=None):
     """One request's OWN sampling setting for SeqOptions.sampling: ... when every argument is None (the request follows the engine's setting), else a dict for
     Engine.seq_set_sampling with stream 0 -- greedy for do_sample=False; otherwise sampled (do_sample None counts as True once another argument is given) with HF's

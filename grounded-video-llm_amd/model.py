@@ -333,6 +333,99 @@ class LLAVA_NEXT_VIDEO:
         top_k = kw.get("top_k", 50)
         self.engine.set_sampling(True, t, 0 if top_k is None else int(top_k), top_p, seed, **{k: v for k, v in LP.resolve_sampling(kw).items() if v is not None})
 
+    def _check_guidance(self, kw, n: int) -> Optional[float]:
+        """generate(guidance_scale=s, ...): HF's classifier-free guidance against a negative prompt (logits.resolve_guidance: off for None / 1).  Returns the scale
+        (None: off) after checking, before any work, that the call names one negative per sample -- negative_prompt_ids (HF's; plain ids, text-only) or
+        negative_prompts (extra; strings through the model's own prompt path) -- and combines guidance with nothing it is not built for."""
+        scale = LP.resolve_guidance(kw)
+        if scale is None:
+            return None
+        if kw.get("num_beams", 1) not in (1, None):
+            raise ValueError("generate(): guidance_scale with num_beams > 1 is not supported yet")
+        ids, texts = kw.get("negative_prompt_ids"), kw.get("negative_prompts")
+        if (ids is None) == (texts is None):
+            raise ValueError("generate(): guidance_scale != 1 needs the negative prompt of every sample: pass negative_prompt_ids (token ids, text-only) or "
+                             "negative_prompts (strings; with the <image> slot they see the same video) -- exactly one of them.  (HF's fallback, the prompt's last "
+                             "id, does not exist for an embeddings prompt.)")
+        if ids is not None:
+            ids = LP.negative_id_rows(ids, kw.get("negative_prompt_attention_mask"))
+            if any(t >= self.geo.vocab for r in ids for t in r):
+                raise ValueError(f"generate(): negative_prompt_ids holds an id outside the vocabulary of {self.geo.vocab} tokens")
+        elif isinstance(texts, str) or any(not isinstance(t, str) for t in texts):
+            raise ValueError("generate(): negative_prompts must be a list of strings, one per sample")
+        if len(ids if ids is not None else texts) != n:
+            raise ValueError(f"generate(): {n} samples need {n} negative prompts, not {len(ids if ids is not None else texts)}")
+        return scale
+
+    def _negative_embeds(self, kw, feats) -> List[torch.Tensor]:
+        """The negative prompts of a guided call as embedding rows, one tensor per sample.  negative_prompt_ids: the ids' embedding rows (what HF runs as the
+        unconditional branch of an inputs_embeds prompt).  negative_prompts: tokenised and truncated like the prompts; a string with the <image> slot is spliced
+        with the sample's own visual rows (a negative instruction about the same video), one without is text-only (the video-free contrast)."""
+        eng = self.engine
+        if kw.get("negative_prompt_ids") is not None:
+            return [eng.embed_ids(r) for r in LP.negative_id_rows(kw["negative_prompt_ids"], kw.get("negative_prompt_attention_mask"))]
+        pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
+        out = []
+        for b, t in enumerate(kw["negative_prompts"]):
+            arr, m = P.left_pad_truncate([self.tokenizer_image_token(t)], pad_id, self.max_txt_len)
+            row = [int(x) for x, k in zip(arr[0], m[0]) if k]
+            if sum(1 for x in row if x == P.IMAGE_TOKEN_INDEX) > 1 or not row:
+                raise ValueError("generate(): a negative prompt holds at most one <image> slot and at least one token")
+            out.append(eng.splice(row, feats[b]) if P.IMAGE_TOKEN_INDEX in row else eng.embed_ids(row))
+        return out
+
+    def guided_generate_ids(self, ids_arr, mask, feats, negatives: Sequence[torch.Tensor], scale: float, max_new: int, processors=None, logprobs: Optional[int] = None,
+                            rules: Optional[int] = None, grammar: Optional[int] = None):
+        """generate_ids with classifier-free guidance: sample i is decoded against negatives[i] (embedding rows) at `scale`.  Each sample becomes a PAIR of sequences:
+        both are prefilled, Engine.seq_set_guidance binds them and re-selects the first token from the guided row, and the pairs decode together -- the negative
+        sequence is one more row of the leader's decode step (one weight stream for both).  Processors, rules, grammar, sampling and log-probabilities are the
+        conditional sequence's and apply to the guided row: both prefills run with every setting off (a prefill's last logits are the row its own selection saw, and guidance
+        needs the RAW rows), then the leader takes the call's processors, rule set `rules` and grammar `grammar`.  Returns what generate_ids returns."""
+        from .lib import GvlError, ERR_OOM
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        eng = self.engine
+        n = ids_arr.shape[0]
+        opts = [LP.SeqOptions(p if p is not None else LP.OFF, -1 if logprobs is None else logprobs, rules, grammar=grammar)
+                for p in (processors if isinstance(processors, (list, tuple)) else [processors] * n)]
+        out: List[List[int]] = []
+        lps = []
+        b = 0
+        while b < n:                                     # as many pairs at once as the KV pool holds
+            leaders, live = [], []
+            try:
+                while b + len(leaders) < n:
+                    i = b + len(leaders)
+                    emb = eng.splice([int(t) for t, m in zip(ids_arr[i], mask[i]) if m], feats[i])
+                    room = min(max_new, self.geo.max_seq - max(emb.shape[0], negatives[i].shape[0]))
+                    if room < 1:
+                        raise ValueError(f"generate(): sample {i}: the prompt (or its negative) leaves no room below max_seq {self.geo.max_seq}")
+                    try:
+                        s = eng.seq_alloc(emb.shape[0] + room); live.append(s)
+                        f = eng.seq_alloc(negatives[i].shape[0] + room); live.append(f)
+                    except GvlError as e:
+                        if e.status == ERR_OOM and leaders:
+                            if len(live) % 2:
+                                eng.seq_free(live.pop())
+                            break                      # pool full: run what fits, the rest in the next group
+                        raise
+                    LP.apply_seq_options(eng, s, LP.SeqOptions.OFF)
+                    LP.apply_seq_options(eng, f, LP.SeqOptions.OFF)     # the follower selects nothing: it is handed the leader's tokens
+                    lc, lu = eng.prefill(s, emb, want_logits=True), eng.prefill(f, negatives[i], want_logits=True)
+                    LP.apply_seq_options(eng, s, opts[i])
+                    eng.seq_set_guidance(s, f, scale, lc, lu)
+                    leaders.append(s)
+                got = eng.decode_greedy_batch(leaders, max_new, eos)
+                if logprobs is not None:
+                    lps += [eng.seq_read_logprobs(s_, 0, len(g), top=logprobs > 0) for s_, g in zip(leaders, got)]
+                out += got
+            finally:
+                for s in live[0::2]:                     # leaders first: freeing one unbinds its pair
+                    eng.seq_free(s)
+                for s in live[1::2]:
+                    eng.seq_free(s)
+            b += len(leaders)
+        return out if logprobs is None else (out, lps)
+
     def _n_visual(self, samples) -> int:
         return int(samples["spatial_pixel_values"].shape[1]) * self.engine.tokens_per_seg
 
@@ -345,9 +438,16 @@ class LLAVA_NEXT_VIDEO:
         grammar (extra): a grammar.Grammar (GrammarBuilder, grounding_grammar) that keeps every answer inside its language -- HF's PrefixConstrainedLogitsProcessor
         in HF's place (after the min-length ban, before forced eos), evaluated on the device at every step of greedy decoding, sampling and both beam_impls;
         log-probabilities are then those of the masked distribution.  prefix_allowed_tokens_fn itself raises ValueError: a Python callback cannot run inside the
-        decode loop.  Still not supported
+        decode loop.
+        guidance_scale (HF's; None or 1 = off): classifier-free guidance against a negative prompt, one per sample -- negative_prompt_ids (+ negative_prompt_attention_mask;
+        HF's names: plain token ids, a text-only negative sequence) or negative_prompts (extra: strings through the model's own prompt path; with the <image> slot
+        the negative sees the same video -- a negative instruction --, without it it is the video-free contrast).  Every step's scores are
+        scale * (log_softmax(conditional) - log_softmax(negative)) + log_softmax(negative), computed on the device IN FRONT of every processor, rule, grammar and
+        warper (HF's order), the first token included; the negative sequence is fed the token the conditional one selected and rides as one more row of the same
+        decode step.  Greedy and sampling; log-probabilities are then the guided distribution's.  guidance_scale != 1 without a negative prompt, with num_beams > 1,
+        or in generate_shared raises ValueError (not supported yet).  Still not supported
         and ignored: bad_words_ids=None, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
-        remove_invalid_values, exponential_decay_length_penalty, guidance_scale, diversity / constrained beams (num_beam_groups, constraints,
+        remove_invalid_values, exponential_decay_length_penalty, diversity / constrained beams (num_beam_groups, constraints,
         force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
         typical_p / epsilon_cutoff / eta_cutoff (those seven run on the device in HF's order; top_h, custom logits_warper lists stay ignored).
         return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
@@ -360,6 +460,7 @@ class LLAVA_NEXT_VIDEO:
             # rows appended with mask 0 so FSDP sees every parameter); the reference's inference never produces it.  forward() handles it.
             raise ValueError("generate(): 'text' samples are a training-only construct of the reference; use forward() for them")
         _beam_impl(generate_kwargs)                       # a bad beam_impl fails before any work
+        self._check_guidance(generate_kwargs, len(samples["prompts"]))     # ... and so do the guidance arguments
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
@@ -395,6 +496,10 @@ class LLAVA_NEXT_VIDEO:
             if scored:
                 lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
                 out_ids = [r[0] for r in out_ids]
+        elif self._check_guidance(generate_kwargs, ids_arr.shape[0]) is not None:      # classifier-free guidance: every sample decodes as a pair with its negative
+            res = self.guided_generate_ids(ids_arr, mask, feats, self._negative_embeds(generate_kwargs, feats), LP.resolve_guidance(generate_kwargs), max_new,
+                                           processors=procs, logprobs=opts.top_n if opts.top_n >= 0 else None, rules=rid, grammar=gid)
+            out_ids, lps = res if opts.top_n >= 0 else (res, None)
         elif opts.top_n >= 0:
             out_ids, lps = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs, logprobs=opts.top_n)
         else:
@@ -490,6 +595,8 @@ class LLAVA_NEXT_VIDEO:
         return_dict_in_generate / output_scores / top_logprobs as in generate()."""
         if samples["spatial_pixel_values"].shape[0] != 1:
             raise ValueError("generate_shared takes the pixel tensors of one video")
+        if LP.resolve_guidance(generate_kwargs) is not None:
+            raise ValueError("generate_shared(): guidance_scale != 1 is not supported yet (generate() takes it)")
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
         ids = [self.tokenizer_image_token(t) for t in prompts]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0

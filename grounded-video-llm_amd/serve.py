@@ -40,6 +40,13 @@ class _Request:
     opts: LP.SeqOptions = LP.SeqOptions()   # this request's settings (a field left alone: the engine's default); opts.rules holds its logits.TokenRules ...
     rules_id: Optional[int] = None   # ... and this their device rule set: created when the request is admitted, destroyed when it retires
     prefix: Optional[int] = None     # add_prefix() id whose rows are the first rows of embeds (None: prefill everything)
+    guidance: Optional[float] = None # classifier-free guidance scale (None: off) against ...
+    negative: object = None          # ... the negative prompt's embedding rows; neg_seq: its sequence, the follower of `seq` (Engine.seq_set_guidance)
+    neg_seq: int = -1
+
+    @property
+    def slots(self) -> int:          # a guided request holds two sequences, and two rows of every decode step
+        return 2 if self.guidance is not None else 1
 
 
 @dataclass
@@ -48,6 +55,10 @@ class _Prefix:
     rows: int                    # P, a multiple of 128
     queued: int = 0              # requests in the queue that name it
     dropped: bool = False
+
+
+class _Guided(Exception):
+    """_admit: a guided request's settings are applied after its prefill"""
 
 
 class ClipScheduler:
@@ -101,7 +112,7 @@ class ClipScheduler:
                begin_suppress_tokens=None, forced_eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
                top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
                epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None,
-               grammar: Optional[int] = None) -> int:
+               grammar: Optional[int] = None, guidance_scale: Optional[float] = None, negative=None) -> int:
         """Queue one request.  embeds: the full spliced prompt.  prefix: an add_prefix() id -- the caller promises that the prompt's first P rows ARE the registered
         ones; only embeds[P:] (at least one row) is then prefilled.  An optimisation only: the result is the same without it.  (It is ignored for a request that
         LongRoPE forbids to share: P <= rope_orig_max_pos < len(embeds) -- a full prefill of that prompt ropes the shared rows with the long factors.)
@@ -118,7 +129,19 @@ class ClipScheduler:
         sampled neighbours, or sampled with its own warpers.  Its ids are a function of its own settings and logits alone -- not of max_active,
         chunk, or the other requests.  None for all nine: the request follows the engine's setting (Engine.set_sampling).
         grammar: an Engine.grammar_create id that constrains THIS request's answer (the caller owns the grammar and destroys it after the request
-        retired); None: the sequence keeps the engine's default (Engine.set_grammar)."""
+        retired); None: the sequence keeps the engine's default (Engine.set_grammar).
+        guidance_scale / negative: HF's classifier-free guidance for THIS request (logits.resolve_guidance: None or 1 = off) against the negative prompt whose
+        embedding rows `negative` holds.  The request runs as a pair of sequences -- the negative one follows it as one more row of every decode step
+        (Engine.seq_set_guidance) -- so it counts as TWO toward max_active; its ids do not depend on its neighbours, max_active or chunk.  Not with prefix=.  Its own
+        settings are applied behind its prefill (guidance works on the raw first rows): engine-wide default processors, rules or a grammar must be off for it."""
+        guidance = LP.resolve_guidance(dict(guidance_scale=guidance_scale))
+        if guidance is not None:
+            if negative is None:
+                raise ValueError("guidance_scale != 1 needs `negative`: the embedding rows of the negative prompt")
+            if prefix is not None:
+                raise ValueError("a guided request cannot name a prefix")
+            if self.max_active < 2:
+                raise ValueError("a guided request counts as two toward max_active, which is 1")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
@@ -144,7 +167,8 @@ class ClipScheduler:
                 prefix = None
             else:
                 p.queued += 1
-        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling, ... if grammar is None else int(grammar)), prefix=prefix)
+        r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling, ... if grammar is None else int(grammar)), prefix=prefix,
+                     guidance=guidance, negative=negative if guidance is not None else None)
         self._next += 1
         self.queue.append(r)
         return r.rid
@@ -165,7 +189,7 @@ class ClipScheduler:
         finished = self._retire()                # a request can finish on its prefill token (eos first, or max_new == 1)
         if self.active:
             k = min([self.chunk] + [r.max_new - r.n_gen for r in self.active])
-            self.eng.decode_steps([r.seq for r in self.active], k)
+            self.eng.decode_steps([r.seq for r in self.active], k)          # (a guided request's follower is stepped with it: only leaders are named)
             self.stats["decode_chunks"] += 1
             self.stats["decode_seq_steps"] += k * len(self.active)
             for r in self.active:
@@ -186,7 +210,7 @@ class ClipScheduler:
     def _admit(self):
         new: List[_Request] = []
         rows = 0
-        while self.queue and len(self.active) + len(new) < self.max_active:
+        while self.queue and sum(q.slots for q in self.active + new) + self.queue[0].slots <= self.max_active:
             r = self.queue[0]
             S = int(r.embeds.shape[0])
             P = self.prefixes[r.prefix].rows if r.prefix is not None else 0     # rows the request does not prefill
@@ -194,6 +218,9 @@ class ClipScheduler:
                 break                                        # next iteration: keep the newcomers' prefill inside the workspace
             max_seq = getattr(getattr(self.eng, "geo", None), "max_seq", None)
             cap = S + r.max_new if max_seq is None else min(S + r.max_new, int(max_seq))
+            Sn = int(r.negative.shape[0]) if r.guidance is not None else 0
+            if max_seq is not None and Sn:                   # the follower needs as much room behind its prompt as the leader keeps
+                cap = min(cap, S + int(max_seq) - Sn)
             if cap < S:
                 raise ValueError(f"request {r.rid}: {S} prefill tokens exceed the engine's max_seq {max_seq}")
             try:
@@ -202,12 +229,24 @@ class ClipScheduler:
                 if getattr(e, "status", 0) == L.ERR_OOM:     # KV pages exhausted: wait for a retirement (FIFO, no overtaking)
                     break
                 raise
+            if r.guidance is not None:
+                try:
+                    r.neg_seq = self.eng.seq_alloc(Sn + cap - S)
+                except L.GvlError as e:
+                    self.eng.seq_free(r.seq)
+                    if getattr(e, "status", 0) == L.ERR_OOM:
+                        break
+                    raise
             try:
+                if r.guidance is not None:                   # its settings follow its prefill (below): guidance needs the raw first rows
+                    raise _Guided()
                 if r.opts.rules is not ... and r.opts.rules.active:    # an inactive set still overrides the engine's default: this request runs without rules
                     r.rules_id = self.eng.rules_create(r.opts.rules)
                 LP.apply_seq_options(self.eng, r.seq, r.opts if r.opts.rules is ... else replace(r.opts, rules=r.rules_id))
+            except _Guided:
+                pass
             except Exception:
-                self.eng.seq_free(r.seq)
+                self._free(r)
                 self._drop_rules(r)
                 raise
             r.max_new = min(r.max_new, cap - S + 1)          # generate() stops at the context limit (Engine.generate_ids does too)
@@ -219,17 +258,37 @@ class ClipScheduler:
                 self._release_prefix(r.prefix)
                 self.stats["prefix_rows_saved"] += P
                 r.embeds = r.embeds[P:]
+        plain = [r for r in new if r.guidance is None]
+        for r in new:                                        # a guided request: both prompts prefilled with their logits, then bound -- the first token is guided too
+            if r.guidance is not None:
+                lc, lu = self.eng.prefill(r.seq, r.embeds, want_logits=True), self.eng.prefill(r.neg_seq, r.negative, want_logits=True)
+                if r.opts.rules is not ... and r.opts.rules.active:
+                    r.rules_id = self.eng.rules_create(r.opts.rules)
+                LP.apply_seq_options(self.eng, r.seq, r.opts if r.opts.rules is ... else replace(r.opts, rules=r.rules_id))
+                self.eng.seq_set_guidance(r.seq, r.neg_seq, r.guidance, lc, lu)
+                r.negative = None
+                self.stats["prefill_calls"] += 1
+        if new:
+            self._prefill(plain)
+            for r in new:
+                r.n_gen = 1
+                r.embeds = None                              # the KV cache holds it now
+            self.active += new
+            self.stats["max_concurrent"] = max(self.stats["max_concurrent"], sum(r.slots for r in self.active))
+
+    def _free(self, r: _Request):
+        self.eng.seq_free(r.seq)                             # the leader first: freeing it unbinds the pair
+        if r.neg_seq >= 0:
+            self.eng.seq_free(r.neg_seq)
+            r.neg_seq = -1
+
+    def _prefill(self, new: List[_Request]):
         if new:
             if any(r.prefix is not None for r in new):       # one ragged pass for all newcomers, each behind its own prefix (none = empty)
                 self.eng.prefill_extend_batch([r.seq for r in new], [r.embeds for r in new])
             else:
                 self.eng.prefill_batch([r.seq for r in new], [r.embeds for r in new])
             self.stats["prefill_calls"] += 1
-            for r in new:
-                r.n_gen = 1
-                r.embeds = None                              # the KV cache holds it now
-            self.active += new
-            self.stats["max_concurrent"] = max(self.stats["max_concurrent"], len(self.active))
 
     def _release_prefix(self, pid: int):
         p = self.prefixes[pid]
@@ -256,7 +315,7 @@ class ClipScheduler:
             if stop or len(r.ids) >= r.max_new:
                 if r.opts.logprobs is not None:              # before the slot is freed: its lists are reused by the next sequence
                     self.done_logprobs[r.rid] = LP.read_seq_logprobs(self.eng, r.seq, r.ids, r.opts)
-                self.eng.seq_free(r.seq)                     # seq_read synchronised the stream: no step of r is in flight
+                self._free(r)                                # seq_read synchronised the stream: no step of r is in flight
                 self._drop_rules(r)
                 self.done[r.rid] = r.ids
                 finished.append(r.rid)

@@ -306,6 +306,32 @@ int gvl_grammar_create(gvl_ctx* ctx, const gvl_grammar_desc* desc, int* grammar_
 int gvl_grammar_destroy(gvl_ctx* ctx, int grammar_id);
 int gvl_set_grammar(gvl_ctx* ctx, int grammar_id);
 int gvl_seq_set_grammar(gvl_ctx* ctx, int seq_id, int grammar_id);
+/* Classifier-free guidance against a negative sequence: HF generate(guidance_scale=s, negative_prompt_ids=...), i.e. transformers'
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor.  Per step, with c = log_softmax(conditional logits) and u = log_softmax(negative logits),
+ *     row = s * (c - u) + u                       (fp32; one subtract, one multiply, one add, each rounded; the log-softmax is the fixed-order
+ *                                                  one the log-probabilities and beam search use: (l - max) - log(sum exp(l - max)))
+ * replaces the conditional row BEFORE everything else the library applies -- processors, token rules, grammar, warpers, selection, log-probabilities
+ * (which are then the guided distribution's) -- HF's order, where it is the first processor.  The negative sequence is fed the token the conditional
+ * one selected, every step; the first token is guided too.  Raw logits are FINITE by contract (lm_head rows are; a row holding -inf or NaN gives
+ * unspecified values, never an out-of-bounds access).
+ * gvl_seq_set_guidance binds the freshly prefilled conditional sequence seq_id (the LEADER) to the freshly prefilled negative one neg_seq_id (the
+ * FOLLOWER).  Preconditions: both live and distinct, each holding exactly the one token its own prefill selected, neither part of a pair, scale finite,
+ * the follower's remaining capacity (max_tokens - tokens held) >= the leader's; cond_logits / neg_logits are the two prefills' last_logits (device,
+ * fp32 [vocab], two different buffers) and are scratch for the call.  They must be the RAW rows: a prefill's last_logits are the row its own selection saw, so
+ * give the leader its processors, rules and grammar between its prefill and this call (settings that change no row -- sampling, log-probabilities -- may come first).  Otherwise GVL_ERR_ARG / GVL_ERR_STATE with a message, before anything runs.
+ * The call re-selects the FIRST token from the guided row with the leader's processors, rules, grammar, sampling and log-probability settings and
+ * writes it to both sequences; afterwards both stand exactly where a prefill that had selected from the guided row would have left them: n_gen 1,
+ * slot 0 = the guided token, the leader's log-probability slot 0 the guided distribution's, a sampled draw the one of (seed, stream, step 0).
+ * From then on the caller names ONLY the leader in gvl_decode_greedy / gvl_decode_greedy_batch / gvl_decode_steps: the follower rides as one more
+ * row of the same decode step (the weights stream once for both; a pair is never split across steps: up to 8 pairs, or any mix that fits 16 rows,
+ * share a step; on the VALU fallback a pair and a plain sequence run as 2 + 1).  One launch computes the guided rows in front of the processors
+ * and one after the selection hands the followers their tokens; a step without pairs takes exactly the launches it took before.  A pair leaves a
+ * decode together, when the leader hits eos / max_new / its capacity; the follower's own eos is never looked at and its ids (gvl_seq_read) are the
+ * leader's.  A leader's ids do not depend on the sequences it is decoded with.
+ * GVL_ERR_STATE, with nothing changed: a bound follower named in any decode, prefill-extend or score call, or freed; either member named in
+ * gvl_seq_fork, gvl_seq_clone, gvl_beam_search or gvl_decode_step_logits*.  neg_seq_id = -1 unbinds (the logits pointers and the scale are ignored),
+ * and so does gvl_seq_free of the leader; the follower lives on as a plain sequence and the caller frees it. */
+int gvl_seq_set_guidance(gvl_ctx* ctx, int seq_id, int neg_seq_id, float scale, float* cond_logits, float* neg_logits, void* stream);
 /* Log-probabilities of the selected tokens, computed on the device by the token-selection kernel itself (prefill's first token,
  * gvl_decode_greedy*, gvl_decode_steps; greedy and sampling alike; graph-replayed steps included).  The distribution is the one the token
  * was selected from: greedy, log_softmax of the row after the logits processors, (s_tok - m) - log(sum_i exp(s_i - m)); sampling, the
@@ -599,6 +625,10 @@ int gvl_op_select_logprobs(gvl_ctx* ctx, const float* logits, int n, int batch, 
  * may be null): 1 where an entry is finite and in the row's final kept set (a greedy row keeps every finite entry), else 0. */
 int gvl_op_select_rows(gvl_ctx* ctx, const float* logits, int n, int batch, const gvl_sampling* rows, const int32_t* steps_dev, const int* top_n,
                        int32_t* tokens_dev, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev, uint8_t* kept_dev, void* stream);
+/* The guidance kernel on its own (operator tests): logits f32 device, row r at logits + r * ld (ld >= n); pairs_host [n_pairs][2] = (conditional row, negative row),
+ * 1 .. 8 pairs, scales_host [n_pairs] finite.  Pair p's conditional row is overwritten with scales[p] * (c - u) + u as above; every other row is untouched.  A conditional
+ * row may not appear in another pair (GVL_ERR_ARG); a negative row may serve several. */
+int gvl_op_guidance(gvl_ctx* ctx, float* logits, int n, int ld, const int* pairs_host, int n_pairs, const float* scales_host, void* stream);
 /* gvl_score_extend_varlen's row kernel on its own (operator tests): `rows` rows (any number) of n fp32 logits, ld >= n floats apart, targets_dev [rows]; lp_dev / rank_dev
  * [rows] and, top_n 1 .. 8, top_ids_dev / top_lp_dev [rows][8] as described there (top_n = 0: untouched, may be NULL).  A target outside [0, n) never indexes its row:
  * lp = -inf, rank = -1. */

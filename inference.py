@@ -60,12 +60,16 @@ def parse_args(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=None, help="HF RepetitionPenaltyLogitsProcessor on the generated ids (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=None, help="HF NoRepeatNGramLogitsProcessor on the generated ids (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=None, help="HF MinNewTokensLengthLogitsProcessor: no eos before this many new ids")
+    p.add_argument("--guidance_scale", type=float, default=None, help="HF classifier-free guidance against --negative_prompt (None / 1 = off); not with --share_visual or --num_beams > 1")
+    p.add_argument("--negative_prompt", type=str, default=None, help="the negative prompt of --guidance_scale: with <image> it sees the same video, without it it is the video-free contrast")
     p.add_argument("--output_scores", action="store_true", help="print each answer's mean token log-prob and, for the grounding answer, every temporal token's probability")
     p.add_argument("--constrain_grounding", action="store_true", help="keep the grounding answer inside 'From <s> to <e>.' with s <= e (generate(grammar=...); not with --share_visual, whose one call answers all three prompts)")
     p.add_argument("--share_visual", type=_bool, default=False, help="encode the video ONCE for the three prompts and batch them (the reference re-encodes per prompt)")
     p.add_argument("--synthetic", action="store_true", help="seeded random weights / frames / tokenizer (offline image)")
     p.add_argument("--synthetic_scale", type=str, default="small", choices=["small", "full"])
     args = p.parse_args(argv)
+    if args.guidance_scale not in (None, 1.0) and (args.negative_prompt is None or args.share_visual or args.num_beams > 1):
+        p.error("--guidance_scale needs --negative_prompt and works with neither --share_visual nor --num_beams > 1")
     if args.constrain_grounding and args.share_visual:
         p.error("--constrain_grounding constrains the grounding answer only: it cannot be combined with --share_visual")
     return args
@@ -149,6 +153,8 @@ def main(argv=None):
     for name in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"):     # forwarded only when given, like any other HF generate kwarg
         if getattr(args, name) is not None:
             kw[name] = getattr(args, name)
+    if args.guidance_scale not in (None, 1.0):
+        kw.update(guidance_scale=args.guidance_scale, negative_prompts=[args.negative_prompt])
     if args.output_scores:
         kw.update(return_dict_in_generate=True, output_scores=True)
     outs, scored = {}, {}
