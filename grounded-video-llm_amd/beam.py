@@ -11,7 +11,7 @@ Semantics kept from 4.40.1 (batch of one, one beam group):
     next running beams;
   * the search is done when k hypotheses exist and (early_stopping, or the worst of them is at least the best running
     sum-log-prob / cur_len ** length_penalty); at max_new_tokens the running beams are added as hypotheses;
-  * the answer is the best hypothesis, with eos appended when it ended by eos.
+  * the answer is the best hypothesis (num_return > 1: the num_return best, best first), with eos appended when it ended by eos.
 
 Beam-SAMPLE (`generate(num_beams=k, do_sample=True)`; reachable from inference.py:45-49,170-176; 4.40.1 GenerationMixin._beam_sample): the same
 bookkeeping, but the 2k candidates of a step are DRAWN: every running beam's log-softmax goes through the warpers (temperature -> top-k ->
@@ -106,7 +106,8 @@ def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[
 def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logits: torch.Tensor, num_beams: int, max_new_tokens: int,
                 eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None,
                 process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None, with_scores: bool = False,
-                candidates: Optional[Callable[[torch.Tensor, torch.Tensor], Tuple[Sequence[float], Sequence[int], Sequence[float]]]] = None):
+                candidates: Optional[Callable[[torch.Tensor, torch.Tensor], Tuple[Sequence[float], Sequence[int], Sequence[float]]]] = None,
+                num_return: int = 1):
     """first_logits [vocab]: logits after the prompt.  step(parents, tokens) -> logits [k, vocab] of the k new running beams, where new beam j
     continues old beam parents[j] with tokens[j] (the caller reorders its KV cache accordingly; at the first call every parent is 0 = the
     prompt).  Returns the NEW ids of the best hypothesis (eos included when it ended by eos), as HF does for inputs_embeds prompts.
@@ -120,10 +121,15 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     the beam score was added -- tracked per running beam through the parent chain.
     candidates (beam search only): a callable (processed rows [k, vocab], beam scores [k]) -> (vals, idxs, proc_vals), the step's 2k candidates best first -- value
     (processed log-probability + beam score), flat index beam * vocab + token, the processed log-probability alone.  It replaces the torch top-2k below and the
-    gather of the transition scores: Engine.op_beam_candidates (the library's own kernels) plugs in here, and tests record every step's list through it."""
+    gather of the transition scores: Engine.op_beam_candidates (the library's own kernels) plugs in here, and tests record every step's list through it.
+    num_return (1 .. num_beams; HF num_return_sequences with beams, BeamSearchScorer.finalize's num_beam_hyps_to_keep): > 1 returns a LIST of results, the num_return
+    best hypotheses, best first -- among equal scores the later added first; beam search and beam-sample alike.  1 returns the one result, as ever."""
     k = int(num_beams)
     if k < 2:
         raise ValueError("beam_search needs num_beams >= 2")
+    n_ret = int(num_return)
+    if n_ret < 1 or n_ret > k:
+        raise ValueError("num_return must be 1 .. num_beams")
     V = first_logits.shape[-1]
     if V < 2 * k:
         raise ValueError("vocabulary smaller than 2 x num_beams")
@@ -191,15 +197,12 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     if not done:
         for j in range(k):                                   # finalize(): the open beams become hypotheses
             hyps.add(seqs[j], float(scores[j]), len(seqs[j]), False, tsc[j])
-    best = max(hyps.beams, key=lambda x: x[0]) if hyps.beams else (0.0, seqs[0], False, tsc[0])
-    # python's sort is stable and HF takes sorted(...)[-1]: among equal scores the LAST added wins
-    top_score = best[0]
-    for h in hyps.beams:
-        if h[0] == top_score:
-            best = h
-    out = list(best[1])
-    if best[2] and eos_id is not None and len(out) < max_new_tokens:
-        out.append(eos_id)
-    if with_scores:
-        return out, float(best[0]), list(best[3])[:len(out)]
-    return out
+    # HF's finalize: sorted(beams, key=score) is stable and hypotheses are popped from its end -- best first, among equal scores the LATER added first
+    ranked = sorted(hyps.beams, key=lambda x: x[0])[::-1] if hyps.beams else [(0.0, seqs[0], False, tsc[0])]
+    results = []
+    for best in ranked[:n_ret]:
+        out = list(best[1])
+        if best[2] and eos_id is not None and len(out) < max_new_tokens:
+            out.append(eos_id)
+        results.append((out, float(best[0]), list(best[3])[:len(out)]) if with_scores else out)
+    return results[0] if n_ret == 1 else results

@@ -120,22 +120,41 @@ struct BeamState {
     return BEAM_CONTINUE;
   }
 
-  // The best hypothesis after BEAM_FINISHED: its new ids (eos included when it ended by eos and there is room), its score, one transition score per id
-  void finalize(std::vector<int>* ids, double* score, std::vector<float>* transition) {
+  // The n best hypotheses after BEAM_FINISHED (BeamSearchScorer.finalize with num_beam_hyps_to_keep = n, 1 <= n <= k; call it once): popped from
+  // sorted(beams, key = score), best first -- among equal scores the LATER added comes first.  Per hypothesis: its new ids (eos included when it ended by eos and there
+  // is room), its score, one transition score per id.  Returns how many were written (n; fewer only if fewer hypotheses exist).
+  int finalize_n(int n, std::vector<std::vector<int>>* ids, std::vector<double>* score, std::vector<std::vector<float>>* transition) {
     if (!done) for (int j = 0; j < k; ++j) hyps.add(seqs[j], (double)scores[j], (int)seqs[j].size(), false, tsc[j]);
-    Hyp best; best.ids = seqs[0]; best.token_scores = tsc[0];
-    if (!hyps.beams.empty()) {
-      size_t bi = 0;
-      for (size_t i = 1; i < hyps.beams.size(); ++i) if (hyps.beams[i].score >= hyps.beams[bi].score) bi = i;   // >=: among equal scores the last added wins
-      best = hyps.beams[bi];
+    std::vector<size_t> order(hyps.beams.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    // descending score, the later added first among equals: the reverse of Python's stable ascending sort
+    for (size_t i = 1; i < order.size(); ++i)
+      for (size_t j = i; j > 0 && (hyps.beams[order[j]].score > hyps.beams[order[j - 1]].score ||
+                                   (hyps.beams[order[j]].score == hyps.beams[order[j - 1]].score && order[j] > order[j - 1])); --j) { const size_t t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+    if (n < 1) n = 1;
+    const int m = n < (int)order.size() ? n : (int)order.size();
+    if (ids) ids->clear();
+    if (score) score->clear();
+    if (transition) transition->clear();
+    for (int r = 0; r < m; ++r) {
+      const Hyp& h = hyps.beams[order[r]];
+      std::vector<int> out = h.ids;
+      if (h.by_eos && eos >= 0 && (int)out.size() < max_new) out.push_back(eos);
+      std::vector<float> ts = h.token_scores;
+      if (ts.size() > out.size()) ts.resize(out.size());
+      if (ids) ids->push_back(out);
+      if (score) score->push_back(h.score);
+      if (transition) transition->push_back(ts);
     }
-    std::vector<int> out = best.ids;
-    if (best.by_eos && eos >= 0 && (int)out.size() < max_new) out.push_back(eos);
-    std::vector<float> ts = best.token_scores;
-    if (ts.size() > out.size()) ts.resize(out.size());
-    if (ids) *ids = out;
-    if (score) *score = best.score;
-    if (transition) *transition = ts;
+    return m;
+  }
+  // The best hypothesis alone: finalize_n(1)
+  void finalize(std::vector<int>* ids, double* score, std::vector<float>* transition) {
+    std::vector<std::vector<int>> i1; std::vector<double> s1; std::vector<std::vector<float>> t1;
+    if (finalize_n(1, &i1, &s1, &t1) < 1) { i1.assign(1, seqs[0]); s1.assign(1, 0.0); t1.assign(1, tsc[0]); }
+    if (ids) *ids = i1[0];
+    if (score) *score = s1[0];
+    if (transition) *transition = t1[0];
   }
 };
 

@@ -75,9 +75,15 @@ int gvl_op_beam_normalize(gvl_ctx* ctx, float* rows, int n, int k, void* stream)
 
 int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_beam_params* p, int32_t* out_ids_host, int cap, int* n_out, double* sequences_score,
                     float* transition_scores_host, void* stream) {
+  return gvl_beam_search_n(ctx, seq_id, first_logits, p, 1, out_ids_host, cap, n_out, sequences_score, transition_scores_host, stream);
+}
+// the search itself; the num_return best hypotheses leave through BeamState::finalize_n (messages name gvl_beam_search: one search, two entry points)
+int gvl_beam_search_n(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_beam_params* p, int num_return, int32_t* out_ids_host, int cap, int* n_out,
+                      double* sequences_scores, float* transition_scores_host, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_beam_search");
   if (!p || !first_logits || !out_ids_host || !n_out) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: bad arguments");
   const int k = p->num_beams, V = ctx->cfg.vocab, max_new = p->max_new_tokens;
+  if (num_return < 1 || num_return > k) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: num_return must be 1 .. num_beams");
   if (k < 2 || k > GVL_MAX_DECODE_BATCH) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: num_beams must be 2 .. 16");
   if (V < 2 * k) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: vocabulary smaller than 2 x num_beams");
   if (!shape_ok(V, k)) return fail(ctx, GVL_ERR_ARG, "gvl_beam_search: num_beams x vocabulary must fit an int32");
@@ -186,13 +192,16 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
     rows = one_part ? ctx->d_logits : ctx->d_beam_rows; stride = V; n_rows = k;
   }
 
-  std::vector<int> ids; double score = 0.0; std::vector<float> ts;
-  bs.finalize(&ids, &score, &ts);
-  const int n = (int)ids.size();                          // <= max_new <= cap
-  for (int i = 0; i < n; ++i) out_ids_host[i] = ids[i];
-  *n_out = n;
-  if (sequences_score) *sequences_score = score;
-  if (transition_scores_host) for (int i = 0; i < n && i < (int)ts.size(); ++i) transition_scores_host[i] = ts[i];
+  std::vector<std::vector<int>> ids; std::vector<double> score; std::vector<std::vector<float>> ts;
+  const int got = bs.finalize_n(num_return, &ids, &score, &ts);
+  if (got < num_return) return fail(ctx, GVL_ERR_STATE, "gvl_beam_search: fewer hypotheses than num_return");
+  for (int r = 0; r < num_return; ++r) {
+    const int n = (int)ids[r].size();                     // <= max_new <= cap
+    for (int i = 0; i < n; ++i) out_ids_host[(size_t)r * cap + i] = ids[r][i];
+    n_out[r] = n;
+    if (sequences_scores) sequences_scores[r] = score[r];
+    if (transition_scores_host) for (int i = 0; i < n && i < (int)ts[r].size(); ++i) transition_scores_host[(size_t)r * cap + i] = ts[r][i];
+  }
   return 0;
 }
 

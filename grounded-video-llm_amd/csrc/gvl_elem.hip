@@ -938,6 +938,39 @@ int gvl_launch_kv_page_copy(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, s
   hipLaunchKernelGGL(kv_page_copy_kernel, dim3(layers, 2), dim3(256), 0, st, kpool, vpool, layer_stride, page_elems, src_page, dst_page);
   return CHECK_LAUNCH();
 }
+// gvl_seq_fanout: the source's partial last page into the private page of every sibling -- block (layer, K | V^T, sibling), ONE launch for all of them.  The source
+// page is read-only here and no two siblings share a destination, so the blocks are independent.
+__global__ __launch_bounds__(256) void kv_page_fanout_kernel(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int src_page, FanoutArgs a) {
+  bf16_t* pool = blockIdx.y == 0 ? kpool : vpool;
+  const u32x4_t* s = (const u32x4_t*)(pool + (size_t)blockIdx.x * layer_stride + (size_t)src_page * page_elems);
+  u32x4_t* d = (u32x4_t*)(pool + (size_t)blockIdx.x * layer_stride + (size_t)a.dst_page[blockIdx.z] * page_elems);
+  for (size_t i = threadIdx.x; i < page_elems / 8; i += 256) d[i] = s[i];
+}
+int gvl_launch_kv_page_fanout(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int layers, int n_pages, int src_page, const FanoutArgs& a, hipStream_t st) {
+  if (layers < 1 || (page_elems & 7) || a.n < 1 || a.n > GVL_MAX_DECODE_BATCH || src_page < 0 || src_page >= n_pages) return -1;
+  for (int i = 0; i < a.n; ++i) {
+    if (a.dst_page[i] < 0 || a.dst_page[i] >= n_pages || a.dst_page[i] == src_page) return -1;
+    for (int j = 0; j < i; ++j) if (a.dst_page[j] == a.dst_page[i]) return -1;
+  }
+  hipLaunchKernelGGL(kv_page_fanout_kernel, dim3(layers, 2, a.n), dim3(256), 0, st, kpool, vpool, layer_stride, page_elems, src_page, a);
+  return CHECK_LAUNCH();
+}
+// ... and the siblings' counters and logits rows in one launch: block (chunk, sibling) copies its part of the source's row `src` [n] to rows + sibling * n (the selection
+// kernels take rows n floats apart); block (0, sibling) also sets the sibling's position and zeroes its generation count, which the selection behind it advances to 1
+__global__ __launch_bounds__(256) void fanout_rows_kernel(const float* __restrict__ src, float* __restrict__ rows, int n, int pos, FanoutArgs a) {
+  const int b = blockIdx.y;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { *a.pos[b] = pos; *a.ngen[b] = 0; }
+  float* d = rows + (size_t)b * n;
+  if (d == src) return;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = src[i];
+}
+int gvl_launch_fanout_rows(const float* src, float* rows, int n, int pos, const FanoutArgs& a, hipStream_t st) {
+  if (!src || !rows || n < 1 || pos < 1 || a.n < 1 || a.n > GVL_MAX_DECODE_BATCH) return -1;
+  for (int i = 0; i < a.n; ++i) if (!a.pos[i] || !a.ngen[i]) return -1;
+  int blocks = (n + 255) / 256; if (blocks > 64) blocks = 64;
+  hipLaunchKernelGGL(fanout_rows_kernel, dim3(blocks, a.n), dim3(256), 0, st, src, rows, n, pos, a);
+  return CHECK_LAUNCH();
+}
 __global__ void set_int_kernel(int* p, int v) { if (threadIdx.x == 0) *p = v; }
 int gvl_launch_set_int(int* p, int v, hipStream_t st) {
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, st, p, v);

@@ -439,6 +439,12 @@ int gvl_launch_embed_norm(const bf16_t* table, const TokPtrs& toks, bf16_t* x, b
 // xn (B-operand tile order) = rmsnorm(x[b]) * w for the row-major residual rows x [batch][cols]: one wave per sequence (gvl_decode.hip)
 int gvl_launch_norm_tiled(bf16_t* x, bf16_t* xn, const bf16_t* w, int batch, int cols, float eps, hipStream_t st);
 int gvl_launch_kv_page_copy(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int layers, int src_page, int dst_page, hipStream_t st);
+// gvl_seq_fanout (gvl_elem.hip): sibling i's private page, position and generation-count words, by value.  kv_page_fanout copies page src_page of every layer's K and V^T
+// to every dst_page[i] in ONE launch (pages distinct, none the source, all < n_pages: checked by the launcher); fanout_rows copies the fp32 row src [n] to
+// rows + i * n (a row that IS src is left alone) and sets *pos[i] = pos, *ngen[i] = 0, one launch for all siblings.
+struct FanoutArgs { int n; int dst_page[GVL_MAX_DECODE_BATCH]; int* pos[GVL_MAX_DECODE_BATCH]; int* ngen[GVL_MAX_DECODE_BATCH]; };
+int gvl_launch_kv_page_fanout(bf16_t* kpool, bf16_t* vpool, size_t layer_stride, size_t page_elems, int layers, int n_pages, int src_page, const FanoutArgs& a, hipStream_t st);
+int gvl_launch_fanout_rows(const float* src, float* rows, int n, int pos, const FanoutArgs& a, hipStream_t st);
 int gvl_launch_set_int(int* p, int v, hipStream_t st);
 int gvl_launch_copy_ints(const int* src, int* dst, int n, hipStream_t st);   // n 4-byte words, device -> device, any alignment (a clone's generated ids)
 

@@ -79,6 +79,11 @@ static int pick_tokens_rows(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipSt
     const int rc = gvl_launch_logits_process(lp, st);
     if (rc) return rc;
   }
+  return select_tokens(ctx, am, sqs, st);
+}
+// the selection alone, on rows that ARE processed already (gvl_seq_fanout selects its siblings' first tokens from the row the source's prefill processed: a second
+// application would show -- sequence_bias is not idempotent)
+int select_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
   for (int b = 0; b < am.batch; ++b) {             // log-probabilities (gvl_seq_set_logprobs): the sequence's slot lists, indexed by its device-side count
     const Seq& q = *sqs[b];
     if (q.sel.top_n < 0 || !q.d_lp) continue;

@@ -14,14 +14,16 @@ inline int fail(gvl_ctx* c, int code, const std::string& msg) { return gvl_fail(
 // a SeqStatus of the sequence table (gvl_seq_table.h) as the result of entry point `fn`: 0, or the status's error
 inline int seq_fail(gvl_ctx* c, const char* fn, int status) {
   if (status >= 0) return 0;
-  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_FOLLOWER
+  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_PAIRED
     {GVL_ERR_ARG, "bad seq"}, {GVL_ERR_ARG, "duplicate seq"}, {GVL_ERR_OOM, "KV pages exhausted"}, {GVL_ERR_OOM, "too many live sequences"}, {GVL_ERR_ARG, "no such rule set"},
     {GVL_ERR_STATE, "the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)"},
     {GVL_ERR_ARG, "too many live rule sets (limit 1024)"}, {GVL_ERR_ARG, "no such grammar"},
     {GVL_ERR_STATE, "the grammar is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_grammar(-1) first)"},
     {GVL_ERR_ARG, "too many live grammars (limit 64)"},
-    {GVL_ERR_STATE, "the sequence follows a guided leader (gvl_seq_set_guidance): free or unbind the leader first"}};
-  const auto& x = e[status >= SEQ_FOLLOWER ? -1 - status : 0];
+    {GVL_ERR_STATE, "the sequence follows a guided leader (gvl_seq_set_guidance): free or unbind the leader first"},
+    {GVL_ERR_STATE, "the sequence must be freshly prefilled (exactly the one token its own prefill selected)"},
+    {GVL_ERR_STATE, "the sequence is a member of a guided pair (gvl_seq_set_guidance)"}};
+  const auto& x = e[status >= SEQ_PAIRED ? -1 - status : 0];
   return fail(c, x.code, std::string(fn) + ": " + x.text);
 }
 
@@ -109,6 +111,8 @@ int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);
 // pairs (null: none): the guidance launch in front of the processors and the followers' commit behind the selection -- a group without pairs takes neither
 int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st, const PairLaunches* pairs = nullptr);
+// what pick_tokens does behind the processors / rules / grammar launch: log-probability lists, per-row or ctx sampling, the selection launch
+int select_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
 // the rows of one step for `n` named sequences (plain ones and leaders): rows[] = the named ones in order, then the leaders' followers in order; returns how many
 int step_rows(gvl_ctx* ctx, Seq* const* named, int n, Seq** rows);
 // one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan

@@ -529,6 +529,46 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
   Seq* src = ctx ? ctx->lookup(src_seq) : nullptr;
   return seq_clone(ctx, src_seq, max_tokens, dst_seq, (hipStream_t)stream, src && src->sel.grammar >= 0);
 }
+
+// n_new siblings of a freshly prefilled sequence: n answers to one prompt from ONE prefill.  The table operation opens all of them or none (SeqTable::fanout); behind it
+// three launches serve every sibling at once -- the partial last page (kv_page_fanout_kernel; none when the prompt ends on a page boundary), positions, counters and the
+// logits rows (fanout_rows_kernel), and the first tokens (select_tokens: warpers and draw only -- first_logits is the row the source's prefill PROCESSED, and at step 0
+// every sibling's processed row is that row).  Everything is checked before the first launch.
+int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const uint32_t* streams, float* first_logits, int* dst_seqs, void* stream) {
+  REQUIRE_READY(ctx->has_llm, "gvl_seq_fanout");
+  if (!streams || !first_logits || !dst_seqs) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: streams, first_logits and dst_seqs are needed");
+  if (!ctx->lookup(src_seq)) return seq_fail(ctx, "gvl_seq_fanout", SEQ_BAD);
+  if (n_new < 1 || n_new > GVL_MAX_DECODE_BATCH - 1) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: n_new must be 1 .. " + std::to_string(GVL_MAX_DECODE_BATCH - 1) + " (repeat the call for more)");
+  const int pos = ctx->seqs[src_seq].pos, V = ctx->cfg.vocab;
+  if (max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: max_tokens must exceed the source's tokens and fit cfg.max_seq");
+  if (first_logits >= ctx->d_logits && first_logits < ctx->d_logits + (size_t)GVL_MAX_DECODE_BATCH * V && (first_logits - ctx->d_logits) % V != 0)
+    return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: first_logits overlaps the library's work rows");
+  Sampling followed;                                  // the ctx setting as a sequence's own (the stream is the sibling's)
+  { const auto& q = ctx->sample;
+    followed.on = q.on; followed.inv_temp = q.inv_temp; followed.top_k = q.top_k; followed.top_p = q.top_p; followed.min_p = q.min_p; followed.typical_p = q.typical_p;
+    followed.eps = q.eps; followed.eta = q.eta; followed.seed = q.seed; }
+  int ids[GVL_MAX_DECODE_BATCH];
+  { const int rc = ctx->fanout(src_seq, n_new, max_tokens, followed, streams, ids); if (rc < 0) return seq_fail(ctx, "gvl_seq_fanout", rc); }
+  hipStream_t st = (hipStream_t)stream;
+  Seq* sqs[GVL_MAX_DECODE_BATCH];
+  FanoutArgs fa; memset(&fa, 0, sizeof(fa)); fa.n = n_new;
+  for (int i = 0; i < n_new; ++i) {
+    Seq& s = ctx->seqs[ids[i]];
+    bind_slot(ctx, s, ids[i]);
+    sqs[i] = &s; fa.pos[i] = s.d_pos; fa.ngen[i] = s.d_ngen;
+    if (pos & 63) fa.dst_page[i] = s.pages[pos >> 6];
+  }
+  for (int i = 0; i < n_new; ++i) { const int rc = upload_table(ctx, *sqs[i], st); if (rc) return rc; }   // by value, on the call's stream: ordered behind the source's prefill there
+  if (pos & 63)                                       // the partial last page is private: the source's into every sibling's (all layers, K and V^T), one launch
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_fanout(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers, ctx->kv_total_pages,
+                                                     ctx->seqs[src_seq].pages[pos >> 6], fa, st));
+  RUN(GVL_PROF_OTHER, 0, gvl_launch_fanout_rows(first_logits, ctx->d_logits, V, pos, fa, st));
+  ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = ctx->d_logits; am.n = V; am.batch = n_new;
+  for (int i = 0; i < n_new; ++i) { am.tok_ptrs[i] = sqs[i]->d_tok; am.out_lists[i] = sqs[i]->d_out; am.ngen_ptrs[i] = sqs[i]->d_ngen; }
+  RUN(GVL_PROF_OTHER, 0, select_tokens(ctx, am, sqs, st));
+  for (int i = 0; i < n_new; ++i) dst_seqs[i] = ids[i];
+  return 0;
+}
 }  // extern "C"
 
 int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated) {

@@ -35,7 +35,7 @@ struct SeqCore {
   int lead = -1, follow = -1; float guide = 1.0f;
 };
 enum SeqStatus { SEQ_OK = 0, SEQ_BAD = -1, SEQ_DUPLICATE = -2, SEQ_NO_PAGES = -3, SEQ_TOO_MANY = -4, SEQ_NO_RULES = -5, SEQ_RULES_BUSY = -6, SEQ_RULES_FULL = -7,
-                 SEQ_NO_GRAMMAR = -8, SEQ_GRAMMAR_BUSY = -9, SEQ_GRAMMAR_FULL = -10, SEQ_FOLLOWER = -11 };
+                 SEQ_NO_GRAMMAR = -8, SEQ_GRAMMAR_BUSY = -9, SEQ_GRAMMAR_FULL = -10, SEQ_FOLLOWER = -11, SEQ_NOT_FRESH = -12, SEQ_PAIRED = -13 };
 
 template <class S = SeqCore>
 struct SeqTable {
@@ -70,6 +70,30 @@ struct SeqTable {
     for (int i = shared; i < np; ++i) { s.pages.push_back(free_pages.back()); free_pages.pop_back(); page_ref[s.pages.back()] = 1; }
     if (id == (int)seqs.size()) seqs.push_back(std::move(s)); else seqs[id] = std::move(s);
     return id;
+  }
+  // gvl_seq_fanout: n_new siblings of the freshly prefilled `src` (n_gen == 1: it holds the one token its own prefill selected) -> their ids in ids[0 .. n_new), or a
+  // negative SeqStatus with NOTHING changed -- all siblings open or none does, slots and pages alike.  A sibling is a clone of the source at its current length (whole
+  // pages shared, later pages its own) with the source's settings, except that it takes the source's EFFECTIVE sampling -- the source's own setting, else `followed`
+  // (the table-wide one at the time of the call, which the caller keeps) -- as a setting of its own, drawing from random stream streams[i].  n_gen = 1: a sibling
+  // stands where its own prefill would have left it, its first token selected by the caller from the source's row.
+  int fanout(int src, int n_new, int max_tokens, const Sampling& followed, const unsigned* streams, int* ids) {
+    const S* s = lookup(src);
+    if (!s || n_new < 1 || !streams || !ids || s->pos <= 0 || max_tokens <= s->pos) return SEQ_BAD;
+    if (s->lead >= 0 || s->follow >= 0) return SEQ_PAIRED;
+    if (s->n_gen != 1) return SEQ_NOT_FRESH;
+    const int pos = s->pos, own_pages = (max_tokens + 63) / 64 - (pos >> 6);
+    if ((long long)free_pages.size() < (long long)n_new * own_pages) return SEQ_NO_PAGES;
+    int slots = max_seqs - (int)seqs.size();
+    for (const S& q : seqs) slots += !q.used;
+    if (slots < n_new) return SEQ_TOO_MANY;
+    Sampling eff = s->sel.own_sampling ? s->sel.sampling : followed;   // by value: open() may move the source
+    for (int i = 0; i < n_new; ++i) {
+      ids[i] = open(max_tokens, src, pos);             // cannot fail: pages and slots were counted above
+      eff.stream = streams[i];
+      set_sampling(seqs[ids[i]].sel, &eff);
+      seqs[ids[i]].n_gen = 1;
+    }
+    return SEQ_OK;
   }
   // the sequence's pages, rule set and grammar go back; a page shared with a fork lives on until its last holder is closed.  A bound follower is refused with nothing
   // changed (its leader's steps write its pages); closing a leader unbinds the pair, and the follower lives on as a plain sequence

@@ -340,6 +340,20 @@ class Engine:
         self._chk(self.lib.gvl_seq_clone(self.ctx, int(src), int(max_tokens), C.byref(sid), self.stream), "gvl_seq_clone")
         return sid.value
 
+    def seq_fanout(self, seq: int, n_new: int, max_tokens: int, streams: Sequence[int], first_logits: torch.Tensor) -> List[int]:
+        """n_new siblings of the freshly prefilled `seq` (gvl_seq_fanout): n answers to one prompt from ONE prefill.  first_logits: that prefill's logits
+        (prefill(..., want_logits=True)); streams: the random stream of every sibling.  A sibling shares the prompt's whole KV pages, copies the source's settings with the
+        source's effective sampling as its own on stream streams[i], and holds its own first token, drawn from first_logits: decode source and siblings together.
+        All or nothing: a refusal (GvlError) leaves every sequence and the pool as they were."""
+        n_new = int(n_new)
+        if len(streams) != n_new:
+            raise ValueError("seq_fanout: one stream per sibling")
+        assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.numel() == self.geo.vocab and first_logits.device == self.device
+        st = (C.c_uint32 * max(n_new, 1))(*[int(x) & 0xFFFFFFFF for x in streams])
+        out = (C.c_int * max(n_new, 1))()
+        self._chk(self.lib.gvl_seq_fanout(self.ctx, int(seq), n_new, int(max_tokens), st, _ptr(first_logits), out, self.stream), "gvl_seq_fanout")
+        return [int(out[i]) for i in range(n_new)]
+
     def prefill_extend(self, seq: int, embeds_new: torch.Tensor, want_logits: bool = False) -> Optional[torch.Tensor]:
         """Prefill of the rows that FOLLOW a forked prefix (gvl_prefill_extend): positions prefix .. prefix + n - 1, attention over prefix + new rows."""
         embeds_new = embeds_new.contiguous()
@@ -538,23 +552,32 @@ class Engine:
         return rows
 
     def beam_search(self, seq: int, first_logits: torch.Tensor, num_beams: int, max_new: int, eos: Optional[int], length_penalty: float = 1.0, early_stopping=False,
-                    processors=None, rules: Optional[int] = None, with_scores: bool = False):
+                    processors=None, rules: Optional[int] = None, with_scores: bool = False, num_return: int = 1):
         """gvl_beam_search: HF beam search (num_beams = k, do_sample = False) from the PREFILLED sequence `seq` and its prefill logits, inside the library; `seq` is not
         consumed.  processors: a logits.Processors (None = off); rules: a rule-set id (None = none); early_stopping: False / True / "never".  Returns the new ids, or with
-        with_scores (ids, sequences_score, transition_scores) as beam.beam_search does."""
+        with_scores (ids, sequences_score, transition_scores) as beam.beam_search does.  num_return > 1 (gvl_beam_search_n): a list of such results, the num_return best
+        hypotheses, best first."""
         if early_stopping not in (False, True, "never"):
             raise ValueError("early_stopping must be False, True or 'never'")
         assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.device == self.device
         pe, ng, mn, pe_eos = processors.args() if processors is not None else (1.0, 0, 0, None)
         prm = L.GvlBeamParams(int(num_beams), int(max_new), -1 if eos is None else int(eos), float(length_penalty), {False: 0, True: 1, "never": 2}[early_stopping],
                               float(pe), int(ng), int(mn), -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
-        cap = max(int(max_new), 1)
-        ids = (C.c_int32 * cap)()
-        ts = (C.c_float * cap)()
-        n, score = C.c_int(0), C.c_double(0.0)
-        self._chk(self.lib.gvl_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, C.byref(n), C.byref(score), ts, self.stream), "gvl_beam_search")
-        out = [int(ids[i]) for i in range(n.value)]
-        return (out, score.value, [float(ts[i]) for i in range(n.value)]) if with_scores else out
+        cap, nr = max(int(max_new), 1), int(num_return)
+        if nr < 1 or nr > int(num_beams):
+            raise ValueError("num_return must be 1 .. num_beams")
+        ids = (C.c_int32 * (cap * nr))()
+        ts = (C.c_float * (cap * nr))()
+        n, score = (C.c_int * nr)(), (C.c_double * nr)()
+        if nr == 1:
+            self._chk(self.lib.gvl_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, n, score, ts, self.stream), "gvl_beam_search")
+        else:
+            self._chk(self.lib.gvl_beam_search_n(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), nr, ids, cap, n, score, ts, self.stream), "gvl_beam_search_n")
+        res = []
+        for r in range(nr):
+            out = [int(ids[r * cap + i]) for i in range(n[r])]
+            res.append((out, score[r], [float(ts[r * cap + i]) for i in range(n[r])]) if with_scores else out)
+        return res[0] if nr == 1 else res
 
     def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None,
                      rules: Optional[int] = None, grammar: Optional[int] = None):

@@ -134,6 +134,7 @@ _SIGS = {
     "gvl_seq_free": (C.c_int, [C.c_void_p, C.c_int]),
     "gvl_seq_fork": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "gvl_seq_clone": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "gvl_seq_fanout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gvl_prefill_extend": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gvl_prefill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gvl_decode_greedy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.c_void_p]),
@@ -211,6 +212,8 @@ _SIGS = {
     "gvl_trace_marker": (C.c_int, [C.c_int, C.c_void_p]),
     "gvl_beam_search": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GvlBeamParams), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_float), C.c_void_p]),
+    "gvl_beam_search_n": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GvlBeamParams), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_float), C.c_void_p]),
     "gvl_op_beam_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvl_op_beam_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "gvl_op_gemv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

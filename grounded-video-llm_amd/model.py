@@ -42,6 +42,33 @@ def _sampling_args(kw):
     return t, top_p, int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+def num_return_sequences(kw) -> int:
+    """generate()'s num_return_sequences (None = 1), with HF's validation (GenerationConfig.validate / GenerationMixin._validate_generated_length [ext]) as ValueError, and
+    the one combination that is not built yet -- guidance_scale with several answers -- refused instead of ignored."""
+    n = kw.get("num_return_sequences")
+    n = 1 if n is None else int(n)
+    if n < 1:
+        raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n}")
+    if n == 1:
+        return 1
+    k = kw.get("num_beams", 1) or 1
+    if k == 1 and not kw.get("do_sample", False):
+        raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).")
+    if k > 1 and n > k:
+        raise ValueError(f"`num_return_sequences` ({n}) has to be smaller or equal to `num_beams` ({k}).")
+    if LP.resolve_guidance(kw) is not None:
+        raise ValueError("generate(): guidance_scale with num_return_sequences > 1 is not supported yet")
+    return n
+
+
+def fanout_stream(prompt: int, member: int) -> int:
+    """The random stream of answer `member` of prompt `prompt` in a generate(do_sample=True, num_return_sequences=n) call: member * 65536 + prompt.  It does not depend on
+    n, so under a fixed seed the answers for n' < n are a prefix of the answers for n, per prompt."""
+    if not 0 <= prompt < 65536 or not 0 <= member < 65536:
+        raise ValueError("num_return_sequences: at most 65536 prompts per call and 65536 answers per prompt")
+    return member * 65536 + prompt
+
+
 class SyntheticTokenizer:
     """Stand-in for the HF tokenizer (tokenizer files are not available offline): whitespace words -> ids by a
     stable hash; the 302 temporal tokens map to the last 302 rows of the vocabulary like `add_tokens` does."""
@@ -426,6 +453,62 @@ class LLAVA_NEXT_VIDEO:
             b += len(leaders)
         return out if logprobs is None else (out, lps)
 
+    def _sampling_dict(self, kw) -> dict:
+        """The call's sampling as ONE sequence's own setting (Engine.seq_set_sampling's dict, without the stream): what _select_tokens gives the engine, for the
+        sequences of a num_return_sequences call, whose draws must not depend on the order they were prefilled in.  Without `seed` one is drawn from torch's CPU generator."""
+        t, top_p, seed = _sampling_args(kw)
+        top_k = kw.get("top_k", 50)
+        return dict(do_sample=True, temperature=t, top_k=0 if top_k is None else int(top_k), top_p=top_p, seed=seed,
+                    **{k: v for k, v in LP.resolve_sampling(kw).items() if v is not None})
+
+    def fanout_generate_ids(self, ids_arr, mask, feats, max_new: int, n: int, sampling: dict, processors=None, logprobs: Optional[int] = None, prompt_index=None):
+        """n sampled answers per row from ONE prefill per row: the row is spliced and prefilled once, Engine.seq_fanout makes n - 1 siblings that share the prompt's KV
+        pages (in parts of at most 15 siblings), and source and siblings decode together (decode_greedy_batch groups them: one weight stream per token for up to 16 answers).
+        Answer j of row p draws from stream fanout_stream(p, j) of sampling["seed"], whatever n is and whatever fits the KV pool at once: when the pool cannot hold all
+        siblings the remaining answers start from another prefill of the same prompt -- a sibling is bit for bit an independent sequence on its stream, so the answers
+        do not change.  prompt_index: the p of every row (default: its position).  Processors, rules, grammar and log-probabilities apply per answer.
+        Returns the ids prompt-major (n per row); with logprobs (ids, lps) as generate_ids."""
+        from .lib import GvlError, ERR_OOM
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        eng = self.engine
+        rows = ids_arr.shape[0]
+        procs = processors if isinstance(processors, (list, tuple)) else [processors] * rows
+        out: List[List[int]] = []
+        lps = []
+        for i in range(rows):
+            p = i if prompt_index is None else int(prompt_index[i])
+            emb = eng.splice([int(t) for t, m in zip(ids_arr[i], mask[i]) if m], feats[i])
+            cap = min(emb.shape[0] + max_new, self.geo.max_seq)
+            done = 0
+            while done < n:
+                opts = LP.SeqOptions(procs[i], logprobs, sampling=dict(sampling, stream=fanout_stream(p, done)))
+                group: List[int] = []
+                try:
+                    group.append(eng.seq_alloc(cap))
+                    LP.apply_seq_options(eng, group[0], opts)
+                    first = eng.prefill(group[0], emb, want_logits=True)
+                    while done + len(group) < n:
+                        part = min(15, n - done - len(group))
+                        while part >= 1:                   # all or nothing per call: halve until it fits
+                            try:
+                                group += eng.seq_fanout(group[0], part, cap, [fanout_stream(p, done + len(group) + j) for j in range(part)], first)
+                                break
+                            except GvlError as e:
+                                if e.status != ERR_OOM:
+                                    raise
+                                part //= 2
+                        if part < 1:
+                            break                          # pool (or slots) full: decode what fits, the rest behind another prefill
+                    got = eng.decode_greedy_batch(group, max_new, eos)
+                    if logprobs is not None:
+                        lps += [LP.read_seq_logprobs(eng, s_, g, opts) for s_, g in zip(group, got)]
+                    out += got
+                finally:
+                    for s_ in group:
+                        eng.seq_free(s_)
+                done += len(group)
+        return out if logprobs is None else (out, lps)
+
     def _n_visual(self, samples) -> int:
         return int(samples["spatial_pixel_values"].shape[1]) * self.engine.tokens_per_seg
 
@@ -461,6 +544,7 @@ class LLAVA_NEXT_VIDEO:
             raise ValueError("generate(): 'text' samples are a training-only construct of the reference; use forward() for them")
         _beam_impl(generate_kwargs)                       # a bad beam_impl fails before any work
         self._check_guidance(generate_kwargs, len(samples["prompts"]))     # ... and so do the guidance arguments
+        num_return_sequences(generate_kwargs)             # ... and num_return_sequences
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
@@ -480,6 +564,7 @@ class LLAVA_NEXT_VIDEO:
     def _generate(self, samples, generate_kwargs, ids_arr, mask, opts, procs, max_new: int, rid: Optional[int], gid: Optional[int] = None):
         feats = self.encode_images(samples)
         k = generate_kwargs.get("num_beams", 1) or 1
+        n_ret = num_return_sequences(generate_kwargs)
         lps, beam_scores = None, None
         if k > 1:                                         # HF beam search (do_sample=False), one sample at a time
             sample = None
@@ -491,14 +576,20 @@ class LLAVA_NEXT_VIDEO:
             scored = opts.return_dict and opts.output_scores
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs), grammar=gid)
+                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs), grammar=gid, num_return=n_ret)
                        for b in range(ids_arr.shape[0])]
+            if n_ret > 1:                                  # the n best hypotheses of every prompt, prompt-major
+                out_ids = [r for per_prompt in out_ids for r in per_prompt]
             if scored:
                 lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
                 out_ids = [r[0] for r in out_ids]
         elif self._check_guidance(generate_kwargs, ids_arr.shape[0]) is not None:      # classifier-free guidance: every sample decodes as a pair with its negative
             res = self.guided_generate_ids(ids_arr, mask, feats, self._negative_embeds(generate_kwargs, feats), LP.resolve_guidance(generate_kwargs), max_new,
                                            processors=procs, logprobs=opts.top_n if opts.top_n >= 0 else None, rules=rid, grammar=gid)
+            out_ids, lps = res if opts.top_n >= 0 else (res, None)
+        elif n_ret > 1:                                   # n sampled answers per prompt from ONE prefill each (gvl_seq_fanout), prompt-major
+            res = self.fanout_generate_ids(ids_arr, mask, feats, max_new, n_ret, self._sampling_dict(generate_kwargs), processors=procs,
+                                           logprobs=opts.top_n if opts.top_n >= 0 else None)
             out_ids, lps = res if opts.top_n >= 0 else (res, None)
         elif opts.top_n >= 0:
             out_ids, lps = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs, logprobs=opts.top_n)
@@ -511,8 +602,9 @@ class LLAVA_NEXT_VIDEO:
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
                           sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
-                          rules: Optional[int] = None, impl: str = "host", grammar: Optional[int] = None):
-        """generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
+                          rules: Optional[int] = None, impl: str = "host", grammar: Optional[int] = None, num_return: int = 1):
+        """num_return > 1: a list of results, the num_return best hypotheses, best first (beam.beam_search's num_return / gvl_beam_search_n).
+        generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
         teacher-forced batched decode step per token (gvl_decode_step_logits_batch: one stream of the weights for the k beams); log-softmax / top-2k of the step run on the device (torch), the bookkeeping on
@@ -536,7 +628,7 @@ class LLAVA_NEXT_VIDEO:
                 LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
                 first = eng.prefill(seq, emb, want_logits=True)
                 return eng.beam_search(seq, first, num_beams, max_new, eos, length_penalty, early_stopping,
-                                       processors if processors is not None and processors.active else None, rules, with_scores)
+                                       processors if processors is not None and processors.active else None, rules, with_scores, num_return=num_return)
             finally:
                 eng.seq_free(seq)
         gi = eng.decode_group_info()                     # which group sizes ONE batched step takes: asked from the library, not restated here
@@ -578,7 +670,7 @@ class LLAVA_NEXT_VIDEO:
                     return eng.decode_step_logits_batch(beams, toks)        # the k beams share ONE stream of the weights
                 return torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(beams, toks)])
 
-            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process, with_scores=with_scores)
+            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process, with_scores=with_scores, num_return=num_return)
         finally:
             for s_ in set(x for x in list(beams) + fresh if x is not None):
                 try:
@@ -597,6 +689,9 @@ class LLAVA_NEXT_VIDEO:
             raise ValueError("generate_shared takes the pixel tensors of one video")
         if LP.resolve_guidance(generate_kwargs) is not None:
             raise ValueError("generate_shared(): guidance_scale != 1 is not supported yet (generate() takes it)")
+        n_ret = num_return_sequences(generate_kwargs)
+        if n_ret > 1 and (generate_kwargs.get("num_beams", 1) or 1) > 1:
+            raise ValueError("generate_shared(): num_return_sequences > 1 is built for sampling (do_sample=True, num_beams=1); generate() returns the n best beams")
         max_new = int(generate_kwargs.get("max_new_tokens", 2048))
         ids = [self.tokenizer_image_token(t) for t in prompts]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
@@ -613,8 +708,14 @@ class LLAVA_NEXT_VIDEO:
             gid = self._select_grammar(dict(generate_kwargs, num_beams=1))       # ... and with the grammar
             feats = self.encode_images(samples)
             want = opts.top_n if opts.top_n >= 0 else None
-            res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want)
-            if res is None:                              # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
+            # num_return_sequences = n: every prompt's sequence is fanned out behind its own (extend-)prefill.  Every prompt stands for a generate() call of its own,
+            # so each draws from the streams of prompt index 0: the n answers of a prompt equal generate(num_return_sequences=n) on that prompt alone
+            fan = (n_ret, self._sampling_dict(generate_kwargs)) if n_ret > 1 else None
+            res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want, fanout=fan)
+            if res is None and fan is not None:
+                res = self.fanout_generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, n_ret, fan[1], processors=procs, logprobs=want,
+                                               prompt_index=[0] * len(prompts))
+            elif res is None:                            # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
                 res = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs, logprobs=want)
         finally:
             self._drop_grammar(gid)
@@ -650,12 +751,15 @@ class LLAVA_NEXT_VIDEO:
         return prefix
 
     def _generate_shared_prefix(self, rows: List[List[int]], vis: torch.Tensor, max_new: int,
-                                processors: Optional[List["LP.Processors"]] = None, logprobs: Optional[int] = None):
+                                processors: Optional[List["LP.Processors"]] = None, logprobs: Optional[int] = None, fanout=None):
         """Prompts about one video share the system prompt and the visual tokens: the common prefix (rounded down to 128 tokens = whole KV pages AND
         whole query blocks, so that every later row is computed exactly as in a full prefill) is prefilled ONCE; every prompt forks it
         (gvl_seq_fork: pages referenced, not copied) and only its own tail is prefilled -- the tails of up to 8 prompts in one ragged decoder pass
         (gvl_prefill_extend_varlen: the weights are streamed once per group, not once per prompt); the answers are decoded together.
-        Ids are bit-identical to one full prefill per prompt.  logprobs: as in generate_ids (then (ids, lps) is returned)."""
+        Ids are bit-identical to one full prefill per prompt.  logprobs: as in generate_ids (then (ids, lps) is returned).
+        fanout: None, or (n, sampling) -- n sampled answers per prompt: every fork takes `sampling` (fanout_generate_ids') on stream fanout_stream(0, 0) and, behind its
+        tail's prefill, n - 1 siblings (Engine.seq_fanout) on the streams fanout_stream(0, j); the answers come back prompt-major.  When the KV pool cannot hold all of
+        them at once: None, and the caller takes the per-prompt path."""
         eng = self.engine
         self.last_shared_prefix = 0                      # tokens prefilled once for all prompts in the last generate_shared call (0 = not shared)
         if len(rows) < 2:
@@ -667,22 +771,42 @@ class LLAVA_NEXT_VIDEO:
             return None
         self.last_shared_prefix = prefix
         eos = getattr(self.tokenizer, "eos_token_id", None)
-        opts = [LP.SeqOptions(p, logprobs) for p in (processors or [None] * len(rows))]
-        base, seqs = None, []
+        from .lib import GvlError, ERR_OOM
+        n = fanout[0] if fanout else 1
+        own = dict(sampling=dict(fanout[1], stream=fanout_stream(0, 0))) if fanout else {}
+        opts = [LP.SeqOptions(p, logprobs, **own) for p in (processors or [None] * len(rows))]
+        base, seqs, sibs = None, [], []
         try:
             base = eng.seq_alloc(prefix)
             eng.prefill(base, embs[0][:prefix])
             for o, e in zip(opts, embs):
                 seqs.append(eng.seq_fork(base, prefix, min(e.shape[0] + max_new, self.geo.max_seq)))
                 LP.apply_seq_options(eng, seqs[-1], o)
+            firsts = []
             for g in range(0, len(seqs), 8):                 # all tails of a group in ONE decoder pass (each exactly as its own gvl_prefill_extend)
-                eng.prefill_extend_batch(seqs[g:g + 8], [e[prefix:] for e in embs[g:g + 8]])
-            got = eng.decode_greedy_batch(seqs, max_new, eos)
+                firsts.append(eng.prefill_extend_batch(seqs[g:g + 8], [e[prefix:] for e in embs[g:g + 8]], want_logits=n > 1))
+            order = list(seqs)
+            if n > 1:
+                try:
+                    order = []
+                    for i, (s_, e) in enumerate(zip(seqs, embs)):
+                        order.append(s_)
+                        first = firsts[i // 8][i % 8].contiguous()
+                        for j0 in range(1, n, 15):
+                            new = eng.seq_fanout(s_, min(15, n - j0), min(e.shape[0] + max_new, self.geo.max_seq), [fanout_stream(0, j) for j in range(j0, min(n, j0 + 15))], first)
+                            sibs += new
+                            order += new
+                except GvlError as e:
+                    if e.status == ERR_OOM:
+                        self.last_shared_prefix = 0
+                        return None
+                    raise
+            got = eng.decode_greedy_batch(order, max_new, eos)
             if logprobs is None:
                 return got
-            return got, [LP.read_seq_logprobs(eng, s_, g, o) for s_, g, o in zip(seqs, got, opts)]
+            return got, [LP.read_seq_logprobs(eng, s_, g, opts[0]) for s_, g in zip(order, got)]
         finally:
-            for s_ in seqs:
+            for s_ in sibs + seqs:
                 eng.seq_free(s_)
             if base is not None:
                 eng.seq_free(base)

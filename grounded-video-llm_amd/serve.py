@@ -43,10 +43,12 @@ class _Request:
     guidance: Optional[float] = None # classifier-free guidance scale (None: off) against ...
     negative: object = None          # ... the negative prompt's embedding rows; neg_seq: its sequence, the follower of `seq` (Engine.seq_set_guidance)
     neg_seq: int = -1
+    fan: int = 1                     # answers wanted from ONE prefill (num_return_sequences); back to 1 once admitted: its siblings are requests of their own then
+    fan_rids: List[int] = field(default_factory=list)   # ... and the request ids reserved for the siblings
 
     @property
-    def slots(self) -> int:          # a guided request holds two sequences, and two rows of every decode step
-        return 2 if self.guidance is not None else 1
+    def slots(self) -> int:          # a guided request holds two sequences, and two rows of every decode step; a queued fan-out needs room for all its answers
+        return 2 if self.guidance is not None else self.fan
 
 
 @dataclass
@@ -77,6 +79,7 @@ class ClipScheduler:
         self._next = 0
         self.prefixes: Dict[int, _Prefix] = {}
         self._next_prefix = 0
+        self._rule_holders: Dict[int, int] = {}      # device rule set -> requests that still hold it (the answers of one fan-out share their request's set)
         self.stats = {"prefill_calls": 0, "decode_chunks": 0, "decode_seq_steps": 0, "wasted_seq_steps": 0, "max_concurrent": 0, "prefix_rows_saved": 0}
 
     # ---- public ------------------------------------------------------------------------------------------
@@ -112,7 +115,7 @@ class ClipScheduler:
                begin_suppress_tokens=None, forced_eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
                top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
                epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None,
-               grammar: Optional[int] = None, guidance_scale: Optional[float] = None, negative=None) -> int:
+               grammar: Optional[int] = None, guidance_scale: Optional[float] = None, negative=None, num_return_sequences: Optional[int] = None):
         """Queue one request.  embeds: the full spliced prompt.  prefix: an add_prefix() id -- the caller promises that the prompt's first P rows ARE the registered
         ones; only embeds[P:] (at least one row) is then prefilled.  An optimisation only: the result is the same without it.  (It is ignored for a request that
         LongRoPE forbids to share: P <= rope_orig_max_pos < len(embeds) -- a full prefill of that prompt ropes the shared rows with the long factors.)
@@ -133,7 +136,20 @@ class ClipScheduler:
         guidance_scale / negative: HF's classifier-free guidance for THIS request (logits.resolve_guidance: None or 1 = off) against the negative prompt whose
         embedding rows `negative` holds.  The request runs as a pair of sequences -- the negative one follows it as one more row of every decode step
         (Engine.seq_set_guidance) -- so it counts as TWO toward max_active; its ids do not depend on its neighbours, max_active or chunk.  Not with prefix=.  Its own
-        settings are applied behind its prefill (guidance works on the raw first rows): engine-wide default processors, rules or a grammar must be off for it."""
+        settings are applied behind its prefill (guidance works on the raw first rows): engine-wide default processors, rules or a grammar must be off for it.
+        num_return_sequences = n > 1 (HF's; needs a sampled setting of the request's own): n sampled answers to this ONE prompt -- a LIST of n request ids is returned, one per answer.  The
+        prompt is prefilled once; at admission the sequence is fanned out into its n - 1 siblings (Engine.seq_fanout: the prompt's KV pages are shared), answer j drawing
+        from random stream j of `seed`.  The request counts as n toward max_active and is admitted only when n slots (and the KV pages of all answers) are free; from
+        then on every answer is a request of its own that retires on its own eos.  Each answer's ids depend on its settings, its stream and its logits alone -- not on
+        max_active, chunk or its neighbours.  Not with guidance_scale."""
+        n_fan = 1 if num_return_sequences is None else int(num_return_sequences)
+        if n_fan < 1:
+            raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n_fan}")
+        if n_fan > 1:
+            if LP.resolve_guidance(dict(guidance_scale=guidance_scale)) is not None:
+                raise ValueError("guidance_scale with num_return_sequences > 1 is not supported yet")
+            if n_fan > self.max_active:
+                raise ValueError(f"a request with num_return_sequences={n_fan} counts as {n_fan} toward max_active, which is {self.max_active}")
         guidance = LP.resolve_guidance(dict(guidance_scale=guidance_scale))
         if guidance is not None:
             if negative is None:
@@ -154,6 +170,9 @@ class ClipScheduler:
         if any(v is not None for v in rkw.values()):
             rules = LP.resolve_rules(rkw, self.eos, int(max_new_tokens), getattr(getattr(self.eng, "geo", None), "vocab", None))
         sampling = LP.request_sampling(do_sample, temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed)
+        if n_fan > 1 and (sampling is ... or not sampling.get("do_sample")):      # the answers differ by their random streams only: the request's own sampled setting
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n_fan}): give the request its own "
+                             "sampling (do_sample=True, or any of temperature / top_k / top_p / ... / seed)")
         if prefix is not None:
             p = self.prefixes.get(prefix)
             if p is None or p.dropped:
@@ -168,10 +187,13 @@ class ClipScheduler:
             else:
                 p.queued += 1
         r = _Request(self._next, embeds, int(max_new_tokens), opts=LP.SeqOptions(procs, logprobs, rules, sampling, ... if grammar is None else int(grammar)), prefix=prefix,
-                     guidance=guidance, negative=negative if guidance is not None else None)
+                     guidance=guidance, negative=negative if guidance is not None else None, fan=n_fan)
         self._next += 1
+        if n_fan > 1:
+            r.fan_rids = list(range(self._next, self._next + n_fan - 1))
+            self._next += n_fan - 1
         self.queue.append(r)
-        return r.rid
+        return r.rid if n_fan == 1 else [r.rid] + r.fan_rids
 
     def logprobs(self, rid: int):
         """(lp, top) of a finished request submitted with logprobs: lp[i] = the log-probability of its i-th id, top[i] = its top N (id,
@@ -209,8 +231,9 @@ class ClipScheduler:
     # ---- internals ---------------------------------------------------------------------------------------
     def _admit(self):
         new: List[_Request] = []
+        fanned: List[_Request] = []                          # fan-out requests (prefilled on admission) and their siblings
         rows = 0
-        while self.queue and sum(q.slots for q in self.active + new) + self.queue[0].slots <= self.max_active:
+        while self.queue and sum(q.slots for q in self.active + new) + sum(q not in new for q in fanned) + self.queue[0].slots <= self.max_active:
             r = self.queue[0]
             S = int(r.embeds.shape[0])
             P = self.prefixes[r.prefix].rows if r.prefix is not None else 0     # rows the request does not prefill
@@ -250,6 +273,16 @@ class ClipScheduler:
                 self._drop_rules(r)
                 raise
             r.max_new = min(r.max_new, cap - S + 1)          # generate() stops at the context limit (Engine.generate_ids does too)
+            if r.fan > 1:                                    # n answers from one prefill: prefill now, with its logits, and fan out -- all siblings or none
+                try:
+                    sibs = self._fan_out(r, cap, P)
+                except Exception as e:
+                    self._free(r)
+                    self._drop_rules(r)
+                    if getattr(e, "status", 0) == L.ERR_OOM and isinstance(e, L.GvlError):
+                        break                                # KV pages for all n answers: wait for a retirement
+                    raise
+                fanned += [r] + sibs
             self.queue.popleft()
             new.append(r)
             rows += S - P
@@ -258,7 +291,7 @@ class ClipScheduler:
                 self._release_prefix(r.prefix)
                 self.stats["prefix_rows_saved"] += P
                 r.embeds = r.embeds[P:]
-        plain = [r for r in new if r.guidance is None]
+        plain = [r for r in new if r.guidance is None and r not in fanned]
         for r in new:                                        # a guided request: both prompts prefilled with their logits, then bound -- the first token is guided too
             if r.guidance is not None:
                 lc, lu = self.eng.prefill(r.seq, r.embeds, want_logits=True), self.eng.prefill(r.neg_seq, r.negative, want_logits=True)
@@ -273,8 +306,29 @@ class ClipScheduler:
             for r in new:
                 r.n_gen = 1
                 r.embeds = None                              # the KV cache holds it now
-            self.active += new
+            for r in new:                                    # a fan-out's answers stand together, in the order of their request ids
+                self.active += [q for q in fanned if q is r or q.rid in r.fan_rids] if r.fan_rids else [r]
+                r.fan_rids = []
             self.stats["max_concurrent"] = max(self.stats["max_concurrent"], sum(r.slots for r in self.active))
+
+    def _fan_out(self, r: _Request, cap: int, P: int) -> List[_Request]:
+        """Prefill `r` (behind its prefix, when it names one) and make its r.fan - 1 siblings, each a request of its own: answer j draws from stream j of the request's
+        seed (the source, answer 0, from stream 0 -- what a plain sampled request does).  A failure leaves no sibling behind."""
+        first = self.eng.prefill_extend(r.seq, r.embeds[P:], want_logits=True) if P else self.eng.prefill(r.seq, r.embeds, want_logits=True)   # (the fork holds the first P rows)
+        self.stats["prefill_calls"] += 1
+        seqs: List[int] = []
+        try:
+            for j0 in range(1, r.fan, 15):
+                seqs += self.eng.seq_fanout(r.seq, min(15, r.fan - j0), cap, list(range(j0, min(r.fan, j0 + 15))), first)
+        except Exception:
+            for s_ in seqs:
+                self.eng.seq_free(s_)
+            raise
+        if r.rules_id is not None:
+            self._rule_holders[r.rules_id] = r.fan
+        sibs = [_Request(rid, None, r.max_new, seq=s_, n_gen=1, opts=r.opts, rules_id=r.rules_id) for rid, s_ in zip(r.fan_rids, seqs)]
+        r.fan = 1
+        return sibs
 
     def _free(self, r: _Request):
         self.eng.seq_free(r.seq)                             # the leader first: freeing it unbinds the pair
@@ -299,6 +353,11 @@ class ClipScheduler:
     def _drop_rules(self, r: _Request):
         if r.rules_id is not None:
             rid, r.rules_id = r.rules_id, None
+            left = self._rule_holders.get(rid, 1) - 1        # the answers of one fan-out share the set: the last one to retire destroys it
+            if left > 0:
+                self._rule_holders[rid] = left
+                return
+            self._rule_holders.pop(rid, None)
             self.eng.rules_destroy(rid)
 
     def _retire(self) -> List[int]:

@@ -175,6 +175,24 @@ int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const 
  * are shared by reference, the partial last page is copied on `stream` (one launch over all layers); the clone then appends to its own pages.
  * Its list of generated ids starts empty -- unless the source has a grammar (gvl_seq_set_grammar): then the clone takes the source's generated ids along, see there. */
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream);
+/* n answers to ONE prompt from one prefill (HF generate(num_return_sequences = n) expands the prompt n times and pays n prefills): n_new SIBLINGS of the freshly prefilled
+ * sequence src_seq -- it holds exactly the one token its own prefill selected, as gvl_seq_set_guidance requires -- each with capacity max_tokens; first_logits (device, fp32
+ * [vocab]) is the last_logits of that prefill; 1 <= n_new <= 15 (GVL_MAX_DECODE_BATCH - 1); the call may be repeated while the source is still fresh.
+ *   copy      a sibling is a gvl_seq_clone of the source at its current length: whole pages shared by reference, the partial last page private.  The siblings' partial pages
+ *             are copied in ONE launch for all siblings (all layers, K and V^T); a prompt that ends on a page boundary copies nothing.
+ *   settings  the source's processors, rule set, grammar and log-probability setting, and the source's EFFECTIVE sampling -- its own (gvl_seq_set_sampling), else the ctx
+ *             setting at the time of the call -- as a setting of the sibling's own with stream = streams[i] (host array [n_new]).
+ *   token     sibling i's first token is selected from first_logits with its own draw (seed, streams[i], step 0), one selection launch for all siblings.  A prefill's
+ *             last_logits is the row its own selection saw, i.e. the PROCESSED row, and at step 0 every sibling's processed row is that same row (empty history, the same
+ *             min-length ban, begin-suppress and grammar start): the call applies warpers and draw only, never processors, rules or grammar a second time.
+ * Afterwards every sibling stands where its own prefill would have left it (n_gen 1; output slot 0, the token word, log-probability slot 0 and the top list from its own
+ * selection) and the source is untouched (token, lists, pages, random stream).  Sibling i's ids and log-probabilities are bit for bit those of an independent sequence
+ * prefilled with the same prompt and settings under gvl_seq_set_sampling(stream = streams[i]), whatever decode group it travels in.  dst_seqs [n_new] receives the ids; free
+ * source and siblings in any order.  All work is enqueued on `stream`; nothing is synchronised.
+ * All or nothing: GVL_ERR_ARG (NULL arguments, unknown source, n_new / max_tokens out of range), GVL_ERR_STATE (source not fresh, or a member of a guided pair) and
+ * GVL_ERR_OOM (KV pages or sequence slots for fewer than n_new siblings) are raised before anything runs, with every sequence and the pool as they were. */
+int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const uint32_t* streams /* [n_new] host */, float* first_logits /* device, fp32 [vocab] */,
+                   int* dst_seqs /* [n_new] */, void* stream);
 int gvl_kv_info(const gvl_ctx* ctx, int* total_pages, int* free_pages, int64_t* pool_bytes, int* max_live_seqs);
 /* The group sizes ONE batched decode step takes (gvl_decode_step_logits_batch, and the parts gvl_decode_greedy_batch / gvl_decode_steps
  * step together), valid after gvl_finalize_weights: *max_group = 16 on the skinny-MFMA decode path, 4 on the VALU fallback
@@ -404,7 +422,11 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
  * unknown rule set, bad processor values, an unknown or not prefilled sequence (GVL_ERR_STATE), early_stopping 2 ("never") with length_penalty > 0 (it needs a maximum
  * length the reference never passes), KV pages exhausted (GVL_ERR_OOM), fewer than num_beams non-eos candidates among a step's 2 x num_beams (GVL_ERR_STATE).
  * NaN logits are outside the contract: the candidate order is then that of the order-preserving integer keys, not IEEE's (no store goes out of bounds).
- * Diverse / constrained beams and num_return_sequences > 1 are not supported. */
+ * gvl_beam_search_n returns the num_return (1 .. num_beams) BEST hypotheses (HF num_return_sequences with beams; BeamSearchScorer.finalize with num_beam_hyps_to_keep =
+ * num_return): popped from sorted(hypotheses, key = score) best first, among equal scores the later added first.  out_ids_host [num_return][cap], n_out [num_return],
+ * sequences_scores [num_return] (non-increasing; may be NULL), transition_scores_host [num_return][cap] (may be NULL).  Everything else -- the search, the errors -- is
+ * gvl_beam_search's, which is the num_return = 1 call.  GVL_ERR_ARG for num_return outside 1 .. num_beams.
+ * Diverse (group) and constrained beams are not supported. */
 typedef struct gvl_beam_params {
   int num_beams;            /* 2 .. 16 (GVL_MAX_DECODE_BATCH) */
   int max_new_tokens;       /* >= 1 */
@@ -416,6 +438,8 @@ typedef struct gvl_beam_params {
 } gvl_beam_params;
 int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_beam_params* params, int32_t* out_ids_host, int cap, int* n_out,
                     double* sequences_score, float* transition_scores_host, void* stream);
+int gvl_beam_search_n(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_beam_params* params, int num_return, int32_t* out_ids_host, int cap, int* n_out,
+                      double* sequences_scores, float* transition_scores_host, void* stream);
 
 /* ---- multi-GPU exchange (SURVEY.md §8 e) -------------------------------------------------------------------------------------
  * The reference's inference is single-GPU (inference.py:17); sharding the frame batch over the GPUs of a node is this build's

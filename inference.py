@@ -62,6 +62,8 @@ def parse_args(argv=None):
     p.add_argument("--min_new_tokens", type=int, default=None, help="HF MinNewTokensLengthLogitsProcessor: no eos before this many new ids")
     p.add_argument("--guidance_scale", type=float, default=None, help="HF classifier-free guidance against --negative_prompt (None / 1 = off); not with --share_visual or --num_beams > 1")
     p.add_argument("--negative_prompt", type=str, default=None, help="the negative prompt of --guidance_scale: with <image> it sees the same video, without it it is the video-free contrast")
+    p.add_argument("--num_return_sequences", type=int, default=1, help="HF num_return_sequences: n sampled answers per prompt from ONE prefill (needs --do_sample True), or the n best "
+                                                                       "beams (n <= --num_beams); the first answer is reported as usual, all of them are listed at the end")
     p.add_argument("--output_scores", action="store_true", help="print each answer's mean token log-prob and, for the grounding answer, every temporal token's probability")
     p.add_argument("--constrain_grounding", action="store_true", help="keep the grounding answer inside 'From <s> to <e>.' with s <= e (generate(grammar=...); not with --share_visual, whose one call answers all three prompts)")
     p.add_argument("--share_visual", type=_bool, default=False, help="encode the video ONCE for the three prompts and batch them (the reference re-encodes per prompt)")
@@ -70,6 +72,8 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.guidance_scale not in (None, 1.0) and (args.negative_prompt is None or args.share_visual or args.num_beams > 1):
         p.error("--guidance_scale needs --negative_prompt and works with neither --share_visual nor --num_beams > 1")
+    if args.num_return_sequences > 1 and args.guidance_scale not in (None, 1.0):
+        p.error("--num_return_sequences > 1 does not work with --guidance_scale yet")
     if args.constrain_grounding and args.share_visual:
         p.error("--constrain_grounding constrains the grounding answer only: it cannot be combined with --share_visual")
     return args
@@ -157,7 +161,10 @@ def main(argv=None):
         kw.update(guidance_scale=args.guidance_scale, negative_prompts=[args.negative_prompt])
     if args.output_scores:
         kw.update(return_dict_in_generate=True, output_scores=True)
-    outs, scored = {}, {}
+    n_ret = args.num_return_sequences
+    if n_ret != 1:
+        kw["num_return_sequences"] = n_ret                                              # generate() validates it as HF does
+    outs, scored, every = {}, {}, {}                                                      # answers come back prompt-major: n per prompt, the first one is reported
     modes = ("grounding", "qa", "referring")
     grounding_kw = grounding_constraint(args, model)
     if args.share_visual:
@@ -166,9 +173,10 @@ def main(argv=None):
         prompts = [per_mode[0]["prompts"][0]] + [create_prompt(args, mode, duration) for mode in modes[1:]]
         res = model.generate_shared(per_mode[0], prompts, **kw)
         texts = res.texts if args.output_scores else res
-        outs = {mode: (p, t) for mode, p, t in zip(modes, prompts, texts)}
+        outs = {mode: (p, texts[i * n_ret]) for i, (mode, p) in enumerate(zip(modes, prompts))}
+        every = {mode: texts[i * n_ret:(i + 1) * n_ret] for i, mode in enumerate(modes)}
         if args.output_scores:
-            scored = {mode: (res.sequences[i], res.transition_scores[i]) for i, mode in enumerate(modes)}
+            scored = {mode: (res.sequences[i * n_ret], res.transition_scores[i * n_ret]) for i, mode in enumerate(modes)}
     else:
         for i, mode in enumerate(modes):
             samples = create_inputs(args, mode, frames, duration, model.engine)
@@ -176,6 +184,7 @@ def main(argv=None):
             # for all three would make their draws perfectly correlated)
             res = model.generate(samples, **{**kw, "seed": args.seed + i, **(grounding_kw if mode == "grounding" else {})})
             outs[mode] = (samples["prompts"][0], (res.texts if args.output_scores else res)[0])
+            every[mode] = list(res.texts if args.output_scores else res)
             if args.output_scores:
                 scored[mode] = (res.sequences[0], res.transition_scores[0])
     print("\n******grounding example******")
@@ -187,6 +196,11 @@ def main(argv=None):
     print("\n******videoqa example******")
     print(outs["qa"][0])
     print(outs["qa"][1])
+    if n_ret > 1:
+        print(f"\n******{n_ret} answers per prompt******")
+        for mode in modes:
+            for j, t in enumerate(every[mode]):
+                print(f"{mode} [{j}]: {t}")
     if args.output_scores:
         print_scores(model.tokenizer, scored)
 
