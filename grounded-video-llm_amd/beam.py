@@ -107,7 +107,7 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
                 eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None,
                 process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None, with_scores: bool = False,
                 candidates: Optional[Callable[[torch.Tensor, torch.Tensor], Tuple[Sequence[float], Sequence[int], Sequence[float]]]] = None,
-                num_return: int = 1):
+                num_return: int = 1, num_beam_groups: int = 1, diversity_penalty: float = 0.0, pad_id: Optional[int] = None):
     """first_logits [vocab]: logits after the prompt.  step(parents, tokens) -> logits [k, vocab] of the k new running beams, where new beam j
     continues old beam parents[j] with tokens[j] (the caller reorders its KV cache accordingly; at the first call every parent is 0 = the
     prompt).  Returns the NEW ids of the best hypothesis (eos included when it ended by eos), as HF does for inputs_embeds prompts.
@@ -123,7 +123,12 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
     (processed log-probability + beam score), flat index beam * vocab + token, the processed log-probability alone.  It replaces the torch top-2k below and the
     gather of the transition scores: Engine.op_beam_candidates (the library's own kernels) plugs in here, and tests record every step's list through it.
     num_return (1 .. num_beams; HF num_return_sequences with beams, BeamSearchScorer.finalize's num_beam_hyps_to_keep): > 1 returns a LIST of results, the num_return
-    best hypotheses, best first -- among equal scores the later added first; beam search and beam-sample alike.  1 returns the one result, as ever."""
+    best hypotheses, best first -- among equal scores the later added first; beam search and beam-sample alike.  1 returns the one result, as ever.
+    num_beam_groups / diversity_penalty / pad_id: anything but (1, 0.0) is diverse (group) beam search -- group_beam_search below, whose hooks take the group; (1, 0.0) is
+    this function as it always was."""
+    if check_groups(num_beams, num_beam_groups, diversity_penalty, sample is not None):
+        return group_beam_search(step, first_logits, num_beams, num_beam_groups, diversity_penalty, max_new_tokens, eos_id, length_penalty, early_stopping,
+                                 process=process, with_scores=with_scores, candidates=candidates, num_return=num_return, pad_id=pad_id)
     k = int(num_beams)
     if k < 2:
         raise ValueError("beam_search needs num_beams >= 2")
@@ -199,6 +204,143 @@ def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logi
             hyps.add(seqs[j], float(scores[j]), len(seqs[j]), False, tsc[j])
     # HF's finalize: sorted(beams, key=score) is stable and hypotheses are popped from its end -- best first, among equal scores the LATER added first
     ranked = sorted(hyps.beams, key=lambda x: x[0])[::-1] if hyps.beams else [(0.0, seqs[0], False, tsc[0])]
+    results = []
+    for best in ranked[:n_ret]:
+        out = list(best[1])
+        if best[2] and eos_id is not None and len(out) < max_new_tokens:
+            out.append(eos_id)
+        results.append((out, float(best[0]), list(best[3])[:len(out)]) if with_scores else out)
+    return results[0] if n_ret == 1 else results
+
+
+# ---- diverse (group) beam search: transformers 4.40.1 GenerationMixin._group_beam_search + BeamSearchScorer(num_beam_groups = G) + HammingDiversityLogitsProcessor [ext] ----
+def check_groups(num_beams, num_beam_groups, diversity_penalty, do_sample: bool = False) -> bool:
+    """HF's validation of num_beam_groups / diversity_penalty (GenerationConfig.validate, BeamSearchScorer and HammingDiversityLogitsProcessor's constructors) as
+    ValueError.  Returns whether the arguments ask for group beam search; (1, 0.0) -- and None for either -- is plain beam search."""
+    G = 1 if num_beam_groups is None else num_beam_groups
+    lam = 0.0 if diversity_penalty is None else diversity_penalty
+    if isinstance(G, bool) or not isinstance(G, int) or G < 1:
+        raise ValueError(f"`num_beam_groups` has to be a strictly positive integer, but is {G!r}")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or lam != lam:
+        raise ValueError(f"`diversity_penalty` should be a float strictly larger than 0., but is {lam!r}")
+    if G == 1 and lam == 0:
+        return False
+    prefix = "`diversity_penalty` is not 0.0 or `num_beam_groups` is not 1, triggering group beam search. In this generation mode, "
+    if do_sample:
+        raise ValueError(prefix + "`do_sample` must be set to `False`")
+    k = 1 if num_beams is None else int(num_beams)
+    if G > k or k % G != 0:
+        raise ValueError(f"`num_beam_groups` ({G}) has to be an integer smaller or equal than `num_beams` ({k}) and `num_beams` has to be divisible by `num_beam_groups`")
+    if G > 1 and lam == 0:
+        raise ValueError(prefix + "`diversity_penalty` should be greater than `0.0`, otherwise your groups will be identical.")
+    if not isinstance(lam, float) or not lam > 0.0:
+        raise ValueError(f"`diversity_penalty` should be a float strictly larger than 0., but is {lam!r}")
+    if G == 1:
+        raise ValueError(prefix + "`num_beam_groups` should be greater than 1: a diversity penalty needs a second group to act on")
+    return True
+
+
+def hamming_penalty(rows: torch.Tensor, prev_tokens: Sequence[int], diversity_penalty: float) -> torch.Tensor:
+    """HammingDiversityLogitsProcessor on one group's rows [s, V]: every row loses fp32(fp32(lambda) * fp32(c[t])) at token t, c = how often t occurs among the
+    tokens the earlier groups chose at this step (`scores -= lambda * bincount`); ids outside [0, V) count nowhere."""
+    V = rows.shape[-1]
+    ids = [int(t) for t in prev_tokens if 0 <= int(t) < V]
+    if not ids:
+        return rows
+    c = torch.bincount(torch.as_tensor(ids, dtype=torch.long), minlength=V).to(device=rows.device, dtype=torch.float32)
+    return rows.float() - torch.tensor(float(diversity_penalty), dtype=torch.float32, device=rows.device) * c
+
+
+def group_beam_search(step: Callable[[List[Optional[int]], List[int]], torch.Tensor], first_logits: torch.Tensor, num_beams: int, num_beam_groups: int,
+                      diversity_penalty: float, max_new_tokens: int, eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False,
+                      process: Optional[Callable] = None, with_scores: bool = False, candidates: Optional[Callable] = None, num_return: int = 1,
+                      pad_id: Optional[int] = None):
+    """generate(num_beams = k, num_beam_groups = G, diversity_penalty = lambda): G groups of s = k / G beams, group g owning the running beams g*s .. g*s + s - 1.  Every
+    step advances all k beams once; then the groups are visited in order, each one beam_search's own step with k := s (its own _Hyps(s), its own done flag, its 2s
+    candidates from its s x vocab grid).  Two things couple them: group g > 0's processed rows lose lambda x (how often the earlier groups chose the token at this step)
+    -- HammingDiversityLogitsProcessor, in HF's list after sequence_bias and before the repetition penalty -- and the tokens a group chose (its first s non-eos candidates)
+    are what the later groups count.  The beam scores start at -1e9 except the first beam of every group.  A group that was done when the step began is not processed: its
+    beams get score 0 and pad_id as their token (which the later groups DO count; None: an id that counts nowhere), and they never become hypotheses.  At the end every
+    open group adds its beams, the hypotheses of all groups are pooled in group order and ranked as beam_search ranks them.
+    step(parents, tokens): as beam_search's, over all k beams -- parents are global (g*s + the local parent; 0 at the first call); the beams of a done group come with
+    parent None (nothing of theirs is read again: the caller may free them) and their rows of the returned [k, vocab] logits are ignored.
+    process(histories, logprobs, group=g, prev_tokens=[...], diversity_penalty=lambda) -> the processed rows [s, vocab] of group g: the whole chain INCLUDING the Hamming
+    term in its place (Engine.op_logits_process(..., hamming=...)); None: the Hamming term alone, in torch.
+    candidates(rows [s, vocab], scores [s], group=g) -> (vals, idxs, proc_vals), the group's 2s candidates, flat index = local beam * vocab + token.
+    with_scores / num_return: as beam_search (the transition score of an id includes its Hamming term, as HF's `scores` do)."""
+    if not check_groups(num_beams, num_beam_groups, diversity_penalty, False):
+        raise ValueError("group_beam_search needs num_beam_groups > 1 and diversity_penalty > 0")
+    k, G, lam = int(num_beams), int(num_beam_groups), float(diversity_penalty)
+    s = k // G
+    n_ret = int(num_return)
+    if n_ret < 1 or n_ret > k:
+        raise ValueError("num_return must be 1 .. num_beams")
+    V = first_logits.shape[-1]
+    if V < 2 * s:
+        raise ValueError("vocabulary smaller than 2 x the beams of a group")
+    pad = -1 if pad_id is None or int(pad_id) < 0 else int(pad_id)
+    dev = first_logits.device
+    seqs: List[List[int]] = [[] for _ in range(k)]
+    tsc: List[List[float]] = [[] for _ in range(k)]
+    scores = torch.full((k,), -1e9, dtype=torch.float32, device=dev)
+    scores[::s] = 0.0
+    hyps = [_Hyps(s, length_penalty, early_stopping) for _ in range(G)]
+    done = [False] * G
+    logits = first_logits.float().unsqueeze(0).expand(k, V)
+    n_gen = 0
+    while True:
+        lp_all = torch.log_softmax(logits.float(), dim=-1)
+        cur_len = n_gen + 1
+        current: List[int] = [pad] * k                        # the tokens chosen at THIS step, filled group by group
+        parents: List[Optional[int]] = [None] * k
+        new_seqs, new_tsc, new_scores = list(seqs), list(tsc), [0.0] * k
+        for g in range(G):
+            lo = g * s
+            if done[g]:                                       # BeamSearchScorer.process: a done group is padded -- score 0, token pad
+                for j in range(s):
+                    new_seqs[lo + j], new_tsc[lo + j] = seqs[lo] + [pad], tsc[lo] + [0.0]
+                continue
+            rows, sc, prev = lp_all[lo:lo + s], scores[lo:lo + s], current[:lo]
+            if process is not None:
+                rows = process([list(q) for q in seqs[lo:lo + s]], rows, group=g, prev_tokens=list(prev), diversity_penalty=lam)
+            elif g > 0:
+                rows = hamming_penalty(rows, prev, lam)
+            if candidates is not None:
+                vals, idxs, pv_tok = (list(x) for x in candidates(rows, sc, group=g))
+            else:
+                top = torch.topk((rows + sc[:, None]).reshape(-1), 2 * s, largest=True, sorted=True)
+                vals, idxs = top.values.tolist(), top.indices.tolist()
+                pv_tok = rows.reshape(-1)[top.indices].tolist() if with_scores else [0.0] * len(idxs)
+            nxt: List[Tuple[float, int, int, float]] = []
+            for rank, (v, ix, t_sc) in enumerate(zip(vals, idxs, pv_tok)):
+                b, tok = lo + ix // V, ix % V
+                if eos_id is not None and tok == eos_id:
+                    if rank >= s:
+                        continue
+                    hyps[g].add(seqs[b], v, cur_len, True, tsc[b] + [t_sc])
+                else:
+                    nxt.append((v, tok, b, t_sc))
+                if len(nxt) == s:
+                    break
+            if len(nxt) < s:
+                raise ValueError("fewer than num_beams non-eos candidates among the top 2 x num_beams")
+            done[g] = hyps[g].is_done(max(vals), cur_len)
+            for j, (v, tok, b, t_sc) in enumerate(nxt):
+                parents[lo + j], current[lo + j] = (0 if cur_len == 1 else b), tok
+                new_seqs[lo + j], new_tsc[lo + j], new_scores[lo + j] = seqs[b] + [tok], tsc[b] + [t_sc], v
+        seqs, tsc = new_seqs, new_tsc
+        scores = torch.tensor(new_scores, dtype=torch.float32, device=dev)
+        n_gen += 1
+        if all(done) or n_gen >= max_new_tokens:
+            break
+        logits = step(parents, list(current))
+    pool = []
+    for g in range(G):
+        if not done[g]:
+            for j in range(g * s, g * s + s):
+                hyps[g].add(seqs[j], float(scores[j]), len(seqs[j]), False, tsc[j])
+        pool += hyps[g].beams
+    ranked = sorted(pool, key=lambda x: x[0])[::-1]
     results = []
     for best in ranked[:n_ret]:
         out = list(best[1])

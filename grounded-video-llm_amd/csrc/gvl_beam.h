@@ -1,5 +1,5 @@
 // gvl_beam.h -- host bookkeeping of beam search (gvl_beam_search): transformers 4.40.1 GenerationMixin._beam_search + BeamSearchScorer / BeamHypotheses [ext] for a
-// batch of one and one beam group, as grounded_video_llm_amd/beam.py restates them (`_Hyps` and the loop body of `beam_search` with sample = None).  Host-only, no HIP
+// batch of one and one beam group (GroupBeamState below: several), as grounded_video_llm_amd/beam.py restates them (`_Hyps` and the loop body of `beam_search` with sample = None).  Host-only, no HIP
 // (tests/c/beam_check.cc drives it on a CPU and tests/test_beam_host_cpu.py compares it with beam.py step by step); the per-step candidates -- the best 2k of the k x vocab
 // grid -- come from the device (gvl_beam.hip).
 //   * every score is a double: a candidate value is the fp32 the device added, widened; a hypothesis scores sum / pow((double)generated_len, length_penalty)
@@ -69,7 +69,12 @@ struct BeamState {
 
   // eos_id < 0: none.  BEAM_CONTINUE or BEAM_ERR_ARG
   int init(int num_beams, int vocab_, int max_new_tokens, int eos_id, double length_penalty, int early_stopping) {
-    if (num_beams < 2 || vocab_ < 2 * num_beams || max_new_tokens < 1 || early_stopping < EARLY_FALSE || early_stopping > EARLY_NEVER) return BEAM_ERR_ARG;
+    if (num_beams < 2) return BEAM_ERR_ARG;
+    return init_sub(num_beams, vocab_, max_new_tokens, eos_id, length_penalty, early_stopping);
+  }
+  // the same for the s >= 1 beams of one group of a GroupBeamState (a group of one beam is legal; a search of one beam is not)
+  int init_sub(int num_beams, int vocab_, int max_new_tokens, int eos_id, double length_penalty, int early_stopping) {
+    if (num_beams < 1 || vocab_ < 2 * num_beams || max_new_tokens < 1 || early_stopping < EARLY_FALSE || early_stopping > EARLY_NEVER) return BEAM_ERR_ARG;
     k = num_beams; vocab = vocab_; max_new = max_new_tokens; eos = eos_id < 0 ? -1 : eos_id;
     hyps = Hyps(); hyps.k = k; hyps.length_penalty = length_penalty; hyps.early = early_stopping;
     seqs.assign(k, std::vector<int>()); tsc.assign(k, std::vector<float>());
@@ -124,20 +129,29 @@ struct BeamState {
   // sorted(beams, key = score), best first -- among equal scores the LATER added comes first.  Per hypothesis: its new ids (eos included when it ended by eos and there
   // is room), its score, one transition score per id.  Returns how many were written (n; fewer only if fewer hypotheses exist).
   int finalize_n(int n, std::vector<std::vector<int>>* ids, std::vector<double>* score, std::vector<std::vector<float>>* transition) {
-    if (!done) for (int j = 0; j < k; ++j) hyps.add(seqs[j], (double)scores[j], (int)seqs[j].size(), false, tsc[j]);
-    std::vector<size_t> order(hyps.beams.size());
+    add_open();
+    std::vector<const Hyp*> pool;
+    for (const Hyp& h : hyps.beams) pool.push_back(&h);
+    return emit_best(pool, n, eos, max_new, ids, score, transition);
+  }
+  // finalize()'s first half: unless the search is done, the open beams become hypotheses
+  void add_open() { if (!done) for (int j = 0; j < k; ++j) hyps.add(seqs[j], (double)scores[j], (int)seqs[j].size(), false, tsc[j]); }
+  // ... and its second half over `pool` (hypotheses in the order they were added; GroupBeamState pools several Hyps): the n best, best first
+  static int emit_best(const std::vector<const Hyp*>& pool, int n, int eos, int max_new, std::vector<std::vector<int>>* ids, std::vector<double>* score,
+                       std::vector<std::vector<float>>* transition) {
+    std::vector<size_t> order(pool.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = i;
     // descending score, the later added first among equals: the reverse of Python's stable ascending sort
     for (size_t i = 1; i < order.size(); ++i)
-      for (size_t j = i; j > 0 && (hyps.beams[order[j]].score > hyps.beams[order[j - 1]].score ||
-                                   (hyps.beams[order[j]].score == hyps.beams[order[j - 1]].score && order[j] > order[j - 1])); --j) { const size_t t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+      for (size_t j = i; j > 0 && (pool[order[j]]->score > pool[order[j - 1]]->score ||
+                                   (pool[order[j]]->score == pool[order[j - 1]]->score && order[j] > order[j - 1])); --j) { const size_t t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
     if (n < 1) n = 1;
     const int m = n < (int)order.size() ? n : (int)order.size();
     if (ids) ids->clear();
     if (score) score->clear();
     if (transition) transition->clear();
     for (int r = 0; r < m; ++r) {
-      const Hyp& h = hyps.beams[order[r]];
+      const Hyp& h = *pool[order[r]];
       std::vector<int> out = h.ids;
       if (h.by_eos && eos >= 0 && (int)out.size() < max_new) out.push_back(eos);
       std::vector<float> ts = h.token_scores;
@@ -155,6 +169,58 @@ struct BeamState {
     if (ids) *ids = i1[0];
     if (score) *score = s1[0];
     if (transition) *transition = t1[0];
+  }
+};
+
+// Diverse (group) beam search (gvl_group_beam_search; transformers 4.40.1 _group_beam_search + BeamSearchScorer(num_beam_groups = G), as beam.py's group_beam_search
+// restates them): G of the states above, s = k / G beams each, ONE step counter, `done` per group.  Group g owns the global beams g*s .. g*s + s - 1.
+//   * a step consumes G candidate lists of 2s triples (flat index = LOCAL beam * vocab + token), group after group; a group that was done when the step began is not
+//     looked at: its beams leave with parent -1 and token pad (they are never read again and never become hypotheses)
+//   * parents are global: g*s + the local parent (0 at the first step: every beam continues the prompt)
+//   * the search is over when every group is done or max_new_tokens ids exist; then every open group adds its beams and the hypotheses of all groups are pooled in group
+//     order and ranked as one BeamState ranks its own
+struct GroupBeamState {
+  int k = 0, G = 0, s = 0, vocab = 0, max_new = 0, eos = -1, pad = -1, n_gen = 0;
+  std::vector<BeamState> groups;
+  bool finished = false;
+
+  // pad_id < 0: an id that counts nowhere (-1).  BEAM_CONTINUE or BEAM_ERR_ARG
+  int init(int num_beams, int num_groups, int vocab_, int max_new_tokens, int eos_id, int pad_id, double length_penalty, int early_stopping) {
+    if (num_groups < 2 || num_beams < num_groups || num_beams % num_groups != 0) return BEAM_ERR_ARG;
+    k = num_beams; G = num_groups; s = k / G; vocab = vocab_; max_new = max_new_tokens; eos = eos_id < 0 ? -1 : eos_id; pad = pad_id < 0 ? -1 : pad_id; n_gen = 0;
+    finished = false;
+    groups.assign(G, BeamState());
+    for (BeamState& b : groups) if (b.init_sub(s, vocab, max_new, eos_id, length_penalty, early_stopping) < 0) return BEAM_ERR_ARG;
+    return BEAM_CONTINUE;
+  }
+  bool group_done(int g) const { return groups[g].done; }
+  float score(int beam) const { return groups[beam / s].done ? 0.f : groups[beam / s].scores[beam % s]; }
+  const std::vector<int>& seq(int beam) const { return groups[beam / s].seqs[beam % s]; }
+
+  // vals / idx / proc [G][n]: group g's candidates at + g * n (n = 2s from the device; a done group's are not read).  parents / tokens [k].  BEAM_CONTINUE,
+  // BEAM_FINISHED or < 0 as BeamState::step
+  int step(const float* vals, const int* idx, const float* proc, int n, int* parents, int* tokens) {
+    if (finished || !parents || !tokens) return BEAM_ERR_ARG;
+    bool all_done = true;
+    for (int g = 0; g < G; ++g) {
+      BeamState& b = groups[g];
+      if (b.done) { for (int j = 0; j < s; ++j) { parents[g * s + j] = -1; tokens[g * s + j] = pad; } continue; }
+      const int rc = b.step(vals + (size_t)g * n, idx + (size_t)g * n, proc + (size_t)g * n, n, parents + g * s, tokens + g * s);
+      if (rc < 0) return rc;
+      b.finished = false;                                  // the group's own end is not the search's: `done` alone keeps it from being stepped again
+      if (n_gen > 0) for (int j = 0; j < s; ++j) parents[g * s + j] += g * s;
+      all_done = all_done && b.done;
+    }
+    ++n_gen;
+    if (all_done || n_gen >= max_new) { finished = true; return BEAM_FINISHED; }
+    return BEAM_CONTINUE;
+  }
+
+  // after BEAM_FINISHED, once: the n best hypotheses over all groups (1 <= n <= k), as BeamState::finalize_n
+  int finalize_n(int n, std::vector<std::vector<int>>* ids, std::vector<double>* score_, std::vector<std::vector<float>>* transition) {
+    std::vector<const Hyp*> pool;
+    for (BeamState& b : groups) { b.add_open(); for (const Hyp& h : b.hyps.beams) pool.push_back(&h); }
+    return BeamState::emit_best(pool, n, eos, max_new, ids, score_, transition);
   }
 };
 

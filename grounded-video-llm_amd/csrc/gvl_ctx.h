@@ -116,6 +116,8 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   // beam search (gvl_beam.hip), allocated by the first call that needs them: the per-row survivors between the two candidate launches, one step's candidates in HOST-MAPPED
   // memory (h_ / d_ views), [GVL_MAX_DECODE_BATCH][vocab] work rows, and the beams' histories + lengths for the logits processors
   void* d_beam_scratch = nullptr; void* h_beam_cand = nullptr; void* d_beam_cand = nullptr; float* d_beam_rows = nullptr; int* d_beam_hist = nullptr;
+  std::vector<int> group_beam_tokens;          // gvl_group_beam_search: the tokens the device chose, step-major [steps][k] (gvl_debug_group_beam_tokens)
+  std::vector<int> group_beam_pool;            // ... and behind every step's cache reorder (clones the search holds, free KV pages) (gvl_debug_group_beam_pool)
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
   // replayed (hipGraph) for the following tokens -- the host pays one graph launch per token instead of the step's kernel launches
   // (decode_plan, gvl_decode_plan.h: 4 * layers + 1 projections + `layers` attention launches + 1 or 1 + 2 * layers in front + token selection)

@@ -387,6 +387,12 @@ int gvl_launch_select_rows(const SelRowsArgs& a, hipStream_t st);
 // proc [2k]: the best 2k of the k x n grid in the order (value descending, flat index beam * n + token ascending) -- value = fp32(log-prob + scores[beam]), proc = the log-prob.
 struct BeamCandArgs { const float* rows; int n, k, row_stride, norm; float scores[GVL_MAX_DECODE_BATCH]; float* row_v; int* row_i; float* row_lp; float* vals; int* idx; float* proc; };
 int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st);
+// One GROUP of diverse beam search (gvl_group_beam_search): c describes the group's s = c.k rows (1 .. 16; n >= 2s), scores and the 2s outputs exactly as above; behind the
+// merge the same wave writes the group's choice -- the tokens of the first s candidates that are not `eos` (eos < 0: none; fewer than s: -1 for the rest) -- to
+// current[0 .. s), device memory the next group's Hamming stage reads, and to mirror[0 .. s) (may be null).  done != 0: no candidates at all, current / mirror <- pad
+// (pad < 0: -1, an id that counts nowhere).
+struct BeamGroupArgs { BeamCandArgs c; int* current; int* mirror; int eos, pad, done; };
+int gvl_launch_beam_group(const BeamGroupArgs& a, hipStream_t st);
 int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st);      // rows [k][n] raw logits -> log-softmax, in place (beam_rows_kernel<true>'s arithmetic)
 // Classifier-free guidance (guidance_rows_kernel, gvl_pick.hip): pair p overwrites the n fp32 entries at cond[p] with scale[p] * (lc - lu) + lu, lc / lu the log-softmax
 // of cond[p] / neg[p] in beam_normalize_kernel's arithmetic; neg[p] is only read.  The conditional rows of one launch are distinct and none is another pair's negative row.
@@ -429,7 +435,10 @@ static_assert(gvl_grammar::HIST_CAP == GVL_LOGITS_HIST_CAP, "the walk covers exa
 struct LogitsProcArgs { float* logits; int n, ld, batch, cap; const int* hist[GVL_MAX_DECODE_BATCH]; const int* len_ptrs[GVL_MAX_DECODE_BATCH];
                         float penalty[GVL_MAX_DECODE_BATCH]; int ngram[GVL_MAX_DECODE_BATCH], min_new[GVL_MAX_DECODE_BATCH], eos[GVL_MAX_DECODE_BATCH];
                         const TokenRulesDev* rules[GVL_MAX_DECODE_BATCH];
-                        const GrammarDev* grammar[GVL_MAX_DECODE_BATCH]; };
+                        const GrammarDev* grammar[GVL_MAX_DECODE_BATCH];
+                        // diverse beam search (after every field the other instantiations read): ham_n[b] > 0 in any row selects logits_process_hamming_kernel --
+                        // row b loses ham_lambda[b] x (how often the token occurs among the ham_n[b] <= 16 ids at ham_tok[b], DEVICE memory read at run time)
+                        const int* ham_tok[GVL_MAX_DECODE_BATCH]; int ham_n[GVL_MAX_DECODE_BATCH]; float ham_lambda[GVL_MAX_DECODE_BATCH]; };
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st);
 // x[b][:] = table[*tok_ptrs[b]][:] for the sequences of the batched decode loop
 struct TokPtrs { const int* p[GVL_MAX_DECODE_BATCH]; int n; };

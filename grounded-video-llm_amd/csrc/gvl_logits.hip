@@ -7,6 +7,8 @@
 // Token rules (gvl_rules_create; TokenRulesDev in gvl_internal.h) add HF's other token-level processors around them, in HF's order:
 //   SequenceBiasLogitsProcessor        BEFORE the penalty: s[t] += the fp32 sum (from 0.0f) of t's length-1 bias, then of every multi-token entry
 //                                      ending in t whose first len - 1 ids equal the last len - 1 history ids; entries longer than the history are skipped
+//   HammingDiversityLogitsProcessor    (diverse beam search, later groups only) after sequence_bias, BEFORE the penalty: s[t] -= fp32(lambda * count of t among
+//                                      the tokens the earlier groups chose at this step), the list read from device memory
 //   NoBadWordsLogitsProcessor          after the n-gram bans: the same mechanism with bias -inf
 //   PrefixConstrainedLogitsProcessor   after the min-length ban: a decoding grammar (gvl_grammar_create, gvl_grammar.h) -- allowed s[t] += 0.0f, forbidden -inf
 //   ForcedEOSTokenLogitsProcessor      after the grammar, when the history holds force_at ids: every score -inf, the forced ids 0
@@ -81,9 +83,15 @@ __device__ __forceinline__ void grammar_stage(float* s, int n, const GrammarDev*
   }
 }
 
-template <bool RULES, bool GRAMMAR>
-__global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcArgs a) {
+// HAMMING = true (with RULES and GRAMMAR: one more instantiation, logits_process_hamming_kernel) is the launch for a later group of diverse beam search: HF's
+// HammingDiversityLogitsProcessor, after sequence_bias and before the penalty's gather.  ham_tok[b] lists the ham_n[b] <= 16 tokens the earlier groups chose at this
+// step -- in DEVICE memory, read at run time: the previous group's choice is made by the kernel in front of this one (beam_group_merge_kernel).  The thread that holds a
+// listed token's FIRST occurrence counts its occurrences c and stores once: s[t] = fp32(s[t] - fp32(lambda * fp32(c))), the product rounded, then one subtract (torch's
+// `scores -= lambda * bincount` on fp32).  Ids outside [0, n) are ignored.  Its barrier is unconditional: uniform per block.
+template <bool RULES, bool GRAMMAR, bool HAMMING>
+__device__ __forceinline__ void logits_process_rows(const LogitsProcArgs& a) {
   static_assert(RULES || !GRAMMAR, "the grammar instantiation carries the rules");
+  static_assert(!HAMMING || (RULES && GRAMMAR), "the Hamming instantiation carries the rules and the grammar");
   __shared__ int h[GVL_LOGITS_HIST_CAP];
   const int b = blockIdx.x, tid = threadIdx.x;
   float* s = a.logits + (size_t)b * a.ld;
@@ -102,6 +110,25 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcAr
   __syncthreads();
   if constexpr (RULES) {                                     // sequence_bias lands before the penalty's gather
     if (R.n_tgt[0] > 0) bias_stage(s, a.n, blob, R, 0, h, L, tid);
+    __syncthreads();
+  }
+  if constexpr (HAMMING) {
+    const int hn = a.ham_n[b] < GVL_MAX_DECODE_BATCH ? a.ham_n[b] : GVL_MAX_DECODE_BATCH;
+    if (tid < hn) {
+      const int* ht = a.ham_tok[b];
+      const int tk = ht[tid];
+      if (tk >= 0 && tk < a.n) {
+        int c = 0; bool first = true;
+        for (int j = 0; j < hn; ++j) if (ht[j] == tk) { ++c; first = first && j >= tid; }
+        if (first) {
+          // __fsub_rn(s, __fmul_rn(lambda, c)) in plain operators with contraction OFF for this block: the _rn wrappers are ordinary operators, and with contraction
+          // allowed the multiply and the subtract fuse into one FMA -- one rounding instead of two, 1 ulp off torch's two ops (guidance_rows_kernel's lesson)
+#pragma clang fp contract(off)
+          const float pr = a.ham_lambda[b] * (float)c;
+          s[tk] = s[tk] - pr;
+        }
+      }
+    }
     __syncthreads();
   }
   if (pen) {
@@ -152,17 +179,23 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcAr
       for (int j = tid; j < R.n_begin; j += 1024) { const int tk = blob[R.off_begin + j]; if (tk >= 0 && tk < a.n) s[tk] = -INFINITY; }
   }
 }
+template <bool RULES, bool GRAMMAR>
+__global__ __launch_bounds__(1024) void logits_process_kernel(const LogitsProcArgs a) { logits_process_rows<RULES, GRAMMAR, false>(a); }
+__global__ __launch_bounds__(1024) void logits_process_hamming_kernel(const LogitsProcArgs a) { logits_process_rows<true, true, true>(a); }
 
 int gvl_launch_logits_process(const LogitsProcArgs& a, hipStream_t st) {
   if (a.batch < 1 || a.batch > GVL_MAX_DECODE_BATCH || !a.logits || a.n < 1 || a.ld < a.n || a.cap < 0 || a.cap > GVL_LOGITS_HIST_CAP) return -1;
-  bool rules = false, grammar = false;
+  bool rules = false, grammar = false, hamming = false;
   for (int b = 0; b < a.batch; ++b) {
+    if (a.ham_n[b] < 0 || a.ham_n[b] > GVL_MAX_DECODE_BATCH || (a.ham_n[b] > 0 && (!a.ham_tok[b] || !(a.ham_lambda[b] == a.ham_lambda[b])))) return -1;
+    hamming = hamming || a.ham_n[b] > 0;
     if (!(a.penalty[b] > 0.f) || a.ngram[b] < 0 || a.min_new[b] < 0) return -1;
     if (a.cap > 0 && (a.penalty[b] != 1.0f || a.ngram[b] > 0 || a.rules[b] || a.grammar[b]) && a.len_ptrs[b] && !a.hist[b]) return -1;
     rules = rules || a.rules[b];
     grammar = grammar || a.grammar[b];
   }
-  if (grammar) hipLaunchKernelGGL((logits_process_kernel<true, true>), dim3(a.batch), dim3(1024), 0, st, a);
+  if (hamming) hipLaunchKernelGGL(logits_process_hamming_kernel, dim3(a.batch), dim3(1024), 0, st, a);
+  else if (grammar) hipLaunchKernelGGL((logits_process_kernel<true, true>), dim3(a.batch), dim3(1024), 0, st, a);
   else if (rules) hipLaunchKernelGGL((logits_process_kernel<true, false>), dim3(a.batch), dim3(1024), 0, st, a);
   else hipLaunchKernelGGL((logits_process_kernel<false, false>), dim3(a.batch), dim3(1024), 0, st, a);
   return CHECK_LAUNCH();

@@ -540,9 +540,9 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const BeamCandArgs a) {
     a.row_v[o] = c_t[tid]; a.row_i[o] = mi; a.row_lp[o] = c_lp[tid];
   }
 }
-__global__ __launch_bounds__(64) void beam_merge_kernel(const BeamCandArgs a) {
-  __shared__ unsigned mk[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
-  __shared__ int mi[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+// the merge of one wave, shared by beam_merge_kernel and beam_group_merge_kernel; sorted (null or LDS [2k]): the merged flat indices, rank by rank, for the caller
+__device__ __forceinline__ void beam_merge_wave(const BeamCandArgs& a, unsigned (&mk)[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND], int (&mi)[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND],
+                                                int* sorted) {
   const int lane = threadIdx.x, K2 = 2 * a.k, total = a.k * K2;
   for (int e = lane; e < total; e += 64) { mk[e] = beam_key(a.row_v[e]); mi[e] = (e / K2) * a.n + a.row_i[e]; }
   __syncthreads();
@@ -558,7 +558,40 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const BeamCandArgs a) {
       }
       rank += lo;
     }
-    if (rank < K2) { a.vals[rank] = a.row_v[e]; a.idx[rank] = ie; a.proc[rank] = a.row_lp[e]; }
+    if (rank < K2) { a.vals[rank] = a.row_v[e]; a.idx[rank] = ie; a.proc[rank] = a.row_lp[e]; if (sorted) sorted[rank] = ie; }
+  }
+}
+__global__ __launch_bounds__(64) void beam_merge_kernel(const BeamCandArgs a) {
+  __shared__ unsigned mk[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+  __shared__ int mi[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+  beam_merge_wave(a, mk, mi, nullptr);
+}
+// One group of diverse beam search (BeamGroupArgs): the merge over the group's s rows, then the group's CHOICE as HF's BeamSearchScorer.process makes it -- the tokens of the
+// first s candidates, in candidate order, that are not eos -- written to `current` for the next group's Hamming stage (logits_process_hamming_kernel, the next launch on the
+// stream) and to the host's mirror.  Lane j finds the j-th non-eos candidate by counting the non-eos candidates in front of each rank: integer counts over <= 32 LDS
+// entries.  A done group has no candidates: its s entries are the pad id.  Every index is bounded by s <= 16 and 2s <= 32 whatever the rows hold.
+__global__ __launch_bounds__(64) void beam_group_merge_kernel(const BeamGroupArgs g) {
+  __shared__ unsigned mk[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+  __shared__ int mi[GVL_MAX_DECODE_BATCH * GVL_BEAM_MAX_CAND];
+  __shared__ int sorted[GVL_BEAM_MAX_CAND];
+  const int lane = threadIdx.x, s = g.c.k, K2 = 2 * s;
+  if (g.done) {
+    if (lane < s) { const int t = g.pad < 0 ? -1 : g.pad; g.current[lane] = t; if (g.mirror) g.mirror[lane] = t; }
+    return;
+  }
+  if (lane < K2) sorted[lane] = -1;
+  __syncthreads();
+  beam_merge_wave(g.c, mk, mi, sorted);
+  __syncthreads();
+  if (lane < s) { g.current[lane] = -1; if (g.mirror) g.mirror[lane] = -1; }
+  __syncthreads();
+  if (lane < K2 && sorted[lane] >= 0) {
+    const int tok = sorted[lane] % g.c.n;
+    if (tok != g.eos) {
+      int before = 0;
+      for (int r = 0; r < lane; ++r) before += (sorted[r] >= 0 && sorted[r] % g.c.n != g.eos) ? 1 : 0;
+      if (before < s) { g.current[before] = tok; if (g.mirror) g.mirror[before] = tok; }
+    }
   }
 }
 __global__ __launch_bounds__(1024) void beam_normalize_kernel(float* rows, int n) {
@@ -574,6 +607,17 @@ int gvl_launch_beam_candidates(const BeamCandArgs& a, hipStream_t st) {
   if (a.norm) hipLaunchKernelGGL(beam_rows_kernel<true>, dim3(a.k), dim3(1024), 0, st, a);
   else hipLaunchKernelGGL(beam_rows_kernel<false>, dim3(a.k), dim3(1024), 0, st, a);
   hipLaunchKernelGGL(beam_merge_kernel, dim3(1), dim3(64), 0, st, a);
+  return CHECK_LAUNCH();
+}
+int gvl_launch_beam_group(const BeamGroupArgs& g, hipStream_t st) {
+  const BeamCandArgs& a = g.c;
+  if (a.k < 1 || a.k > GVL_MAX_DECODE_BATCH || !g.current) return -1;
+  if (!g.done) {
+    if (a.n < 2 * a.k || (long long)a.n * a.k > 0x7fffffffLL || !a.rows || a.row_stride < 0 || !a.row_v || !a.row_i || !a.row_lp || !a.vals || !a.idx || !a.proc) return -1;
+    if (a.norm) hipLaunchKernelGGL(beam_rows_kernel<true>, dim3(a.k), dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL(beam_rows_kernel<false>, dim3(a.k), dim3(1024), 0, st, a);
+  }
+  hipLaunchKernelGGL(beam_group_merge_kernel, dim3(1), dim3(64), 0, st, g);
   return CHECK_LAUNCH();
 }
 int gvl_launch_beam_normalize(float* rows, int n, int k, hipStream_t st) {

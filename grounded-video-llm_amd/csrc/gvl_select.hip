@@ -88,10 +88,12 @@ int gvl_seq_set_processors(gvl_ctx* ctx, int seq_id, float penalty, int ngram, i
 }
 // the processors, with rules_ids (entry points gvl_op_logits_process_rules / _ex) the rule sets and with grammar_ids (gvl_op_logits_process_ex) the grammars, on `batch` rows of logits
 static int op_logits_process(gvl_ctx* ctx, const char* what, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
-                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream, const int* grammar_ids = nullptr) {
+                             const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream, const int* grammar_ids = nullptr,
+                             const int32_t* ham_dev = nullptr, int n_ham = 0, float ham_lambda = 0.f) {
   if (!ctx || !logits || !lens_dev || !penalty || !ngram || !min_new || !eos_ids || n < 1 || batch < 1 || batch > GVL_MAX_DECODE_BATCH ||
       hist_stride < 0 || (hist_stride > 0 && !hist_dev))
     return fail(ctx, GVL_ERR_ARG, std::string(what) + ": bad arguments");
+  if (n_ham < 0 || n_ham > GVL_MAX_DECODE_BATCH || (n_ham > 0 && (!ham_dev || !(ham_lambda == ham_lambda)))) return fail(ctx, GVL_ERR_ARG, std::string(what) + ": 0 .. 16 Hamming tokens on the device and a penalty that is a number");
   hipStream_t st = (hipStream_t)stream;
   LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
   lp.logits = logits; lp.n = n; lp.ld = n; lp.batch = batch; lp.cap = hist_stride < GVL_LOGITS_HIST_CAP ? hist_stride : GVL_LOGITS_HIST_CAP;
@@ -101,6 +103,7 @@ static int op_logits_process(gvl_ctx* ctx, const char* what, float* logits, int 
     lp.hist[b] = hist_dev ? hist_dev + (size_t)b * hist_stride : nullptr; lp.len_ptrs[b] = lens_dev + b;
     lp.penalty[b] = penalty[b]; lp.ngram[b] = ngram[b]; lp.eos[b] = eos_ids[b] < 0 ? -1 : eos_ids[b]; lp.min_new[b] = lp.eos[b] >= 0 ? min_new[b] : 0;
     lp.rules[b] = rules_ids && rules_ids[b] >= 0 ? (const TokenRulesDev*)ctx->rule_sets[rules_ids[b]].d : nullptr;
+    lp.ham_tok[b] = ham_dev; lp.ham_n[b] = n_ham; lp.ham_lambda[b] = ham_lambda;
     if (grammar_ids && grammar_ids[b] != -1) {
       if (const int rc = ctx->check_grammar(grammar_ids[b])) return seq_fail(ctx, what, rc);
       const GrammarSet& g = ctx->grammars[grammar_ids[b]];
@@ -211,6 +214,12 @@ int gvl_op_logits_process_rules(gvl_ctx* ctx, float* logits, int n, int batch, c
                                 const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, void* stream) {
   if (!rules_ids) return fail(ctx, GVL_ERR_ARG, "gvl_op_logits_process_rules: bad arguments");
   return op_logits_process(ctx, "gvl_op_logits_process_rules", logits, n, batch, hist_dev, hist_stride, lens_dev, penalty, ngram, min_new, eos_ids, rules_ids, stream);
+}
+int gvl_op_logits_process_hamming(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                                  const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, const int* grammar_ids,
+                                  const int32_t* ham_tokens_dev, int n_ham, float diversity_penalty, void* stream) {
+  return op_logits_process(ctx, "gvl_op_logits_process_hamming", logits, n, batch, hist_dev, hist_stride, lens_dev, penalty, ngram, min_new, eos_ids, rules_ids, stream, grammar_ids,
+                           ham_tokens_dev, n_ham, diversity_penalty);
 }
 int gvl_op_logits_process_ex(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
                              const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, const int* grammar_ids, void* stream) {

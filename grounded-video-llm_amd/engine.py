@@ -579,6 +579,71 @@ class Engine:
             res.append((out, score[r], [float(ts[r * cap + i]) for i in range(n[r])]) if with_scores else out)
         return res[0] if nr == 1 else res
 
+    def op_beam_group(self, rows: Optional[torch.Tensor], scores, eos: Optional[int] = None, pad: Optional[int] = None, logprobs: bool = True, stride0: bool = False,
+                      done: bool = False, s: Optional[int] = None):
+        """gvl_op_beam_group: ONE group of a diverse beam search step -- op_beam_candidates for the group's s rows [s, n] (s = len(scores), 1 .. 16) -> (vals [2s], idx
+        int32 [2s] local beam * n + token, proc [2s], chosen int32 [s]) on the device; chosen = the tokens of the first s candidates that are not eos (-1 where there are
+        fewer).  done: the group is finished -- no candidates (the first three are None), chosen [s] = pad (None: -1); give s."""
+        if done:
+            chosen = torch.full((int(s),), -7, dtype=torch.int32, device=self.device)
+            self._chk(self.lib.gvl_op_beam_group(self.ctx, None, 0, int(s), 0, None, 1, -1 if eos is None else int(eos), -1 if pad is None else int(pad), 1, None, None, None,
+                                                 _ptr(chosen), self.stream), "gvl_op_beam_group")
+            return None, None, None, chosen
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.device == self.device
+        sc = [float(x) for x in (scores.tolist() if isinstance(scores, torch.Tensor) else scores)]
+        s_, n = len(sc), rows.shape[-1]
+        if not stride0 and (rows.dim() != 2 or rows.shape[0] != s_):
+            raise ValueError(f"op_beam_group: {s_} scores for rows of shape {tuple(rows.shape)}")
+        vals = torch.full((2 * s_,), float("nan"), dtype=torch.float32, device=self.device)
+        idx = torch.full((2 * s_,), -1, dtype=torch.int32, device=self.device)
+        proc = torch.full((2 * s_,), float("nan"), dtype=torch.float32, device=self.device)
+        chosen = torch.full((s_,), -7, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.gvl_op_beam_group(self.ctx, _ptr(rows), n, s_, 0 if stride0 else n, (C.c_float * s_)(*sc), int(bool(logprobs)), -1 if eos is None else int(eos),
+                                             -1 if pad is None else int(pad), 0, _ptr(vals), _ptr(idx), _ptr(proc), _ptr(chosen), self.stream), "gvl_op_beam_group")
+        return vals, idx, proc, chosen
+
+    def group_beam_search(self, seq: int, first_logits: torch.Tensor, num_beams: int, num_beam_groups: int, diversity_penalty: float, max_new: int, eos: Optional[int],
+                          pad: Optional[int] = None, length_penalty: float = 1.0, early_stopping=False, processors=None, rules: Optional[int] = None,
+                          with_scores: bool = False, num_return: int = 1):
+        """gvl_group_beam_search: HF diverse (group) beam search (num_beams = k, num_beam_groups = G, diversity_penalty) from the PREFILLED sequence `seq`, inside the
+        library; everything else as beam_search.  pad: the token of a finished group's beams (None: an id no later group counts)."""
+        if early_stopping not in (False, True, "never"):
+            raise ValueError("early_stopping must be False, True or 'never'")
+        assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.device == self.device
+        pe, ng, mn, pe_eos = processors.args() if processors is not None else (1.0, 0, 0, None)
+        base = L.GvlBeamParams(int(num_beams), int(max_new), -1 if eos is None else int(eos), float(length_penalty), {False: 0, True: 1, "never": 2}[early_stopping],
+                               float(pe), int(ng), int(mn), -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
+        prm = L.GvlGroupBeamParams(base, int(num_beam_groups), float(diversity_penalty), -1 if pad is None else int(pad))
+        cap, nr = max(int(max_new), 1), int(num_return)
+        if nr < 1 or nr > int(num_beams):
+            raise ValueError("num_return must be 1 .. num_beams")
+        ids = (C.c_int32 * (cap * nr))()
+        ts = (C.c_float * (cap * nr))()
+        n, score = (C.c_int * nr)(), (C.c_double * nr)()
+        self._chk(self.lib.gvl_group_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), nr, ids, cap, n, score, ts, self.stream), "gvl_group_beam_search")
+        res = []
+        for r in range(nr):
+            out = [int(ids[r * cap + i]) for i in range(n[r])]
+            res.append((out, score[r], [float(ts[r * cap + i]) for i in range(n[r])]) if with_scores else out)
+        return res[0] if nr == 1 else res
+
+    def group_beam_tokens(self, num_beams: int) -> List[List[int]]:
+        """gvl_debug_group_beam_tokens: per step of the last group_beam_search, the num_beams tokens the DEVICE chose (a finished group's: its pad)."""
+        n = C.c_int(0)
+        self._chk(self.lib.gvl_debug_group_beam_tokens(self.ctx, None, 0, C.byref(n)), "gvl_debug_group_beam_tokens")
+        buf = (C.c_int32 * max(n.value, 1))()
+        self._chk(self.lib.gvl_debug_group_beam_tokens(self.ctx, buf, n.value, C.byref(n)), "gvl_debug_group_beam_tokens")
+        k = int(num_beams)
+        return [[int(buf[i * k + j]) for j in range(k)] for i in range(n.value // k)]
+
+    def group_beam_pool(self) -> List[Tuple[int, int]]:
+        """gvl_debug_group_beam_pool: behind every step's cache reorder of the last group_beam_search (every step but the last), (clones the search held, free KV pages)."""
+        n = C.c_int(0)
+        self._chk(self.lib.gvl_debug_group_beam_pool(self.ctx, None, 0, C.byref(n)), "gvl_debug_group_beam_pool")
+        buf = (C.c_int32 * max(n.value, 1))()
+        self._chk(self.lib.gvl_debug_group_beam_pool(self.ctx, buf, n.value, C.byref(n)), "gvl_debug_group_beam_pool")
+        return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n.value // 2)]
+
     def generate_ids(self, embeds: torch.Tensor, max_new_tokens: int, eos_id: Optional[int], processors=None, logprobs: Optional[int] = None,
                      rules: Optional[int] = None, grammar: Optional[int] = None):
         """language_model.generate(inputs_embeds=..., greedy): returns only the NEW ids (eos included).  grammar: a grammar_create id for this sequence (None: the
@@ -789,12 +854,14 @@ class Engine:
         self._chk(self.lib.gvl_seq_set_processors(self.ctx, int(seq), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
                                                   -1 if eos_id is None else int(eos_id)), "gvl_seq_set_processors")
 
-    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos, rules=None, grammar=None):
+    def op_logits_process(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], penalty, ngram, min_new, eos, rules=None, grammar=None, hamming=None):
         """gvl_op_logits_process on fp32 rows [B, n] (any B; 16 rows per launch): row b gets the processors (penalty[b], ngram[b], min_new[b],
         eos[b]) over the history histories[b].  `logits` must be a contiguous fp32 device tensor: it is changed IN PLACE and returned.
         rules: None, one rule-set id (rules_create) for every row, or a list with an id or None per row -- then gvl_op_logits_process_rules
         runs the whole ordered pipeline (token rules around the processors).  grammar: the same for grammar ids (grammar_create; the grammar's
-        vocab must equal n) -- then gvl_op_logits_process_ex runs the pipeline with the grammar stage in HF's place."""
+        vocab must equal n) -- then gvl_op_logits_process_ex runs the pipeline with the grammar stage in HF's place.
+        hamming: (tokens, diversity_penalty) -- gvl_op_logits_process_hamming: HF's HammingDiversityLogitsProcessor in its place (behind sequence_bias, in front of the
+        repetition penalty) on every row; tokens = 0 .. 16 ids, a list (uploaded here) or an int32 device tensor (what the group candidate launch left)."""
         assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2 and logits.device == self.device
         B, n = logits.shape
         assert len(histories) == B
@@ -809,12 +876,21 @@ class Engine:
         pe, ng, mn, eo = per_row(penalty, float), per_row(ngram, int), per_row(min_new, int), per_row(eos, lambda x: -1 if x is None else int(x))
         ru = None if rules is None else per_row(rules, lambda x: -1 if x is None else int(x))
         gr = None if grammar is None else per_row(grammar, lambda x: -1 if x is None else int(x))
+        ham = None
+        if hamming is not None:
+            ham = hamming[0] if isinstance(hamming[0], torch.Tensor) else torch.tensor([int(t) for t in hamming[0]], dtype=torch.int32, device=self.device)
+            assert ham.dtype == torch.int32 and ham.is_contiguous() and ham.device == self.device and ham.numel() <= 16
         for b0 in range(0, B, 16):
             nb = min(16, B - b0)
             args = (self.ctx, C.c_void_p(logits.data_ptr() + b0 * n * 4), n, nb, C.c_void_p(hist.data_ptr() + b0 * width * 4),
                     width, C.c_void_p(lens.data_ptr() + b0 * 4), (C.c_float * nb)(*pe[b0:b0 + nb]), (C.c_int * nb)(*ng[b0:b0 + nb]),
                     (C.c_int * nb)(*mn[b0:b0 + nb]), (C.c_int * nb)(*eo[b0:b0 + nb]))
-            if gr is not None:
+            if ham is not None:
+                rr = None if ru is None else (C.c_int * nb)(*ru[b0:b0 + nb])
+                gg = None if gr is None else (C.c_int * nb)(*gr[b0:b0 + nb])
+                self._chk(self.lib.gvl_op_logits_process_hamming(*args, rr, gg, C.c_void_p(ham.data_ptr()) if ham.numel() else None, int(ham.numel()),
+                                                                 float(hamming[1]), self.stream), "gvl_op_logits_process_hamming")
+            elif gr is not None:
                 rr = None if ru is None else (C.c_int * nb)(*ru[b0:b0 + nb])
                 self._chk(self.lib.gvl_op_logits_process_ex(*args, rr, (C.c_int * nb)(*gr[b0:b0 + nb]), self.stream), "gvl_op_logits_process_ex")
             elif ru is None:

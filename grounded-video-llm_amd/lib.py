@@ -63,6 +63,11 @@ class GvlBeamParams(C.Structure):
                 ("penalty", C.c_float), ("ngram", C.c_int), ("min_new", C.c_int), ("proc_eos_id", C.c_int), ("rules_id", C.c_int)]
 
 
+class GvlGroupBeamParams(C.Structure):
+    """gvl_group_beam_params (include/gvl.h)."""
+    _fields_ = [("base", GvlBeamParams), ("num_beam_groups", C.c_int), ("diversity_penalty", C.c_float), ("pad_id", C.c_int)]
+
+
 class GvlDecodeProj(C.Structure):
     """gvl_decode_proj (include/gvl.h): one decode projection with any prologue / epilogue, for the operator tests."""
     _fields_ = [("path", C.c_int32), ("variant", C.c_int32), ("w_fmt", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("batch", C.c_int32),
@@ -216,6 +221,15 @@ _SIGS = {
                                     C.POINTER(C.c_float), C.c_void_p]),
     "gvl_op_beam_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvl_op_beam_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_group_beam_search": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GvlGroupBeamParams), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p]),
+    "gvl_debug_group_beam_tokens": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
+    "gvl_debug_group_beam_pool": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
+    "gvl_op_beam_group": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gvl_op_logits_process_hamming": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float),
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "gvl_op_gemv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)

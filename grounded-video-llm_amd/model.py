@@ -14,7 +14,7 @@ from __future__ import annotations
 import dataclasses
 
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -59,6 +59,19 @@ def num_return_sequences(kw) -> int:
     if LP.resolve_guidance(kw) is not None:
         raise ValueError("generate(): guidance_scale with num_return_sequences > 1 is not supported yet")
     return n
+
+
+def beam_groups(kw) -> Optional[Tuple[int, float]]:
+    """generate()'s num_beam_groups / diversity_penalty: None for plain decoding (1 / 0.0 / absent), else (G, lambda) after HF's validation (beam.check_groups) as
+    ValueError; the combinations that are not built -- groups with guidance_scale, groups with constrained beams -- are refused, never ignored."""
+    from . import beam as B
+    if not B.check_groups(kw.get("num_beams", 1) or 1, kw.get("num_beam_groups"), kw.get("diversity_penalty"), bool(kw.get("do_sample", False))):
+        return None
+    if LP.resolve_guidance(kw) is not None:
+        raise ValueError("generate(): num_beam_groups > 1 with guidance_scale is not supported")
+    if kw.get("constraints") or kw.get("force_words_ids"):
+        raise ValueError("generate(): constrained beams (constraints / force_words_ids) with num_beam_groups > 1 are not supported")
+    return int(kw["num_beam_groups"]), float(kw["diversity_penalty"])
 
 
 def fanout_stream(prompt: int, member: int) -> int:
@@ -530,14 +543,18 @@ class LLAVA_NEXT_VIDEO:
         decode step.  Greedy and sampling; log-probabilities are then the guided distribution's.  guidance_scale != 1 without a negative prompt, with num_beams > 1,
         or in generate_shared raises ValueError (not supported yet).  Still not supported
         and ignored: bad_words_ids=None, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
-        remove_invalid_values, exponential_decay_length_penalty, diversity / constrained beams (num_beam_groups, constraints,
+        remove_invalid_values, exponential_decay_length_penalty, constrained beams (constraints,
         force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
         typical_p / epsilon_cutoff / eta_cutoff (those seven run on the device in HF's order; top_h, custom logits_warper lists stay ignored).
         return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
         log-probabilities; logprobs.py) instead of the list of texts.
         beam_impl (extra; num_beams > 1): "host" (default) = beam.py's bookkeeping with torch's log-softmax / top-2k per step; "device" = gvl_beam_search, the whole
         search inside the library (its own kernels select the candidates; sequences_scores / transition scores come from it).  "device" with do_sample=True raises
-        ValueError: beam-sample stays on beam.py, its draws are torch's."""
+        ValueError: beam-sample stays on beam.py, its draws are torch's.
+        num_beam_groups = G > 1 with diversity_penalty = lambda > 0 (HF's; num_beams divisible by G, do_sample=False): diverse (group) beam search -- G groups of
+        num_beams / G beams, every later group's scores lowered by lambda x how often the earlier groups chose the token at this step (HammingDiversityLogitsProcessor,
+        in HF's place behind sequence_bias); on both beam_impls, with num_return_sequences and return_dict_in_generate as for plain beams.  HF's validation errors are
+        ValueErrors; groups with guidance_scale, with constrained beams, in generate_shared or in ClipScheduler raise ValueError (not built)."""
         if any(v == "text" for v in samples.get("video_ids", [])):
             # prepare_multimodal_inputs' `video_ids == 'text'` branch (llava_next_video.py:583-586) is a TRAINING device (dummy visual
             # rows appended with mask 0 so FSDP sees every parameter); the reference's inference never produces it.  forward() handles it.
@@ -545,6 +562,7 @@ class LLAVA_NEXT_VIDEO:
         _beam_impl(generate_kwargs)                       # a bad beam_impl fails before any work
         self._check_guidance(generate_kwargs, len(samples["prompts"]))     # ... and so do the guidance arguments
         num_return_sequences(generate_kwargs)             # ... and num_return_sequences
+        beam_groups(generate_kwargs)                      # ... and num_beam_groups / diversity_penalty
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
@@ -574,9 +592,11 @@ class LLAVA_NEXT_VIDEO:
                 gen.manual_seed(seed)
                 sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen, **LP.resolve_sampling(generate_kwargs))
             scored = opts.return_dict and opts.output_scores
+            G, lam = beam_groups(generate_kwargs) or (1, 0.0)
             out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
                                               float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs), grammar=gid, num_return=n_ret)
+                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs), grammar=gid, num_return=n_ret,
+                                              num_beam_groups=G, diversity_penalty=lam)
                        for b in range(ids_arr.shape[0])]
             if n_ret > 1:                                  # the n best hypotheses of every prompt, prompt-major
                 out_ids = [r for per_prompt in out_ids for r in per_prompt]
@@ -602,8 +622,12 @@ class LLAVA_NEXT_VIDEO:
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
                           sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
-                          rules: Optional[int] = None, impl: str = "host", grammar: Optional[int] = None, num_return: int = 1):
-        """num_return > 1: a list of results, the num_return best hypotheses, best first (beam.beam_search's num_return / gvl_beam_search_n).
+                          rules: Optional[int] = None, impl: str = "host", grammar: Optional[int] = None, num_return: int = 1,
+                          num_beam_groups: int = 1, diversity_penalty: float = 0.0):
+        """num_beam_groups / diversity_penalty: anything but (1, 0.0) is diverse (group) beam search (beam.group_beam_search / gvl_group_beam_search) with the
+        tokenizer's pad_token_id as the token of a finished group's beams; on the host path the Hamming term is subtracted in torch, or -- when processors, rules or a
+        grammar are active -- inside the processor launch, in HF's place.
+        num_return > 1: a list of results, the num_return best hypotheses, best first (beam.beam_search's num_return / gvl_beam_search_n).
         generate(num_beams = k, do_sample = False): HF beam search (beam.py restates transformers 4.40.1's scorer) on the paged KV cache.  The k running
         beams are k sequences; HF's per-step cache reorder becomes gvl_seq_clone -- a beam that continues another one shares its whole KV pages by
         reference and copies only the partial last page; the first child of a parent simply keeps the parent's sequence.  All beams advance by ONE
@@ -618,6 +642,8 @@ class LLAVA_NEXT_VIDEO:
         eng = self.engine
         if impl not in ("host", "device"):
             raise ValueError(f"beam search: impl must be 'host' or 'device', not {impl!r}")
+        grouped = B.check_groups(num_beams, num_beam_groups, diversity_penalty, sample is not None)
+        pad = getattr(self.tokenizer, "pad_token_id", None)
         if impl == "device":
             if sample is not None:
                 raise ValueError("beam-sample runs on the host path only (its draws are torch's): impl='device' needs sample=None")
@@ -627,6 +653,9 @@ class LLAVA_NEXT_VIDEO:
             try:
                 LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
                 first = eng.prefill(seq, emb, want_logits=True)
+                if grouped:
+                    return eng.group_beam_search(seq, first, num_beams, num_beam_groups, diversity_penalty, max_new, eos, pad, length_penalty, early_stopping,
+                                                 processors if processors is not None and processors.active else None, rules, with_scores, num_return=num_return)
                 return eng.beam_search(seq, first, num_beams, max_new, eos, length_penalty, early_stopping,
                                        processors if processors is not None and processors.active else None, rules, with_scores, num_return=num_return)
             finally:
@@ -641,7 +670,10 @@ class LLAVA_NEXT_VIDEO:
         if (processors is not None and processors.active) or rules is not None or grammar is not None:
             pa = (processors if processors is not None else LP.OFF).args()
 
-            def process(histories: List[List[int]], logprobs: torch.Tensor) -> torch.Tensor:
+            def process(histories: List[List[int]], logprobs: torch.Tensor, group: int = 0, prev_tokens=(), diversity_penalty: float = 0.0) -> torch.Tensor:
+                if group > 0:                                # a later group of diverse beam search: the Hamming term rides in the same launch, in HF's place
+                    return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules, grammar=grammar,
+                                                 hamming=(list(prev_tokens), float(diversity_penalty)))
                 if grammar is not None:
                     return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules, grammar=grammar)
                 if rules is None:
@@ -651,7 +683,9 @@ class LLAVA_NEXT_VIDEO:
             LP.apply_seq_options(eng, beams[0], LP.SeqOptions.OFF)    # the steps must hand back raw logits, the scores come from the host rows (beam.py); clones copy these settings
             first = eng.prefill(beams[0], emb, want_logits=True)
 
-            def step(parents: List[int], toks: List[int]) -> torch.Tensor:
+            def step(parents: List[Optional[int]], toks: List[int]) -> torch.Tensor:
+                if grouped:
+                    return group_step(parents, toks)
                 keep, new = {}, [None] * len(parents)
                 for j, p_ in enumerate(parents):             # clones first: every parent is still at the length the children continue from
                     if p_ in keep:
@@ -670,7 +704,36 @@ class LLAVA_NEXT_VIDEO:
                     return eng.decode_step_logits_batch(beams, toks)        # the k beams share ONE stream of the weights
                 return torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(beams, toks)])
 
-            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process, with_scores=with_scores, num_return=num_return)
+            def group_step(parents: List[Optional[int]], toks: List[int]) -> torch.Tensor:
+                # the same reorder over the beams that live on: a finished group's beams (parent None) are freed and their rows stay zero -- nothing reads them
+                keep, new = {}, [None] * len(parents)
+                for j, p_ in enumerate(parents):
+                    if p_ is None:
+                        continue
+                    if p_ in keep:
+                        new[j] = eng.seq_clone(beams[p_], cap)
+                        fresh.append(new[j])
+                    else:
+                        keep[p_] = j
+                for p_, j in keep.items():
+                    new[j] = beams[p_]
+                losers = [s_ for p_, s_ in enumerate(beams) if p_ not in keep and s_ is not None]
+                beams[:] = new
+                del fresh[:]
+                for s_ in losers:
+                    eng.seq_free(s_)
+                live = [j for j, s_ in enumerate(beams) if s_ is not None]
+                ls, lt = [beams[j] for j in live], [toks[j] for j in live]
+                if len(ls) <= gi["max_group"] and (gi["any_size"] or len(ls) in (1, 2, 4)):
+                    got = eng.decode_step_logits_batch(ls, lt)
+                else:
+                    got = torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(ls, lt)])
+                out = torch.zeros((len(parents), got.shape[-1]), dtype=torch.float32, device=got.device)
+                out[torch.as_tensor(live, device=got.device)] = got
+                return out
+
+            return B.beam_search(step, first, num_beams, max_new, eos, length_penalty, early_stopping, sample, process=process, with_scores=with_scores, num_return=num_return,
+                                 num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty, pad_id=pad)
         finally:
             for s_ in set(x for x in list(beams) + fresh if x is not None):
                 try:
@@ -689,6 +752,8 @@ class LLAVA_NEXT_VIDEO:
             raise ValueError("generate_shared takes the pixel tensors of one video")
         if LP.resolve_guidance(generate_kwargs) is not None:
             raise ValueError("generate_shared(): guidance_scale != 1 is not supported yet (generate() takes it)")
+        if beam_groups(generate_kwargs) is not None:
+            raise ValueError("generate_shared(): num_beam_groups > 1 (diverse beam search) is not supported (generate() takes it)")
         n_ret = num_return_sequences(generate_kwargs)
         if n_ret > 1 and (generate_kwargs.get("num_beams", 1) or 1) > 1:
             raise ValueError("generate_shared(): num_return_sequences > 1 is built for sampling (do_sample=True, num_beams=1); generate() returns the n best beams")

@@ -115,7 +115,8 @@ class ClipScheduler:
                begin_suppress_tokens=None, forced_eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
                top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
                epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None,
-               grammar: Optional[int] = None, guidance_scale: Optional[float] = None, negative=None, num_return_sequences: Optional[int] = None):
+               grammar: Optional[int] = None, guidance_scale: Optional[float] = None, negative=None, num_return_sequences: Optional[int] = None,
+               num_beam_groups: Optional[int] = None, diversity_penalty: Optional[float] = None):
         """Queue one request.  embeds: the full spliced prompt.  prefix: an add_prefix() id -- the caller promises that the prompt's first P rows ARE the registered
         ones; only embeds[P:] (at least one row) is then prefilled.  An optimisation only: the result is the same without it.  (It is ignored for a request that
         LongRoPE forbids to share: P <= rope_orig_max_pos < len(embeds) -- a full prefill of that prompt ropes the shared rows with the long factors.)
@@ -141,7 +142,11 @@ class ClipScheduler:
         prompt is prefilled once; at admission the sequence is fanned out into its n - 1 siblings (Engine.seq_fanout: the prompt's KV pages are shared), answer j drawing
         from random stream j of `seed`.  The request counts as n toward max_active and is admitted only when n slots (and the KV pages of all answers) are free; from
         then on every answer is a request of its own that retires on its own eos.  Each answer's ids depend on its settings, its stream and its logits alone -- not on
-        max_active, chunk or its neighbours.  Not with guidance_scale."""
+        max_active, chunk or its neighbours.  Not with guidance_scale.
+        num_beam_groups / diversity_penalty: the scheduler decodes greedily or by sampling, never by beams -- anything but (None / 1, None / 0) raises ValueError
+        (generate() runs diverse beam search)."""
+        if num_beam_groups not in (None, 1) or diversity_penalty not in (None, 0, 0.0):
+            raise ValueError("ClipScheduler: num_beam_groups / diversity_penalty (diverse beam search) are not supported; generate() takes them")
         n_fan = 1 if num_return_sequences is None else int(num_return_sequences)
         if n_fan < 1:
             raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n_fan}")

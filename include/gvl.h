@@ -426,7 +426,7 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
  * num_return): popped from sorted(hypotheses, key = score) best first, among equal scores the later added first.  out_ids_host [num_return][cap], n_out [num_return],
  * sequences_scores [num_return] (non-increasing; may be NULL), transition_scores_host [num_return][cap] (may be NULL).  Everything else -- the search, the errors -- is
  * gvl_beam_search's, which is the num_return = 1 call.  GVL_ERR_ARG for num_return outside 1 .. num_beams.
- * Diverse (group) and constrained beams are not supported. */
+ * Diverse (group) beams are gvl_group_beam_search below; constrained beams are not supported. */
 typedef struct gvl_beam_params {
   int num_beams;            /* 2 .. 16 (GVL_MAX_DECODE_BATCH) */
   int max_new_tokens;       /* >= 1 */
@@ -440,6 +440,32 @@ int gvl_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const g
                     double* sequences_score, float* transition_scores_host, void* stream);
 int gvl_beam_search_n(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_beam_params* params, int num_return, int32_t* out_ids_host, int cap, int* n_out,
                       double* sequences_scores, float* transition_scores_host, void* stream);
+/* Diverse (group) beam search: HF generate(num_beams = k, num_beam_groups = G, diversity_penalty = lambda) (transformers 4.40.1 GenerationMixin._group_beam_search +
+ * BeamSearchScorer(num_beam_groups) + HammingDiversityLogitsProcessor [ext]; batch of one).  G groups of s = k / G beams; group g owns the beams g*s .. g*s + s - 1 and
+ * is gvl_beam_search's step with k := s (its own hypotheses, its own done flag, its own 2s candidates), beam scores -1e9 except the first beam of every group.  Per step
+ * all live beams advance by one decode step, every row is normalised once, and then per group, in order, ONE chain on the stream: the processor launch (for g > 0 with
+ * the Hamming stage in HF's place, behind sequence_bias and in front of the repetition penalty: s[t] -= fp32(lambda * count of t among the tokens the earlier groups chose
+ * at this step), the product rounded first) -> the group's row candidates -> its merge, which also writes the group's choice -- the tokens of its first s non-eos
+ * candidates -- to device memory for the next group's Hamming stage.  One stream synchronise per step; the host bookkeeping (csrc/gvl_beam.h GroupBeamState) must arrive
+ * at the tokens the device chose (GVL_ERR_HIP otherwise).  A group that was done when a step began is not processed: its beams are closed at once (their pages go back to
+ * the pool), its s entries of the step's tokens are pad_id (which later groups DO count; pad_id < 0: an id that counts nowhere), they never become hypotheses.  The search
+ * ends when every group is done or at max_new_tokens; every open group adds its beams, the hypotheses of all groups are pooled in group order and the num_return best leave
+ * as from gvl_beam_search_n (outputs, ownership and the remaining errors are that call's: seq_id is never stepped, every clone is closed on every return path).  The
+ * transition score of an id includes its Hamming term.  GVL_ERR_ARG: num_beam_groups outside 2 .. num_beams, num_beams % num_beam_groups != 0, diversity_penalty <= 0 or
+ * NaN, vocab < 2 x (num_beams / num_beam_groups).
+ * gvl_debug_group_beam_tokens: the tokens the DEVICE chose in the last gvl_group_beam_search of this context, step-major [steps][num_beams] (tests compare them with the
+ * host bookkeeping's); *n_out = how many exist, at most cap are copied.  gvl_debug_group_beam_pool: behind every step's cache reorder of that search (every step but
+ * the last) two numbers -- the clones the search held and the free KV pages: a group that finished has given its beams back by then. */
+typedef struct gvl_group_beam_params {
+  gvl_beam_params base;
+  int   num_beam_groups;    /* 2 .. num_beams, dividing it */
+  float diversity_penalty;  /* > 0 */
+  int   pad_id;             /* -1: none */
+} gvl_group_beam_params;
+int gvl_group_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_group_beam_params* params, int num_return, int32_t* out_ids_host, int cap,
+                          int* n_out, double* sequences_scores, float* transition_scores_host, void* stream);
+int gvl_debug_group_beam_tokens(gvl_ctx* ctx, int32_t* out_host, int cap, int* n_out);
+int gvl_debug_group_beam_pool(gvl_ctx* ctx, int32_t* out_host, int cap, int* n_out);
 
 /* ---- multi-GPU exchange (SURVEY.md §8 e) -------------------------------------------------------------------------------------
  * The reference's inference is single-GPU (inference.py:17); sharding the frame batch over the GPUs of a node is this build's
@@ -666,6 +692,17 @@ int gvl_op_score_rows(gvl_ctx* ctx, const float* logits_dev, int n, int ld, int 
 int gvl_op_beam_candidates(gvl_ctx* ctx, const float* rows, int n, int k, int row_stride, const float* beam_scores_host, int rows_are_logprobs, float* vals_dev,
                            int32_t* idx_dev, float* proc_dev, void* stream);
 int gvl_op_beam_normalize(gvl_ctx* ctx, float* rows, int n, int k, void* stream);
+/* One GROUP of a diverse beam search step on its own (operator tests): gvl_op_beam_candidates for the group's s rows (s 1 .. 16, n >= 2 s; outputs [2 s], flat index
+ * local beam * n + token), and the group's choice in chosen_dev [s] (device int32): the tokens of the first s candidates that are not eos_id (-1: none; fewer than s such
+ * candidates: -1 for the rest).  group_done != 0: no candidates are computed (rows / scores / outputs may be null), chosen_dev [s] <- pad_id (< 0: -1). */
+int gvl_op_beam_group(gvl_ctx* ctx, const float* rows, int n, int s, int row_stride, const float* beam_scores_host, int rows_are_logprobs, int eos_id, int pad_id,
+                      int group_done, float* vals_dev, int32_t* idx_dev, float* proc_dev, int32_t* chosen_dev, void* stream);
+/* gvl_op_logits_process_ex with HammingDiversityLogitsProcessor in HF's place (behind sequence_bias, in front of the repetition penalty): every row loses
+ * fp32(diversity_penalty * count) at each token of ham_tokens_dev [n_ham] (device int32, 0 .. 16 ids, read by the kernel at run time; ids outside [0, n) are ignored),
+ * count = how often the token is listed. */
+int gvl_op_logits_process_hamming(gvl_ctx* ctx, float* logits, int n, int batch, const int32_t* hist_dev, int hist_stride, const int32_t* lens_dev,
+                                  const float* penalty, const int* ngram, const int* min_new, const int* eos_ids, const int* rules_ids, const int* grammar_ids,
+                                  const int32_t* ham_tokens_dev, int n_ham, float diversity_penalty, void* stream);
 /* y[b][N] = W[N,K] x[b][K] (+bias) for b < batch <= 16 -- the decode projections as ONE skinny MFMA GEMM (the weight stream is
  * read once for all sequences; K % 256 == 0).  x bf16 [batch][K], y f32 [batch][N]. */
 int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch,

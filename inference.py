@@ -64,6 +64,9 @@ def parse_args(argv=None):
     p.add_argument("--negative_prompt", type=str, default=None, help="the negative prompt of --guidance_scale: with <image> it sees the same video, without it it is the video-free contrast")
     p.add_argument("--num_return_sequences", type=int, default=1, help="HF num_return_sequences: n sampled answers per prompt from ONE prefill (needs --do_sample True), or the n best "
                                                                        "beams (n <= --num_beams); the first answer is reported as usual, all of them are listed at the end")
+    p.add_argument("--num_beam_groups", type=int, default=1, help="HF diverse (group) beam search: this many groups of --num_beams / groups beams (needs --diversity_penalty > 0, "
+                                                                 "--do_sample False; not with --share_visual)")
+    p.add_argument("--diversity_penalty", type=float, default=0.0, help="HF diversity_penalty: what a token chosen by an earlier group costs the later groups at the same step")
     p.add_argument("--output_scores", action="store_true", help="print each answer's mean token log-prob and, for the grounding answer, every temporal token's probability")
     p.add_argument("--constrain_grounding", action="store_true", help="keep the grounding answer inside 'From <s> to <e>.' with s <= e (generate(grammar=...); not with --share_visual, whose one call answers all three prompts)")
     p.add_argument("--share_visual", type=_bool, default=False, help="encode the video ONCE for the three prompts and batch them (the reference re-encodes per prompt)")
@@ -161,6 +164,8 @@ def main(argv=None):
         kw.update(guidance_scale=args.guidance_scale, negative_prompts=[args.negative_prompt])
     if args.output_scores:
         kw.update(return_dict_in_generate=True, output_scores=True)
+    if args.num_beam_groups != 1 or args.diversity_penalty != 0.0:
+        kw.update(num_beam_groups=args.num_beam_groups, diversity_penalty=args.diversity_penalty)       # generate() validates them as HF does
     n_ret = args.num_return_sequences
     if n_ret != 1:
         kw["num_return_sequences"] = n_ret                                              # generate() validates it as HF does
