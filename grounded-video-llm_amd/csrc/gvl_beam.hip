@@ -52,6 +52,18 @@ struct Owned {
 
 }  // namespace
 
+// what gvl_contrastive_search (gvl_contrastive.hip) shares with the beam searches: the work buffers and the candidate launch's arguments
+int gvlm::beam_search_buffers(gvl_ctx* ctx) { return ensure_beam_search_buffers(ctx); }
+void gvlm::beam_cand_args(gvl_ctx* ctx, BeamCandArgs& a, const float* rows, int n, int k, int row_stride, const float* scores, int norm, float* vals, int* idx, float* proc) {
+  fill_cand_args(ctx, a, rows, n, k, row_stride, scores, norm, vals, idx, proc);
+}
+gvlm::BeamCandBufs gvlm::beam_cand_bufs(gvl_ctx* ctx) {
+  BeamCandBufs b;
+  b.h_vals = (float*)ctx->h_beam_cand; b.h_idx = (int*)(b.h_vals + kMaxCand); b.h_proc = b.h_vals + 2 * kMaxCand;
+  b.d_vals = (float*)ctx->d_beam_cand; b.d_idx = (int*)(b.d_vals + kMaxCand); b.d_proc = b.d_vals + 2 * kMaxCand;
+  return b;
+}
+
 extern "C" {
 
 int gvl_op_beam_candidates(gvl_ctx* ctx, const float* rows, int n, int k, int row_stride, const float* beam_scores_host, int rows_are_logprobs, float* vals_dev,
@@ -133,6 +145,7 @@ int gvl_beam_search_n(gvl_ctx* ctx, int seq_id, const float* first_logits, const
   if (p->rules_id != -1 && (p->rules_id < 0 || ctx->check_rules(p->rules_id))) return seq_fail(ctx, "gvl_beam_search", SEQ_NO_RULES);
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_beam_search", SEQ_BAD);
   if (const int rc = pair_refuse(ctx, "gvl_beam_search", seq_id, true)) return rc;
+  if (const int rc = bank_refuse(ctx, "gvl_beam_search", seq_id)) return rc;
   const int pos0 = ctx->seqs[seq_id].pos;
   if (pos0 <= 0) return fail(ctx, GVL_ERR_STATE, "gvl_beam_search: the sequence is not prefilled");
   if (const int rc = ensure_beam_search_buffers(ctx)) return rc;
@@ -267,6 +280,7 @@ int gvl_group_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, c
   if (p->rules_id != -1 && (p->rules_id < 0 || ctx->check_rules(p->rules_id))) return seq_fail(ctx, "gvl_group_beam_search", SEQ_NO_RULES);
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_group_beam_search", SEQ_BAD);
   if (const int rc = pair_refuse(ctx, "gvl_group_beam_search", seq_id, true)) return rc;
+  if (const int rc = bank_refuse(ctx, "gvl_group_beam_search", seq_id)) return rc;
   const int pos0 = ctx->seqs[seq_id].pos;
   if (pos0 <= 0) return fail(ctx, GVL_ERR_STATE, "gvl_group_beam_search: the sequence is not prefilled");
   if (const int rc = ensure_beam_search_buffers(ctx)) return rc;

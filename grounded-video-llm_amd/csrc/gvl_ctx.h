@@ -46,6 +46,9 @@ struct Seq : SeqCore {
   // log-probability lists of the slot (sel.top_n >= 0), index = generation step like d_out ([outlist_cap], top lists [outlist_cap][GVL_MAX_TOP_LOGPROBS]);
   // null until the ctx allocated them (gvl_ctx::d_seq_lp / d_seq_top_*)
   float* d_lp = nullptr; int* d_top_ids = nullptr; float* d_top_lp = nullptr;
+  // hidden bank (gvl_seq_keep_hidden): ONE device allocation of bank_cap rows -- [bank_cap][hidden] bf16 post-final-norm hidden states, then [bank_cap] fp32 inverse
+  // norms (bank_inv points into it); bank_rows rows are written, row j = position j.  Owned by the slot: gvl_ctx::close frees it
+  bf16_t* bank = nullptr; float* bank_inv = nullptr; int bank_cap = 0, bank_rows = 0;
 };
 
 struct ProfRec { int cat; hipEvent_t e0, e1; double work; };
@@ -116,6 +119,9 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   // beam search (gvl_beam.hip), allocated by the first call that needs them: the per-row survivors between the two candidate launches, one step's candidates in HOST-MAPPED
   // memory (h_ / d_ views), [GVL_MAX_DECODE_BATCH][vocab] work rows, and the beams' histories + lengths for the logits processors
   void* d_beam_scratch = nullptr; void* h_beam_cand = nullptr; void* d_beam_cand = nullptr; float* d_beam_rows = nullptr; int* d_beam_hist = nullptr;
+  // contrastive search (gvl_contrastive.hip), allocated by the first call that needs them: [16][hidden] bf16 candidate rows + [16] inverse norms + the ranking launch's
+  // per-block maxima (device), and one step's p / pen / score / selected rank in HOST-MAPPED memory (h_ / d_ views)
+  void* d_cs_scratch = nullptr; void* h_cs_out = nullptr; void* d_cs_out = nullptr;
   std::vector<int> group_beam_tokens;          // gvl_group_beam_search: the tokens the device chose, step-major [steps][k] (gvl_debug_group_beam_tokens)
   std::vector<int> group_beam_pool;            // ... and behind every step's cache reorder (clones the search holds, free KV pages) (gvl_debug_group_beam_pool)
   // result-neutral launch parameters (gvl_debug_set): 0 = the launcher's own choice.  decode_graph: a decode group's step is captured once and
@@ -124,6 +130,13 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   struct { int decode_attn_cpb = 0, decode_attn_hpb = 0; bool decode_graph = true; int vision_in_place = 1, prefill_group = 4, attn_ring = 0, attn_pipe = 1, attn_pipe_rows = 128, patch_fused = 1, varlen_attn = 1, varlen_extend = 1, norm_fused = 1, last_layer_tail = 1; } dbg;
   // RCCL communicator owned by the ctx (gvl_comm_init); the library is dlopen'ed on first use
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
+  // a slot's hidden bank goes with the slot (hipFree waits for the device: no launch still reads it)
+  void drop_bank(Seq& s) { if (s.bank) (void)hipFree(s.bank); s.bank = nullptr; s.bank_inv = nullptr; s.bank_cap = s.bank_rows = 0; }
+  int close(int id) {
+    Seq* s = lookup(id);
+    if (s && s->lead < 0) drop_bank(*s);
+    return SeqTable<Seq>::close(id);
+  }
   // profiling
   bool prof = false; std::vector<ProfRec> recs;
   double prof_ms[GVL_PROF_NCAT] = {0}, prof_work[GVL_PROF_NCAT] = {0}; int64_t prof_n[GVL_PROF_NCAT] = {0};

@@ -126,7 +126,8 @@ int select_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st)
 // WHICH launches a group takes -- one per member, one with a batch dimension, one ragged grid, the same behind prefixes -- is prefill_plan's decision
 // (gvl_prefill_plan.h: pure, tested on the CPU); this function is plan, allocate, walk.  The GEMMs are shared whatever the form, and every row is bit-identical to the
 // sequence's own prefill / extend.  Everything the plan refuses is refused before the first launch.
-int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, const int* pos0s, const ScoreReq* score) {
+int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss, const int* pos0s, const ScoreReq* score,
+                bool keep_hidden) {
   const gvl_config& f = ctx->cfg;
   const int Hd = f.hidden, H = f.heads, KV = f.kv_heads, Dr = ctx->l_Dr, D = ctx->l_D, I = f.inter;
   const int qkvw = (H + 2 * KV) * Dr;
@@ -135,6 +136,8 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
   for (int b = 0; b < nb && b < GVL_MAX_PREFILL_BATCH; ++b) { geo.lens[b] = lens[b]; geo.pos0[b] = pos0s ? pos0s[b] : 0; }
   geo.rope_orig_max_pos = f.rope_orig_max_pos; geo.long_table = ctx->cos_l != nullptr; geo.loss = loss != nullptr; geo.page_id_cap = (int)(sizeof(IntList::v) / sizeof(int));
   geo.hidden = Hd; geo.qkv_width = qkvw; geo.gate_up_width = 2 * I; geo.fused_weights = !ctx->ll.empty() && ctx->ll[0].qkvw_f; geo.score = score != nullptr;
+  geo.keep_hidden = keep_hidden;
+  if (keep_hidden && (sqs[0]->bank_rows != 0 || lens[0] > sqs[0]->bank_cap)) return fail(ctx, GVL_ERR_STATE, "llm_prefill: the hidden bank is not empty or too small");
   PrefillPlan plan;
   { const int rc = prefill_plan(geo, PrefillKnobs{ctx->dbg.varlen_attn, ctx->dbg.varlen_extend != 0, ctx->dbg.last_layer_tail != 0, ctx->dbg.norm_fused != 0}, &plan);
     if (rc) return fail(ctx, GVL_ERR_ARG, prefill_refusal_reason(rc)); }
@@ -299,6 +302,8 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
       RUN(GVL_PROF_OTHER, 0, gvl_launch_score_rows(sr, st));
     }
   }
+  // hidden bank (gvl_seq_keep_hidden): the plan ran the last layer on every row, so x IS the final residual stream -- one launch normalises the M rows into the bank
+  if (keep_hidden) { const int rc = bank_append(ctx, *sqs[0], x, Hd, M, st); if (rc) return rc; }
   // last-row-only lm_head: final RMSNorm fused into the GEMV; one weight stream for the nb last rows
   const bf16_t* last = x + (size_t)(S0 - 1) * Hd;
   int last_stride = S0 * Hd;

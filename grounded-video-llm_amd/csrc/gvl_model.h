@@ -105,7 +105,24 @@ int build_visual(gvl_ctx* ctx, const float* clip_feats, const bf16_t* iv2_feats,
 
 // gvl_model.hip: gvl_seq_clone.  carry_generated: the clone also takes the source's generated ids, their count and the id to feed next (what gvl_seq_clone does for a
 // source with a grammar); false: its history starts empty (gvl_beam_search's beams, whose histories the search keeps itself)
-int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated);
+// carry_bank: the clone of a keep-hidden source gets its own bank with a copy of the source's rows (gvl_seq_clone); false: a plain sequence (gvl_contrastive_search's
+// candidates, whose rows the search ranks itself)
+int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated, bool carry_bank = false);
+// n plain clones at once (gvl_contrastive_search's candidates): all or nothing, one launch for the n partial-page copies, one for the counters; dst_seqs [n]
+int seq_clone_many(gvl_ctx* ctx, int src_seq, int max_tokens, int n, int* dst_seqs, hipStream_t stream);
+// hidden bank (gvl_seq_keep_hidden; gvl_ctx.h Seq::bank).  bank_refuse: entry `fn` is not taught the bank -- GVL_ERR_STATE for a keep-hidden sequence, nothing changed.
+// bank_alloc: one allocation for `cap` rows, all or nothing.  bank_append (gvl_contrastive.hip): n residual rows x (ldx elements apart) -> final RMSNorm -> bank rows
+// [bank_rows, bank_rows + n) and their inverse norms; bank_rows += n
+int bank_refuse(gvl_ctx* c, const char* fn, int id);
+int bank_alloc(gvl_ctx* ctx, Seq& s, int cap);
+int bank_append(gvl_ctx* ctx, Seq& s, const bf16_t* x, int ldx, int n, hipStream_t st);
+
+// gvl_beam.hip: the [16][vocab] work rows, histories and candidate buffers of a search (allocated on first use); the arguments of one candidate launch; one step's
+// best 2k candidates (value, flat index, log-probability) in host-mapped memory, host and device views
+int beam_search_buffers(gvl_ctx* ctx);
+void beam_cand_args(gvl_ctx* ctx, BeamCandArgs& a, const float* rows, int n, int k, int row_stride, const float* scores, int norm, float* vals, int* idx, float* proc);
+struct BeamCandBufs { float *h_vals, *d_vals; int *h_idx, *d_idx; float *h_proc, *d_proc; };
+BeamCandBufs beam_cand_bufs(gvl_ctx* ctx);
 
 // gvl_llm.hip
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);
@@ -117,7 +134,7 @@ int select_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st)
 int step_rows(gvl_ctx* ctx, Seq* const* named, int n, Seq** rows);
 // one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan
 int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr,
-                const ScoreReq* score = nullptr);   // pos0s: tokens each sequence already holds (null = none); score: rows of the group to score on the way (not with loss)
+                const ScoreReq* score = nullptr, bool keep_hidden = false);   // keep_hidden: one keep-hidden member -- no last-layer tail, every row joins its bank; pos0s: tokens each sequence already holds (null = none); score: rows of the group to score on the way (not with loss)
 // one step of B sequences (decode_batch_ok): plans its launches (decode_plan, gvl_decode_plan.h -- it refuses before the first launch), then walks the plan
 int decode_step(gvl_ctx* ctx, Seq* const* sqs, int B, hipStream_t st);
 int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, int32_t* const* out_ids, int* const* n_out, hipStream_t st);

@@ -173,6 +173,8 @@ int gvl_destroy(gvl_ctx* ctx) {
   if (ctx->h_eos_flags) hipHostFree(ctx->h_eos_flags);
   if (ctx->h_seq_out) hipHostFree(ctx->h_seq_out);
   if (ctx->h_beam_cand) hipHostFree(ctx->h_beam_cand);
+  if (ctx->h_cs_out) hipHostFree(ctx->h_cs_out);
+  for (Seq& q : ctx->seqs) ctx->drop_bank(q);
   for (int i = 0; i < 3; ++i) if (ctx->step_ev[i]) hipEventDestroy(ctx->step_ev[i]);
   for (auto& kv : ctx->w) if (kv.second.p) hipFree(kv.second.p);
   for (void* p : ctx->dw_allocs) if (p) hipFree(p);
@@ -183,7 +185,7 @@ int gvl_destroy(gvl_ctx* ctx) {
   if (ctx->comm) gvl_comm_destroy(ctx);
   for (RuleSet& r : ctx->rule_sets) if (r.used && r.d) hipFree(r.d);
   for (GrammarSet& g : ctx->grammars) if (g.used && g.d) hipFree(g.d);
-  void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch, ctx->d_beam_scratch, ctx->d_beam_rows, ctx->d_beam_hist};
+  void* ptrs[] = {ctx->d_xn, ctx->d_seq_ngen, ctx->d_seq_lp, ctx->d_seq_top_ids, ctx->d_seq_top_lp, ctx->arena, ctx->arena_l, ctx->kpool, ctx->vpool, ctx->d_x, ctx->d_qkv, ctx->d_q, ctx->d_attn, ctx->d_act, ctx->d_logits, ctx->d_part, ctx->d_counters, ctx->d_xt, ctx->d_sqpart, ctx->d_seq_tok, ctx->d_seq_tables, ctx->d_seq_pos, ctx->pre_scratch, ctx->d_beam_scratch, ctx->d_beam_rows, ctx->d_beam_hist, ctx->d_cs_scratch};
   for (void* p : ptrs) if (p) hipFree(p);
   for (auto& r : ctx->recs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   delete ctx;
@@ -497,6 +499,7 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
   REQUIRE_READY(ctx->has_llm, "gvl_seq_fork");
   if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: bad arguments");
   if (const int rc = pair_refuse(ctx, "gvl_seq_fork", src_seq, true)) return rc;
+  if (const int rc = bank_refuse(ctx, "gvl_seq_fork", src_seq)) return rc;
   if (n_tokens <= 0 || (n_tokens & 63) || n_tokens > ctx->seqs[src_seq].pos) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: n_tokens must be a positive multiple of 64 within the source's tokens");
   if (max_tokens <= n_tokens || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fork: max_tokens must exceed n_tokens and fit cfg.max_seq");
   if (ctx->fork_cuts_answer(ctx->seqs[src_seq], n_tokens))
@@ -517,7 +520,7 @@ int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, float* 
   if (sq.pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_prefill: sequence already holds tokens");
   hipStream_t st = (hipStream_t)stream;
   Seq* one[1] = {&sq}; const bf16_t* e1[1] = {embeds};
-  int rc = llm_prefill(ctx, one, 1, e1, &S, st);
+  int rc = llm_prefill(ctx, one, 1, e1, &S, st, nullptr, nullptr, nullptr, sq.bank != nullptr);   // a keep-hidden sequence: the bank takes one row per prompt row
   if (rc) return rc;
   if (last_logits) HIPCHK(ctx, hipMemcpyAsync(last_logits, ctx->d_logits, (size_t)ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
   return 0;
@@ -527,7 +530,7 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
   // A source with a grammar hands its answer so far to the clone: the mask is a function of the generated ids, so without them the clone's walk would start over
   // mid-answer.  Without a grammar a clone's history starts empty, as ever.
   Seq* src = ctx ? ctx->lookup(src_seq) : nullptr;
-  return seq_clone(ctx, src_seq, max_tokens, dst_seq, (hipStream_t)stream, src && src->sel.grammar >= 0);
+  return seq_clone(ctx, src_seq, max_tokens, dst_seq, (hipStream_t)stream, src && src->sel.grammar >= 0, src && src->bank);
 }
 
 // n_new siblings of a freshly prefilled sequence: n answers to one prompt from ONE prefill.  The table operation opens all of them or none (SeqTable::fanout); behind it
@@ -538,6 +541,7 @@ int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const u
   REQUIRE_READY(ctx->has_llm, "gvl_seq_fanout");
   if (!streams || !first_logits || !dst_seqs) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: streams, first_logits and dst_seqs are needed");
   if (!ctx->lookup(src_seq)) return seq_fail(ctx, "gvl_seq_fanout", SEQ_BAD);
+  if (const int rc = bank_refuse(ctx, "gvl_seq_fanout", src_seq)) return rc;
   if (n_new < 1 || n_new > GVL_MAX_DECODE_BATCH - 1) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: n_new must be 1 .. " + std::to_string(GVL_MAX_DECODE_BATCH - 1) + " (repeat the call for more)");
   const int pos = ctx->seqs[src_seq].pos, V = ctx->cfg.vocab;
   if (max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_fanout: max_tokens must exceed the source's tokens and fit cfg.max_seq");
@@ -571,18 +575,44 @@ int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const u
 }
 }  // extern "C"
 
-int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated) {
+// Entries that are not taught the hidden bank refuse a keep-hidden sequence: its bank would fall out of step with its position
+int gvlm::bank_refuse(gvl_ctx* c, const char* fn, int id) {
+  const Seq* s = c->lookup(id);
+  if (s && s->bank) return fail(c, GVL_ERR_STATE, std::string(fn) + ": sequence " + std::to_string(id) + " keeps its hidden states (gvl_seq_keep_hidden); this entry does not fill the bank");
+  return 0;
+}
+// the bank of `s`: rows for `cap` positions, all or nothing
+int gvlm::bank_alloc(gvl_ctx* ctx, Seq& s, int cap) {
+  const int Hd = ctx->cfg.hidden;
+  if (Hd % 64 || Hd > 8192) return fail(ctx, GVL_ERR_ARG, "gvl_seq_keep_hidden: hidden must be a multiple of 64 and <= 8192");
+  ctx->drop_bank(s);
+  const size_t row_bytes = al256((size_t)cap * Hd * 2);
+  void* p = nullptr;
+  if (hipMalloc(&p, row_bytes + (size_t)cap * 4) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, GVL_ERR_OOM, "gvl_seq_keep_hidden: no device memory for the hidden bank"); }
+  s.bank = (bf16_t*)p; s.bank_inv = (float*)((char*)p + row_bytes); s.bank_cap = cap; s.bank_rows = 0;
+  return 0;
+}
+
+int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated, bool carry_bank) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
   if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
   if (const int rc = pair_refuse(ctx, "gvl_seq_clone", src_seq, true)) return rc;
   const int pos = ctx->seqs[src_seq].pos;
   if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
   if (carry_generated && ctx->seqs[src_seq].n_gen > ctx->outlist_cap) return fail(ctx, GVL_ERR_STATE, "gvl_seq_clone: the source generated more ids than an output list holds");
+  if (carry_bank && ctx->seqs[src_seq].bank_rows != pos) return fail(ctx, GVL_ERR_STATE, "gvl_seq_clone: the source's hidden bank is not in step with its position");
   const int id = ctx->open(max_tokens, src_seq, pos);
   if (id < 0) return seq_fail(ctx, "gvl_seq_clone", id);
   Seq& s = ctx->seqs[id];
   bind_slot(ctx, s, id);
   hipStream_t st = stream;
+  if (carry_bank) {                                   // a keep-hidden source: the clone keeps its own copy of the rows so far
+    if (const int rc = bank_alloc(ctx, s, max_tokens)) { ctx->close(id); return rc; }
+    const Seq& b = ctx->seqs[src_seq];
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(b.bank, s.bank, (size_t)pos * ctx->cfg.hidden * 2, st));
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(b.bank_inv, s.bank_inv, (size_t)pos * 4, st));
+    s.bank_rows = pos;
+  }
   { const int rc = upload_table(ctx, s, st); if (rc) return rc; }   // by value, on the clone's stream: ordered behind the source's pending steps there
   if (pos & 63)                                       // the partial last page is private: copy the source's (all layers, K and V^T)
     RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_copy(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers,
@@ -606,12 +636,51 @@ int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hip
   *dst_seq = id;
   return 0;
 }
+// n plain clones of `src_seq` at its current length for gvl_contrastive_search's candidates (no bank, empty histories): what n seq_clone calls give, but all or
+// nothing -- pages and slots are counted before the first one opens -- and with ONE launch for the n private copies of the partial last page (gvl_seq_fanout's) and ONE
+// for the positions and generation counts; the block tables still go up one launch each (page ids travel by value).
+__global__ void clone_counters_kernel(const FanoutArgs a, int pos) { if ((int)threadIdx.x < a.n) { *a.pos[threadIdx.x] = pos; *a.ngen[threadIdx.x] = 0; } }
+int gvlm::seq_clone_many(gvl_ctx* ctx, int src_seq, int max_tokens, int n, int* dst_seqs, hipStream_t st) {
+  REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
+  if (!dst_seqs || n < 1 || n > GVL_MAX_DECODE_BATCH || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
+  if (const int rc = pair_refuse(ctx, "gvl_seq_clone", src_seq, true)) return rc;
+  const int pos = ctx->seqs[src_seq].pos;
+  if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
+  const int own_pages = (max_tokens + 63) / 64 - (pos >> 6);
+  if ((long long)ctx->free_pages.size() < (long long)n * own_pages) return seq_fail(ctx, "gvl_seq_clone", SEQ_NO_PAGES);
+  int slots = ctx->max_seqs - (int)ctx->seqs.size();
+  for (const Seq& q : ctx->seqs) slots += !q.used;
+  if (slots < n) return seq_fail(ctx, "gvl_seq_clone", SEQ_TOO_MANY);
+  FanoutArgs fa; memset(&fa, 0, sizeof(fa)); fa.n = n;
+  struct Undo { gvl_ctx* c; const int* ids; int n; bool keep; ~Undo() { if (!keep) for (int i = 0; i < n; ++i) c->close(ids[i]); } } undo{ctx, dst_seqs, 0, false};
+  for (int i = 0; i < n; ++i) {
+    const int id = ctx->open(max_tokens, src_seq, pos);              // cannot fail: pages and slots were counted above
+    if (id < 0) return seq_fail(ctx, "gvl_seq_clone", id);
+    dst_seqs[i] = id; undo.n = i + 1;
+  }
+  for (int i = 0; i < n; ++i) {                                       // after the last open(): `seqs` no longer moves
+    Seq& s = ctx->seqs[dst_seqs[i]];
+    bind_slot(ctx, s, dst_seqs[i]);
+    s.n_gen = 0;
+    fa.pos[i] = s.d_pos; fa.ngen[i] = s.d_ngen;
+    if (pos & 63) fa.dst_page[i] = s.pages[pos >> 6];
+    if (const int rc = upload_table(ctx, s, st)) return rc;
+  }
+  if (pos & 63)
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_fanout(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers, ctx->kv_total_pages,
+                                                     ctx->seqs[src_seq].pages[pos >> 6], fa, st));
+  hipLaunchKernelGGL(clone_counters_kernel, dim3(1), dim3(64), 0, st, fa, pos);
+  if (hipGetLastError() != hipSuccess) return fail(ctx, GVL_ERR_HIP, "gvl_seq_clone: launch failed");
+  undo.keep = true;
+  return 0;
+}
 extern "C" {
 
 int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_new, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend");
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_prefill_extend", SEQ_BAD);
   if (const int rc = pair_refuse(ctx, "gvl_prefill_extend", seq_id, false)) return rc;
+  if (const int rc = bank_refuse(ctx, "gvl_prefill_extend", seq_id)) return rc;
   Seq& sq = ctx->seqs[seq_id];
   if (sq.pos <= 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend: the sequence must hold a prefix of whole pages (gvl_seq_fork)");
   if (!embeds || n_new <= 0 || sq.pos + n_new > sq.max_tokens || n_new > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad length");
@@ -627,6 +696,7 @@ int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_n
 int gvl_forward_loss(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, const int64_t* labels, double* nll_sum, int* n_valid, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_forward_loss");
   if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_forward_loss", SEQ_BAD);
+  if (const int rc = bank_refuse(ctx, "gvl_forward_loss", seq_id)) return rc;
   Seq& sq = ctx->seqs[seq_id];
   if (!embeds || !labels || !nll_sum || !n_valid || S <= 0 || S > sq.max_tokens || S > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_forward_loss: bad arguments / length");
   if (sq.pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_forward_loss: sequence already holds tokens");
@@ -657,6 +727,7 @@ int gvl_prefill_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint1
   for (int i = 0; i < n_seqs; ++i) {
     const int id = seq_ids[i];
     if (!ctx->lookup(id) || !embeds[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad seq / embeds");
+    if (const int rc = bank_refuse(ctx, "gvl_prefill_varlen", id)) return rc;
     if (seq_lens[i] <= 0 || seq_lens[i] > ctx->seqs[id].max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad length");
     if (seq_lens[i] > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: seq_len exceeds cfg.max_prefill");
     if (ctx->seqs[id].pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_varlen: sequence already holds tokens");
@@ -684,6 +755,7 @@ int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, cons
     const int id = seq_ids[i];
     if (!ctx->lookup(id) || !embeds_new[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad seq / embeds");
     if (const int rc = pair_refuse(ctx, "gvl_prefill_extend_varlen", id, false)) return rc;
+    if (const int rc = bank_refuse(ctx, "gvl_prefill_extend_varlen", id)) return rc;
     const Seq& sq = ctx->seqs[id];
     if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
     if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad length");
@@ -716,6 +788,7 @@ int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const 
     const int id = seq_ids[i];
     if (!ctx->lookup(id) || !embeds_new[i] || !next_ids_host[i]) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad seq / embeds / next ids");
     if (const int rc = pair_refuse(ctx, "gvl_score_extend_varlen", id, false)) return rc;
+    if (const int rc = bank_refuse(ctx, "gvl_score_extend_varlen", id)) return rc;
     const Seq& sq = ctx->seqs[id];
     if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_score_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
     if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad length");
@@ -768,6 +841,7 @@ int gvl_decode_greedy_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int ma
     const int id = seq_ids[i];
     if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_BAD);
     if (const int rc = pair_refuse(ctx, "gvl_decode_greedy_batch", id, false)) return rc;
+    if (const int rc = bank_refuse(ctx, "gvl_decode_greedy_batch", id)) return rc;
     if (ctx->seqs[id].n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_greedy: call gvl_prefill first");   // members of a group must also be at the SAME step (checked per group)
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_DUPLICATE);
   }
@@ -796,6 +870,7 @@ int gvl_decode_steps(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int n_steps, 
     const int id = seq_ids[i];
     if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_steps", SEQ_BAD);
     if (const int rc = pair_refuse(ctx, "gvl_decode_steps", id, false)) return rc;
+    if (const int rc = bank_refuse(ctx, "gvl_decode_steps", id)) return rc;
     const Seq& sq = ctx->seqs[id];
     if (sq.n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_steps: call gvl_prefill first");
     if (sq.pos + n_steps > sq.max_tokens || sq.n_gen + n_steps > ctx->outlist_cap) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: sequence would exceed its capacity");
@@ -840,8 +915,10 @@ int gvl_decode_step_logits(gvl_ctx* ctx, int seq_id, int tok, float* logits, voi
   hipStream_t st = (hipStream_t)stream;
   RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sq.d_tok, tok, st));
   Seq* one[1] = {&sq};
+  if (sq.bank && (sq.bank_rows != sq.pos || sq.bank_rows >= sq.bank_cap)) return fail(ctx, GVL_ERR_STATE, "gvl_decode_step_logits: the hidden bank is not in step with the sequence");
   int rc = decode_step(ctx, one, 1, st);
   if (rc) return rc;
+  if (sq.bank) { rc = bank_append(ctx, sq, ctx->d_x, ctx->cfg.hidden, 1, st); if (rc) return rc; }   // the step's residual row behind the last layer
   if (logits) HIPCHK(ctx, hipMemcpyAsync(logits, ctx->d_logits, (size_t)ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
   return 0;
 }
@@ -858,12 +935,15 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
     Seq& sq = ctx->seqs[id];
     if (toks[i] < 0 || toks[i] >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: bad token / sequence full / not prefilled");
     if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_DUPLICATE);
+    if (sq.bank && (sq.bank_rows != sq.pos || sq.bank_rows >= sq.bank_cap)) return fail(ctx, GVL_ERR_STATE, "gvl_decode_step_logits_batch: the hidden bank is not in step with the sequence");
     sqs[i] = &sq;
   }
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_seqs; ++i) RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sqs[i]->d_tok, toks[i], st));
   const int rc = decode_step(ctx, sqs, n_seqs, st);       // ONE weight stream for all of them; row i depends on sequence i only (batch-invariant kernels)
   if (rc) return rc;
+  for (int i = 0; i < n_seqs; ++i)                        // keep-hidden members: row i of the step's residual rows joins sequence i's bank
+    if (sqs[i]->bank) { const int brc = bank_append(ctx, *sqs[i], ctx->d_x + (size_t)i * ctx->cfg.hidden, ctx->cfg.hidden, 1, st); if (brc) return brc; }
   if (logits) HIPCHK(ctx, hipMemcpyAsync(logits, ctx->d_logits, (size_t)n_seqs * ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
   return 0;
 }

@@ -19,7 +19,8 @@ enum PrefillLastRows : int {   // where the lm_head reads the members' last rows
   GVL_PREFILL_LAST_GATHERED,      // copied together first (ragged rows are not equally spaced)
   GVL_PREFILL_LAST_TAIL,          // the rows the last layer's tail left
 };
-enum PrefillRefusal : int { GVL_PREFILL_BAD_BATCH = -1, GVL_PREFILL_BAD_PREFIX = -2, GVL_PREFILL_LOSS_BEHIND_PREFIX = -3, GVL_PREFILL_LOSS_GROUP = -4, GVL_PREFILL_SCORE_AND_LOSS = -5 };
+enum PrefillRefusal : int { GVL_PREFILL_BAD_BATCH = -1, GVL_PREFILL_BAD_PREFIX = -2, GVL_PREFILL_LOSS_BEHIND_PREFIX = -3, GVL_PREFILL_LOSS_GROUP = -4, GVL_PREFILL_SCORE_AND_LOSS = -5,
+                            GVL_PREFILL_KEEP_HIDDEN_GROUP = -6 };
 inline const char* prefill_refusal_reason(int rc) {
   switch (rc) {
     case GVL_PREFILL_BAD_BATCH: return "llm_prefill: batch must be 1 .. 8 sequences";
@@ -27,6 +28,7 @@ inline const char* prefill_refusal_reason(int rc) {
     case GVL_PREFILL_LOSS_BEHIND_PREFIX: return "llm_prefill: no loss tail behind a cached prefix";
     case GVL_PREFILL_LOSS_GROUP: return "llm_prefill: loss tail takes one sequence";
     case GVL_PREFILL_SCORE_AND_LOSS: return "llm_prefill: a score tail and a loss tail exclude each other";
+    case GVL_PREFILL_KEEP_HIDDEN_GROUP: return "llm_prefill: a keep-hidden sequence is prefilled alone, from empty, without a loss or score tail";
     default: return "";
   }
 }
@@ -39,7 +41,8 @@ struct PrefillGeometry {         // only what the decision reads
   int page_id_cap;               // page ids one by-value list carries (IntList: 256)
   int hidden, qkv_width, gate_up_width;   // the fused RMSNorm's widths: hidden, (H + 2 KV) * Dr, 2 * inter
   bool fused_weights;            // the norm-folded weights were loaded
-  bool score;                    // a score tail is requested (gvl_score_extend_varlen): any group, behind any prefixes.  LAST member: a value-initialised geometry reads false
+  bool score;                    // a score tail is requested (gvl_score_extend_varlen): any group, behind any prefixes.  A value-initialised geometry reads false
+  bool keep_hidden;              // the member keeps its hidden states (gvl_seq_keep_hidden): every row's last-layer output is read.  LAST member: value-initialised = false
 };
 struct PrefillKnobs { int varlen_attn; bool varlen_extend, last_layer_tail, norm_fused; };   // gvl_debug_set
 
@@ -81,6 +84,7 @@ inline int prefill_plan(const PrefillGeometry& g, const PrefillKnobs& k, Prefill
   if (g.score && g.loss) return GVL_PREFILL_SCORE_AND_LOSS;
   if (ext && g.loss) return GVL_PREFILL_LOSS_BEHIND_PREFIX;
   if (g.loss && nb != 1) return GVL_PREFILL_LOSS_GROUP;
+  if (g.keep_hidden && (nb != 1 || ext || g.loss || g.score)) return GVL_PREFILL_KEEP_HIDDEN_GROUP;
   PrefillPlan p{};
   bool uniform = !ext, same_table = true;              // the batched launch shares one qpos0: empty sequences only.  same_table: one LongRoPE table serves every member
   for (int b = 0; b < nb; ++b) {
@@ -127,7 +131,8 @@ inline int prefill_plan(const PrefillGeometry& g, const PrefillKnobs& k, Prefill
   // lm_head takes last rows only) -- gate_up / down run on the nb last rows alone: -2 x M x hidden x 3 inter flops (2.1 % of the prefill's GEMM work at S = 3.5 k).
   // The gathered row statistics of the fused norm are finished four partial sums at a time.  A score tail reads rows anywhere in the group, so it keeps the full pass
   // (the MLP on scored rows + last rows only is left out on purpose: DESIGN.md 3.9).
-  p.tail = !g.loss && !g.score && k.last_layer_tail && (!p.nf || (g.hidden / 64) % 4 == 0);
+  // A keep-hidden member's bank takes the last layer's output of EVERY row: the full pass, whatever the knob says.
+  p.tail = !g.loss && !g.score && !g.keep_hidden && k.last_layer_tail && (!p.nf || (g.hidden / 64) % 4 == 0);
   p.last_rows = p.tail ? GVL_PREFILL_LAST_TAIL : (nb == 1 || uniform) ? GVL_PREFILL_LAST_STRIDED : GVL_PREFILL_LAST_GATHERED;
   for (int b0 = 0; b0 < nb; b0 += p.chunks[p.n_chunks - 1]) p.chunks[p.n_chunks++] = nb - b0 >= 4 ? 4 : (nb - b0 >= 2 ? 2 : 1);   // row results do not depend on the chunking
   *out = p;

@@ -383,6 +383,8 @@ int gvl_seq_set_guidance(gvl_ctx* ctx, int seq_id, int neg_seq_id, float scale, 
   Seq* fol = ctx->lookup(neg_seq_id);
   if (!fol) return seq_fail(ctx, "gvl_seq_set_guidance", SEQ_BAD);
   if (seq_id == neg_seq_id) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_guidance: the negative sequence must be another sequence");
+  if (const int rc = bank_refuse(ctx, "gvl_seq_set_guidance", seq_id)) return rc;
+  if (const int rc = bank_refuse(ctx, "gvl_seq_set_guidance", neg_seq_id)) return rc;
   if (!cond_logits || !neg_logits || cond_logits == neg_logits) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_guidance: the two prefills' last_logits are needed (two device buffers)");
   if (!std::isfinite(scale)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_set_guidance: scale must be finite");
   if (lead->lead >= 0 || lead->follow >= 0 || fol->lead >= 0 || fol->follow >= 0) return fail(ctx, GVL_ERR_STATE, "gvl_seq_set_guidance: a sequence is already part of a guided pair");

@@ -627,6 +627,73 @@ class Engine:
             res.append((out, score[r], [float(ts[r * cap + i]) for i in range(n[r])]) if with_scores else out)
         return res[0] if nr == 1 else res
 
+    # ---- contrastive search (gvl_contrastive.hip) --------------------------------------------------
+    def seq_keep_hidden(self, seq: int, on: bool = True):
+        """gvl_seq_keep_hidden: the EMPTY sequence `seq` gets a hidden bank -- per context row the post-final-norm hidden state (bf16) and its inverse norm --
+        filled by prefill() and by every decode_step_logits* step.  Call it before the prefill; contrastive_search needs it."""
+        self._chk(self.lib.gvl_seq_keep_hidden(self.ctx, int(seq), int(bool(on))), "gvl_seq_keep_hidden")
+
+    def seq_read_hidden(self, seq: int, first: int, n: int):
+        """gvl_seq_read_hidden: bank rows [first, first + n) of a keep-hidden sequence -> (bf16 [n, hidden], fp32 inverse norms [n]) on the device."""
+        rows = torch.empty((int(n), self.geo.hidden), dtype=bf, device=self.device)
+        inv = torch.empty((int(n),), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.gvl_seq_read_hidden(self.ctx, int(seq), int(first), int(n), _ptr(rows), _ptr(inv), self.stream), "gvl_seq_read_hidden")
+        return rows, inv
+
+    def op_hidden_bank_append(self, x: torch.Tensor, w: torch.Tensor, eps: float):
+        """gvl_op_hidden_bank_append: residual rows x bf16 [n, cols] (any row pitch) -> (rows bf16 [n, cols] = op_rmsnorm(x, w, eps) bit for bit, inverse norms fp32 [n])."""
+        assert x.dtype == bf and x.dim() == 2 and x.stride(1) == 1 and w.dtype == bf and w.is_contiguous() and x.device == self.device
+        n, cols = x.shape
+        rows = torch.empty((n, cols), dtype=bf, device=self.device)
+        inv = torch.empty((n,), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.gvl_op_hidden_bank_append(self.ctx, _ptr(x), int(x.stride(0)), _ptr(w), float(eps), _ptr(rows), _ptr(inv), n, cols, self.stream),
+                  "gvl_op_hidden_bank_append")
+        return rows, inv
+
+    def op_contrastive_rank(self, bank: torch.Tensor, bank_inv: torch.Tensor, cand: torch.Tensor, cand_inv: torch.Tensor, p: torch.Tensor, alpha: float):
+        """gvl_op_contrastive_rank: bank bf16 [n_ctx, D] + inverse norms, candidates bf16 [k, D] + inverse norms, p fp32 [k] -> (pen fp32 [k], score fp32 [k],
+        selected rank int32 [1]) on the device: pen_i = max_j cos(g_i, h_j), score_i = (1 - alpha) p_i - alpha pen_i, ties to the lower rank."""
+        for t in (bank, bank_inv, cand, cand_inv, p):
+            assert t.is_contiguous() and t.device == self.device
+        assert bank.dtype == bf and cand.dtype == bf and bank_inv.dtype == cand_inv.dtype == p.dtype == torch.float32
+        n_ctx, D = bank.shape
+        k = cand.shape[0]
+        assert cand.shape[1] == D and bank_inv.numel() == n_ctx and cand_inv.numel() == k and p.numel() == k
+        pen = torch.full((k,), float("nan"), dtype=torch.float32, device=self.device)
+        score = torch.full((k,), float("nan"), dtype=torch.float32, device=self.device)
+        sel = torch.full((1,), -1, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.gvl_op_contrastive_rank(self.ctx, _ptr(bank), _ptr(bank_inv), n_ctx, D, _ptr(cand), _ptr(cand_inv), _ptr(p), k, float(alpha),
+                                                   _ptr(pen), _ptr(score), _ptr(sel), self.stream), "gvl_op_contrastive_rank")
+        return pen, score, sel
+
+    def contrastive_search(self, seq: int, first_logits: torch.Tensor, top_k: int, penalty_alpha: float, max_new: int, eos: Optional[int], processors=None,
+                           rules: Optional[int] = None, with_trace: bool = False):
+        """gvl_contrastive_search: HF contrastive search (penalty_alpha, top_k) from the PREFILLED keep-hidden sequence `seq` and its prefill logits, inside the
+        library; `seq` is not consumed.  processors / rules as beam_search; the sequence's grammar applies.  Returns the new ids, or with with_trace (ids, trace):
+        trace = {"ids": [steps][k] candidate ids in rank order, "p": [steps][k], "pen": [steps][k], "sel": [steps] selected ranks, "hidden": bf16 [steps, hidden] the
+        rows the search committed to its bank, "rows": fp32 [steps, vocab] the processed row every step's candidates were taken from}."""
+        assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.device == self.device
+        pe, ng, mn, pe_eos = processors.args() if processors is not None else (1.0, 0, 0, None)
+        k = int(top_k)
+        prm = L.GvlContrastiveParams(k, float(penalty_alpha), int(max_new), -1 if eos is None else int(eos), float(pe), int(ng), int(mn),
+                                     -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
+        cap = max(int(max_new), 1)
+        ids, n = (C.c_int32 * cap)(), C.c_int(0)
+        if not with_trace:
+            self._chk(self.lib.gvl_contrastive_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, C.byref(n), None, None, None, None, None, None,
+                                                      self.stream), "gvl_contrastive_search")
+            return [int(ids[i]) for i in range(n.value)]
+        kk = max(k, 1)
+        t_ids, t_p, t_pen, t_sel = (C.c_int32 * (cap * kk))(), (C.c_float * (cap * kk))(), (C.c_float * (cap * kk))(), (C.c_int32 * cap)()
+        hid = torch.zeros((cap, self.geo.hidden), dtype=bf, device=self.device)
+        rows = torch.zeros((cap, self.geo.vocab), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.gvl_contrastive_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, C.byref(n), t_ids, t_p, t_pen, t_sel, _ptr(rows), _ptr(hid),
+                                                  self.stream), "gvl_contrastive_search")
+        steps = n.value
+        trace = {"ids": [[int(t_ids[s * k + i]) for i in range(k)] for s in range(steps)], "p": [[float(t_p[s * k + i]) for i in range(k)] for s in range(steps)],
+                 "pen": [[float(t_pen[s * k + i]) for i in range(k)] for s in range(steps)], "sel": [int(t_sel[s]) for s in range(steps)], "hidden": hid[:steps], "rows": rows[:steps]}
+        return [int(ids[i]) for i in range(steps)], trace
+
     def group_beam_tokens(self, num_beams: int) -> List[List[int]]:
         """gvl_debug_group_beam_tokens: per step of the last group_beam_search, the num_beams tokens the DEVICE chose (a finished group's: its pad)."""
         n = C.c_int(0)

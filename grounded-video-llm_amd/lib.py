@@ -68,6 +68,12 @@ class GvlGroupBeamParams(C.Structure):
     _fields_ = [("base", GvlBeamParams), ("num_beam_groups", C.c_int), ("diversity_penalty", C.c_float), ("pad_id", C.c_int)]
 
 
+class GvlContrastiveParams(C.Structure):
+    """gvl_contrastive_params (include/gvl.h)."""
+    _fields_ = [("top_k", C.c_int), ("penalty_alpha", C.c_float), ("max_new_tokens", C.c_int), ("eos_id", C.c_int),
+                ("penalty", C.c_float), ("ngram", C.c_int), ("min_new", C.c_int), ("proc_eos_id", C.c_int), ("rules_id", C.c_int)]
+
+
 class GvlDecodeProj(C.Structure):
     """gvl_decode_proj (include/gvl.h): one decode projection with any prologue / epilogue, for the operator tests."""
     _fields_ = [("path", C.c_int32), ("variant", C.c_int32), ("w_fmt", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("batch", C.c_int32),
@@ -231,6 +237,13 @@ _SIGS = {
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                 C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "gvl_op_gemv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_seq_keep_hidden": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "gvl_seq_read_hidden": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gvl_contrastive_search": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GvlContrastiveParams), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gvl_op_hidden_bank_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gvl_op_contrastive_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -131,6 +131,31 @@ def resolve_guidance(kw: dict) -> Optional[float]:
     return None if s == 1 else float(s)
 
 
+MAX_CONTRASTIVE_TOP_K = 16   # = GVL_MAX_DECODE_BATCH (csrc/gvl_limits.h): a step's candidates advance in ONE decode batch
+
+
+def resolve_contrastive(kw: dict) -> Optional[tuple]:
+    """HF's contrastive search among generate()'s kwargs -> (top_k, penalty_alpha), or None when the call is another mode.  HF's rule (GenerationMixin
+    ._get_generation_mode, transformers 4.40.1 [ext]): num_beams == 1, do_sample false, top_k not None and > 1, penalty_alpha not None and > 0.  penalty_alpha must be a
+    real number in [0, 1] whatever the mode (HF validates nothing and would compute with any value; here it travels to the device as one fp32 constant), and in the mode
+    top_k is an integer of at most MAX_CONTRASTIVE_TOP_K: the candidates of a step share one decode batch."""
+    a = kw.get("penalty_alpha")
+    if a is None:
+        return None
+    if isinstance(a, bool) or not isinstance(a, (int, float, np.integer, np.floating)) or not 0.0 <= float(a) <= 1.0:
+        raise ValueError(f"`penalty_alpha` has to be a float in [0, 1], but is {a!r}")
+    k = kw.get("top_k")
+    if not float(a) > 0 or k is None or kw.get("do_sample", False) or (kw.get("num_beams", 1) or 1) != 1:
+        return None
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"`top_k` has to be an integer, but is {k!r}")
+    if int(k) <= 1:
+        return None
+    if int(k) > MAX_CONTRASTIVE_TOP_K:
+        raise ValueError(f"contrastive search (penalty_alpha > 0): `top_k` is at most {MAX_CONTRASTIVE_TOP_K} (the candidates of a step share one decode batch), but is {k}")
+    return int(k), float(a)
+
+
 def negative_id_rows(ids, mask=None) -> list:
     """HF's negative_prompt_ids (+ negative_prompt_attention_mask) -> one plain list of token ids per row: a tensor / array / list of rows (or one flat row), the ids
     whose mask is 0 (padding) dropped.  Raises ValueError for an empty row, a negative id or a mask of another shape."""

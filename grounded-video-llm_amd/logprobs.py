@@ -29,6 +29,9 @@ class GenerateOutput:
     transition_scores: Optional[List[List[float]]] = None
     top_logprobs: Optional[List[List[List[Tuple[int, float]]]]] = None
     sequences_scores: Optional[List[float]] = None
+    # contrastive search (penalty_alpha, top_k) with output_scores: per token the degeneration penalty max_j cos(h, h_j) it was selected with; transition_scores are
+    # then the tokens' PROBABILITIES p (the model confidence of the score (1 - alpha) p - alpha pen), not log-probabilities
+    degeneration_penalties: Optional[List[List[float]]] = None
 
 
 @dataclass(frozen=True)

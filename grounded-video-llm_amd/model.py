@@ -42,6 +42,19 @@ def _sampling_args(kw):
     return t, top_p, int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+def _check_contrastive(kw) -> None:
+    """generate()'s contrastive search (logits.resolve_contrastive: penalty_alpha > 0, top_k > 1, do_sample false, num_beams 1) with the combinations that are not built
+    refused instead of ignored; penalty_alpha itself is validated whatever the mode."""
+    if LP.resolve_contrastive(kw) is None:
+        return
+    if LP.resolve_guidance(kw) is not None:
+        raise ValueError("generate(): contrastive search (penalty_alpha, top_k) with guidance_scale is not supported")
+    if (kw.get("num_return_sequences") or 1) > 1:
+        raise ValueError("generate(): contrastive search (penalty_alpha, top_k) is deterministic and returns one answer: num_return_sequences > 1 is not supported")
+    if kw.get("top_logprobs") is not None:
+        raise ValueError("generate(): `top_logprobs` is not supported with contrastive search (penalty_alpha, top_k); output_scores gives p and the degeneration penalty")
+
+
 def num_return_sequences(kw) -> int:
     """generate()'s num_return_sequences (None = 1), with HF's validation (GenerationConfig.validate / GenerationMixin._validate_generated_length [ext]) as ValueError, and
     the one combination that is not built yet -- guidance_scale with several answers -- refused instead of ignored."""
@@ -301,7 +314,7 @@ class LLAVA_NEXT_VIDEO:
         absent, and off for beam search, which applies them to its log-softmax rows itself -- so nothing carries over from one call to the next
         (the same rule as _select_tokens for sampling).  Returns the resolved processors."""
         procs = LP.resolve(kw, getattr(self.tokenizer, "eos_token_id", None), embed_len)
-        beams = kw.get("num_beams", 1) not in (1, None)
+        beams = kw.get("num_beams", 1) not in (1, None) or LP.resolve_contrastive(kw) is not None   # contrastive search processes its rows itself, as beams do
         self.engine.set_logits_processors(*(LP.OFF if beams else procs).args())
         return procs
 
@@ -315,7 +328,7 @@ class LLAVA_NEXT_VIDEO:
         if not rules.active:
             return None
         rid = self.engine.rules_create(rules)
-        if kw.get("num_beams", 1) in (1, None):
+        if kw.get("num_beams", 1) in (1, None) and LP.resolve_contrastive(kw) is None:
             self.engine.set_token_rules(rid)
         return rid
 
@@ -341,7 +354,7 @@ class LLAVA_NEXT_VIDEO:
         if g.vocab != self.geo.vocab:
             raise ValueError(f"generate(): the grammar classifies {g.vocab} ids, the model's vocabulary holds {self.geo.vocab}")
         gid = self.engine.grammar_create(g)
-        if kw.get("num_beams", 1) in (1, None):
+        if kw.get("num_beams", 1) in (1, None) and LP.resolve_contrastive(kw) is None:
             self.engine.set_grammar(gid)
         return gid
 
@@ -354,7 +367,7 @@ class LLAVA_NEXT_VIDEO:
         """return_dict_in_generate / output_scores / top_logprobs (logprobs.py; raises its ValueErrors).  Sets the engine's default on EVERY generate
         call -- the call's setting, off for beam search (its scores come from beam.py) -- so nothing carries over from one call to the next."""
         opts = LPR.resolve(kw)
-        beams = kw.get("num_beams", 1) not in (1, None)
+        beams = kw.get("num_beams", 1) not in (1, None) or LP.resolve_contrastive(kw) is not None   # contrastive search reports its own per-token p / penalty
         self.engine.set_logprobs(-1 if beams else opts.top_n)
         return opts
 
@@ -541,7 +554,12 @@ class LLAVA_NEXT_VIDEO:
         scale * (log_softmax(conditional) - log_softmax(negative)) + log_softmax(negative), computed on the device IN FRONT of every processor, rule, grammar and
         warper (HF's order), the first token included; the negative sequence is fed the token the conditional one selected and rides as one more row of the same
         decode step.  Greedy and sampling; log-probabilities are then the guided distribution's.  guidance_scale != 1 without a negative prompt, with num_beams > 1,
-        or in generate_shared raises ValueError (not supported yet).  Still not supported
+        or in generate_shared raises ValueError (not supported yet).
+        penalty_alpha = a in (0, 1] with top_k = k in 2 .. 16 (HF's; do_sample false, num_beams 1): contrastive search -- per token the k most probable ids (no warpers;
+        processors, rules and the grammar shape the row first) are each run one step and the arg-max of (1 - a) p - a max_j cos(h, h_j) over the hidden states of the
+        whole context wins, on the device (contrastive_generate_ids).  return_dict_in_generate with output_scores: transition_scores are the tokens' p,
+        degeneration_penalties their penalties.  With guidance_scale, num_return_sequences > 1 or top_logprobs, in generate_shared or ClipScheduler.submit it raises
+        ValueError (not built); penalty_alpha outside [0, 1] or top_k > 16 raises ValueError.  Still not supported
         and ignored: bad_words_ids=None, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
         remove_invalid_values, exponential_decay_length_penalty, constrained beams (constraints,
         force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
@@ -563,6 +581,7 @@ class LLAVA_NEXT_VIDEO:
         self._check_guidance(generate_kwargs, len(samples["prompts"]))     # ... and so do the guidance arguments
         num_return_sequences(generate_kwargs)             # ... and num_return_sequences
         beam_groups(generate_kwargs)                      # ... and num_beam_groups / diversity_penalty
+        _check_contrastive(generate_kwargs)               # ... and penalty_alpha / top_k
         ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
         pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
         ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
@@ -584,7 +603,18 @@ class LLAVA_NEXT_VIDEO:
         k = generate_kwargs.get("num_beams", 1) or 1
         n_ret = num_return_sequences(generate_kwargs)
         lps, beam_scores = None, None
-        if k > 1:                                         # HF beam search (do_sample=False), one sample at a time
+        cs = LP.resolve_contrastive(generate_kwargs)
+        if cs is not None:                                # HF contrastive search (penalty_alpha, top_k), one sample at a time like beams
+            scored = opts.return_dict and opts.output_scores
+            res = [self.contrastive_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], cs[0], cs[1], max_new, processors=procs, rules=rid,
+                                                 grammar=gid, with_scores=scored) for b in range(ids_arr.shape[0])]
+            if scored:
+                texts = [t.strip() for t in self.tokenizer.batch_decode([r[0] for r in res], skip_special_tokens=True)]
+                out = LPR.build_output(texts, [list(r[0]) for r in res], opts, [(r[1], None) for r in res])
+                out.degeneration_penalties = [list(r[2]) for r in res]
+                return out
+            out_ids = res
+        elif k > 1:                                         # HF beam search (do_sample=False), one sample at a time
             sample = None
             if generate_kwargs.get("do_sample", False):      # beam-sample (HF _beam_sample): the warpers' arguments as generate() takes them; one generator per call
                 t, top_p, seed = _sampling_args(generate_kwargs)
@@ -619,6 +649,30 @@ class LLAVA_NEXT_VIDEO:
         if not opts.return_dict:
             return texts
         return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps, beam_scores)
+
+    def contrastive_generate_ids(self, row: List[int], vis: torch.Tensor, top_k: int, penalty_alpha: float, max_new: int, processors: Optional["LP.Processors"] = None,
+                                 rules: Optional[int] = None, grammar: Optional[int] = None, with_scores: bool = False):
+        """generate(penalty_alpha = a, top_k = k): HF contrastive search (tests/contrastive_ref.py restates transformers 4.40.1's) inside the library
+        (Engine.contrastive_search = gvl_contrastive_search).  The prompt is prefilled once into a keep-hidden sequence -- its bank holds the post-final-norm hidden state
+        of every prompt row, the visual ones included --; per token the k most probable ids advance k sequences (the current one and k - 1 clones sharing its KV pages)
+        by one batched decode step, and the device ranks score = (1 - a) p - a max_j cos(h, h_j) over the bank.  Deterministic: no seed, one answer.  processors / rules:
+        applied to every step's raw logits row before the softmax (HF's order), history = the ids chosen so far; grammar: the search sequence carries it.  No warpers.
+        with_scores: (ids, p per id, degeneration penalty per id)."""
+        eng = self.engine
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        emb = eng.splice(row, vis)
+        seq = eng.seq_alloc(min(emb.shape[0], self.geo.max_seq))
+        try:
+            LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
+            eng.seq_keep_hidden(seq)
+            first = eng.prefill(seq, emb, want_logits=True)
+            procs = processors if processors is not None and processors.active else None
+            if not with_scores:
+                return eng.contrastive_search(seq, first, top_k, penalty_alpha, max_new, eos, procs, rules)
+            ids, tr = eng.contrastive_search(seq, first, top_k, penalty_alpha, max_new, eos, procs, rules, with_trace=True)
+            return ids, [tr["p"][s][r] for s, r in enumerate(tr["sel"])], [tr["pen"][s][r] for s, r in enumerate(tr["sel"])]
+        finally:
+            eng.seq_free(seq)
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
                           sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
@@ -754,6 +808,8 @@ class LLAVA_NEXT_VIDEO:
             raise ValueError("generate_shared(): guidance_scale != 1 is not supported yet (generate() takes it)")
         if beam_groups(generate_kwargs) is not None:
             raise ValueError("generate_shared(): num_beam_groups > 1 (diverse beam search) is not supported (generate() takes it)")
+        if LP.resolve_contrastive(generate_kwargs) is not None:
+            raise ValueError("generate_shared(): contrastive search (penalty_alpha > 0 with top_k > 1) is not supported (generate() takes it)")
         n_ret = num_return_sequences(generate_kwargs)
         if n_ret > 1 and (generate_kwargs.get("num_beams", 1) or 1) > 1:
             raise ValueError("generate_shared(): num_return_sequences > 1 is built for sampling (do_sample=True, num_beams=1); generate() returns the n best beams")

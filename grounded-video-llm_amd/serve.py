@@ -116,7 +116,7 @@ class ClipScheduler:
                top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None, typical_p: Optional[float] = None,
                epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, seed: Optional[int] = None, prefix: Optional[int] = None,
                grammar: Optional[int] = None, guidance_scale: Optional[float] = None, negative=None, num_return_sequences: Optional[int] = None,
-               num_beam_groups: Optional[int] = None, diversity_penalty: Optional[float] = None):
+               num_beam_groups: Optional[int] = None, diversity_penalty: Optional[float] = None, penalty_alpha: Optional[float] = None):
         """Queue one request.  embeds: the full spliced prompt.  prefix: an add_prefix() id -- the caller promises that the prompt's first P rows ARE the registered
         ones; only embeds[P:] (at least one row) is then prefilled.  An optimisation only: the result is the same without it.  (It is ignored for a request that
         LongRoPE forbids to share: P <= rope_orig_max_pos < len(embeds) -- a full prefill of that prompt ropes the shared rows with the long factors.)
@@ -144,7 +144,11 @@ class ClipScheduler:
         then on every answer is a request of its own that retires on its own eos.  Each answer's ids depend on its settings, its stream and its logits alone -- not on
         max_active, chunk or its neighbours.  Not with guidance_scale.
         num_beam_groups / diversity_penalty: the scheduler decodes greedily or by sampling, never by beams -- anything but (None / 1, None / 0) raises ValueError
-        (generate() runs diverse beam search)."""
+        (generate() runs diverse beam search).
+        penalty_alpha: with top_k it would select HF's contrastive search (logits.resolve_contrastive), which the scheduler does not run -- ValueError
+        (generate() takes it); a penalty_alpha that selects nothing (None, 0, or with do_sample) is accepted and has no effect, as in HF."""
+        if LP.resolve_contrastive(dict(penalty_alpha=penalty_alpha, top_k=top_k, do_sample=bool(do_sample))) is not None:
+            raise ValueError("ClipScheduler: contrastive search (penalty_alpha > 0 with top_k > 1) is not supported; generate() takes it")
         if num_beam_groups not in (None, 1) or diversity_penalty not in (None, 0, 0.0):
             raise ValueError("ClipScheduler: num_beam_groups / diversity_penalty (diverse beam search) are not supported; generate() takes them")
         n_fan = 1 if num_return_sequences is None else int(num_return_sequences)

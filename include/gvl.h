@@ -467,6 +467,60 @@ int gvl_group_beam_search(gvl_ctx* ctx, int seq_id, const float* first_logits, c
 int gvl_debug_group_beam_tokens(gvl_ctx* ctx, int32_t* out_host, int cap, int* n_out);
 int gvl_debug_group_beam_pool(gvl_ctx* ctx, int32_t* out_host, int cap, int* n_out);
 
+/* ---- contrastive search (HF generate(penalty_alpha > 0, top_k > 1, do_sample = False, num_beams = 1); transformers 4.40.1 GenerationMixin._contrastive_search and
+ * _ranking_fast [ext], restated in tests/contrastive_ref.py; batch of one) -----------------------------------------------------------------------------------------
+ * The hidden bank.  gvl_seq_keep_hidden(ctx, seq, 1) on an EMPTY sequence (before its prefill; GVL_ERR_STATE later) gives it a bank of max_tokens rows: per context row
+ * the hidden state AFTER the final RMSNorm -- bf16 [hidden], bit for bit gvl_op_rmsnorm of that residual row with the final norm weight (fp32 statistics, bf16 out) --
+ * and one fp32 inverse norm 1 / sqrtf(sum h^2) over the bf16 values of the row, summed in fp32 in a fixed order (lane l of one wave adds the squares of its elements
+ * 8 (l + 64 i) .. + 7 in index order, i ascending, then the xor butterfly 32, 16, .. 1).  One device allocation, all or nothing (GVL_ERR_OOM), freed with the sequence;
+ * on = 0 drops it.  hidden % 64 == 0 and hidden <= 8192, else GVL_ERR_ARG.  gvl_prefill of such a sequence runs the LAST decoder layer on every row (the last-layer
+ * tail is off: its MLP output IS the bank) and appends one bank row per prompt row; every gvl_decode_step_logits / gvl_decode_step_logits_batch step appends the row of
+ * the token it fed, so bank row j always belongs to position j.  Entries that are not taught the bank refuse a keep-hidden sequence with GVL_ERR_STATE and nothing
+ * changed: gvl_prefill_varlen / _batch, gvl_prefill_extend*, gvl_score_extend_varlen, gvl_forward_loss, gvl_seq_fork, gvl_seq_fanout, gvl_seq_set_guidance pairs,
+ * gvl_decode_greedy*, gvl_decode_steps, gvl_beam_search*.  gvl_seq_clone of a keep-hidden source gives a keep-hidden clone with its own copy of the rows so far
+ * (GVL_ERR_OOM with nothing opened when the copy cannot be allocated).
+ * gvl_seq_read_hidden: bank rows [first, first + n) as bf16 into rows_dev [n][hidden] and their inverse norms into inv_dev [n] (device; either may be NULL), on `stream`.
+ *
+ * gvl_contrastive_search.  seq_id is a PREFILLED keep-hidden sequence, first_logits (device, f32 [vocab]) the last_logits of its gvl_prefill.  Ownership is
+ * gvl_beam_search's: seq_id is never stepped, the search runs on clones (capacity min(tokens + max_new_tokens + 1, cfg.max_seq)) and a private copy of the bank, every
+ * sequence and buffer the call made is freed on every return path, the pool ends as it began.  Per step, the first token included:
+ *     row   = the current context's last logits, behind the processors / rule set / grammar (HF's order, on RAW logits; history = the ids chosen so far).  No warpers.
+ *     lp    = (l - max) - logf(sum exp(l - max))       gvl_beam_search's fixed-order log-softmax; candidates = the top_k largest lp, ties to the lower token id
+ *     p_i   = expf(lp_i)                               rounded once
+ *     the k candidates advance k sequences (the current one and k - 1 clones of it: opened all or nothing, their partial-page copies ONE launch) by ONE teacher-forced decode step on one stream of the weights (VALU-fallback
+ *     geometries: parts of 4 / 2 / 1); g_i = candidate i's bank row (the same normalisation code), with its inverse norm
+ *     dot_ij = sum_d g_i[d] h_j[d]                     fp32; products of two bf16 values are exact; the order depends on hidden only: lane l of an 8-lane group adds
+ *                                                      elements 8 (l + 8 c) .. + 7 in index order with one fma each, c ascending, then the xor butterfly 4, 2, 1
+ *     pen_i = max_j (dot_ij * inv_j) * ginv_i          bit-identical whatever k, the context length or the grid (the max is order-free)
+ *     score_i = fmaf(-alpha, pen_i, (1 - alpha) * p_i) fp32; the arg-max wins, ties go to the lower candidate rank.  A candidate whose lp is -inf (fewer than k ids
+ *                                                      survive a grammar or the token rules; it still fills its place in the trace) scores -inf and is never chosen
+ * The winner's sequence lives on and takes over the bank, its row is committed as bank row n_ctx by the ranking launch itself; the losers go back to the pool; the winner's
+ * logits are the next step's row.  One stream synchronise per step.  The search ends behind eos_id (appended) or at max_new_tokens.  Output: the new ids in out_ids_host
+ * [cap >= max_new_tokens], their number in *n_out.  Trace (each may be NULL; host arrays): trace_ids / trace_p / trace_pen [steps][top_k] -- candidate ids in rank order,
+ * their p and pen -- and trace_sel [steps], the selected rank.  trace_rows_dev (may be NULL; device f32 [cap][vocab]): per step the row the candidates were taken from,
+ * behind the processors / rule set / grammar -- bit for bit gvl_op_logits_process* of the raw row with the ids chosen so far as history.  final_hidden_dev (may be NULL; device bf16 [n_out][hidden]): the bank rows the search committed.
+ * Errors as gvl_beam_search's, and: top_k outside 2 .. 16, penalty_alpha outside [0, 1] or NaN, vocab < max(4, 2 * ((top_k + 1) / 2)) -- the candidate launches' row width --, the candidate rows beyond the ranking kernel's LDS
+ * (rows x hidden x 2 bytes <= 128 KiB with rows = top_k rounded up to 4, 8 or 16: top_k <= 8 up to hidden 8192, top_k 9 .. 16 up to hidden 4096) (all GVL_ERR_ARG, before anything runs); a sequence without a bank
+ * or whose bank is not in step with its position (GVL_ERR_STATE); device memory for the bank copy or KV pages exhausted (GVL_ERR_OOM). */
+typedef struct gvl_contrastive_params {
+  int top_k;                /* 2 .. 16 (GVL_MAX_DECODE_BATCH) */
+  float penalty_alpha;      /* 0 .. 1 */
+  int max_new_tokens;       /* >= 1 */
+  int eos_id;               /* -1: none */
+  float penalty; int ngram; int min_new; int proc_eos_id;  /* gvl_set_logits_processors' meaning; 1.0 / 0 / 0 / -1 = off */
+  int rules_id;             /* -1: none */
+} gvl_contrastive_params;
+int gvl_seq_keep_hidden(gvl_ctx* ctx, int seq_id, int on);
+int gvl_seq_read_hidden(gvl_ctx* ctx, int seq_id, int first, int n, uint16_t* rows_dev, float* inv_dev, void* stream);
+int gvl_contrastive_search(gvl_ctx* ctx, int seq_id, const float* first_logits, const gvl_contrastive_params* params, int32_t* out_ids_host, int cap, int* n_out,
+                           int32_t* trace_ids, float* trace_p, float* trace_pen, int32_t* trace_sel, float* trace_rows_dev, uint16_t* final_hidden_dev, void* stream);
+/* Operator entries (caller-owned device buffers).  gvl_op_hidden_bank_append: residual rows x [n][cols] bf16 (rows ldx elements apart) -> rows_out [n][cols] =
+ * gvl_op_rmsnorm(x, w, eps) bit for bit, inv_out [n] = their inverse norms (above).  gvl_op_contrastive_rank: bank [n_ctx][D] + bank_inv [n_ctx], cand [k][D] +
+ * cand_inv [k], p [k] -> pen [k], score [k], *sel (all device), in the arithmetic above.  D % 64 == 0, D <= 8192, 2 <= k <= 16, n_ctx >= 1, alpha in [0, 1]. */
+int gvl_op_hidden_bank_append(gvl_ctx* ctx, const uint16_t* x, int ldx, const uint16_t* w, float eps, uint16_t* rows_out, float* inv_out, int n, int cols, void* stream);
+int gvl_op_contrastive_rank(gvl_ctx* ctx, const uint16_t* bank, const float* bank_inv, int n_ctx, int D, const uint16_t* cand, const float* cand_inv, const float* p, int k,
+                            float alpha, float* pen, float* score, int32_t* sel, void* stream);
+
 /* ---- multi-GPU exchange (SURVEY.md §8 e) -------------------------------------------------------------------------------------
  * The reference's inference is single-GPU (inference.py:17); sharding the frame batch over the GPUs of a node is this build's
  * addition: every rank encodes its segments, ONE all-gather moves the per-segment token blocks (llava_next_video.py:563) to
@@ -515,7 +569,9 @@ int gvl_preprocess_frames(gvl_ctx* ctx, const uint8_t* frames, int n, int height
 /* When enabled, every launch of a kernel family is bracketed by hipEvents on the caller's stream
  * (slow; bench.py uses it for ONE profiled step after the timed region). */
 enum { GVL_PROF_GEMM = 0, GVL_PROF_ATTN = 1, GVL_PROF_GEMV = 2, GVL_PROF_DECODE_ATTN = 3, GVL_PROF_OTHER = 4,
-       GVL_PROF_NCAT = 5 };
+       GVL_PROF_CS_RANK = 5,    /* gvl_contrastive_search: the ranking launch of a step (rank + finish kernels), one record per step */
+       GVL_PROF_CS_CLONE = 6,   /* gvl_contrastive_search: the k - 1 clones of a step as ONE bracket (the launches inside are also booked under OTHER) */
+       GVL_PROF_NCAT = 7 };
 int gvl_prof_enable(gvl_ctx* ctx, int on);
 int gvl_prof_read(gvl_ctx* ctx, int category, double* total_ms, int64_t* launches, double* work);
 

@@ -60,6 +60,8 @@ def parse_args(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=None, help="HF RepetitionPenaltyLogitsProcessor on the generated ids (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=None, help="HF NoRepeatNGramLogitsProcessor on the generated ids (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=None, help="HF MinNewTokensLengthLogitsProcessor: no eos before this many new ids")
+    p.add_argument("--penalty_alpha", type=float, default=None, help="HF contrastive search: with --top_k > 1, --do_sample false and --num_beams 1 (0 < alpha <= 1)")
+    p.add_argument("--top_k", type=int, default=None, help="HF top_k: the sampling warper (HF default 50 when absent), or the candidates per token of contrastive search (2 .. 16)")
     p.add_argument("--guidance_scale", type=float, default=None, help="HF classifier-free guidance against --negative_prompt (None / 1 = off); not with --share_visual or --num_beams > 1")
     p.add_argument("--negative_prompt", type=str, default=None, help="the negative prompt of --guidance_scale: with <image> it sees the same video, without it it is the video-free contrast")
     p.add_argument("--num_return_sequences", type=int, default=1, help="HF num_return_sequences: n sampled answers per prompt from ONE prefill (needs --do_sample True), or the n best "
@@ -157,7 +159,7 @@ def main(argv=None):
         frames, fps, vlen, duration = read_frames(args.video_path, args.num_frames)
 
     kw = {"do_sample": args.do_sample, "num_beams": args.num_beams, "max_new_tokens": args.max_new_tokens, "temperature": args.temperature, "top_p": args.top_p, "seed": args.seed}
-    for name in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"):     # forwarded only when given, like any other HF generate kwarg
+    for name in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "penalty_alpha", "top_k"):     # forwarded only when given, like any other HF generate kwarg
         if getattr(args, name) is not None:
             kw[name] = getattr(args, name)
     if args.guidance_scale not in (None, 1.0):
