@@ -103,6 +103,24 @@ def warp_scores(scores: torch.Tensor, temperature: float = 1.0, top_k: Optional[
     return s
 
 
+def reorder(beams: Sequence[Optional[int]], parents: Sequence[Optional[int]]) -> Tuple[List[Optional[int]], List[int], List[int]]:
+    """HF's cache reorder as a plan over beam slots (csrc/gvl_beam.h's reorder, the one definition every stepper follows): new beam j continues old slot parents[j]
+    (None: slot j dies); beams[q] None: slot q is closed already.  Returns (src, clones, closed): src[j] the slot beam j continues or None; clones the j that need a
+    clone of beams[src[j]] -- every child of a parent but its first, made before anything is closed --; closed the live slots nobody continues.  Both ascending."""
+    src: List[Optional[int]] = [None] * len(parents)
+    kept, clones = set(), []
+    for j, p in enumerate(parents):
+        if p is None or p < 0:
+            continue
+        if p >= len(beams) or beams[p] is None:
+            raise ValueError("a beam continues a closed beam")
+        src[j] = p
+        if p in kept:
+            clones.append(j)
+        kept.add(p)
+    return src, clones, [q for q, b in enumerate(beams) if b is not None and q not in kept]
+
+
 def beam_search(step: Callable[[List[int], List[int]], torch.Tensor], first_logits: torch.Tensor, num_beams: int, max_new_tokens: int,
                 eos_id: Optional[int], length_penalty: float = 1.0, early_stopping=False, sample: Optional[dict] = None,
                 process: Optional[Callable[[List[List[int]], torch.Tensor], torch.Tensor]] = None, with_scores: bool = False,

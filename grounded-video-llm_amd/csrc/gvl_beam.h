@@ -10,6 +10,7 @@
 #pragma once
 #include <cmath>
 #include <cstddef>
+#include <string>
 #include <vector>
 
 namespace gvl_beam {
@@ -24,6 +25,53 @@ inline const char* status_text(int s) {
     case BEAM_ERR_ARG: return "bad beam-search arguments or candidate list";
     default: return "";
   }
+}
+
+// What gvl_beam_search_n (groups 0) and gvl_group_beam_search (groups = num_beam_groups) refuse by the VALUES of their arguments alone, each in its own order: "" or
+// what is wrong (the entry prefixes its name).  max_new_cap: the room of a sequence's output list.
+inline std::string refusal(bool grouped, int k, int groups, float diversity_penalty, int num_return, int vocab, int max_new, int max_new_cap, int cap, int early_stopping,
+                           double length_penalty, float penalty, int ngram, int min_new) {
+  const char* nr = num_return < 1 || num_return > k ? "num_return must be 1 .. num_beams" : nullptr;
+  if (!grouped && nr) return nr;
+  if (k < 2 || k > 16) return "num_beams must be 2 .. 16";
+  if (grouped) {
+    if (groups < 2 || groups > k || k % groups != 0) return "num_beam_groups must be 2 .. num_beams and divide num_beams";
+    if (!(diversity_penalty > 0.f)) return "diversity_penalty must be > 0";
+    if (nr) return nr;
+  }
+  const int s = grouped ? k / groups : k;                  // the rows of one candidate launch
+  if (vocab < 2 * s) return grouped ? "vocabulary smaller than 2 x the beams of a group" : "vocabulary smaller than 2 x num_beams";
+  if ((long long)vocab * s > 0x7fffffffLL) return grouped ? "beams of a group x vocabulary must fit an int32" : "num_beams x vocabulary must fit an int32";
+  if (max_new < 1 || max_new > max_new_cap) return "max_new_tokens must be 1 .. " + std::to_string(max_new_cap);
+  if (cap < max_new) return "cap (room of out_ids_host) must be >= max_new_tokens";
+  if (early_stopping < 0 || early_stopping > 2) return "early_stopping must be 0 (False), 1 (True) or 2 (\"never\")";
+  if (early_stopping == 2 && length_penalty > 0.0) return status_text(BEAM_ERR_NEVER);
+  if (!(length_penalty == length_penalty)) return "length_penalty is NaN";
+  if (!(penalty > 0.f) || ngram < 0 || min_new < 0) return "penalty must be > 0, ngram >= 0, min_new >= 0";
+  return "";
+}
+
+// HF's cache reorder as a plan over beam SLOTS: new beam j continues old slot parents[j] (< 0: slot j dies).  The first child of a parent keeps the parent's sequence,
+// every further child is a clone of it -- made while the parent is still at the length the children continue from, so before anything is closed --, and a live parent
+// without a child is closed.  beams[q] < 0: slot q is closed already.
+struct ReorderPlan {
+  std::vector<int> src;      // [k] the slot new beam j continues, -1: dies
+  std::vector<int> clones;   // the j that get a clone of beams[src[j]], ascending; every other live j takes beams[src[j]] itself
+  std::vector<int> closed;   // the live slots nobody continues, ascending
+};
+// false (plan unusable): a parent out of range or closed already
+inline bool reorder(const std::vector<int>& beams, const int* parents, int k, ReorderPlan* plan) {
+  plan->src.assign(k, -1); plan->clones.clear(); plan->closed.clear();
+  std::vector<char> kept(beams.size(), 0);
+  for (int j = 0; j < k; ++j) {
+    const int pj = parents[j];
+    if (pj < 0) continue;
+    if (pj >= (int)beams.size() || beams[pj] < 0) return false;
+    plan->src[j] = pj;
+    if (kept[pj]) plan->clones.push_back(j); else kept[pj] = 1;
+  }
+  for (size_t q = 0; q < beams.size(); ++q) if (!kept[q] && beams[q] >= 0) plan->closed.push_back((int)q);
+  return true;
 }
 
 struct Hyp { double score = 0.0; std::vector<int> ids; bool by_eos = false; std::vector<float> token_scores; };

@@ -2,7 +2,7 @@
 // GenerationMixin._contrastive_search / _ranking_fast [ext], restated in tests/contrastive_ref.py) inside the library, the hidden bank it ranks against
 // (gvl_seq_keep_hidden / gvl_seq_read_hidden) and the operator-level entries of its two kernels.  The bookkeeping is gvl_contrastive.h (host-only, CPU-tested); the top-k
 // of the probabilities are gvl_beam_search's candidate launches (gvl_pick.hip: the fixed-order log-softmax, ties to the lower id); the candidates advance through
-// decode_step (gvl_llm.hip) on clones of the caller's sequence.
+// the SearchSession (gvl_search.hip: the clones of the caller's sequence, the processor launch, the teacher-forced step).
 //   hidden_bank_append_kernel   residual rows -> final RMSNorm (rmsnorm_bf16_kernel's arithmetic, statement for statement: bit-identical rows) -> bf16 bank row + its
 //                               inverse norm 1 / sqrtf(sum h^2) over the ROUNDED row, one wave per row
 //   contrastive_rank_kernel     every context row against the k candidate rows in LDS: the bank is read once, 16 bytes per lane.  Eight lanes share a row: lane l takes
@@ -209,14 +209,6 @@ int cs_buffers(gvl_ctx* ctx, CsBufs* b) {
   return 0;
 }
 
-// every sequence the search made goes back on every return path (its bank with it: gvl_ctx::close)
-struct Owned {
-  gvl_ctx* ctx; std::vector<int> ids;
-  explicit Owned(gvl_ctx* c) : ctx(c) {}
-  ~Owned() { for (int id : ids) ctx->close(id); }
-  void drop(int id) { ids.erase(std::find(ids.begin(), ids.end(), id)); ctx->close(id); }
-};
-
 }  // namespace
 
 int gvlm::bank_append(gvl_ctx* ctx, Seq& s, const bf16_t* x, int ldx, int n, hipStream_t st) {
@@ -289,108 +281,64 @@ int gvl_contrastive_search(gvl_ctx* ctx, int seq_id, const float* first_logits, 
   const float alpha = p->penalty_alpha;
   if (const char* why = gvl_contrastive::refusal(k, alpha, max_new, ctx->outlist_cap, cap, V, Hd)) return fail(ctx, GVL_ERR_ARG, std::string("gvl_contrastive_search: ") + why);
   if (!(p->penalty > 0.f) || p->ngram < 0 || p->min_new < 0) return fail(ctx, GVL_ERR_ARG, "gvl_contrastive_search: penalty must be > 0, ngram >= 0, min_new >= 0");
-  if (p->rules_id != -1 && (p->rules_id < 0 || ctx->check_rules(p->rules_id))) return seq_fail(ctx, "gvl_contrastive_search", SEQ_NO_RULES);
-  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_contrastive_search", SEQ_BAD);
-  if (const int rc = pair_refuse(ctx, "gvl_contrastive_search", seq_id, true)) return rc;
-  const int pos0 = ctx->seqs[seq_id].pos;
-  if (pos0 <= 0) return fail(ctx, GVL_ERR_STATE, "gvl_contrastive_search: the sequence is not prefilled");
-  if (!ctx->seqs[seq_id].bank) return fail(ctx, GVL_ERR_STATE, "gvl_contrastive_search: the sequence keeps no hidden states (gvl_seq_keep_hidden before its prefill)");
-  if (ctx->seqs[seq_id].bank_rows != pos0) return fail(ctx, GVL_ERR_STATE, "gvl_contrastive_search: the hidden bank is not in step with the sequence");
-  if (const int rc = beam_search_buffers(ctx)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // The current sequence -- at first the session's root clone -- carries a private copy of the caller's bank.
+  SearchSession ss(ctx, "gvl_contrastive_search", st);
+  if (const int rc = ss.open(seq_id, p->penalty, p->ngram, p->min_new, p->proc_eos_id, p->rules_id, max_new, true)) return rc;
   CsBufs cb;
   if (const int rc = cs_buffers(ctx, &cb)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-
-  LogitsProc proc{p->penalty, p->ngram, p->min_new, p->proc_eos_id < 0 ? -1 : p->proc_eos_id};
-  const int grammar_id = ctx->seqs[seq_id].sel.grammar;      // the caller's sequence holds its reference for the whole call
-  const GrammarDev* grammar = grammar_id >= 0 ? (const GrammarDev*)ctx->grammars[grammar_id].d : nullptr;
-  const TokenRulesDev* rules = p->rules_id >= 0 ? (const TokenRulesDev*)ctx->rule_sets[p->rules_id].d : nullptr;
-  const bool processed = proc.on() || rules || grammar;
-  const int seq_cap = std::min(pos0 + max_new + 1, (int)ctx->cfg.max_seq);
+  const int pos0 = ss.pos0;
 
   gvl_contrastive::State cs;
   if (cs.init(k, max_new, p->eos_id) < 0) return fail(ctx, GVL_ERR_ARG, "gvl_contrastive_search: bad arguments");
 
-  // The search runs on clones of the caller's sequence (never stepped: on return it is where it was) with their selection options off, so a step's own token pick
-  // leaves the logits rows raw.  The current sequence carries a private copy of the caller's bank.
-  Owned own(ctx);
-  auto clone = [&](int src, int* dst) {
-    const int rc = seq_clone(ctx, src, seq_cap, dst, st, false);
-    if (rc == 0) own.ids.push_back(*dst);
-    return rc;
-  };
-  int cur = -1;
-  if (const int rc = clone(seq_id, &cur)) return rc;
-  { SeqSelect& sel = ctx->seqs[cur].sel;
-    sel.proc = LogitsProc(); ctx->set_rules(sel, -1); ctx->set_grammar(sel, -1); sel.top_n = -1;
-    const Sampling greedy; ctx->set_sampling(sel, &greedy); }
-  if (const int rc = bank_alloc(ctx, ctx->seqs[cur], seq_cap)) return fail(ctx, rc, "gvl_contrastive_search: no device memory for the search's copy of the hidden bank");
+  int cur = ss.root;
+  if (const int rc = bank_alloc(ctx, ctx->seqs[cur], ss.seq_cap)) return fail(ctx, rc, "gvl_contrastive_search: no device memory for the search's copy of the hidden bank");
   { const Seq& from = ctx->seqs[seq_id]; Seq& to = ctx->seqs[cur];
     RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(from.bank, to.bank, (size_t)pos0 * Hd * 2, st));
     RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(from.bank_inv, to.bank_inv, (size_t)pos0 * 4, st));
     to.bank_rows = pos0; }
 
-  const BeamCandBufs bb = beam_cand_bufs(ctx);
   const int kb = gvl_contrastive::cand_beams(k);
   float cand_scores[GVL_MAX_DECODE_BATCH];
   for (int b = 0; b < GVL_MAX_DECODE_BATCH; ++b) cand_scores[b] = b == 0 ? 0.f : -INFINITY;   // every "beam" reads the one row; only the first one's entries can rank
-  int* d_hist = ctx->d_beam_hist; int* d_lens = ctx->d_beam_hist + (size_t)GVL_MAX_DECODE_BATCH * GVL_LOGITS_HIST_CAP;
-  std::vector<int> h_hist;
   float* row = nullptr;                                    // the current context's last logits; null: the caller's first_logits
   int n_ctx = pos0;
 
   for (int step = 0;; ++step) {
-    if (processed) {
+    if (ss.processed) {
       // HF's order: processors (token rules around them, then the grammar) on the RAW logits, then the softmax.  In place on the library's rows; first_logits are copied.
-      if (!row) { row = ctx->d_beam_rows; HIPCHK(ctx, hipMemcpyAsync(row, first_logits, (size_t)V * 4, hipMemcpyDeviceToDevice, st)); }
-      const int len = (int)cs.ids.size(), hs = len > 0 ? std::min(len, (int)GVL_LOGITS_HIST_CAP) : 1;
-      h_hist.assign((size_t)hs + 1, 0);
-      for (int i = 0; i < hs && i < len; ++i) h_hist[i] = cs.ids[i];
-      h_hist[hs] = len;
-      HIPCHK(ctx, hipMemcpyAsync(d_hist, h_hist.data(), (size_t)hs * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(ctx, hipMemcpyAsync(d_lens, h_hist.data() + hs, 4, hipMemcpyHostToDevice, st));
-      LogitsProcArgs lp; memset(&lp, 0, sizeof(lp));
-      lp.logits = row; lp.n = V; lp.ld = V; lp.batch = 1; lp.cap = hs;
-      lp.hist[0] = d_hist; lp.len_ptrs[0] = d_lens;
-      lp.penalty[0] = proc.penalty; lp.ngram[0] = proc.ngram; lp.eos[0] = proc.eos; lp.min_new[0] = proc.eos >= 0 ? proc.min_new : 0; lp.rules[0] = rules; lp.grammar[0] = grammar;
-      RUN(GVL_PROF_OTHER, 0, gvl_launch_logits_process(lp, st));
+      if (!row) { if (const int rc = ss.copy_first(first_logits, &row)) return rc; }
+      const std::vector<int>* hist = &cs.ids;
+      if (const int rc = ss.upload_histories(1, (int)cs.ids.size(), &hist)) return rc;
+      if (const int rc = ss.process(row, 0, 1)) return rc;
     }
     if (trace_rows_dev) HIPCHK(ctx, hipMemcpyAsync(trace_rows_dev + (size_t)step * V, row ? row : first_logits, (size_t)V * 4, hipMemcpyDeviceToDevice, st));
     // the top_k of the probabilities: the log-softmax and the strict order (value descending, id ascending) of gvl_beam_search's candidate launches
-    BeamCandArgs ca; beam_cand_args(ctx, ca, row ? row : first_logits, V, kb, 0, cand_scores, 1, bb.d_vals, bb.d_idx, bb.d_proc);
+    BeamCandArgs ca; SearchSession::cand_args(ctx, ca, row ? row : first_logits, V, kb, 0, cand_scores, 1, ss.d_vals, ss.d_idx, ss.d_proc);
     RUN(GVL_PROF_OTHER, 0, gvl_launch_beam_candidates(ca, st));
 
     // k - 1 clones of the current sequence; candidate i runs on seqs[i]
     int seqs[GVL_MAX_DECODE_BATCH]; seqs[0] = cur;
-    { ProfScope clones(ctx, GVL_PROF_CS_CLONE, 0, st);   // all or nothing; the partial-page copies of all k - 1 are one launch
-      if (const int crc = seq_clone_many(ctx, cur, seq_cap, k - 1, seqs + 1, st)) return crc;
-      for (int i = 1; i < k; ++i) own.ids.push_back(seqs[i]); }
+    if (const int crc = ss.clone_many(cur, k - 1, seqs + 1)) return crc;
     Seq* sqs[GVL_MAX_DECODE_BATCH];
-    FeedArgs fa; memset(&fa, 0, sizeof(fa)); fa.idx = bb.d_idx; fa.k = k;
-    for (int i = 0; i < k; ++i) {
-      sqs[i] = &ctx->seqs[seqs[i]];
-      if (sqs[i]->pos >= sqs[i]->max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_contrastive_search: the context is full (cfg.max_seq) before max_new_tokens");
-      fa.tok[i] = sqs[i]->d_tok;
-    }
+    FeedArgs fa; memset(&fa, 0, sizeof(fa)); fa.idx = ss.d_idx; fa.k = k;
+    for (int i = 0; i < k; ++i) { sqs[i] = &ctx->seqs[seqs[i]]; fa.tok[i] = sqs[i]->d_tok; }
     Seq& cs_seq = *sqs[0];
     if (cs_seq.bank_rows != n_ctx || n_ctx >= cs_seq.bank_cap) return fail(ctx, GVL_ERR_STATE, "gvl_contrastive_search: the hidden bank is out of step");
     hipLaunchKernelGGL(contrastive_feed_kernel, dim3(1), dim3(64), 0, st, fa);
     if (hipGetLastError() != hipSuccess) return fail(ctx, GVL_ERR_HIP, "gvl_contrastive_search: launch failed");
 
-    // one teacher-forced step of the k candidates, in the parts the decode path takes; a part's residual rows become candidate rows before the next part overwrites them
-    int sizes[GVL_MAX_DECODE_BATCH];
-    const int n_parts = decode_parts(ctx->decode_mfma, k, sizes);
-    const bool one_part = n_parts == 1;
-    for (int q = 0, o = 0; q < n_parts; ++q) {
-      const int nb = sizes[q];
-      if (const int drc = decode_step(ctx, sqs + o, nb, st)) return drc;
+    // one teacher-forced step of the k candidates; a part's residual rows become candidate rows before the next part overwrites them
+    float* rows = nullptr;
+    const auto append_cand = [&](int o, int nb) -> int {
       RUN(GVL_PROF_OTHER, 0, launch_hidden_append(ctx->d_x, Hd, ctx->l_norm, ctx->cfg.rms_eps, cb.cand + (size_t)o * Hd, cb.cand_inv + o, nb, Hd, st));
-      if (!one_part) HIPCHK(ctx, hipMemcpyAsync(ctx->d_beam_rows + (size_t)o * V, ctx->d_logits, (size_t)nb * V * 4, hipMemcpyDeviceToDevice, st));
-      o += nb;
-    }
+      return 0;
+    };
+    if (const int arc = ss.advance(sqs, k, nullptr, append_cand, &rows)) return arc;
     RankArgs ra; memset(&ra, 0, sizeof(ra));
     ra.bank = cs_seq.bank; ra.bank_inv = cs_seq.bank_inv; ra.n_ctx = n_ctx; ra.D = Hd; ra.k = k; ra.cand = cb.cand; ra.cand_inv = cb.cand_inv;
-    ra.p = bb.d_proc; ra.p_is_logprob = 1; ra.alpha = alpha; ra.part = cb.part; ra.pen = cb.d_pen; ra.score = cb.d_score; ra.p_out = cb.d_p; ra.sel = cb.d_sel;
+    ra.p = ss.d_proc; ra.p_is_logprob = 1; ra.alpha = alpha; ra.part = cb.part; ra.pen = cb.d_pen; ra.score = cb.d_score; ra.p_out = cb.d_p; ra.sel = cb.d_sel;
     ra.commit_row = cs_seq.bank + (size_t)n_ctx * Hd; ra.commit_inv = cs_seq.bank_inv + n_ctx;
     RUN(GVL_PROF_CS_RANK, 0, launch_rank(ra, st));
     HIPCHK(ctx, hipStreamSynchronize(st));               // the ONE synchronise of the step: candidate ids, p, pen and the selected rank sit in host-mapped memory
@@ -398,7 +346,7 @@ int gvl_contrastive_search(gvl_ctx* ctx, int seq_id, const float* first_logits, 
     const int sel = *cb.h_sel;
     int cand_ids[GVL_MAX_DECODE_BATCH];
     for (int i = 0; i < k; ++i) {
-      cand_ids[i] = bb.h_idx[i];
+      cand_ids[i] = ss.h_idx[i];
       if (cand_ids[i] < 0 || cand_ids[i] >= V) return fail(ctx, GVL_ERR_HIP, "gvl_contrastive_search: a candidate id outside the vocabulary");
       if (trace_ids) trace_ids[(size_t)step * k + i] = cand_ids[i];
       if (trace_p) trace_p[(size_t)step * k + i] = cb.h_p[i];
@@ -413,9 +361,9 @@ int gvl_contrastive_search(gvl_ctx* ctx, int seq_id, const float* first_logits, 
       std::swap(w.bank, c.bank); std::swap(w.bank_inv, c.bank_inv); std::swap(w.bank_cap, c.bank_cap); std::swap(w.bank_rows, c.bank_rows);
     }
     ctx->seqs[winner].bank_rows = ++n_ctx;
-    for (int i = 0; i < k - 1; ++i) own.drop(losers[i]);
+    for (int i = 0; i < k - 1; ++i) ss.drop(losers[i]);
     cur = winner;
-    row = (one_part ? ctx->d_logits : ctx->d_beam_rows) + (size_t)sel * V;
+    row = rows + (size_t)sel * V;
     if (rc == gvl_contrastive::CS_FINISHED) break;
   }
 

@@ -116,7 +116,7 @@ struct gvl_ctx : SeqTable<Seq> {          // the base: sequences, KV pages, rule
   // log-probability lists of every sequence slot ([kMaxSeqs][outlist_cap], top lists x GVL_MAX_TOP_LOGPROBS: ~134 MB), allocated by the first
   // gvl_set_logprobs / gvl_seq_set_logprobs that needs them
   float* d_seq_lp = nullptr; int* d_seq_top_ids = nullptr; float* d_seq_top_lp = nullptr;
-  // beam search (gvl_beam.hip), allocated by the first call that needs them: the per-row survivors between the two candidate launches, one step's candidates in HOST-MAPPED
+  // the searches (SearchSession, gvl_search.hip), allocated by the first call that needs them: the per-row survivors between the two candidate launches, one step's candidates in HOST-MAPPED
   // memory (h_ / d_ views), [GVL_MAX_DECODE_BATCH][vocab] work rows, and the beams' histories + lengths for the logits processors
   void* d_beam_scratch = nullptr; void* h_beam_cand = nullptr; void* d_beam_cand = nullptr; float* d_beam_rows = nullptr; int* d_beam_hist = nullptr;
   // contrastive search (gvl_contrastive.hip), allocated by the first call that needs them: [16][hidden] bf16 candidate rows + [16] inverse norms + the ranking launch's

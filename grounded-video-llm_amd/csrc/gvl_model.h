@@ -1,8 +1,9 @@
-// gvl_model.h -- what the four host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the sequence / prefill / decode
+// gvl_model.h -- what the host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the sequence / prefill / decode
 // and operator entry points of include/gvl.h), gvl_select.hip (the token-selection entry points), gvl_vision.hip (the towers' launch sequences) and
 // gvl_llm.hip (prefill, the decode step -- planned in gvl_decode_plan.h --, the decode loop).  Internal: nothing here is part of the ABI.
 #pragma once
 #include "gvl_ctx.h"
+#include <functional>
 #include "gvl_decode_plan.h"   // the decode path's predicates, batch admission and grouping, and decode_step's launch plan (host-only, tested on the CPU)
 
 namespace gvlm {
@@ -117,12 +118,58 @@ int bank_refuse(gvl_ctx* c, const char* fn, int id);
 int bank_alloc(gvl_ctx* ctx, Seq& s, int cap);
 int bank_append(gvl_ctx* ctx, Seq& s, const bf16_t* x, int ldx, int n, hipStream_t st);
 
-// gvl_beam.hip: the [16][vocab] work rows, histories and candidate buffers of a search (allocated on first use); the arguments of one candidate launch; one step's
-// best 2k candidates (value, flat index, log-probability) in host-mapped memory, host and device views
-int beam_search_buffers(gvl_ctx* ctx);
-void beam_cand_args(gvl_ctx* ctx, BeamCandArgs& a, const float* rows, int n, int k, int row_stride, const float* scores, int norm, float* vals, int* idx, float* proc);
-struct BeamCandBufs { float *h_vals, *d_vals; int *h_idx, *d_idx; float *h_proc, *d_proc; };
-BeamCandBufs beam_cand_bufs(gvl_ctx* ctx);
+// gvl_search.hip: one search inside the library (gvl_beam_search_n, gvl_group_beam_search, gvl_contrastive_search), entry point `fn`, on `stream`.  Every int result is
+// 0 or the error the entry returns (gvl_fail has the message, prefixed with fn).  The searches keep their own loops; this is what they share.
+struct SearchSession {
+  gvl_ctx* ctx; const char* fn; hipStream_t st;
+  SearchSession(gvl_ctx* c, const char* fn_, hipStream_t s) : ctx(c), fn(fn_), st(s) {}
+  ~SearchSession();                              // every sequence the search still holds goes back to the pool (its bank with it: gvl_ctx::close)
+  SearchSession(const SearchSession&) = delete;
+  SearchSession& operator=(const SearchSession&) = delete;
+
+  // The sequence-side refusals, in this order: rules_id, seq_id, guided pairs, the hidden bank (ranks_hidden false: a keep-hidden sequence is refused; true: the bank
+  // must be there and in step), "not prefilled" in front of the bank's state.  Then the buffers, the processors / rules / the CALLER's grammar, and `root`: a clone of
+  // the caller's sequence with every selection option off (further clones copy that).
+  int open(int seq_id, float penalty, int ngram, int min_new, int proc_eos_id, int rules_id, int max_new, bool ranks_hidden);
+  int V = 0, pos0 = 0, seq_cap = 0, root = -1;
+  LogitsProc proc; const TokenRulesDev* rules = nullptr; const GrammarDev* grammar = nullptr; bool processed = false;
+
+  std::vector<int> ids;                          // the sequences the search holds
+  int clone(int src, int* dst);                  // history-less, bank-less clones of seq_cap tokens
+  int clone_many(int src, int n, int* dst);      // n at once, all or nothing (seq_clone_many), one GVL_PROF_CS_CLONE record
+  void drop(int id);
+
+  // one step's candidates in host-mapped memory, [2 * 16] each: (value, flat index, log-probability), and behind them the [16] tokens the groups of a diverse beam
+  // search chose (d_chosen: where the device chains them; d_chosen_mirror / h_chosen: the host-mapped copy)
+  float *h_vals = nullptr, *h_proc = nullptr, *d_vals = nullptr, *d_proc = nullptr;
+  int *h_idx = nullptr, *d_idx = nullptr, *h_chosen = nullptr, *d_chosen_mirror = nullptr, *d_chosen = nullptr;
+  static int ensure_scratch(gvl_ctx* ctx);       // what a candidate launch alone needs (the operator entries)
+  static int ensure_buffers(gvl_ctx* ctx);
+  static void cand_args(gvl_ctx* ctx, BeamCandArgs& a, const float* rows, int n, int k, int row_stride, const float* scores, int norm, float* vals, int* idx, float* proc);
+
+  // the caller's first_logits -> the first work row (the processors work in place and never on the caller's memory)
+  int copy_first(const float* first_logits, float** work);
+  // histories of n_rows work rows, `len` ids each (the last GVL_LOGITS_HIST_CAP are kept); row_ids[r] null: zeros.  Two copies on the stream; the staging vector is
+  // free again behind the step's synchronise
+  int upload_histories(int n_rows, int len, const std::vector<int>* const* row_ids);
+  // the processor launch over work rows [n_rows][V] whose histories are rows first_row .. of the last upload; ham_tok: the Hamming term over ham_n chosen tokens
+  int process(float* work, int first_row, int n_rows, const int* ham_tok = nullptr, int ham_n = 0, float ham_lambda = 0.f);
+
+  // One teacher-forced step of n sequences: "the context is full", toks[j] -> sequence j's input (null: the caller fed them on the stream), then decode_step per
+  // part of the decode path; after_part(first row, rows) runs between a part's step and the gather of its logits rows (d_x still holds the part's residual rows).
+  // *rows: [n][V], valid until the next step
+  using PartHook = std::function<int(int, int)>;
+  int advance(Seq* const* sqs, int n, const int* toks, const PartHook& after_part, float** rows);
+  // HF's cache reorder (gvl_beam::reorder, gvl_beam.h) over sequence ids: beams[j] = the sequence of beam j, -1 closed; new beam j continues parents[j] (< 0: dies)
+  int reorder(std::vector<int>& beams, const int* parents, int k);
+  // the num_return best hypotheses (finalize_n's output, `got` of them) -> the caller's arrays, rows `cap` apart
+  int write_hypotheses(int got, int num_return, const std::vector<std::vector<int>>& hyp_ids, const std::vector<double>& score, const std::vector<std::vector<float>>& ts,
+                       int32_t* out_ids_host, int cap, int* n_out, double* sequences_scores, float* transition_scores_host);
+
+ private:
+  int* d_hist = nullptr; int* d_lens = nullptr; int hs = 1;
+  std::vector<int> h_hist;
+};
 
 // gvl_llm.hip
 int upload_table(gvl_ctx* ctx, Seq& s, hipStream_t st);

@@ -551,33 +551,44 @@ class Engine:
         self._chk(self.lib.gvl_op_beam_normalize(self.ctx, _ptr(rows), rows.shape[1], rows.shape[0], self.stream), "gvl_op_beam_normalize")
         return rows
 
-    def beam_search(self, seq: int, first_logits: torch.Tensor, num_beams: int, max_new: int, eos: Optional[int], length_penalty: float = 1.0, early_stopping=False,
-                    processors=None, rules: Optional[int] = None, with_scores: bool = False, num_return: int = 1):
-        """gvl_beam_search: HF beam search (num_beams = k, do_sample = False) from the PREFILLED sequence `seq` and its prefill logits, inside the library; `seq` is not
-        consumed.  processors: a logits.Processors (None = off); rules: a rule-set id (None = none); early_stopping: False / True / "never".  Returns the new ids, or with
-        with_scores (ids, sequences_score, transition_scores) as beam.beam_search does.  num_return > 1 (gvl_beam_search_n): a list of such results, the num_return best
-        hypotheses, best first."""
+    def _beam_params(self, first_logits: torch.Tensor, num_beams: int, max_new: int, eos: Optional[int], length_penalty: float, early_stopping, processors,
+                     rules: Optional[int]) -> "L.GvlBeamParams":
+        """what the two beam entries share of their arguments"""
         if early_stopping not in (False, True, "never"):
             raise ValueError("early_stopping must be False, True or 'never'")
         assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.device == self.device
         pe, ng, mn, pe_eos = processors.args() if processors is not None else (1.0, 0, 0, None)
-        prm = L.GvlBeamParams(int(num_beams), int(max_new), -1 if eos is None else int(eos), float(length_penalty), {False: 0, True: 1, "never": 2}[early_stopping],
-                              float(pe), int(ng), int(mn), -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
+        return L.GvlBeamParams(int(num_beams), int(max_new), -1 if eos is None else int(eos), float(length_penalty), {False: 0, True: 1, "never": 2}[early_stopping],
+                               float(pe), int(ng), int(mn), -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
+
+    def _run_beam_entry(self, entry, num_beams: int, max_new: int, num_return: int, with_scores: bool):
+        """entry(nr, ids, cap, n, score, ts) -> (status, name): one beam entry over result buffers for num_return hypotheses, unpacked as beam_search documents"""
         cap, nr = max(int(max_new), 1), int(num_return)
         if nr < 1 or nr > int(num_beams):
             raise ValueError("num_return must be 1 .. num_beams")
         ids = (C.c_int32 * (cap * nr))()
         ts = (C.c_float * (cap * nr))()
         n, score = (C.c_int * nr)(), (C.c_double * nr)()
-        if nr == 1:
-            self._chk(self.lib.gvl_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, n, score, ts, self.stream), "gvl_beam_search")
-        else:
-            self._chk(self.lib.gvl_beam_search_n(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), nr, ids, cap, n, score, ts, self.stream), "gvl_beam_search_n")
+        self._chk(*entry(nr, ids, cap, n, score, ts))
         res = []
         for r in range(nr):
             out = [int(ids[r * cap + i]) for i in range(n[r])]
             res.append((out, score[r], [float(ts[r * cap + i]) for i in range(n[r])]) if with_scores else out)
         return res[0] if nr == 1 else res
+
+    def beam_search(self, seq: int, first_logits: torch.Tensor, num_beams: int, max_new: int, eos: Optional[int], length_penalty: float = 1.0, early_stopping=False,
+                    processors=None, rules: Optional[int] = None, with_scores: bool = False, num_return: int = 1):
+        """gvl_beam_search: HF beam search (num_beams = k, do_sample = False) from the PREFILLED sequence `seq` and its prefill logits, inside the library; `seq` is not
+        consumed.  processors: a logits.Processors (None = off); rules: a rule-set id (None = none); early_stopping: False / True / "never".  Returns the new ids, or with
+        with_scores (ids, sequences_score, transition_scores) as beam.beam_search does.  num_return > 1 (gvl_beam_search_n): a list of such results, the num_return best
+        hypotheses, best first."""
+        prm = self._beam_params(first_logits, num_beams, max_new, eos, length_penalty, early_stopping, processors, rules)
+
+        def entry(nr, ids, cap, n, score, ts):
+            if nr == 1:
+                return self.lib.gvl_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), ids, cap, n, score, ts, self.stream), "gvl_beam_search"
+            return self.lib.gvl_beam_search_n(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), nr, ids, cap, n, score, ts, self.stream), "gvl_beam_search_n"
+        return self._run_beam_entry(entry, num_beams, max_new, num_return, with_scores)
 
     def op_beam_group(self, rows: Optional[torch.Tensor], scores, eos: Optional[int] = None, pad: Optional[int] = None, logprobs: bool = True, stride0: bool = False,
                       done: bool = False, s: Optional[int] = None):
@@ -607,25 +618,10 @@ class Engine:
                           with_scores: bool = False, num_return: int = 1):
         """gvl_group_beam_search: HF diverse (group) beam search (num_beams = k, num_beam_groups = G, diversity_penalty) from the PREFILLED sequence `seq`, inside the
         library; everything else as beam_search.  pad: the token of a finished group's beams (None: an id no later group counts)."""
-        if early_stopping not in (False, True, "never"):
-            raise ValueError("early_stopping must be False, True or 'never'")
-        assert first_logits.dtype == torch.float32 and first_logits.is_contiguous() and first_logits.device == self.device
-        pe, ng, mn, pe_eos = processors.args() if processors is not None else (1.0, 0, 0, None)
-        base = L.GvlBeamParams(int(num_beams), int(max_new), -1 if eos is None else int(eos), float(length_penalty), {False: 0, True: 1, "never": 2}[early_stopping],
-                               float(pe), int(ng), int(mn), -1 if pe_eos is None else int(pe_eos), -1 if rules is None else int(rules))
+        base = self._beam_params(first_logits, num_beams, max_new, eos, length_penalty, early_stopping, processors, rules)
         prm = L.GvlGroupBeamParams(base, int(num_beam_groups), float(diversity_penalty), -1 if pad is None else int(pad))
-        cap, nr = max(int(max_new), 1), int(num_return)
-        if nr < 1 or nr > int(num_beams):
-            raise ValueError("num_return must be 1 .. num_beams")
-        ids = (C.c_int32 * (cap * nr))()
-        ts = (C.c_float * (cap * nr))()
-        n, score = (C.c_int * nr)(), (C.c_double * nr)()
-        self._chk(self.lib.gvl_group_beam_search(self.ctx, int(seq), _ptr(first_logits), C.byref(prm), nr, ids, cap, n, score, ts, self.stream), "gvl_group_beam_search")
-        res = []
-        for r in range(nr):
-            out = [int(ids[r * cap + i]) for i in range(n[r])]
-            res.append((out, score[r], [float(ts[r * cap + i]) for i in range(n[r])]) if with_scores else out)
-        return res[0] if nr == 1 else res
+        return self._run_beam_entry(lambda nr, ids, cap, n, score, ts: (self.lib.gvl_group_beam_search(
+            self.ctx, int(seq), _ptr(first_logits), C.byref(prm), nr, ids, cap, n, score, ts, self.stream), "gvl_group_beam_search"), num_beams, max_new, num_return, with_scores)
 
     # ---- contrastive search (gvl_contrastive.hip) --------------------------------------------------
     def seq_keep_hidden(self, seq: int, on: bool = True):

@@ -11,6 +11,7 @@ merged at load (#16), greedy decoding only on this tier (the reference CLI defau
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 
 import os
@@ -650,6 +651,21 @@ class LLAVA_NEXT_VIDEO:
             return texts
         return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps, beam_scores)
 
+    @contextlib.contextmanager
+    def _search_seq(self, row: List[int], vis: torch.Tensor, grammar: Optional[int], keep_hidden: bool = False):
+        """(seq, first logits): the prompt prefilled once into a sequence of its own for a search inside the library -- every option off but the grammar, which the
+        search reads from it -- and freed on the way out."""
+        eng = self.engine
+        emb = eng.splice(row, vis)
+        seq = eng.seq_alloc(min(emb.shape[0], self.geo.max_seq))
+        try:
+            LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
+            if keep_hidden:
+                eng.seq_keep_hidden(seq)
+            yield seq, eng.prefill(seq, emb, want_logits=True)
+        finally:
+            eng.seq_free(seq)
+
     def contrastive_generate_ids(self, row: List[int], vis: torch.Tensor, top_k: int, penalty_alpha: float, max_new: int, processors: Optional["LP.Processors"] = None,
                                  rules: Optional[int] = None, grammar: Optional[int] = None, with_scores: bool = False):
         """generate(penalty_alpha = a, top_k = k): HF contrastive search (tests/contrastive_ref.py restates transformers 4.40.1's) inside the library
@@ -660,19 +676,12 @@ class LLAVA_NEXT_VIDEO:
         with_scores: (ids, p per id, degeneration penalty per id)."""
         eng = self.engine
         eos = getattr(self.tokenizer, "eos_token_id", None)
-        emb = eng.splice(row, vis)
-        seq = eng.seq_alloc(min(emb.shape[0], self.geo.max_seq))
-        try:
-            LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
-            eng.seq_keep_hidden(seq)
-            first = eng.prefill(seq, emb, want_logits=True)
-            procs = processors if processors is not None and processors.active else None
+        procs = processors if processors is not None and processors.active else None
+        with self._search_seq(row, vis, grammar, keep_hidden=True) as (seq, first):
             if not with_scores:
                 return eng.contrastive_search(seq, first, top_k, penalty_alpha, max_new, eos, procs, rules)
             ids, tr = eng.contrastive_search(seq, first, top_k, penalty_alpha, max_new, eos, procs, rules, with_trace=True)
             return ids, [tr["p"][s][r] for s, r in enumerate(tr["sel"])], [tr["pen"][s][r] for s, r in enumerate(tr["sel"])]
-        finally:
-            eng.seq_free(seq)
 
     def beam_generate_ids(self, row: List[int], vis: torch.Tensor, num_beams: int, max_new: int, length_penalty: float = 1.0, early_stopping=False,
                           sample: Optional[dict] = None, processors: Optional["LP.Processors"] = None, with_scores: bool = False,
@@ -702,18 +711,12 @@ class LLAVA_NEXT_VIDEO:
             if sample is not None:
                 raise ValueError("beam-sample runs on the host path only (its draws are torch's): impl='device' needs sample=None")
             eos = getattr(self.tokenizer, "eos_token_id", None)
-            emb = eng.splice(row, vis)
-            seq = eng.seq_alloc(min(emb.shape[0], self.geo.max_seq))
-            try:
-                LP.apply_seq_options(eng, seq, dataclasses.replace(LP.SeqOptions.OFF, grammar=grammar))
-                first = eng.prefill(seq, emb, want_logits=True)
+            procs = processors if processors is not None and processors.active else None
+            with self._search_seq(row, vis, grammar) as (seq, first):
                 if grouped:
                     return eng.group_beam_search(seq, first, num_beams, num_beam_groups, diversity_penalty, max_new, eos, pad, length_penalty, early_stopping,
-                                                 processors if processors is not None and processors.active else None, rules, with_scores, num_return=num_return)
-                return eng.beam_search(seq, first, num_beams, max_new, eos, length_penalty, early_stopping,
-                                       processors if processors is not None and processors.active else None, rules, with_scores, num_return=num_return)
-            finally:
-                eng.seq_free(seq)
+                                                 procs, rules, with_scores, num_return=num_return)
+                return eng.beam_search(seq, first, num_beams, max_new, eos, length_penalty, early_stopping, procs, rules, with_scores, num_return=num_return)
         gi = eng.decode_group_info()                     # which group sizes ONE batched step takes: asked from the library, not restated here
         eos = getattr(self.tokenizer, "eos_token_id", None)
         emb = eng.splice(row, vis)
@@ -724,64 +727,39 @@ class LLAVA_NEXT_VIDEO:
         if (processors is not None and processors.active) or rules is not None or grammar is not None:
             pa = (processors if processors is not None else LP.OFF).args()
 
+            opt = {name: v for name, v in (("rules", rules), ("grammar", grammar)) if v is not None}     # only what is set: op_logits_process defaults the rest
+
             def process(histories: List[List[int]], logprobs: torch.Tensor, group: int = 0, prev_tokens=(), diversity_penalty: float = 0.0) -> torch.Tensor:
-                if group > 0:                                # a later group of diverse beam search: the Hamming term rides in the same launch, in HF's place
-                    return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules, grammar=grammar,
-                                                 hamming=(list(prev_tokens), float(diversity_penalty)))
-                if grammar is not None:
-                    return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules, grammar=grammar)
-                if rules is None:
-                    return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa)
-                return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, rules=rules)
+                # a later group of diverse beam search: the Hamming term rides in the same launch, in HF's place
+                ham = {"hamming": (list(prev_tokens), float(diversity_penalty))} if group > 0 else {}
+                return eng.op_logits_process(logprobs.float().contiguous(), histories, *pa, **opt, **ham)
         try:
             LP.apply_seq_options(eng, beams[0], LP.SeqOptions.OFF)    # the steps must hand back raw logits, the scores come from the host rows (beam.py); clones copy these settings
             first = eng.prefill(beams[0], emb, want_logits=True)
 
             def step(parents: List[Optional[int]], toks: List[int]) -> torch.Tensor:
-                if grouped:
-                    return group_step(parents, toks)
-                keep, new = {}, [None] * len(parents)
-                for j, p_ in enumerate(parents):             # clones first: every parent is still at the length the children continue from
-                    if p_ in keep:
-                        new[j] = eng.seq_clone(beams[p_], cap)
-                        fresh.append(new[j])                 # if a later clone raises (pool exhausted, kMaxSeqs), `finally` frees these
-                    else:
-                        keep[p_] = j
-                for p_, j in keep.items():
-                    new[j] = beams[p_]
-                losers = [s_ for p_, s_ in enumerate(beams) if p_ not in keep]
+                # beam.reorder's plan over the sequences; a finished group's beams (parent None) are freed and their rows stay zero -- nothing reads them
+                src, clones, closed = B.reorder(beams, parents)
+                new: List[Optional[int]] = [None] * len(parents)
+                for j in clones:                             # clones first: every parent is still at the length the children continue from
+                    new[j] = eng.seq_clone(beams[src[j]], cap)
+                    fresh.append(new[j])                     # if a later clone raises (pool exhausted, kMaxSeqs), `finally` frees these
+                for j, p_ in enumerate(src):
+                    if p_ is not None and new[j] is None:
+                        new[j] = beams[p_]
+                losers = [beams[q] for q in closed]
                 beams[:] = new                               # install before freeing: `finally` never sees an id twice or a freed id
-                del fresh[:]
-                for s_ in losers:
-                    eng.seq_free(s_)
-                if len(beams) <= gi["max_group"] and (gi["any_size"] or len(beams) in (1, 2, 4)):
-                    return eng.decode_step_logits_batch(beams, toks)        # the k beams share ONE stream of the weights
-                return torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(beams, toks)])
-
-            def group_step(parents: List[Optional[int]], toks: List[int]) -> torch.Tensor:
-                # the same reorder over the beams that live on: a finished group's beams (parent None) are freed and their rows stay zero -- nothing reads them
-                keep, new = {}, [None] * len(parents)
-                for j, p_ in enumerate(parents):
-                    if p_ is None:
-                        continue
-                    if p_ in keep:
-                        new[j] = eng.seq_clone(beams[p_], cap)
-                        fresh.append(new[j])
-                    else:
-                        keep[p_] = j
-                for p_, j in keep.items():
-                    new[j] = beams[p_]
-                losers = [s_ for p_, s_ in enumerate(beams) if p_ not in keep and s_ is not None]
-                beams[:] = new
                 del fresh[:]
                 for s_ in losers:
                     eng.seq_free(s_)
                 live = [j for j, s_ in enumerate(beams) if s_ is not None]
                 ls, lt = [beams[j] for j in live], [toks[j] for j in live]
                 if len(ls) <= gi["max_group"] and (gi["any_size"] or len(ls) in (1, 2, 4)):
-                    got = eng.decode_step_logits_batch(ls, lt)
+                    got = eng.decode_step_logits_batch(ls, lt)              # the live beams share ONE stream of the weights
                 else:
                     got = torch.stack([eng.decode_step_logits(s_, t) for s_, t in zip(ls, lt)])
+                if len(live) == len(beams):
+                    return got
                 out = torch.zeros((len(parents), got.shape[-1]), dtype=torch.float32, device=got.device)
                 out[torch.as_tensor(live, device=got.device)] = got
                 return out
