@@ -665,7 +665,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_iv2_pipe_kernel(const AttnArg
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                     // last tile
-      if (pass || !__syncthreads_or(0)) break;          // the block repeats the pass in safe mode: once more
+      if (pass || !(NW == 8 ? (__syncthreads_or(0) | __syncthreads_or(0)) : __syncthreads_or(0))) break;   // the block repeats the pass in safe mode: once more (NW = 8: one vote per 128-row half, below)
     }
     return;
   }
@@ -915,6 +915,27 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_iv2_pipe_kernel(const AttnArg
     run(IC<0>{});
     l_tot = row_sum();
 #ifndef GVL_PIPE_LAB                                     // (LAB builds compute garbage on purpose: no second pass)
+    if constexpr (NW == 8) {
+      // The 8-wave form votes per 128-row HALF of its block, i.e. per query block of the 4-wave form: which pass computes a row must not depend on the form that
+      // runs it (the two passes round differently once a later tile is more than 2^8 above the first), or attn_pipe_rows would not be bit-neutral.  The barriers are
+      // the block's, so a half that keeps its normal pass still walks through the other half's safe pass -- as a wave without queries does: DMA shares and barriers only.
+      const bool bad = !(l_tot > 0.f && l_tot < 1.2676506e30f);
+      const int lo = __syncthreads_or(bad && wave < 4), hi = __syncthreads_or(bad && wave >= 4);
+      redo = (wave < 4 ? lo : hi) != 0;
+      if (!redo && (lo | hi)) {
+        stage_first();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                     // tile 0
+        for (int t = 0; t + 1 < n_tiles; ++t) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
+          stage_k(t & 1, t + 2 < n_tiles ? t + 2 : n_tiles - 1);
+          stage_v(1 - (t & 1), t + 1 <= last_full ? t + 1 : last_full);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                     // last tile
+      }
+    } else
     redo = __syncthreads_or(!(l_tot > 0.f && l_tot < 1.2676506e30f)) != 0;     // 2^100; also catches NaN.  Block-uniform: every wave repeats the pass (the barriers are shared)
 #endif
   }

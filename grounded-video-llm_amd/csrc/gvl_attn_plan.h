@@ -117,7 +117,7 @@ inline int attn_plan(const AttnGeometry& g, const AttnKnobs& k, AttnLaunch out[G
     // whole 256-row query blocks go to the 8-wave form (half the DMA pieces per MFMA), the remaining rows (S = 2049: one) to the 4-wave form in a second launch.
     // MEASURED SLOWER and therefore not the default: 106.5-106.8 against 95.3-95.9 ms per 39 launches, same box (profiles/r04_attention_pipe_lab.txt) -- eight
     // waves in lock-step behind one barrier and one block per CU lose more than the halved DMA issue gives back (round 2 saw the same with 6-wave blocks).
-    // A row's arithmetic does not depend on which form computes it (asserted).
+    // A row's arithmetic does not depend on which form computes it (asserted): the 8-wave form votes its safe re-pass per 128-row half of a block.
     const int lds = 2 * 2 * 64 * 96 * 2 + 64 * 96 * 2;                   // the ring + the partial-last-tile V slot: 60 KB
     const int rows8 = g.pipe_rows == 256 ? (g.S / 256) * 256 : 0;
     int n = 0;

@@ -1465,6 +1465,47 @@ int gvl_op_prefill_attention(gvl_ctx* ctx, const gvl_prefill_attn* p, void* stre
   HIPCHK(ctx, hipStreamSynchronize(st));
   return 0;
 }
+// operator-level entry for the attention launch of an InternVideo2 block (tests/test_gpu_iv2_attn.py): the ONES instantiations of attn_fwd_kernel, the q-normalised-on-load
+// operand mode and attn_iv2_pipe_kernel, on caller-owned buffers.  ONE gvl_launch_attention (two kernel launches where the plan splits the rows), no arena allocation,
+// no qkv_post; the form, pipe and pipe_rows come from the descriptor, never from gvl_debug_set.  The plan is asked first: GVL_ERR_ARG before anything is launched or written.
+int gvl_op_iv2_attention(gvl_ctx* ctx, const gvl_iv2_attn* p, void* stream) {
+  if (!ctx) return GVL_ERR_ARG;
+  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_iv2_attention: null descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const char* bad = nullptr;
+  const int f = p->form;
+  if (f < 0 || f > 2) bad = "form 0, 1 or 2";
+  else if (!p->Kt || !p->out) bad = "Kt and out set";
+  else if (f == 0 && (!p->Q || !p->Vt || p->qkv || p->q_rs || p->q_nw)) bad = "form 0 takes Q, Kt, Vt and no qkv, q_rs, q_nw";
+  else if (f == 1 && (!p->Q || !p->qkv || p->Vt || p->q_rs || p->q_nw)) bad = "form 1 takes Q, Kt, qkv and no Vt, q_rs, q_nw";
+  else if (f == 2 && (!p->qkv || !p->q_rs || !p->q_nw || p->Q || p->Vt)) bad = "form 2 takes qkv, Kt, q_rs, q_nw and no Q, Vt";
+  else if (p->B < 1 || p->S < 1 || p->H < 1) bad = "B, S, H >= 1";
+  else if ((p->Dr & 7) || p->Dr <= 64 || p->Dr >= 96) bad = "Dr 72, 80 or 88 (a padded head on the D = 96 kernels: the ones row needs D > Dr)";
+  else if (f == 2 && p->Dr != 88) bad = "form 2 needs Dr == 88";
+  else if (f == 2 && (p->pipe < 0 || p->pipe > 2)) bad = "pipe 0, 1 or 2";
+  else if (f == 2 && p->pipe_rows != 0 && p->pipe_rows != 256) bad = "pipe_rows 0 or 256";
+  else if (f && ((p->ld & 7) || (long long)p->ld < 3ll * p->H * p->Dr)) bad = "ld % 8 == 0, ld >= 3 H Dr";
+  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_iv2_attention: ") + bad);
+  AttnArgs a; memset(&a, 0, sizeof(a));
+  a.Q = p->Q; a.Kt = p->Kt; a.Vt = p->Vt; a.O = p->out; a.B = p->B; a.H = p->H; a.KV = p->H; a.S = p->S; a.D = pad_head(p->Dr); a.Dout = p->Dr;
+  a.scale = p->scale; a.causal = 0; a.ones_row = 1;
+  if (f) { a.Vrows = p->qkv + (size_t)2 * p->H * p->Dr; a.v_ld = p->ld; }
+  if (f == 2) { a.Qrows = p->qkv; a.q_ld = p->ld; a.q_rs = p->q_rs; a.q_nw = p->q_nw; a.k_ones = 1; a.pipe = p->pipe; a.pipe_rows = p->pipe_rows; }
+  {
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    AttnGeometry g{};
+    g.B = a.B; g.H = a.H; g.KV = a.KV; g.S = a.S; g.D = a.D; g.Dout = a.Dout; g.ones_row = 1; g.k_ones = a.k_ones; g.pipe = a.pipe; g.pipe_rows = a.pipe_rows;
+    g.v_ld = a.v_ld; g.q_ld = a.q_ld; g.Vrows = a.Vrows; g.Qrows = a.Qrows; g.q_rs = a.q_rs; g.q_nw = a.q_nw;
+    g.O16 = al16(a.O); g.Vrows16 = al16(a.Vrows); g.Qrows16 = al16(a.Qrows); g.Krows16 = true; g.q_nw16 = al16(a.q_nw);
+    AttnLaunch l[GVL_ATTN_MAX_LAUNCHES];
+    const int n = attn_plan(g, GVL_ATTN_KNOBS_DEFAULT, l);
+    if (n < 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_iv2_attention: attn_plan does not serve this launch (at most 256 key tiles, out / qkv / q_nw 16-byte aligned, a 64-row tile of qkv below 4 GiB)");
+    if (!l[0].ONES) return fail(ctx, GVL_ERR_ARG, "gvl_op_iv2_attention: the plan chose no ONES kernel for this launch");
+  }
+  RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return 0;
+}
 // micro-benchmark of the decode projection kernels on synthetic operands (tools/decode_bench.py): mode 0 = skinny MFMA GEMM (variant:
 // see gvl_launch_dgemm), 1 = round-1 VALU GEMV (batch 1, 2, 4), 2 / 3 = the same two with the fused RMSNorm prologue (batch <= 4).  `rounds` distinct weight matrices are cycled so that the
 // Infinity Cache cannot hold the stream; returns the average microseconds per launch.

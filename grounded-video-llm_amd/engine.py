@@ -1162,6 +1162,11 @@ class Engine:
         op_qkv_post takes them (O is written in place).  Raises GvlError (status ERR_ARG) on a refusal."""
         self._op_paged(L.GvlPrefillAttn, self.lib.gvl_op_prefill_attention, "gvl_op_prefill_attention", kw)
 
+    def op_iv2_attention(self, **kw):
+        """gvl_op_iv2_attention (include/gvl.h): the attention launch of one InternVideo2 block on caller-owned buffers.  Every field of gvl_iv2_attn by keyword, as
+        op_qkv_post takes them (out is written in place; a pointer field may be a view into a larger allocation).  Raises GvlError (status ERR_ARG) on a refusal."""
+        self._op_paged(L.GvlIv2Attn, self.lib.gvl_op_iv2_attention, "gvl_op_iv2_attention", kw)
+
     def op_gemv(self, W, x, bias=None):
         N, K = W.shape
         y = torch.empty((N,), dtype=torch.float32, device=self.device)

@@ -111,6 +111,13 @@ class GvlPrefillAttn(C.Structure):
                 ("vl_pos0", C.c_int32 * 8), ("table_len", C.c_int32 * 8), ("ext", C.c_int32), ("n_pages", C.c_int32)]
 
 
+class GvlIv2Attn(C.Structure):
+    """gvl_iv2_attn (include/gvl.h): the attention launch of one InternVideo2 block (ONES forms, q normalised on load, attn_iv2_pipe_kernel) on caller-owned buffers."""
+    _fields_ = [("qkv", C.c_void_p), ("ld", C.c_int32), ("Q", C.c_void_p), ("Kt", C.c_void_p), ("Vt", C.c_void_p), ("q_rs", C.c_void_p), ("q_nw", C.c_void_p),
+                ("out", C.c_void_p), ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("Dr", C.c_int32), ("scale", C.c_float), ("form", C.c_int32),
+                ("pipe", C.c_int32), ("pipe_rows", C.c_int32)]
+
+
 class GvlPatchEmbed(C.Structure):
     """gvl_patch_embed (include/gvl.h): the patch embedding of either vision tower by either path, for the operator tests."""
     _fields_ = [("mode", C.c_int32), ("path", C.c_int32), ("n", C.c_int32), ("T", C.c_int32), ("image", C.c_int32), ("patch", C.c_int32), ("C", C.c_int32),
@@ -218,6 +225,7 @@ _SIGS = {
     "gvl_op_decode_attention": (C.c_int, [C.c_void_p, C.POINTER(GvlDecodeAttn), C.c_void_p]),
     "gvl_op_qkv_post": (C.c_int, [C.c_void_p, C.POINTER(GvlQkvPost), C.c_void_p]),
     "gvl_op_prefill_attention": (C.c_int, [C.c_void_p, C.POINTER(GvlPrefillAttn), C.c_void_p]),
+    "gvl_op_iv2_attention": (C.c_int, [C.c_void_p, C.POINTER(GvlIv2Attn), C.c_void_p]),
     "gvl_op_decode_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "gvl_probe_mfma": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "gvl_trace_marker": (C.c_int, [C.c_int, C.c_void_p]),

@@ -586,7 +586,8 @@ int gvl_prof_read(gvl_ctx* ctx, int category, double* total_ms, int64_t* launche
  *                      or transform; with InternVideo2's q RMSNorm applied in the kernel prologue -- straight from the fused-qkv matrix;
  *                      2: V only; 0: the round-2 path through Q / K pages and a V^T transpose pass
  *   "attn_pipe_rows"   128 (default): that kernel's 4-wave form (128 query rows per block) for every row; 256: whole 256-row query blocks on its 8-wave form (half
- *                      the DMA pieces per MFMA; measured 12 % slower), the remaining rows on the 4-wave form -- bit-identical
+ *                      the DMA pieces per MFMA; measured 12 % slower), the remaining rows on the 4-wave form -- bit-identical (the 8-wave form decides the safe
+ *                      re-pass per 128-row half of its block, as the 4-wave form does per block)
  *   "varlen_attn"      1 (default): the causal attention of a ragged prefill group (gvl_prefill_varlen) runs as ONE grid over the query blocks of all its sequences,
  *                      and so do its RoPE / KV-append and V^T-page passes (one launch each per layer); 2: the attention only (round 5), the passes per sequence;
  *                      0: one launch per sequence for all of them (rounds 2-4) -- bit-identical
@@ -913,6 +914,37 @@ typedef struct {
   int32_t ext, n_pages;
 } gvl_prefill_attn;
 int gvl_op_prefill_attention(gvl_ctx* ctx, const gvl_prefill_attn* p, void* stream);
+/* The attention launch of one InternVideo2 block on caller-owned buffers: the ones-row (ONES) forms of attn_fwd_kernel, the q-normalised-on-load operand mode and
+ * attn_iv2_pipe_kernel (operator tests: tests/test_gpu_iv2_attn.py).  Non-causal self attention of B sequences of S tokens, H heads of Dr padded to D = 96 (Dr 72, 80 or
+ * 88), the softmax row sum taken from a ones row / column of V.  ONE attention launch (two kernels where the plan splits the rows); no workspace, no qkv_post pass: the
+ * pages are EXACTLY what gvl_op_qkv_post mode 1 writes on implicit pages (block_table NULL) with ones_row / k_ones / q_rs.  All pointers are device memory.
+ *   qkv      bf16 token rows [B S] of [H Dr | H Dr | H Dr] (q, k, v), ld elements apart (>= 3 H Dr, a multiple of 8; wider is legal), 16-byte aligned.  Forms 1 and 2
+ *   Q        bf16 [B][H][S][D], pad columns zero.  Forms 0 and 1
+ *   Kt       bf16 [B ceil(S / 64)][H][64][D]: key j of sequence b is slot j % 64 of page b ceil(S / 64) + j / 64; column Dr holds 1.0 (k_ones; form 2 needs it, forms 0
+ *            and 1 multiply it by Q's zero pad), the other pad columns 0.  Slots of keys >= S may hold anything
+ *   Vt       bf16 [B ceil(S / 64)][H][D][64], row Dr = 1.0 in every slot (ones_row), the other pad rows and the slots of keys >= S finite.  Form 0 only
+ *   q_rs     f32 [B S] the row scale of q's RMSNorm, q_nw bf16 [H Dr] its weight (16-byte aligned): the kernel forms q'[d] = bf16(q_nw[h Dr + d] * bf16(q[d] * q_rs[token])
+ *            * scale * log2(e)) as it loads q.  Form 2 only
+ *   out      bf16 [B S][H Dr], 16-byte aligned
+ *   form     0: Q, K and V^T pages;  1: Q and K pages, V read in place from qkv;  2: q read in place from qkv and normalised on load, K pages, V in place (Dr == 88 only)
+ *   pipe     form 2 only: 0 attn_fwd_kernel, 1 attn_iv2_pipe_kernel, 2 its safe pass only;  pipe_rows  form 2, pipe != 0: 256 = whole 256-row query blocks on the 8-wave
+ *            form and the rest on the 4-wave form, 0 = the 4-wave form for every row.  Neither may change an output bit, except that pipe 1 keeps the first key tile's
+ *            row maximum as the softmax reference where pipe 0 / 2 move it once a later tile exceeds it by more than 2^8: there the results agree to rounding only
+ *   V range  the output is finite for |v| <= 2^27 / S: the pipelined kernel keeps a row whose sum of probabilities (relative to the first tile's maximum) is below
+ *            2^100 and its fp32 accumulators are bounded by that sum times max |v|
+ * Returns GVL_ERR_ARG with a message that names this entry, before anything is launched or written, for whatever attn_plan refuses (more than 256 key tiles, a
+ * misaligned out / qkv / q_nw, ld % 8 != 0 or ld < 3 H Dr), a NULL pointer the form needs, a non-NULL pointer the form does not take, Dr other than 72 / 80 / 88 (form 2: 88),
+ * form, pipe or pipe_rows outside their values.  Synchronises the stream. */
+typedef struct {
+  const uint16_t* qkv; int32_t ld;
+  const uint16_t* Q; const uint16_t* Kt; const uint16_t* Vt;
+  const float* q_rs; const uint16_t* q_nw;
+  uint16_t* out;
+  int32_t B, S, H, Dr;
+  float scale;
+  int32_t form, pipe, pipe_rows;
+} gvl_iv2_attn;
+int gvl_op_iv2_attention(gvl_ctx* ctx, const gvl_iv2_attn* p, void* stream);
 /* measurement only (tools/decode_bench.py): average microseconds per launch of one decode projection [N,K] x `batch` sequences on
  * synthetic operands; mode 0 = skinny MFMA GEMM (variant 0 = default), 1 = VALU GEMV; `rounds` distinct weight copies are cycled. */
 int gvl_op_decode_bench(gvl_ctx* ctx, int N, int K, int batch, int mode, int variant, int rounds, int iters, double* us_per_launch,

@@ -4,6 +4,7 @@ design: only the plan can say which kernel a case exercised.
 
 The helpers that build a geometry the way a caller in the library does:
   op_attention   gvl_op_attention (gvl_model.hip): gvl_debug_set vision_in_place / attn_ring choose the operand mode and the ring depth
+  op_iv2_attention   gvl_op_iv2_attention (gvl_model.hip): the descriptor's form / pipe / pipe_rows choose everything, no gvl_debug_set
   iv2_block      the attention launch of an InternVideo2 block (iv2_encode, gvl_vision.hip): vision_in_place, attn_pipe, attn_pipe_rows
   decode_step    the decode-attention launch of decode_step (gvl_llm.hip): decode_attn_shape on the sequences' positions, then decode_attn_plan"""
 import functools
@@ -115,6 +116,20 @@ def op_attention(B, S, H, KV, Dr, causal, vision_in_place=1, attn_ring=0):
     p = plans([prefill_line(**kw)])[0]
     assert p is not None, f"gvl_op_attention {kw}: refused"
     return tuple(p)
+
+
+@functools.lru_cache(maxsize=None)
+def op_iv2_attention(B, S, H, Dr, form, pipe=0, pipe_rows=0, ld=0):
+    """the launches of gvl_op_iv2_attention: form 0 = Q, K, V^T pages; 1 = Q, K pages + V in place; 2 = q normalised on load + K pages (k_ones) + V in place, where pipe /
+    pipe_rows are read.  ones_row = 1 and KV = H in every form; ld = the pitch of qkv (0: 3 H Dr).  None: the plan refuses"""
+    kw = dict(B=B, H=H, KV=H, S=S, D=pad_head(Dr), Dout=Dr, ones_row=1)
+    ld = ld or 3 * H * Dr
+    if form >= 1:
+        kw.update(present=VROWS, v_ld=ld)
+    if form == 2:
+        kw.update(present=VROWS | QROWS | Q_RS | Q_NW, q_ld=ld, k_ones=1, pipe=pipe, pipe_rows=pipe_rows)
+    p = plans([prefill_line(**kw)])[0]
+    return None if p is None else tuple(p)
 
 
 @functools.lru_cache(maxsize=None)

@@ -147,3 +147,18 @@ def test_shape_offers_every_sequence_its_splits(planned, golden):
         need = max(min(nsplit, max(1, -(-(p + 1) // 256))) for p in pos)
         assert s.cpb == (fc if 1 <= fc <= 16 else 1) and s.gsplit == -(-need // s.cpb), (c, s)
         assert s.hpb == (0 if G == 1 else fh if fh >= 1 and G % fh == 0 else s.hpb) and (G == 1 or G % s.hpb == 0), (c, s)
+
+
+def test_op_iv2_attention_reaches_every_ones_form_and_both_pipelined_forms():
+    """gvl_op_iv2_attention's launches (tests/test_gpu_iv2_attn.py asserts them per case): the descriptor alone chooses the kernel"""
+    k = lambda *a, **kw: [A.kernel_of(l) for l in A.op_iv2_attention(*a, **kw)]
+    for Dr in (72, 80, 88):
+        assert k(2, 129, 3, Dr, 0) == [("fwd", 96, 4, 2, 1, 0, 0)] and k(2, 129, 3, Dr, 1) == [("fwd", 96, 4, 2, 1, 1, 0)]
+    assert k(3, 257, 5, 88, 2, 0) == k(3, 257, 5, 88, 2, 0, 256) == [("fwd", 96, 4, 2, 1, 3, 0)]
+    for pipe in (1, 2):
+        assert k(3, 257, 5, 88, 2, pipe) == [("iv2_pipe", 4)] and k(3, 257, 5, 88, 2, pipe, 256) == [("iv2_pipe", 8), ("iv2_pipe", 4)]
+        assert k(1, 512, 3, 88, 2, pipe, 256) == [("iv2_pipe", 8)] and k(1, 255, 3, 88, 2, pipe, 256) == [("iv2_pipe", 4)]
+    l8, l4 = A.op_iv2_attention(3, 321, 5, 88, 2, 1, 256, ld=3 * 5 * 88 + 16)
+    assert (l8.q_begin, l8.q_rows, l4.q_begin, l4.q_rows) == (0, 256, 256, 65) and l8.block == 512 and l4.block == 256 and l8.grid == 16 * 1 and l4.grid == 16 * 1
+    assert A.op_iv2_attention(1, 16385, 3, 88, 2, 1) is None and A.op_iv2_attention(1, 129, 3, 88, 2, 1, ld=3 * 3 * 88 + 4) is None and A.op_iv2_attention(1, 129, 3, 80, 2, 1) is None
+    assert {kk for f in (0, 1, 2) for kk in k(1, 129, 3, 88, f)} | {("iv2_pipe", 4), ("iv2_pipe", 8)} == {x for x in A.lists() if (x[0] == "fwd" and x[4] == 1) or x[0] == "iv2_pipe"}

@@ -16,7 +16,7 @@ Forms: vision_in_place 1 / 0 / 2 (non-causal, head dim <= 96: Q, K, V in place a
 pages) and attn_ring 0 / 2 / 3 on the paged forms.  gvl.h: none of them may change an output bit, so the bounded cases must also be bit-identical across forms.
 The output buffer carries 160 guard rows (more than a 128-row query block's overhang) that must keep their fill; qkv is the prefix of an allocation whose next 64 rows are
 NaN: the in-place forms must re-read the last real key row for the tail tile's pad keys -- a DMA past the end shows up as NaN (0 . NaN) without any out-of-bounds access.
-The folded softmax / ones-row sum of InternVideo2 (VROW = 3, ONES, attn_iv2_pipe_kernel) is not reachable through gvl_op_attention: test_gpu_towers.py."""
+The folded softmax / ones-row sum of InternVideo2 (VROW = 3, ONES, attn_iv2_pipe_kernel) is not reachable through gvl_op_attention: gvl_op_iv2_attention, test_gpu_iv2_attn.py."""
 import ctypes as C
 
 import pytest
