@@ -25,6 +25,11 @@ int gvl_kv_info(const gvl_ctx* ctx, int* total_pages, int* free_pages, int64_t* 
   return 0;
 }
 
+int gvl_debug_seq_pages(const gvl_ctx* ctx, int seq_id, int32_t* pages_host, int cap, int* n_pages) {
+  static_assert(sizeof(int32_t) == sizeof(int), "pages_host is handed to the sequence table as int*");
+  return ctx && ctx->pages_of(seq_id, (int*)pages_host, cap, n_pages) == SEQ_OK ? 0 : GVL_ERR_ARG;   // SeqTable::pages_of (CPU-tested: tests/test_seq_table_cpu.py)
+}
+
 int gvl_decode_group_info(const gvl_ctx* ctx, int* max_group, int* any_size) {
   if (!ctx) return GVL_ERR_ARG;
   if (max_group) *max_group = decode_group_size(ctx->decode_mfma, GVL_MAX_DECODE_BATCH);

@@ -51,6 +51,15 @@ struct SeqTable {
   S* lookup(int id) { return id >= 0 && id < (int)seqs.size() && seqs[id].used ? &seqs[id] : nullptr; }
   // ids[i] names a sequence that an earlier member of the group named already
   static bool repeats(const int* ids, int i) { for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) return true; return false; }
+  // tests (gvl_debug_seq_pages): the pages of live sequence `id` in position order -> SEQ_OK with *n (may be null) = how many it holds and the first min(cap, that
+  // many) of them in out (may be null when cap is 0); SEQ_BAD with nothing written: not a live sequence, cap < 0, cap > 0 without out
+  int pages_of(int id, int* out, int cap, int* n) const {
+    if (id < 0 || id >= (int)seqs.size() || !seqs[id].used || cap < 0 || (cap > 0 && !out)) return SEQ_BAD;
+    const std::vector<int>& p = seqs[id].pages;
+    if (n) *n = (int)p.size();
+    for (int i = 0; i < cap && i < (int)p.size(); ++i) out[i] = p[i];
+    return SEQ_OK;
+  }
   bool any_live() const { for (const S& q : seqs) if (q.used) return true; return false; }
   // A new sequence of up to max_tokens tokens -> its id, or a negative SeqStatus with nothing changed.  src < 0 (pos 0): empty, default settings.  src >= 0: it starts with the source's
   // first `pos` tokens and settings; the pos / 64 whole pages of that prefix are shared (immutable from now on for both holders: appends go to later pages), later pages are its own.

@@ -200,6 +200,14 @@ class Engine:
         self._chk(self.lib.gvl_kv_info(self.ctx, C.byref(t), C.byref(f), C.byref(b), C.byref(m)), "gvl_kv_info")
         return {"total_pages": t.value, "free_pages": f.value, "pool_bytes": b.value, "max_live_seqs": m.value, "tokens": t.value * 64}
 
+    def seq_pages(self, seq: int) -> List[int]:
+        """gvl_debug_seq_pages (tests): the KV pages of a live sequence in position order.  Host-only: no device call."""
+        n = C.c_int(0)
+        self._chk(self.lib.gvl_debug_seq_pages(self.ctx, int(seq), None, 0, C.byref(n)), "gvl_debug_seq_pages")
+        buf = (C.c_int32 * max(n.value, 1))()
+        self._chk(self.lib.gvl_debug_seq_pages(self.ctx, int(seq), buf, n.value, C.byref(n)), "gvl_debug_seq_pages")
+        return [int(buf[i]) for i in range(n.value)]
+
     def decode_group_info(self) -> Dict[str, int]:
         """gvl_decode_group_info: the group sizes one batched decode step takes ({max_group: 16, any_size: 1} on the skinny-MFMA path;
         {4, 0} = sizes 1 / 2 / 4 on the VALU fallback)."""

@@ -194,6 +194,10 @@ int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void*
 int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const uint32_t* streams /* [n_new] host */, float* first_logits /* device, fp32 [vocab] */,
                    int* dst_seqs /* [n_new] */, void* stream);
 int gvl_kv_info(const gvl_ctx* ctx, int* total_pages, int* free_pages, int64_t* pool_bytes, int* max_live_seqs);
+/* Tests: the KV pages of a live sequence in position order (page i holds tokens 64 i .. 64 i + 63; the element offset of page p inside a layer's K or V^T slice is
+ * p * kv_heads * 64 * head_dim).  Host-only: reads the sequence table, touches no device memory and enqueues nothing.  *n_pages (may be NULL) = how many pages the
+ * sequence holds; the first min(cap, *n_pages) of them are written to pages_host (may be NULL when cap is 0).  GVL_ERR_ARG: no ctx, unknown sequence, cap < 0. */
+int gvl_debug_seq_pages(const gvl_ctx* ctx, int seq_id, int32_t* pages_host, int cap, int* n_pages);
 /* The group sizes ONE batched decode step takes (gvl_decode_step_logits_batch, and the parts gvl_decode_greedy_batch / gvl_decode_steps
  * step together), valid after gvl_finalize_weights: *max_group = 16 on the skinny-MFMA decode path, 4 on the VALU fallback
  * (geometries whose projection widths are not multiples of 256); *any_size = 1 when every size 1 .. max_group is taken, 0 when only

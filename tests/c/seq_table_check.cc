@@ -3,6 +3,8 @@
 // One operation per line; every line is answered by one JSON object: the result code "rc" (an id, 0, or a negative SeqStatus) and the whole table.
 //   alloc MAX | fork SRC N MAX | clone SRC MAX | free SEQ | pos SEQ N (the sequence now holds N tokens: what a prefill / decode leaves)
 //   newrules | delrules ID | rules SEQ ID | topn SEQ N | proc SEQ PENALTY NGRAM MIN_NEW EOS      (SEQ -1: the default of later allocs)
+//   pages SEQ CAP I | pagesnull SEQ CAP I: pages_of into 64 words filled with -77 (CAP -2: a null buffer with cap 0; pagesnull: a null count) -> a negative status, else
+//     word I of the buffer afterwards (I -1: the count, -99 when it was not asked for)
 //   live SEQ (0 / SEQ_BAD) | group SEQ... (the first member that is not live or repeats an earlier one decides: SEQ_BAD / SEQ_DUPLICATE)
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +44,14 @@ int main(int argc, char** argv) {
     else if (op == "rules") { in >> a >> b; SeqSelect* s = sel_of(a); rc = s ? t.set_rules(*s, b) : (int)SEQ_BAD; }
     else if (op == "topn") { in >> a >> b; SeqSelect* s = sel_of(a); rc = s ? (s->top_n = b, 0) : (int)SEQ_BAD; }
     else if (op == "proc") { double p; in >> a >> p >> b >> c; int e; in >> e; SeqSelect* s = sel_of(a); rc = s ? (s->proc = LogitsProc{(float)p, b, c, e}, 0) : (int)SEQ_BAD; }
+    else if (op == "pages" || op == "pagesnull") {
+      in >> a >> b >> c;
+      int buf[64], n = -99;
+      for (int& w : buf) w = -77;
+      if (b > 64 || c < -1 || c >= 64) return 6;
+      const int st = t.pages_of(a, b == -2 ? nullptr : buf, b == -2 ? 0 : b, op == "pages" ? &n : nullptr);
+      rc = st < 0 ? st : (c == -1 ? n : buf[c]);
+    }
     else if (op == "live") { in >> a; rc = t.lookup(a) ? SEQ_OK : SEQ_BAD; }
     else if (op == "group") {
       std::vector<int> ids; while (in >> a) ids.push_back(a);

@@ -22,7 +22,11 @@ exact_case(N, K, batch, form, seed, w_fmt, wide)   operands on which every numbe
     sq_out        16 squares of at most 124 units each (one unit per 16-row block): exact in fp32 in any order
     sq_in         partial sums that the kernel's order adds without rounding while other associations round (see exact_sq_in); the total is K * 4^m per
                   sequence, so rsqrt gives 2, 1 or 1/2 and the scaled accumulators stay exact
-    rope          tables (cos, sin) = (1, 0), (0, 1), or (1, 0) short / (0, -1) long: rotation sign, partner and placement, no arithmetic
+    rope          tables (cos, sin) = (1, 0), (0, 1), or (1, 0) short / (0, -1) long: rotation sign, partner and placement, no arithmetic.
+                  first_page / n_pages: the page tables name first_page + (the same pages) in caller-owned pools of n_pages pages; expect_Kt / expect_Vt hold the 24
+                  pages first_page .. first_page + 23 only (c.page0, c.win).  rope_relocated_cases(): cases of the GPU test's rope sweep on pages whose element
+                  offsets lie above 2^31 (one above 2^30); rope_emulate / rope_mismatch: the epilogue in float32 over SPARSE pools (page id -> array), and the
+                  comparison the GPU test makes, for test_decode_proj_ref_cpu.py
   SwiGLU is not exact (the sigmoid): it belongs to the bounded family.
 
 bounded_*(...)   dense data (row scales 2^-6 .. 2^6, K^-0.5 weights), a float64 reference with the bf16 roundings where the kernels place them and a PER-ELEMENT
@@ -38,8 +42,10 @@ import numpy as np
 import torch
 
 import gemm_ref as G
+from kv_page_ref import PAGE_MUTATIONS, POOL_ELEMS, first_page_above, wrap_page_offset
 
 bf = torch.bfloat16
+MUTATIONS = PAGE_MUTATIONS          # wrong kernels of rope_emulate: a page's base address formed in 32 bits (kv_page_ref.wrap_page_offset)
 U32 = G.U32
 ACT_NONE, ACT_SILU_MUL = 0, 3
 RSQRT_ULP = 1.0                     # HIP math API: rsqrtf, maximum error 1 ulp
@@ -250,7 +256,7 @@ def sq_in_sum(sq_row, nw, order="kernel"):
     return tot
 
 
-def exact_case(N, K, batch, form, seed=0, w_fmt=0, wide=False, rope_geo=None, nw=8):
+def exact_case(N, K, batch, form, seed=0, w_fmt=0, wide=False, rope_geo=None, nw=8, first_page=0, n_pages=None):
     """see the module docstring.  rope forms: rope_geo = (H, KV, Dr, D), N = (H + 2 KV) Dr.  -> Case: W, x (bf16), the epilogue operands, kwargs for
     Engine.op_decode_proj without the output buffers, and the expected outputs (expect / expect_sq / expect_Q / expect_Kt / expect_Vt)"""
     f = EXACT_FORMS[form]
@@ -279,7 +285,7 @@ def exact_case(N, K, batch, form, seed=0, w_fmt=0, wide=False, rope_geo=None, nw
     c.kw = dict(w_fmt=w_fmt)
     n_t, b_t = torch.arange(N, dtype=torch.int64), torch.arange(batch, dtype=torch.int64) + seed * batch
     if "rope" in f:
-        _rope_expect(c, acc, rope_geo, f["rope"], seed)
+        _rope_expect(c, acc, rope_geo, f["rope"], seed, first_page, n_pages)
         return c
     v = acc
     if f.get("consumer"):
@@ -308,8 +314,8 @@ def rope_tables(max_pos, half, cs):
     return torch.full((max_pos, half), float(cs[0])), torch.full((max_pos, half), float(cs[1]))
 
 
-def rope_layout(batch, seed, table_stride=4, n_pages=24):
-    """positions ROPE_POS mixed across the batch and a page table per sequence: a non-identity permutation of distinct pages"""
+def rope_layout(batch, seed, table_stride=4, n_pages=24, first_page=0):
+    """positions ROPE_POS mixed across the batch and a page table per sequence: a non-identity permutation of distinct pages first_page .. first_page + n_pages - 1"""
     pos = torch.tensor([ROPE_POS[(b + seed) % len(ROPE_POS)] for b in range(batch)], dtype=torch.int32)
     assert batch <= n_pages                                 # every sequence writes a page of its own
     g = torch.Generator().manual_seed(1234 + seed)
@@ -321,7 +327,7 @@ def rope_layout(batch, seed, table_stride=4, n_pages=24):
         while int(tables[b, pg]) in used:
             tables[b, pg] = (int(tables[b, pg]) + 1) % n_pages
         used.add(int(tables[b, pg]))
-    return pos, tables, n_pages
+    return pos, tables + first_page, n_pages
 
 
 def rope_place(q, k, v, pos, tables, n_pages, geo, dtype=bf, fill=SENTINEL):
@@ -340,12 +346,14 @@ def rope_place(q, k, v, pos, tables, n_pages, geo, dtype=bf, fill=SENTINEL):
     return Q.reshape(B, H * D), Kt, Vt
 
 
-def _rope_expect(c, acc, geo, cs, seed):
+def _rope_expect(c, acc, geo, cs, seed, first_page=0, n_pages=None):
     H, KV, Dr, D = geo
     half = Dr // 2
     B = c.batch
     c.geo = geo
-    c.pos, c.tables, c.n_pages = rope_layout(B, seed)
+    c.pos, c.tables, c.win = rope_layout(B, seed, first_page=first_page)
+    c.page0, c.page_elems, c.n_pages = first_page, KV * 64 * D, n_pages or first_page + c.win
+    assert first_page + c.win <= c.n_pages
     c.max_pos = max(ROPE_POS) + 2
     (c.cos_s, c.sin_s), (c.cos_l, c.sin_l) = rope_tables(c.max_pos, half, cs[0]), rope_tables(c.max_pos, half, cs[1])
     y = torch.from_numpy(acc).reshape(B, H + 2 * KV, Dr)
@@ -356,11 +364,67 @@ def _rope_expect(c, acc, geo, cs, seed):
         x1, x2 = qk[b, :, :half], qk[b, :, half:]
         out[b, :, :half] = x1 * co - x2 * si
         out[b, :, half:] = x2 * co + x1 * si
-    c.expect_Q, c.expect_Kt, c.expect_Vt = rope_place(out[:, :H], out[:, H:], y[:, H + KV:], c.pos, c.tables, c.n_pages, geo)
+    c.expect_Q, c.expect_Kt, c.expect_Vt = rope_place(out[:, :H], out[:, H:], y[:, H + KV:], c.pos, c.tables - c.page0, c.win, geo)
     want = torch.cat([out, y[:, H + KV:]], 1)
     assert bool((want.to(bf).double() == want).all()), "rope: expected values not representable in bf16"
     assert not bool((want == SENTINEL).any()), "rope: an expected value equals the sentinel and could not be told from an unwritten element"
     c.kw.update(rope_on=1, rope_switch=ROPE_SWITCH, max_pos=c.max_pos, n_pages=c.n_pages, table_stride=c.tables.shape[1], q_stride=H * D, H=H, KV=KV, Dr=Dr, D=D)
+
+
+# (geo, form, w_fmt, K, batch, path, k): cases of test_gpu_decode_proj.py's rope sweep, pages from the first one at or above 2^k elements of POOL_ELEMS pools
+def rope_relocated_cases():
+    """the VALU kernel at batch 1, 2 and 4, the skinny GEMM at batch 16 and at 5 with the three weight formats; k = 30: byte offsets between 2^31 and 2^32"""
+    g = ((8, 8, 96, 128), (8, 2, 128, 128), (4, 4, 64, 64))
+    return [(g[0], "rope_switch", 0, 256, 16, 0, 31), (g[1], "rope01", 1, 512, 5, 0, 31), (g[2], "rope10", 2, 1024, 5, 0, 31), (g[1], "rope_switch", 0, 256, 5, 0, 31),
+            (g[0], "rope01", 0, 256, 1, 1, 31), (g[2], "rope_switch", 0, 256, 2, 1, 31), (g[1], "rope10", 0, 256, 4, 1, 31), (g[1], "rope_switch", 0, 256, 16, 0, 30)]
+
+
+def rope_relocated_case(geo, form, w_fmt, K, batch, path, k, seed=0):
+    H, KV, Dr, D = geo
+    pe = KV * 64 * D
+    return exact_case((H + 2 * KV) * Dr, K, batch, form, seed=seed, w_fmt=w_fmt, rope_geo=geo, first_page=first_page_above(1 << k, pe), n_pages=POOL_ELEMS // pe)
+
+
+def rope_emulate(c, mut=None):
+    """the rope epilogue of an exact case in float32, writing THROUGH the page tables into sparse pools -> dict(Q = bf16 [B, H D], Kt / Vt = {page id: bf16 page over the
+    sentinel}).  mut (MUTATIONS): the page's offset wraps, the write lands at ("stray", element offset) instead"""
+    H, KV, Dr, D = c.geo
+    half, B = Dr // 2, c.batch
+    y = (c.x.float() @ c.W.float().T).view(B, H + 2 * KV, Dr)          # exact in fp32 (test_exact_cases_are_exact)
+    Q = torch.full((B, H, D), SENTINEL, dtype=bf)
+    Kt, Vt = {}, {}
+    for b in range(B):
+        p = int(c.pos[b])
+        co, si = (c.cos_l[p], c.sin_l[p]) if p + 1 > ROPE_SWITCH else (c.cos_s[p], c.sin_s[p])
+        x1, x2 = y[b, :H + KV, :half], y[b, :H + KV, half:]
+        qk = torch.cat([x1 * co - x2 * si, x2 * co + x1 * si], -1).to(bf)
+        page, slot = int(c.tables[b, p >> 6]), p & 63
+        off = page * c.page_elems
+        key = page if wrap_page_offset(off, mut) == off else ("stray", wrap_page_offset(off, mut))
+        Q[b, :, :Dr] = qk[:H]
+        Kt.setdefault(key, torch.full((KV, 64, D), SENTINEL, dtype=bf))[:, slot, :Dr] = qk[H:]
+        Vt.setdefault(key, torch.full((KV, D, 64), SENTINEL, dtype=bf))[:, :Dr, slot] = y[b, H + KV:].to(bf)
+    return dict(Q=Q.reshape(B, H * D), Kt=Kt, Vt=Vt)
+
+
+def rope_mismatch(c, got):
+    """None when Q and the pages c.page0 .. c.page0 + c.win - 1 of sparse pools equal the expectation bit for bit and nothing else was written, else the message"""
+    msgs = []
+    if not torch.equal(got["Q"].view(torch.int16), c.expect_Q.view(torch.int16)):
+        msgs.append("Q differs")
+    for name, exp in (("Kt", c.expect_Kt), ("Vt", c.expect_Vt)):
+        for w in range(c.win):
+            page = got[name].get(c.page0 + w)
+            page = torch.full_like(exp[w], SENTINEL) if page is None else page
+            bad = (page.view(torch.int16) != exp[w].view(torch.int16)).nonzero()
+            if bad.numel():
+                i = tuple(bad[0].tolist())
+                msgs.append(f"{name}: page {c.page0 + w}: {bad.shape[0]} elements wrong; first at {list(i)}: got {float(page[i])}, expected {float(exp[w][i])} (sentinel {SENTINEL} = not written)")
+                break
+        other = [k for k in got[name] if not (isinstance(k, int) and c.page0 <= k < c.page0 + c.win)]
+        if other:
+            msgs.append(f"{name}: {len(other)} pages written outside pages {c.page0} .. {c.page0 + c.win - 1}: {other[:2]}")
+    return "; ".join(msgs) if msgs else None
 
 
 def recompute_fp32(c, order):

@@ -32,6 +32,22 @@ def tiny_geo(**kw):
     return E.TowerGeometry(**base)
 
 
+def big_pool_pair(elems):
+    """two flat device buffers of `elems` 16-bit elements (the K and V^T pools of the tests that place pages above 2^31 elements); the caller drops them at teardown"""
+    return [torch.empty(elems, dtype=torch.int16, device=DEV) for _ in range(2)]
+
+
+def count_other(pool, value, lo=0, hi=0, chunk=1 << 29):
+    """how many 16-bit patterns of the flat int16 pool OUTSIDE elements [lo, hi) differ from `value`: counted where the pool lives, over the WHOLE pool, `chunk` elements
+    at a time (tests/test_gpu_util_cpu.py: every single changed element is counted, exactly [lo, hi) is skipped)"""
+    assert 0 <= lo <= hi <= pool.numel() and chunk > 0
+    n = torch.zeros((), dtype=torch.int64, device=pool.device)
+    for a, b in ((0, lo), (hi, pool.numel())):
+        for x in range(a, b, chunk):
+            n += torch.count_nonzero(pool[x:min(b, x + chunk)] != value)
+    return int(n)
+
+
 def llm_engine(geo, W, towers=("llm",)):
     eng = E.Engine(geo, DEV, towers=towers)
     packed = Wt.pack_llm(W, geo.kind, geo.layers, geo.heads, geo.kv_heads, geo.max_seq, geo.rope_theta, geo.rope_short, geo.rope_long,

@@ -14,6 +14,9 @@ them and the kernel masks by index), V^T slots >= Sk hold +-1e30 (finite: P = 0 
 emulate(case, mut=None)   the kernel's documented arithmetic reading the pages THROUGH the tables (attn_ref.emulate's, plus the per-wave causal tile skip, the per-block
                           tile count and the need_mask predicate, which a correct kernel cannot tell from masking everything -- the mutations can); mut: MUTATIONS.
 exact_cases() / bounded_cases() / group_cases()   THE lists test_gpu_prefill_attn.py runs; make(spec) -> Case.
+relocated_cases()         cases of those lists on pages whose element offsets inside the pools lie above 2^31 (one above 2^30): make(spec, first_page=, pools=) names the
+                          pages first_page + (the same permutation) in caller-owned, all-NaN pools and writes the named pages only; on the CPU the pools are sparse
+                          (SparsePools: page id -> array).  Data, targets, expectation and bound do not depend on first_page.
 """
 import copy
 
@@ -23,6 +26,7 @@ import torch
 import attn_ref as A
 from attn_ref import SENT, LAZY, LOG2E, KINDS, _bits, _code, onehot_v
 from gemm_ref import _mix
+from kv_page_ref import PAGE_MUTATIONS, POOL_ELEMS, first_page_above, wrap_page_offset
 
 bf = torch.bfloat16
 VPAD = 1e30
@@ -30,7 +34,7 @@ GUARD_ROWS = 160
 CAUSAL_MAPS = ("diag", "zero", "tile_first", "prefix_last", "first_new", "hash")
 FULL_MAPS = ("last", "perm", "edges")
 MUTATIONS = ("mask_plus", "mask_minus", "skip_no_qpos0", "mask_no_qpos0", "n_tiles_from_S", "no_tail_mask", "wrong_member_table", "prefix_offset_dropped", "member_off_by_one",
-             "gqa_mod", "no_rescale_O", "skip_last8")
+             "gqa_mod", "no_rescale_O", "skip_last8") + PAGE_MUTATIONS           # the last three: a page's base address formed in 32 bits (kv_page_ref.wrap_page_offset)
 BENIGN = ("need_mask_pred_no_qpos0",)   # qpos0 dropped from the need_mask PREDICATE alone makes it true on a superset of the tiles: masks are applied where none is needed, no bit changes
 SHAPES = ((64, 1), (64, 31), (64, 33), (64, 64), (64, 65), (128, 129), (192, 130), (0, 130), (960, 65))      # (qpos0, S), Sk = qpos0 + S
 DGEOS = ((64, 64), (64, 32), (96, 80), (128, 128))                                                            # (D, Dout)
@@ -51,8 +55,22 @@ class Case:
         return f"{self.what} {self.form} {body} H{self.H}/{self.KV} D{self.D} Dout{self.Dr} causal{self.causal} ring{self.ring}"
 
 
-def layout(spec):
-    """-> Case with members, tables (permuted, one spare entry that is no page, behind each), n_pages (4 pages nobody names); no data yet"""
+class SparsePools:
+    """a pool as page id -> [KV, ., .] array, for the CPU: a page nobody wrote reads as NaN, which is what the GPU test fills its pools with"""
+
+    def __init__(self, n_pages, shape, device):
+        self.shape, self.page_shape, self.device, self.pages = (n_pages,) + tuple(shape), tuple(shape), device, {}
+
+    def __getitem__(self, pg):
+        assert 0 <= pg < self.shape[0]
+        if pg not in self.pages:
+            self.pages[pg] = torch.full(self.page_shape, float("nan"), dtype=bf, device=self.device)
+        return self.pages[pg]
+
+
+def layout(spec, first_page=0, n_pages=None):
+    """-> Case with members, tables (permuted, one spare entry that is no page, behind each), n_pages (4 pages nobody names); no data yet.  first_page / n_pages: the
+    case's pages are first_page + (the same permutation) in pools of n_pages pages; c.page0 = first_page, c.win = the pages laid out (the named ones and the 4 spares)"""
     c = Case()
     c.spec = dict(spec)
     c.form, c.H, c.KV, c.D, c.Dr, c.causal, c.ring, c.seed = spec["form"], spec["H"], spec["KV"], spec["D"], spec["Dout"], int(spec["causal"]), spec.get("ring", 0), spec["seed"]
@@ -70,8 +88,10 @@ def layout(spec):
         c.B, c.S, c.qpos0, c.Sk = 1, max(lens), 0, 0
     tiles = [(Sk + 63) // 64 for _, _, Sk, _ in trip]
     own = [t - (q0 // 64 if sh is not None else 0) for t, (_, q0, _, sh) in zip(tiles, trip)]
-    c.n_pages = sum(own) + 4
-    perm = list(rng.permutation(c.n_pages)[:sum(own)])
+    c.page0, c.win, c.page_elems = first_page, sum(own) + 4, c.KV * 64 * c.D
+    c.n_pages = n_pages or first_page + c.win
+    assert first_page + c.win <= c.n_pages
+    perm = [first_page + int(x) for x in rng.permutation(c.win)[:sum(own)]]
     c.members, row0 = [], 0
     for u, (S, q0, Sk, sh) in enumerate(trip):
         head = c.members[sh].table[:q0 // 64] if sh is not None else []
@@ -84,22 +104,29 @@ def layout(spec):
     return c
 
 
-def place(c, device="cpu"):
-    """members' q / k / v (bf16 [S, H, Dr], [Sk, KV, Dr] x 2) -> Q [rows H D + a NaN tail], Kt, Vt pools as the docstring describes"""
+def place(c, device="cpu", pools=None):
+    """members' q / k / v (bf16 [S, H, Dr], [Sk, KV, Dr] x 2) -> Q [rows H D + a NaN tail], Kt, Vt pools as the docstring describes.  pools = (Kt, Vt): the caller's
+    [n_pages, KV, 64, D] / [n_pages, KV, D, 64] tensors, all NaN already -- only the named pages are written; pools = "sparse": SparsePools (CPU)"""
     H, KV, D, Dr = c.H, c.KV, c.D, c.Dr
     c.Q = torch.full((c.rows * H * D + 64 * D,), float("nan"), dtype=bf, device=device)
-    c.Kt = torch.full((c.n_pages, KV, 64, D), float("nan"), dtype=bf, device=device)
-    c.Vt = torch.full((c.n_pages, KV, D, 64), float("nan"), dtype=bf, device=device)
+    if pools is None:
+        c.Kt = torch.full((c.n_pages, KV, 64, D), float("nan"), dtype=bf, device=device)
+        c.Vt = torch.full((c.n_pages, KV, D, 64), float("nan"), dtype=bf, device=device)
+    elif pools == "sparse":
+        c.Kt, c.Vt = SparsePools(c.n_pages, (KV, 64, D), device), SparsePools(c.n_pages, (KV, D, 64), device)
+    else:
+        c.Kt, c.Vt = pools
+        assert tuple(c.Kt.shape) == (c.n_pages, KV, 64, D) and tuple(c.Vt.shape) == (c.n_pages, KV, D, 64)
     pad = torch.where(torch.arange(64, device=device) % 2 == 0, VPAD, -VPAD).to(bf)
     for m, q, k, v in zip(c.members, c.q, c.k, c.v):
         Qm = c.Q[m.row0 * H * D:(m.row0 + m.S) * H * D].view(H, m.S, D)
         Qm[:, :, :Dr], Qm[:, :, Dr:] = q.permute(1, 0, 2), 0
         for t in range((m.Sk + 63) // 64):
             n = min(64, m.Sk - t * 64)
-            pg = m.table[t]
-            c.Kt[pg, :, :n, :Dr], c.Kt[pg, :, :n, Dr:] = k[t * 64:t * 64 + n].permute(1, 0, 2), 0
-            c.Vt[pg, :, :Dr, :n], c.Vt[pg, :, Dr:, :] = v[t * 64:t * 64 + n].permute(1, 2, 0), 0
-            c.Vt[pg, :, :Dr, n:] = pad[n:]
+            kp, vp = c.Kt[m.table[t]], c.Vt[m.table[t]]
+            kp[:, :n, :Dr], kp[:, :n, Dr:] = k[t * 64:t * 64 + n].permute(1, 0, 2), 0
+            vp[:, :Dr, :n], vp[:, Dr:, :] = v[t * 64:t * 64 + n].permute(1, 2, 0), 0
+            vp[:, :Dr, n:] = pad[n:]
     c.tables = [torch.tensor(m.table, dtype=torch.int32, device=device) for m in c.members]
     if c.block_table is not None:
         c.block_table = c.block_table.to(device)
@@ -130,8 +157,8 @@ def targets(m, H, target, seed, u, device="cpu"):
     raise ValueError(target)
 
 
-def onehot_case(spec, device="cpu"):
-    c = layout(spec)
+def onehot_case(spec, device="cpu", first_page=0, pools=None, n_pages=None):
+    c = layout(spec, first_page, n_pages if pools is None or pools == "sparse" else pools[0].shape[0])
     c.what, c.scale, c.target_map = f"one-hot {spec['target']}", 1.0, spec["target"]
     assert spec["target"] in (CAUSAL_MAPS if c.causal else FULL_MAPS)
     H, KV, Dr = c.H, c.KV, c.Dr
@@ -157,7 +184,7 @@ def onehot_case(spec, device="cpu"):
         exp.append(torch.gather(vh, 1, t[..., None].expand(H, m.S, Dr)).permute(1, 0, 2).reshape(m.S, H * Dr))
         c.q.append(q), c.k.append(k), c.v.append(v), c.target.append(t)
     c.expect = torch.cat(exp).contiguous()
-    return place(c, device)
+    return place(c, device, pools)
 
 
 def where_of(c, row):
@@ -191,16 +218,16 @@ def onehot_mismatch(got, c, what=""):
 
 
 # ---- bounded family ----------------------------------------------------------------------------------------------------------------------------------------------------
-def bounded_case(spec, device="cpu"):
+def bounded_case(spec, device="cpu", first_page=0, pools=None, n_pages=None):
     """per member attn_ref.bounded_case over the whole context; -> Case with .full (the attn_ref cases) for elementwise_bound"""
-    c = layout(spec)
+    c = layout(spec, first_page, n_pages if pools is None or pools == "sparse" else pools[0].shape[0])
     c.what, c.scale = spec["kind"], c.Dr ** -0.5
     c.q, c.k, c.v, c.full = [], [], [], []
     for u, m in enumerate(c.members):
         f = A.bounded_case(1, m.Sk, c.H, c.KV, c.Dr, c.causal, spec["kind"], c.seed * 16 + u, device)
         q, k, v = (t[0] for t in f.split())
         c.q.append(q[m.qpos0:m.qpos0 + m.S].contiguous()), c.k.append(k.contiguous()), c.v.append(v.contiguous()), c.full.append(f)
-    return place(c, device)
+    return place(c, device, pools)
 
 
 def elementwise_bound(c):
@@ -257,9 +284,10 @@ def _run(c, q, table, qpos0, Sk, mut):
     for t in range(int(n_tiles.max())):
         tt = t - qpos0 // 64 if (mut == "prefix_offset_dropped" and t >= qpos0 // 64) else t
         pg = table[tt] if tt < len(table) else -1
-        if 0 <= pg < c.n_pages:
-            kt, vt = c.Kt[pg, :, :, :Dr].float()[hk], c.Vt[pg, :, :Dr, :].float().transpose(-1, -2)[hk]     # [H, 64, Dr] each
-        else:                                                                        # no page at all (only under a mutation): the GPU would read foreign memory
+        wrapped = mut in PAGE_MUTATIONS and wrap_page_offset(pg * c.page_elems, mut) != pg * c.page_elems
+        if 0 <= pg < c.n_pages and not wrapped:
+            kt, vt = c.Kt[pg][:, :, :Dr].float()[hk], c.Vt[pg][:, :Dr, :].float().transpose(-1, -2)[hk]     # [H, 64, Dr] each
+        else:     # no page at all (only under a mutation): the GPU would read foreign memory.  A wrapped offset points in front of the case's pages, where the pools hold NaN
             kt = vt = torch.full((H, 64, Dr), float("nan"), device=dev)
         keys = torch.arange(t * 64, t * 64 + 64, device=dev)
         active = t < n_tiles
@@ -373,5 +401,35 @@ def bounded_cases():
     return out
 
 
-def make(spec, device="cpu"):
-    return onehot_case(spec, device) if "target" in spec else bounded_case(spec, device)
+def make(spec, device="cpu", **kw):
+    return onehot_case(spec, device, **kw) if "target" in spec else bounded_case(spec, device, **kw)
+
+
+# ---- the relocated cases: the same launches on pages whose offsets inside the pools need more than 32 bits ---------------------------------------------------------------
+def relocated_cases():
+    """-> [(spec, k)]: specs TAKEN FROM the lists above, to be laid out from the first page at or above 2^k elements of POOL_ELEMS pools (make_relocated).  k = 31: the
+    caller's block table causal (ring 0 and 3) and full, a VL = 1 group of 8, VL = 2 groups of 8 and with a shared prefix, a dense bounded case; D 64 / 96 / 128 (page
+    sizes that are and are not powers of two).  The hash / perm targets reach every page of every member.  k = 30: one more, byte offsets between 2^31 and 2^32."""
+    ex, gr, bd = exact_cases(), group_cases("exact"), bounded_cases()
+
+    def pick(lst, test=lambda s: True, **kw):
+        return next(s for s in lst if all(s.get(k) == v for k, v in kw.items()) and test(s))
+
+    return [(pick(ex, D=64, target="hash", qpos0=192, ring=0), 31),
+            (pick(ex, D=128, target="hash", qpos0=960, test=lambda s: s["ring"] != 0), 31),
+            (pick(ex, D=96, causal=0, target="perm"), 31),
+            (pick(gr, form="ragged", D=128, lens=GROUPS[2], target="hash"), 31),
+            (pick(gr, form="ext", D=64, Dout=32, lens=GROUPS[2], vl_pos0=EXT_POS0[0], target="hash"), 31),
+            (pick(gr, share=(1, 0), target="hash"), 31),
+            (pick(bd, D=96, kind="late_heavy", test=lambda s: s["qpos0"] >= 128), 31),
+            (pick(gr, form="ext", D=128, lens=GROUPS[2], vl_pos0=EXT_POS0[0], target="diag"), 30)]
+
+
+def make_relocated(spec, k, device="cpu", pools="sparse"):
+    """make(spec) with its pages from the first one at or above 2^k elements of pools of POOL_ELEMS elements: pools = (Kt, Vt) flat bf16 tensors of that size, all NaN
+    (they are viewed as [n_pages][KV][64][D]), or "sparse" (CPU)"""
+    pe = spec["KV"] * 64 * spec["D"]
+    n = POOL_ELEMS // pe
+    if pools != "sparse":
+        pools = (pools[0][:n * pe].view(n, spec["KV"], 64, spec["D"]), pools[1][:n * pe].view(n, spec["KV"], spec["D"], 64))
+    return make(spec, device, first_page=first_page_above(1 << k, pe), pools=pools, n_pages=n)

@@ -13,6 +13,9 @@ expect(case)            -> Expect   the images of emulate for modes 0 / 2 (bit f
                                     element (pads, V^T, sentinels) bit for bit.
 mismatch(case, images, expect)      None, or the message the tests fail with: the count, the first (buffer, page / row, head, slot, d), the member and the source row.
 cases()                 THE list test_gpu_qkv_post.py runs; build(spec) -> Case.
+relocated_cases()       cases of that list to be run on pages whose element offsets inside the pools lie above 2^31 (one above 2^30): build(spec, first_page, n_pages) names
+                        the pages first_page + (the same permutation) in caller-owned pools; the Images hold those pages only (image index = page - first_page), and
+                        what a wrong kernel writes anywhere else is kept sparsely (Images.stray).  Expectations do not depend on first_page.
 
 Inputs are hashed bf16 bit patterns (data_bits): modes 0 / 2 normal values 2^-30 ... 2^30 of both signs plus signed zeros, no subnormal, inf or NaN, hashed per (row, column) so
 that a misplaced 16-byte chunk cannot equal the right one; mode 1 2^-4 ... 2^4.  cos / sin are hashed per (pos, j) over +-[1/4, 2) -- not a rotation: a wrong position
@@ -20,6 +23,8 @@ or a wrong j is a wrong number.  The qkv matrix is the prefix of an allocation w
 The sentinel of every output is a NaN pattern no bf16 arithmetic on this data produces (0x7FA5), so an unwritten element can never pass for a written one.
 """
 import numpy as np
+
+from kv_page_ref import PAGE_MUTATIONS, POOL_ELEMS, first_page_above, wrap_page_offset
 
 U32 = 2.0 ** -24                    # unit roundoff of fp32
 RSQRT_REL = 2.0 ** -23              # HIP math API: rsqrtf, maximum error 1 ulp -- at most 2^-23 relative
@@ -31,6 +36,7 @@ GUARD = 4096                        # sentinel elements behind Q: 32 guard rows 
 TAIL_ROWS = 64
 MUTATIONS = ("rope_sign", "partner_same_half", "cos_stride_Dr", "pos_plus_1", "slot_ignores_pos0", "one_rounding", "neighbour_table", "member_off_by_one", "q_row0_dropped",
              "pad_not_zeroed", "k_ones_missing", "k_ones_col_plus_1", "ones_row_missing", "v_tail_not_zeroed", "v_ext_tile_at_64t", "q_rs_writes_Q", "rms_per_head")
+MUTATIONS += PAGE_MUTATIONS         # a page's base address formed in 32 bits (kv_page_ref.wrap_page_offset): the identity on cases(), wrong on relocated_cases()
 GEOS = ((4, 4, 64, 64), (6, 2, 80, 96), (2, 2, 128, 128), (8, 1, 32, 64), (3, 3, 16, 64))          # every mode
 GEO_IV2, GEO_WIDE = (4, 4, 88, 96), (13, 13, 128, 128)                                             # modes 0 / 1: in_regs (44 chunks) with and without q_rs;  mode 1: 208 chunks, streaming
 LENS = (1, 3, 4, 5, 63, 64, 65, 130)
@@ -106,8 +112,10 @@ class Case:
                 else f"members {s['lens']} pos0 {s.get('vl_pos0')}") + f" vt {int(self.vt)} k_ones {self.k_ones} ones_row {self.ones_row} q_rs {int(self.q_rs)} ld {self.ld}")
 
 
-def build(spec):
-    """spec: dict(form, geo, mode, seed, and -- single: B, S, pos0, table (bool) -- ragged / ext: lens, vl_pos0) + vt, k_ones, ones_row, q_rs, ld_pad"""
+def build(spec, first_page=0, n_pages=None):
+    """spec: dict(form, geo, mode, seed, and -- single: B, S, pos0, table (bool) -- ragged / ext: lens, vl_pos0) + vt, k_ones, ones_row, q_rs, ld_pad.
+    first_page, n_pages: the case's pages are first_page + (the same permutation) in caller-owned pools of n_pages pages (default: pools that end behind the case's
+    pages, as before).  c.page0 = first_page, c.win = the pages the case lays out; Images hold the pages page0 .. page0 + win - 1, image index = page - page0."""
     c = Case()
     c.spec = dict(spec)
     c.H, c.KV, c.Dr, c.D = spec["geo"]
@@ -124,19 +132,21 @@ def build(spec):
         nt, need = (S + 63) // 64, (pos0 + S + 63) // 64
         if spec["table"]:
             c.max_pages = need + 2                                   # max_pages > the tiles a sequence has
-            c.n_pages = B * need + 3                                 # pages no table names
-            perm = rng.permutation(c.n_pages)
+            c.win = B * need + 3                                     # pages no table names
+            c.n_pages = n_pages or first_page + c.win
+            perm = rng.permutation(c.win)
             c.block_table = np.full((B, c.max_pages), c.n_pages + 7, dtype=np.int32)     # entries behind a sequence's tiles are never read
-            c.block_table[:, :need] = perm[:B * need].reshape(B, need)
+            c.block_table[:, :need] = first_page + perm[:B * need].reshape(B, need)
             c.block_table[:, :pos0 // 64] = -3                       # ... nor the prefix pages this launch does not write
             if spec.get("identity"):
-                c.n_pages = B * nt + 3
+                c.win = B * nt + 3
+                c.n_pages = n_pages or first_page + c.win
                 c.block_table = np.full((B, c.max_pages), c.n_pages + 7, dtype=np.int32)
-                c.block_table[:, :nt] = np.arange(B * nt).reshape(B, nt)
+                c.block_table[:, :nt] = first_page + np.arange(B * nt).reshape(B, nt)
             tabs = [c.block_table[b] for b in range(B)]
         else:
-            assert pos0 == 0
-            c.n_pages = B * nt + 3
+            assert pos0 == 0 and first_page == 0 and n_pages is None, "implicit pages start at page 0"
+            c.win = c.n_pages = B * nt + 3
             tabs = [np.arange(b * nt, (b + 1) * nt) for b in range(B)]
         c.members = [Member(b * S, S, pos0, tabs[b], b) for b in range(B)]
     else:
@@ -145,8 +155,9 @@ def build(spec):
         c.B, c.S, c.pos0, c.rows = 1, max(lens), 0, sum(lens)
         need = [(p + s + 63) // 64 for p, s in zip(p0, lens)]
         new = [n - p // 64 for n, p in zip(need, p0)]
-        c.n_pages = sum(new) + 5
-        perm = list(rng.permutation(c.n_pages)[:sum(new)])
+        c.win = sum(new) + 5
+        c.n_pages = n_pages or first_page + c.win
+        perm = [first_page + int(x) for x in rng.permutation(c.win)[:sum(new)]]
         r0 = 0
         for u, s in enumerate(lens):
             tab = np.full(need[u] + 1 + u % 2, c.n_pages + 7, dtype=np.int32)
@@ -161,6 +172,8 @@ def build(spec):
     c.qn = data_bits(1, c.H * c.Dr, c.seed + 101, True)[0] if c.mode == 1 else None
     c.kn = data_bits(1, c.KV * c.Dr, c.seed + 202, True)[0] if c.mode == 1 else None
     c.q_elems = c.rows * c.H * c.D
+    c.page0, c.page_elems = first_page, c.KV * 64 * c.D
+    assert c.page0 + c.win <= c.n_pages
     return c
 
 
@@ -181,9 +194,10 @@ def single_launch_of(c, u):
 class Images:
     def __init__(self, c):
         self.Q = np.full(c.q_elems + GUARD, SENT, dtype=np.uint16)
-        self.Kt = np.full((c.n_pages, c.KV, 64, c.D), SENT, dtype=np.uint16)
-        self.Vt = np.full((c.n_pages, c.KV, c.D, 64), SENT, dtype=np.uint16)
+        self.Kt = np.full((c.win, c.KV, 64, c.D), SENT, dtype=np.uint16)     # pages c.page0 .. c.page0 + c.win - 1 of the pool
+        self.Vt = np.full((c.win, c.KV, c.D, 64), SENT, dtype=np.uint16)
         self.q_rs = np.full(c.rows + 64, SENT_F32, dtype=np.uint32)          # float32 bit patterns
+        self.stray = {}                                                      # (buffer, element offset in the pool) -> what was written OUTSIDE those pages: a sparse pool
 
 
 # ---- the pass in plain numpy -------------------------------------------------------------------------------------------------------------------------------------------
@@ -244,6 +258,7 @@ def emulate(c, mut=None):
     im = Images(c)
     ragged = c.form != "single"
     n = len(c.members)
+    p0 = c.page0
     for u, m in enumerate(c.members):
         S, r0 = m.rows, m.row0
         x = c.qkv[r0:r0 + S, :c.width]
@@ -276,8 +291,8 @@ def emulate(c, mut=None):
         if mut in ("neighbour_table", "slot_ignores_pos0"):                  # a wrong table entry may be no page at all: that write is dropped here (the GPU would fault)
             tile = np.minimum(tile, len(table) - 1)
             page = np.asarray(table)[tile]
-            rows_ok = rows_ok & (page >= 0) & (page < c.n_pages)
-        page, slot = np.asarray(table)[tile], kpos & 63
+            rows_ok = rows_ok & (page >= p0) & (page < p0 + c.win)
+        page, slot = np.asarray(table)[tile] - p0, kpos & 63
         page, slot, kk = page[rows_ok], slot[rows_ok], ko.reshape(S, KV, Dr)[rows_ok]
         g = np.arange(KV)[None, :]
         im.Kt[page[:, None], g, slot[:, None], :Dr] = kk
@@ -292,14 +307,14 @@ def emulate(c, mut=None):
         if mut == "member_off_by_one" and ragged and u > 0:                  # ... and its key lands behind the previous member's last key
             pm = c.members[u - 1]
             pp = pm.pos0 + pm.rows
-            if pp >> 6 < len(pm.table) and 0 <= pm.table[pp >> 6] < c.n_pages:
-                im.Kt[pm.table[pp >> 6], :, pp & 63, :Dr] = ko.reshape(S, KV, Dr)[0]
+            if pp >> 6 < len(pm.table) and p0 <= pm.table[pp >> 6] < p0 + c.win:
+                im.Kt[pm.table[pp >> 6] - p0, :, pp & 63, :Dr] = ko.reshape(S, KV, Dr)[0]
         # V^T: whole pages
         if c.vt:
             for t in range((S + 63) // 64):
                 tt = t if (mut == "v_ext_tile_at_64t" and c.form == "ext") else (m.pos0 >> 6) + t
-                pg = m.table[tt]
-                if not 0 <= pg < c.n_pages:                                  # only under the mutation: no page at all, the write is dropped here
+                pg = m.table[tt] - p0
+                if not 0 <= pg < c.win:                                      # only under the mutation: no page at all, the write is dropped here
                     continue
                 blk = np.zeros((KV, D, 64), dtype=np.uint16)
                 cnt = min(64, S - t * 64)
@@ -309,6 +324,14 @@ def emulate(c, mut=None):
                 if c.ones_row and mut != "ones_row_missing":
                     blk[:, Dr, :] = ONE
                 im.Vt[pg] = blk
+    if mut in PAGE_MUTATIONS:                                                # every written page lands where the wrapped offset points: outside the case's pages
+        for name in ("Kt", "Vt"):
+            img = getattr(im, name)
+            for w in np.nonzero((img != SENT).reshape(c.win, -1).any(1))[0]:
+                off = (p0 + int(w)) * c.page_elems
+                if wrap_page_offset(off, mut) != off:
+                    im.stray[(name, wrap_page_offset(off, mut))] = img[w].copy()
+                    img[w] = SENT
     return im
 
 
@@ -368,7 +391,7 @@ def expect(c):
         ref, bound, _, _ = norm_expect(x[:, H * Dr:(H + KV) * Dr], c.kn, c.eps)
         pos = m.pos0 + np.arange(S)
         page, slot = np.asarray(m.table)[pos >> 6], pos & 63
-        idx = ((page[:, None, None] * KV + np.arange(KV)[None, :, None]) * 64 + slot[:, None, None]) * D + np.arange(Dr)[None, None, :]
+        idx = (((page - c.page0)[:, None, None] * KV + np.arange(KV)[None, :, None]) * 64 + slot[:, None, None]) * D + np.arange(Dr)[None, None, :]
         ki.append(idx.reshape(-1)), kr.append(ref.reshape(-1)), kb.append(bound.reshape(-1))
     cat = lambda a: np.concatenate(a) if a else np.zeros(0)
     e.bounded = {"Q": (cat(qi).astype(np.int64), cat(qr), cat(qb)), "Kt": (cat(ki).astype(np.int64), cat(kr), cat(kb)), "q_rs": (cat(ri).astype(np.int64), cat(rr), cat(rb))}
@@ -391,7 +414,7 @@ def locate(c, name, flat):
             if lo <= row_block < lo + m.rows * H:
                 h, i = (row_block - lo) // m.rows, (row_block - lo) % m.rows
                 return f"(Q, row {i} of member {k}, head {h}, d {d}): member {k}, source row {m.row0 + i}"
-    page, rest = flat // (KV * 64 * D), flat % (KV * 64 * D)
+    page, rest = c.page0 + flat // (KV * 64 * D), flat % (KV * 64 * D)
     g, rest = rest // (64 * D), rest % (64 * D)
     slot, d = (rest // D, rest % D) if name == "Kt" else (rest % 64, rest // 64)
     for k, m in enumerate(c.members):
@@ -430,6 +453,8 @@ def mismatch(c, got, e, stats=None):
             f = int(bad[0])
             msgs.append(f"{name}: {bad.size} of {g.size} elements differ; first {locate(c, name, f)} got 0x{int(g[f]):04x}, expected 0x{int(x[f]):04x}"
                         + (" (the sentinel: nobody may write here)" if int(x[f]) in (SENT, SENT_F32) else " (still the sentinel: not written)" if int(g[f]) in (SENT, SENT_F32) else ""))
+    for (name, off), _ in sorted(getattr(got, "stray", {}).items())[:1]:
+        msgs.append(f"{name}: {len(got.stray)} pages written outside pages {c.page0} .. {c.page0 + c.win - 1}; first at element offset {off} of the pool (the sentinel: nobody may write here)")
     return f"{c}: " + "; ".join(msgs) if msgs else None
 
 
@@ -462,3 +487,36 @@ def cases():
                     continue
                 out.append(dict(form="ext", geo=geo, mode=2, seed=n + 700 + pi, lens=lens, vl_pos0=p0, vt=True, **f))
     return out
+
+
+# ---- the relocated cases: the same launches on pages whose offsets inside the pool need more than 32 bits ----------------------------------------------------------------
+def relocated_cases():
+    """-> [(spec, k)]: specs TAKEN FROM cases() (no new shape), to be laid out from the first page at or above 2^k elements of a POOL_ELEMS pool (build_relocated).
+    k = 31: every page offset is above 2^31 elements.  Between them: all four kernels (single with a table: qkv_post_kernel + v_transpose_kernel, also in their
+    ragged form; extend: the two _ext kernels), modes 0 / 1 / 2, q_rs, Vt NULL, head dims 64, 128 and the padded 80 -> 96 and 88 -> 96 (page sizes that are not powers of
+    two: a wrapped offset is not even page aligned).  k = 30: one more, byte offsets between 2^31 and 2^32."""
+    sp = cases()
+
+    def pick(**kw):
+        test = kw.pop("test", lambda s: True)
+        return next(s for s in sp if all(s.get(k) == v for k, v in kw.items()) and test(s))
+
+    table = dict(form="single", table=True)
+    out = [(pick(geo=GEOS[0], mode=0, S=65, vt=True, **table), 31),
+           (pick(geo=GEOS[2], mode=2, S=65, vt=True, test=lambda s: s["pos0"] > 0, **table), 31),
+           (pick(geo=GEOS[1], mode=2, S=130, vt=True, k_ones=1, ones_row=1, **table), 31),
+           (pick(geo=GEO_IV2, mode=1, q_rs=False, S=65, vt=True, **table), 31),
+           (pick(geo=GEO_IV2, mode=1, q_rs=True, S=130, vt=True, **table), 31),
+           (pick(geo=GEOS[2], mode=0, vt=False, test=lambda s: s["pos0"] & 63, **table), 31),
+           (pick(form="ragged", geo=GEOS[1], lens=GROUPS[4], vt=True), 31),
+           (pick(form="ragged", geo=GEOS[2], lens=GROUPS[3], vt=True), 31),
+           (pick(form="ext", geo=GEOS[2], lens=GROUPS[5], vl_pos0=EXT_POS0[2]), 31),
+           (pick(form="ext", geo=GEOS[1], lens=GROUPS[2], vl_pos0=EXT_POS0[0]), 31),
+           (pick(form="ext", geo=GEOS[0], lens=GROUPS[4], vl_pos0=EXT_POS0[0]), 30)]
+    return out
+
+
+def build_relocated(spec, k):
+    """build(spec) with its pages from the first one at or above 2^k elements of a pool of POOL_ELEMS elements"""
+    pe = spec["geo"][1] * 64 * spec["geo"][3]
+    return build(spec, first_page=first_page_above(1 << k, pe), n_pages=POOL_ELEMS // pe)

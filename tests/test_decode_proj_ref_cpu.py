@@ -1,6 +1,7 @@
 """tests/decode_proj_ref.py checked on its own, without a GPU: the exact cases are exact, the quantiser restatements agree with torch.float8_e4m3fn and with the
 oracle's de-quantisers (on random data and on the edge set the GPU test feeds the kernels), the coverage claims hold, and the bounded references evaluated in
-float32 stay well inside their own bounds."""
+float32 stay well inside their own bounds.  The relocated rope cases (decode_proj_ref.rope_relocated_cases): a float32 emulation of the epilogue over sparse
+pools passes, and three wrong kernels that form a page's offset in 32 bits are reported."""
 import numpy as np
 import pytest
 import torch
@@ -235,3 +236,46 @@ def test_rope_reference_in_fp32(geo):
         assert bad == 0 and r < 0.6
         assert R.max_ratio(o[H:], k.x[b], k.e[b])[1] == 0 and R.max_ratio(y[b, H + KV:].to(bf), v.x[b], v.e[b])[1] == 0
     assert not bool((tabs[0][100] == tabs[2][100]).all())
+
+
+# ---- the relocated rope cases ----------------------------------------------------------------------------------------------------------------------------------------
+RELOCATED = R.rope_relocated_cases()
+
+
+def test_the_relocated_rope_cases_are_what_the_issue_of_page_offsets_needs():
+    hi = [r for r in RELOCATED if r[6] == 31]
+    assert sorted(r[6] for r in RELOCATED) == [30] + [31] * len(hi)
+    assert {r[4] for r in hi if r[5] == 1} == {1, 2, 4} and 16 in {r[4] for r in hi if r[5] == 0} and {r[2] for r in hi if r[5] == 0} == {0, 1, 2} and all(r[2] == 0 for r in hi if r[5] == 1)
+    assert {r[0] for r in RELOCATED} == set(ROPE_GEOS) and {r[1] for r in RELOCATED} == {"rope10", "rope01", "rope_switch"}
+    for r in RELOCATED:
+        geo, form, w_fmt, K, B, path, k = r
+        c = R.rope_relocated_case(*r)
+        small = R.exact_case(c.N, K, B, form, seed=0, w_fmt=w_fmt, rope_geo=geo)
+        pe = geo[1] * 64 * geo[3]
+        written = [int(c.tables[b, int(c.pos[b]) >> 6]) for b in range(B)]
+        assert c.page_elems == pe and c.n_pages == R.POOL_ELEMS // pe == c.kw["n_pages"] and c.page0 + c.win <= c.n_pages and (c.page0 - 1) * pe < 1 << k
+        assert int(c.tables.min()) * pe >= 1 << k and min(written) * pe >= 1 << k and (k == 31 or (int(c.tables.max()) + 1) * pe * 2 <= 1 << 32)
+        assert torch.equal(c.tables - c.page0, small.tables) and torch.equal(c.pos, small.pos) and small.page0 == 0 and small.n_pages == small.win == c.win
+        for name in ("expect_Q", "expect_Kt", "expect_Vt"):   # the expectation does not depend on first_page
+            assert torch.equal(getattr(c, name).view(torch.int16), getattr(small, name).view(torch.int16))
+
+
+@pytest.mark.parametrize("n", range(len(RELOCATED)))
+def test_page_offsets_formed_in_32_bits_are_caught_on_every_relocated_rope_case(n):
+    """the float32 emulation over sparse pools passes; a page offset taken mod 2^31 elements or mod 2^32 bytes is reported on every case above 2^31 elements.  On the
+    case above 2^30 those two ARE the identity (every offset is below 2^31 elements = 2^32 bytes) -- what that placement catches is the SIGNED 32-bit byte offset"""
+    r = RELOCATED[n]
+    c = R.rope_relocated_case(*r)
+    ok = R.rope_emulate(c)
+    assert R.rope_mismatch(c, ok) is None and len(ok["Kt"]) == c.batch == len(ok["Vt"])
+    for mut in R.MUTATIONS:
+        got = R.rope_emulate(c, mut)
+        msg = R.rope_mismatch(c, got)
+        if r[6] == 30 and mut != "page_byte_int32":
+            assert msg is None
+            continue
+        assert msg is not None and "Kt: page" in msg and "Vt: page" in msg and "not written" in msg and "written outside pages" in msg and "Q differs" not in msg, (mut, msg)
+        assert all(k[0] == "stray" and k[1] + c.page_elems <= c.page0 * c.page_elems for k in got["Kt"]), "the wrapped writes land in front of the case's pages"
+    small = R.exact_case(c.N, r[3], r[4], r[1], seed=0, w_fmt=r[2], rope_geo=r[0])
+    for mut in (None,) + R.MUTATIONS:                         # on the small pools the three are the identity
+        assert R.rope_mismatch(small, R.rope_emulate(small, mut)) is None

@@ -7,6 +7,8 @@ test_decode_proj_ref_cpu.py).
   quantisers every finite bf16 pattern in range of its row / block scale plus the edge set (decode_proj_ref.fp8_edge_rows / mxfp4_edge_rows): de-quantised
              weight, scales and -- through one-hot activations -- the tile stream, bit for bit against the numpy restatements
   bounded    dense data, float64 reference, per-element derived bound (decode_proj_ref: nothing fitted); the largest err / bound per form is printed
+  above 2^31 decode_proj_ref.rope_relocated_cases(): rope cases of the sweep whose tables name pages above 2^31 elements (one: above 2^30) of 4.3 GB pools -- the same
+             expectation, the rest of both pools all sentinel (checked whole, on the device), bit-identical to the case at first_page = 0
   refusals   every documented precondition comes back as GVL_ERR_ARG and leaves the outputs untouched
 
 What the launchers refuse (asserted, not skipped): path 1 serves batch 1, 2, 4 only and no quantised weights, fused-norm sums or tiled buffers; sq_in needs
@@ -31,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 import decode_proj_ref as R  # noqa: E402
 import gemm_ref as G  # noqa: E402
-from gpu_util import DEV, bf, check, tiny_geo  # noqa: E402
+from gpu_util import DEV, bf, big_pool_pair, check, count_other, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, lib as L  # noqa: E402
 
 FILL = -7776.0                                              # a bf16 number no exact case produces
@@ -61,8 +63,9 @@ def refused(eng, W, x, outs, **kw):
         assert torch.equal(o.view(torch.uint8), b.view(torch.uint8)), "a refused call wrote to an output"
 
 
-def run_case(eng, c, path=0, variant=0, guard=0, rows=None, tiled_x=False):
-    """one call for an exact case (rows: a subset of its sequences, run as their own batch).  -> dict of the output tensors, on the CPU"""
+def run_case(eng, c, path=0, variant=0, guard=0, rows=None, tiled_x=False, pools=None):
+    """one call for an exact case (rows: a subset of its sequences, run as their own batch).  -> dict of the output tensors, on the CPU.  pools (rope): the flat K and
+    V^T buffers to view as [c.n_pages][KV][64][D], sentinel-filled by the caller; of them the pages c.page0 .. c.page0 + c.win - 1 come back"""
     sel = list(range(c.batch)) if rows is None else rows
     B, N, f = len(sel), c.N, c.f
     kw = dict(c.kw, path=path, variant=variant)
@@ -71,8 +74,12 @@ def run_case(eng, c, path=0, variant=0, guard=0, rows=None, tiled_x=False):
     if "rope" in f:
         H, KV, Dr, D = c.geo
         out["Q"] = torch.full((B, H * D), R.SENTINEL, dtype=bf, device=DEV)
-        out["Kt"] = torch.full((c.n_pages, KV, 64, D), R.SENTINEL, dtype=bf, device=DEV)
-        out["Vt"] = torch.full((c.n_pages, KV, D, 64), R.SENTINEL, dtype=bf, device=DEV)
+        if pools is None:
+            out["Kt"] = torch.full((c.n_pages, KV, 64, D), R.SENTINEL, dtype=bf, device=DEV)
+            out["Vt"] = torch.full((c.n_pages, KV, D, 64), R.SENTINEL, dtype=bf, device=DEV)
+        else:
+            n = c.n_pages * c.page_elems
+            out["Kt"], out["Vt"] = pools[0][:n].view(bf).view(c.n_pages, KV, 64, D), pools[1][:n].view(bf).view(c.n_pages, KV, D, 64)
         kw.update(out, cos_s=dev(c.cos_s), sin_s=dev(c.sin_s), cos_l=dev(c.cos_l), sin_l=dev(c.sin_l), pos=dev(c.pos[sel].contiguous()), tables=dev(c.tables[sel].contiguous()))
     else:
         stride = N + guard
@@ -97,6 +104,8 @@ def run_case(eng, c, path=0, variant=0, guard=0, rows=None, tiled_x=False):
         x = R.to_tiled(x)
         kw.update(x_is_tiled=1, batch=B)
     eng.op_decode_proj(dev(c.W), dev(x), **kw)
+    if "rope" in f:                                         # the case's pages: all of the pool on the small pools
+        out["Kt"], out["Vt"] = out["Kt"][c.page0:c.page0 + c.win], out["Vt"][c.page0:c.page0 + c.win]
     return {k: v.cpu() for k, v in out.items()}
 
 
@@ -109,7 +118,7 @@ def assert_case(c, got, what, rows=None, guard=0):
         if rows is not None:                                # only these sequences' slots are written
             ek, ev = torch.full_like(ek, R.SENTINEL), torch.full_like(ev, R.SENTINEL)
             for b in sel:
-                p = int(c.pos[b]); page, slot = int(c.tables[b, p >> 6]), p & 63
+                p = int(c.pos[b]); page, slot = int(c.tables[b, p >> 6]) - c.page0, p & 63
                 ek[page, :, slot] = c.expect_Kt[page, :, slot]
                 ev[page, :, :, slot] = c.expect_Vt[page, :, :, slot]
         for name, g, w in (("Q", got["Q"].view(len(sel), H, D), eq), ("Kt", got["Kt"], ek), ("Vt", got["Vt"], ev)):
@@ -238,6 +247,43 @@ def test_exact_rope_placement(eng, geo, form):
     for w_fmt, K in ((0, 256), (1, 512), (2, 1024)):
         sweep(eng, form, w_fmt, (N,), (K,), (5, 16) if w_fmt == 0 else (5,), rope_geo=geo)
     sweep(eng, form, 0, (N,), (256,), (1, 2, 4), path=1, rope_geo=geo)
+
+
+# ---- exact: RoPE + Q + paged KV append on pages whose offsets need more than 32 bits ------------------------------------------------------------------------
+RELOCATED = R.rope_relocated_cases()
+SENT_BITS = int(torch.tensor(R.SENTINEL, dtype=bf).view(torch.int16))
+
+
+@pytest.fixture(scope="module")
+def big_pools():
+    """K and V^T pools of decode_proj_ref.POOL_ELEMS (just over 2^31) bf16 elements each, 4.3 GB apiece, shared by every relocated case and freed with the module"""
+    pools = big_pool_pair(R.POOL_ELEMS)
+    yield pools
+    pools.clear()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("n", range(len(RELOCATED)))
+def test_exact_rope_placement_above_2_to_the_31_elements_of_the_pools(eng, big_pools, n):
+    """decode_rope_pair (gvl_decode_epi.h) from both kernels: a case of the rope sweep whose page tables name pages from the first one at or above 2^31 (the last case:
+    2^30) elements of 4.3 GB pools.  Q, the K page slots and the V^T page slots bit for bit; EVERY other element of both pools still the sentinel (the low part never
+    holds the case's data: a wrapped write cannot produce the right pages); every output bit-identical to the same case on its small pools at first_page = 0"""
+    geo, form, w_fmt, K, B, path, k = RELOCATED[n]
+    c = R.rope_relocated_case(*RELOCATED[n])
+    small = R.exact_case(c.N, K, B, form, seed=0, w_fmt=w_fmt, rope_geo=geo)
+    assert int(c.tables.min()) * c.page_elems >= 1 << k and (k == 31 or (int(c.tables.max()) + 1) * c.page_elems <= 1 << 31), "the pages of this case do not lie where the test says"
+    for p in big_pools:
+        p.fill_(SENT_BITS)
+    what = f"{form} {FMT_NAME[w_fmt]} path {path} {geo} K={K} batch={B} pages from {int(c.tables.min())} (2^{k} elements)"
+    got = run_case(eng, c, path, pools=big_pools)
+    assert_case(c, got, what)
+    lo, hi = c.page0 * c.page_elems, (c.page0 + c.win) * c.page_elems
+    for name, p in (("K", big_pools[0]), ("V^T", big_pools[1])):
+        bad = count_other(p, SENT_BITS, lo, hi)
+        assert bad == 0, f"{what}: {bad} elements of the {name} pool outside pages {c.page0} .. {c.page0 + c.win - 1} are no longer the sentinel"
+    low = run_case(eng, small, path)
+    for name in ("Q", "Kt", "Vt"):
+        assert torch.equal(bits(got[name]), bits(low[name])), f"{what}: {name} differs from the same case at first_page = 0"
 
 
 # ---- quantisers ----------------------------------------------------------------------------------------------------------------------------------------

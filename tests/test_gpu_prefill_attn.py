@@ -15,6 +15,8 @@ implicit pages only; the model-level tests see these forms through goldens at mo
                  ring 0 / 2 / 3.
   every launch   160 sentinel guard rows behind O.
   refusals       what the plans refuse, a page outside the pools, a table shorter than the key tiles read: nothing written.
+  above 2^31     prefill_attn_ref.relocated_cases(): cases of the lists on pages whose element offsets inside 4.3 GB all-NaN pools lie above 2^31 (one: above 2^30,
+                 where the byte offsets pass 2^31) -- the same expectations, the pools unchanged (checked whole, on the device), bit-identical to the case at first_page = 0.
   joined         gvl_op_qkv_post then gvl_op_prefill_attention on the same buffers for one extend group: page layout, D padding and 64-slot pages of the two contracts meet.
 test_prefill_attn_ref_cpu.py proves on these lists that twelve wrong kernels are reported by the comparisons used here.
 
@@ -28,7 +30,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import DEV, bf, tiny_geo  # noqa: E402
+from gpu_util import DEV, bf, big_pool_pair, count_other, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, lib as L  # noqa: E402
 import prefill_attn_ref as P  # noqa: E402
 from attn_ref import SENT, _bits  # noqa: E402
@@ -231,3 +233,48 @@ def test_qkv_post_then_prefill_attention_on_the_same_buffers(eng):
     ref, bound = P.elementwise_bound(c)
     msg, w = P.bound_violations(got, ref, bound, c)
     assert msg is None, msg
+
+
+# ---- page offsets that need more than 32 bits ----------------------------------------------------------------------------------------------------------------------------
+RELOCATED = P.relocated_cases()
+NAN_BITS = 0x7FC0                                       # the bf16 NaN the pools are filled with: what torch.full(..., nan) holds
+
+
+@pytest.fixture(scope="module")
+def big_pools():
+    """K and V^T pools of prefill_attn_ref.POOL_ELEMS (just over 2^31) bf16 elements each, 4.3 GB apiece, shared by every relocated case and freed with the module"""
+    pools = big_pool_pair(P.POOL_ELEMS)
+    yield pools
+    pools.clear()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("n", range(len(RELOCATED)))
+def test_pages_above_2_to_the_31_elements_of_the_pools(eng, big_pools, n):
+    """a case of the lists on pages from the first one at or above 2^31 (the last case: 2^30) elements of 4.3 GB pools that are NaN everywhere else -- the low part never
+    holds the case's data, so a wrapped read finds NaN: O against the same expectation as on the small pools (one-hot: bit for bit; dense: zero elements outside the
+    float64 bound), the pools unchanged (outside the case's pages all NaN, checked whole; the case's pages as the reference wrote them), and O bit-identical to the same
+    case on its small pools at first_page = 0"""
+    s, k = RELOCATED[n]
+    for p in big_pools:
+        p.fill_(NAN_BITS)
+    c = P.make_relocated(s, k, DEV, [p.view(bf) for p in big_pools])
+    small = P.make(s, DEV)
+    named = [m.table[t] for m in c.members for t in range((m.Sk + 63) // 64)]
+    assert min(named) * c.page_elems >= 1 << k and (k == 31 or (max(named) + 1) * c.page_elems <= 1 << 31), "the pages of this case do not lie where the test says"
+    assert c.Kt.data_ptr() == big_pools[0].data_ptr() and c.Vt.data_ptr() == big_pools[1].data_ptr() and c.n_pages * c.page_elems <= P.POOL_ELEMS
+    got = launch(eng, c)
+    if "target" in s:
+        msg, what = P.onehot_mismatch(got, c), "bit for bit"
+    else:
+        ref, bound = P.elementwise_bound(c)
+        msg, w = P.bound_violations(got, ref, bound, c)
+        what = f"zero elements outside the bound, worst err / bound {w:.3f}"
+    assert msg is None, msg
+    lo, hi = c.page0 * c.page_elems, (c.page0 + c.win) * c.page_elems
+    for name, p, mine, ref_pool in (("K", big_pools[0], c.Kt, small.Kt), ("V^T", big_pools[1], c.Vt, small.Vt)):
+        bad = count_other(p, NAN_BITS, lo, hi)
+        assert bad == 0, f"{c}: {bad} elements of the {name} pool outside pages {c.page0} .. {c.page0 + c.win - 1} are no longer NaN"
+        assert torch.equal(_bits(mine[c.page0:c.page0 + c.win]), _bits(ref_pool)), f"{c}: the case's pages of the {name} pool changed, or were not laid out as on the small pools"
+    assert torch.equal(_bits(got), _bits(launch(eng, small))), f"{c}: O differs from the same case at first_page = 0"
+    print(f"[parity] prefill attention on pages {min(named)} .. {max(named)} (element offsets from {min(named) * c.page_elems}, 2^{k} = {1 << k}): {what}")

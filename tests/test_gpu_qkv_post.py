@@ -14,6 +14,8 @@ the form-against-form tests (test_gpu_extend_varlen.py, test_prefix_sharing_fork
                  straddle two and three members.  test_qkv_post_ref_cpu.py proves on this list that seventeen wrong kernels are reported by the comparison used here.
   bit identity   a ragged / extend member against its own single-sequence launch at pos0 = vl_pos0[u]; implicit pages against an identity table.
   refusals       every refusal of the contract in include/gvl.h, with every output all-sentinel afterwards.
+  above 2^31     qkv_post_ref.relocated_cases(): cases of THE list on pages whose element offsets inside 4.3 GB pools lie above 2^31 (one: above 2^30, where the byte offsets
+                 pass 2^31) -- the same expectations, the rest of both pools all sentinel (checked whole, on the device), bit-identical to the case at first_page = 0.
 
 A failure names the count, the first (buffer, page / row, head, slot, d), the member and the source row.
 
@@ -28,7 +30,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import DEV, bf, tiny_geo  # noqa: E402
+from gpu_util import DEV, bf, big_pool_pair, count_other, tiny_geo  # noqa: E402
 from grounded_video_llm_amd import engine as E, lib as L  # noqa: E402
 import qkv_post_ref as R  # noqa: E402
 
@@ -186,3 +188,62 @@ def test_refusals_write_nothing_and_a_good_launch_follows(eng):
     for c in (single, plain, norm, group, ragged):
         msg = R.mismatch(c, launch(eng, c), R.expect(c))
         assert msg is None, "after the refusals: " + msg
+
+
+# ---- page offsets that need more than 32 bits ----------------------------------------------------------------------------------------------------------------------------
+RELOCATED = R.relocated_cases()
+
+
+@pytest.fixture(scope="module")
+def big_pools():
+    """K and V^T pools of qkv_post_ref.POOL_ELEMS (just over 2^31) bf16 elements each, 4.3 GB apiece, shared by every relocated case and freed with the module"""
+    pools = big_pool_pair(R.POOL_ELEMS)
+    yield pools
+    pools.clear()
+    torch.cuda.empty_cache()
+
+
+class BigBuffers(Buffers):
+    """Buffers whose pools are views [n_pages][KV][64][D] of the big ones, sentinel-filled on the device before the launch"""
+
+    def __init__(self, c, pools):
+        Buffers.__init__(self, c)
+        self.flat, n = pools, c.n_pages * c.page_elems
+        for p in pools:
+            p.fill_(R.SENT)
+        self.Kt, self.Vt = pools[0][:n].view(bf).view(c.n_pages, c.KV, 64, c.D), pools[1][:n].view(bf).view(c.n_pages, c.KV, c.D, 64)
+        self.win = (c.page0 * c.page_elems, (c.page0 + c.win) * c.page_elems)
+
+    def images(self):
+        torch.cuda.synchronize()
+        im = type("Got", (), {})()
+        im.Q = self.Q.view(torch.int16).cpu().numpy().view(np.uint16)
+        for name, p, shape in (("Kt", self.flat[0], self.Kt.shape[1:]), ("Vt", self.flat[1], self.Vt.shape[1:])):   # the case's pages, as qkv_post_ref.Images holds them
+            setattr(im, name, p[self.win[0]:self.win[1]].cpu().numpy().view(np.uint16).reshape((-1,) + tuple(shape)))
+        im.q_rs = self.q_rs.view(torch.int32).cpu().numpy().view(np.uint32)
+        return im
+
+
+@pytest.mark.parametrize("n", range(len(RELOCATED)))
+def test_pages_above_2_to_the_31_elements_of_the_pools(eng, big_pools, n):
+    """a case of THE list on pages from the first one at or above 2^31 (the last case: 2^30) elements of 4.3 GB pools: the named pages and Q / q_rs against the same
+    expectation as on the small pools (bit for bit; mode 1 inside its bound), EVERY other element of both pools still the sentinel -- the low part never holds the case's
+    data, so a wrapped write cannot land on the right values -- and every buffer bit-identical to the same case on its small pools at first_page = 0"""
+    s, k = RELOCATED[n]
+    c, small = R.build_relocated(s, k), R.build(s)
+    named = [m.table[t] for m in c.members for t in range(m.pos0 >> 6, (m.pos0 + m.rows + 63) >> 6)]
+    assert min(named) * c.page_elems >= 1 << k and (k == 31 or max(named) * c.page_elems < 1 << 31), "the pages of this case do not lie where the test says"
+    b = BigBuffers(c, big_pools)
+    eng.op_qkv_post(**fields(c, b))
+    got = b.images()
+    stats = {}
+    msg = R.mismatch(c, got, R.expect(c), stats)
+    assert msg is None, msg
+    for name, p in (("K", big_pools[0]), ("V^T", big_pools[1])):
+        bad = count_other(p, R.SENT, *b.win)
+        assert bad == 0, f"{c}: {bad} elements of the {name} pool outside pages {c.page0} .. {c.page0 + c.win - 1} are no longer the sentinel"
+    low = launch(eng, small)
+    for name in ("Q", "Kt", "Vt", "q_rs"):
+        assert np.array_equal(getattr(got, name).reshape(-1), getattr(low, name).reshape(-1)), f"{c}: {name} differs from the same case at first_page = 0"
+    print(f"[parity] qkv_post on pages {min(named)} .. {max(named)} (element offsets from {min(named) * c.page_elems}, 2^{k} = {1 << k}): "
+          + ("bit for bit" if c.mode != 1 else "zero elements outside the bound, largest err / bound " + ", ".join(f"{a} {v:.3f}" for a, v in sorted(stats.items()))))

@@ -106,6 +106,15 @@ def test_c_abi_exports_every_declared_symbol():
     assert n_fields >= 10 and ctypes.sizeof(L.GvlConfig) == 4 * len(L.GvlConfig._fields_)
 
 
+def test_seq_pages_accessor_without_a_ctx_is_an_argument_error_that_writes_nothing():
+    """gvl_debug_seq_pages is host-only: it can be called here.  Its argument handling on a live table is SeqTable::pages_of's (test_seq_table_cpu.py); what the entry
+    adds is the ctx check"""
+    lib = L.load()
+    buf, n = (ctypes.c_int32 * 4)(-7, -7, -7, -7), ctypes.c_int(-9)
+    assert lib.gvl_debug_seq_pages(None, 0, buf, 4, ctypes.byref(n)) == L.ERR_ARG == lib.gvl_debug_seq_pages(None, 0, None, 0, None)
+    assert list(buf) == [-7] * 4 and n.value == -9
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -1,6 +1,8 @@
 """CPU tests of tests/prefill_attn_ref.py: the references of test_gpu_prefill_attn.py can fail, and a correct implementation stays inside them.
 prefill_attn_ref.emulate -- attn_fwd_kernel's documented arithmetic reading the pages through the tables -- stands in for a correct kernel over THE lists the GPU test
-runs, and with mut=... for twelve wrong ones: every one of them must be reported by the comparisons the GPU test asserts with, on cases of those lists."""
+runs, and with mut=... for twelve wrong ones: every one of them must be reported by the comparisons the GPU test asserts with, on cases of those lists.
+Three more wrong kernels form a page's offset in 32 bits: they are the identity on those lists and must be reported on every relocated case
+(prefill_attn_ref.relocated_cases), read through sparse pools."""
 import os
 import sys
 
@@ -120,7 +122,7 @@ PROOFS = {
 }
 
 
-@pytest.mark.parametrize("mut", P.MUTATIONS)
+@pytest.mark.parametrize("mut", [m for m in P.MUTATIONS if m not in P.PAGE_MUTATIONS])             # the page mutations: test_page_offsets_formed_in_32_bits_...
 def test_every_mutation_is_caught_by_the_comparisons_of_the_gpu_test(mut):
     assert len(PROOFS[mut]) >= 2, mut
     for s in PROOFS[mut]:
@@ -144,3 +146,60 @@ def test_a_group_member_is_its_own_single_sequence_launch_in_the_reference_too()
         for u, m in enumerate(c.members):
             d = P.single_launch_of(c, u)
             assert (d.qpos0, d.Sk) == (m.qpos0, m.qpos0 + m.S) and torch.equal(_bits(P.emulate(d)[:m.S]), _bits(whole[m.row0:m.row0 + m.S]))
+
+
+# ---- the relocated cases ------------------------------------------------------------------------------------------------------------------------------------------------
+RELOCATED = P.relocated_cases()
+
+
+def _judge(c, out):
+    if hasattr(c, "target"):
+        return P.onehot_mismatch(out, c)
+    ref, bound = P.elementwise_bound(c)
+    return P.bound_violations(out, ref, bound, c)[0]
+
+
+def test_the_relocated_cases_are_cases_of_the_lists_on_pages_above_2_to_the_31():
+    every = EXACT + GROUPS_EXACT + BOUNDED + GROUPS_BOUNDED
+    assert all(s in every for s, _ in RELOCATED) and sorted(k for _, k in RELOCATED) == [30] + [31] * (len(RELOCATED) - 1)
+    hi = [s for s, k in RELOCATED if k == 31]
+    single = [s for s in hi if s["form"] == "single"]
+    assert {s["causal"] for s in single} == {0, 1} and 0 in {s["ring"] for s in single} and {s["ring"] for s in single} - {0}
+    assert any(s["form"] == "ragged" and len(s["lens"]) == 8 for s in hi) and any(s["form"] == "ext" and s.get("share") for s in hi)
+    assert any(s["form"] == "ext" and len(s["lens"]) == 8 and any(s["vl_pos0"]) for s in hi) and {s["D"] for s in hi} == {64, 96, 128} and any("kind" in s for s in hi)
+    for s, k in RELOCATED:
+        c, small = P.make_relocated(s, k), P.make(s)
+        pe = c.KV * 64 * c.D
+        named = sorted({m.table[t] for m in c.members for t in range((m.Sk + 63) // 64)})
+        assert c.page_elems == pe and c.n_pages == P.POOL_ELEMS // pe and min(named) * pe >= 1 << k and (c.page0 - 1) * pe < 1 << k
+        assert k == 31 or (1 << 31) <= min(named) * pe * 2 and (max(named) + 1) * pe * 2 <= 1 << 32
+        assert sorted(c.Kt.pages) == named == sorted(c.Vt.pages), "only the named pages are written"
+        for m, ms in zip(c.members, small.members):
+            assert [x - c.page0 for x in m.table[:-1]] == ms.table[:-1] and not 0 <= m.table[-1] < c.n_pages, "the same permutation, moved; the spare entry is no page"
+            for t in range((m.Sk + 63) // 64):               # the same pages, bit for bit
+                assert torch.equal(_bits(c.Kt[m.table[t]]), _bits(small.Kt[ms.table[t]])) and torch.equal(_bits(c.Vt[m.table[t]]), _bits(small.Vt[ms.table[t]]))
+        assert torch.equal(_bits(c.Q), _bits(small.Q))
+        if "target" in s:
+            assert torch.equal(_bits(c.expect), _bits(small.expect))
+
+
+@pytest.mark.parametrize("n", range(len(RELOCATED)))
+def test_page_offsets_formed_in_32_bits_are_caught_on_every_relocated_case(n):
+    """the unmutated emulation, reading the sparse pools through the tables, passes and equals the emulation on the small pools bit for bit; a page offset taken mod 2^31
+    elements or mod 2^32 bytes is reported on every case above 2^31 elements.  On the case above 2^30 those two ARE the identity (every offset is below 2^31 elements =
+    2^32 bytes) -- what that placement catches is the SIGNED 32-bit byte offset, which every case reports."""
+    s, k = RELOCATED[n]
+    c = P.make_relocated(s, k)
+    ok = P.emulate(c)
+    assert _judge(c, ok[:c.rows]) is None and torch.equal(_bits(ok), _bits(P.emulate(P.make(s))))
+    for mut in P.PAGE_MUTATIONS:
+        out = P.emulate(c, mut)
+        if k == 30 and mut != "page_byte_int32":
+            assert torch.equal(_bits(out), _bits(ok))
+            continue
+        msg = _judge(c, out[:c.rows])
+        assert msg is not None and "member" in msg and "query block" in msg, (mut, msg)
+        assert bool(torch.isnan(out[:c.rows].float()).all()), "every row multiplies the NaN it finds in front of the case's pages"
+    small = P.make(s)                                        # on the small pools of the lists the three are the identity
+    for mut in P.PAGE_MUTATIONS:
+        assert torch.equal(_bits(P.emulate(small, mut)), _bits(P.emulate(small)))

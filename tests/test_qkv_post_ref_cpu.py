@@ -1,6 +1,8 @@
 """CPU tests of tests/qkv_post_ref.py: the reference of test_gpu_qkv_post.py can fail, and a correct implementation stays inside it.
 qkv_post_ref.emulate -- the contract of gvl_qkv_post (include/gvl.h) in plain numpy -- stands in for a correct kernel over THE list the GPU test runs, and with mut=... for
-seventeen wrong ones: every one of them must be reported by the same qkv_post_ref.mismatch the GPU test asserts with, on at least one case of that list."""
+seventeen wrong ones: every one of them must be reported by the same qkv_post_ref.mismatch the GPU test asserts with, on at least one case of that list.
+Three more wrong kernels form a page's offset in 32 bits: they are the identity on that list and must be reported on every relocated case (qkv_post_ref.relocated_cases),
+evaluated over sparse pools."""
 import os
 import sys
 
@@ -146,7 +148,7 @@ def _applies(mut, s):
     return True
 
 
-@pytest.mark.parametrize("mut", R.MUTATIONS)
+@pytest.mark.parametrize("mut", [m for m in R.MUTATIONS if m not in R.PAGE_MUTATIONS])       # the page mutations: test_page_offsets_formed_in_32_bits_...
 def test_every_mutation_is_caught_by_the_comparison_of_the_gpu_test(mut):
     caught, tried, first = 0, 0, None
     for s in SPECS:
@@ -219,3 +221,60 @@ def test_the_report_names_buffer_place_member_and_source_row():
     got.Q[c.q_elems + 5] = 0
     msg = R.mismatch(c, got, e)
     assert "a page no table of this launch names" in msg and "guard element 5" in msg and "nobody may write here" in msg, msg
+
+
+# ---- the relocated cases ------------------------------------------------------------------------------------------------------------------------------------------------
+RELOCATED = R.relocated_cases()
+
+
+def _named(c):
+    return sorted({m.table[t] for m in c.members for t in range(m.pos0 >> 6, (m.pos0 + m.rows + 63) >> 6)})
+
+
+def test_the_relocated_cases_are_cases_of_the_list_on_pages_above_2_to_the_31():
+    assert all(s in SPECS for s, _ in RELOCATED) and [k for _, k in RELOCATED].count(30) == 1 and {k for _, k in RELOCATED} == {30, 31}
+    hi = [s for s, k in RELOCATED if k == 31]
+    assert {s["form"] for s in hi} == {"single", "ragged", "ext"} and all(s["table"] for s in hi if s["form"] == "single")
+    assert {s["mode"] for s in hi} == {0, 1, 2} and any(s["q_rs"] for s in hi) and any(not s["vt"] for s in hi)
+    assert {s["geo"][2:] for s in hi} >= {(64, 64), (128, 128), (80, 96), (88, 96)}
+    assert any(any(s["vl_pos0"][:len(s["lens"])]) for s in hi if s["form"] == "ext") and any(s["pos0"] > 0 for s in hi if s["form"] == "single")
+    for s, k in RELOCATED:
+        c, small = R.build_relocated(s, k), R.build(s)
+        pe = c.KV * 64 * c.D
+        assert c.page_elems == pe and c.n_pages * pe <= R.POOL_ELEMS < (c.n_pages + 1) * pe and c.page0 + c.win <= c.n_pages
+        assert min(_named(c)) * pe >= 1 << k and (c.page0 - 1) * pe < 1 << k, "the first page at or above 2^k elements"
+        assert k == 31 or (1 << 31) <= min(_named(c)) * pe * 2 and max(_named(c)) * pe * 2 < 1 << 32, "k = 30: byte offsets between 2^31 and 2^32"
+        assert [x - c.page0 for x in _named(c)] == _named(small) and c.win == small.win, "the same permutation, moved"
+        for m, ms in zip(c.members, small.members):        # what is no page in the small case is no page here either
+            assert all((a - c.page0 == b) if 0 <= b < small.n_pages else not 0 <= a < c.n_pages for a, b in zip(m.table, ms.table))
+        e, es = R.expect(c), R.expect(small)                 # the expectation does not depend on first_page
+        for name in ("Q", "Kt", "Vt", "q_rs"):
+            assert np.array_equal(getattr(e.bits, name), getattr(es.bits, name))
+            assert (name in e.bounded) == (name in es.bounded) and all(np.array_equal(a, b) for a, b in zip(e.bounded.get(name, ()), es.bounded.get(name, ())))
+
+
+@pytest.mark.parametrize("n", range(len(RELOCATED)))
+def test_page_offsets_formed_in_32_bits_are_caught_on_every_relocated_case(n):
+    """the unmutated emulation passes; a page offset taken mod 2^31 elements or mod 2^32 bytes is reported on every case above 2^31 elements.  On the case above 2^30 those
+    two ARE the identity (every offset is below 2^31 elements = 2^32 bytes: no unsigned 32-bit form is wrong there) -- what that placement catches is the SIGNED 32-bit
+    byte offset, which every case reports."""
+    s, k = RELOCATED[n]
+    c = R.build_relocated(s, k)
+    e = R.expect(c)
+    ok = R.emulate(c)
+    assert R.mismatch(c, ok, e) is None and not ok.stray
+    for mut in R.PAGE_MUTATIONS:
+        got = R.emulate(c, mut)
+        msg = R.mismatch(c, got, e)
+        if k == 30 and mut != "page_byte_int32":
+            assert msg is None and not got.stray and all(np.array_equal(getattr(got, x), getattr(ok, x)) for x in ("Q", "Kt", "Vt", "q_rs"))
+            continue
+        assert msg is not None and "member" in msg and "source row" in msg and "still the sentinel: not written" in msg and "written outside pages" in msg, (mut, msg)
+        assert len(got.stray) == len(_named(c)) * (2 if c.vt else 1) and (got.Kt == R.SENT).all() and (got.Vt == R.SENT).all()
+        lo = [off for _, off in got.stray]
+        assert all(off + c.page_elems <= c.page0 * c.page_elems for off in lo), "the wrapped writes land in front of the case's pages: in the part of the pool the GPU test keeps all sentinel"
+        assert mut == "page_byte_int32" or all(off >= 0 for off in lo)
+        assert np.array_equal(got.Q, ok.Q) and np.array_equal(got.q_rs, ok.q_rs)
+    small = R.build(s)                                       # on the small pools of the list the three are the identity
+    for mut in R.PAGE_MUTATIONS:
+        assert R.mismatch(small, R.emulate(small, mut), R.expect(small)) is None

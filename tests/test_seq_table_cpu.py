@@ -109,6 +109,22 @@ def test_clone_on_and_off_a_page_boundary():
     assert out[4]["ref"][:6] == [3, 2, 1, 1, 1, 1] and same_table(out[-1], initial(8))
 
 
+def test_pages_of_reports_a_sequences_pages_and_refuses_the_rest():
+    """SeqTable::pages_of, the body of gvl_debug_seq_pages: the count, the first min(cap, count) pages, nothing behind them; unknown / freed sequences and a negative
+    cap are refused with nothing written; a null count and a null buffer with cap 0 are fine"""
+    out = run("alloc 129\npos 0 100\nfork 0 64 200\npages 1 64 -1\npages 1 64 0\npages 1 64 1\npages 1 64 3\npages 1 64 4\npages 1 2 -1\npages 1 2 1\npages 1 2 2\n"
+              "pages 1 0 -1\npages 1 0 0\npages 1 -2 -1\npagesnull 1 64 -1\npagesnull 1 64 3\npagesnull 1 -2 0\n"
+              "pages 1 -1 -1\npages 2 64 -1\npages -1 64 -1\npages 99 64 -1\nfree 1\npages 1 64 -1\npages 0 64 2\nfree 0")
+    rc = [st["rc"] for st in out]
+    assert out[2]["seqs"]["1"]["pages"] == [0, 3, 4, 5] and out[2]["seqs"]["0"]["pages"] == [0, 1, 2]
+    assert rc[3:8] == [4, 0, 3, 5, -77], "cap >= count: the count, every page in position order, the word behind them untouched"
+    assert rc[8:11] == [4, 3, -77], "cap < count: the count is still the whole count, cap pages are written and no more"
+    assert rc[11:14] == [4, -77, 4], "cap 0: only the count, with or without a buffer"
+    assert rc[14:17] == [-99, 5, -77], "a null count: the pages alone; with a null buffer too, nothing at all"
+    assert rc[17:21] == [BAD] * 4 and rc[22] == BAD, "cap < 0, a slot never opened, ids outside the table, a freed sequence"
+    assert rc[23] == 2 and same_table(out[-1], initial(8))
+
+
 def test_bad_sources():
     assert rcs("fork 0 64 128\nclone 0 64\nalloc 64\nfree 0\nfork 0 64 128\nclone 0 64\nfork -1 64 128\nfree 0\nfree -1\nfree 7") == [BAD, BAD, 0, 0, BAD, BAD, BAD, BAD, BAD, BAD]
     assert rcs("alloc 64\nfork 0 128 192\nfork 0 64 64\nfork 0 -64 64") == [0, BAD, BAD, BAD]         # more shared pages than the source holds; no room beyond the prefix
