@@ -7,93 +7,33 @@ Same constructor arguments and `generate()` contract as models/llava_next_video.
 
 Differences that are deliberate and documented: 23 CLIP layers instead of 24
 (#2), last-row lm_head (#7), paged KV instead of DynamicCache (#8), glb_GN projected once (#5), LoRA
-merged at load (#16), greedy decoding only on this tier (the reference CLI defaults to sampling).
+merged at load (#16).  Decoding covers HF generate's modes as the reference forwards them -- greedy, sampling, beam / beam-sample / group beam search, contrastive
+search, classifier-free guidance, num_return_sequences --, each on the device; call.py resolves a call's kwargs into its mode once.
 """
 from __future__ import annotations
 
 import contextlib
 import dataclasses
-
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import call as C
 from . import dist as gdist
-from . import grammar as GR
 from . import logits as LP
 from . import logprobs as LPR
 from . import prompts as P
 from . import weights as Wt
+from .call import Mode, beam_groups, fanout_stream, num_return_sequences  # noqa: F401  (the resolvers live in call.py; these names are part of this module's surface)
 from .engine import Engine, TowerGeometry
 
 bf = torch.bfloat16
 
 
-def _sampling_args(kw):
-    """(temperature, top_p, seed) of a do_sample call, validated as HF's warpers do; without `seed` one is drawn from torch's CPU generator."""
-    t = kw.get("temperature", 1.0)
-    t = 1.0 if t is None else float(t)
-    if not t > 0:
-        raise ValueError("`temperature` has to be a strictly positive float")      # HF's TemperatureLogitsWarper check
-    top_p = kw.get("top_p")
-    if top_p is not None and not (0 < float(top_p) <= 1.0):
-        raise ValueError("`top_p` has to be a float > 0 and <= 1")
-    seed = kw.get("seed")
-    return t, top_p, int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-
-
-def _check_contrastive(kw) -> None:
-    """generate()'s contrastive search (logits.resolve_contrastive: penalty_alpha > 0, top_k > 1, do_sample false, num_beams 1) with the combinations that are not built
-    refused instead of ignored; penalty_alpha itself is validated whatever the mode."""
-    if LP.resolve_contrastive(kw) is None:
-        return
-    if LP.resolve_guidance(kw) is not None:
-        raise ValueError("generate(): contrastive search (penalty_alpha, top_k) with guidance_scale is not supported")
-    if (kw.get("num_return_sequences") or 1) > 1:
-        raise ValueError("generate(): contrastive search (penalty_alpha, top_k) is deterministic and returns one answer: num_return_sequences > 1 is not supported")
-    if kw.get("top_logprobs") is not None:
-        raise ValueError("generate(): `top_logprobs` is not supported with contrastive search (penalty_alpha, top_k); output_scores gives p and the degeneration penalty")
-
-
-def num_return_sequences(kw) -> int:
-    """generate()'s num_return_sequences (None = 1), with HF's validation (GenerationConfig.validate / GenerationMixin._validate_generated_length [ext]) as ValueError, and
-    the one combination that is not built yet -- guidance_scale with several answers -- refused instead of ignored."""
-    n = kw.get("num_return_sequences")
-    n = 1 if n is None else int(n)
-    if n < 1:
-        raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n}")
-    if n == 1:
-        return 1
-    k = kw.get("num_beams", 1) or 1
-    if k == 1 and not kw.get("do_sample", False):
-        raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).")
-    if k > 1 and n > k:
-        raise ValueError(f"`num_return_sequences` ({n}) has to be smaller or equal to `num_beams` ({k}).")
-    if LP.resolve_guidance(kw) is not None:
-        raise ValueError("generate(): guidance_scale with num_return_sequences > 1 is not supported yet")
-    return n
-
-
-def beam_groups(kw) -> Optional[Tuple[int, float]]:
-    """generate()'s num_beam_groups / diversity_penalty: None for plain decoding (1 / 0.0 / absent), else (G, lambda) after HF's validation (beam.check_groups) as
-    ValueError; the combinations that are not built -- groups with guidance_scale, groups with constrained beams -- are refused, never ignored."""
-    from . import beam as B
-    if not B.check_groups(kw.get("num_beams", 1) or 1, kw.get("num_beam_groups"), kw.get("diversity_penalty"), bool(kw.get("do_sample", False))):
-        return None
-    if LP.resolve_guidance(kw) is not None:
-        raise ValueError("generate(): num_beam_groups > 1 with guidance_scale is not supported")
-    if kw.get("constraints") or kw.get("force_words_ids"):
-        raise ValueError("generate(): constrained beams (constraints / force_words_ids) with num_beam_groups > 1 are not supported")
-    return int(kw["num_beam_groups"]), float(kw["diversity_penalty"])
-
-
-def fanout_stream(prompt: int, member: int) -> int:
-    """The random stream of answer `member` of prompt `prompt` in a generate(do_sample=True, num_return_sequences=n) call: member * 65536 + prompt.  It does not depend on
-    n, so under a fixed seed the answers for n' < n are a prefix of the answers for n, per prompt."""
-    if not 0 <= prompt < 65536 or not 0 <= member < 65536:
-        raise ValueError("num_return_sequences: at most 65536 prompts per call and 65536 answers per prompt")
-    return member * 65536 + prompt
+def _row(ids_arr, mask, i: int) -> List[int]:
+    """Row i of a padded id batch without its padding."""
+    return [int(t) for t, m in zip(ids_arr[i], mask[i]) if m]
 
 
 class SyntheticTokenizer:
@@ -309,124 +249,97 @@ class LLAVA_NEXT_VIDEO:
         return vis.view(bs, S * L, self.geo.hidden)
 
     # generate -----------------------------------------------------------------------------------------------
-    def _select_processors(self, kw, embed_len: int) -> "LP.Processors":
-        """HF generate's logits processors for the kwargs the reference forwards (repetition_penalty, no_repeat_ngram_size, min_new_tokens /
-        min_length; logits.py), resolved for inputs_embeds of `embed_len` rows.  Sets the engine's default on EVERY generate call -- off when
-        absent, and off for beam search, which applies them to its log-softmax rows itself -- so nothing carries over from one call to the next
-        (the same rule as _select_tokens for sampling).  Returns the resolved processors."""
-        procs = LP.resolve(kw, getattr(self.tokenizer, "eos_token_id", None), embed_len)
-        beams = kw.get("num_beams", 1) not in (1, None) or LP.resolve_contrastive(kw) is not None   # contrastive search processes its rows itself, as beams do
-        self.engine.set_logits_processors(*(LP.OFF if beams else procs).args())
-        return procs
+    def _resolve(self, kw, entry: str, n: int) -> "C.Call":
+        tk = getattr(self, "tokenizer", None)     # the argument errors need none; an unseeded call draws from torch's CPU generator: torch.manual_seed governs it, as HF's
+        return C.resolve_call(kw, entry=entry, n_samples=n, eos_id=getattr(tk, "eos_token_id", None), pad_id=getattr(tk, "pad_token_id", 0) or 0,
+                              vocab=self.geo.vocab, draw_seed=lambda: int(torch.randint(0, 2 ** 62, (1,)).item()))
 
-    def _select_rules(self, kw, max_new: int) -> Optional[int]:
-        """HF's token rules (sequence_bias, bad_words_ids, forced_eos_token_id, suppress_tokens, begin_suppress_tokens; logits.resolve_rules) as a
-        device rule set.  Sets the engine's default on EVERY generate call -- none when absent, and none for beam search, which passes the set
-        to its own processing of the log-softmax rows -- so nothing carries over.  Returns the rule set's id (None: no rules); the caller
-        clears the default and destroys the set in a `finally` (_drop_rules)."""
-        rules = LP.resolve_rules(kw, getattr(self.tokenizer, "eos_token_id", None), max_new, self.geo.vocab)
-        self.engine.set_token_rules(None)
-        if not rules.active:
-            return None
-        rid = self.engine.rules_create(rules)
-        if kw.get("num_beams", 1) in (1, None) and LP.resolve_contrastive(kw) is None:
-            self.engine.set_token_rules(rid)
-        return rid
+    def _check_guidance(self, kw, n: int) -> Optional[float]:     # the scale of a guided call of n samples (None: off), after call.check_guidance's checks
+        return C.check_guidance(kw, n, self.geo.vocab)[0]
 
-    def _drop_rules(self, rid: Optional[int]):
-        self.engine.set_token_rules(None)
-        if rid is not None:
-            self.engine.rules_destroy(rid)
+    @contextlib.contextmanager
+    def _settings(self, call: "C.Call", procs: "LP.Processors" = LP.OFF):
+        """The engine's settings for the length of one call: writes the five defaults on EVERY call -- log-probabilities, processors (`procs`), sampling, token rules,
+        grammar; off where the call leaves them out, so nothing carries over from one call to the next -- and creates the call's device rule set and grammar; yields
+        their two ids (None: none); clears the two defaults and destroys the two objects on the way out.  A search (not call.device_selects) gets every default off:
+        it hands the processors and the two ids to its own processing of the rows.  A rule set beyond the device's capacities is refused by Engine.rules_create."""
+        eng, on = self.engine, call.device_selects
+        eng.set_logprobs(call.logprobs.top_n if on else -1)
+        eng.set_logits_processors(*(procs if on else LP.OFF).args())
+        eng.set_sampling(*call.sampling_args, **call.warpers)
+        eng.set_token_rules(None)
+        rid = gid = None
+        if call.rules.active:
+            rid = eng.rules_create(call.rules)
+            if on:
+                eng.set_token_rules(rid)
+        try:
+            eng.set_grammar(None)
+            if call.grammar is not None:
+                gid = eng.grammar_create(call.grammar)
+                if on:
+                    eng.set_grammar(gid)
+            yield rid, gid
+        finally:
+            eng.set_grammar(None)
+            if gid is not None:
+                eng.grammar_destroy(gid)
+            eng.set_token_rules(None)
+            if rid is not None:
+                eng.rules_destroy(rid)
 
-    def _select_grammar(self, kw) -> Optional[int]:
-        """generate(grammar=g): a grammar.Grammar that constrains every answer of the call (HF's prefix_allowed_tokens_fn as a device object; the callback
-        itself cannot run inside a multi-token decode call and raises ValueError).  Sets the engine's default on EVERY generate call -- none when absent,
-        and none for beam search, whose own processing of the log-softmax rows takes the grammar -- so nothing carries over.  Returns the device grammar's
-        id (None: no grammar); the caller clears the default and destroys it in a `finally` (_drop_grammar)."""
-        if kw.get("prefix_allowed_tokens_fn") is not None:
-            raise ValueError("generate(): prefix_allowed_tokens_fn is a Python callback and cannot run inside the device's decode loop; pass grammar= "
-                             "(grounded_video_llm_amd.grammar: GrammarBuilder / grounding_grammar; Grammar.as_prefix_allowed_tokens_fn gives HF the same language)")
-        g = kw.get("grammar")
-        self.engine.set_grammar(None)
-        if g is None:
-            return None
-        if not isinstance(g, GR.Grammar):
-            raise ValueError(f"generate(): grammar must be a grounded_video_llm_amd.grammar.Grammar, not {type(g).__name__}")
-        if g.vocab != self.geo.vocab:
-            raise ValueError(f"generate(): the grammar classifies {g.vocab} ids, the model's vocabulary holds {self.geo.vocab}")
-        gid = self.engine.grammar_create(g)
-        if kw.get("num_beams", 1) in (1, None) and LP.resolve_contrastive(kw) is None:
-            self.engine.set_grammar(gid)
-        return gid
-
-    def _drop_grammar(self, gid: Optional[int]):
-        self.engine.set_grammar(None)
-        if gid is not None:
-            self.engine.grammar_destroy(gid)
-
-    def _select_logprobs(self, kw) -> "LPR.Options":
-        """return_dict_in_generate / output_scores / top_logprobs (logprobs.py; raises its ValueErrors).  Sets the engine's default on EVERY generate
-        call -- the call's setting, off for beam search (its scores come from beam.py) -- so nothing carries over from one call to the next."""
-        opts = LPR.resolve(kw)
-        beams = kw.get("num_beams", 1) not in (1, None) or LP.resolve_contrastive(kw) is not None   # contrastive search reports its own per-token p / penalty
-        self.engine.set_logprobs(-1 if beams else opts.top_n)
-        return opts
-
-    def _select_tokens(self, kw):
-        """HF generate's token selection for the kwargs the reference forwards (inference.py:170-176 -> llava_next_video.py:655-661):
-        greedy, or temperature -> top-k (HF default 50) -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff sampling on the device
-        (logits.resolve_sampling validates the last four as HF does; they are ignored without do_sample, as in HF); `seed` (extra) makes a run reproducible,
-        otherwise every call draws a fresh seed from torch's CPU generator (so torch.manual_seed governs it, as it does HF's).  Set on EVERY generate
-        call, so nothing carries over from one call to the next."""
-        LP.resolve_sampling(kw)                           # HF validates the warpers' arguments whether or not the call samples
-        if not kw.get("do_sample", False) or kw.get("num_beams", 1) not in (1, None):
-            # greedy -- and every kind of beam search: the steps return logits, the selection (top-2k, or the beam-sample draw) lives in beam.py
-            self.engine.set_sampling(False)
-            return
-        t, top_p, seed = _sampling_args(kw)
-        top_k = kw.get("top_k", 50)
-        self.engine.set_sampling(True, t, 0 if top_k is None else int(top_k), top_p, seed, **{k: v for k, v in LP.resolve_sampling(kw).items() if v is not None})
-
-    def _check_guidance(self, kw, n: int) -> Optional[float]:
-        """generate(guidance_scale=s, ...): HF's classifier-free guidance against a negative prompt (logits.resolve_guidance: off for None / 1).  Returns the scale
-        (None: off) after checking, before any work, that the call names one negative per sample -- negative_prompt_ids (HF's; plain ids, text-only) or
-        negative_prompts (extra; strings through the model's own prompt path) -- and combines guidance with nothing it is not built for."""
-        scale = LP.resolve_guidance(kw)
-        if scale is None:
-            return None
-        if kw.get("num_beams", 1) not in (1, None):
-            raise ValueError("generate(): guidance_scale with num_beams > 1 is not supported yet")
-        ids, texts = kw.get("negative_prompt_ids"), kw.get("negative_prompts")
-        if (ids is None) == (texts is None):
-            raise ValueError("generate(): guidance_scale != 1 needs the negative prompt of every sample: pass negative_prompt_ids (token ids, text-only) or "
-                             "negative_prompts (strings; with the <image> slot they see the same video) -- exactly one of them.  (HF's fallback, the prompt's last "
-                             "id, does not exist for an embeddings prompt.)")
-        if ids is not None:
-            ids = LP.negative_id_rows(ids, kw.get("negative_prompt_attention_mask"))
-            if any(t >= self.geo.vocab for r in ids for t in r):
-                raise ValueError(f"generate(): negative_prompt_ids holds an id outside the vocabulary of {self.geo.vocab} tokens")
-        elif isinstance(texts, str) or any(not isinstance(t, str) for t in texts):
-            raise ValueError("generate(): negative_prompts must be a list of strings, one per sample")
-        if len(ids if ids is not None else texts) != n:
-            raise ValueError(f"generate(): {n} samples need {n} negative prompts, not {len(ids if ids is not None else texts)}")
-        return scale
-
-    def _negative_embeds(self, kw, feats) -> List[torch.Tensor]:
-        """The negative prompts of a guided call as embedding rows, one tensor per sample.  negative_prompt_ids: the ids' embedding rows (what HF runs as the
-        unconditional branch of an inputs_embeds prompt).  negative_prompts: tokenised and truncated like the prompts; a string with the <image> slot is spliced
-        with the sample's own visual rows (a negative instruction about the same video), one without is text-only (the video-free contrast)."""
+    def _negative_embeds(self, call: "C.Call", feats) -> List[torch.Tensor]:
+        """The negative prompts of a guided call as embedding rows, one tensor per sample.  negative_ids: the ids' embedding rows (what HF runs as the unconditional
+        branch of an inputs_embeds prompt).  negative_texts: tokenised and truncated like the prompts; a string with the <image> slot is spliced with the sample's own
+        visual rows (a negative instruction about the same video), one without is text-only (the video-free contrast)."""
         eng = self.engine
-        if kw.get("negative_prompt_ids") is not None:
-            return [eng.embed_ids(r) for r in LP.negative_id_rows(kw["negative_prompt_ids"], kw.get("negative_prompt_attention_mask"))]
-        pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
+        if call.negative_ids is not None:
+            return [eng.embed_ids(r) for r in call.negative_ids]
         out = []
-        for b, t in enumerate(kw["negative_prompts"]):
-            arr, m = P.left_pad_truncate([self.tokenizer_image_token(t)], pad_id, self.max_txt_len)
-            row = [int(x) for x, k in zip(arr[0], m[0]) if k]
+        for b, t in enumerate(call.negative_texts):
+            row = _row(*P.left_pad_truncate([self.tokenizer_image_token(t)], call.pad_id, self.max_txt_len), 0)
             if sum(1 for x in row if x == P.IMAGE_TOKEN_INDEX) > 1 or not row:
                 raise ValueError("generate(): a negative prompt holds at most one <image> slot and at least one token")
             out.append(eng.splice(row, feats[b]) if P.IMAGE_TOKEN_INDEX in row else eng.embed_ids(row))
         return out
+
+    def _decode_in_pool_groups(self, n: int, plan, max_new: int, logprobs: Optional[int], launch=None):
+        """Items 0 .. n - 1, as many at once as the KV pool holds.  plan(i) -> (capacities, begin): item i needs one sequence per capacity -- a single one, or a
+        leader and its follower --, allocated in that order; begin(seqs) then sets them up.  An item the pool has no room for (ERR_OOM from seq_alloc) closes the
+        group once at least one item is in: what fits runs, the rest in the next group.  A closed group: launch(firsts, what every begin returned), if given; the
+        items' first sequences decode together; all are freed, the first sequences first -- freeing a leader unbinds its pair.  Returns what generate_ids returns."""
+        from .lib import GvlError, ERR_OOM
+        eng, eos = self.engine, getattr(self.tokenizer, "eos_token_id", None)
+        out, lps, b = [], [], 0
+        while b < n:
+            live, begun = [], []                         # per admitted item: its sequences; what its begin returned
+            try:
+                while b + len(live) < n:
+                    caps, begin = plan(b + len(live))
+                    seqs: List[int] = []
+                    try:
+                        for cap in caps:
+                            seqs.append(eng.seq_alloc(cap))
+                    except GvlError as e:
+                        for s in seqs:
+                            eng.seq_free(s)
+                        if e.status == ERR_OOM and live:
+                            break
+                        raise
+                    live.append(seqs)
+                    begun.append(begin(seqs))
+                firsts = [seqs[0] for seqs in live]
+                if launch is not None:
+                    launch(firsts, begun)
+                got = eng.decode_greedy_batch(firsts, max_new, eos)
+                if logprobs is not None:
+                    lps += [eng.seq_read_logprobs(s, 0, len(g), top=logprobs > 0) for s, g in zip(firsts, got)]
+                out += got
+            finally:
+                for s in [seqs[0] for seqs in live] + [s for seqs in live for s in seqs[1:]]:
+                    eng.seq_free(s)
+            b += len(live)
+        return out if logprobs is None else (out, lps)
 
     def guided_generate_ids(self, ids_arr, mask, feats, negatives: Sequence[torch.Tensor], scale: float, max_new: int, processors=None, logprobs: Optional[int] = None,
                             rules: Optional[int] = None, grammar: Optional[int] = None):
@@ -435,58 +348,26 @@ class LLAVA_NEXT_VIDEO:
         sequence is one more row of the leader's decode step (one weight stream for both).  Processors, rules, grammar, sampling and log-probabilities are the
         conditional sequence's and apply to the guided row: both prefills run with every setting off (a prefill's last logits are the row its own selection saw, and guidance
         needs the RAW rows), then the leader takes the call's processors, rule set `rules` and grammar `grammar`.  Returns what generate_ids returns."""
-        from .lib import GvlError, ERR_OOM
-        eos = getattr(self.tokenizer, "eos_token_id", None)
         eng = self.engine
         n = ids_arr.shape[0]
         opts = [LP.SeqOptions(p if p is not None else LP.OFF, -1 if logprobs is None else logprobs, rules, grammar=grammar)
                 for p in (processors if isinstance(processors, (list, tuple)) else [processors] * n)]
-        out: List[List[int]] = []
-        lps = []
-        b = 0
-        while b < n:                                     # as many pairs at once as the KV pool holds
-            leaders, live = [], []
-            try:
-                while b + len(leaders) < n:
-                    i = b + len(leaders)
-                    emb = eng.splice([int(t) for t, m in zip(ids_arr[i], mask[i]) if m], feats[i])
-                    room = min(max_new, self.geo.max_seq - max(emb.shape[0], negatives[i].shape[0]))
-                    if room < 1:
-                        raise ValueError(f"generate(): sample {i}: the prompt (or its negative) leaves no room below max_seq {self.geo.max_seq}")
-                    try:
-                        s = eng.seq_alloc(emb.shape[0] + room); live.append(s)
-                        f = eng.seq_alloc(negatives[i].shape[0] + room); live.append(f)
-                    except GvlError as e:
-                        if e.status == ERR_OOM and leaders:
-                            if len(live) % 2:
-                                eng.seq_free(live.pop())
-                            break                      # pool full: run what fits, the rest in the next group
-                        raise
-                    LP.apply_seq_options(eng, s, LP.SeqOptions.OFF)
-                    LP.apply_seq_options(eng, f, LP.SeqOptions.OFF)     # the follower selects nothing: it is handed the leader's tokens
-                    lc, lu = eng.prefill(s, emb, want_logits=True), eng.prefill(f, negatives[i], want_logits=True)
-                    LP.apply_seq_options(eng, s, opts[i])
-                    eng.seq_set_guidance(s, f, scale, lc, lu)
-                    leaders.append(s)
-                got = eng.decode_greedy_batch(leaders, max_new, eos)
-                if logprobs is not None:
-                    lps += [eng.seq_read_logprobs(s_, 0, len(g), top=logprobs > 0) for s_, g in zip(leaders, got)]
-                out += got
-            finally:
-                for s in live[0::2]:                     # leaders first: freeing one unbinds its pair
-                    eng.seq_free(s)
-                for s in live[1::2]:
-                    eng.seq_free(s)
-            b += len(leaders)
-        return out if logprobs is None else (out, lps)
 
-    def _sampling_dict(self, kw) -> dict:
-        """The call's sampling as ONE sequence's own setting (Engine.seq_set_sampling's dict, without the stream): what _select_tokens gives the engine, for the
-        sequences of a num_return_sequences call, whose draws must not depend on the order they were prefilled in.  Without `seed` one is drawn from torch's CPU generator."""
-        t, top_p, seed = _sampling_args(kw)
-        top_k = kw.get("top_k", 50)
-        return dict(do_sample=True, temperature=t, top_k=0 if top_k is None else int(top_k), top_p=top_p, seed=seed,
-                    **{k: v for k, v in LP.resolve_sampling(kw).items() if v is not None})
+        def plan(i):
+            emb = eng.splice(_row(ids_arr, mask, i), feats[i])
+            room = min(max_new, self.geo.max_seq - max(emb.shape[0], negatives[i].shape[0]))
+            if room < 1:
+                raise ValueError(f"generate(): sample {i}: the prompt (or its negative) leaves no room below max_seq {self.geo.max_seq}")
+
+            def begin(pair):
+                s, f = pair
+                LP.apply_seq_options(eng, s, LP.SeqOptions.OFF)
+                LP.apply_seq_options(eng, f, LP.SeqOptions.OFF)     # the follower selects nothing: it is handed the leader's tokens
+                lc, lu = eng.prefill(s, emb, want_logits=True), eng.prefill(f, negatives[i], want_logits=True)
+                LP.apply_seq_options(eng, s, opts[i])
+                eng.seq_set_guidance(s, f, scale, lc, lu)
+            return (emb.shape[0] + room, negatives[i].shape[0] + room), begin
+        return self._decode_in_pool_groups(n, plan, max_new, logprobs)
 
     def fanout_generate_ids(self, ids_arr, mask, feats, max_new: int, n: int, sampling: dict, processors=None, logprobs: Optional[int] = None, prompt_index=None):
         """n sampled answers per row from ONE prefill per row: the row is spliced and prefilled once, Engine.seq_fanout makes n - 1 siblings that share the prompt's KV
@@ -494,7 +375,7 @@ class LLAVA_NEXT_VIDEO:
         Answer j of row p draws from stream fanout_stream(p, j) of sampling["seed"], whatever n is and whatever fits the KV pool at once: when the pool cannot hold all
         siblings the remaining answers start from another prefill of the same prompt -- a sibling is bit for bit an independent sequence on its stream, so the answers
         do not change.  prompt_index: the p of every row (default: its position).  Processors, rules, grammar and log-probabilities apply per answer.
-        Returns the ids prompt-major (n per row); with logprobs (ids, lps) as generate_ids."""
+        Returns the ids prompt-major (n per row); with logprobs (ids, lps) as generate_ids.  (Not _decode_in_pool_groups: a full pool halves the part, then re-prefills the row.)"""
         from .lib import GvlError, ERR_OOM
         eos = getattr(self.tokenizer, "eos_token_id", None)
         eng = self.engine
@@ -504,7 +385,7 @@ class LLAVA_NEXT_VIDEO:
         lps = []
         for i in range(rows):
             p = i if prompt_index is None else int(prompt_index[i])
-            emb = eng.splice([int(t) for t, m in zip(ids_arr[i], mask[i]) if m], feats[i])
+            emb = eng.splice(_row(ids_arr, mask, i), feats[i])
             cap = min(emb.shape[0] + max_new, self.geo.max_seq)
             done = 0
             while done < n:
@@ -541,115 +422,76 @@ class LLAVA_NEXT_VIDEO:
 
     @torch.inference_mode()
     def generate(self, samples, **generate_kwargs):
-        """The reference's generate(samples, **generate_kwargs).  Besides greedy / sampling / beam search it honours HF's repetition_penalty,
-        no_repeat_ngram_size and min_new_tokens / min_length (logits.py; applied on the device to the generated ids only, as HF does for an
-        inputs_embeds prompt), and the token rules sequence_bias, bad_words_ids, forced_eos_token_id, suppress_tokens and begin_suppress_tokens,
-        in HF's order (logits.py), with HF's validation errors; a rule set beyond the device capacities raises ValueError.
-        grammar (extra): a grammar.Grammar (GrammarBuilder, grounding_grammar) that keeps every answer inside its language -- HF's PrefixConstrainedLogitsProcessor
-        in HF's place (after the min-length ban, before forced eos), evaluated on the device at every step of greedy decoding, sampling and both beam_impls;
-        log-probabilities are then those of the masked distribution.  prefix_allowed_tokens_fn itself raises ValueError: a Python callback cannot run inside the
-        decode loop.
-        guidance_scale (HF's; None or 1 = off): classifier-free guidance against a negative prompt, one per sample -- negative_prompt_ids (+ negative_prompt_attention_mask;
-        HF's names: plain token ids, a text-only negative sequence) or negative_prompts (extra: strings through the model's own prompt path; with the <image> slot
-        the negative sees the same video -- a negative instruction --, without it it is the video-free contrast).  Every step's scores are
-        scale * (log_softmax(conditional) - log_softmax(negative)) + log_softmax(negative), computed on the device IN FRONT of every processor, rule, grammar and
-        warper (HF's order), the first token included; the negative sequence is fed the token the conditional one selected and rides as one more row of the same
-        decode step.  Greedy and sampling; log-probabilities are then the guided distribution's.  guidance_scale != 1 without a negative prompt, with num_beams > 1,
-        or in generate_shared raises ValueError (not supported yet).
-        penalty_alpha = a in (0, 1] with top_k = k in 2 .. 16 (HF's; do_sample false, num_beams 1): contrastive search -- per token the k most probable ids (no warpers;
-        processors, rules and the grammar shape the row first) are each run one step and the arg-max of (1 - a) p - a max_j cos(h, h_j) over the hidden states of the
-        whole context wins, on the device (contrastive_generate_ids).  return_dict_in_generate with output_scores: transition_scores are the tokens' p,
-        degeneration_penalties their penalties.  With guidance_scale, num_return_sequences > 1 or top_logprobs, in generate_shared or ClipScheduler.submit it raises
-        ValueError (not built); penalty_alpha outside [0, 1] or top_k > 16 raises ValueError.  Still not supported
-        and ignored: bad_words_ids=None, encoder_repetition_penalty / encoder_no_repeat_ngram_size, forced_bos_token_id,
-        remove_invalid_values, exponential_decay_length_penalty, constrained beams (constraints,
-        force_words_ids), watermarking, renormalize_logits, custom logits_processor lists and the warpers other than temperature / top_k / top_p / min_p /
-        typical_p / epsilon_cutoff / eta_cutoff (those seven run on the device in HF's order; top_h, custom logits_warper lists stay ignored).
-        return_dict_in_generate=True returns a logprobs.GenerateOutput (texts, sequences, and with output_scores / top_logprobs the per-token
-        log-probabilities; logprobs.py) instead of the list of texts.
-        beam_impl (extra; num_beams > 1): "host" (default) = beam.py's bookkeeping with torch's log-softmax / top-2k per step; "device" = gvl_beam_search, the whole
-        search inside the library (its own kernels select the candidates; sequences_scores / transition scores come from it).  "device" with do_sample=True raises
-        ValueError: beam-sample stays on beam.py, its draws are torch's.
-        num_beam_groups = G > 1 with diversity_penalty = lambda > 0 (HF's; num_beams divisible by G, do_sample=False): diverse (group) beam search -- G groups of
-        num_beams / G beams, every later group's scores lowered by lambda x how often the earlier groups chose the token at this step (HammingDiversityLogitsProcessor,
-        in HF's place behind sequence_bias); on both beam_impls, with num_return_sequences and return_dict_in_generate as for plain beams.  HF's validation errors are
-        ValueErrors; groups with guidance_scale, with constrained beams, in generate_shared or in ClipScheduler raise ValueError (not built)."""
+        """The reference's generate(samples, **generate_kwargs) -> the answers' texts, or with return_dict_in_generate=True a logprobs.GenerateOutput (texts,
+        sequences and, with output_scores / top_logprobs, per-token log-probabilities).  call.resolve_call turns the kwargs into one call.Call -- raising every
+        argument error before any work -- and the call's mode decides what runs:
+
+          mode          kwargs (HF's unless marked extra)                       runs                         Call fields
+          greedy        (none)                                                  generate_ids                 --
+          sample        do_sample, temperature, top_k, top_p, min_p, typical_p, generate_ids                 sampling_args, warpers
+                        epsilon_cutoff, eta_cutoff, seed (extra)
+          fan-out       do_sample with num_return_sequences = n                 fanout_generate_ids          n_return, seq_sampling
+          guided        guidance_scale != 1 with negative_prompt_ids (+ mask)   guided_generate_ids          guidance, negative_ids / negative_texts
+                        or negative_prompts (extra); greedy or sampled
+          beam          num_beams = k > 1, length_penalty, early_stopping,      beam_generate_ids            num_beams, beam_impl, length_penalty,
+                        num_return_sequences <= k, beam_impl (extra)                                         early_stopping, n_return
+          beam-sample   ... with do_sample; beam_impl "host" only               beam_generate_ids            beam_sample
+          group-beam    ... with num_beam_groups = G > 1, diversity_penalty > 0 beam_generate_ids            groups
+          contrastive   penalty_alpha in (0, 1] with top_k in 2 .. 16           contrastive_generate_ids     contrastive
+
+        In every mode, on the device and in HF's order (logits.py), guidance in front: repetition_penalty, no_repeat_ngram_size, min_new_tokens / min_length
+        (Call.processors); sequence_bias, bad_words_ids, forced_eos_token_id, suppress_tokens, begin_suppress_tokens (Call.rules); grammar (extra: a grammar.Grammar in
+        the place of HF's prefix_allowed_tokens_fn, which itself is refused); max_new_tokens; return_dict_in_generate, output_scores, top_logprobs (extra;
+        Call.logprobs).  The first four modes let the device's own selection apply them (Call.device_selects), a search applies them to its own rows; the method
+        that runs a mode says what it returns as scores.  Combinations that are not built raise ValueError.  Other HF kwargs are ignored."""
         if any(v == "text" for v in samples.get("video_ids", [])):
             # prepare_multimodal_inputs' `video_ids == 'text'` branch (llava_next_video.py:583-586) is a TRAINING device (dummy visual
             # rows appended with mask 0 so FSDP sees every parameter); the reference's inference never produces it.  forward() handles it.
             raise ValueError("generate(): 'text' samples are a training-only construct of the reference; use forward() for them")
-        _beam_impl(generate_kwargs)                       # a bad beam_impl fails before any work
-        self._check_guidance(generate_kwargs, len(samples["prompts"]))     # ... and so do the guidance arguments
-        num_return_sequences(generate_kwargs)             # ... and num_return_sequences
-        beam_groups(generate_kwargs)                      # ... and num_beam_groups / diversity_penalty
-        _check_contrastive(generate_kwargs)               # ... and penalty_alpha / top_k
-        ids = [self.tokenizer_image_token(t) for t in samples["prompts"]]
-        pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
-        ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
-        opts = self._select_logprobs(generate_kwargs)
-        procs = self._select_processors(generate_kwargs, LP.padded_embed_len(ids_arr.shape[1], self._n_visual(samples)))
-        self._select_tokens(generate_kwargs)
-        max_new = int(generate_kwargs.get("max_new_tokens", 2048))
-        rid = self._select_rules(generate_kwargs, max_new)
-        gid = None
-        try:
-            gid = self._select_grammar(generate_kwargs)
-            return self._generate(samples, generate_kwargs, ids_arr, mask, opts, procs, max_new, rid, gid)
-        finally:
-            self._drop_grammar(gid)
-            self._drop_rules(rid)
+        call = self._resolve(generate_kwargs, "generate", len(samples["prompts"]))
+        ids_arr, mask = P.left_pad_truncate([self.tokenizer_image_token(t) for t in samples["prompts"]], call.pad_id, self.max_txt_len)
+        procs = call.processors(LP.padded_embed_len(ids_arr.shape[1], self._n_visual(samples)))
+        with self._settings(call, procs) as (rid, gid):
+            return self._generate(call, samples, ids_arr, mask, procs, rid, gid)
 
-    def _generate(self, samples, generate_kwargs, ids_arr, mask, opts, procs, max_new: int, rid: Optional[int], gid: Optional[int] = None):
+    def _generate(self, call: "C.Call", samples, ids_arr, mask, procs, rid: Optional[int], gid: Optional[int]):
         feats = self.encode_images(samples)
-        k = generate_kwargs.get("num_beams", 1) or 1
-        n_ret = num_return_sequences(generate_kwargs)
-        lps, beam_scores = None, None
-        cs = LP.resolve_contrastive(generate_kwargs)
-        if cs is not None:                                # HF contrastive search (penalty_alpha, top_k), one sample at a time like beams
-            scored = opts.return_dict and opts.output_scores
-            res = [self.contrastive_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], cs[0], cs[1], max_new, processors=procs, rules=rid,
-                                                 grammar=gid, with_scores=scored) for b in range(ids_arr.shape[0])]
-            if scored:
-                texts = [t.strip() for t in self.tokenizer.batch_decode([r[0] for r in res], skip_special_tokens=True)]
-                out = LPR.build_output(texts, [list(r[0]) for r in res], opts, [(r[1], None) for r in res])
-                out.degeneration_penalties = [list(r[2]) for r in res]
-                return out
-            out_ids = res
-        elif k > 1:                                         # HF beam search (do_sample=False), one sample at a time
-            sample = None
-            if generate_kwargs.get("do_sample", False):      # beam-sample (HF _beam_sample): the warpers' arguments as generate() takes them; one generator per call
-                t, top_p, seed = _sampling_args(generate_kwargs)
-                gen = torch.Generator(device=self.engine.device)
-                gen.manual_seed(seed)
-                sample = dict(temperature=t, top_k=generate_kwargs.get("top_k", 50), top_p=top_p, generator=gen, **LP.resolve_sampling(generate_kwargs))
-            scored = opts.return_dict and opts.output_scores
-            G, lam = beam_groups(generate_kwargs) or (1, 0.0)
-            out_ids = [self.beam_generate_ids([int(t) for t, m in zip(ids_arr[b], mask[b]) if m], feats[b], k, max_new,
-                                              float(generate_kwargs.get("length_penalty", 1.0)), generate_kwargs.get("early_stopping", False), sample,
-                                              processors=procs, with_scores=scored, rules=rid, impl=_beam_impl(generate_kwargs), grammar=gid, num_return=n_ret,
+        n, max_new, want = ids_arr.shape[0], call.max_new, call.want_logprobs
+        scored = call.logprobs.return_dict and call.logprobs.output_scores
+        if call.mode is Mode.CONTRASTIVE:                 # one sample at a time, like beams
+            res = [self.contrastive_generate_ids(_row(ids_arr, mask, b), feats[b], *call.contrastive, max_new, processors=procs, rules=rid, grammar=gid, with_scores=scored)
+                   for b in range(n)]
+            if not scored:
+                return self._output(call, res)
+            out = self._output(call, [r[0] for r in res], [(r[1], None) for r in res])
+            out.degeneration_penalties = [list(r[2]) for r in res]
+            return out
+        if not call.device_selects:                       # beam, beam-sample, group-beam: one sample at a time
+            sample = call.beam_sample                     # HF _beam_sample: the warpers' arguments as generate() takes them; one generator per call
+            if sample is not None:
+                sample = dict(sample, generator=torch.Generator(device=self.engine.device).manual_seed(sample["seed"]))
+            G, lam = call.groups or (1, 0.0)
+            out_ids = [self.beam_generate_ids(_row(ids_arr, mask, b), feats[b], call.num_beams, max_new, call.length_penalty, call.early_stopping, sample,
+                                              processors=procs, with_scores=scored, rules=rid, impl=call.beam_impl, grammar=gid, num_return=call.n_return,
                                               num_beam_groups=G, diversity_penalty=lam)
-                       for b in range(ids_arr.shape[0])]
-            if n_ret > 1:                                  # the n best hypotheses of every prompt, prompt-major
+                       for b in range(n)]
+            if call.n_return > 1:                         # the n best hypotheses of every prompt, prompt-major
                 out_ids = [r for per_prompt in out_ids for r in per_prompt]
-            if scored:
-                lps, beam_scores = [(r[2], None) for r in out_ids], [r[1] for r in out_ids]
-                out_ids = [r[0] for r in out_ids]
-        elif self._check_guidance(generate_kwargs, ids_arr.shape[0]) is not None:      # classifier-free guidance: every sample decodes as a pair with its negative
-            res = self.guided_generate_ids(ids_arr, mask, feats, self._negative_embeds(generate_kwargs, feats), LP.resolve_guidance(generate_kwargs), max_new,
-                                           processors=procs, logprobs=opts.top_n if opts.top_n >= 0 else None, rules=rid, grammar=gid)
-            out_ids, lps = res if opts.top_n >= 0 else (res, None)
-        elif n_ret > 1:                                   # n sampled answers per prompt from ONE prefill each (gvl_seq_fanout), prompt-major
-            res = self.fanout_generate_ids(ids_arr, mask, feats, max_new, n_ret, self._sampling_dict(generate_kwargs), processors=procs,
-                                           logprobs=opts.top_n if opts.top_n >= 0 else None)
-            out_ids, lps = res if opts.top_n >= 0 else (res, None)
-        elif opts.top_n >= 0:
-            out_ids, lps = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs, logprobs=opts.top_n)
+            if scored:                                    # (ids, sequences_score, transition_scores) per hypothesis
+                return self._output(call, [r[0] for r in out_ids], [(r[2], None) for r in out_ids], [r[1] for r in out_ids])
+            return self._output(call, out_ids)
+        if call.mode is Mode.GUIDED:                      # every sample decodes as a pair with its negative
+            res = self.guided_generate_ids(ids_arr, mask, feats, self._negative_embeds(call, feats), call.guidance, max_new, processors=procs, logprobs=want,
+                                           rules=rid, grammar=gid)
+        elif call.mode is Mode.FANOUT:                    # n sampled answers per prompt from ONE prefill each (gvl_seq_fanout), prompt-major
+            res = self.fanout_generate_ids(ids_arr, mask, feats, max_new, call.n_return, call.seq_sampling, processors=procs, logprobs=want)
         else:
-            out_ids = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs)
+            res = self.generate_ids(ids_arr, mask, feats, max_new, processors=procs, logprobs=want)
+        return self._output(call, *(res if want is not None else (res, None)))
+
+    def _output(self, call: "C.Call", out_ids, lps=None, beam_scores=None):      # the new ids of every answer -> generate()'s return value
         texts = [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
-        if not opts.return_dict:
-            return texts
-        return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps, beam_scores)
+        return LPR.build_output(texts, [list(x) for x in out_ids], call.logprobs, lps, beam_scores) if call.logprobs.return_dict else texts
 
     @contextlib.contextmanager
     def _search_seq(self, row: List[int], vis: torch.Tensor, grammar: Optional[int], keep_hidden: bool = False):
@@ -779,51 +621,28 @@ class LLAVA_NEXT_VIDEO:
         referring, inference.py:178-182) and re-runs both vision towers every time; here the video is encoded once and the prompts
         are prefilled and decoded together.  Texts are identical to one generate() call per prompt (batch-invariant kernels) -- the logits
         processors included: each prompt gets its own (its min_length is lowered by its own embedding length, as its own reference call would).
-        return_dict_in_generate / output_scores / top_logprobs as in generate()."""
+        Modes greedy, sample and fan-out (call.resolve_call, entry "generate_shared"); return_dict_in_generate / output_scores / top_logprobs as in generate()."""
         if samples["spatial_pixel_values"].shape[0] != 1:
             raise ValueError("generate_shared takes the pixel tensors of one video")
-        if LP.resolve_guidance(generate_kwargs) is not None:
-            raise ValueError("generate_shared(): guidance_scale != 1 is not supported yet (generate() takes it)")
-        if beam_groups(generate_kwargs) is not None:
-            raise ValueError("generate_shared(): num_beam_groups > 1 (diverse beam search) is not supported (generate() takes it)")
-        if LP.resolve_contrastive(generate_kwargs) is not None:
-            raise ValueError("generate_shared(): contrastive search (penalty_alpha > 0 with top_k > 1) is not supported (generate() takes it)")
-        n_ret = num_return_sequences(generate_kwargs)
-        if n_ret > 1 and (generate_kwargs.get("num_beams", 1) or 1) > 1:
-            raise ValueError("generate_shared(): num_return_sequences > 1 is built for sampling (do_sample=True, num_beams=1); generate() returns the n best beams")
-        max_new = int(generate_kwargs.get("max_new_tokens", 2048))
-        ids = [self.tokenizer_image_token(t) for t in prompts]
-        pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
-        ids_arr, mask = P.left_pad_truncate(ids, pad_id, self.max_txt_len)
-        rows = [[int(t) for t, m in zip(ids_arr[i], mask[i]) if m] for i in range(len(prompts))]
+        call = self._resolve(generate_kwargs, "generate_shared", len(prompts))
+        ids_arr, mask = P.left_pad_truncate([self.tokenizer_image_token(t) for t in prompts], call.pad_id, self.max_txt_len)
+        rows = [_row(ids_arr, mask, i) for i in range(len(prompts))]
         n_vis = self._n_visual(samples)
-        opts = self._select_logprobs(generate_kwargs)
-        self._select_processors(generate_kwargs, LP.padded_embed_len(len(rows[0]), n_vis) if rows else 0)
-        self._select_tokens(generate_kwargs)
-        procs = [LP.resolve(generate_kwargs, getattr(self.tokenizer, "eos_token_id", None), LP.padded_embed_len(len(r), n_vis)) for r in rows]
-        rid = self._select_rules(dict(generate_kwargs, num_beams=1), max_new)    # token rules: every sequence allocated below starts with them
-        gid = None
-        try:
-            gid = self._select_grammar(dict(generate_kwargs, num_beams=1))       # ... and with the grammar
+        procs = [call.processors(LP.padded_embed_len(len(r), n_vis)) for r in rows]
+        max_new, want = call.max_new, call.want_logprobs
+        with self._settings(call, procs[0] if procs else call.processors(0)):       # rules and grammar: every sequence allocated below starts with them
             feats = self.encode_images(samples)
-            want = opts.top_n if opts.top_n >= 0 else None
             # num_return_sequences = n: every prompt's sequence is fanned out behind its own (extend-)prefill.  Every prompt stands for a generate() call of its own,
             # so each draws from the streams of prompt index 0: the n answers of a prompt equal generate(num_return_sequences=n) on that prompt alone
-            fan = (n_ret, self._sampling_dict(generate_kwargs)) if n_ret > 1 else None
+            fan = (call.n_return, call.seq_sampling) if call.mode is Mode.FANOUT else None
             res = self._generate_shared_prefix(rows, feats[0], max_new, procs, logprobs=want, fanout=fan)
             if res is None and fan is not None:
-                res = self.fanout_generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, n_ret, fan[1], processors=procs, logprobs=want,
+                res = self.fanout_generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, fan[0], fan[1], processors=procs, logprobs=want,
                                                prompt_index=[0] * len(prompts))
             elif res is None:                            # nothing worth sharing (one prompt, or the prompts part ways before 128 tokens)
                 res = self.generate_ids(ids_arr, mask, feats.expand(len(prompts), -1, -1), max_new, processors=procs, logprobs=want)
-        finally:
-            self._drop_grammar(gid)
-            self._drop_rules(rid)
-        out_ids, lps = res if want is not None else (res, None)
-        texts = [t.strip() for t in self.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
-        if not opts.return_dict:
-            return texts
-        return LPR.build_output(texts, [list(x) for x in out_ids], opts, lps)
+        return self._output(call, *(res if want is not None else (res, None)))
+
 
     def _shared_prefix(self, rows: Sequence[Sequence[int]], n_vis: int, lens: Sequence[int], limit: int) -> int:
         """THE shared-prefix rule of generate_shared and score: how many leading EMBEDDING rows the id rows `rows` (one image slot each, n_vis visual rows) have in
@@ -1004,8 +823,7 @@ class LLAVA_NEXT_VIDEO:
                 # logits come from a masked pad row; that term is dropped here (it trains nothing but the pad embedding)
                 print("WARNING: label on a masked (padding) position ignored")
                 self._warned_pad_label = True
-            row = [int(t) for t, m in zip(ids[b], mask[b]) if m]
-            emb = self.engine.splice(row, feats[b][:0] if is_text else feats[b])
+            emb = self.engine.splice(_row(ids, mask, b), feats[b][:0] if is_text else feats[b])
             assert emb.shape[0] == n
             s, c = self.engine.forward_loss(emb, ml[:n].tolist())
             total, count = total + s, count + c
@@ -1018,57 +836,25 @@ class LLAVA_NEXT_VIDEO:
         """Greedy / sampled ids of every row.  processors: one logits.Processors for all rows, a list with one per row, or None (the engine's
         default, set_logits_processors).  logprobs: None = the ids only; -1 .. 8 = every row's gvl_seq_set_logprobs setting, and the return value
         is (ids, lps) with lps[i] = (lp, top) of row i as Engine.seq_read_logprobs reads them back before the sequence is freed."""
-        eos = getattr(self.tokenizer, "eos_token_id", None)
         eng = self.engine
         opts = [LP.SeqOptions(p, logprobs) for p in (processors if isinstance(processors, (list, tuple)) else [processors] * ids_arr.shape[0])]
         if ids_arr.shape[0] == 1:
-            row = [int(t) for t, m in zip(ids_arr[0], mask[0]) if m]
-            got = eng.generate_ids(eng.splice(row, feats[0]), max_new, eos, processors=opts[0].processors, logprobs=logprobs)
+            got = eng.generate_ids(eng.splice(_row(ids_arr, mask, 0), feats[0]), max_new, getattr(self.tokenizer, "eos_token_id", None),
+                                   processors=opts[0].processors, logprobs=logprobs)
             return [got] if logprobs is None else ([got[0]], [got[1]])
         # bs > 1 (the reference left-pads the batch, llava_next_video.py:622-647): every sample keeps its own paged KV and its
-        # un-padded length -- identical maths to the masked left-padded batch.  Prefill runs over the packed rows of the batch
-        # (gvl_prefill_varlen) and the greedy decode of the whole batch runs together (gvl_decode_greedy_batch: one weight stream
+        # un-padded length -- identical maths to the masked left-padded batch.  Prefill runs over the packed rows of a group
+        # (gvl_prefill_varlen) and the greedy decode of the whole group runs together (gvl_decode_greedy_batch: one weight stream
         # per token for groups of up to 16 sequences)
-        # The KV pool bounds how many samples are resident at once: the batch is processed in as many groups as it takes.
-        from .lib import GvlError, ERR_OOM
-        out: List[List[int]] = []
-        lps = []
-        b, n = 0, ids_arr.shape[0]
-        while b < n:
-            seqs, embs = [], []
-            try:
-                while b + len(seqs) < n:
-                    i = b + len(seqs)
-                    row = [int(t) for t, m in zip(ids_arr[i], mask[i]) if m]
-                    emb = eng.splice(row, feats[i])
-                    try:
-                        seqs.append(eng.seq_alloc(min(emb.shape[0] + max_new, self.geo.max_seq)))
-                    except GvlError as e:
-                        if e.status == ERR_OOM and seqs:
-                            break                      # pool full: run what fits, the rest in the next group
-                        raise
-                    LP.apply_seq_options(eng, seqs[-1], opts[i])
-                    embs.append(emb)
-                eng.prefill_batch(seqs, embs)
-                got = eng.decode_greedy_batch(seqs, max_new, eos)
-                if logprobs is not None:
-                    lps += [LP.read_seq_logprobs(eng, s_, g, o) for s_, g, o in zip(seqs, got, opts[b:])]
-                out += got
-            finally:
-                for seq in seqs:
-                    eng.seq_free(seq)
-            b += len(seqs)
-        return out if logprobs is None else (out, lps)
 
+        def plan(i):
+            emb = eng.splice(_row(ids_arr, mask, i), feats[i])
 
-def _beam_impl(kw) -> str:
-    """generate()'s beam_impl: "host" (default) or "device"; "device" is beam search only."""
-    impl = kw.get("beam_impl", "host")
-    if impl not in ("host", "device"):
-        raise ValueError(f"beam_impl must be 'host' or 'device', not {impl!r}")
-    if impl == "device" and kw.get("do_sample", False) and kw.get("num_beams", 1) not in (1, None):
-        raise ValueError("beam_impl='device' is beam search (do_sample=False); beam-sample runs on the host path: its draws are torch's")
-    return impl
+            def begin(seqs):
+                LP.apply_seq_options(eng, seqs[0], opts[i])
+                return emb
+            return (min(emb.shape[0] + max_new, self.geo.max_seq),), begin
+        return self._decode_in_pool_groups(ids_arr.shape[0], plan, max_new, logprobs, launch=eng.prefill_batch)
 
 
 BASE_VOCAB = {"phi3.5": 32064, "llama3": 128256, "vicuna": 32000}     # tokenizer sizes before reset_embeddings [ext]

@@ -59,20 +59,75 @@ def test_resolve_contrastive_errors():
 
 # ---- 2. generate() on a stub engine ---------------------------------------------------------------------------------------------------------
 class _StubEngine:
-    """Records every call; the few that generate() reads a value from return one."""
-    def __init__(self):
+    """Records every call; the ones that generate(), generate_shared() and score() read a value from return one.  Sequence ids are the lowest free slot from 5 up, so
+    an alloc / free pair at a time always sees 5 and sequences that live together are told apart.  logits=True: prefills and teacher-forced steps hand back real
+    (deterministic) rows, for the searches that compute on them on the host.  pool=n: the KV pool holds n sequences, one more is refused with ERR_OOM."""
+    def __init__(self, logits=False, vocab=640, pool=None):
         self.calls = []
         self.device = "cpu"
+        self._logits, self._vocab, self._live, self._pool = logits, vocab, set(), pool
+
+    def _need(self, n):
+        if self._pool is not None and len(self._live) + n > self._pool:
+            from grounded_video_llm_amd import lib as L
+            e = L.GvlError("gvl_seq_alloc failed (status %d): the KV pool is exhausted" % L.ERR_OOM)
+            e.status = L.ERR_OOM
+            raise e
+
+    def _alloc(self):
+        self._need(1)
+        sid = next(i for i in range(5, 4096) if i not in self._live)
+        self._live.add(sid)
+        return sid
+
+    def _row(self, tok):
+        return torch.sin(torch.arange(self._vocab, dtype=torch.float32) * (0.37 * (int(tok) % 97 + 1)))
 
     def __getattr__(self, name):
         def call(*a, **kw):
             self.calls.append((name, a, kw))
             if name == "splice":
-                return torch.zeros((a[0].__len__() + 3, 8))
-            if name == "seq_alloc":
-                return 5
+                return torch.zeros((len(a[0]) - 1 + a[1].shape[0], 8))
+            if name == "embed_ids":
+                return torch.zeros((len(a[0]), 8))
+            if name in ("seq_alloc", "seq_fork", "seq_clone"):
+                return self._alloc()
+            if name == "seq_fanout":
+                self._need(a[1])                             # all or nothing, as gvl_seq_fanout is
+                return [self._alloc() for _ in range(a[1])]
+            if name == "seq_free":
+                self._live.discard(a[0])
+                return None
+            if name in ("rules_create", "grammar_create"):
+                return 7 if name == "rules_create" else 9
+            if name == "decode_group_info":
+                return dict(max_group=16, any_size=1)
             if name == "prefill":
-                return "FIRST" if kw.get("want_logits") else None
+                if not kw.get("want_logits"):
+                    return None
+                return self._row(0) if self._logits else "FIRST"
+            if name == "prefill_extend_batch":
+                return torch.stack([self._row(0) for _ in a[0]]) if kw.get("want_logits") else None
+            if name == "decode_step_logits":
+                return self._row(a[1])
+            if name == "decode_step_logits_batch":
+                return torch.stack([self._row(t) for t in a[1]])
+            if name == "op_logits_process":
+                return a[0]
+            if name in ("beam_search", "group_beam_search"):      # (..., with_scores, num_return=n) are the last two arguments of both
+                res = ([11, 2], -0.25, [-0.125, -0.125]) if a[-1] else [11, 2]
+                return [res] * kw["num_return"] if kw.get("num_return", 1) > 1 else res
+            if name == "seq_read_logprobs":
+                n = a[2]
+                return [-0.5] * n, ([[(1, -0.5)] for _ in range(n)] if kw.get("top") else None)
+            if name == "score_extend_batch":
+                n = sum(1 for ids in a[2] for t in ids if t != -100)
+                top = a[3] if len(a) > 3 else kw.get("top_n", 0)
+                return (torch.full((n,), -0.5), torch.zeros((n,), dtype=torch.int32), torch.ones((n, 8), dtype=torch.int32) if top else None,
+                        torch.full((n, 8), -0.5) if top else None)
+            if name == "generate_ids":
+                lp = kw.get("logprobs")
+                return [1, 2] if lp is None else ([1, 2], ([-0.5, -0.5], [[(1, -0.5)], [(2, -0.5)]] if lp > 0 else None))
             if name == "contrastive_search":
                 ids = [11, 12, 2]
                 tr = dict(ids=[[11, 7, 8, 9], [6, 12, 8, 9], [2, 7, 8, 9]], p=[[.5, .2, .1, .1], [.4, .3, .1, .1], [.9, .05, .01, .01]],
@@ -93,12 +148,13 @@ class _Tok:
         return [" ".join(str(i) for i in row) for row in ids]
 
 
-def _stub_model():
+def _stub_model(logits=False, n_visual=6, pool=None):
     m = M.LLAVA_NEXT_VIDEO.__new__(M.LLAVA_NEXT_VIDEO)
-    m.engine, m.geo, m.tokenizer, m.max_txt_len = _StubEngine(), SimpleNamespace(vocab=640, max_seq=4096), _Tok(), 64
+    m.engine, m.tokenizer, m.max_txt_len = _StubEngine(logits, pool=pool), _Tok(), 64
+    m.geo = SimpleNamespace(vocab=640, max_seq=4096, max_prefill=4096, rope_long=None, rope_orig_max_pos=0)
     m.tokenizer_image_token = lambda text: [1, 20, -200, 21, 22]
-    m.encode_images = lambda samples: [torch.zeros((6, 8)) for _ in samples["prompts"]]
-    m._n_visual = lambda samples: 6
+    m.encode_images = lambda samples: torch.zeros((len(samples.get("prompts", "v")), n_visual, 8))     # one video when the call names no prompts of its own
+    m._n_visual = lambda samples: n_visual
     return m
 
 

@@ -547,42 +547,26 @@ def test_generate_kwargs_map_to_hf_token_selection_semantics():
     """generate(**kw) -> token selection (the reference forwards do_sample / num_beams / temperature / top_p to HF generate,
     inference.py:170-176 -> models/llava_next_video.py:655-661): greedy unless do_sample; HF's defaults temperature 1.0 and top_k 50 when
     not given; HF's argument checks; an unseeded call takes its seed from torch's CPU generator (so torch.manual_seed governs it)."""
-    from grounded_video_llm_amd.model import LLAVA_NEXT_VIDEO
+    from grounded_video_llm_amd.call import resolve_call
 
-    class Rec:
-        def __init__(self):
-            self.calls = []
-
-        def set_sampling(self, *a, **k):
-            self.calls.append((a, k))
-
-    class Dummy:
-        pass
-
-    d = Dummy(); d.engine = Rec()
-    sel = lambda **kw: LLAVA_NEXT_VIDEO._select_tokens(d, kw)
-    sel(do_sample=False, num_beams=1, temperature=0.2, top_p=None)
-    assert d.engine.calls[-1] == ((False,), {})
-    sel()                                                            # no kwargs at all: greedy
-    assert d.engine.calls[-1] == ((False,), {})
-    sel(do_sample=True, temperature=0.2, top_p=None, seed=7)         # the reference CLI's defaults
-    assert d.engine.calls[-1] == ((True, 0.2, 50, None, 7), {})
-    sel(do_sample=True, seed=1)
-    assert d.engine.calls[-1] == ((True, 1.0, 50, None, 1), {})
-    sel(do_sample=True, temperature=0.7, top_k=None, top_p=0.9, seed=3)
-    assert d.engine.calls[-1] == ((True, 0.7, 0, 0.9, 3), {})
-    torch.manual_seed(123); sel(do_sample=True); s1 = d.engine.calls[-1][0][4]
-    torch.manual_seed(123); sel(do_sample=True); s2 = d.engine.calls[-1][0][4]
-    sel(do_sample=True); s3 = d.engine.calls[-1][0][4]
+    def sel(**kw):
+        c = resolve_call(kw, entry="generate", n_samples=1, eos_id=2, pad_id=0, vocab=640, draw_seed=lambda: int(torch.randint(0, 2 ** 62, (1,)).item()))
+        return c.sampling_args, c.warpers                  # Engine.set_sampling's positional and keyword arguments
+    assert sel(do_sample=False, num_beams=1, temperature=0.2, top_p=None) == ((False,), {})
+    assert sel() == ((False,), {})                                   # no kwargs at all: greedy
+    assert sel(do_sample=True, temperature=0.2, top_p=None, seed=7) == ((True, 0.2, 50, None, 7), {})         # the reference CLI's defaults
+    assert sel(do_sample=True, seed=1) == ((True, 1.0, 50, None, 1), {})
+    assert sel(do_sample=True, temperature=0.7, top_k=None, top_p=0.9, seed=3) == ((True, 0.7, 0, 0.9, 3), {})
+    torch.manual_seed(123); s1 = sel(do_sample=True)[0][4]
+    torch.manual_seed(123); s2 = sel(do_sample=True)[0][4]
+    s3 = sel(do_sample=True)[0][4]
     assert s1 == s2 and s3 != s1 and 0 <= s1 < 2 ** 62
     for bad in (dict(do_sample=True, temperature=0.0), dict(do_sample=True, temperature=-1.0), dict(do_sample=True, top_p=0.0),
                 dict(do_sample=True, top_p=1.5)):
         with pytest.raises(ValueError):
             sel(**bad)
-    sel(do_sample=False, num_beams=4)                   # beam search: greedy token selection inside the steps, the beams live in generate()
-    assert d.engine.calls[-1] == ((False,), {})
-    sel(do_sample=True, num_beams=4)                    # beam-sample: the draw happens in beam.py on the steps' logits; the device sampler stays off
-    assert d.engine.calls[-1] == ((False,), {})
+    assert sel(do_sample=False, num_beams=4) == ((False,), {})       # beam search: greedy token selection inside the steps, the beams live in generate()
+    assert sel(do_sample=True, num_beams=4) == ((False,), {})        # beam-sample: the draw happens in beam.py on the steps' logits; the device sampler stays off
 
 
 def test_beam_sample_warpers_and_draw():
