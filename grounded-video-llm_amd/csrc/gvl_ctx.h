@@ -47,8 +47,8 @@ struct Seq : SeqCore {
   // null until the ctx allocated them (gvl_ctx::d_seq_lp / d_seq_top_*)
   float* d_lp = nullptr; int* d_top_ids = nullptr; float* d_top_lp = nullptr;
   // hidden bank (gvl_seq_keep_hidden): ONE device allocation of bank_cap rows -- [bank_cap][hidden] bf16 post-final-norm hidden states, then [bank_cap] fp32 inverse
-  // norms (bank_inv points into it); bank_rows rows are written, row j = position j.  Owned by the slot: gvl_ctx::close frees it
-  bf16_t* bank = nullptr; float* bank_inv = nullptr; int bank_cap = 0, bank_rows = 0;
+  // norms (bank_inv points into it); SeqCore's bank_cap / bank_rows count them (bank_cap > 0 exactly while `bank` is set).  Owned by the slot: gvl_ctx::close frees it
+  bf16_t* bank = nullptr; float* bank_inv = nullptr;
 };
 
 struct ProfRec { int cat; hipEvent_t e0, e1; double work; };

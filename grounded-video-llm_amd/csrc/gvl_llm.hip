@@ -62,6 +62,11 @@ int step_rows(gvl_ctx* ctx, Seq* const* named, int n, Seq** rows) {
   for (int b = 0; b < n; ++b) if (named[b]->follow >= 0) rows[k++] = &ctx->seqs[named[b]->follow];
   return k;
 }
+int named_parts(gvl_ctx* ctx, Seq* const* named, int n, int* sizes) {
+  int rows[gvl_ctx::kMaxSeqs];
+  for (int i = 0; i < n; ++i) rows[i] = named[i]->follow >= 0 ? 2 : 1;
+  return decode_parts_paired(ctx->decode_mfma, rows, n, sizes);
+}
 static int pick_tokens_rows(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st) {
   bool any_proc = false;
   for (int b = 0; b < am.batch; ++b) any_proc = any_proc || sqs[b]->sel.proc.on() || sqs[b]->sel.rules >= 0 || sqs[b]->sel.grammar >= 0;
@@ -524,9 +529,8 @@ int decode_group(gvl_ctx* ctx, Seq* const* sqs, int B, int max_new, int eos_id, 
     if (n_now != n_live || memcmp(now, live, sizeof(Seq*) * n_now) != 0) {
       for (auto& p : parts) retired.push_back(std::move(p.sg));
       parts.clear();
-      int sizes[GVL_MAX_DECODE_BATCH], rows[GVL_MAX_DECODE_BATCH];   // a leader takes two rows of its part: its follower's comes with it (decode_parts_paired never splits them)
-      for (int b = 0; b < n_now; ++b) rows[b] = now[b]->follow >= 0 ? 2 : 1;
-      for (int k = 0, o = 0, nk = decode_parts_paired(ctx->decode_mfma, rows, n_now, sizes); k < nk; ++k) {
+      int sizes[GVL_MAX_DECODE_BATCH];   // a leader takes two rows of its part: its follower's comes with it
+      for (int k = 0, o = 0, nk = named_parts(ctx, now, n_now, sizes); k < nk; ++k) {
         Part p; p.n = step_rows(ctx, now + o, sizes[k], p.m); p.sg.reset(new StepGraph());
         o += sizes[k]; parts.push_back(std::move(p));
       }

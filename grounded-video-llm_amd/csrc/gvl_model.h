@@ -1,8 +1,11 @@
 // gvl_model.h -- what the host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the sequence / prefill / decode
 // and operator entry points of include/gvl.h), gvl_select.hip (the token-selection entry points), gvl_vision.hip (the towers' launch sequences) and
 // gvl_llm.hip (prefill, the decode step -- planned in gvl_decode_plan.h --, the decode loop).  Internal: nothing here is part of the ABI.
+// The sequence entries are wrappers: REQUIRE_READY, their own pointer and count checks, ONE admit() call (the table of gvl_admit.h decides which sequences the entry
+// takes and says why not), then the work.
 #pragma once
 #include "gvl_ctx.h"
+#include "gvl_admit.h"      // which sequences an entry takes: the admission table and its one function (host-only, tested on the CPU)
 #include <functional>
 #include "gvl_decode_plan.h"   // the decode path's predicates, batch admission and grouping, and decode_step's launch plan (host-only, tested on the CPU)
 
@@ -12,29 +15,19 @@ inline int fail(gvl_ctx* c, int code, const std::string& msg) { return gvl_fail(
 
 #define REQUIRE_READY(cond, what) do { if (!ctx) return GVL_ERR_ARG; if (!ctx->finalized || !(cond)) return fail(ctx, GVL_ERR_STATE, what ": weights not finalized or tower not configured"); } while (0)
 
-// a SeqStatus of the sequence table (gvl_seq_table.h) as the result of entry point `fn`: 0, or the status's error
-inline int seq_fail(gvl_ctx* c, const char* fn, int status) {
-  if (status >= 0) return 0;
-  static const struct { int code; const char* text; } e[] = {   // indexed by -1 - status: SEQ_BAD .. SEQ_PAIRED
-    {GVL_ERR_ARG, "bad seq"}, {GVL_ERR_ARG, "duplicate seq"}, {GVL_ERR_OOM, "KV pages exhausted"}, {GVL_ERR_OOM, "too many live sequences"}, {GVL_ERR_ARG, "no such rule set"},
-    {GVL_ERR_STATE, "the rule set is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_token_rules(-1) first)"},
-    {GVL_ERR_ARG, "too many live rule sets (limit 1024)"}, {GVL_ERR_ARG, "no such grammar"},
-    {GVL_ERR_STATE, "the grammar is still referenced by a live sequence or is the default (gvl_seq_free / gvl_set_grammar(-1) first)"},
-    {GVL_ERR_ARG, "too many live grammars (limit 64)"},
-    {GVL_ERR_STATE, "the sequence follows a guided leader (gvl_seq_set_guidance): free or unbind the leader first"},
-    {GVL_ERR_STATE, "the sequence must be freshly prefilled (exactly the one token its own prefill selected)"},
-    {GVL_ERR_STATE, "the sequence is a member of a guided pair (gvl_seq_set_guidance)"}};
-  const auto& x = e[status >= SEQ_PAIRED ? -1 - status : 0];
-  return fail(c, x.code, std::string(fn) + ": " + x.text);
-}
-
-// Guided pairs (gvl_seq_set_guidance): entry point `fn` cannot take sequence `id` -- a bound follower always (it is stepped as its leader's extra row and nowhere else),
-// a leader too where `leader_too` (entries that would copy one member or move it without the other).  0, or GVL_ERR_STATE with nothing changed.
-inline int pair_refuse(gvl_ctx* c, const char* fn, int id, bool leader_too) {
-  const Seq* s = c->lookup(id);
-  if (s && s->lead >= 0) return fail(c, GVL_ERR_STATE, std::string(fn) + ": sequence " + std::to_string(id) + " follows guided leader " + std::to_string(s->lead) + "; name the leader");
-  if (s && leader_too && s->follow >= 0) return fail(c, GVL_ERR_STATE, std::string(fn) + ": sequence " + std::to_string(id) + " leads a guided pair (gvl_seq_set_guidance(seq, -1, ...) unbinds)");
-  return 0;
+// Which sequences an entry takes is decided in gvl_admit.h (one table, one function, tested on the CPU); these turn its verdicts into an entry's result: 0, or the
+// status with the message as gvl_last_error.  Nothing is built on the admitted path.
+static_assert(gvl_admit::ERR_ARG == GVL_ERR_ARG && gvl_admit::ERR_STATE == GVL_ERR_STATE && gvl_admit::ERR_OOM == GVL_ERR_OOM, "gvl_admit.h restates include/gvl.h's codes");
+inline int refuse(gvl_ctx* c, const gvl_admit::Verdict& v) { return v.status ? fail(c, v.status, v.message) : 0; }
+// a SeqStatus of the sequence table (gvl_seq_table.h) as the result of entry point `fn`
+inline int seq_fail(gvl_ctx* c, const char* fn, int status) { return status >= 0 ? 0 : refuse(c, gvl_admit::seq_refusal(fn, status)); }
+// entry `fn` cannot take sequence `id`: a bound follower always, a guided leader too where `leader_too`; a keep-hidden sequence (the entry is not taught the bank)
+inline int pair_refuse(gvl_ctx* c, const char* fn, int id, bool leader_too) { return refuse(c, gvl_admit::pair_refusal(c->lookup(id), fn, id, leader_too)); }
+inline int bank_refuse(gvl_ctx* c, const char* fn, int id) { return refuse(c, gvl_admit::bank_refusal(c->lookup(id), fn, id)); }
+// the members of a call of entry `e` (nums: one number per member `stride` apart, stride 0: one for all); fn: the searches' own name
+inline int admit(gvl_ctx* c, gvl_admit::Entry e, const int* ids, int n, const int* nums, int stride, const char* fn = nullptr) {
+  const gvl_admit::Limits lim{c->cfg.max_prefill, c->cfg.max_seq, c->outlist_cap, c->cfg.vocab};
+  return refuse(c, gvl_admit::admit(*c, e, ids, n, nums, stride, lim, fn));
 }
 // the log-probability lists of slot `id` (null while the ctx has not allocated them)
 inline void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
@@ -104,17 +97,14 @@ int clip_encode(gvl_ctx* ctx, const float* px, int n, float* out, hipStream_t st
 int iv2_encode(gvl_ctx* ctx, const float* px, int n, bf16_t* out, hipStream_t st);
 int build_visual(gvl_ctx* ctx, const float* clip_feats, const bf16_t* iv2_feats, int n, bf16_t* visual, hipStream_t st);
 
-// gvl_model.hip: gvl_seq_clone.  carry_generated: the clone also takes the source's generated ids, their count and the id to feed next (what gvl_seq_clone does for a
-// source with a grammar); false: its history starts empty (gvl_beam_search's beams, whose histories the search keeps itself)
-// carry_bank: the clone of a keep-hidden source gets its own bank with a copy of the source's rows (gvl_seq_clone); false: a plain sequence (gvl_contrastive_search's
-// candidates, whose rows the search ranks itself)
-int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated, bool carry_bank = false);
+// gvl_model.hip: gvl_seq_clone.  carry: the clone of a source with a grammar also takes the source's generated ids, their count and the id to feed next, and the clone of a
+// keep-hidden source gets its own bank with a copy of the source's rows (gvl_seq_clone); false: a plain sequence whose history starts empty (the searches' clones: they
+// keep the histories and rank the rows themselves)
+int seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry);
 // n plain clones at once (gvl_contrastive_search's candidates): all or nothing, one launch for the n partial-page copies, one for the counters; dst_seqs [n]
 int seq_clone_many(gvl_ctx* ctx, int src_seq, int max_tokens, int n, int* dst_seqs, hipStream_t stream);
-// hidden bank (gvl_seq_keep_hidden; gvl_ctx.h Seq::bank).  bank_refuse: entry `fn` is not taught the bank -- GVL_ERR_STATE for a keep-hidden sequence, nothing changed.
-// bank_alloc: one allocation for `cap` rows, all or nothing.  bank_append (gvl_contrastive.hip): n residual rows x (ldx elements apart) -> final RMSNorm -> bank rows
+// hidden bank (gvl_seq_keep_hidden; gvl_ctx.h Seq::bank).  bank_alloc: one allocation for `cap` rows, all or nothing.  bank_append (gvl_contrastive.hip): n residual rows x (ldx elements apart) -> final RMSNorm -> bank rows
 // [bank_rows, bank_rows + n) and their inverse norms; bank_rows += n
-int bank_refuse(gvl_ctx* c, const char* fn, int id);
 int bank_alloc(gvl_ctx* ctx, Seq& s, int cap);
 int bank_append(gvl_ctx* ctx, Seq& s, const bf16_t* x, int ldx, int n, hipStream_t st);
 
@@ -179,6 +169,9 @@ int pick_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st, c
 int select_tokens(gvl_ctx* ctx, ArgmaxArgs& am, Seq* const* sqs, hipStream_t st);
 // the rows of one step for `n` named sequences (plain ones and leaders): rows[] = the named ones in order, then the leaders' followers in order; returns how many
 int step_rows(gvl_ctx* ctx, Seq* const* named, int n, Seq** rows);
+// the parts one step of `n` named sequences is cut into -> how many, sizes[k] named sequences each: groups of up to 16 rows (VALU fallback: 4, 2, 1), one weight stream
+// per step per part.  A guided leader counts two rows: its follower is stepped with it and never split from it (decode_parts_paired; without pairs the cut is decode_parts')
+int named_parts(gvl_ctx* ctx, Seq* const* named, int n, int* sizes);
 // one group of 1 .. GVL_MAX_PREFILL_BATCH sequences: plans its launches (prefill_plan, gvl_prefill_plan.h -- it refuses before the first launch), then walks the plan
 int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embeds, const int* lens, hipStream_t st, const LossReq* loss = nullptr, const int* pos0s = nullptr,
                 const ScoreReq* score = nullptr, bool keep_hidden = false);   // keep_hidden: one keep-hidden member -- no last-layer tail, every row joins its bank; pos0s: tokens each sequence already holds (null = none); score: rows of the group to score on the way (not with loss)

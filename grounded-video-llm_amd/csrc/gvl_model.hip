@@ -514,10 +514,9 @@ int gvl_seq_fork(gvl_ctx* ctx, int src_seq, int n_tokens, int max_tokens, int* d
 
 int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill");
-  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_prefill", SEQ_BAD);
+  if (!embeds) return fail(ctx, GVL_ERR_ARG, "gvl_prefill: bad length");
+  if (const int rc = admit(ctx, gvl_admit::PREFILL, &seq_id, 1, &S, 0)) return rc;
   Seq& sq = ctx->seqs[seq_id];
-  if (!embeds || S <= 0 || S > sq.max_tokens || S > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill: bad length");
-  if (sq.pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_prefill: sequence already holds tokens");
   hipStream_t st = (hipStream_t)stream;
   Seq* one[1] = {&sq}; const bf16_t* e1[1] = {embeds};
   int rc = llm_prefill(ctx, one, 1, e1, &S, st, nullptr, nullptr, nullptr, sq.bank != nullptr);   // a keep-hidden sequence: the bank takes one row per prompt row
@@ -529,8 +528,25 @@ int gvl_prefill(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, float* 
 int gvl_seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, void* stream) {
   // A source with a grammar hands its answer so far to the clone: the mask is a function of the generated ids, so without them the clone's walk would start over
   // mid-answer.  Without a grammar a clone's history starts empty, as ever.
-  Seq* src = ctx ? ctx->lookup(src_seq) : nullptr;
-  return seq_clone(ctx, src_seq, max_tokens, dst_seq, (hipStream_t)stream, src && src->sel.grammar >= 0, src && src->bank);
+  return seq_clone(ctx, src_seq, max_tokens, dst_seq, (hipStream_t)stream, true);
+}
+
+// The device side of n new copies of `src_seq` at its length `pos` (gvl_seq_fanout's siblings, seq_clone_many's clones; ids[] from SeqTable::open_many): slots bound, the
+// block tables up -- one launch each, by value, on the call's stream: ordered behind the source's pending work there --, then ONE launch for the n private copies of the
+// partial last page (all layers, K and V^T; none when pos ends on a page boundary).  fa: the copies' position and count pointers, for the caller's own launch behind
+static int bind_copies(gvl_ctx* ctx, int src_seq, int pos, const int* ids, int n, FanoutArgs& fa, Seq** sqs, hipStream_t st) {
+  memset(&fa, 0, sizeof(fa)); fa.n = n;
+  for (int i = 0; i < n; ++i) {                           // after the last open(): `seqs` no longer moves
+    Seq& s = ctx->seqs[ids[i]];
+    bind_slot(ctx, s, ids[i]);
+    sqs[i] = &s; fa.pos[i] = s.d_pos; fa.ngen[i] = s.d_ngen;
+    if (pos & 63) fa.dst_page[i] = s.pages[pos >> 6];
+  }
+  for (int i = 0; i < n; ++i) { const int rc = upload_table(ctx, *sqs[i], st); if (rc) return rc; }
+  if (pos & 63)
+    RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_fanout(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers, ctx->kv_total_pages,
+                                                     ctx->seqs[src_seq].pages[pos >> 6], fa, st));
+  return 0;
 }
 
 // n_new siblings of a freshly prefilled sequence: n answers to one prompt from ONE prefill.  The table operation opens all of them or none (SeqTable::fanout); behind it
@@ -554,18 +570,8 @@ int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const u
   int ids[GVL_MAX_DECODE_BATCH];
   { const int rc = ctx->fanout(src_seq, n_new, max_tokens, followed, streams, ids); if (rc < 0) return seq_fail(ctx, "gvl_seq_fanout", rc); }
   hipStream_t st = (hipStream_t)stream;
-  Seq* sqs[GVL_MAX_DECODE_BATCH];
-  FanoutArgs fa; memset(&fa, 0, sizeof(fa)); fa.n = n_new;
-  for (int i = 0; i < n_new; ++i) {
-    Seq& s = ctx->seqs[ids[i]];
-    bind_slot(ctx, s, ids[i]);
-    sqs[i] = &s; fa.pos[i] = s.d_pos; fa.ngen[i] = s.d_ngen;
-    if (pos & 63) fa.dst_page[i] = s.pages[pos >> 6];
-  }
-  for (int i = 0; i < n_new; ++i) { const int rc = upload_table(ctx, *sqs[i], st); if (rc) return rc; }   // by value, on the call's stream: ordered behind the source's prefill there
-  if (pos & 63)                                       // the partial last page is private: the source's into every sibling's (all layers, K and V^T), one launch
-    RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_fanout(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers, ctx->kv_total_pages,
-                                                     ctx->seqs[src_seq].pages[pos >> 6], fa, st));
+  Seq* sqs[GVL_MAX_DECODE_BATCH]; FanoutArgs fa;
+  if (const int rc = bind_copies(ctx, src_seq, pos, ids, n_new, fa, sqs, st)) return rc;
   RUN(GVL_PROF_OTHER, 0, gvl_launch_fanout_rows(first_logits, ctx->d_logits, V, pos, fa, st));
   ArgmaxArgs am; memset(&am, 0, sizeof(am)); am.logits = ctx->d_logits; am.n = V; am.batch = n_new;
   for (int i = 0; i < n_new; ++i) { am.tok_ptrs[i] = sqs[i]->d_tok; am.out_lists[i] = sqs[i]->d_out; am.ngen_ptrs[i] = sqs[i]->d_ngen; }
@@ -575,12 +581,6 @@ int gvl_seq_fanout(gvl_ctx* ctx, int src_seq, int n_new, int max_tokens, const u
 }
 }  // extern "C"
 
-// Entries that are not taught the hidden bank refuse a keep-hidden sequence: its bank would fall out of step with its position
-int gvlm::bank_refuse(gvl_ctx* c, const char* fn, int id) {
-  const Seq* s = c->lookup(id);
-  if (s && s->bank) return fail(c, GVL_ERR_STATE, std::string(fn) + ": sequence " + std::to_string(id) + " keeps its hidden states (gvl_seq_keep_hidden); this entry does not fill the bank");
-  return 0;
-}
 // the bank of `s`: rows for `cap` positions, all or nothing
 int gvlm::bank_alloc(gvl_ctx* ctx, Seq& s, int cap) {
   const int Hd = ctx->cfg.hidden;
@@ -593,14 +593,12 @@ int gvlm::bank_alloc(gvl_ctx* ctx, Seq& s, int cap) {
   return 0;
 }
 
-int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry_generated, bool carry_bank) {
+int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hipStream_t stream, bool carry) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
-  if (!dst_seq || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
-  if (const int rc = pair_refuse(ctx, "gvl_seq_clone", src_seq, true)) return rc;
+  if (!dst_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
+  if (const int rc = admit(ctx, carry ? gvl_admit::SEQ_CLONE : gvl_admit::SEQ_CLONE_PLAIN, &src_seq, 1, &max_tokens, 0)) return rc;
   const int pos = ctx->seqs[src_seq].pos;
-  if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
-  if (carry_generated && ctx->seqs[src_seq].n_gen > ctx->outlist_cap) return fail(ctx, GVL_ERR_STATE, "gvl_seq_clone: the source generated more ids than an output list holds");
-  if (carry_bank && ctx->seqs[src_seq].bank_rows != pos) return fail(ctx, GVL_ERR_STATE, "gvl_seq_clone: the source's hidden bank is not in step with its position");
+  const bool carry_generated = carry && ctx->seqs[src_seq].sel.grammar >= 0, carry_bank = carry && ctx->seqs[src_seq].bank;
   const int id = ctx->open(max_tokens, src_seq, pos);
   if (id < 0) return seq_fail(ctx, "gvl_seq_clone", id);
   Seq& s = ctx->seqs[id];
@@ -642,48 +640,44 @@ int gvlm::seq_clone(gvl_ctx* ctx, int src_seq, int max_tokens, int* dst_seq, hip
 __global__ void clone_counters_kernel(const FanoutArgs a, int pos) { if ((int)threadIdx.x < a.n) { *a.pos[threadIdx.x] = pos; *a.ngen[threadIdx.x] = 0; } }
 int gvlm::seq_clone_many(gvl_ctx* ctx, int src_seq, int max_tokens, int n, int* dst_seqs, hipStream_t st) {
   REQUIRE_READY(ctx->has_llm, "gvl_seq_clone");
-  if (!dst_seqs || n < 1 || n > GVL_MAX_DECODE_BATCH || !ctx->lookup(src_seq)) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
-  if (const int rc = pair_refuse(ctx, "gvl_seq_clone", src_seq, true)) return rc;
+  if (!dst_seqs || n < 1 || n > GVL_MAX_DECODE_BATCH) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: bad arguments");
+  if (const int rc = admit(ctx, gvl_admit::SEQ_CLONE_PLAIN, &src_seq, 1, &max_tokens, 0)) return rc;
+  if (const int rc = ctx->open_many(src_seq, n, max_tokens, dst_seqs)) return seq_fail(ctx, "gvl_seq_clone", rc);
   const int pos = ctx->seqs[src_seq].pos;
-  if (pos <= 0 || max_tokens <= pos || max_tokens > ctx->cfg.max_seq) return fail(ctx, GVL_ERR_ARG, "gvl_seq_clone: the source must hold tokens and max_tokens must exceed them (and fit cfg.max_seq)");
-  const int own_pages = (max_tokens + 63) / 64 - (pos >> 6);
-  if ((long long)ctx->free_pages.size() < (long long)n * own_pages) return seq_fail(ctx, "gvl_seq_clone", SEQ_NO_PAGES);
-  int slots = ctx->max_seqs - (int)ctx->seqs.size();
-  for (const Seq& q : ctx->seqs) slots += !q.used;
-  if (slots < n) return seq_fail(ctx, "gvl_seq_clone", SEQ_TOO_MANY);
-  FanoutArgs fa; memset(&fa, 0, sizeof(fa)); fa.n = n;
-  struct Undo { gvl_ctx* c; const int* ids; int n; bool keep; ~Undo() { if (!keep) for (int i = 0; i < n; ++i) c->close(ids[i]); } } undo{ctx, dst_seqs, 0, false};
-  for (int i = 0; i < n; ++i) {
-    const int id = ctx->open(max_tokens, src_seq, pos);              // cannot fail: pages and slots were counted above
-    if (id < 0) return seq_fail(ctx, "gvl_seq_clone", id);
-    dst_seqs[i] = id; undo.n = i + 1;
+  Seq* sqs[GVL_MAX_DECODE_BATCH]; FanoutArgs fa;
+  int rc = bind_copies(ctx, src_seq, pos, dst_seqs, n, fa, sqs, st);
+  if (!rc) {
+    hipLaunchKernelGGL(clone_counters_kernel, dim3(1), dim3(64), 0, st, fa, pos);
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, GVL_ERR_HIP, "gvl_seq_clone: launch failed");
   }
-  for (int i = 0; i < n; ++i) {                                       // after the last open(): `seqs` no longer moves
-    Seq& s = ctx->seqs[dst_seqs[i]];
-    bind_slot(ctx, s, dst_seqs[i]);
-    s.n_gen = 0;
-    fa.pos[i] = s.d_pos; fa.ngen[i] = s.d_ngen;
-    if (pos & 63) fa.dst_page[i] = s.pages[pos >> 6];
-    if (const int rc = upload_table(ctx, s, st)) return rc;
-  }
-  if (pos & 63)
-    RUN(GVL_PROF_OTHER, 0, gvl_launch_kv_page_fanout(ctx->kpool, ctx->vpool, ctx->layer_stride, (size_t)ctx->cfg.kv_heads * 64 * ctx->l_D, ctx->cfg.layers, ctx->kv_total_pages,
-                                                     ctx->seqs[src_seq].pages[pos >> 6], fa, st));
-  hipLaunchKernelGGL(clone_counters_kernel, dim3(1), dim3(64), 0, st, fa, pos);
-  if (hipGetLastError() != hipSuccess) return fail(ctx, GVL_ERR_HIP, "gvl_seq_clone: launch failed");
-  undo.keep = true;
+  if (rc) for (int i = 0; i < n; ++i) ctx->close(dst_seqs[i]);   // all or nothing on a failed launch too
+  return rc;
+}
+// The ragged prefill entries: every member's operands are there (`what`: the text behind "bad "; the same text as for a member that is no live sequence), and the walk
+// over their groups -- up to `cap` members in call order, as many as the prefill workspace (cfg.max_prefill rows in total) allows; run(first member, B, sqs, embeds, pos0)
+static int members_present(gvl_ctx* ctx, const char* fn, const char* what, int n_seqs, const void* const* operands, const void* const* operands2 = nullptr) {
+  for (int i = 0; i < n_seqs; ++i) if (!operands[i] || (operands2 && !operands2[i])) return fail(ctx, GVL_ERR_ARG, std::string(fn) + ": bad " + what);
   return 0;
 }
+template <class Run>
+static int prefill_groups(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds, const int* lens, int cap, Run&& run) {
+  for (int i = 0; i < n_seqs;) {
+    const int B = prefill_group_size(lens + i, n_seqs - i, cap, ctx->cfg.max_prefill);
+    Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH]; int pos0[GVL_MAX_PREFILL_BATCH];
+    for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds[i + b]; pos0[b] = sqs[b]->pos; }
+    if (const int rc = run(i, B, sqs, es, pos0)) return rc;
+    i += B;
+  }
+  return 0;
+}
+
 extern "C" {
 
 int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_new, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend");
-  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_prefill_extend", SEQ_BAD);
-  if (const int rc = pair_refuse(ctx, "gvl_prefill_extend", seq_id, false)) return rc;
-  if (const int rc = bank_refuse(ctx, "gvl_prefill_extend", seq_id)) return rc;
+  if (!embeds) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad length");
+  if (const int rc = admit(ctx, gvl_admit::PREFILL_EXTEND, &seq_id, 1, &n_new, 0)) return rc;
   Seq& sq = ctx->seqs[seq_id];
-  if (sq.pos <= 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend: the sequence must hold a prefix of whole pages (gvl_seq_fork)");
-  if (!embeds || n_new <= 0 || sq.pos + n_new > sq.max_tokens || n_new > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend: bad length");
   hipStream_t st = (hipStream_t)stream;
   Seq* one[1] = {&sq}; const bf16_t* e1[1] = {embeds};
   const int pos0 = sq.pos;
@@ -695,11 +689,9 @@ int gvl_prefill_extend(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int n_n
 
 int gvl_forward_loss(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, const int64_t* labels, double* nll_sum, int* n_valid, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_forward_loss");
-  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_forward_loss", SEQ_BAD);
-  if (const int rc = bank_refuse(ctx, "gvl_forward_loss", seq_id)) return rc;
+  if (!embeds || !labels || !nll_sum || !n_valid) return fail(ctx, GVL_ERR_ARG, "gvl_forward_loss: bad arguments / length");
+  if (const int rc = admit(ctx, gvl_admit::FORWARD_LOSS, &seq_id, 1, &S, 0)) return rc;
   Seq& sq = ctx->seqs[seq_id];
-  if (!embeds || !labels || !nll_sum || !n_valid || S <= 0 || S > sq.max_tokens || S > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_forward_loss: bad arguments / length");
-  if (sq.pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_forward_loss: sequence already holds tokens");
   // shift (logits[:-1] vs labels[1:]) and drop ignore_index (-100) on the host: integer work
   std::vector<int> rows, tgt;
   for (int t = 0; t + 1 < S; ++t) {
@@ -724,26 +716,13 @@ int gvl_forward_loss(gvl_ctx* ctx, int seq_id, const uint16_t* embeds, int S, co
 int gvl_prefill_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds, const int* seq_lens, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_varlen");
   if (!seq_ids || !embeds || !seq_lens || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad arguments");
-  for (int i = 0; i < n_seqs; ++i) {
-    const int id = seq_ids[i];
-    if (!ctx->lookup(id) || !embeds[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad seq / embeds");
-    if (const int rc = bank_refuse(ctx, "gvl_prefill_varlen", id)) return rc;
-    if (seq_lens[i] <= 0 || seq_lens[i] > ctx->seqs[id].max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: bad length");
-    if (seq_lens[i] > ctx->cfg.max_prefill) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_varlen: seq_len exceeds cfg.max_prefill");
-    if (ctx->seqs[id].pos != 0) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_varlen: sequence already holds tokens");
-    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_prefill_varlen", SEQ_DUPLICATE);
-  }
+  if (const int rc = members_present(ctx, "gvl_prefill_varlen", "seq / embeds", n_seqs, (const void* const*)embeds)) return rc;
+  if (const int rc = admit(ctx, gvl_admit::PREFILL_VARLEN, seq_ids, n_seqs, seq_lens, 1)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // groups of up to prefill_group (gvl_debug_set) sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
-  for (int i = 0; i < n_seqs;) {
-    const int B = prefill_group_size(seq_lens + i, n_seqs - i, ctx->dbg.prefill_group, ctx->cfg.max_prefill);
-    Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH];
-    for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds[i + b]; }
-    const int rc = llm_prefill(ctx, sqs, B, es, seq_lens + i, st);
-    if (rc) return rc;
-    i += B;
-  }
-  return 0;
+  // today's behaviour: groups of up to prefill_group (gvl_debug_set) sequences here, of up to GVL_MAX_PREFILL_BATCH in the extend and score entries
+  return prefill_groups(ctx, seq_ids, n_seqs, embeds, seq_lens, ctx->dbg.prefill_group, [&](int i, int B, Seq* const* sqs, const bf16_t* const* es, const int*) {
+    return llm_prefill(ctx, sqs, B, es, seq_lens + i, st);
+  });
 }
 
 // Ragged prefill where every member sits behind its own cached prefix (0 = none).  Everything is checked before the first launch, so an error leaves every sequence
@@ -751,28 +730,14 @@ int gvl_prefill_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint1
 int gvl_prefill_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const uint16_t* const* embeds_new, const int* n_new, float* last_logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_prefill_extend_varlen");
   if (!seq_ids || !embeds_new || !n_new || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad arguments");
-  for (int i = 0; i < n_seqs; ++i) {
-    const int id = seq_ids[i];
-    if (!ctx->lookup(id) || !embeds_new[i]) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad seq / embeds");
-    if (const int rc = pair_refuse(ctx, "gvl_prefill_extend_varlen", id, false)) return rc;
-    if (const int rc = bank_refuse(ctx, "gvl_prefill_extend_varlen", id)) return rc;
-    const Seq& sq = ctx->seqs[id];
-    if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_prefill_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
-    if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_prefill_extend_varlen: bad length");
-    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_prefill_extend_varlen", SEQ_DUPLICATE);
-  }
+  if (const int rc = members_present(ctx, "gvl_prefill_extend_varlen", "seq / embeds", n_seqs, (const void* const*)embeds_new)) return rc;
+  if (const int rc = admit(ctx, gvl_admit::PREFILL_EXTEND_VARLEN, seq_ids, n_seqs, n_new, 1)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // groups of up to GVL_MAX_PREFILL_BATCH sequences in call order -- as many as the prefill workspace (cfg.max_prefill rows in total) allows
-  for (int i = 0; i < n_seqs;) {
-    const int B = prefill_group_size(n_new + i, n_seqs - i, GVL_MAX_PREFILL_BATCH, ctx->cfg.max_prefill);
-    Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH]; int pos0[GVL_MAX_PREFILL_BATCH];
-    for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds_new[i + b]; pos0[b] = sqs[b]->pos; }
-    const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0);
-    if (rc) return rc;
+  return prefill_groups(ctx, seq_ids, n_seqs, embeds_new, n_new, GVL_MAX_PREFILL_BATCH, [&](int i, int B, Seq* const* sqs, const bf16_t* const* es, const int* pos0) {
+    if (const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0)) return rc;
     if (last_logits) HIPCHK(ctx, hipMemcpyAsync(last_logits + (size_t)i * ctx->cfg.vocab, ctx->d_logits, (size_t)B * ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
-    i += B;
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // gvl_prefill_extend_varlen that also scores given next ids on the way: the same members, groups, refusals and final states; per group the scored rows' packed indices and
@@ -784,39 +749,28 @@ int gvl_score_extend_varlen(gvl_ctx* ctx, const int* seq_ids, int n_seqs, const 
     return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad arguments");
   if (top_n < 0 || top_n > GVL_MAX_TOP_LOGPROBS || (top_n > 0 && (!top_ids_dev || !top_lp_dev)))
     return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: top_n must be 0 .. 8 (top lists needed for > 0)");
-  for (int i = 0; i < n_seqs; ++i) {
-    const int id = seq_ids[i];
-    if (!ctx->lookup(id) || !embeds_new[i] || !next_ids_host[i]) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad seq / embeds / next ids");
-    if (const int rc = pair_refuse(ctx, "gvl_score_extend_varlen", id, false)) return rc;
-    if (const int rc = bank_refuse(ctx, "gvl_score_extend_varlen", id)) return rc;
-    const Seq& sq = ctx->seqs[id];
-    if (sq.pos < 0 || (sq.pos & 63)) return fail(ctx, GVL_ERR_STATE, "gvl_score_extend_varlen: every sequence must be empty or hold a prefix of whole pages (gvl_seq_fork)");
-    if (n_new[i] <= 0 || n_new[i] > ctx->cfg.max_prefill || sq.pos + n_new[i] > sq.max_tokens) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: bad length");
-    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_score_extend_varlen", SEQ_DUPLICATE);
+  if (const int rc = members_present(ctx, "gvl_score_extend_varlen", "seq / embeds / next ids", n_seqs, (const void* const*)embeds_new, (const void* const*)next_ids_host)) return rc;
+  if (const int rc = admit(ctx, gvl_admit::SCORE_EXTEND_VARLEN, seq_ids, n_seqs, n_new, 1)) return rc;
+  for (int i = 0; i < n_seqs; ++i)
     for (int r = 0; r < n_new[i]; ++r) {
       const int32_t y = next_ids_host[i][r];
       if (y != -100 && (y < 0 || y >= ctx->cfg.vocab)) return fail(ctx, GVL_ERR_ARG, "gvl_score_extend_varlen: next id out of range");
     }
-  }
   hipStream_t st = (hipStream_t)stream;
   int done = 0;                                        // scored rows of the groups before this one: where its packed outputs start
   std::vector<int> rows, tgt;
-  for (int i = 0; i < n_seqs;) {
-    const int B = prefill_group_size(n_new + i, n_seqs - i, GVL_MAX_PREFILL_BATCH, ctx->cfg.max_prefill);
-    Seq* sqs[GVL_MAX_PREFILL_BATCH]; const bf16_t* es[GVL_MAX_PREFILL_BATCH]; int pos0[GVL_MAX_PREFILL_BATCH];
+  const int rc = prefill_groups(ctx, seq_ids, n_seqs, embeds_new, n_new, GVL_MAX_PREFILL_BATCH, [&](int i, int B, Seq* const* sqs, const bf16_t* const* es, const int* pos0) {
     rows.clear(); tgt.clear();
-    for (int b = 0, off = 0; b < B; off += n_new[i + b], ++b) {
-      sqs[b] = &ctx->seqs[seq_ids[i + b]]; es[b] = embeds_new[i + b]; pos0[b] = sqs[b]->pos;
+    for (int b = 0, off = 0; b < B; off += n_new[i + b], ++b)
       for (int r = 0; r < n_new[i + b]; ++r) if (next_ids_host[i + b][r] != -100) { rows.push_back(off + r); tgt.push_back(next_ids_host[i + b][r]); }
-    }
     ScoreReq sr{(int)rows.size(), rows.data(), tgt.data(), top_n, lp_dev + done, rank_dev + done,
                 top_n > 0 ? top_ids_dev + (size_t)done * GVL_MAX_TOP_LOGPROBS : nullptr, top_n > 0 ? top_lp_dev + (size_t)done * GVL_MAX_TOP_LOGPROBS : nullptr};
-    const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0, &sr);
-    if (rc) return rc;
+    if (const int rc = llm_prefill(ctx, sqs, B, es, n_new + i, st, nullptr, pos0, &sr)) return rc;
     if (last_logits) HIPCHK(ctx, hipMemcpyAsync(last_logits + (size_t)i * ctx->cfg.vocab, ctx->d_logits, (size_t)B * ctx->cfg.vocab * 4, hipMemcpyDeviceToDevice, st));
     done += sr.n;
-    i += B;
-  }
+    return 0;
+  });
+  if (rc) return rc;
   if (n_scored) *n_scored = done;
   return 0;
 }
@@ -837,24 +791,16 @@ int gvl_decode_greedy_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int ma
   REQUIRE_READY(ctx->has_llm, "gvl_decode_greedy_batch");
   if (!seq_ids || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs || !out_ids || !n_out || max_new <= 0 || max_new > ctx->outlist_cap)
     return fail(ctx, GVL_ERR_ARG, "gvl_decode_greedy_batch: bad arguments");
-  for (int i = 0; i < n_seqs; ++i) {
-    const int id = seq_ids[i];
-    if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_BAD);
-    if (const int rc = pair_refuse(ctx, "gvl_decode_greedy_batch", id, false)) return rc;
-    if (const int rc = bank_refuse(ctx, "gvl_decode_greedy_batch", id)) return rc;
-    if (ctx->seqs[id].n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_greedy: call gvl_prefill first");   // members of a group must also be at the SAME step (checked per group)
-    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_greedy_batch", SEQ_DUPLICATE);
-  }
+  if (const int rc = admit(ctx, gvl_admit::DECODE_GREEDY_BATCH, seq_ids, n_seqs, nullptr, 0)) return rc;   // members of a group must also be at the SAME step (checked per group)
   hipStream_t st = (hipStream_t)stream;
-  // groups of up to 16 rows (VALU fallback: 4, 2, 1): a group streams the weights once per step for all of its members.  A guided leader counts two rows: its follower
-  // is stepped with it (decode_parts_paired; without pairs the cut is decode_parts')
-  int sizes[gvl_ctx::kMaxSeqs], rows[gvl_ctx::kMaxSeqs];
-  for (int i = 0; i < n_seqs; ++i) rows[i] = ctx->seqs[seq_ids[i]].follow >= 0 ? 2 : 1;
-  for (int k = 0, i = 0, nk = decode_parts_paired(ctx->decode_mfma, rows, n_seqs, sizes); k < nk; ++k) {
+  // a group streams the weights once per step for all of its members (named_parts)
+  Seq* named[gvl_ctx::kMaxSeqs]; int sizes[gvl_ctx::kMaxSeqs];
+  for (int i = 0; i < n_seqs; ++i) named[i] = &ctx->seqs[seq_ids[i]];
+  for (int k = 0, i = 0, nk = named_parts(ctx, named, n_seqs, sizes); k < nk; ++k) {
     const int B = sizes[k];
-    Seq* sqs[GVL_MAX_DECODE_BATCH]; int32_t* outs[GVL_MAX_DECODE_BATCH]; int* nouts[GVL_MAX_DECODE_BATCH];
-    for (int b = 0; b < B; ++b) { sqs[b] = &ctx->seqs[seq_ids[i + b]]; outs[b] = out_ids + (size_t)(i + b) * max_new; nouts[b] = n_out + i + b; }
-    const int rc = decode_group(ctx, sqs, B, max_new, eos_id, outs, nouts, st);
+    int32_t* outs[GVL_MAX_DECODE_BATCH]; int* nouts[GVL_MAX_DECODE_BATCH];
+    for (int b = 0; b < B; ++b) { outs[b] = out_ids + (size_t)(i + b) * max_new; nouts[b] = n_out + i + b; }
+    const int rc = decode_group(ctx, named + i, B, max_new, eos_id, outs, nouts, st);
     if (rc) return rc;
     i += B;
   }
@@ -866,28 +812,17 @@ int gvl_decode_greedy_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int ma
 int gvl_decode_steps(gvl_ctx* ctx, const int* seq_ids, int n_seqs, int n_steps, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_decode_steps");
   if (!seq_ids || n_seqs <= 0 || n_seqs > gvl_ctx::kMaxSeqs || n_steps <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: bad arguments");
-  for (int i = 0; i < n_seqs; ++i) {
-    const int id = seq_ids[i];
-    if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_steps", SEQ_BAD);
-    if (const int rc = pair_refuse(ctx, "gvl_decode_steps", id, false)) return rc;
-    if (const int rc = bank_refuse(ctx, "gvl_decode_steps", id)) return rc;
-    const Seq& sq = ctx->seqs[id];
-    if (sq.n_gen < 1) return fail(ctx, GVL_ERR_STATE, "gvl_decode_steps: call gvl_prefill first");
-    if (sq.pos + n_steps > sq.max_tokens || sq.n_gen + n_steps > ctx->outlist_cap) return fail(ctx, GVL_ERR_ARG, "gvl_decode_steps: sequence would exceed its capacity");
-    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_steps", SEQ_DUPLICATE);
-  }
+  if (const int rc = admit(ctx, gvl_admit::DECODE_STEPS, seq_ids, n_seqs, &n_steps, 0)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  int sizes[gvl_ctx::kMaxSeqs], rows[gvl_ctx::kMaxSeqs];
-  for (int i = 0; i < n_seqs; ++i) rows[i] = ctx->seqs[seq_ids[i]].follow >= 0 ? 2 : 1;   // a guided leader brings its follower's row (bound with at least the leader's capacity left)
-  const int nk = decode_parts_paired(ctx->decode_mfma, rows, n_seqs, sizes);   // groups of up to 16 rows (VALU fallback: 4, 2, 1): one weight stream per step per group
+  Seq* named[gvl_ctx::kMaxSeqs]; int sizes[gvl_ctx::kMaxSeqs];
+  for (int i = 0; i < n_seqs; ++i) named[i] = &ctx->seqs[seq_ids[i]];
+  const int nk = named_parts(ctx, named, n_seqs, sizes);   // a guided leader brings its follower's row (bound with at least the leader's capacity left)
   for (int s = 0; s < n_steps; ++s) {
     for (int k = 0, i = 0; k < nk; ++k) {
-      const int B = sizes[k];
-      Seq* named[GVL_MAX_DECODE_BATCH]; Seq* sqs[GVL_MAX_DECODE_BATCH];
-      for (int b = 0; b < B; ++b) named[b] = &ctx->seqs[seq_ids[i + b]];
-      const int rc = decode_step(ctx, sqs, step_rows(ctx, named, B, sqs), st);
+      Seq* sqs[GVL_MAX_DECODE_BATCH];
+      const int rc = decode_step(ctx, sqs, step_rows(ctx, named + i, sizes[k], sqs), st);
       if (rc) return rc;
-      i += B;
+      i += sizes[k];
     }
   }
   return 0;
@@ -908,14 +843,11 @@ int gvl_seq_read(gvl_ctx* ctx, int seq_id, int first, int32_t* out_ids, int cap,
 
 int gvl_decode_step_logits(gvl_ctx* ctx, int seq_id, int tok, float* logits, void* stream) {
   REQUIRE_READY(ctx->has_llm, "gvl_decode_step_logits");
-  if (!ctx->lookup(seq_id)) return seq_fail(ctx, "gvl_decode_step_logits", SEQ_BAD);
-  if (const int rc = pair_refuse(ctx, "gvl_decode_step_logits", seq_id, true)) return rc;
+  if (const int rc = admit(ctx, gvl_admit::DECODE_STEP_LOGITS, &seq_id, 1, &tok, 0)) return rc;
   Seq& sq = ctx->seqs[seq_id];
-  if (tok < 0 || tok >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits: bad token / sequence full / not prefilled");
   hipStream_t st = (hipStream_t)stream;
   RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sq.d_tok, tok, st));
   Seq* one[1] = {&sq};
-  if (sq.bank && (sq.bank_rows != sq.pos || sq.bank_rows >= sq.bank_cap)) return fail(ctx, GVL_ERR_STATE, "gvl_decode_step_logits: the hidden bank is not in step with the sequence");
   int rc = decode_step(ctx, one, 1, st);
   if (rc) return rc;
   if (sq.bank) { rc = bank_append(ctx, sq, ctx->d_x, ctx->cfg.hidden, 1, st); if (rc) return rc; }   // the step's residual row behind the last layer
@@ -927,17 +859,9 @@ int gvl_decode_step_logits_batch(gvl_ctx* ctx, const int* seq_ids, int n_seqs, c
   REQUIRE_READY(ctx->has_llm, "gvl_decode_step_logits_batch");
   if (!seq_ids || !toks || !decode_batch_ok(ctx->decode_mfma, n_seqs))
     return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: 1 .. 16 sequences (VALU fallback geometries: 1, 2 or 4)");
+  if (const int rc = admit(ctx, gvl_admit::DECODE_STEP_LOGITS_BATCH, seq_ids, n_seqs, toks, 1)) return rc;
   Seq* sqs[GVL_MAX_DECODE_BATCH];
-  for (int i = 0; i < n_seqs; ++i) {
-    const int id = seq_ids[i];
-    if (!ctx->lookup(id)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_BAD);
-    if (const int rc = pair_refuse(ctx, "gvl_decode_step_logits_batch", id, true)) return rc;
-    Seq& sq = ctx->seqs[id];
-    if (toks[i] < 0 || toks[i] >= ctx->cfg.vocab || sq.pos >= sq.max_tokens || sq.pos == 0) return fail(ctx, GVL_ERR_ARG, "gvl_decode_step_logits_batch: bad token / sequence full / not prefilled");
-    if (ctx->repeats(seq_ids, i)) return seq_fail(ctx, "gvl_decode_step_logits_batch", SEQ_DUPLICATE);
-    if (sq.bank && (sq.bank_rows != sq.pos || sq.bank_rows >= sq.bank_cap)) return fail(ctx, GVL_ERR_STATE, "gvl_decode_step_logits_batch: the hidden bank is not in step with the sequence");
-    sqs[i] = &sq;
-  }
+  for (int i = 0; i < n_seqs; ++i) sqs[i] = &ctx->seqs[seq_ids[i]];
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_seqs; ++i) RUN(GVL_PROF_OTHER, 0, gvl_launch_set_int(sqs[i]->d_tok, toks[i], st));
   const int rc = decode_step(ctx, sqs, n_seqs, st);       // ONE weight stream for all of them; row i depends on sequence i only (batch-invariant kernels)

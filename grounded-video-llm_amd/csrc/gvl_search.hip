@@ -48,15 +48,8 @@ SearchSession::~SearchSession() { for (int id : ids) ctx->close(id); }
 
 int SearchSession::open(int seq_id, float penalty, int ngram, int min_new, int proc_eos_id, int rules_id, int max_new, bool ranks_hidden) {
   if (rules_id != -1 && (rules_id < 0 || ctx->check_rules(rules_id))) return seq_fail(ctx, fn, SEQ_NO_RULES);
-  if (!ctx->lookup(seq_id)) return seq_fail(ctx, fn, SEQ_BAD);
-  if (const int rc = pair_refuse(ctx, fn, seq_id, true)) return rc;
-  if (!ranks_hidden) { if (const int rc = bank_refuse(ctx, fn, seq_id)) return rc; }
+  if (const int rc = admit(ctx, ranks_hidden ? gvl_admit::SEARCH_HIDDEN : gvl_admit::SEARCH, &seq_id, 1, nullptr, 0, fn)) return rc;
   pos0 = ctx->seqs[seq_id].pos;
-  if (pos0 <= 0) return fail(ctx, GVL_ERR_STATE, std::string(fn) + ": the sequence is not prefilled");
-  if (ranks_hidden) {
-    if (!ctx->seqs[seq_id].bank) return fail(ctx, GVL_ERR_STATE, std::string(fn) + ": the sequence keeps no hidden states (gvl_seq_keep_hidden before its prefill)");
-    if (ctx->seqs[seq_id].bank_rows != pos0) return fail(ctx, GVL_ERR_STATE, std::string(fn) + ": the hidden bank is not in step with the sequence");
-  }
   if (const int rc = ensure_buffers(ctx)) return rc;
   V = ctx->cfg.vocab;
   h_vals = (float*)ctx->h_beam_cand; h_idx = (int*)(h_vals + kMaxCand); h_proc = h_vals + 2 * kMaxCand; h_chosen = (int*)(h_vals + kCandFloats);

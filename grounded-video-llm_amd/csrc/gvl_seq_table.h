@@ -33,6 +33,9 @@ struct SeqCore {
   // classifier-free guidance (gvl_seq_set_guidance): a LEADER names its follower in `follow` and carries the pair's scale; the FOLLOWER names its leader in `lead`.
   // A follower takes its leader's token every step and is stepped only as the leader's extra row.  -1: not part of a pair.  A copy (fork / clone) starts unpaired.
   int lead = -1, follow = -1; float guide = 1.0f;
+  // hidden bank (gvl_seq_keep_hidden), the host side: room for bank_cap rows (> 0: the sequence keeps its hidden states), bank_rows of them written, row j = position j.
+  // The rows themselves are Seq's (gvl_ctx.h); a copy (fork / clone) starts without a bank
+  int bank_cap = 0, bank_rows = 0;
 };
 enum SeqStatus { SEQ_OK = 0, SEQ_BAD = -1, SEQ_DUPLICATE = -2, SEQ_NO_PAGES = -3, SEQ_TOO_MANY = -4, SEQ_NO_RULES = -5, SEQ_RULES_BUSY = -6, SEQ_RULES_FULL = -7,
                  SEQ_NO_GRAMMAR = -8, SEQ_GRAMMAR_BUSY = -9, SEQ_GRAMMAR_FULL = -10, SEQ_FOLLOWER = -11, SEQ_NOT_FRESH = -12, SEQ_PAIRED = -13 };
@@ -49,6 +52,7 @@ struct SeqTable {
   void reset_pool(int pages) { free_pages.clear(); page_ref.assign(pages, 0); for (int p = pages - 1; p >= 0; --p) free_pages.push_back(p); }
   template <class V> static int first_unused(const V& v) { int i = 0; while (i < (int)v.size() && v[i].used) ++i; return i; }   // v.size(): none
   S* lookup(int id) { return id >= 0 && id < (int)seqs.size() && seqs[id].used ? &seqs[id] : nullptr; }
+  const S* lookup(int id) const { return id >= 0 && id < (int)seqs.size() && seqs[id].used ? &seqs[id] : nullptr; }
   // ids[i] names a sequence that an earlier member of the group named already
   static bool repeats(const int* ids, int i) { for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) return true; return false; }
   // tests (gvl_debug_seq_pages): the pages of live sequence `id` in position order -> SEQ_OK with *n (may be null) = how many it holds and the first min(cap, that
@@ -80,6 +84,19 @@ struct SeqTable {
     if (id == (int)seqs.size()) seqs.push_back(std::move(s)); else seqs[id] = std::move(s);
     return id;
   }
+  // n clones of `src` at its current length, max_tokens each -> their ids in ids[0 .. n), or a negative SeqStatus with NOTHING changed: pages and slots are counted
+  // before the first one opens, so all n open or none does.  Otherwise exactly what n open(max_tokens, src, pos) calls give
+  int open_many(int src, int n, int max_tokens, int* ids) {
+    const S* s = lookup(src);
+    if (!s || n < 1 || !ids || max_tokens <= s->pos) return SEQ_BAD;
+    const int pos = s->pos, own_pages = (max_tokens + 63) / 64 - (pos >> 6);
+    if ((long long)free_pages.size() < (long long)n * own_pages) return SEQ_NO_PAGES;
+    int slots = max_seqs - (int)seqs.size();
+    for (const S& q : seqs) slots += !q.used;
+    if (slots < n) return SEQ_TOO_MANY;
+    for (int i = 0; i < n; ++i) ids[i] = open(max_tokens, src, pos);   // cannot fail: pages and slots were counted above
+    return SEQ_OK;
+  }
   // gvl_seq_fanout: n_new siblings of the freshly prefilled `src` (n_gen == 1: it holds the one token its own prefill selected) -> their ids in ids[0 .. n_new), or a
   // negative SeqStatus with NOTHING changed -- all siblings open or none does, slots and pages alike.  A sibling is a clone of the source at its current length (whole
   // pages shared, later pages its own) with the source's settings, except that it takes the source's EFFECTIVE sampling -- the source's own setting, else `followed`
@@ -90,14 +107,9 @@ struct SeqTable {
     if (!s || n_new < 1 || !streams || !ids || s->pos <= 0 || max_tokens <= s->pos) return SEQ_BAD;
     if (s->lead >= 0 || s->follow >= 0) return SEQ_PAIRED;
     if (s->n_gen != 1) return SEQ_NOT_FRESH;
-    const int pos = s->pos, own_pages = (max_tokens + 63) / 64 - (pos >> 6);
-    if ((long long)free_pages.size() < (long long)n_new * own_pages) return SEQ_NO_PAGES;
-    int slots = max_seqs - (int)seqs.size();
-    for (const S& q : seqs) slots += !q.used;
-    if (slots < n_new) return SEQ_TOO_MANY;
     Sampling eff = s->sel.own_sampling ? s->sel.sampling : followed;   // by value: open() may move the source
+    if (const int rc = open_many(src, n_new, max_tokens, ids)) return rc;
     for (int i = 0; i < n_new; ++i) {
-      ids[i] = open(max_tokens, src, pos);             // cannot fail: pages and slots were counted above
       eff.stream = streams[i];
       set_sampling(seqs[ids[i]].sel, &eff);
       seqs[ids[i]].n_gen = 1;

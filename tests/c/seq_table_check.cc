@@ -1,7 +1,7 @@
 // Drives the sequence table (csrc/gvl_seq_table.h: host-only, no HIP) from a script on stdin: built with the host C++ compiler by tests/test_seq_table_cpu.py.
 //   usage: seq_table_check <kv pages> <max sequences> <max rule sets>
 // One operation per line; every line is answered by one JSON object: the result code "rc" (an id, 0, or a negative SeqStatus) and the whole table.
-//   alloc MAX | fork SRC N MAX | clone SRC MAX | free SEQ | pos SEQ N (the sequence now holds N tokens: what a prefill / decode leaves)
+//   alloc MAX | fork SRC N MAX | clone SRC MAX | openmany SRC N MAX (N clones at once, all or nothing: 0 or a negative status) | free SEQ | pos SEQ N (the sequence now holds N tokens: what a prefill / decode leaves)
 //   newrules | delrules ID | rules SEQ ID | topn SEQ N | proc SEQ PENALTY NGRAM MIN_NEW EOS      (SEQ -1: the default of later allocs)
 //   pages SEQ CAP I | pagesnull SEQ CAP I: pages_of into 64 words filled with -77 (CAP -2: a null buffer with cap 0; pagesnull: a null count) -> a negative status, else
 //     word I of the buffer afterwards (I -1: the count, -99 when it was not asked for)
@@ -31,6 +31,7 @@ int main(int argc, char** argv) {
     if (op == "alloc") { in >> a; rc = t.open(a, -1, 0); }
     else if (op == "fork") { in >> a >> b >> c; rc = t.open(c, a, b); }
     else if (op == "clone") { in >> a >> b; rc = t.open(b, a, t.lookup(a) ? t.lookup(a)->pos : 0); }
+    else if (op == "openmany") { in >> a >> b >> c; std::vector<int> ids(b > 0 ? b : 1, -1); rc = t.open_many(a, b, c, ids.data()); }
     else if (op == "free") { in >> a; rc = t.close(a); }
     else if (op == "pos") { in >> a >> b; rc = t.lookup(a) ? (t.lookup(a)->pos = b, 0) : (int)SEQ_BAD; }
     else if (op == "newrules") { rc = t.add_rules(&blobs[n_blobs]); if (rc >= 0) ++n_blobs; }

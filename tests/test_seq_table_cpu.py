@@ -109,6 +109,20 @@ def test_clone_on_and_off_a_page_boundary():
     assert out[4]["ref"][:6] == [3, 2, 1, 1, 1, 1] and same_table(out[-1], initial(8))
 
 
+def test_open_many_opens_all_or_none_and_otherwise_what_single_opens_give():
+    """SeqTable::open_many (gvl_seq_fanout's siblings, the searches' candidates): pages and slots are counted before the first clone opens"""
+    head = "alloc 129\npos 0 100\n"                                                        # 3 pages, 1 whole; a clone of 129 tokens owns 2
+    assert rcs(head + "openmany 0 3 129", pages=8) == [0, 0, NO_PAGES]                       # 5 free, 6 needed: one page too few, nothing opened (run() checks the table)
+    assert rcs(head + "openmany 0 3 129", pages=9, max_seqs=3) == [0, 0, TOO_MANY]            # pages for three, slots for two
+    assert rcs(head + "alloc 64\nfree 1\nopenmany 0 3 129", pages=9, max_seqs=4) == [0, 0, 1, 0, 0]    # a freed slot counts
+    assert rcs(head + "openmany 0 0 129\nopenmany 0 2 100\nopenmany 1 2 129\nopenmany -1 2 129", pages=9) == [0, 0, BAD, BAD, BAD, BAD]
+    many = run(head + "openmany 0 3 129", pages=9)[-1]
+    single = run(head + "clone 0 129\nclone 0 129\nclone 0 129", pages=9)[-1]
+    assert many["rc"] == 0 and single["rc"] == 3
+    assert {k: v for k, v in many.items() if k != "rc"} == {k: v for k, v in single.items() if k != "rc"}      # the same slots, pages, counts and free list, to the bit
+    assert [many["seqs"][k]["pages"] for k in "123"] == [[0, 3, 4], [0, 5, 6], [0, 7, 8]] and many["free"] == []
+
+
 def test_pages_of_reports_a_sequences_pages_and_refuses_the_rest():
     """SeqTable::pages_of, the body of gvl_debug_seq_pages: the count, the first min(cap, count) pages, nothing behind them; unknown / freed sequences and a negative
     cap are refused with nothing written; a null count and a null buffer with cap 0 are fine"""
@@ -230,6 +244,17 @@ class Model:
             return self.open(a[2], a[0], a[1])
         if op == "clone":
             return self.open(a[1], a[0], st["seqs"][str(a[0])]["pos"] if str(a[0]) in st["seqs"] else 0)
+        if op == "openmany":
+            src = st["seqs"].get(str(a[0]))
+            if src is None or a[1] < 1 or a[2] <= src["pos"]:
+                return BAD
+            if len(st["free"]) < a[1] * ((a[2] + 63) // 64 - (src["pos"] >> 6)):
+                return NO_PAGES
+            if self.max_seqs - len(st["seqs"]) < a[1]:
+                return TOO_MANY
+            for _ in range(a[1]):
+                assert self.open(a[2], a[0], src["pos"]) >= 0
+            return 0
         if op == "free":
             s = st["seqs"].pop(str(a[0]), None)
             if s is None:
@@ -287,8 +312,10 @@ def random_ops(rng, n, max_seqs, max_rules):
             ops.append(("alloc", rng.choice(LENGTHS + (200,))))
         elif k < 0.34:
             ops.append(("fork", seq(), rng.choice((64, 64, 128, 192, 0)), rng.choice((65, 128, 129, 200, 64))))
-        elif k < 0.44:
+        elif k < 0.41:
             ops.append(("clone", seq(), rng.choice((65, 129, 200, 256))))
+        elif k < 0.44:
+            ops.append(("openmany", seq(), rng.randrange(0, 4), rng.choice((65, 129, 200, 256))))
         elif k < 0.52:
             ops.append(("pos", max(seq(), 0), rng.choice((0, 1, 63, 64, 65, 100, 128, 129))))
         elif k < 0.74:
@@ -321,6 +348,6 @@ def test_random_operations_match_the_model():
         seen.add((op[0], min(rc, 0)))
     # the mix reached every limit and every refusal
     assert {("alloc", NO_PAGES), ("alloc", TOO_MANY), ("fork", NO_PAGES), ("fork", TOO_MANY), ("fork", BAD), ("fork", 0), ("clone", NO_PAGES), ("clone", TOO_MANY),
-            ("clone", BAD), ("clone", 0), ("free", BAD), ("newrules", RULES_FULL), ("delrules", RULES_BUSY), ("delrules", NO_RULES), ("delrules", 0),
+            ("clone", BAD), ("clone", 0), ("openmany", NO_PAGES), ("openmany", TOO_MANY), ("openmany", BAD), ("openmany", 0), ("free", BAD), ("newrules", RULES_FULL), ("delrules", RULES_BUSY), ("delrules", NO_RULES), ("delrules", 0),
             ("rules", NO_RULES), ("rules", BAD), ("rules", 0)} <= seen
     assert same_table(out[-1], initial(pages))
