@@ -1,5 +1,5 @@
 // gvl_model.h -- what the host translation units of libgvl.so share: gvl_model.hip (context, weights, paged KV pool, the sequence / prefill / decode
-// and operator entry points of include/gvl.h), gvl_select.hip (the token-selection entry points), gvl_vision.hip (the towers' launch sequences) and
+// entry points of include/gvl.h), gvl_ops.hip (the operator entry points), gvl_select.hip (the token-selection entry points), gvl_vision.hip (the towers' launch sequences) and
 // gvl_llm.hip (prefill, the decode step -- planned in gvl_decode_plan.h --, the decode loop).  Internal: nothing here is part of the ABI.
 // The sequence entries are wrappers: REQUIRE_READY, their own pointer and count checks, ONE admit() call (the table of gvl_admit.h decides which sequences the entry
 // takes and says why not), then the work.
@@ -37,7 +37,6 @@ inline void bind_logprobs(gvl_ctx* ctx, Seq& s, int id) {
   s.d_top_lp = ctx->d_seq_top_lp ? ctx->d_seq_top_lp + (size_t)id * cap * GVL_MAX_TOP_LOGPROBS : nullptr;
 }
 
-inline int pad_head(int dr) { return dr <= 64 ? 64 : (dr <= 96 ? 96 : (dr <= 128 ? 128 : -1)); }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -1,11 +1,10 @@
 // gvl_model.hip -- host side of libgvl.so: context, packed weights, workspace arenas, paged KV pool and the C ABI of include/gvl.h except its token-selection part (gvl_select.hip):
-// the towers, splice, the sequence / prefill / decode entry points over the sequence table (gvl_seq_table.h), the operator-level entries.  The launch sequences behind the ABI live in gvl_vision.hip
+// the towers, splice, the sequence / prefill / decode entry points over the sequence table (gvl_seq_table.h); the operator-level entries live in gvl_ops.hip.  The launch sequences behind the ABI live in gvl_vision.hip
 // (CLIP, InternVideo2, glue / projectors) and gvl_llm.hip (prefill, decode step, decode loop); gvl_model.h is what the four share.  Restates (file:line in the reference):
 //   splice          models/llava_next_video.py:568-596
 //   generate()      models/llava_next_video.py:655-661 (greedy; transformers GenerationMixin [ext])
 #include "gvl_model.h"
 #include "gvl_prefill_plan.h"   // prefill_group_size: how the *_varlen entry points cut their sequences into llm_prefill groups
-#include "gvl_attn_plan.h"      // decode_attn_plan: gvl_op_decode_attention refuses what the plan refuses, before anything is launched
 
 std::string& gvl_create_error() { static std::string e; return e; }
 
@@ -928,545 +927,6 @@ int gvl_prof_read(gvl_ctx* ctx, int cat, double* total_ms, int64_t* launches, do
   if (total_ms) *total_ms = ctx->prof_ms[cat];
   if (launches) *launches = ctx->prof_n[cat];
   if (work) *work = ctx->prof_work[cat];
-  return 0;
-}
-
-// ---- operator-level entry points -------------------------------------------------------------------
-int gvl_op_gemm(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, void* C, int M, int N, int K, const float* bias, const float* gamma,
-                const void* resid, int act, int out_f32, int tile_cfg, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  GemmArgs g = gemm(A, K, W, C, act == GVL_ACT_SILU_MUL ? N / 2 : N, M, N, K);
-  g.bias = bias; g.gamma = gamma; g.resid = resid; g.ldr = N; g.act = act; g.out_f32 = out_f32; g.round_pre_resid = 1; g.tile_cfg = tile_cfg;
-  if (const char* e = gvl_lab_env("GVL_LAB_LD")) { int la = 0, lw = 0; if (sscanf(e, "%d,%d", &la, &lw) == 2) { g.lda = la; g.ldw = lw; } }   // LAB: operand row pitches (tools/gemm_lab.py)
-  RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st));
-  return 0;
-}
-// The fused-RMSNorm epilogues at operator level (bf16 output): rowscale [M] f32 or null multiplies the accumulator rows before bias / activation; rowsq
-// [M][rowsq_ld] f32 or null receives the sums of squares of the rounded outputs per aligned 64-column block (N % 64 == 0).
-int gvl_op_gemm_rows(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, uint16_t* C, int M, int N, int K, const float* bias, const float* gamma,
-                     const uint16_t* resid, int act, const float* rowscale, float* rowsq, int rowsq_ld, int tile_cfg, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  GemmArgs g = gemm(A, K, W, C, act == GVL_ACT_SILU_MUL ? N / 2 : N, M, N, K);
-  g.bias = bias; g.gamma = gamma; g.resid = resid; g.ldr = N; g.act = act; g.round_pre_resid = 1; g.tile_cfg = tile_cfg;
-  g.rowscale = rowscale; g.rowsq = rowsq; g.rowsq_ld = rowsq_ld;
-  RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st));
-  return 0;
-}
-// The row-remapping store of build_visual at operator level: GEMM row m lands at row (m / grp_rows) * grp_stride + m % grp_rows + row_off of C.
-int gvl_op_gemm_grouped(gvl_ctx* ctx, const uint16_t* A, const uint16_t* W, void* C, int M, int N, int K, const float* bias, const float* gamma,
-                        const void* resid, int act, int out_f32, float* rowsq, int rowsq_ld, int grp_rows, int grp_stride, int row_off, int tile_cfg,
-                        void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!A || !W || !C) return fail(ctx, GVL_ERR_ARG, "gvl_op_gemm_grouped: null operand");
-  if (grp_rows < 1 || row_off < 0 || (long)row_off + grp_rows > grp_stride) return fail(ctx, GVL_ERR_ARG, "gvl_op_gemm_grouped: needs grp_rows >= 1, row_off >= 0 and row_off + grp_rows <= grp_stride");
-  hipStream_t st = (hipStream_t)stream;
-  GemmArgs g = gemm(A, K, W, C, act == GVL_ACT_SILU_MUL ? N / 2 : N, M, N, K);
-  g.bias = bias; g.gamma = gamma; g.resid = resid; g.ldr = N; g.act = act; g.out_f32 = out_f32; g.round_pre_resid = 1; g.tile_cfg = tile_cfg;
-  g.rowsq = rowsq; g.rowsq_ld = rowsq_ld; g.grp_rows = grp_rows; g.grp_stride = grp_stride; g.row_off = row_off;
-  RUN(GVL_PROF_GEMM, gvl_gemm_flops(g), gvl_launch_gemm(g, st));
-  return 0;
-}
-// W' = bf16(W diag(gamma)) and rs = rsqrt(sum of the blocks [b0, b0 + nblk) / cols + eps): the two small kernels around those epilogues
-int gvl_op_fold_gamma(gvl_ctx* ctx, const uint16_t* W, const uint16_t* gamma, uint16_t* Wo, int64_t rows, int cols, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_fold_gamma(W, gamma, Wo, (long)rows, cols, st));
-  return 0;
-}
-int gvl_op_rowsq_finish(gvl_ctx* ctx, const float* rowsq, int ld, int b0, int nblk, float* rs, int rows, int cols, float eps, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_rowsq_finish(rowsq, ld, b0, nblk, rs, rows, cols, eps, st));
-  return 0;
-}
-int gvl_op_attention(gvl_ctx* ctx, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H, int KV, int Dr,
-                     float scale, int causal, void* stream) {
-  // q/k/v here are column blocks of ONE fused row-major qkv tensor [B*S][(H+2KV)*Dr]: q points at column 0;
-  // k and v must equal q + H*Dr and q + (H+KV)*Dr (checked) -- the layout every tower produces.
-  if (!ctx) return GVL_ERR_ARG;
-  if (k != q + (size_t)H * Dr || v != q + (size_t)(H + KV) * Dr) return fail(ctx, GVL_ERR_ARG, "gvl_op_attention: q,k,v must be the column blocks of one fused qkv tensor");
-  const int D = pad_head(Dr);
-  if (D < 0 || (Dr & 7)) return fail(ctx, GVL_ERR_ARG, "gvl_op_attention: head dim unsupported");
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = (S + 63) / 64;
-  ArenaScope arena_scope(ctx->arena_off);
-  AALLOC(Q, bf16_t, (size_t)B * H * S * D); AALLOC(Kt, bf16_t, (size_t)B * tiles * KV * 64 * D); AALLOC(Vt, bf16_t, (size_t)B * tiles * KV * 64 * D);
-  // non-causal (vision) attention reads v -- and, when no head-dim padding is needed, q and k -- in place, exactly as the towers do
-  const int ld = (H + 2 * KV) * Dr;
-  const bool v_rows = ctx->dbg.vision_in_place && !causal && D != 128, qk_rows = ctx->dbg.vision_in_place == 1 && v_rows && D == Dr && D == 64;
-  if (!qk_rows) { QkvPostArgs p; memset(&p, 0, sizeof(p)); p.qkv = q; p.ld = ld; p.Q = Q; p.Kt = Kt; p.Vt = v_rows ? nullptr : Vt; p.B = B; p.S = S; p.H = H; p.KV = KV; p.Dr = Dr; p.D = D; p.mode = 0;
-    RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(p, st)); }
-  { AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Q; a.Kt = Kt; a.Vt = Vt; a.O = out; a.B = B; a.H = H; a.KV = KV; a.S = S; a.D = D; a.Dout = Dr; a.scale = scale; a.causal = causal; a.ring = ctx->dbg.attn_ring;
-    if (v_rows) { a.Vrows = v; a.v_ld = ld; }
-    if (qk_rows) { a.Qrows = q; a.Krows = k; a.q_ld = a.k_ld = ld; }
-    RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st)); }
-  return 0;
-}
-int gvl_op_layernorm(gvl_ctx* ctx, const float* x, const float* w, const float* b, uint16_t* y, int rows, int cols, float eps, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_layernorm_f32(x, w, b, y, rows, cols, eps, st));
-  return 0;
-}
-int gvl_op_rmsnorm(gvl_ctx* ctx, const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int cols, float eps, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_rmsnorm_bf16(x, w, y, rows, cols, eps, st));
-  return 0;
-}
-// ---- the vision front end and the glue of the visual prefix at operator level (tests/test_gpu_vision_ops.py; fields and geometry: include/gvl.h) ----------------
-// The patch embedding of either tower by EITHER path, chosen by the caller: a geometry the fused launcher refuses is an error here, not a fall-back.
-int gvl_op_patch_embed(gvl_ctx* ctx, const gvl_patch_embed* p, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_patch_embed: null descriptor");
-  const char* bad = nullptr;
-  if (p->mode != 0 && p->mode != 1) bad = "mode is 0 (CLIP) or 1 (InternVideo2)";
-  else if (p->path != 0 && p->path != 1) bad = "path is 0 (fused) or 1 (three passes)";
-  else if (p->n <= 0 || p->T <= 0 || p->image <= 0 || p->patch <= 0 || p->C <= 0 || p->Kp <= 0) bad = "n, T, image, patch, C and Kp must be positive";
-  else if (p->image % p->patch) bad = "image must be a multiple of patch";
-  else if (p->Kp % 8 || p->Kp < 3 * p->patch * p->patch) bad = "Kp must be a multiple of 8 and hold 3 patch^2 columns";
-  else if (!p->px || !p->W || !p->cls || !p->pos || !p->out) bad = "px, W, cls, pos and out are required";
-  else if (p->mode == 0 && (!p->lnw || !p->lnb)) bad = "CLIP needs lnw and lnb";
-  else if (p->mode == 0 && p->T != 1) bad = "CLIP has one frame per image (T = 1)";
-  else if (p->mode == 1 && !p->bias) bad = "InternVideo2 needs the conv bias";
-  else if (p->path == 0 && p->im2col) bad = "the fused path forms no im2col matrix";
-  else if (p->path == 1 && (p->Kp % 64 || p->C % 8 || (p->mode == 0 && p->C > 4096))) bad = "the three passes need Kp % 64 == 0 and C % 8 == 0 (CLIP: C <= 4096)";
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_patch_embed: ") + bad);
-  const int g = p->image / p->patch;
-  const long M_l = (long)p->n * p->T * g * g;
-  if (M_l > (1l << 30)) return fail(ctx, GVL_ERR_ARG, "gvl_op_patch_embed: too many patch rows");
-  const int M = (int)M_l, TL = p->T * g * g, C = p->C;
-  hipStream_t st = (hipStream_t)stream;
-  ArenaScope arena_scope(ctx->arena_off);
-  if (p->path == 0) {
-    if (C % 16 || p->patch > 16 || (p->patch & 1)) return fail(ctx, GVL_ERR_ARG, "gvl_op_patch_embed: geometry outside the fused kernel");
-    AALLOC(Wt, bf16_t, (size_t)(C / 16) * (3 * p->patch / 2) * 512);
-    PatchEmbedArgs e; memset(&e, 0, sizeof(e)); e.px = p->px; e.Wt = Wt; e.n_img = p->n; e.T = p->T; e.image = p->image; e.patch = p->patch; e.C = C;
-    e.M = M; e.S = TL + 1; e.mode = p->mode; e.eps = p->eps;
-    if (p->mode == 0) { e.cls_f32 = (const float*)p->cls; e.pos_f32 = (const float*)p->pos; e.lnw = p->lnw; e.lnb = p->lnb; e.x_f32 = (float*)p->out; }
-    else { e.bias = p->bias; e.cls_bf = (const bf16_t*)p->cls; e.pos_bf = (const bf16_t*)p->pos; e.x_bf = (bf16_t*)p->out; }
-    RUN(GVL_PROF_OTHER, 0, gvl_retile_patch_weight(p->W, Wt, C, p->Kp, p->patch, st));
-    const int rc = gvl_launch_patch_embed(e, st);
-    if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, rc == -1 ? "gvl_op_patch_embed: geometry outside the fused kernel" : "gvl_op_patch_embed: launch failed");
-    return 0;
-  }
-  bf16_t* pA = p->im2col;
-  if (!pA) { AALLOC(pA_, bf16_t, (size_t)M * p->Kp); pA = pA_; }
-  AALLOC(pO, bf16_t, (size_t)M * C);
-  GemmArgs gm = gemm(pA, p->Kp, p->W, pO, C, M, C, p->Kp);
-  if (p->mode == 1) gm.bias = p->bias;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_patchify(p->px, pA, p->n, p->T, p->image, p->patch, p->Kp, st));
-  RUN(GVL_PROF_GEMM, gvl_gemm_flops(gm), gvl_launch_gemm(gm, st));
-  if (p->mode == 0) RUN(GVL_PROF_OTHER, 0, gvl_launch_clip_embed_ln(pO, (const float*)p->cls, (const float*)p->pos, p->lnw, p->lnb, (float*)p->out, p->n, TL, C, p->eps, st));
-  else RUN(GVL_PROF_OTHER, 0, gvl_launch_iv2_embed(pO, (const bf16_t*)p->cls, (const bf16_t*)p->pos, (bf16_t*)p->out, p->n, TL, C, st));
-  return 0;
-}
-int gvl_op_patchify(gvl_ctx* ctx, const float* px, uint16_t* A, int n, int T, int image, int patch, int Kp, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!px || !A || n <= 0 || T <= 0 || image <= 0 || patch <= 0 || Kp <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_patchify: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_patchify(px, A, n, T, image, patch, Kp, st));
-  return 0;
-}
-int gvl_op_hd_merge(gvl_ctx* ctx, const float* f, const float* sub_gn, uint16_t* out, int n, int C, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!f || !sub_gn || !out || n <= 0 || C <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_hd_merge: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_hd_merge(f, sub_gn, out, n, C, st));
-  return 0;
-}
-int gvl_op_pool_spatial(gvl_ctx* ctx, const float* f, uint16_t* out, int n, int C, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!f || !out || n <= 0 || C <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_pool_spatial: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_pool_spatial(f, out, n, C, st));
-  return 0;
-}
-int gvl_op_pool_temporal(gvl_ctx* ctx, const uint16_t* f, uint16_t* out, int n, int T, int C, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!f || !out || n <= 0 || T <= 0 || C <= 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_pool_temporal: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_pool_temporal(f, out, n, T, C, st));
-  return 0;
-}
-int gvl_op_strip_cls(gvl_ctx* ctx, const void* x, void* y, int n, int S, int C, int elem_bytes, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!x || !y || n <= 0 || S < 2 || C <= 0 || (elem_bytes != 2 && elem_bytes != 4)) return fail(ctx, GVL_ERR_ARG, "gvl_op_strip_cls: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_strip_cls(x, y, n, S, C, elem_bytes, st));
-  return 0;
-}
-int gvl_op_bcast_row(gvl_ctx* ctx, const uint16_t* row, uint16_t* dst, int n, int stride_rows, int row_off, int cols, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!row || !dst || n <= 0 || cols <= 0 || row_off < 0 || row_off >= stride_rows) return fail(ctx, GVL_ERR_ARG, "gvl_op_bcast_row: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  RUN(GVL_PROF_OTHER, 0, gvl_launch_bcast_row(row, dst, n, stride_rows, row_off, cols, st));
-  return 0;
-}
-// operator-level entry for the WHOLE GemvArgs surface (tests/test_gpu_decode_proj.py): row-major operands in, private tiled / quantised copies made here, every launcher
-// refusal returned as GVL_ERR_ARG before anything is written.  See include/gvl.h for the fields.  gvl_op_decode_proj checks the descriptor, decode_proj_run does the work.
-static int decode_proj_run(gvl_ctx* ctx, const gvl_decode_proj* p, hipStream_t st, const char* who);
-int gvl_op_decode_proj(gvl_ctx* ctx, const gvl_decode_proj* p, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: null descriptor");
-  hipStream_t st = (hipStream_t)stream;
-  const char* bad = nullptr;
-  const int N = p->N, K = p->K, B = p->batch;
-  if (N <= 0 || K <= 0 || !p->W || !p->x) bad = "N, K > 0 and W, x set";
-  else if (B < 1 || B > GVL_MAX_DECODE_BATCH) bad = "1 <= batch <= 16";
-  else if (p->path < 0 || p->path > 1 || p->w_fmt < 0 || p->w_fmt > 2) bad = "path 0 / 1, w_fmt 0 / 1 / 2";
-  else if (K % (p->path == 0 ? 32 : 8)) bad = "K % 32 == 0 (tile order; the VALU GEMV: K % 8 == 0)";
-  else if (p->act != GVL_ACT_NONE && p->act != GVL_ACT_SILU_MUL) bad = "act is NONE or SILU_MUL";
-  else if (p->x_is_tiled && (p->norm_w || p->path == 1)) bad = "a tiled x feeds the skinny GEMM without norm_w only";
-  else if (p->path == 1 && (p->variant || p->w_fmt || p->out_tiled || p->sq_in || p->sq_out || p->out_tiled2)) bad = "the VALU GEMV has no variants, quantised weights, tiled outputs or fused-norm sums";
-  else if (p->out_stride < 0 || (p->out_stride && p->out_stride < (p->act == GVL_ACT_SILU_MUL ? N / 2 : N))) bad = "out_stride >= the output row length";
-  else if (!p->rope_on && !p->out_bf16 && !p->out_f32) bad = "an output buffer";
-  else if (p->path == 0 && B > 1 && !p->rope_on && (p->out_f32 || p->resid || (p->out_bf16 && !p->out_tiled)) && (p->out_stride ? p->out_stride : (p->act == GVL_ACT_SILU_MUL ? N / 2 : N)) % 4) bad = "out_stride % 4 == 0 for batch > 1 (8- and 16-byte epilogue stores)";
-  else if (p->rope_on) {
-    if (p->H < 1 || p->KV < 1 || p->Dr < 2 || (p->Dr & 1) || p->D < p->Dr || (long)N != (long)(p->H + 2 * p->KV) * p->Dr) bad = "rope: Dr even, D >= Dr, N == (H + 2 KV) Dr";
-    else if (!p->cos_s || !p->sin_s || !p->pos || !p->tables || !p->Q || !p->Kt || !p->Vt) bad = "rope: tables, pos, page tables, Q, Kt, Vt set";
-    else if (p->rope_switch > 0 && (!p->cos_l || !p->sin_l)) bad = "rope: long tables set when rope_switch > 0";
-    else if (p->max_pos < 1 || p->n_pages < 1 || p->table_stride < 1 || p->q_stride < p->H * p->D) bad = "rope: max_pos, n_pages, table_stride >= 1, q_stride >= H D";
-    else if (p->act || p->bias || p->resid) bad = "rope: no other epilogue";
-  }
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_decode_proj: ") + bad);
-  if (p->rope_on) {                                // the kernel trusts positions and page numbers: check them here, on the host
-    std::vector<int> pos(B), tab((size_t)B * p->table_stride);
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipMemcpy(pos.data(), p->pos, sizeof(int) * B, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(tab.data(), p->tables, sizeof(int) * tab.size(), hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b) {
-      if (pos[b] < 0 || pos[b] >= p->max_pos || (pos[b] >> 6) >= p->table_stride) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: position outside the tables");
-      const int page = tab[(size_t)b * p->table_stride + (pos[b] >> 6)];
-      if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_proj: page outside the pools");
-    }
-  }
-  return decode_proj_run(ctx, p, st, "gvl_op_decode_proj");
-}
-static int decode_proj_run(gvl_ctx* ctx, const gvl_decode_proj* p, hipStream_t st, const char* who) {
-  const int N = p->N, K = p->K, B = p->batch;
-  struct Bufs { void* v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Bufs() { for (void* q : v) if (q) hipFree(q); } } bufs;
-  void *&wc = bufs.v[0], *&wt = bufs.v[1], *&ws = bufs.v[2], *&xt = bufs.v[3];
-  const size_t nb16 = (size_t)((N + 15) / 16);
-  const int Dr = p->rope_on ? p->Dr : 0, nqk = p->rope_on ? p->H + p->KV : 0;
-  GemvArgs g; memset(&g, 0, sizeof(g));
-  int rc = 0;
-  if (p->path == 0) {
-    if (p->w_fmt) {                                // the quantisers rewrite their row-major source: work on a copy
-      if (K % (p->w_fmt == 2 ? 1024 : 512)) return fail(ctx, GVL_ERR_ARG, std::string(who) + ": FP8 needs K % 512 == 0, MXFP4 K % 1024 == 0");
-      HIPCHK(ctx, hipMalloc(&wc, (size_t)N * K * 2));
-      HIPCHK(ctx, hipMemcpyAsync(wc, p->W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st));
-      HIPCHK(ctx, hipMalloc(&wt, nb16 * 16 * K));
-      HIPCHK(ctx, hipMalloc(&ws, p->w_fmt == 1 ? (size_t)N * 4 : nb16 * (K / 128) * 16 * 4));
-      rc = p->w_fmt == 1 ? gvl_fp8_quantise_decode_weight((bf16_t*)wc, (unsigned char*)wt, (float*)ws, N, K, Dr, nqk, st)
-                         : gvl_mxfp4_quantise_decode_weight((bf16_t*)wc, (unsigned char*)wt, (unsigned*)ws, N, K, Dr, nqk, st);
-      g.wscale = (const float*)ws;
-    } else {
-      HIPCHK(ctx, hipMalloc(&wt, nb16 * 16 * K * 2));
-      rc = gvl_retile_decode_weight(p->W, (bf16_t*)wt, N, K, Dr, nqk, st);
-    }
-    g.W = (const bf16_t*)wt; g.w_fp8 = p->w_fmt;
-    if (!rc && !p->x_is_tiled && !p->norm_w) {
-      HIPCHK(ctx, hipMalloc(&xt, (size_t)16 * K * 2));
-      HIPCHK(ctx, hipMemsetAsync(xt, 0, (size_t)16 * K * 2, st));
-      rc = gvl_launch_rows_to_tiled(p->x, (bf16_t*)xt, B, K, K, st);
-      g.x = (const bf16_t*)xt;
-    } else g.x = p->x;
-  } else { g.W = p->W; g.x = p->x; }
-  g.N = N; g.K = K; g.batch = B; g.x_stride = K;
-  g.out_stride = p->out_stride ? p->out_stride : (p->act == GVL_ACT_SILU_MUL ? N / 2 : N);
-  g.norm_w = p->norm_w; g.eps = p->eps; g.bias = p->bias; g.resid = p->resid; g.act = p->act; g.out_bf16 = p->out_bf16; g.out_f32 = p->out_f32;
-  g.variant = p->variant; g.out_tiled = p->out_tiled; g.sq_in = p->sq_in; g.sq_n = p->sq_n; g.sq_out = p->sq_out; g.out_tiled2 = p->out_tiled2;
-  if (p->rope_on) {
-    g.rope_on = 1; g.cos_s = p->cos_s; g.sin_s = p->sin_s; g.cos_l = p->cos_l; g.sin_l = p->sin_l; g.rope_switch = p->rope_switch;
-    for (int b = 0; b < B; ++b) { g.pos_ptrs[b] = p->pos + b; g.tables[b] = p->tables + (size_t)b * p->table_stride; }
-    g.Q = p->Q; g.Kt = p->Kt; g.Vt = p->Vt; g.H = p->H; g.KV = p->KV; g.Dr = p->Dr; g.D = p->D; g.q_stride = p->q_stride;
-  }
-  if (!rc) { ProfScope _ps(ctx, GVL_PROF_GEMV, 2.0 * N * K, st); rc = p->path == 0 ? gvl_launch_dgemm(g, st) : gvl_launch_gemv(g, st); }
-  if (!rc && p->w_fmt) {                           // read back what the quantiser left, only once the launcher has accepted the call
-    if (p->w_deq) HIPCHK(ctx, hipMemcpyAsync(p->w_deq, wc, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st));
-    if (p->w_scale) HIPCHK(ctx, hipMemcpyAsync(p->w_scale, ws, p->w_fmt == 1 ? (size_t)N * 4 : nb16 * (K / 128) * 16 * 4, hipMemcpyDeviceToDevice, st));
-  }
-  const hipError_t se = hipStreamSynchronize(st);
-  if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, std::string(who) + (rc == -1 ? ": the launcher does not serve this combination" : ": launch failed"));
-  if (se != hipSuccess) return gvl_hipfail(ctx, se, (std::string(who) + ": hipStreamSynchronize").c_str());
-  return 0;
-}
-// y f32 [batch][N] = x W^T + bias on the skinny GEMM: the plain form of the descriptor above, under this entry's own precondition (any N; K % 256 == 0)
-int gvl_op_dgemm(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, int batch, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (N <= 0 || K <= 0 || K % 256 || batch < 1 || batch > GVL_MAX_DECODE_BATCH) return fail(ctx, GVL_ERR_ARG, "gvl_op_dgemm: K % 256 == 0 and 1 <= batch <= 16");
-  gvl_decode_proj p; memset(&p, 0, sizeof(p));
-  p.W = W; p.x = x; p.bias = bias; p.out_f32 = y; p.N = N; p.K = K; p.batch = batch;
-  return decode_proj_run(ctx, &p, (hipStream_t)stream, "gvl_op_dgemm");
-}
-// operator-level entry for the WHOLE DecodeAttnArgs surface (tests/test_gpu_decode_attn_exact.py): the caller supplies every device tensor, the workspace (part, counters)
-// included, so a test can poison it before a launch and look at it afterwards.  The kernels trust positions and page numbers: they are read back and checked here, on
-// the host, and every refusal comes back as GVL_ERR_ARG before anything is launched or written.  Otherwise DecodeAttnArgs is filled as decode_step fills it.
-int gvl_op_decode_attention(gvl_ctx* ctx, const gvl_decode_attn* p, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: null descriptor");
-  hipStream_t st = (hipStream_t)stream;
-  const int B = p->batch;
-  const char* bad = nullptr;
-  DecodeAttnLaunch l;
-  if (!p->q || !p->Kt || !p->Vt || !p->tables || !p->pos || !p->part || !p->counters || !p->out) bad = "q, Kt, Vt, tables, pos, part, counters, out set";
-  else if (B < 1 || B > GVL_MAX_DECODE_BATCH) bad = "1 <= batch <= 16";
-  else if (decode_attn_plan(DecodeAttnGeometry{p->H, p->KV, p->D, p->nsplit, B, p->hpb, p->cpb, p->gsplit}, GVL_DECODE_ATTN_KNOBS_DEFAULT, &l) < 0)
-    bad = "the launch plan does not serve this geometry (H % KV == 0, D 64 / 96 / 128, 1 <= nsplit <= 16)";
-  else if (p->Dout < 1 || p->Dout > p->D) bad = "1 <= Dout <= D";
-  else if (p->q_stride < p->H * p->D || (p->q_stride & 7) || ((uintptr_t)p->q & 15)) bad = "q_stride >= H D, q rows 16-byte aligned";
-  else if (!p->out_tiled && p->out_stride < p->H * p->Dout) bad = "out_stride >= H Dout";
-  else if (p->n_pages < 1 || p->table_stride < 1) bad = "n_pages, table_stride >= 1";
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_decode_attention: ") + bad);
-  std::vector<int> pos(B), tab((size_t)B * p->table_stride);
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  HIPCHK(ctx, hipMemcpy(pos.data(), p->pos, sizeof(int) * B, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(tab.data(), p->tables, sizeof(int) * tab.size(), hipMemcpyDeviceToHost));
-  int longest = 1;                                   // split count of the longest sequence: one per 4 pages of its own length, at most nsplit
-  for (int b = 0; b < B; ++b) {
-    if (pos[b] < 0 || (long long)pos[b] >= (long long)p->table_stride * 64) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: position outside the tables");
-    const int np = (pos[b] + 1 + 63) >> 6, n4 = (np + 3) >> 2, ns = n4 > p->nsplit ? p->nsplit : n4;
-    for (int i = 0; i < np; ++i) {
-      const int page = tab[(size_t)b * p->table_stride + i];
-      if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: page outside the pools");
-    }
-    longest = ns > longest ? ns : longest;
-  }
-  if ((long long)l.gsplit * l.cpb < longest) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_attention: gsplit * cpb is smaller than the longest sequence's split count (the ticket would never complete)");
-  DecodeAttnArgs a; memset(&a, 0, sizeof(a));
-  a.q = p->q; a.q_stride = p->q_stride; a.Kt = p->Kt; a.Vt = p->Vt;
-  for (int b = 0; b < B; ++b) { a.tables[b] = p->tables + (size_t)b * p->table_stride; a.pos_ptrs[b] = p->pos + b; }
-  a.part = p->part; a.counters = p->counters; a.batch = B; a.gsplit = p->gsplit; a.cpb = p->cpb; a.hpb = p->hpb;
-  a.out = p->out; a.out_stride = p->out_stride; a.out_tiled = p->out_tiled ? 1 : 0; a.H = p->H; a.KV = p->KV; a.D = p->D; a.Dout = p->Dout; a.nsplit = p->nsplit; a.scale = p->scale;
-  RUN(GVL_PROF_DECODE_ATTN, 0, gvl_launch_decode_attention(a, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  return 0;
-}
-// operator-level entry for the WHOLE QkvPostArgs surface and both launchers (tests/test_gpu_qkv_post.py).  The kernels trust page numbers, positions and the ragged
-// row offsets: the tables are read back and everything is checked here, on the host; every refusal comes back as GVL_ERR_ARG before anything is launched or written.
-int gvl_op_qkv_post(gvl_ctx* ctx, const gvl_qkv_post* p, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: null descriptor");
-  hipStream_t st = (hipStream_t)stream;
-  const int n = p->vl_n;
-  const char* bad = nullptr;
-  if (!p->qkv || !p->Kt || (!p->Q && !p->q_rs)) bad = "qkv, Kt and Q (or q_rs) set";
-  else if (p->mode < 0 || p->mode > 2) bad = "mode 0, 1 or 2";
-  else if (p->H < 1 || p->KV < 1 || p->B < 1 || p->n_pages < 1) bad = "H, KV, B, n_pages >= 1";
-  else if ((p->Dr & 7) || (p->mode == 2 && (p->Dr & 15)) || (p->D & 7) || p->D < p->Dr || p->Dr < 8 || p->Dr > 128) bad = "Dr % 8 == 0 (mode 2: % 16), 8 <= Dr <= 128, D % 8 == 0, D >= Dr";
-  else if ((p->ld & 7) || (long long)p->ld < (long long)(p->H + 2 * p->KV) * p->Dr) bad = "ld % 8 == 0, ld >= (H + 2 KV) Dr";
-  else if (p->mode == 1 && (!p->qn || !p->kn)) bad = "mode 1 needs qn and kn";
-  else if (p->mode == 2 && (!p->cos || !p->sin || p->max_pos < 1)) bad = "mode 2 needs cos, sin and max_pos";
-  else if (p->q_rs && p->mode != 1) bad = "q_rs is a mode 1 form";
-  else if (p->q_rs && !p->k_ones) bad = "q_rs needs k_ones";
-  else if ((p->ones_row || p->k_ones) && p->D == p->Dr) bad = "ones_row / k_ones need D > Dr";
-  else if (n < 0 || n > GVL_MAX_PREFILL_BATCH) bad = "0 <= vl_n <= 8";
-  else if (p->ext && (n < 1 || p->q_rs || !p->Vt)) bad = "ext needs a ragged group, Vt and no q_rs";
-  else if (n && (p->mode != 2 || p->B != 1 || p->pos0 != 0 || p->block_table)) bad = "a ragged group needs mode 2, B == 1, pos0 == 0 and no block_table";
-  else if (!n && (p->S < 1 || p->pos0 < 0)) bad = "S >= 1, pos0 >= 0";
-  else if (!n && p->Vt && (p->pos0 & 63)) bad = "Vt needs pos0 % 64 == 0 (V^T pages are written whole)";
-  else if (!n && !p->block_table && p->pos0) bad = "pos0 > 0 needs a block table";
-  else if (!n && p->block_table && p->max_pages < 1) bad = "max_pages >= 1";
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_qkv_post: ") + bad);
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  // per sequence: first position, rows and the table as the launch will index it (null: implicit pages)
-  struct Member { long long pos0, rows, page0; std::vector<int> tab; bool has_tab; };
-  std::vector<Member> ms;
-  if (n) {
-    if (p->vl_rows[0] != 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: vl_rows[0] must be 0");
-    for (int u = 0; u < n; ++u) {
-      const long long rows = (long long)p->vl_rows[u + 1] - p->vl_rows[u];
-      if (rows < 1) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: an empty ragged member");
-      if (!p->vl_tables[u] || p->table_len[u] < 1) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: every ragged member needs a block table");
-      const int pos0 = p->ext ? p->vl_pos0[u] : 0;
-      if (pos0 < 0 || (pos0 & 63)) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: vl_pos0 must be a multiple of 64");
-      Member m{pos0, rows, 0, std::vector<int>((size_t)p->table_len[u]), true};
-      HIPCHK(ctx, hipMemcpy(m.tab.data(), p->vl_tables[u], sizeof(int) * m.tab.size(), hipMemcpyDeviceToHost));
-      ms.push_back(std::move(m));
-    }
-  } else {
-    std::vector<int> all;
-    if (p->block_table) { all.resize((size_t)p->B * p->max_pages); HIPCHK(ctx, hipMemcpy(all.data(), p->block_table, sizeof(int) * all.size(), hipMemcpyDeviceToHost)); }
-    const long long nt = ((long long)p->S + 63) >> 6;
-    for (int b = 0; b < p->B; ++b) {
-      Member m{p->pos0, p->S, b * nt, {}, p->block_table != nullptr};
-      if (p->block_table) m.tab.assign(all.begin() + (size_t)b * p->max_pages, all.begin() + (size_t)(b + 1) * p->max_pages);
-      ms.push_back(std::move(m));
-    }
-  }
-  std::vector<char> used((size_t)p->n_pages, 0);
-  for (const Member& m : ms) {
-    const long long end = m.pos0 + m.rows;                                   // one past the last position written
-    if (p->mode == 2 && end > p->max_pos) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: a position outside the cos / sin tables");
-    const long long t0 = m.pos0 >> 6, t1 = (end + 63) >> 6;
-    if (m.has_tab && t1 > (long long)m.tab.size()) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: a block table shorter than ceil((pos0 + S) / 64)");
-    for (long long t = t0; t < t1; ++t) {
-      const long long page = m.has_tab ? m.tab[(size_t)t] : m.page0 + t;
-      if (page < 0 || page >= p->n_pages) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: page outside the pools");
-      if (used[(size_t)page]) return fail(ctx, GVL_ERR_ARG, "gvl_op_qkv_post: a page named twice among the pages the launch writes");
-      used[(size_t)page] = 1;
-    }
-  }
-  QkvPostArgs a; memset(&a, 0, sizeof(a));
-  a.qkv = p->qkv; a.ld = p->ld; a.Q = p->Q; a.Kt = p->Kt; a.Vt = p->Vt; a.block_table = p->block_table; a.max_pages = p->max_pages;
-  a.B = p->B; a.S = p->S; a.H = p->H; a.KV = p->KV; a.Dr = p->Dr; a.D = p->D; a.mode = p->mode; a.qn = p->qn; a.kn = p->kn; a.eps = p->eps;
-  a.cos = p->cos; a.sin = p->sin; a.pos0 = p->pos0; a.ones_row = p->ones_row ? 1 : 0; a.k_ones = p->k_ones ? 1 : 0; a.q_rs = p->q_rs; a.vl_n = n;
-  for (int u = 0; u <= n; ++u) a.vl_rows[u] = p->vl_rows[u];
-  for (int u = 0; u < n; ++u) { a.vl_tables[u] = p->vl_tables[u]; a.vl_pos0[u] = p->vl_pos0[u]; }
-  if (p->ext) RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post_ext(a, st));
-  else RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(a, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  return 0;
-}
-// operator-level entry for the paged forms of attn_fwd_kernel behind a cached prefix (tests/test_gpu_prefill_attn.py): a caller-supplied block table with qpos0 / Sk, the
-// ragged grid and the ragged-extend grid, on caller-owned pages.  The plans are asked first (a refusal names them), then the tables are read back and every page the
-// launch will read is checked: GVL_ERR_ARG before anything is launched or written.
-int gvl_op_prefill_attention(gvl_ctx* ctx, const gvl_prefill_attn* p, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_prefill_attention: null descriptor");
-  hipStream_t st = (hipStream_t)stream;
-  const int n = p->vl_n;
-  const bool O16 = ((uintptr_t)p->O & 15) == 0;
-  const char* bad = nullptr;
-  if (!p->Q || !p->Kt || !p->Vt || !p->O) bad = "Q, Kt, Vt, O set";
-  else if (p->n_pages < 1) bad = "n_pages >= 1";
-  else if (n < 0 || n > GVL_MAX_PREFILL_BATCH) bad = "0 <= vl_n <= 8";
-  else if (p->ext && n < 1) bad = "ext needs a ragged group";
-  else if (!n && (!p->block_table || p->max_pages < 1)) bad = "the single form needs a block table (implicit pages: gvl_op_attention)";
-  else if (p->ring != 0 && p->ring != 2 && p->ring != 3) bad = "ring 0, 2 or 3";
-  else if (p->ext) {
-    AttnExtGeometry g{};
-    g.H = p->H; g.KV = p->KV; g.D = p->D; g.Dout = p->Dout; g.causal = p->causal; g.vl_n = n; g.O16 = O16;
-    for (int u = 0; u <= n; ++u) g.vl_rows[u] = p->vl_rows[u];
-    for (int u = 0; u < n; ++u) { g.vl_tables[u] = p->vl_tables[u] != nullptr; g.vl_pos0[u] = p->vl_pos0[u]; }
-    AttnExtLaunch l;
-    if (p->B != 1 || p->Sk || p->qpos0 || p->block_table || attn_ext_plan(g, GVL_ATTN_KNOBS_DEFAULT, &l) < 0)
-      bad = "attn_ext_plan does not serve this launch (causal, B == 1, Sk == qpos0 == 0, no block_table, vl_rows[0] == 0, per member a table, >= 1 query, vl_pos0 % 64 == 0)";
-  } else {
-    AttnGeometry g{};
-    g.B = p->B; g.H = p->H; g.KV = p->KV; g.S = p->S; g.D = p->D; g.Dout = p->Dout; g.Sk = p->Sk; g.qpos0 = p->qpos0; g.causal = p->causal; g.ring = p->ring;
-    g.max_pages = p->max_pages; g.vl_n = n; g.block_table = p->block_table != nullptr; g.O16 = O16;
-    for (int u = 0; u <= n; ++u) g.vl_rows[u] = p->vl_rows[u];
-    for (int u = 0; u < n; ++u) g.vl_tables[u] = p->vl_tables[u] != nullptr;
-    AttnLaunch l[GVL_ATTN_MAX_LAUNCHES];
-    if (attn_plan(g, GVL_ATTN_KNOBS_DEFAULT, l) < 0 || (n && p->vl_rows[0] != 0))
-      bad = "attn_plan does not serve this launch (D 64 / 96 / 128, Dout % 8 == 0, H % KV == 0, Sk == 0 or Sk >= qpos0 + S; ragged: causal, B == 1, Sk == qpos0 == 0, no block_table, per member a table and 1 .. S queries)";
-  }
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_prefill_attention: ") + bad);
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  auto check = [&](const std::vector<int>& tab, long long qpos0, long long S, long long Sk) -> const char* {   // one sequence: the key tiles its blocks read
-    const long long tiles = p->causal ? ((qpos0 + S - 1) >> 6) + 1 : (Sk + 63) >> 6;
-    if (tiles > (long long)tab.size()) return "a block table shorter than the key tiles the launch reads";
-    for (long long t = 0; t < tiles; ++t) if (tab[(size_t)t] < 0 || tab[(size_t)t] >= p->n_pages) return "page outside the pools";
-    return nullptr;
-  };
-  if (n) {
-    for (int u = 0; u < n && !bad; ++u) {
-      if (p->table_len[u] < 1) { bad = "table_len >= 1"; break; }
-      std::vector<int> tab((size_t)p->table_len[u]);
-      HIPCHK(ctx, hipMemcpy(tab.data(), p->vl_tables[u], sizeof(int) * tab.size(), hipMemcpyDeviceToHost));
-      const long long S = (long long)p->vl_rows[u + 1] - p->vl_rows[u], q0 = p->ext ? p->vl_pos0[u] : 0;
-      bad = check(tab, q0, S, q0 + S);
-    }
-  } else {
-    std::vector<int> all((size_t)p->B * p->max_pages);
-    HIPCHK(ctx, hipMemcpy(all.data(), p->block_table, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
-    for (int b = 0; b < p->B && !bad; ++b)
-      bad = check(std::vector<int>(all.begin() + (size_t)b * p->max_pages, all.begin() + (size_t)(b + 1) * p->max_pages), p->qpos0, p->S, p->Sk > 0 ? p->Sk : p->S);
-  }
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_prefill_attention: ") + bad);
-  AttnArgs a; memset(&a, 0, sizeof(a));
-  a.Q = p->Q; a.Kt = p->Kt; a.Vt = p->Vt; a.O = p->O; a.block_table = p->block_table; a.max_pages = p->max_pages;
-  a.B = p->B; a.H = p->H; a.KV = p->KV; a.S = p->S; a.D = p->D; a.Dout = p->Dout; a.Sk = p->Sk; a.qpos0 = p->qpos0; a.scale = p->scale; a.causal = p->causal ? 1 : 0; a.ring = p->ring;
-  a.vl_n = n;
-  for (int u = 0; u <= n; ++u) a.vl_rows[u] = p->vl_rows[u];
-  for (int u = 0; u < n; ++u) { a.vl_tables[u] = p->vl_tables[u]; a.vl_pos0[u] = p->ext ? p->vl_pos0[u] : 0; }
-  if (p->ext) RUN(GVL_PROF_ATTN, 0, gvl_launch_attention_ext(a, st));
-  else RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  return 0;
-}
-// operator-level entry for the attention launch of an InternVideo2 block (tests/test_gpu_iv2_attn.py): the ONES instantiations of attn_fwd_kernel, the q-normalised-on-load
-// operand mode and attn_iv2_pipe_kernel, on caller-owned buffers.  ONE gvl_launch_attention (two kernel launches where the plan splits the rows), no arena allocation,
-// no qkv_post; the form, pipe and pipe_rows come from the descriptor, never from gvl_debug_set.  The plan is asked first: GVL_ERR_ARG before anything is launched or written.
-int gvl_op_iv2_attention(gvl_ctx* ctx, const gvl_iv2_attn* p, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  if (!p) return fail(ctx, GVL_ERR_ARG, "gvl_op_iv2_attention: null descriptor");
-  hipStream_t st = (hipStream_t)stream;
-  const char* bad = nullptr;
-  const int f = p->form;
-  if (f < 0 || f > 2) bad = "form 0, 1 or 2";
-  else if (!p->Kt || !p->out) bad = "Kt and out set";
-  else if (f == 0 && (!p->Q || !p->Vt || p->qkv || p->q_rs || p->q_nw)) bad = "form 0 takes Q, Kt, Vt and no qkv, q_rs, q_nw";
-  else if (f == 1 && (!p->Q || !p->qkv || p->Vt || p->q_rs || p->q_nw)) bad = "form 1 takes Q, Kt, qkv and no Vt, q_rs, q_nw";
-  else if (f == 2 && (!p->qkv || !p->q_rs || !p->q_nw || p->Q || p->Vt)) bad = "form 2 takes qkv, Kt, q_rs, q_nw and no Q, Vt";
-  else if (p->B < 1 || p->S < 1 || p->H < 1) bad = "B, S, H >= 1";
-  else if ((p->Dr & 7) || p->Dr <= 64 || p->Dr >= 96) bad = "Dr 72, 80 or 88 (a padded head on the D = 96 kernels: the ones row needs D > Dr)";
-  else if (f == 2 && p->Dr != 88) bad = "form 2 needs Dr == 88";
-  else if (f == 2 && (p->pipe < 0 || p->pipe > 2)) bad = "pipe 0, 1 or 2";
-  else if (f == 2 && p->pipe_rows != 0 && p->pipe_rows != 256) bad = "pipe_rows 0 or 256";
-  else if (f && ((p->ld & 7) || (long long)p->ld < 3ll * p->H * p->Dr)) bad = "ld % 8 == 0, ld >= 3 H Dr";
-  if (bad) return fail(ctx, GVL_ERR_ARG, std::string("gvl_op_iv2_attention: ") + bad);
-  AttnArgs a; memset(&a, 0, sizeof(a));
-  a.Q = p->Q; a.Kt = p->Kt; a.Vt = p->Vt; a.O = p->out; a.B = p->B; a.H = p->H; a.KV = p->H; a.S = p->S; a.D = pad_head(p->Dr); a.Dout = p->Dr;
-  a.scale = p->scale; a.causal = 0; a.ones_row = 1;
-  if (f) { a.Vrows = p->qkv + (size_t)2 * p->H * p->Dr; a.v_ld = p->ld; }
-  if (f == 2) { a.Qrows = p->qkv; a.q_ld = p->ld; a.q_rs = p->q_rs; a.q_nw = p->q_nw; a.k_ones = 1; a.pipe = p->pipe; a.pipe_rows = p->pipe_rows; }
-  {
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    AttnGeometry g{};
-    g.B = a.B; g.H = a.H; g.KV = a.KV; g.S = a.S; g.D = a.D; g.Dout = a.Dout; g.ones_row = 1; g.k_ones = a.k_ones; g.pipe = a.pipe; g.pipe_rows = a.pipe_rows;
-    g.v_ld = a.v_ld; g.q_ld = a.q_ld; g.Vrows = a.Vrows; g.Qrows = a.Qrows; g.q_rs = a.q_rs; g.q_nw = a.q_nw;
-    g.O16 = al16(a.O); g.Vrows16 = al16(a.Vrows); g.Qrows16 = al16(a.Qrows); g.Krows16 = true; g.q_nw16 = al16(a.q_nw);
-    AttnLaunch l[GVL_ATTN_MAX_LAUNCHES];
-    const int n = attn_plan(g, GVL_ATTN_KNOBS_DEFAULT, l);
-    if (n < 0) return fail(ctx, GVL_ERR_ARG, "gvl_op_iv2_attention: attn_plan does not serve this launch (at most 256 key tiles, out / qkv / q_nw 16-byte aligned, a 64-row tile of qkv below 4 GiB)");
-    if (!l[0].ONES) return fail(ctx, GVL_ERR_ARG, "gvl_op_iv2_attention: the plan chose no ONES kernel for this launch");
-  }
-  RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  return 0;
-}
-// micro-benchmark of the decode projection kernels on synthetic operands (tools/decode_bench.py): mode 0 = skinny MFMA GEMM (variant:
-// see gvl_launch_dgemm), 1 = round-1 VALU GEMV (batch 1, 2, 4), 2 / 3 = the same two with the fused RMSNorm prologue (batch <= 4).  `rounds` distinct weight matrices are cycled so that the
-// Infinity Cache cannot hold the stream; returns the average microseconds per launch.
-int gvl_op_decode_bench(gvl_ctx* ctx, int N, int K, int batch, int mode, int variant, int rounds, int iters, double* us_per_launch, void* stream) {
-  if (!ctx || !us_per_launch || N <= 0 || K <= 0 || K % 256 || batch < 1 || batch > GVL_MAX_DECODE_BATCH || rounds < 1 || iters < 1) return fail(ctx, GVL_ERR_ARG, "gvl_op_decode_bench: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t wbytes = (size_t)((N + 15) / 16) * 16 * K * 2;
-  char *w = nullptr, *x = nullptr, *y = nullptr;
-  HIPCHK(ctx, hipMalloc((void**)&w, wbytes * rounds));
-  HIPCHK(ctx, hipMalloc((void**)&x, (size_t)16 * K * 2));
-  HIPCHK(ctx, hipMalloc((void**)&y, (size_t)16 * N * 4));
-  hipMemsetAsync(w, 0x11, wbytes * rounds, st); hipMemsetAsync(x, 0x22, (size_t)16 * K * 2, st);
-  hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  int rc = 0;
-  for (int pass = 0; pass < 2 && !rc; ++pass) {          // pass 0 = warm-up
-    if (pass == 1) hipEventRecord(e0, st);
-    for (int it = 0; it < (pass ? iters : 3) && !rc; ++it) {
-      GemvArgs g; memset(&g, 0, sizeof(g)); g.W = (const bf16_t*)(w + wbytes * (it % rounds)); g.N = N; g.K = K; g.x = (const bf16_t*)x; g.out_f32 = (float*)y;
-      g.batch = batch; g.x_stride = K; g.out_stride = N; g.variant = variant;
-      if (mode == 2 || mode == 3) { g.norm_w = (const bf16_t*)x; g.eps = 1e-5f; }   // fused RMSNorm prologue: 2 = skinny GEMM (LDS), 3 = VALU GEMV
-      rc = (mode == 1 || mode == 3) ? gvl_launch_gemv(g, st) : gvl_launch_dgemm(g, st);
-    }
-    if (pass == 1) hipEventRecord(e1, st);
-  }
-  hipStreamSynchronize(st);
-  float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0); hipEventDestroy(e1);
-  hipFree(w); hipFree(x); hipFree(y);
-  if (rc) return fail(ctx, rc == -1 ? GVL_ERR_ARG : GVL_ERR_HIP, "gvl_op_decode_bench: launch failed (unsupported variant / geometry)");
-  *us_per_launch = 1e3 * ms / iters;
-  return 0;
-}
-int gvl_op_gemv(gvl_ctx* ctx, const uint16_t* W, const uint16_t* x, const float* bias, float* y, int N, int K, void* stream) {
-  if (!ctx) return GVL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  GemvArgs g; memset(&g, 0, sizeof(g)); g.W = W; g.N = N; g.K = K; g.x = x; g.bias = bias; g.out_f32 = y;
-  RUN(GVL_PROF_GEMV, 2.0 * N * K, gvl_launch_gemv(g, st));
   return 0;
 }
 

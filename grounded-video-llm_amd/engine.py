@@ -1091,47 +1091,21 @@ class Engine:
         """gvl_op_decode_proj (include/gvl.h): one decode projection with any prologue / epilogue.  W bf16 [N, K], x bf16 [B, K] (or the tiled
         stream with x_is_tiled=1); every other field of gvl_decode_proj by keyword -- tensors for the pointer fields (outputs are written in
         place, the caller allocates and pre-fills them), ints / floats for the rest.  Raises GvlError (status ERR_ARG) on a refusal."""
-        d = L.GvlDecodeProj()
-        names = {n: t for n, t in L.GvlDecodeProj._fields_}
-        N, K = W.shape
-        keep = [W.contiguous(), x.contiguous()]
-        d.N, d.K, d.W, d.x = N, K, keep[0].data_ptr(), keep[1].data_ptr()
-        d.batch = int(kw.pop("batch", x.shape[0]))
-        for k, v in kw.items():
-            if k not in names or k in ("W", "x", "N", "K"):
-                raise TypeError(f"op_decode_proj: unknown field {k}")
-            if v is None:
-                continue
-            if names[k] is C.c_void_p:
-                assert v.is_contiguous() and v.device.type == "cuda", k
-                keep.append(v)
-                setattr(d, k, v.data_ptr())
-            else:
-                setattr(d, k, v)
-        self._chk(self.lib.gvl_op_decode_proj(self.ctx, C.byref(d), self.stream), "gvl_op_decode_proj")
+        for k in ("W", "x", "N", "K"):
+            if k in kw:
+                raise TypeError(f"gvl_op_decode_proj: unknown field {k}")
+        kw = dict(kw, N=W.shape[0], K=W.shape[1], W=W.contiguous(), x=x.contiguous(), batch=int(kw.get("batch", x.shape[0])))
+        self._op_desc(L.GvlDecodeProj, self.lib.gvl_op_decode_proj, "gvl_op_decode_proj", kw)
 
     def op_decode_attention(self, **kw):
         """gvl_op_decode_attention (include/gvl.h): one decode-attention launch.  Every field of gvl_decode_attn by keyword -- device tensors for the
         pointer fields (out, part and counters are written in place: the caller allocates and pre-fills them), ints / floats for the rest.  Raises
         GvlError (status ERR_ARG) on a refusal."""
-        d = L.GvlDecodeAttn()
-        names = {n: t for n, t in L.GvlDecodeAttn._fields_}
-        keep = []
-        for k, v in kw.items():
-            if k not in names:
-                raise TypeError(f"op_decode_attention: unknown field {k}")
-            if v is None:
-                continue
-            if names[k] is C.c_void_p:
-                assert v.is_contiguous() and v.device.type == "cuda", k
-                keep.append(v)
-                setattr(d, k, v.data_ptr())
-            else:
-                setattr(d, k, v)
-        self._chk(self.lib.gvl_op_decode_attention(self.ctx, C.byref(d), self.stream), "gvl_op_decode_attention")
+        self._op_desc(L.GvlDecodeAttn, self.lib.gvl_op_decode_attention, "gvl_op_decode_attention", kw)
 
-    def _op_paged(self, struct, fn, what, kw):
-        """fill a descriptor that carries a ragged group (vl_rows / vl_tables / vl_pos0 / table_len arrays) from keywords and call fn"""
+    def _op_desc(self, struct, fn, what, kw):
+        """fill a descriptor from keywords and call fn: an unknown field raises TypeError, None is skipped, a pointer field takes a contiguous device tensor (kept alive
+        over the call); the arrays of a ragged group -- vl_rows / vl_pos0 / table_len: lists of ints, vl_tables: a list of device int32 tensors"""
         d = struct()
         names = {n: t for n, t in struct._fields_}
         keep = []
@@ -1163,17 +1137,17 @@ class Engine:
         """gvl_op_qkv_post (include/gvl.h): one launch of the qkv_post pass.  Every field of gvl_qkv_post by keyword -- device tensors for the pointer fields (Q, Kt,
         Vt and q_rs are written in place: the caller allocates and pre-fills them), ints / floats for the rest; vl_rows, vl_pos0 and table_len take lists of ints,
         vl_tables a list of device int32 tensors (table_len defaults to their lengths).  Raises GvlError (status ERR_ARG) on a refusal."""
-        self._op_paged(L.GvlQkvPost, self.lib.gvl_op_qkv_post, "gvl_op_qkv_post", kw)
+        self._op_desc(L.GvlQkvPost, self.lib.gvl_op_qkv_post, "gvl_op_qkv_post", kw)
 
     def op_prefill_attention(self, **kw):
         """gvl_op_prefill_attention (include/gvl.h): one paged prefill-attention launch on caller-owned pages.  Every field of gvl_prefill_attn by keyword, as
         op_qkv_post takes them (O is written in place).  Raises GvlError (status ERR_ARG) on a refusal."""
-        self._op_paged(L.GvlPrefillAttn, self.lib.gvl_op_prefill_attention, "gvl_op_prefill_attention", kw)
+        self._op_desc(L.GvlPrefillAttn, self.lib.gvl_op_prefill_attention, "gvl_op_prefill_attention", kw)
 
     def op_iv2_attention(self, **kw):
         """gvl_op_iv2_attention (include/gvl.h): the attention launch of one InternVideo2 block on caller-owned buffers.  Every field of gvl_iv2_attn by keyword, as
         op_qkv_post takes them (out is written in place; a pointer field may be a view into a larger allocation).  Raises GvlError (status ERR_ARG) on a refusal."""
-        self._op_paged(L.GvlIv2Attn, self.lib.gvl_op_iv2_attention, "gvl_op_iv2_attention", kw)
+        self._op_desc(L.GvlIv2Attn, self.lib.gvl_op_iv2_attention, "gvl_op_iv2_attention", kw)
 
     def op_gemv(self, W, x, bias=None):
         N, K = W.shape

@@ -3,8 +3,8 @@
 design: only the plan can say which kernel a case exercised.
 
 The helpers that build a geometry the way a caller in the library does:
-  op_attention   gvl_op_attention (gvl_model.hip): gvl_debug_set vision_in_place / attn_ring choose the operand mode and the ring depth
-  op_iv2_attention   gvl_op_iv2_attention (gvl_model.hip): the descriptor's form / pipe / pipe_rows choose everything, no gvl_debug_set
+  op_attention   gvl_op_attention (gvl_ops.hip): gvl_debug_set vision_in_place / attn_ring choose the operand mode and the ring depth
+  op_iv2_attention   gvl_op_iv2_attention (gvl_ops.hip): the descriptor's form / pipe / pipe_rows choose everything, no gvl_debug_set
   iv2_block      the attention launch of an InternVideo2 block (iv2_encode, gvl_vision.hip): vision_in_place, attn_pipe, attn_pipe_rows
   decode_step    the decode-attention launch of decode_step (gvl_llm.hip): decode_attn_shape on the sequences' positions, then decode_attn_plan"""
 import functools
