@@ -16,7 +16,7 @@ TAG = os.environ.get("GVL_BUILD_TAG", "")
 OUT = os.path.join(HERE, f"libgvl_{TAG}.so" if TAG else "libgvl.so")
 SOURCES = ["gvl_gemm.hip", "gvl_gemm4.hip", "gvl_gemm4p.hip", "gvl_attn.hip", "gvl_elem.hip", "gvl_pick.hip", "gvl_decode.hip", "gvl_model.hip", "gvl_ops.hip", "gvl_vision.hip", "gvl_llm.hip", "gvl_host.hip", "gvl_pre.hip",
            "gvl_probe.hip", "gvl_patch.hip", "gvl_logits.hip", "gvl_select.hip", "gvl_beam.hip", "gvl_contrastive.hip", "gvl_search.hip"]
-CSRC_HEADERS = ["gvl_internal.h", "gvl_ctx.h", "gvl_seq_table.h", "gvl_admit.h", "gvl_op_check.h", "gvl_beam.h", "gvl_contrastive.h", "gvl_grammar.h", "gvl_model.h", "gvl_gemm_epi.h", "gvl_decode_epi.h", "gvl_gemm_plan.h", "gvl_attn_plan.h", "gvl_prefill_plan.h", "gvl_decode_plan.h", "gvl_limits.h", "gvl_gemm4_loop.inc", "gvl_gemm4p_loop.inc", "gvl_gemm4p_operands.inc"]
+CSRC_HEADERS = ["gvl_internal.h", "gvl_ctx.h", "gvl_seq_table.h", "gvl_admit.h", "gvl_op_check.h", "gvl_beam.h", "gvl_contrastive.h", "gvl_grammar.h", "gvl_model.h", "gvl_gemm_epi.h", "gvl_decode_epi.h", "gvl_gemm_plan.h", "gvl_attn_plan.h", "gvl_prefill_plan.h", "gvl_decode_plan.h", "gvl_vision_plan.h", "gvl_limits.h", "gvl_gemm4_loop.inc", "gvl_gemm4p_loop.inc", "gvl_gemm4p_operands.inc"]
 HEADERS = CSRC_HEADERS + [os.path.join("..", "..", "include", "gvl.h")]   # what every object is rebuilt for
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result", "-Wno-cuda-compat",
          # MFMA accumulators in VGPRs (gfx950 has a unified file): no v_accvgpr_read/write copies around the softmax / epilogue VALU

@@ -161,7 +161,7 @@ int llm_prefill(gvl_ctx* ctx, Seq* const* sqs, int nb, const bf16_t* const* embe
     group_table = tb;
   }
   for (int b = 0; b < nb; ++b) RUN(GVL_PROF_OTHER, 0, gvl_launch_copy_bytes(embeds[b], x + (size_t)off[b] * Hd, (size_t)lens[b] * Hd * 2, st));
-  // fused RMSNorm (see iv2_encode): o_proj / down_proj leave the row statistics of the new residual stream, qkv_proj / gate_up_proj consume the raw
+  // fused RMSNorm (see gvl_vision_plan.h): o_proj / down_proj leave the row statistics of the new residual stream, qkv_proj / gate_up_proj consume the raw
   // stream with the norm weight folded in and scale their accumulator rows; layer 0's input norm keeps the pass
   const int NBLK = Hd / 64;
   const bool nf = plan.nf;

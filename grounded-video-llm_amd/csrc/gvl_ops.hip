@@ -5,6 +5,7 @@
 // gvl_op_check.h -- host-only, tested on a CPU -- and is returned before anything is launched or written.
 #include "gvl_model.h"
 #include "gvl_op_check.h"
+#include "gvl_vision_plan.h"
 
 using namespace gvlm;
 
@@ -156,14 +157,14 @@ int gvl_op_attention(gvl_ctx* ctx, const uint16_t* q, const uint16_t* k, const u
   const int tiles = (S + 63) / 64;
   ArenaScope arena_scope(ctx->arena_off);
   AALLOC(Q, bf16_t, (size_t)B * H * S * D); AALLOC(Kt, bf16_t, (size_t)B * tiles * KV * 64 * D); AALLOC(Vt, bf16_t, (size_t)B * tiles * KV * 64 * D);
-  // non-causal (vision) attention reads v -- and, when no head-dim padding is needed, q and k -- in place, exactly as the towers do
+  // non-causal (vision) attention reads v -- and, when no head-dim padding is needed, q and k -- in place: the towers' own decision (gvl_vision_plan.h), CLIP's form
   const int ld = (H + 2 * KV) * Dr;
-  const bool v_rows = ctx->dbg.vision_in_place && !causal && D != 128, qk_rows = ctx->dbg.vision_in_place == 1 && v_rows && D == Dr && D == 64;
-  if (!qk_rows) { QkvPostArgs p; memset(&p, 0, sizeof(p)); p.qkv = q; p.ld = ld; p.Q = Q; p.Kt = Kt; p.Vt = v_rows ? nullptr : Vt; p.B = B; p.S = S; p.H = H; p.KV = KV; p.Dr = Dr; p.D = D; p.mode = 0;
+  const VisionOperandPath path = vision_operand_path(ctx->dbg.vision_in_place, D, Dr, causal != 0, GVL_TOWER_CLIP);
+  if (path.qkv_post) { QkvPostArgs p; memset(&p, 0, sizeof(p)); p.qkv = q; p.ld = ld; p.Q = Q; p.Kt = Kt; p.Vt = path.vt_pages ? Vt : nullptr; p.B = B; p.S = S; p.H = H; p.KV = KV; p.Dr = Dr; p.D = D; p.mode = 0;
     RUN(GVL_PROF_OTHER, 0, gvl_launch_qkv_post(p, st)); }
   { AttnArgs a; memset(&a, 0, sizeof(a)); a.Q = Q; a.Kt = Kt; a.Vt = Vt; a.O = out; a.B = B; a.H = H; a.KV = KV; a.S = S; a.D = D; a.Dout = Dr; a.scale = scale; a.causal = causal; a.ring = ctx->dbg.attn_ring;
-    if (v_rows) { a.Vrows = v; a.v_ld = ld; }
-    if (qk_rows) { a.Qrows = q; a.Krows = k; a.q_ld = a.k_ld = ld; }
+    if (!path.vt_pages) { a.Vrows = v; a.v_ld = ld; }
+    if (path.qk_rows) { a.Qrows = q; a.Krows = k; a.q_ld = a.k_ld = ld; }
     RUN(GVL_PROF_ATTN, gvl_attn_flops(a), gvl_launch_attention(a, st)); }
   return 0;
 }

@@ -25,6 +25,7 @@
 // order): results agree with it to fp32 rounding before the bf16 round, not bit for bit (tests: both paths against the reference goldens,
 // and against each other).
 #include "gvl_internal.h"
+#include "gvl_vision_plan.h"
 
 #define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -3)
 
@@ -272,16 +273,15 @@ __global__ __launch_bounds__(PE_NW * 64, 2) void patch_embed_kernel(const PatchE
   }
 }
 
-// 0 launched; -1 geometry outside this kernel (the caller takes the three-pass path); -3 launch error
+// 0 launched; -1 geometry outside this kernel (patch_embed_fused_ok, gvl_vision_plan.h: the towers ask it first and take the three-pass path) or a missing operand; -3 launch error
 int gvl_launch_patch_embed(const PatchEmbedArgs& a, hipStream_t st) {
   const int p = a.patch;
-  if (p != 14 || a.image % p || a.C % 128 || (a.C != 1024 && a.C != 1408) || a.M <= 0 || a.T <= 0) return -1;
-  if ((size_t)a.n_img * 3 * a.T * a.image * a.image >= 0xffffffffull) return -1;      // 32-bit pixel offsets
+  if (!patch_embed_fused_ok(a.mode == 0 ? GVL_TOWER_CLIP : GVL_TOWER_IV2, a.n_img, a.T, a.image, p, a.C, a.M)) return -1;
   const int ASTR = p * 32 + 16;
   const int lds = 2 * PE_BM * ASTR;
   const int tiles = (a.M + PE_BM - 1) / PE_BM, grid = tiles + (a.n_img + PE_NW - 1) / PE_NW;
   if (a.mode == 0) {
-    if (a.C != 1024 || !a.x_f32 || !a.cls_f32 || !a.pos_f32 || !a.lnw || !a.lnb || a.T != 1) return -1;
+    if (!a.x_f32 || !a.cls_f32 || !a.pos_f32 || !a.lnw || !a.lnb) return -1;
     hipLaunchKernelGGL((patch_embed_kernel<8, 0>), dim3(grid), dim3(PE_NW * 64), lds, st, a);
   } else {
     if (!a.x_bf || !a.cls_bf || !a.pos_bf || !a.bias) return -1;

@@ -95,7 +95,7 @@ inline int prefill_plan(const PrefillGeometry& g, const PrefillKnobs& k, Prefill
   p.M = p.off[nb];
   if (uniform && nb * ((g.lens[0] + 63) / 64) > g.page_id_cap) uniform = false;   // the [nb][P0] table is filled from ONE by-value list of page ids
   p.batched_table = nb > 1 && uniform;
-  // fused RMSNorm (see iv2_encode): the widths the staged epilogue takes
+  // fused RMSNorm (see vision_norm_fused_ok, gvl_vision_plan.h): the widths the staged epilogue takes
   p.nf = k.norm_fused && g.hidden % 64 == 0 && g.qkv_width % 16 == 0 && g.gate_up_width % 16 == 0 && g.fused_weights;
 
   // ---- the steps of one layer --------------------------------------------------------------------------------------------------------------------------------

@@ -3,15 +3,19 @@
 design: only the plan can say which kernel a case exercised.
 
 The helpers that build a geometry the way a caller in the library does:
-  op_attention   gvl_op_attention (gvl_ops.hip): gvl_debug_set vision_in_place / attn_ring choose the operand mode and the ring depth
+  op_attention   gvl_op_attention (gvl_ops.hip): gvl_debug_set vision_in_place / attn_ring choose the operand mode (vision_operand_path, asked through tests/vision_plan.py)
+                 and the ring depth
   op_iv2_attention   gvl_op_iv2_attention (gvl_ops.hip): the descriptor's form / pipe / pipe_rows choose everything, no gvl_debug_set
-  iv2_block      the attention launch of an InternVideo2 block (iv2_encode, gvl_vision.hip): vision_in_place, attn_pipe, attn_pipe_rows
+  iv2_block      the attention launch of an InternVideo2 block (gvl_vision.hip): vision_in_place chooses the operand path (vision_operand_path), then attn_pipe, attn_pipe_rows
   decode_step    the decode-attention launch of decode_step (gvl_llm.hip): decode_attn_shape on the sequences' positions, then decode_attn_plan"""
 import functools
 import os
 import subprocess
 import tempfile
 from collections import namedtuple
+
+import vision_plan
+from vision_plan import pad_head  # noqa: F401  (callers use attn_plan.pad_head)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "grounded-video-llm_amd", "csrc")
@@ -97,21 +101,16 @@ def plans(lines):
     return out
 
 
-def pad_head(dr):
-    return 64 if dr <= 64 else 96 if dr <= 96 else 128
-
-
 @functools.lru_cache(maxsize=None)
 def op_attention(B, S, H, KV, Dr, causal, vision_in_place=1, attn_ring=0):
     """the launches of gvl_op_attention(B, S, H, KV, Dr, causal) under gvl_debug_set vision_in_place / attn_ring: q, k, v are the column blocks of one fused
     [B * S][(H + 2 KV) * Dr] tensor"""
     D, ld = pad_head(Dr), (H + 2 * KV) * Dr
-    v_rows = bool(vision_in_place) and not causal and D != 128
-    qk_rows = vision_in_place == 1 and v_rows and D == Dr == 64
+    path = vision_plan.operand_path(vision_in_place, D, Dr, bool(causal), vision_plan.CLIP)
     kw = dict(B=B, H=H, KV=KV, S=S, D=D, Dout=Dr, causal=int(causal), ring=attn_ring)
-    if v_rows:
+    if not path.vt_pages:
         kw.update(present=VROWS, v_ld=ld)
-    if qk_rows:
+    if path.qk_rows:
         kw.update(present=VROWS | QROWS | KROWS, q_ld=ld, k_ld=ld)
     p = plans([prefill_line(**kw)])[0]
     assert p is not None, f"gvl_op_attention {kw}: refused"
@@ -136,13 +135,12 @@ def op_iv2_attention(B, S, H, Dr, form, pipe=0, pipe_rows=0, ld=0):
 def iv2_block(n, S, H, Dr, vision_in_place=1, attn_pipe=1, attn_pipe_rows=0):
     """the attention launches of one InternVideo2 block for n segments of S tokens, H heads of Dr, under gvl_debug_set vision_in_place / attn_pipe / attn_pipe_rows"""
     D, C = pad_head(Dr), H * Dr
-    vt_pages = not vision_in_place or D == 128
-    q_in_place = vision_in_place == 1 and D == 96 and Dr == 88
-    kw = dict(B=n, H=H, KV=H, S=S, D=D, Dout=Dr, ones_row=int(D > Dr))
-    if not vt_pages:
+    path = vision_plan.operand_path(vision_in_place, D, Dr, False, vision_plan.IV2)
+    kw = dict(B=n, H=H, KV=H, S=S, D=D, Dout=Dr, ones_row=path.attn_ones_row)
+    if not path.vt_pages:
         kw.update(present=VROWS, v_ld=3 * C)
-    if q_in_place:
-        kw.update(present=kw.get("present", 0) | QROWS | Q_RS | Q_NW, q_ld=3 * C, k_ones=1, pipe=attn_pipe, pipe_rows=attn_pipe_rows)
+    if path.q_on_load:
+        kw.update(present=kw.get("present", 0) | QROWS | Q_RS | Q_NW, q_ld=3 * C, k_ones=path.attn_k_ones, pipe=attn_pipe, pipe_rows=attn_pipe_rows)
     p = plans([prefill_line(**kw)])[0]
     assert p is not None, f"iv2 block attention {kw}: refused"
     return tuple(p)
